@@ -8,19 +8,28 @@ One "step" = one commit of a BLOCK-sample batch that is already resident in HBM:
 written), 32 stage-2 FIRs with their discriminators fused in, history carry-over.  value = input IQ Msamples/s
 over all ranks.  N > 1: one independent 20 Msps front-end per GPU (config_denver_massive_p25-style, BASELINE
 configs[3]); weak scaling; no data-path collective -- the only RCCL traffic is the all-gather of detected-peak
-lists (ncclAllGather through librcf's C ABI) after the timed region, reported as peaks_allgather_us.
+lists (ncclAllGather through librcf's C ABI) after the timed region, reported as peaks_allgather_us (--full).
 
-OUTPUT.  The LAST (and only) stdout line is a compact JSON object of <= 7 600 bytes (benchlib/compact.py): the
+PLAIN RUN AND --full.  A plain run (no --full) sets up, runs the fixed pre-warm and the W warm-up steps, times the K
+steps, writes their outputs if --dump-outputs is given and prints one JSON line: the contract keys (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...) and the roofline the timed region's own events give.  Nothing
+else runs.  --full runs everything below as well (the legs, the CPU baseline, the roofline's passes of their own).
+
+OUTPUT of --full.  The LAST (and only) stdout line is a compact JSON object of <= 7 600 bytes (benchlib/compact.py): the
 contract keys, `roofline`, `cpu_baseline` and one-number summaries of every leg.  The full record -- every point of
-every leg -- is written to bench_full.json (cwd, and gpurun_out/ which is what comes back from a GPU box); the
-compact line names it in `full_record`.
+every leg -- is written to bench_full.json (where: benchlib/compact.py write_full); the compact line names it in
+`full_record`.
+
+--dump-outputs DIR (benchlib/outputs.py): after the timed steps, what the last of them computed -- every filterbank bin
+at a fixed, seeded sample of frames and the stage-2 channels' IQ and FM outputs -- as DIR/<name>.npy (float32, ~34 MB).
+The pre-warm is a fixed number of commits (--prewarm-steps), so the same arguments give the same inputs every run.
 
 No PyTorch: device work goes through librcf's C ABI (ctypes), ranks meet over rcf.multigpu.HostGroup (TCP next
 to MASTER_PORT), the barrier on both sides of the timed region is `rcf_allreduce_max` (stream sync + one
 ncclAllReduce), which also yields the max-over-ranks time.  The process pins itself to the CPUs of its GPU's NUMA
 node before the HIP runtime starts (N = 1 too).
 
-The legs (benchlib/, one module each; all but the first outside the timed region, rank 0 at N = 1):
+The legs of --full (benchlib/, one module each; all but the first outside the timed region, rank 0 at N = 1):
   headline.py   the timed configuration, its roofline (HIP events attached to the filterbank's dispatch), the
                 filterbank alone, `sustained` (>= 2 s of commits, launch time per window of 100, shader clock)
   traffic.py    roofline.traffic: two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE) of a short headline run
@@ -41,7 +50,7 @@ The legs (benchlib/, one module each; all but the first outside the timed region
 --config cfg5 = BASELINE configs[4]'s per-GPU shape instead (25 Msps slice, 512-bin bank, N = 2^20 / 1000 / 100 scan
 on the slice, <= 1024 peaks per rank into the all-gather); the default (cfg4) is configs[1] / configs[3].
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  For N > 1 either a launcher starts the ranks
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].  For N > 1 either a launcher starts the ranks
         (python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...: RANK / LOCAL_RANK /
         WORLD_SIZE / MASTER_* come from the environment), or -- when WORLD_SIZE is not set -- bench.py starts its own
         N rank processes (one per GPU, the way the reference starts one channelizer process per source:
@@ -91,9 +100,9 @@ def parse_args(argv=None):
     ap.add_argument("--alone-launches", type=int, default=100, help="timed launches of the filterbank-alone pass")
     ap.add_argument("--time-every", type=int, default=4,
                     help="HIP events around every n-th filterbank launch of the timed region (1 = all of them)")
-    ap.add_argument("--prewarm-seconds", type=float, default=0.5,
-                    help="untimed commits before the warm-up steps: the metric is SUSTAINED throughput, and the chip needs "
-                         "~100 launches (15 ms) after idling before the filterbank launch settles; 0 = none")
+    ap.add_argument("--prewarm-steps", type=int, default=4096,
+                    help="untimed commits before the warm-up steps (~0.5 s): the metric is SUSTAINED throughput, and the chip "
+                         "needs ~100 launches (15 ms) after idling before the filterbank launch settles; 0 = none")
     ap.add_argument("--sweep-max", type=int, default=196608, help="largest direct-bank channel count to open")
     ap.add_argument("--rt-seconds", type=float, default=10.0, help="seconds of the paced leg's confirmation run (0 = skip the leg)")
     ap.add_argument("--rt-block-ms", type=float, default=20.0, help="block length of the paced real-time leg")
@@ -106,8 +115,16 @@ def parse_args(argv=None):
     ap.add_argument("--rt-shapes", default="pfb256,grid1600,grid1600fm", help="shapes of the real-time leg")
     ap.add_argument("--rt-burst", action="store_true",
                     help="real-time leg: every front-end's block completes at the same instant (default: spread over the period)")
-    ap.add_argument("--full-on-stdout", action="store_true", help="print the FULL record as the one line (pre-round-6 behaviour)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full-on-stdout", action="store_true",
+                    help="print the FULL record as the one line (pre-round-6 behaviour); implies --full")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg, the CPU baseline and the roofline's own passes as well, and write the full record "
+                         "(default: the timed headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (benchlib/outputs.py)")
+    args = ap.parse_args(argv)
+    args.full = args.full or args.full_on_stdout
+    return args
 
 
 def leg(fn, *a, **k):
@@ -159,6 +176,11 @@ def main():
 
     out, ctx = headline.run(args, R, native, multigpu, synth, numa)
     if R.rank != 0:
+        return
+    if not args.full:
+        line = json.dumps(out)
+        assert len(line) + 1 <= compact.LIMIT, "the plain line grew to %d bytes" % len(line)
+        print(line, flush=True)
         return
     if R.n_gpus == 1 and not args.no_extras and not ctx["cfg5"]:
         untimed_legs(args, out, ctx, native, synth, R.local_rank)

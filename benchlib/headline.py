@@ -103,6 +103,109 @@ def rt_k_per_gpu(args, world):
     return k, quota
 
 
+def _alg_bytes(fe, chans, nb, B):
+    """-> (filterbank bytes, stage-2 rider bytes, whether the rider rides) of one filterbank launch"""
+    alg_bytes_pfb = 16.0 * B                          # 8 B read + 8 B written per input sample (critically sampled)
+    # the stage-2 work of the previous block rides in the filterbank's launch (rcf_set_stage2_lag: 256-bin kernel only):
+    # the launch then also moves that work's algorithmic bytes -- SURVEY 8(d): per active bin 8 B read per frame of its
+    # stream, 8 B (IQ) + 4 B (fused discriminator) written per output at a third of the frame rate
+    s2_rides = bool(chans) and nb == 256 and os.environ.get("RCF_S2_LAG", "1") != "0" and hasattr(fe, "set_stage2_lag")
+    alg_bytes_s2 = len(chans) * (8.0 * (B // nb) + 12.0 * ((B // nb) // 3)) if s2_rides else 0.0
+    return alg_bytes_pfb, alg_bytes_s2, s2_rides
+
+
+def _tracked_traffic(cfg5, B):
+    """-> (HBM bytes per launch, where from) out of the tracked profiles/ file of this configuration, or (None, None)"""
+    traffic, traffic_src = None, None
+    tname = "pfb512_traffic.json" if cfg5 else "pfb_traffic.json"
+    tpath = os.path.join(ROOT, "profiles", tname)
+    if os.path.exists(tpath):
+        try:
+            with open(tpath) as f:
+                tj = json.load(f)
+            if tj.get("block") == B:
+                traffic = tj.get("hbm_bytes_per_launch")
+                traffic_src = "profiles/%s: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of %s (not measured " \
+                              "in this run)" % (tname, tj.get("measured", "an earlier run of this configuration"))
+        except Exception:
+            traffic = None
+    return traffic, traffic_src
+
+
+def _workload(cfg5):
+    """-> (the line's config.workload, the roofline's kernel)"""
+    if cfg5:
+        return ("BASELINE configs[4], per-GPU shape: 512-bin critically-sampled PFB (6981-tap prototype) over "
+                "one 25 Msps cf32 spectrum slice per GPU (x8 = 4096 channels at 200 Msps), N=2^20 scan of the "
+                "slice + <=1024 peaks per rank into the all-gather outside the timed region",
+                "pfb_kernel_2b<256, 14, 3, false> (512 bins: 256-thread workgroups, two branches per thread)")
+    return ("BASELINE configs[1]: 256-bin critically-sampled PFB (3491-tap prototype) over one "
+            "20 Msps cf32 stream per GPU, stage-2 xlating FIR /3 + FM discriminator on 32 active bins",
+            "pfb_kernel_os<256,1,14,4,false>")
+
+
+def _plain_record(args, R, fe, barrier_max, B, nb, fs, cfg5, chans, elapsed, per_rank_ms, pfb_ms, pfb_n, time_every,
+                  dumped):
+    """the record of a plain run (no --full): the timed region's figures and nothing that takes a run of its own -- the
+    roofline is the one the timed region's own events give, its traffic the tracked profiles/ file's"""
+    n_gpus, world = R.n_gpus, R.world
+    avg_ms = pfb_ms / max(pfb_n, 1)
+    avg_ms_max = barrier_max(avg_ms) if R.group is not None else avg_ms
+    alg_bytes_pfb, alg_bytes_s2, s2_rides = _alg_bytes(fe, chans, nb, B)
+    fe.close()
+    if R.group is not None:
+        R.group.close()
+    if R.rank != 0:
+        return None
+    alg_bytes = alg_bytes_pfb + alg_bytes_s2
+    value = float(B) * args.steps * n_gpus / elapsed / 1e6
+    achieved = alg_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+    traffic, traffic_src = _tracked_traffic(cfg5, B)
+    workload, kname = _workload(cfg5)
+    out = {
+        "metric": "input IQ Msamples/s + concurrent 12.5 kHz FM channels sustained",
+        "value": value,
+        "unit": "Msamples/s",
+        "n_gpus": n_gpus,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "prewarm": {"untimed_steps": args.prewarm_steps},
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "ms_per_step_by_rank": per_rank_ms,
+        "ranks_started_by": ("bench.py itself (one process per GPU)" if os.environ.get("RCF_BENCH_SPAWNED")
+                             else "the launcher's environment (RANK / WORLD_SIZE)") if world > 1 else "single process",
+        "rccl_ranks": R.rccl_ranks if world > 1 else 1,
+        "transport": ("rccl" if R.use_rccl else "host-tcp") if world > 1 else "none (one rank)",
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": workload,
+            "samp_rate": fs, "pfb_bins": nb, "fm_channels_per_gpu": 0 if cfg5 else N_ACTIVE,
+            "block_samples": B, "parallelism": "1 front-end per GPU x%d" % n_gpus,
+        },
+        "roofline": {
+            "bound": "hbm", "kernel": kname,
+            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS,
+            "traffic": traffic, "traffic_source": traffic_src,
+            "algorithmic_bytes_per_launch": alg_bytes,
+            "algorithmic_bytes_filterbank": alg_bytes_pfb, "algorithmic_bytes_stage2_rider": alg_bytes_s2,
+            "stage2_rides_in_this_launch": s2_rides,
+            "avg_launch_ms": avg_ms, "launches": pfb_n, "timed_every": time_every,
+            "avg_launch_ms_slowest_rank": avg_ms_max,
+            "frac_slowest_rank": alg_bytes / (avg_ms_max * 1e-3) / 1e9 / HBM_PEAK_GBS if avg_ms_max > 0 else 0.0,
+        },
+        "cpu_baseline": None,
+        "legs": "not run: a plain run times the headline alone (--full runs every leg and writes the full record)",
+    }
+    if dumped is not None:
+        out["outputs_dumped"] = {"dir": args.dump_outputs, "arrays": dumped}
+    return out
+
+
 def run(args, R, native, multigpu, synth, numa):
     """-> (out, ctx): rank 0's record of the timed configuration (None on the other ranks) and what the untimed legs need"""
     rank, world, n_gpus, local_rank = R.rank, R.world, R.n_gpus, R.local_rank
@@ -144,12 +247,10 @@ def run(args, R, native, multigpu, synth, numa):
         fe.commit(B)
     fe.sync()
 
-    tp = time.perf_counter()
-    n_prewarm = 0
-    while time.perf_counter() - tp < args.prewarm_seconds:
-        for _ in range(32):
-            fe.commit(B)
-        n_prewarm += 32
+    # a fixed number of them: the commits before the last timed step, and with them what that step computes
+    # (--dump-outputs), depend on the arguments alone
+    for _ in range(args.prewarm_steps):
+        fe.commit(B)
     # HIP events only on the kernel the roofline reports, and only on every 4th launch of it.  The two events are
     # ATTACHED to the filterbank's dispatch (hipExtLaunchKernelGGL), not recorded around it: one barrier packet less
     # inside the measured interval.  A timed launch costs the step ~4 us, hence every 4th.  Switched on BEFORE the
@@ -171,6 +272,13 @@ def run(args, R, native, multigpu, synth, numa):
         [struct.unpack("<d", p)[0] / args.steps * 1e3 for p in group.all_gather(struct.pack("<d", t1 - t0))]
 
     pfb_ms, pfb_n = fe.timing_read(native.T_PFB)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        from .outputs import dump_outputs
+        dumped = dump_outputs(fe, nb, frames, out_cap, chans, args.dump_outputs)
+    if not args.full:
+        return _plain_record(args, R, fe, barrier_max, B, nb, fs, cfg5, chans, elapsed, per_rank_ms, pfb_ms, pfb_n,
+                             time_every, dumped), {"cfg5": cfg5}
     fe.timing_stride(1)
     # ... and a second pass, NOT timed by the wall clock, in which EVERY launch of the same number of steps (at least
     # 20) carries its two events: the large-sample launch time beside the every-4th one of the timed region
@@ -198,12 +306,7 @@ def run(args, R, native, multigpu, synth, numa):
     if chans:
         assert fe.chan_produced(chans[0]) > 0        # the FM channels really produced output
 
-    alg_bytes_pfb = 16.0 * B                          # 8 B read + 8 B written per input sample (critically sampled)
-    # the stage-2 work of the previous block rides in the filterbank's launch (rcf_set_stage2_lag: 256-bin kernel only):
-    # the launch then also moves that work's algorithmic bytes -- SURVEY 8(d): per active bin 8 B read per frame of its
-    # stream, 8 B (IQ) + 4 B (fused discriminator) written per output at a third of the frame rate
-    s2_rides = bool(chans) and nb == 256 and os.environ.get("RCF_S2_LAG", "1") != "0" and hasattr(fe, "set_stage2_lag")
-    alg_bytes_s2 = len(chans) * (8.0 * (B // nb) + 12.0 * ((B // nb) // 3)) if s2_rides else 0.0
+    alg_bytes_pfb, alg_bytes_s2, s2_rides = _alg_bytes(fe, chans, nb, B)
     alg_bytes = alg_bytes_pfb + alg_bytes_s2
     # ... and the filterbank kernel ALONE (the lag switched off for a pass of its own: every launch timed)
     pfb_alone_ms = pfb_alone_n = None
@@ -309,39 +412,19 @@ def run(args, R, native, multigpu, synth, numa):
         value = total_samples / elapsed / 1e6
         avg_pfb_s = (pfb_ms / max(pfb_n, 1)) * 1e-3
         achieved = alg_bytes / avg_pfb_s / 1e9 if avg_pfb_s > 0 else 0.0
-        traffic, traffic_src = None, None
         live = None
         if n_gpus == 1 and not args.no_live_traffic and B == 1 << 25:
             fe.sync()
             live = measure_traffic_live(cfg5, B, "pfb_kernel_2b<256" if cfg5 else "pfb_kernel_os<256")
-        tname = "pfb512_traffic.json" if cfg5 else "pfb_traffic.json"
-        tpath = os.path.join(ROOT, "profiles", tname)
-        if os.path.exists(tpath):
-            try:
-                with open(tpath) as f:
-                    tj = json.load(f)
-                if tj.get("block") == B:
-                    traffic = tj.get("hbm_bytes_per_launch")
-                    traffic_src = "profiles/%s: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of %s (not measured " \
-                                  "in this run)" % (tname, tj.get("measured", "an earlier run of this configuration"))
-            except Exception:
-                traffic = None
+        traffic, traffic_src = _tracked_traffic(cfg5, B)
         traffic_file = traffic
         if live is not None:
             traffic = live["hbm_bytes_per_launch"]
             traffic_src = ("measured in this run on this box: two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE; "
-                           "--kernel-trace only) over `bench.py --steps 5 --no-extras --no-cpu-baseline --no-sustained`, "
+                           "--kernel-trace only) over `bench.py --full --steps 5 --no-extras --no-cpu-baseline --no-sustained`, "
                            "%d dispatches of the kernel averaged; KiB x 1024, FETCH x 2 (gfx950, MI355X_MICROARCH.md)"
                            % live["dispatches_averaged"])
-        if cfg5:
-            workload = ("BASELINE configs[4], per-GPU shape: 512-bin critically-sampled PFB (6981-tap prototype) over "
-                        "one 25 Msps cf32 spectrum slice per GPU (x8 = 4096 channels at 200 Msps), N=2^20 scan of the "
-                        "slice + <=1024 peaks per rank into the all-gather outside the timed region")
-            kname = "pfb_kernel_2b<256, 14, 3, false> (512 bins: 256-thread workgroups, two branches per thread)"
-        else:
-            workload = ("BASELINE configs[1]: 256-bin critically-sampled PFB (3491-tap prototype) over one "
-                        "20 Msps cf32 stream per GPU, stage-2 xlating FIR /3 + FM discriminator on 32 active bins")
-            kname = "pfb_kernel_os<256,1,14,4,false>"
+        workload, kname = _workload(cfg5)
         frac_of = lambda ms: alg_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS if ms and ms > 0 else None
         out = {
             "metric": "input IQ Msamples/s + concurrent 12.5 kHz FM channels sustained",
@@ -350,7 +433,7 @@ def run(args, R, native, multigpu, synth, numa):
             "n_gpus": n_gpus,
             "steps": args.steps,
             "warmup": args.warmup,
-            "prewarm": {"seconds": args.prewarm_seconds, "untimed_steps": n_prewarm,
+            "prewarm": {"untimed_steps": args.prewarm_steps,
                         "why": "steady state before the W warm-up steps (metric: sustained); see `sustained`"},
             "ms_per_step": elapsed / args.steps * 1e3,
             "ms_per_step_by_rank": per_rank_ms,
@@ -448,4 +531,6 @@ def run(args, R, native, multigpu, synth, numa):
     fe.close()
     if group is not None:
         group.close()
+    if out is not None and dumped is not None:
+        out["outputs_dumped"] = {"dir": args.dump_outputs, "arrays": dumped}
     return out, {"tile": tile, "meta": meta, "fm_check": fm_check, "fs": fs, "cfg5": cfg5}

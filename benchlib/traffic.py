@@ -21,8 +21,8 @@ def measure_traffic_live(cfg5, block, kernel_substr, timeout_s=150):
     if any(k.startswith("ROCPROF") for k in os.environ) or "rocprofiler" in os.environ.get("LD_PRELOAD", ""):
         return None                                          # this run is itself being profiled: no profiler inside a profiler
     out = {}
-    child = [sys.executable, BENCH_PY, "--steps", "5", "--warmup", "1", "--block", str(block), "--no-extras",
-             "--no-cpu-baseline", "--no-sustained", "--no-live-traffic", "--prewarm-seconds", "0.2"]
+    child = [sys.executable, BENCH_PY, "--full", "--steps", "5", "--warmup", "1", "--block", str(block), "--no-extras",
+             "--no-cpu-baseline", "--no-sustained", "--no-live-traffic", "--prewarm-steps", "1750"]
     if cfg5:
         child += ["--config", "cfg5"]
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):

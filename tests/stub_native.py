@@ -65,8 +65,19 @@ class Frontend:
     def chan_produced(self, c):
         return 1
 
-    def chan_read_fm(self, c, gain, max_samples=0):
-        return np.zeros(8, dtype=np.float32)
+    def chan_read_fm(self, c, gain, max_samples=8):
+        return np.zeros(min(max_samples, self.samples_in // self.nb // 3), dtype=np.float32)
+
+    # what --dump-outputs reads: the newest samples of every bin / channel (a ramp, so that a slice is recognisable)
+    def pfb_read_bin(self, b, max_samples=1 << 20):
+        n = min(max_samples, self.samples_in // self.nb)
+        return (np.arange(self.samples_in // self.nb - n, self.samples_in // self.nb) + 1j * b).astype(np.complex64)
+
+    def chan_info(self, c):
+        return dict(decim=3, ntaps=33, out_rate=0.0, offset_hz=0.0)
+
+    def chan_read_iq(self, c, max_samples=1 << 20):
+        return np.full(min(max_samples, self.samples_in // self.nb // 3), c, dtype=np.complex64)
 
     def scan_start(self, n, f, l):
         pass

@@ -9,7 +9,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLAGS = ["--steps", "6", "--warmup", "1", "--block", str(1 << 16), "--prewarm-seconds", "0", "--no-extras",
+FLAGS = ["--full", "--steps", "6", "--warmup", "1", "--block", str(1 << 16), "--prewarm-steps", "0", "--no-extras",
          "--no-cpu-baseline", "--no-sustained"]
 
 
@@ -129,7 +129,7 @@ def test_eight_rank_line_carries_every_rank_and_a_real_time_point_per_gpu(tmp_pa
     the slowest rank's), each rank's NUMA pinning, `--config cfg5` with the scan time over ranks, the gather time and the
     gathered count checked against the sum of the ranks' peak counts, and one paced real-time point PER GPU so that the
     line answers "channels sustained" at N = 8 too -- here on the stub, one rank told to miss its deadlines"""
-    flags = ["--steps", "6", "--warmup", "1", "--block", str(1 << 20), "--prewarm-seconds", "0", "--no-cpu-baseline",
+    flags = ["--full", "--steps", "6", "--warmup", "1", "--block", str(1 << 20), "--prewarm-steps", "0", "--no-cpu-baseline",
              "--sustained-seconds", "0.05", "--config", "cfg5", "--rt-seconds", "0.5", "--rt-k-per-gpu", "6", "--rt-pumps", "2"]
     full_path = str(tmp_path / "full.json")
     env = dict(os.environ, RCF_BENCH_NATIVE="stub_native", RCF_BENCH_TRANSPORT="rccl", STUB_RCCL="1", STUB_DEVICES="8", STUB_RT_MISS="5",
@@ -171,7 +171,7 @@ def test_numa_pinning_reads_sysfs_and_survives_its_absence(monkeypatch):
         os.sched_setaffinity(0, before)
 
 
-REALTIME_FLAGS = ["--steps", "6", "--warmup", "1", "--block", str(1 << 20), "--prewarm-seconds", "0", "--no-cpu-baseline",
+REALTIME_FLAGS = ["--full", "--steps", "6", "--warmup", "1", "--block", str(1 << 20), "--prewarm-steps", "0", "--no-cpu-baseline",
                   "--sustained-seconds", "0.05", "--rt-seconds", "0.5", "--rt-k-per-gpu", "6", "--rt-pumps", "2"]
 
 
@@ -276,3 +276,58 @@ def test_compact_guard_drops_summaries_before_it_breaks_the_limit():
     assert len(line) + 1 <= compact.LIMIT
     d = json.loads(line)
     assert d["roofline"]["frac"] == 0.5 and d["realtime"]["pfb256"]["K_max"] == 1 and "points" not in d["realtime"]["pfb256"]
+
+
+PLAIN_KEYS = ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus", "config",
+              "roofline")
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_a_plain_run_times_the_headline_alone(world, tmp_path):
+    """no --full: set-up, warm-up, the K timed steps and the line -- no leg, no CPU baseline, no full record"""
+    r = _run_flags(world, ["--steps", "7", "--warmup", "2", "--block", str(1 << 16), "--prewarm-steps", "3"],
+                   {"RCF_BENCH_TRANSPORT": "host", "RCF_BENCH_FULL": str(tmp_path / "full.json")}, timeout=180)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert len([l for l in r.stdout.splitlines() if l.strip()]) == 1
+    d = json.loads(r.stdout)
+    for k in PLAIN_KEYS:
+        assert k in d, k
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["prewarm"]["untimed_steps"] == 3 and d["n_gpus"] == world
+    assert d["metric"] == "input IQ Msamples/s + concurrent 12.5 kHz FM channels sustained" and d["unit"] == "Msamples/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - world * 7 * (1 << 16) / (d["ms_per_step"] * 7e-3) / 1e6) / d["value"] < 1e-6
+    assert d["roofline"]["launches"] == 7 and d["cpu_baseline"] is None
+    for k in ("sustained", "channels", "realtime", "scan", "kernel_ms_per_step", "peaks_allgather", "full_record"):
+        assert k not in d, k
+    assert not os.path.exists(tmp_path / "full.json")
+
+
+def test_dump_outputs_writes_the_last_steps_arrays(tmp_path):
+    out = tmp_path / "outputs"
+    r = _run_flags(1, ["--steps", "4", "--warmup", "1", "--block", str(1 << 16), "--prewarm-steps", "2",
+                       "--dump-outputs", str(out)], {}, timeout=180)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads(r.stdout)
+    import numpy as np
+    frames = (1 << 16) // 256
+    arrays = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+    assert set(arrays) == {"pfb_bins", "pfb_bins_frames", "chan_iq", "chan_fm"} == set(d["outputs_dumped"]["arrays"])
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays["pfb_bins"].shape == (256, frames, 2) and arrays["chan_fm"].shape == (32, frames // 3)
+    # the stub's bins are a ramp over the stream's frames: the dump holds the LAST step's -- before it the two commits that
+    # make the batch resident, the 2 pre-warm, the 1 warm-up and 3 timed commits
+    first = (2 + 2 + 1 + 3) * frames
+    assert arrays["pfb_bins"][7, 0, 0] == first + arrays["pfb_bins_frames"][0] and arrays["pfb_bins"][7, 0, 1] == 7.0
+
+
+def test_a_full_sample_of_a_full_size_block_stays_within_64_mb():
+    sys.path.insert(0, ROOT)
+    from benchlib import outputs
+    for nb, n_chan in ((256, 32), (512, 0)):            # the default configuration and --config cfg5
+        frames = (1 << 25) // nb
+        idx = outputs.frame_sample(frames)
+        assert len(idx) == outputs.FRAME_SAMPLE and len(set(idx.tolist())) == len(idx)
+        assert (idx == outputs.frame_sample(frames)).all()
+        total = nb * len(idx) * 8 + len(idx) * 8 + n_chan * (frames // 3) * 12
+        assert total <= 64 << 20, (nb, total)
