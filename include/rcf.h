@@ -168,7 +168,7 @@ int rcf_timing_read(rcf_t *h, int what, double *total_ms, int64_t *launches, int
  * and every channel's sub_source (rc_frontend/channel.py:29).  Pageable or large blocks are copied on a second stream
  * (the copy of block n + 1 overlaps the kernels of block n); a block of <= 4 MiB in pinned memory (rcf_host_alloc) is
  * fetched by a kernel on the compute stream straight out of host memory -- no second stream, no cross-stream waits:
- * what a real-time block wants (RCF_RAW_DIRECT moves the threshold).  Returns once the caller's buffer has been read. */
+ * what a real-time block wants.  Returns once the caller's buffer has been read. */
 int rcf_push_iq(rcf_t *h, const float *iq_interleaved, size_t n_samples);
 /* Zero-copy ingest: *dev_ptr is where the producer (SDR DMA, generator kernel, hipMemcpy) must put
  * the next block (device memory, room for *max_samples); rcf_commit(n) then processes the n samples
@@ -186,7 +186,7 @@ int rcf_commit(rcf_t *h, size_t n_samples);
  * scale 1/128; sc16 (USRP wire, bladeRF Q11): RCF_FMT_S16, offset 0, scale 1/32768 or 1/2048.
  * A block of up to 4 MiB in pinned memory (rcf_host_alloc) is converted straight out of host memory -- one launch, no
  * staging copy: the shape of a real-time SDR block; larger ones go through a staged copy that overlaps the previous
- * block's kernels (RCF_RAW_DIRECT=<bytes> moves the threshold, 0 = always staged).  Either way the call returns once
+ * block's kernels.  Either way the call returns once
  * the caller's buffer has been read. */
 #define RCF_FMT_CF32 0   /* float32 I,Q interleaved (rcf_group_push only: rcf_push_iq is the single-front-end form) */
 #define RCF_FMT_U8   1   /* unsigned 8-bit I,Q interleaved */

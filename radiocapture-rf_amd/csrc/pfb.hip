@@ -46,7 +46,6 @@ namespace rcfx {
 namespace {
 
 constexpr int F = 16;   // frames per LDS chunk
-int env_int(const char *name, int dflt);
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -305,12 +304,10 @@ __global__ __launch_bounds__(NB, MINW) void pfb_kernel_os(PfbLaunch p, int n_wg,
     if (p.rider_n8[0] + p.rider_n8[1] && bid < kPfbRiderWgs)
         pfb_copy_rider(p, bid, min(kPfbRiderWgs, (int)gridDim.x - (int)sr.n_wgs), tid, NB);
     int wg;
-    if (n_wg < 0) {
+    if (n_wg < 0)
         wg = bid;                                          // probe: no XCD remap
-    } else {
-        const int b = bid, q = n_wg / 8, r = n_wg % 8, xcd = b % 8;
-        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + b / 8;
-    }
+    else
+        wg = xcd_chunk_first(n_wg, bid) + bid / 8;
     pfb_os_chunk<NB, OS, P, ZH>(p, wg, tid, buf, tw_lds);
 }
 
@@ -352,7 +349,7 @@ __global__ __launch_bounds__(NB, MINW) void pfb_kernel_pp(PfbLaunch p, int n_chu
     const int tid = threadIdx.x;
     const int xcd = blockIdx.x % 8, li = blockIdx.x / 8, step = gridDim.x / 8;
     const int q = n_chunks / 8, r = n_chunks % 8;
-    const int c_lo = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+    const int c_lo = xcd_chunk_first(n_chunks, xcd);
     const int c_hi = c_lo + (xcd < r ? q + 1 : q);
     int c = c_lo + li;
     if (c >= c_hi) return;
@@ -640,8 +637,8 @@ __global__ __launch_bounds__(NH, MINW) void pfb_kernel_2b(PfbLaunch p, int n_wg)
     if (n_wg < 0) {
         wg = blockIdx.x;
     } else {
-        const int b = blockIdx.x, q = n_wg / 8, r = n_wg % 8, xcd = b % 8;
-        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + b / 8;
+        const int b = blockIdx.x;
+        wg = xcd_chunk_first(n_wg, b) + b / 8;
     }
     pfb_2b_chunk<NH, P, ZH>(p, wg, tid, buf, tw_lds);
 }
@@ -660,74 +657,51 @@ __global__ __launch_bounds__(NH, MINW) void pfb_group_kernel_2b(const PfbLaunch 
     pfb_2b_chunk<NH, P, false>(p, wg, threadIdx.x, buf, tw_lds);
 }
 
-int env_int(const char *name, int dflt)
-{
-    const char *e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
+// The form of the kernel is a function of the shape:
+//   * critically sampled banks of >= 512 bins: the two-branch kernel (pfb_kernel_2b), zero history or not;
+//   * oversampled banks of >= 512 bins: the persistent kernel (pfb_kernel_pp; 2 / 1 workgroups per CU at 512 / 1024 bins:
+//     +2 % / +10 %), and the plain kernel's zero-history instantiation while the launch still sees zero history;
+//   * 256 bins and below: the plain kernel (pfb_kernel_os).  Four independent workgroups per CU already overlap their
+//     phases, and the persistent form's extra barrier per chunk cost 8 % (measured, block 2^25); 256 bins as 128-thread
+//     two-branch workgroups, eight per CU, reached 0.56-0.60 of the HBM peak against the plain kernel's 0.63.
+template <int NB, int OS> constexpr bool pfb_is_two_branch() { return OS == 1 && NB >= 512; }
+template <int NB, int OS> constexpr bool pfb_is_persistent() { return OS != 1 && NB >= 512; }
 
-bool pfb_persistent(int NB)
-{
-    static const int pp_env = env_int("RCF_PFB_PP", -1);
-    return pp_env < 0 ? NB >= 512 : pp_env != 0;
-}
-
-// critically sampled banks of >= 512 bins run the two-branch form (RCF_PFB_2B=0: the persistent form instead)
-bool pfb_two_branch(int NB, int OS)
-{
-    // (256 bins as 128-thread two-branch workgroups, eight per CU: 0.56-0.60 against the plain kernel's 0.63 -- not kept)
-    static const int env = env_int("RCF_PFB_2B", 1);
-    return env != 0 && OS == 1 && NB >= 512;
-}
+// the stage-2 rider's batches, a multiple of 8 workgroups each (1 = all riders first).  Fused launch on one box, filterbank
+// alone 101.3 us: 1 batch 114.8, 4: 114.4, 16: 114.3, 64: 112.7 us (all riders LAST: the same as 64) -- the rider costs
+// its ~50 MB of traffic wherever it sits, the trailing launch cost 18 us
+constexpr int kS2RiderBatches = 64;
 
 template <int NB, int OS, int P, int MINW>
 void launch_os(const PfbLaunch &p, hipStream_t s, const S2Rider *sr_in)
 {
     const int n_wg = (p.n_frames + F - 1) / F;
-    S2Rider sr{};
-    if (sr_in) {
-        sr = *sr_in;
-        // batches (RCF_S2_RIDER_BATCHES; 1 = all riders first): batch size and period are multiples of 8.  Fused launch on one box, filterbank alone 101.3 us: 1 batch 114.8, 4: 114.4, 16: 114.3, 64: 112.7 us (all riders LAST: the same as 64) -- the rider costs its ~50 MB of traffic wherever it sits, the trailing launch cost 18 us
-        static const int nb_env = env_int("RCF_S2_RIDER_BATCHES", 64);
-        const int work = sr.n_chans * sr.n_tiles;
-        int nbat = std::max(1, std::min(nb_env, (work + 7) / 8));
-        sr.batch_wgs = ((work + nbat - 1) / nbat + 7) & ~7;
-        sr.n_batches = (work + sr.batch_wgs - 1) / sr.batch_wgs;
-        sr.n_wgs = sr.n_batches * sr.batch_wgs;
-        const int total = n_wg + sr.n_wgs;
-        sr.period = std::max(sr.batch_wgs + 8, (total / sr.n_batches) & ~7);
-        if ((long long)sr.period * (sr.n_batches - 1) + sr.batch_wgs > total) {     // (a tiny launch: everything first)
-            sr.n_batches = 1; sr.batch_wgs = (work + 7) & ~7; sr.n_wgs = sr.batch_wgs; sr.period = n_wg + sr.n_wgs + 8;
-        }
-    }
-    static const int no_remap = env_int("RCF_PFB_NOREMAP", 0);
+    // RCF_PFB_NOREMAP=1: the plain and two-branch kernels without the XCD-aware chunk map (tools/pfb_probe.py).  Kept while
+    // the kernels' n_wg < 0 branch shapes the headline kernel's schedule: without it the same arithmetic runs 0.7 % slower.
+    static const bool no_remap = [] { const char *e = getenv("RCF_PFB_NOREMAP"); return e && atoi(e) != 0; }();
     const int arg = no_remap ? -n_wg : n_wg;
     const size_t lds = ((size_t)F * row_stride<NB>() + NB) * sizeof(cf);
     const bool zh = (p.n_lo - (int64_t)OS * (P - 1)) * (NB / OS) - (NB - 1) < p.start_sample;
-    if constexpr (OS == 1 && NB >= 512) {
-        if (pfb_two_branch(NB, OS)) {
-            constexpr int NH = NB / 2;
-            // waves per SIMD the register budget is for: 3 / 2 workgroups per CU.  The zero-history instantiation (the
-            // first launch after rcf_pfb_open only) masks rows and gets 256 VGPRs instead of spilling
-            constexpr int MW2 = NH == 256 ? 3 : 4;
-            const size_t lds2 = ((size_t)F * row_stride<NH>() + NB) * sizeof(cf);
-            static DynLdsAttr attr_zh, attr;
-            if (zh) {
-                attr_zh.ensure((const void *)pfb_kernel_2b<NH, P, 2, true>, lds2);
-                RCF_PFB_LAUNCH(p, (pfb_kernel_2b<NH, P, 2, true>), dim3(n_wg), dim3(NH), lds2, s, p, arg);
-            } else {
-                attr.ensure((const void *)pfb_kernel_2b<NH, P, MW2, false>, lds2);
-                RCF_PFB_LAUNCH(p, (pfb_kernel_2b<NH, P, MW2, false>), dim3(n_wg), dim3(NH), lds2, s, p, arg);
-            }
-            return;
+    if constexpr (pfb_is_two_branch<NB, OS>()) {
+        constexpr int NH = NB / 2;
+        // waves per SIMD the register budget is for: 3 / 2 workgroups per CU.  The zero-history instantiation (the
+        // first launch after rcf_pfb_open only) masks rows and gets 256 VGPRs instead of spilling
+        constexpr int MW2 = NH == 256 ? 3 : 4;
+        const size_t lds2 = ((size_t)F * row_stride<NH>() + NB) * sizeof(cf);
+        static DynLdsAttr attr_zh, attr;
+        if (zh) {
+            attr_zh.ensure((const void *)pfb_kernel_2b<NH, P, 2, true>, lds2);
+            RCF_PFB_LAUNCH(p, (pfb_kernel_2b<NH, P, 2, true>), dim3(n_wg), dim3(NH), lds2, s, p, arg);
+        } else {
+            attr.ensure((const void *)pfb_kernel_2b<NH, P, MW2, false>, lds2);
+            RCF_PFB_LAUNCH(p, (pfb_kernel_2b<NH, P, MW2, false>), dim3(n_wg), dim3(NH), lds2, s, p, arg);
         }
-    }
-    // 512 / 1024 bins run the persistent form (2 / 1 workgroups per CU: +2 % / +10 %); at 256 bins and below four
-    // independent workgroups per CU already overlap their phases and the persistent form's extra barrier per chunk
-    // costs 8 % (measured, block 2^25).  RCF_PFB_PP=0 / 1 forces it off / on.
-    if (pfb_persistent(NB) && !zh) {
+    } else if (zh) {
+        S2Rider none{};
+        RCF_PFB_LAUNCH(p, (pfb_kernel_os<NB, OS, P, MINW, true>), dim3(n_wg), dim3(NB), lds, s, p, arg, none);
+    } else if constexpr (pfb_is_persistent<NB, OS>()) {
         constexpr int PF = NB >= 1024 ? 8 : 16;
-        const int wg_per_cu = NB <= 256 ? 4 : (NB == 512 ? 2 : 1);
+        constexpr int wg_per_cu = NB == 512 ? 2 : 1;
         static const int cus = [] {
             int d = 0, n = 256;
             (void)hipGetDevice(&d);
@@ -737,12 +711,24 @@ void launch_os(const PfbLaunch &p, hipStream_t s, const S2Rider *sr_in)
         int grid = 8 * (cus / 8) * wg_per_cu;                 // one resident round, the same count on every XCD
         if (grid > ((n_wg + 7) / 8) * 8) grid = ((n_wg + 7) / 8) * 8;
         RCF_PFB_LAUNCH(p, (pfb_kernel_pp<NB, OS, P, MINW, false, PF>), dim3(grid), dim3(NB), lds, s, p, n_wg);
-        return;
-    }
-    if (zh) { S2Rider none{}; RCF_PFB_LAUNCH(p, (pfb_kernel_os<NB, OS, P, MINW, true>), dim3(n_wg), dim3(NB), lds, s, p, arg, none); }
-    else {
+    } else {
+        S2Rider sr{};
         size_t lds_s2 = 0;
-        if (sr.n_wgs > 0) lds_s2 = ((size_t)sr.KB * sr.D + 2 * sr.T + sr.KB + 1) * sizeof(float2) + 264 * sizeof(float);
+        if (sr_in) {
+            sr = *sr_in;
+            // batch size and period are multiples of 8: the chunks keep their XCDs
+            const int work = sr.n_chans * sr.n_tiles;
+            int nbat = std::max(1, std::min(kS2RiderBatches, (work + 7) / 8));
+            sr.batch_wgs = ((work + nbat - 1) / nbat + 7) & ~7;
+            sr.n_batches = (work + sr.batch_wgs - 1) / sr.batch_wgs;
+            sr.n_wgs = sr.n_batches * sr.batch_wgs;
+            const int total = n_wg + sr.n_wgs;
+            sr.period = std::max(sr.batch_wgs + 8, (total / sr.n_batches) & ~7);
+            if ((long long)sr.period * (sr.n_batches - 1) + sr.batch_wgs > total) {     // (a tiny launch: everything first)
+                sr.n_batches = 1; sr.batch_wgs = (work + 7) & ~7; sr.n_wgs = sr.batch_wgs; sr.period = n_wg + sr.n_wgs + 8;
+            }
+            if (sr.n_wgs > 0) lds_s2 = ((size_t)sr.KB * sr.D + 2 * sr.T + sr.KB + 1) * sizeof(float2) + 264 * sizeof(float);
+        }
         RCF_PFB_LAUNCH(p, (pfb_kernel_os<NB, OS, P, MINW, false>), dim3(n_wg + sr.n_wgs), dim3(NB), std::max(lds, lds_s2), s, p, arg, sr);
     }
 }
@@ -752,8 +738,7 @@ void launch_os(const PfbLaunch &p, hipStream_t s, const S2Rider *sr_in)
 template <int NB, int OS, int P, int MINW>
 bool launch_os_group(const PfbLaunch *d_pls, const GroupMap &gm, hipStream_t s)
 {
-    if constexpr (OS == 1 && NB >= 512) {
-        if (!pfb_two_branch(NB, OS)) return false;
+    if constexpr (pfb_is_two_branch<NB, OS>()) {
         constexpr int NH = NB / 2;
         constexpr int MW2 = NH == 256 ? 3 : 4;
         const size_t lds2 = ((size_t)F * row_stride<NH>() + NB) * sizeof(cf);
@@ -761,8 +746,9 @@ bool launch_os_group(const PfbLaunch *d_pls, const GroupMap &gm, hipStream_t s)
         attr.ensure((const void *)pfb_group_kernel_2b<NH, P, MW2>, lds2);
         hipLaunchKernelGGL((pfb_group_kernel_2b<NH, P, MW2>), dim3(gm.total_wg), dim3(NH), lds2, s, d_pls, gm);
         return true;
+    } else if constexpr (pfb_is_persistent<NB, OS>()) {
+        return false;
     } else {
-        if (pfb_persistent(NB)) return false;
         const size_t lds = ((size_t)F * row_stride<NB>() + NB) * sizeof(cf);
         hipLaunchKernelGGL((pfb_group_kernel_os<NB, OS, P, MINW>), dim3(gm.total_wg), dim3(NB), lds, s, d_pls, gm);
         return true;
@@ -842,9 +828,9 @@ int pfb_padded_p(int NB, int D, int P)
 bool pfb_takes_rider(const PfbLaunch &p)
 {
     if (pfb_frame_major(p.NB)) return false;            // pfb5_kernel: measured, +5.7 us on the 1600-bin launch for 4.7 saved
-    // (a launch that still sees zero history runs the plain form whatever the bin count: being wrong about that one
-    // launch costs a late start, nothing else)
-    return pfb_two_branch(p.NB, p.D > 0 ? p.NB / p.D : 1) || !pfb_persistent(p.NB);
+    // every form but the persistent one (oversampled banks of >= 512 bins).  A launch that still sees zero history runs
+    // the plain form whatever the bin count: being wrong about that one launch costs a late start, nothing else
+    return p.NB < 512 || (p.D > 0 ? p.NB / p.D : 1) == 1;
 }
 
 void launch_pfb(const PfbLaunch &p, hipStream_t s, const S2Rider *sr)
@@ -859,7 +845,7 @@ bool pfb_can_carry_s2(const PfbLaunch &p)
 {
     if (p.NB != kSmallThreads || pfb_frame_major(p.NB) || p.D <= 0 || p.n_frames <= 0) return false;
     const int OS = p.NB / p.D;
-    if ((OS != 1 && OS != 2) || round_p(p.P, OS) == 0 || pfb_persistent(p.NB) || pfb_two_branch(p.NB, OS)) return false;
+    if ((OS != 1 && OS != 2) || round_p(p.P, OS) == 0) return false;
     return !pfb_sees_zero_history(p);
 }
 

@@ -167,15 +167,6 @@ __device__ __forceinline__ void pfb5_chunk(const PfbLaunch &p, const int wg, con
     static_assert((size_t)BUF * sizeof(cf) <= 64 * 1280, "at least two workgroups per CU");
     static_assert(R == 20 && F * BPF == kThreads5, "one butterfly per thread and pass");
     static_assert(OS == 1 || OS == 2 || OS == 4, "bin phase factor must be a power of -j");
-    // -DRCF_PFB5_TRACE: two workgroups print the cycle counts of their phases (how the time of this kernel was found:
-    // phase A ~45 % before the window was staged through LDS, phase B ~30 %; hipcc ... -DRCF_PFB5_TRACE -c pfb5.hip, link as another librcf, RCF_LIBRCF=...)
-#ifdef RCF_PFB5_TRACE
-    long long ts[8];
-    ts[0] = clock64();
-#define TS(i) ts[i] = clock64()
-#else
-#define TS(i)
-#endif
     const int fb0 = wg * F;
     if (fb0 >= p.n_frames) return;
     const int nf = min(F, p.n_frames - fb0);
@@ -351,9 +342,7 @@ __device__ __forceinline__ void pfb5_chunk(const PfbLaunch &p, const int wg, con
                 if (tid < 256) buf[pfb5_tab_slot<R, R3>(tid)] = tabpair;
         }
     }
-    TS(1);
     __syncthreads();
-    TS(2);
     // (look-back form: the table pair is requested HERE, a whole second pass ahead of the barrier it is written behind -- at
     // kernel entry two more dependent-address loads per thread set the first pass back, the reason the twiddle seeds are not
     // requested there either)
@@ -423,7 +412,6 @@ __device__ __forceinline__ void pfb5_chunk(const PfbLaunch &p, const int wg, con
                 pos[f * (N2 + N2 / R)] = phase(R3 > 1 ? w[Dft<R3, +1>::reg_of(f)] : w[0], jj + f * N2);
         }
     }
-    TS(3);
     if constexpr (FM == FM_HALO) {
         // the chunk before the span: its last frame, bin tid + 320 bb in zprev[bb], is all that is wanted of it
         __syncthreads();
@@ -470,7 +458,6 @@ __device__ __forceinline__ void pfb5_chunk(const PfbLaunch &p, const int wg, con
             if (tid < 256) buf[pfb5_tab_slot<R, R3>(tid)] = tabpair_lb;      // (spare slots: no pass of the FFT touches them)
     }
     __syncthreads();
-    TS(4);
     if (n_mat > 0) {
         float2 *trow = p.tap_mat + (size_t)fb0 * p.tap_pitch;        // column = slot - tap_first
 #pragma unroll
@@ -488,7 +475,6 @@ __device__ __forceinline__ void pfb5_chunk(const PfbLaunch &p, const int wg, con
         }
     }
 
-    TS(5);
     if constexpr (FM == FM_BOTH || FM == FM_ONLY) {
         // ---- copy-out with the discriminator fused in: frame f of bin k leaves as fm_ring[((n0 + f) & mask) NB + k] =
         // fast_atan2f(bin[n] conj(bin[n - 1]) x inc_k) -- tap_finalize's discriminator-only arithmetic (tapfin.hip: the
@@ -507,13 +493,7 @@ __device__ __forceinline__ void pfb5_chunk(const PfbLaunch &p, const int wg, con
             const float ti = __fsub_rn(__fmul_rn(z.y, prev.x), __fmul_rn(z.x, prev.y));
             const float ur = __fsub_rn(__fmul_rn(tr, inc.x), __fmul_rn(ti, inc.y));
             const float ui = __fadd_rn(__fmul_rn(tr, inc.y), __fmul_rn(ti, inc.x));
-#ifdef RCF_X_NOATAN
-            const float fm = ui + ur;
-#elif defined(RCF_X_NODISC)
-            const float fm = z.x;
-#else
             const float fm = fast_atan2f_gr_lut<decltype(lookup), (RCF_FM_RCP != 0)>(ui, ur, lookup);
-#endif
             // one descriptor per frame row (scalar arithmetic, redone per bin column: a table of F of them is 64
             // SGPRs at 400 bins and went to scratch)
             const int64_t slot = (int64_t)((uint64_t)(n0 + f - p.n_abs0) & p.ring_mask);
@@ -682,14 +662,6 @@ __device__ __forceinline__ void pfb5_chunk(const PfbLaunch &p, const int wg, con
             }
         }
     }
-#ifdef RCF_PFB5_TRACE
-    TS(6);
-    __builtin_amdgcn_s_waitcnt(0);
-    TS(7);
-    if ((wg == 1000 || wg == 3000) && (tid == 0 || tid == 256))
-        printf("wg %d tid %d: A %lld bar1 %lld B %lld bar2 %lld taps %lld copy %lld acks %lld\n", wg, tid, ts[1] - ts[0], ts[2] - ts[1],
-               ts[3] - ts[2], ts[4] - ts[3], ts[5] - ts[4], ts[6] - ts[5], ts[7] - ts[6]);
-#endif
 }
 
 template <int R, int R3, int OS, int P, bool ZH>
@@ -698,8 +670,8 @@ __global__ __launch_bounds__(kThreads5, 3) void pfb5_kernel(PfbLaunch p, int n_w
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     cf *buf = reinterpret_cast<cf *>(smem_raw);
     // neighbouring chunks (they share input rows and complete each other's 128-byte output lines) on one XCD
-    const int b = blockIdx.x, q8 = n_wg / 8, r8 = n_wg % 8, xcd = b % 8;
-    const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + b / 8;
+    const int b = blockIdx.x;
+    const int wg = xcd_chunk_first(n_wg, b) + b / 8;
     pfb5_chunk<R, R3, OS, P, ZH>(p, wg, threadIdx.x, buf);
 }
 
@@ -715,11 +687,7 @@ __device__ __forceinline__ void pfb5_fm_span(const PfbLaunch &p, const int wg, c
     if (c0 >= n_chunks) return;
     cf zprev[NBT];
     const cf tabpair = tid < 256 ? make_float2(p.atan_tab[tid], p.atan_tab[tid + 1]) : make_float2(0.f, 0.f);
-#ifndef RCF_X_NOHALO
     pfb5_chunk<R, R3, OS, P, ZH, FM_HALO>(p, c0 - 1, tid, buf, zprev);
-#else
-    for (int bb = 0; bb < NBT; ++bb) zprev[bb] = make_float2(0.f, 0.f);
-#endif
     for (int c = c0; c < c1; ++c) {
         // Nothing may be carried from chunk to chunk but zprev / tabpair.  Everything a chunk derives from the thread index
         // (twenty 64-bit prototype-row addresses, the LDS addresses of three phases) is loop invariant, and hoisted out of
@@ -744,8 +712,8 @@ __global__ __launch_bounds__(kThreads5, pfb5_fm_waves(R, R3, OS, P)) void pfb5_f
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     cf *buf = reinterpret_cast<cf *>(smem_raw);
-    const int b = blockIdx.x, q8 = n_wg / 8, r8 = n_wg % 8, xcd = b % 8;
-    const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + b / 8;
+    const int b = blockIdx.x;
+    const int wg = xcd_chunk_first(n_wg, b) + b / 8;
     pfb5_fm_span<R, R3, OS, P, ZH, FM>(p, wg, threadIdx.x, buf);
 }
 
@@ -761,8 +729,8 @@ __global__ __launch_bounds__(kThreads5, pfb5_fm_waves(R, R3, OS, P)) void pfb5_f
     cf *buf = reinterpret_cast<cf *>(smem_raw);
     constexpr int NB = R * R * R3;
     const int tid = threadIdx.x;
-    const int b = blockIdx.x, q8 = n_wg / 8, r8 = n_wg % 8, xcd = b % 8;
-    const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + b / 8;
+    const int b = blockIdx.x, xcd = b % 8;
+    const int wg = xcd_chunk_first(n_wg, b) + b / 8;
     const bool own_halo = b / 8 == 0;
     const cf tabpair = make_float2(0.f, 0.f);              // (requested inside the chunk: pfb5_chunk, LB)
     unsigned long long *halo_row = p.fm_edge + (size_t)(p.fm_slots + xcd) * NB;

@@ -192,8 +192,7 @@ int rcf_pfb_fm_enable(rcf_t *h, int mode, int gr_phase)
             RCF_HIP(hipMalloc(&p.d_fm_err, sizeof(int)));
             RCF_HIP(hipMemsetAsync(p.d_fm_flag, 0, sizeof(unsigned long long) * (size_t)p.fm_slots * 8, h->stream));
             RCF_HIP(hipMemsetAsync(p.d_fm_err, 0, sizeof(int), h->stream));
-            static const bool want_local = [] { const char *e = getenv("RCF_PFB5_FM_LOCAL"); return !e || atoi(e) != 0; }();
-            p.fm_local = want_local && pfb5_xcd_map_ok(h->device, h->stream) ? 1 : 0;
+            p.fm_local = pfb5_xcd_map_ok(h->device, h->stream) ? 1 : 0;
         }
         p.rd_fm.assign((size_t)p.NB, p.produced);
         p.fm_from = p.produced;
@@ -283,8 +282,7 @@ int rcf_scan_start(rcf_t *h, int fft_len, int n_frames, int avg_len)
     Scan &s = h->scan;
     // frames per launch: enough workgroups to fill 256 CUs (2^25 samples per launch), bounded so that
     // the log-magnitude ring ((avg_len + chunk) x N floats) and the four-step scratch stay modest
-    static const int chunk_log2 = [] { const char *e = getenv("RCF_SCAN_CHUNK_LOG2"); return e ? atoi(e) : 25; }();
-    int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(512, (int64_t(1) << chunk_log2) / fft_len));
+    int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(512, (int64_t(1) << 25) / fft_len));
     chunk = std::min(chunk, n_frames);
     if (s.d_vring && s.N == fft_len && s.L == avg_len && s.chunk == chunk) {
         // same geometry as the previous scan: keep every buffer (fresh device allocations cost tens of

@@ -13,6 +13,9 @@
 namespace rcfx {
 
 static thread_local char g_err[512] = "";
+// largest block (bytes in the caller's pinned buffer) that rcf_push_iq / rcf_push_raw read straight out of host memory on
+// the compute stream; larger ones are staged on the copy stream so that a bulk replay's copies overlap the kernels
+constexpr size_t kRawDirectBytes = size_t(4) << 20;
 
 void set_error(const char *fmt, ...)
 {
@@ -201,16 +204,9 @@ int rcf_open_ex(int device, double samp_rate, double center_freq, size_t block_c
     h->hist_cap = hist_capacity ? hist_capacity : (size_t(1) << 16);
     h->out_cap = pow2_at_least(out_capacity ? out_capacity : (size_t(1) << 16));
     h->ring_mask = (uint64_t)h->out_cap - 1;
-    {
-        if (const char *nm = getenv("RCF_FIR_NOMFMA")) h->no_mfma = atoi(nm) != 0;
-        if (const char *rm = getenv("RCF_ROTATOR")) h->exact_rot = std::strcmp(rm, "exact") == 0;
-        if (const char *df = getenv("RCF_DECIM_FLOOR")) h->decim_rule = std::atoi(df) ? RCF_DECIM_FLOOR : RCF_DECIM_EXACT;
-        if (const char *ck = getenv("RCF_COPY_KERNELS")) h->copy_kernels = h->copy_kernels && atoi(ck) != 0;
-        if (const char *lg = getenv("RCF_S2_LAG")) h->lag_enabled = atoi(lg) != 0;
-    if (const char *nm = getenv("RCF_FIR_MFMA_MIN")) h->mfma_min = std::max(1, atoi(nm));
-        if (const char *nm = getenv("RCF_FIR_MFMA_NT")) h->mfma_nt = atoi(nm);
-        if (const char *nm = getenv("RCF_FIR_MFMA_PARTS")) h->mfma_parts = atoi(nm);
-    }
+    if (const char *rm = getenv("RCF_ROTATOR")) h->exact_rot = std::strcmp(rm, "exact") == 0;
+    if (const char *df = getenv("RCF_DECIM_FLOOR")) h->decim_rule = std::atoi(df) ? RCF_DECIM_FLOOR : RCF_DECIM_EXACT;
+    if (const char *lg = getenv("RCF_S2_LAG")) h->lag_enabled = atoi(lg) != 0;
     RCF_HIP(hipSetDevice(device));
     RCF_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     const size_t buf_samples = h->hist_cap + h->block_cap;
@@ -338,9 +334,8 @@ int rcf_push_iq(rcf_t *h, const float *iq, size_t n)
         // a real-time-sized block in pinned memory (see rcf_push_raw): copied by a kernel on the compute stream straight
         // out of host memory -- no second stream, no cross-stream waits.  In order behind every kernel that read this
         // buffer, so no buf_done bookkeeping either.
-        static const int direct = [] { const char *e = getenv("RCF_RAW_DIRECT"); return e ? atoi(e) : (4 << 20); }();
         void *dv = nullptr;
-        if (direct && n * sizeof(float2) <= (size_t)direct && h->copy_kernels &&
+        if (n * sizeof(float2) <= kRawDirectBytes && h->copy_kernels &&
             hipHostGetDevicePointer(&dv, const_cast<float *>(iq), 0) == hipSuccess && dv) {
             launch_copy8(h->d_buf[h->cur] + h->hist_cap, dv, sizeof(float2) * n, h->stream);
             RCF_HIP(hipEventRecord(h->copy_ev, h->stream));
@@ -379,12 +374,11 @@ int rcf_push_raw(rcf_t *h, const void *iq_raw, size_t n, int fmt, float scale, f
         // memory across PCIe -- no staging copy, no second stream, no cross-stream event waits: one event instead of
         // two and two barrier packets fewer per block, which is what a real-time-sized block (a handful of ~5 us
         // kernels) is made of: 256 front-ends of the bench's real-time leg p99 1.9 -> 0.2 ms, 384 sustained instead
-        // of missing.  Blocks above RCF_RAW_DIRECT bytes (default 4 MiB; 0 = never) keep the staged copy: in a bulk
+        // of missing.  Blocks above kRawDirectBytes keep the staged copy: in a bulk
         // replay the copy of block n + 1 then overlaps the kernels of block n, which a PCIe-bound kernel on the
         // compute stream would not.
-        static const int direct = [] { const char *e = getenv("RCF_RAW_DIRECT"); return e ? atoi(e) : (4 << 20); }();
         void *dv = nullptr;
-        if (direct && n * bps <= (size_t)direct && hipHostGetDevicePointer(&dv, const_cast<void *>(iq_raw), 0) == hipSuccess && dv) {
+        if (n * bps <= kRawDirectBytes && hipHostGetDevicePointer(&dv, const_cast<void *>(iq_raw), 0) == hipSuccess && dv) {
             launch_convert(fmt, dv, h->d_buf[h->cur] + h->hist_cap, n, scale, offset, h->stream);
             RCF_HIP(hipEventRecord(h->copy_ev, h->stream));
             int rc = process_block(h, n);

@@ -149,6 +149,7 @@ inline int fir_small_outputs_rider(int D, int T)
 // has no size limit.
 constexpr int kM2Group = 32;      // channels per group (4 M-tiles of 8)
 constexpr int kM2ChunkSteps = 8;  // steps per LDS chunk (32 KB)
+constexpr int kM2MinChans = 8;    // fewest channels of a class worth a matrix-core launch
 __host__ __device__ inline int bank2_steps(int T)
 {
     const int s = ((T / 2 + 1) + 3) / 4;
@@ -175,17 +176,15 @@ inline bool mfma2_applicable(int D, int T, size_t hist_cap, size_t buf_samples)
 // Deterministic for a given sequence of commits; cut-invariant to ~1e-6 relative (5e-6 on noise-only channels), not bit for bit
 // (tests/test_gpu_round3.py::test_matrix_core_bank_uneven_cuts_agree_to_summation_order) -- unlike the filterbanks.
 struct MfmaPlan { int nt, parts; };
-inline MfmaPlan mfma_plan(int n_chans, int n_k, int T, int force_nt = 0, int force_parts = 0)
+inline MfmaPlan mfma_plan(int n_chans, int n_k, int T)
 {
     const int groups = (n_chans + kM2Group - 1) / kM2Group;
     const int n_chunks = bank2_steps(T) / kM2ChunkSteps;
     MfmaPlan best{1, 1};
     double best_cost = 1e300;
     for (int nt = 1; nt <= 2; ++nt) {
-        if (force_nt && nt != force_nt) continue;
         const int64_t wgs = (int64_t)groups * ((n_k + 64 * nt - 1) / (64 * nt));
         for (int parts = 1; parts <= 8 && parts <= n_chunks; ++parts) {
-            if (force_parts && parts != force_parts) continue;
             const int64_t rounds = (wgs * parts + 511) / 512;
             // time in units of one NT = 1 full-K round; NT = 2 units are twice as long but ~6 % more efficient;
             // split launches pay the finishing pass (partials written + read) and a little per part
@@ -414,10 +413,19 @@ struct GroupMap {
     int32_t n_fe, total_wg, uniform_nwg;
 };
 #ifdef __HIPCC__
+// The XCD-aware block -> chunk map: blocks are dealt to the eight XCDs round-robin (block b to XCD b % 8), and each XCD
+// owns a contiguous range of the n chunks (the first n % 8 XCDs one chunk more).  This is where the range of block b's
+// XCD starts; block b runs chunk xcd_chunk_first(n, b) + b / 8.  Neighbouring chunks share input rows -- and the fused
+// discriminator's hand-over -- in one XCD's L2; pfb5_xcd_map_ok checks on the device that blocks are dealt this way.
+__device__ __forceinline__ int xcd_chunk_first(int n, int b)
+{
+    const int q = n / 8, r = n % 8, xcd = b % 8;
+    return xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+}
+
 __device__ __forceinline__ void group_resolve(const GroupMap &m, int b, int &fe, int &wg)
 {
-    const int q = m.total_wg / 8, r = m.total_wg % 8, xcd = b % 8;
-    const int v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + b / 8;
+    const int v = xcd_chunk_first(m.total_wg, b) + b / 8;
     if (m.uniform_nwg > 0) {
         fe = v / m.uniform_nwg;
         wg = v - fe * m.uniform_nwg;

@@ -61,12 +61,10 @@ int launch_plan(rcf_t *h, BlockPlan &bp)
         // the stream): one small launch per block instead of two
         const size_t from = arena_base & ~size_t(63);
         const size_t bytes = ar.used > arena_base ? ((ar.used + 63) & ~size_t(63)) - from : 0;
-        static const bool merge = [] { const char *e = getenv("RCF_COPY_MERGE"); return !e || atoi(e) != 0; }();   // A/B
         // ... or none at all: when the filterbank's launch is the first of the block that needs neither (no direct
         // channels, no exact-rotator fill before it, no tap matrix whose slot list the bank itself reads from the
         // arena), its first workgroups do both copies on the way in (PfbLaunch::rider_*)
-        static const bool ride_env = [] { const char *e = getenv("RCF_COPY_RIDE"); return !e || atoi(e) != 0; }();    // A/B
-        const bool ride = ride_env && merge && h->copy_kernels && run_pfb && !d_rot_fills &&
+        const bool ride = h->copy_kernels && run_pfb && !d_rot_fills &&
                           (fir_by_depth.empty() || fir_by_depth[0].empty()) && pl.n_taps == pl.tap_first &&
                           bytes / 8 < (1u << 31) && h->hist_cap < (1u << 28) && pfb_takes_rider(pl);
         if (ride) {
@@ -77,8 +75,6 @@ int launch_plan(rcf_t *h, BlockPlan &bp)
             pl.rider_src[1] = reinterpret_cast<const unsigned long long *>(h->d_buf[h->cur] + bp.n);
             pl.rider_n8[1] = (uint32_t)(sizeof(float2) * h->hist_cap / 8);
             bp.history_done = true;
-        } else if (h->copy_kernels && !merge) {
-            if (bytes) launch_copy8(ar.d + from, h->arenas.h_dev[a] + from, bytes, st);
         } else if (h->copy_kernels) {
             Timed t(h, RCF_T_HISTORY);
             launch_copy8x2(ar.d + from, h->arenas.h_dev[a] + from, bytes, h->d_buf[h->cur ^ 1], h->d_buf[h->cur] + bp.n,

@@ -378,7 +378,7 @@ int plan_class_jobs(rcf_t *h, BlockPlan &bp, ClassPlan &cp, int depth, std::pair
     std::vector<ChanLaunch> clean, rest, fixups;
     std::vector<Chan *> clean_ch;
     int n_common_of_clean = max_n;
-    if (shared_src && depth == 0 && mfma2_applicable(D, T, h->hist_cap, h->hist_cap + h->block_cap) && !h->no_mfma) {
+    if (shared_src && depth == 0 && mfma2_applicable(D, T, h->hist_cap, h->hist_cap + h->block_cap)) {
         int64_t k_common = -1;
         int32_t n_common = 0;
         for (auto &L : launches)                                   // the range most channels share: the earliest
@@ -409,7 +409,7 @@ int plan_class_jobs(rcf_t *h, BlockPlan &bp, ClassPlan &cp, int depth, std::pair
                 if (F.n_k > 0) fixups.push_back(F);
             }
         // (no size limit on a class: every group of 32 channels has its own tap slab)
-        if ((int)clean.size() < h->mfma_min) {
+        if ((int)clean.size() < kM2MinChans) {
             rest.insert(rest.end(), clean.begin(), clean.end());   // (order within a vector launch is free)
             clean.clear();
             clean_ch.clear();
@@ -463,7 +463,7 @@ int plan_class_jobs(rcf_t *h, BlockPlan &bp, ClassPlan &cp, int depth, std::pair
         mj.dims.max_n_k = n_common_of_clean;
         mj.dims.src_len = (int64_t)(h->hist_cap + n);
         {
-            const MfmaPlan plan = mfma_plan((int)clean.size(), n_common_of_clean, T, h->mfma_nt, h->mfma_parts);
+            const MfmaPlan plan = mfma_plan((int)clean.size(), n_common_of_clean, T);
             mj.dims.mfma_nt = plan.nt;
             mj.dims.mfma_parts = plan.parts;
             mj.dims.partial = nullptr;

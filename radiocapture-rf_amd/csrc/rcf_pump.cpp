@@ -444,12 +444,7 @@ int rcf_pump_start(rcf_group_t *g, const rcf_pump_config_t *cfg, rcf_pump_t **ou
     }
     p->h_recs = static_cast<unsigned char *>(hp);
     p->h_recs_dev = static_cast<unsigned char *>(dv);
-    {
-        // RCF_PUMP_BLOCKING=1: the pump sleeps in the driver while it waits for a group block instead of spinning on the event
-        static const bool blocking = [] { const char *e = getenv("RCF_PUMP_BLOCKING"); return e && atoi(e) != 0; }();
-        for (int i = 0; i < 2; ++i)
-            RCF_HIP(hipEventCreateWithFlags(&p->slot_ev[i], hipEventDisableTiming | (blocking ? hipEventBlockingSync : 0)));
-    }
+    for (int i = 0; i < 2; ++i) RCF_HIP(hipEventCreateWithFlags(&p->slot_ev[i], hipEventDisableTiming));
     // room in the group's arena for a group block of ALL members at once (after a hiccup everything that is complete goes
     // out together): growing the arena means a stream synchronisation and pinned allocations -- not in the middle of a run
     {

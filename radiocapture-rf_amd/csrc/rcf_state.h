@@ -114,7 +114,7 @@ struct Pfb {
     unsigned long long *d_fm_edge = nullptr, *d_fm_flag = nullptr;
     int *d_fm_err = nullptr;
     int fm_slots = 0;
-    int fm_local = 0;              // the hand-over stays in one XCD's L2 (pfb5_xcd_map_ok said so; RCF_PFB5_FM_LOCAL=0: never)
+    int fm_local = 0;              // the hand-over stays in one XCD's L2 (pfb5_xcd_map_ok said so)
     uint64_t fm_serial = 0;        // launches so far (the flags' tags)
     std::vector<int64_t> rd_fm;    // per-bin read cursors
 };
@@ -174,7 +174,7 @@ struct rcf {
     void *d_raw = nullptr;        // wire-format staging (rcf_push_raw), block_cap * 4 bytes, lazily allocated
     // launch-parameter arenas (pinned host + device), double buffered
     rcfx::ArenaSet arenas;
-    bool copy_kernels = true;     // RCF_COPY_KERNELS=0: hipMemcpyAsync for the launch records and the history (A/B)
+    bool copy_kernels = true;     // false (arenas not mapped): hipMemcpyAsync for the launch records and the history
     // Stage-2 lag (rcf_launch.cpp): the small-T FIR + discriminator launch of the last block has NOT been queued -- it rides
     // in the next block's filterbank launch (S2Rider), or goes out on its own as soon as anybody could look at its outputs
     // (every entry point that touches the stream flushes it: set_dev).  RCF_S2_LAG=0 / rcf_set_stage2_lag(h, 0): off.
@@ -241,8 +241,6 @@ struct rcf {
     // optional per-kernel-class HIP-event timing (rcf_timing_*)
     bool timing = false;
     unsigned timing_mask = ~0u;
-    int mfma_min = 8;             // fewest channels of a class worth a matrix-core launch (RCF_FIR_MFMA_MIN)
-    int mfma_nt = 0, mfma_parts = 0;   // RCF_FIR_MFMA_NT / RCF_FIR_MFMA_PARTS: override the launch plan (measurements)
     bool exact_rot = false;       // rcf_set_rotator / RCF_ROTATOR=exact: channels iterate GNU Radio's float32 rotator
     int decim_rule = RCF_DECIM_EXACT;   // rcf_set_decim_rule / RCF_DECIM_FLOOR=1
     uint64_t plan_calls = 0;            // blocks planned so far (RCF_FAIL_PLAN_AT)
@@ -250,7 +248,6 @@ struct rcf {
     size_t tapmat_cap = 0;        // in float2
     float2 *d_partial = nullptr;  // split-K slabs of the matrix-core bank
     size_t partial_cap = 0;       // in float2
-    bool no_mfma = false;         // RCF_FIR_NOMFMA=1: keep the vector-FMA bank kernel (A/B measurements)
     struct TimeRec { int what; hipEvent_t a, b; };
     std::vector<TimeRec> time_pending;
     std::vector<hipEvent_t> time_pool;

@@ -331,8 +331,7 @@ void launch_scan_movsum(float *vring, int N, int R, int L, int f0, int n_frames,
     if (n_frames <= 0) return;
     int n1 = 0, n2 = 0;
     if (N > 16384 && !scan4_split(N, &n1, &n2)) return;
-    static const int coop = [] { const char *e = getenv("RCF_SCAN_MOVSUM_COOP"); return e ? atoi(e) : 1; }();
-    if (N <= (1 << 15) && coop && R >= 128) {   // measured: 16384 bins 53 -> 34 us per 512 frames, 131072 bins 2x slower
+    if (N <= (1 << 15) && R >= 128) {   // measured: 16384 bins 53 -> 34 us per 512 frames, 131072 bins 2x slower
         constexpr int TT = 128;
         const size_t lds = sizeof(float) * 2 * 2 * TT * 64;
         static DynLdsAttr attr;

@@ -2,7 +2,6 @@
 for the 2^25-sample filterbank block the checks are size-independent properties: invariance to how the stream is
 cut, linearity, and where a bin-centred tone lands."""
 import math
-import os
 
 import numpy as np
 import pytest
@@ -36,8 +35,7 @@ def test_reference_shaped_bank_256_channels_at_20msps_equals_oracle(gpu_required
         fe.push(x[:n1])                  # history becomes real: the matrix-core kernel already runs, and a vector
         #                                  launch behind it redoes the few outputs that still see zero history
         fe.push(x[n1:])                  # the full-size block: matrix-core kernel only
-        if not os.environ.get("RCF_FIR_NOMFMA"):
-            assert fe.timing_read(nat.T_FIR_MFMA)[1] == 2 and fe.timing_read(nat.T_FIR)[1] == 1
+        assert fe.timing_read(nat.T_FIR_MFMA)[1] == 2 and fe.timing_read(nat.T_FIR)[1] == 1
         ys = np.stack([fe.chan_read_iq(c) for c in ids])
     cts = np.stack([OC.xlating_composite(taps, D, f, FS)[0] for f in offs])
     inc = np.array([OC.xlating_composite(taps, D, f, FS)[1] for f in offs], dtype=np.complex64)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Scan-path micro-benchmark (BASELINE configs[2] shape): N-point scan FFT + log-mag + running sum over
 resident IQ, HIP-event kernel times, then the peak pick.  env: N (default 2^20), FRAMES, AVG, REPS (scans; the last is
-timed), SAVE (npy of the emitted spectrum: RCF_SCAN_FUSED=0 / 1 runs are compared bit for bit)."""
+timed), SAVE (npy of the emitted spectrum, for bit-for-bit comparison of two builds' runs)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "radiocapture-rf_amd")]
