@@ -300,8 +300,10 @@ int rcf_source_shift(rcf_t *h, double delta_hz);
  * into a frame-major ring fm_ring[((n - n0) & (capacity - 1)) n_bins + k] -- the arithmetic (and the bits) of a tap opened
  * with rcf_pfb_tap_open(bin, gr_phase) + rcf_chan_set_fm_only, without the tap matrix, the IQ round trip through HBM and
  * the tap_finalize pass: 8 + 8 bytes per input sample instead of 48 at 1600 bins / decimation 800.
- *   mode 1: beside the bins ring;  mode 2: INSTEAD of it (rcf_pfb_read_bin, rcf_pfb_chan_open and zero-copy readers of the
- *   bins ring then see no new frames: RCF_ESTATE);  mode 0: off again.  Takes effect with the next block.
+ *   mode 1: beside the bins ring;  mode 2: INSTEAD of it -- rcf_pfb_read_bin, rcf_pfb_rings, rcf_pfb_chan_open and any other
+ *   channel on a bin (rcf_chan_open_taps with src >= RCF_SRC_PFB_BIN0) then fail with RCF_ESTATE, and mode 2 itself is
+ *   refused (RCF_ESTATE) while such a channel is open; taps (rcf_pfb_tap_open) keep working.  Leaving mode 2, readers of the
+ *   bins ring go on from the frame of the switch;  mode 0: off again.  Takes effect with the next block.
  *   gr_phase != 0: inc_k = the float32 rotator increment GNU Radio's freq_xlating_fir_filter_ccc on bin k would carry
  *   (what rcf_pfb_tap_open(bin, 1) models); 0: the bank's exact phases (inc_k = 1).  rcf_source_shift is followed.
  * The first frame after enabling takes its predecessor from the input history (recomputed, not stored): the handle's

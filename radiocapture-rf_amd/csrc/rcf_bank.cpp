@@ -166,6 +166,17 @@ int rcf_pfb_fm_enable(rcf_t *h, int mode, int gr_phase)
     if (set_dev(h)) return RCF_EHIP;
     Pfb &p = h->pfb;
     if (!p.open) { set_error("no filterbank open"); return RCF_ESTATE; }
+    if (mode == 2) {
+        // the bins ring is not written in mode 2: nothing may be left filtering it (taps are copied by the kernel itself)
+        for (const auto &kv : h->chans)
+            if (kv.second->src >= RCF_SRC_PFB_BIN0 && !kv.second->is_tap) {
+                set_error("channel %d reads bin %d of the bins ring, which mode 2 stops writing: close it first", kv.first,
+                          kv.second->src - RCF_SRC_PFB_BIN0);
+                return RCF_ESTATE;
+            }
+    }
+    if (p.fm_mode == 2 && mode != 2)                      // the frames of mode 2 never reached the bins ring: its readers skip them
+        for (auto &r : p.rd) r = std::max(r, p.produced);
     if (mode == 0) {
         if (p.fm_mode) p.fm_until = p.produced;          // frames from here on are not demodulated: readers stop here
         p.fm_mode = 0;
@@ -178,23 +189,45 @@ int rcf_pfb_fm_enable(rcf_t *h, int mode, int gr_phase)
     const size_t need = pfb5_fm_history(p.NB, p.D, p.P);
     if (need > h->hist_cap) { set_error("history capacity %zu < %zu (the fused discriminator's halo chunk)", h->hist_cap, need); return RCF_ECAP; }
     if (!p.d_fm) {
-        const size_t ring = (size_t)p.NB * h->out_cap;
-        RCF_HIP(hipMalloc(&p.d_fm, sizeof(float) * ring));
-        RCF_HIP(hipMemsetAsync(p.d_fm, 0, sizeof(float) * ring, h->stream));
-        RCF_HIP(hipMalloc(&p.d_fm_inc, sizeof(float2) * (size_t)p.NB));
-        // the look-back form's hand-over rows (RCF_PFB5_FM_LOOKBACK=0: the span form, which needs none): more slots than
-        // workgroups can be resident at once, so a row is never rewritten while the chunk behind it still wants it
+        // The look-back form's hand-over rows (RCF_PFB5_FM_LOOKBACK=0: the span form, which needs none).  Chunk c of a launch
+        // publishes its last frame in row c mod fm_slots and waits for row c - 1: with one slot per chunk of the largest
+        // launch the handle accepts no two chunks of a launch share a row or a flag, however the workgroups are dispatched,
+        // retired or interleaved.  A launch is one block: at most ceil(block_cap / D) frames, and at most out_cap (plan_pfb,
+        // which also refuses a launch with more chunks than rows).  Rows of an earlier launch are never taken for this
+        // one's: launches of one bank run in stream order and every launch has its own tag (plan_pfb).
         static const bool lookback = [] { const char *e = getenv("RCF_PFB5_FM_LOOKBACK"); return !e || atoi(e) != 0; }();
-        if (lookback) {
-            p.fm_slots = 4096;
-            RCF_HIP(hipMalloc(&p.d_fm_edge, sizeof(unsigned long long) * (size_t)(p.fm_slots + 9) * (size_t)p.NB));
-            RCF_HIP(hipMalloc(&p.d_fm_flag, sizeof(unsigned long long) * (size_t)p.fm_slots * 8));      // one flag per wave of a chunk's workgroup
-            RCF_HIP(hipMalloc(&p.d_fm_err, sizeof(int)));
-            RCF_HIP(hipMemsetAsync(p.d_fm_flag, 0, sizeof(unsigned long long) * (size_t)p.fm_slots * 8, h->stream));
-            RCF_HIP(hipMemsetAsync(p.d_fm_err, 0, sizeof(int), h->stream));
-            p.fm_local = pfb5_xcd_map_ok(h->device, h->stream) ? 1 : 0;
-        }
+        const int64_t max_frames = std::min<int64_t>((int64_t)h->out_cap, ceil_div((int64_t)h->block_cap, p.D));
+        const int64_t slots = lookback ? ceil_div(max_frames, pfb_chunk_frames(p.NB)) : 0;
+        if (slots > (int64_t(1) << 27)) { set_error("output capacity %zu: too many hand-over rows for the fused discriminator", h->out_cap); return RCF_ECAP; }
         p.rd_fm.assign((size_t)p.NB, p.produced);
+        // all or nothing: every buffer goes into a local first, the bank takes them only once all of them exist
+        const size_t ring = (size_t)p.NB * h->out_cap;
+        float *d_fm = nullptr;
+        float2 *d_fm_inc = nullptr;
+        unsigned long long *d_fm_edge = nullptr, *d_fm_flag = nullptr;      // [slots + 9][NB] rows, [slots][8] flags (one per wave)
+        int *d_fm_err = nullptr;
+        bool ok = hip_ok(hipMalloc(&d_fm, sizeof(float) * ring), "hipMalloc(fm ring)") &&
+                  hip_ok(hipMalloc(&d_fm_inc, sizeof(float2) * (size_t)p.NB), "hipMalloc(fm increments)") &&
+                  hip_ok(hipMemsetAsync(d_fm, 0, sizeof(float) * ring, h->stream), "hipMemset(fm ring)");
+        if (ok && slots)
+            ok = hip_ok(hipMalloc(&d_fm_edge, sizeof(unsigned long long) * (size_t)(slots + 9) * (size_t)p.NB), "hipMalloc(fm edge rows)") &&
+                 hip_ok(hipMalloc(&d_fm_flag, sizeof(unsigned long long) * (size_t)slots * 8), "hipMalloc(fm flags)") &&
+                 hip_ok(hipMalloc(&d_fm_err, sizeof(int)), "hipMalloc(fm lost count)") &&
+                 hip_ok(hipMemsetAsync(d_fm_flag, 0, sizeof(unsigned long long) * (size_t)slots * 8, h->stream), "hipMemset(fm flags)") &&
+                 hip_ok(hipMemsetAsync(d_fm_err, 0, sizeof(int), h->stream), "hipMemset(fm lost count)");
+        if (!ok) {
+            (void)hipStreamSynchronize(h->stream);       // (a memset may be queued on what is freed)
+            for (void *q : {(void *)d_fm, (void *)d_fm_inc, (void *)d_fm_edge, (void *)d_fm_flag, (void *)d_fm_err})
+                if (q) (void)hipFree(q);
+            return RCF_EHIP;
+        }
+        p.d_fm = d_fm;
+        p.d_fm_inc = d_fm_inc;
+        p.d_fm_edge = d_fm_edge;
+        p.d_fm_flag = d_fm_flag;
+        p.d_fm_err = d_fm_err;
+        p.fm_slots = (int)slots;
+        if (slots) p.fm_local = pfb5_xcd_map_ok(h->device, h->stream) ? 1 : 0;
         p.fm_from = p.produced;
     } else if (p.fm_mode == 0) {                       // switched on again: the frames in between were not demodulated
         p.fm_from = p.produced;
@@ -265,6 +298,7 @@ int rcf_pfb_rings(rcf_t *h, void **bins_ring, size_t *capacity, size_t *pitch)
     std::lock_guard<std::mutex> g(h->mu);
     if (set_dev(h)) return RCF_EHIP;                  // (queues the deferred stage-2 launch: see rcf_chan_rings)
     if (!h->pfb.open) return RCF_ESTATE;
+    if (h->pfb.fm_mode == 2) { set_error("the bank writes its discriminator ring only (rcf_pfb_fm_enable mode 2): no bins ring"); return RCF_ESTATE; }
     if (bins_ring) *bins_ring = h->pfb.d_bins;
     if (capacity) *capacity = h->out_cap;
     if (pitch) *pitch = h->pfb.frame_major ? 0 : (size_t(1) << kPfbTileLog2);   // frames per tile (0: frame-major)

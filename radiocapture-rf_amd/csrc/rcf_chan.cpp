@@ -80,9 +80,13 @@ int upload_composite(rcf_t *h, Chan *c)
     return RCF_OK;
 }
 
-int new_channel(rcf_t *h, int src, int D, const float *taps, int T, double offset_hz, int *chan_id)
+int new_channel(rcf_t *h, int src, int D, const float *taps, int T, double offset_hz, int *chan_id, bool tap)
 {
     if (D < 1 || T < 1 || !taps || !chan_id) { set_error("bad channel arguments"); return RCF_EINVAL; }
+    if (src >= RCF_SRC_PFB_BIN0 && !tap && h->pfb.open && h->pfb.fm_mode == 2) {
+        set_error("the bank writes its discriminator ring only (rcf_pfb_fm_enable mode 2): no bins ring to filter");
+        return RCF_ESTATE;
+    }
     std::unique_ptr<Chan> c(new Chan);
     c->src = src;
     c->D = D;
@@ -250,7 +254,7 @@ int rcf_pfb_tap_open(rcf_t *h, int bin, int gr_phase, int *chan_id)
     Pfb &p = h->pfb;
     if (!p.open || bin < 0 || bin >= p.NB) { set_error("no such PFB bin %d", bin); return RCF_EINVAL; }
     const float one = 1.0f;
-    int rc = new_channel(h, RCF_SRC_PFB_BIN0 + bin, 1, &one, 1, 0.0, chan_id);
+    int rc = new_channel(h, RCF_SRC_PFB_BIN0 + bin, 1, &one, 1, 0.0, chan_id, p.frame_major);
     if (rc != RCF_OK) return rc;
     h->chans[*chan_id]->is_tap = p.frame_major;     // power-of-two banks: an ordinary D = 1, T = 1 channel on the bin's ring
     ++h->chans_epoch;                                // (the planning summary counts taps and FIR channels differently)

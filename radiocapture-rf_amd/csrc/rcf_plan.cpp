@@ -145,6 +145,14 @@ int plan_pfb(rcf_t *h, BlockPlan &bp)
                           (long long)cnt, bp.reach_x && bp.reach_x->count(RCF_SRC_PFB_BIN0) ? bp.reach_x->at(RCF_SRC_PFB_BIN0) : (size_t)0, h->out_cap);
                 return RCF_ECAP;
             }
+            if (p.fm_mode && p.d_fm_edge && ceil_div(cnt, pfb_chunk_frames(p.NB)) > p.fm_slots) {
+                // the look-back form's invariant: one hand-over row and flag per chunk of the launch (rcf_pfb_fm_enable
+                // sizes them for the largest launch the handle accepts, so this does not fire); two chunks of one launch on
+                // one row would wait for a tag that was overwritten and take a wrong predecessor frame
+                set_error("block yields %lld chunks of the fused discriminator > %d hand-over rows",
+                          (long long)ceil_div(cnt, pfb_chunk_frames(p.NB)), p.fm_slots);
+                return RCF_ECAP;
+            }
             pl.src.base = h->d_buf[h->cur];
             pl.src.mask = ~0ull;
             pl.src.origin = S0 - (int64_t)h->hist_cap;
@@ -173,6 +181,10 @@ int plan_pfb(rcf_t *h, BlockPlan &bp)
                     pl.fm_err = p.d_fm_err;
                     pl.fm_slots = p.fm_slots;
                     pl.fm_local = p.fm_local;
+                    // a tag of its own per launch: the rows and flags of the launch before are never taken for this one's.
+                    // Launches of one bank are in stream order -- the handle's own stream, or, while it is a group member,
+                    // the group's for all of them, single or grouped (rcf_group_open waits for the member's stream first,
+                    // rcf_group_close for the group's) -- so no earlier launch writes a row this one reads.
                     pl.fm_tag = (unsigned long long)(++p.fm_serial) << 32;
                 }
             } else {

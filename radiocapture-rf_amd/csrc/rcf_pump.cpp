@@ -255,6 +255,7 @@ void pump_main(rcf_pump *p)
                                 if (!pf.open || !pf.d_fm || bin >= pf.NB) continue;
                                 const int64_t end = pf.fm_mode ? pf.produced : pf.fm_until;
                                 int64_t &cur = p->bin_rd[(size_t)e];
+                                cur = std::max(cur, pf.fm_from);          // (switched off and on again: the frames between were never demodulated)
                                 int64_t avail = end - cur;
                                 if (avail <= 0) continue;
                                 if ((size_t)avail > h->out_cap) { cur = end - (int64_t)h->out_cap; avail = (int64_t)h->out_cap; }

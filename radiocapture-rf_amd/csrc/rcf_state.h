@@ -327,7 +327,8 @@ bool source_range(rcf_t *h, int src, int64_t S0, int64_t S1, SrcRange *out);
 int upload_composite(rcf_t *h, Chan *c);
 double pfb_tap_gr_dangle(const rcf_t *h, int bin);
 int pfb_fm_upload_increments(rcf_t *h);
-int new_channel(rcf_t *h, int src, int D, const float *taps, int T, double offset_hz, int *chan_id);
+// tap: a frame-major bank's tap (rcf_pfb_tap_open), copied by the bank's kernel -- the one bin consumer mode 2 keeps
+int new_channel(rcf_t *h, int src, int D, const float *taps, int T, double offset_hz, int *chan_id, bool tap = false);
 void free_channel(rcf_t *h, Chan *c);
 int64_t ring_read_enqueue(rcf_t *h, const void *ring, size_t elem, int64_t produced, int64_t *cursor, void *out,
                           size_t max_items);

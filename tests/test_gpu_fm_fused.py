@@ -320,3 +320,178 @@ def test_pump_delivers_bins_of_the_fused_discriminator_ring(gpu_required):
     w = np.concatenate(want[3])
     n = len(got[3])
     assert n < len(w) and n % (blk // D) == 0 and _same_bits(got[3], w[len(w) - n:]), (n, len(w))   # from the block it was subscribed in on
+
+
+def test_mode_2_refuses_bin_consumers_and_taps_keep_their_bits(gpu_required):
+    """mode 2 stops writing the bins ring: a channel filtering a bin (rcf_pfb_chan_open, or rcf_chan_open_taps on
+    RCF_SRC_PFB_BIN0 + bin) and the bins ring itself (rcf_pfb_rings) are refused while it is on, and it is refused while such
+    a channel is open; taps keep their bits (the bank's kernel copies them in every mode)"""
+    import ctypes as C
+    nat = gpu_required
+    fs = 5e6
+    D, taps = G.channel_params(fs, 12500)
+    nb = 2 * D
+    x = _signal(np.random.default_rng(606), fs, D * 300, nb, [21, 140])
+    caps = dict(block_capacity=D * 100, hist_capacity=1 << 15, out_capacity=1 << 12)
+    with nat.Frontend(fs, 0.0, device=0, **caps) as fa, nat.Frontend(fs, 0.0, device=0, **caps) as fb:
+        for f in (fa, fb):
+            f.pfb_open(nb, D, taps)
+        ta = [fa.pfb_tap_open(b, gr_phase=True) for b in (21, 140)]
+        tb = [fb.pfb_tap_open(b, gr_phase=True) for b in (21, 140)]
+        c = fb.pfb_chan_open(21, 6250, 0.0)
+        with pytest.raises(nat.RcfError) as ei:
+            fb.pfb_fm_enable(2, gr_phase=True)                     # a channel still filters a bin
+        assert ei.value.code == nat.RCF_ESTATE
+        fb.pfb_fm_enable(1, gr_phase=True)                         # (mode 1 keeps the bins ring: fine)
+        fb.pfb_fm_enable(0)
+        fb.chan_close(c)
+        fb.pfb_fm_enable(2, gr_phase=True)
+        for i in range(3):
+            fa.push(x[i * D * 100:(i + 1) * D * 100])
+            fb.push(x[i * D * 100:(i + 1) * D * 100])
+            for ca, cb in zip(ta, tb):
+                assert _same_bits(fa.chan_read_iq(ca), fb.chan_read_iq(cb))
+        with pytest.raises(nat.RcfError) as ei:
+            fb.pfb_chan_open(21, 6250, 0.0)
+        assert ei.value.code == nat.RCF_ESTATE
+        with pytest.raises(nat.RcfError) as ei:
+            fb.chan_open_taps(nat.SRC_PFB_BIN0 + 21, 4, G.low_pass_2(1.0, fs / D, 5000, 2000, 40.0), 0.0)
+        assert ei.value.code == nat.RCF_ESTATE
+        assert nat.lib().rcf_pfb_rings(fb._h, None, None, None) == nat.RCF_ESTATE
+        with pytest.raises(nat.RcfError):
+            fb.pfb_read_bin(21)
+        ring, cap, pitch = C.c_void_p(), C.c_size_t(), C.c_size_t()
+        assert nat.lib().rcf_pfb_rings(fa._h, C.byref(ring), C.byref(cap), C.byref(pitch)) == 0 and ring.value
+        fb.pfb_tap_open(77, gr_phase=True)                         # taps may still be opened
+        fb.pfb_fm_enable(0)
+        assert nat.lib().rcf_pfb_rings(fb._h, None, None, None) == 0
+
+
+def test_bin_channels_after_mode_2_and_beside_mode_1_have_the_bits_of_a_plain_bank(gpu_required):
+    """after mode 2 is switched off, a channel opened on a bin has the bits of the same channel on a bank that never had the
+    discriminator on, and the bins ring's reader goes on from the frame of the switch (the frames of mode 2 were never
+    written to it); in mode 1 a bin channel beside the fused ring has the bits of one on a plain bank"""
+    nat = gpu_required
+    fs = 5e6
+    D, taps = G.channel_params(fs, 12500)
+    nb = 2 * D
+    x = _signal(np.random.default_rng(707), fs, D * 500 + 17, nb, [21, 140])
+    caps = dict(block_capacity=D * 100 + 7, hist_capacity=1 << 15, out_capacity=1 << 12)
+    with nat.Frontend(fs, 0.0, device=0, **caps) as fa, nat.Frontend(fs, 0.0, device=0, **caps) as fb, \
+            nat.Frontend(fs, 0.0, device=0, **caps) as fc:
+        for f in (fa, fb, fc):
+            f.pfb_open(nb, D, taps)
+        fb.pfb_fm_enable(2, gr_phase=True)
+        fc.pfb_fm_enable(1, gr_phase=True)
+        ca = [fa.pfb_chan_open(140, 6250, 300.0)]
+        cc = [fc.pfb_chan_open(140, 6250, 300.0)]
+        cb = []
+        at = 0
+        bins_a, bins_b = [], []
+        for i, n in enumerate([D * 100 + 7, D * 100, D * 100 + 3, D * 100, D * 100 + 7]):
+            if i == 2:
+                fb.pfb_fm_enable(0)
+                ca.append(fa.pfb_chan_open(21, 6250, -200.0))
+                cb.append(fb.pfb_chan_open(21, 6250, -200.0))
+                cc.append(fc.pfb_chan_open(21, 6250, -200.0))
+            for f in (fa, fb, fc):
+                f.push(x[at:at + n])
+            at += n
+            ra = fa.pfb_read_bin(21)
+            if i >= 2:
+                bins_a.append(ra)
+                bins_b.append(fb.pfb_read_bin(21))                 # from the frame of the switch on: nothing of mode 2
+            assert _same_bits(fc.pfb_read_bin(21), ra)
+            for k, (a_, c_) in enumerate(zip(ca, cc)):
+                ya, fa_ = fa.chan_read_iq(a_), fa.chan_read_fm(a_, 5.0)
+                assert len(ya) > 0 and _same_bits(ya, fc.chan_read_iq(c_)) and _same_bits(fa_, fc.chan_read_fm(c_, 5.0)), (i, k)
+                if k == 1:                                         # opened after mode 2 was switched off
+                    assert _same_bits(ya, fb.chan_read_iq(cb[0])) and _same_bits(fa_, fb.chan_read_fm(cb[0], 5.0)), i
+        assert fc.pfb_fm_lost() == 0 and fb.pfb_fm_lost() == 0
+        wa, wb = np.concatenate(bins_a), np.concatenate(bins_b)
+        assert len(wb) == len(wa) and _same_bits(wa, wb), (len(wa), len(wb))
+
+
+def test_pump_bins_of_the_fused_ring_across_off_and_on(gpu_required):
+    """a pump slot on a bin of the fused discriminator ring while the discriminator is switched on (mode 2), off, and on
+    again, at block boundaries the test controls (counter-fed sources): what it delivers is, bit for bit, gain x what
+    rcf_pfb_read_fm hands out for the same blocks pushed one by one with the same switches -- nothing of the frames between
+    the switches, which were never demodulated"""
+    import time
+    nat = gpu_required
+    fs = 5e6
+    D, taps = G.channel_params(fs, 12500)
+    nb = 2 * D
+    blk = 100000
+    phases = [2, 0, 2, 0, 1]                                       # mode per run of blocks
+    per = [3, 2, 3, 1, 2]                                          # blocks per run
+    n_blocks = sum(per)
+    rng = np.random.default_rng(818)
+    xs = [_signal(rng, fs, blk * n_blocks, nb, [21 + 9 * m, nb - 30 - m]) for m in range(2)]
+    u8 = [np.clip(np.round(x.view(np.float32) * 32.0 + 127.4), 0, 255).astype(np.uint8) for x in xs]
+    gain = 2.5
+    bins = [(0, 21), (0, nb - 30), (1, 30), (1, 319)]
+
+    def open_all():
+        fes = []
+        for m in range(2):
+            fe = nat.Frontend(fs, 0.0, device=0, block_capacity=blk, hist_capacity=1 << 15, out_capacity=1 << 13)
+            fe.pfb_open(nb, D, taps)
+            fe.pfb_fm_enable(phases[0], gr_phase=True)
+            fes.append(fe)
+        return fes
+
+    fes = open_all()
+    rings, counters = [], []
+    for m in range(2):
+        r = nat.PinnedArray(len(u8[m]), np.uint8)
+        r.array[:] = u8[m]
+        rings.append(r)
+        counters.append(np.zeros(1, dtype=np.uint64))
+    grp = nat.Group(fes)
+    pump = nat.Pump(grp, rings, blk, fs, [(m, nat.SRC_PFB_BIN0 + b) for m, b in bins], fmt=nat.FMT_U8, scale=1.0 / 32,
+                    offset=127.4, what="fm", gain=gain, out_ring_samples=1 << 14, n_blocks=n_blocks, written=counters,
+                    start_delay_s=0.0)
+    got = [[] for _ in bins]
+    done = 0
+    for run, (mode, k) in enumerate(zip(phases, per)):
+        if run:
+            for fe in fes:
+                fe.pfb_fm_enable(mode, gr_phase=True)
+        done += k
+        for c in counters:
+            c[0] = done
+        t_end = time.monotonic() + 60.0
+        while pump.stats()["blocks_done"] < 2 * done and time.monotonic() < t_end:
+            time.sleep(0.002)
+        st = pump.stats()
+        assert st["error"] == 0 and st["blocks_done"] == 2 * done, st
+        for e in range(len(bins)):
+            got[e].append(pump.read(e))
+    pump.stop()
+    grp.close()
+    for fe in fes:
+        assert fe.pfb_fm_lost() == 0
+        fe.close()
+    fes = open_all()
+    want = [[] for _ in bins]
+    b = 0
+    for run, (mode, k) in enumerate(zip(phases, per)):
+        if run:
+            for fe in fes:
+                fe.pfb_fm_enable(mode, gr_phase=True)
+        for _ in range(k):
+            for m in range(2):
+                fes[m].push_raw(u8[m][2 * b * blk: 2 * (b + 1) * blk], nat.FMT_U8, 1.0 / 32, 127.4)
+            b += 1
+        for e, (m, bin_) in enumerate(bins):
+            want[e].append(fes[m].pfb_read_fm(bin_, gain))
+    for fe in fes:
+        fe.close()
+    for r in rings:
+        r.free()
+    for e in range(len(bins)):
+        for run in range(len(phases)):
+            g_, w_ = got[e][run], want[e][run]
+            assert len(g_) == len(w_) and _same_bits(g_, w_), (bins[e], run, phases[run], len(g_), len(w_))
+        assert len(np.concatenate(want[e])) == (per[0] + per[2] + per[4]) * (blk // D)
