@@ -237,12 +237,14 @@ int64_t rcf_chan_read_iq(rcf_t *h, int chan_id, float *out_interleaved, size_t m
 int64_t rcf_chan_read_fm(rcf_t *h, int chan_id, float gain, float *out, size_t max_samples);
 /* The same reads for MANY channels behind one stream synchronisation -- what an egress pump that serves hundreds of
  * channel.py:36 PUB sockets needs per pass (a single-channel read costs a device round trip each).  what: RCF_READ_IQ
- * (out = float2[n_chans][cap_each]) or RCF_READ_FM (out = float[n_chans][cap_each], scaled by gain); counts[i] = samples
- * copied for chan_ids[i] (0: nothing new; RCF_ENOCHAN: no such channel, RCF_EINVAL: a channel listed a second time -- it
- * has one reader position per stream; the others are still served).  `out` may be
- * pinned memory (rcf_host_alloc): the copies then overlap each other. */
+ * (out = float2[n_chans][cap_each]), RCF_READ_FM (out = float[n_chans][cap_each], scaled by gain) or RCF_READ_AGC
+ * (out = float2[n_chans][cap_each], the AGC ring of rcf_chan_agc); counts[i] = samples copied for chan_ids[i] (0: nothing
+ * new; RCF_ENOCHAN: no such channel, RCF_EINVAL: a channel listed a second time -- it has one reader position per stream;
+ * RCF_ESTATE: the channel has no such stream -- IQ of a discriminator-only tap, AGC of a channel without one; the others
+ * are still served).  `out` may be pinned memory (rcf_host_alloc): the copies then overlap each other. */
 #define RCF_READ_IQ 0
 #define RCF_READ_FM 1
+#define RCF_READ_AGC 2    /* rcf_chan_read_many / rcf_group_read_many: cf32 rows from the AGC ring (rcf_chan_agc) */
 int rcf_chan_read_many(rcf_t *h, int what, const int *chan_ids, int n_chans, float gain, void *out, size_t cap_each,
                        int64_t *counts);
 /* P25 C4FM front half after the discriminator (p25_control_demod.py:129-133, logging_receiver.py:240-244):
@@ -251,6 +253,27 @@ int rcf_chan_read_many(rcf_t *h, int what, const int *chan_ids, int n_chans, flo
  * at the channel's rate (the sequential symbol-timing loop, op25 fsk4_demod_ff, stays on the host). */
 int rcf_chan_fm_filter(rcf_t *h, int chan_id, float gain, const float *taps, int ntaps);
 int64_t rcf_chan_read_sym(rcf_t *h, int chan_id, float *out, size_t max_samples);
+/* P25 CQPSK front half after the pre-filter (p25_control_demod.py:146-149,182-183; logging_receiver.py:278-332 runs the
+ * same chain on every call of a CQPSK system): analog.feedforward_agc_cc(nsamples, reference) on the channel's IQ
+ * (p25_control_demod.py:149, logging_receiver.py:281) -- the multiply_const_cc(1.0) on either side is the identity.  With
+ * x[m] = 0 before the stage's first input, N = nsamples, R = reference:
+ *     env(z) = float(|re| > |im| ? (double)|re| + 0.4 (double)|im| : (double)|im| + 0.4 (double)|re|)
+ *     out[n] = (R / max(1e-4f, max env(x[n-N+1 .. n]))) * x[n-N+1]          (float division, float products)
+ * i.e. the input delayed by N - 1 samples, scaled by a gain that looks N - 1 samples ahead; the first N - 1 outputs are 0.
+ * Bit-identical to GNU Radio's naive loop restated in float (every step is exactly rounded).  nsamples = 0 switches it off.
+ * Starts, with zero history, at the channel's next output (again on every call); applies from the next block on, on every
+ * channel kind (direct, chained, stage-2, filterbank tap); a retune keeps it, closing the channel releases it.  The
+ * sequential loops behind it (op25 gardner_costas_cc, diff_phasor_cc) stay with the consumer.
+ * RCF_EINVAL: nsamples outside 0 .. 4096 or a non-finite reference; RCF_ENOCHAN: no such channel; RCF_ESTATE: a
+ * discriminator-only tap (rcf_chan_set_fm_only: no IQ; switching that on is refused while an AGC reads the channel);
+ * RCF_ECAP: out_capacity < 2 nsamples -- and at a block that yields more outputs than the ring holds beside the N - 1
+ * samples of look-back (nothing is queued then). */
+int rcf_chan_agc(rcf_t *h, int chan_id, int nsamples, float reference);
+/* unread AGC outputs (cf32), oldest first, at the channel's rate; RCF_ESTATE without an AGC */
+int64_t rcf_chan_read_agc(rcf_t *h, int chan_id, float *out_interleaved, size_t max_samples);
+/* device pointer of the AGC's cf32 ring and its capacity (zero-copy, like rcf_chan_rings): output n lives at index
+ * n & (capacity-1), n counted as rcf_chan_produced counts the channel's outputs */
+int rcf_chan_agc_ring(rcf_t *h, int chan_id, void **agc_ring, size_t *capacity);
 /* drift probe of p25_control_demod.py:123-127: moving_average_ff(window, 1) * (1/window) of the
  * discriminator output (window = 10000 there) == mean of gain*fm over the last `window` samples; this is
  * the value demod_watcher hands to frontend_connector.report_offset */

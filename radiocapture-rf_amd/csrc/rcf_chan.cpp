@@ -1,5 +1,5 @@
 // rcf_chan.cpp -- channels: lifecycle (channel.channel / set_offset / destroy of /root/reference/rc_frontend/channel.py),
-// ring reads, the P25 symbol filter, the analog voice chain, source shift.
+// ring reads, the P25 symbol filter and AGC, the analog voice chain, source shift.
 #include "rcf_plan.h"
 
 namespace rcfx {
@@ -151,6 +151,8 @@ void free_channel(rcf_t *h, Chan *c)
     c->d_rot = nullptr;
     bury(h, c->d_sym);
     bury(h, c->d_symtaps);
+    bury(h, c->d_agc);
+    c->d_agc = nullptr;
     if (c->audio) { bury(h, c->audio->d_state); bury(h, c->audio->d_rings); bury(h, c->audio->d_taps); c->audio.reset(); }
     c->d_sym = nullptr;
     c->d_symtaps = nullptr;
@@ -197,6 +199,17 @@ int64_t ring_read(rcf_t *h, const void *ring, size_t elem, int64_t produced, int
     free_graveyard_idle(h);       // retuned / closed channels' old buffers: every read is a chance to release them
     *cursor += n;
     return n;
+}
+
+// the ring and reader position rcf_chan_read_many / rcf_group_read_many take for `what` (RCF_READ_*)
+int64_t *chan_read_cursor(Chan *c, int what)
+{
+    return what == RCF_READ_IQ ? &c->rd_iq : what == RCF_READ_AGC ? &c->rd_agc : &c->rd_fm;
+}
+
+const void *chan_read_ring(const Chan *c, int what)
+{
+    return what == RCF_READ_IQ ? (const void *)c->d_iq : what == RCF_READ_AGC ? (const void *)c->d_agc : (const void *)c->d_fm;
 }
 
 }  // namespace rcfx
@@ -380,13 +393,13 @@ int64_t rcf_chan_read_fm(rcf_t *h, int chan_id, float gain, float *out, size_t m
 int rcf_chan_read_many(rcf_t *h, int what, const int *chan_ids, int n_chans, float gain, void *out, size_t cap_each,
                        int64_t *counts)
 {
-    if (!h || !chan_ids || !out || !counts || n_chans < 0 || (what != RCF_READ_IQ && what != RCF_READ_FM)) {
+    if (!h || !chan_ids || !out || !counts || n_chans < 0 || (what != RCF_READ_IQ && what != RCF_READ_FM && what != RCF_READ_AGC)) {
         set_error("bad batched read arguments");
         return RCF_EINVAL;
     }
     std::lock_guard<std::mutex> g(h->mu);
     if (set_dev(h)) return RCF_EHIP;
-    const size_t elem = what == RCF_READ_IQ ? sizeof(float2) : sizeof(float);
+    const size_t elem = what == RCF_READ_FM ? sizeof(float) : sizeof(float2);
     const uint32_t ew = (uint32_t)(elem / 4);
     // what every channel has to give, and where its reader stands
     struct Item { Chan *c; int64_t *cur; const void *ring; int64_t n; size_t pos; };
@@ -403,9 +416,10 @@ int rcf_chan_read_many(rcf_t *h, int what, const int *chan_ids, int n_chans, flo
         if (c->many_stamp == stamp) { counts[i] = RCF_EINVAL; continue; }   // listed twice: one reader position per channel
         c->many_stamp = stamp;
         if (what == RCF_READ_IQ && c->fm_only) { counts[i] = RCF_ESTATE; continue; }   // discriminator only
+        if (what == RCF_READ_AGC && !c->d_agc) { counts[i] = RCF_ESTATE; continue; }   // no AGC on this channel
         it.c = c;
-        it.cur = what == RCF_READ_IQ ? &c->rd_iq : &c->rd_fm;
-        it.ring = what == RCF_READ_IQ ? (const void *)c->d_iq : (const void *)c->d_fm;
+        it.cur = chan_read_cursor(c, what);
+        it.ring = chan_read_ring(c, what);
         int64_t avail = c->produced - *it.cur;
         if (avail > 0 && (size_t)avail > h->out_cap) {          // reader lagged: oldest samples are gone
             *it.cur = c->produced - (int64_t)h->out_cap;
@@ -514,6 +528,57 @@ int64_t rcf_chan_read_sym(rcf_t *h, int chan_id, float *out, size_t max_samples)
     FIND_CHAN(h, chan_id, c);
     if (!c->d_sym) { set_error("channel %d has no fm filter", chan_id); return RCF_ESTATE; }
     return ring_read(h, c->d_sym, sizeof(float), c->produced, &c->rd_sym, out, max_samples);
+}
+
+int rcf_chan_agc(rcf_t *h, int chan_id, int nsamples, float reference)
+{
+    if (!h || nsamples < 0 || nsamples > 4096 || !std::isfinite(reference)) { set_error("bad AGC arguments"); return RCF_EINVAL; }
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (nsamples == 0) {                // off: the ring goes once the stream has passed it
+        if (c->d_agc) {
+            bury(h, c->d_agc);
+            c->d_agc = nullptr;
+            c->agc_n = 0;
+            ++h->chans_epoch;
+        }
+        return RCF_OK;
+    }
+    if (c->fm_only) { set_error("channel %d exposes its discriminator only: the AGC reads IQ", chan_id); return RCF_ESTATE; }
+    if ((size_t)nsamples * 2 > h->out_cap) { set_error("ring of %zu too small for a %d-sample AGC window", h->out_cap, nsamples); return RCF_ECAP; }
+    if (!c->d_agc) {
+        RCF_HIP(hipMalloc(&c->d_agc, sizeof(float2) * h->out_cap));
+        RCF_HIP(hipMemsetAsync(c->d_agc, 0, sizeof(float2) * h->out_cap, h->stream));
+    }
+    c->agc_n = nsamples;
+    c->agc_ref = reference;
+    c->agc_from = c->produced;          // a new GR block starts with zero history
+    c->rd_agc = c->produced;
+    ++h->chans_epoch;
+    return RCF_OK;
+}
+
+int64_t rcf_chan_read_agc(rcf_t *h, int chan_id, float *out, size_t max_samples)
+{
+    if (!h || !out) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!c->d_agc) { set_error("channel %d has no AGC", chan_id); return RCF_ESTATE; }
+    return ring_read(h, c->d_agc, sizeof(float2), c->produced, &c->rd_agc, out, max_samples);
+}
+
+int rcf_chan_agc_ring(rcf_t *h, int chan_id, void **agc_ring, size_t *capacity)
+{
+    if (!h) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;                  // (zero-copy readers order themselves on rcf_stream: nothing stays deferred)
+    FIND_CHAN(h, chan_id, c);
+    if (!c->d_agc) { set_error("channel %d has no AGC", chan_id); return RCF_ESTATE; }
+    if (agc_ring) *agc_ring = c->d_agc;
+    if (capacity) *capacity = h->out_cap;
+    return RCF_OK;
 }
 
 int rcf_chan_audio_open(rcf_t *h, int chan_id, const rcf_audio_params_t *p)
@@ -631,6 +696,7 @@ int rcf_chan_set_fm_only(rcf_t *h, int chan_id, int on)
     if (!c->is_tap) { set_error("channel %d is not a tap of a frame-major filterbank", chan_id); return RCF_EINVAL; }
     if (on) {
         if (c->audio) { set_error("channel %d carries a voice chain, which reads its IQ stream", chan_id); return RCF_ESTATE; }
+        if (c->d_agc) { set_error("channel %d carries an AGC, which reads its IQ stream", chan_id); return RCF_ESTATE; }
         for (auto &kv : h->chans)
             if (kv.second->src == chan_id) { set_error("channel %d reads channel %d's IQ stream", kv.first, chan_id); return RCF_ESTATE; }
     } else if (c->fm_only) {

@@ -11,7 +11,7 @@
 //   pfb_group_kernel_* / pfb5_group_kernel   the chunks of every member of one bank shape   (pfb.hip, pfb5.hip)
 //   fir_small_kernel / fir_bank_kernel       stage-2 channels of all members of one (D, T) class (records concatenated)
 //   tap_finalize_group_kernel  the tapped bins of every member                               (tapfin.hip)
-//   disc / fm_fir / rot_fill   records concatenated
+//   disc / fm_fir / agc / rot_fill   records concatenated
 //   gather_rings_kernel        the read: new output of any channels of any members -> pinned host memory, one launch
 // What is not concatenable (matrix-core banks with their per-handle tap slabs, voice chains, scans, banks that still see
 // zero history) follows per member on the same stream, in dependency order.  The bits are those of the members run alone.
@@ -182,11 +182,12 @@ int rcfx::group_process(rcf_group *g, const std::vector<GroupItem> &items, int f
             kv.second.dims.n_chans = (int)kv.second.recs.size();
             if (!ga.put(kv.second.recs, &kv.second.dev)) return oom();
         }
-    // discriminators, symbol filters, exact-rotator fills
+    // discriminators, symbol filters, AGCs, exact-rotator fills
     std::vector<DiscLaunch> discs;
     std::vector<FmFirLaunch> symf;
+    std::vector<AgcLaunch> agcf;
     std::vector<RotFill> rots;
-    int disc_max_n = 0, symf_max_n = 0;
+    int disc_max_n = 0, symf_max_n = 0, agcf_max_n = 0, agcf_max_ns = 0;
     for (auto &bp : plans) {
         for (DiscJob &dj : bp->disc_jobs) {
             discs.insert(discs.end(), dj.host.begin(), dj.host.end());
@@ -194,13 +195,17 @@ int rcfx::group_process(rcf_group *g, const std::vector<GroupItem> &items, int f
         }
         symf.insert(symf.end(), bp->symf.begin(), bp->symf.end());
         symf_max_n = std::max(symf_max_n, bp->symf_max_n);
+        agcf.insert(agcf.end(), bp->agcf.begin(), bp->agcf.end());
+        agcf_max_n = std::max(agcf_max_n, bp->agcf_max_n);
+        agcf_max_ns = std::max(agcf_max_ns, bp->agcf_max_ns);
         rots.insert(rots.end(), bp->rot_fills.begin(), bp->rot_fills.end());
     }
     const DiscLaunch *d_discs = nullptr;
     const FmFirLaunch *d_symf = nullptr;
+    const AgcLaunch *d_agcf = nullptr;
     const RotFill *d_rots = nullptr;
     if ((!discs.empty() && !ga.put(discs, &d_discs)) || (!symf.empty() && !ga.put(symf, &d_symf)) ||
-        (!rots.empty() && !ga.put(rots, &d_rots)))
+        (!agcf.empty() && !ga.put(agcf, &d_agcf)) || (!rots.empty() && !ga.put(rots, &d_rots)))
         return oom();
 
     // ---- 5. the prep launch's records, last: one of them uploads everything put so far
@@ -321,6 +326,7 @@ int rcfx::group_process(rcf_group *g, const std::vector<GroupItem> &items, int f
     for (size_t d = 1; d <= (size_t)max_depth; ++d) launch_depth(d, RCF_T_FIR_DERIVED);
     if (d_discs) { Timed t(h0, RCF_T_DISC); launch_discriminator(d_discs, (int)discs.size(), disc_max_n, h0->ring_mask, h0->d_atan, st); }
     if (d_symf) { Timed t(h0, RCF_T_DISC); launch_fm_fir(d_symf, (int)symf.size(), symf_max_n, h0->ring_mask, st); }
+    if (d_agcf) { Timed t(h0, RCF_T_DISC); launch_agc(d_agcf, (int)agcf.size(), agcf_max_n, agcf_max_ns, h0->ring_mask, st); }
     for (size_t i = 0; i < NI; ++i) {
         rcf_t *h = g->members[(size_t)items[i].m];
         BlockPlan &bp = *plans[i];
@@ -371,10 +377,11 @@ int resolve_read(rcf_group *g, int what, int member, int chan_id, size_t cap_eac
     if (c->many_stamp == stamps[(size_t)member]) { count = RCF_EINVAL; return 0; }     // listed twice
     c->many_stamp = stamps[(size_t)member];
     if (what == RCF_READ_IQ && c->fm_only) { count = RCF_ESTATE; return 0; }           // discriminator only
+    if (what == RCF_READ_AGC && !c->d_agc) { count = RCF_ESTATE; return 0; }           // no AGC on this channel
     it.h = h;
     it.c = c;
-    it.cur = what == RCF_READ_IQ ? &c->rd_iq : &c->rd_fm;
-    it.ring = what == RCF_READ_IQ ? (const void *)c->d_iq : (const void *)c->d_fm;
+    it.cur = chan_read_cursor(c, what);
+    it.ring = chan_read_ring(c, what);
     int64_t avail = c->produced - *it.cur;
     if (avail > 0 && (size_t)avail > h->out_cap) {              // reader lagged: oldest samples are gone
         *it.cur = c->produced - (int64_t)h->out_cap;
@@ -532,7 +539,7 @@ int rcf_group_sync(rcf_group_t *g)
 int rcf_group_read_many(rcf_group_t *g, int what, const int *members, const int *chan_ids, int n, float gain, void *out,
                         size_t cap_each, int64_t *counts)
 {
-    if (!g || !members || !chan_ids || !out || !counts || n < 0 || (what != RCF_READ_IQ && what != RCF_READ_FM)) {
+    if (!g || !members || !chan_ids || !out || !counts || n < 0 || (what != RCF_READ_IQ && what != RCF_READ_FM && what != RCF_READ_AGC)) {
         set_error("bad batched read arguments");
         return RCF_EINVAL;
     }
@@ -540,7 +547,7 @@ int rcf_group_read_many(rcf_group_t *g, int what, const int *members, const int 
     MemberLocks ml(g->members);
     RCF_HIP(hipSetDevice(g->device));
     for (rcf_t *h : g->members) flush_lagged(h);            // (a member that was fed on its own meanwhile)
-    const size_t elem = what == RCF_READ_IQ ? sizeof(float2) : sizeof(float);
+    const size_t elem = what == RCF_READ_FM ? sizeof(float) : sizeof(float2);
     const uint32_t ew = (uint32_t)(elem / 4);
     std::vector<uint64_t> stamps(g->members.size());
     for (size_t m = 0; m < g->members.size(); ++m) stamps[m] = ++g->members[m]->many_stamp;

@@ -242,6 +242,19 @@ struct FmFirLaunch {
     int32_t pad_;
 };
 void launch_fm_fir(const FmFirLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
+// GNU Radio's feedforward_agc_cc(nsamples, reference) on a channel's IQ ring (agc.hip; the P25 CQPSK front half,
+// p25_control_demod.py:149): out[n] = (R / max(1e-4, max env(x[n-N+1 .. n]))) * x[n-N+1], n relative index
+struct AgcLaunch {
+    const float2 *iq_ring;
+    float2 *agc_ring;
+    int64_t n_lo;            // first relative output index
+    int64_t n_first;         // inputs before this index count as zero (the stage's start)
+    float reference;         // R
+    int32_t nsamples;        // N, 1 .. 4096
+    int32_t n_k;
+    int32_t pad_;
+};
+void launch_agc(const AgcLaunch *d_items, int n_items, int max_n_k, int max_nsamples, uint64_t ring_mask, hipStream_t s);
 // mean of gain * fm over the last `window` samples ending at n_end (exclusive), one workgroup
 void launch_fm_level(const float *fm_ring, int64_t n_end, int window, float gain, uint64_t ring_mask, float *d_out,
                      hipStream_t s);

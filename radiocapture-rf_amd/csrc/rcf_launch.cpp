@@ -28,6 +28,7 @@ int launch_plan(rcf_t *h, BlockPlan &bp)
     const TapLaunch *d_tap_list = bp.d_tap_list;
     const RotFill *d_rot_fills = bp.d_rot_fills;
     const FmFirLaunch *d_symf = bp.d_symf;
+    const AgcLaunch *d_agcf = bp.d_agcf;
     const AudioLaunch *d_audf = bp.d_audf;
     const int symf_max_n = bp.symf_max_n, audf_max_n = bp.audf_max_n, audf_num = bp.audf_num, audf_den = bp.audf_den;
 
@@ -53,7 +54,7 @@ int launch_plan(rcf_t *h, BlockPlan &bp)
     // ... and this block's own: ONE small-T job on the bank's bins, nothing that consumes its outputs within the block
     FirJob *lag_job = nullptr;
     if (h->lag_enabled && carry && fir_by_depth.size() == 2 && fir_by_depth[1].size() == 1 && fir_by_depth[1][0].dims.small &&
-        fir_by_depth[1][0].dev && fir_by_depth[1][0].bank_src && !d_symf && !d_audf && (size_t)pl.n_frames * 2 + pfb_reach <= h->out_cap)
+        fir_by_depth[1][0].dev && fir_by_depth[1][0].bank_src && !d_symf && !d_agcf && !d_audf && (size_t)pl.n_frames * 2 + pfb_reach <= h->out_cap)
         lag_job = &fir_by_depth[1][0];
     {
         // the block's launch records host -> device, and -- in the same launch -- its history tail behind the OTHER input
@@ -120,6 +121,10 @@ int launch_plan(rcf_t *h, BlockPlan &bp)
     if (d_symf) {
         Timed t(h, RCF_T_DISC);
         launch_fm_fir(d_symf, (int)symf.size(), symf_max_n, h->ring_mask, st);
+    }
+    if (d_agcf) {
+        Timed t(h, RCF_T_DISC);
+        launch_agc(d_agcf, (int)bp.agcf.size(), bp.agcf_max_n, bp.agcf_max_ns, h->ring_mask, st);
     }
     if (d_audf) {
         Timed t(h, RCF_T_AUDIO);

@@ -59,11 +59,17 @@ const rcf_t::PlanCache &plan_cache(rcf_t *h)
         need += c.is_tap ? sizeof(TapLaunch) + 8 : 2 * sizeof(ChanLaunch) + sizeof(DiscLaunch) + sizeof(RotFill) + 12 + 128;
         n_fir += c.is_tap ? 0 : 1;
         if (c.d_sym) need += sizeof(FmFirLaunch);
+        if (c.d_agc) need += sizeof(AgcLaunch);
         if (c.audio) need += sizeof(AudioLaunch);
         pc.max_depth = std::max(pc.max_depth, c.depth);
         if (c.src < 0 && (pc.min_d0 == 0 || c.D < pc.min_d0)) pc.min_d0 = c.D;
         if (c.audio) pc.max_reach = std::max<size_t>(pc.max_reach, (size_t)std::max(std::max(c.audio->n_lpf, c.audio->n_hpf), c.audio->nt_rs));
         if (c.d_sym) { size_t &own = pc.reach_x[c.id]; own = std::max<size_t>(own, std::max<size_t>(1, (size_t)c.sym_ntaps)); }
+        if (c.d_agc) {                                // the AGC's window reaches N - 1 samples behind the block's first output
+            size_t &own = pc.reach_x[c.id];
+            own = std::max<size_t>(own, std::max<size_t>(1, (size_t)c.agc_n - 1));
+            pc.max_reach = std::max(pc.max_reach, own);
+        }
         if (c.src >= RCF_SRC_PFB_BIN0) {              // (the bank's ring: one entry for all of its consumers, set after the loop)
             pfb_reach = std::max<size_t>(pfb_reach, (size_t)(c.T - 1 + c.D));
         } else if (c.src >= 0) {
@@ -199,7 +205,7 @@ int plan_pfb(rcf_t *h, BlockPlan &bp)
     return RCF_OK;
 }
 
-// one channel's launch records (FIR / tap, discriminator, symbol filter, voice chain, exact rotator) and the advance of
+// one channel's launch records (FIR / tap, discriminator, symbol filter, AGC, voice chain, exact rotator) and the advance of
 // its state.  Returns RCF_OK also when the channel has nothing to do in this block.
 int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c, int D)
 {
@@ -215,6 +221,7 @@ int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c, int D)
     auto &tap_bins = bp.tap_bins;
     auto &symf = bp.symf;
     int &symf_max_n = bp.symf_max_n;
+    auto &agcf = bp.agcf;
     auto &audf = bp.audf;
     int &audf_max_n = bp.audf_max_n;
     double &audf_ratio = bp.audf_ratio;
@@ -312,6 +319,21 @@ int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c, int D)
         fl.n_k = (int32_t)(dl.n_lo + dl.n_k - fl.n_lo);
         if (fl.n_k > 0) symf.push_back(fl);
         symf_max_n = std::max(symf_max_n, (int)cnt);
+    }
+    if (c->d_agc) {
+        AgcLaunch al{};
+        al.iq_ring = c->d_iq;
+        al.agc_ring = c->d_agc;
+        al.reference = c->agc_ref;
+        al.nsamples = c->agc_n;
+        al.n_lo = std::max(dl.n_lo, c->agc_from);
+        al.n_first = c->agc_from;
+        al.n_k = (int32_t)(dl.n_lo + dl.n_k - al.n_lo);
+        if (al.n_k > 0) {
+            agcf.push_back(al);
+            bp.agcf_max_n = std::max(bp.agcf_max_n, (int)al.n_k);
+            bp.agcf_max_ns = std::max(bp.agcf_max_ns, c->agc_n);
+        }
     }
     if (c->audio) {
         Chan::Audio &au = *c->audio;
@@ -535,6 +557,7 @@ int plan_tail(rcf_t *h, BlockPlan &bp)
     auto &tap_bins = bp.tap_bins;
     auto &rot_fills = bp.rot_fills;
     auto &symf = bp.symf;
+    auto &agcf = bp.agcf;
     auto &audf = bp.audf;
     PfbLaunch &pl = bp.pl;
     const bool run_pfb = bp.run_pfb;
@@ -592,9 +615,10 @@ int plan_tail(rcf_t *h, BlockPlan &bp)
         pl.tap_pitch = (int32_t)mat_pitch;
         pl.n_taps = (int32_t)tap_list.size();
     }
-    // (a group's block: the exact-rotator fills and the symbol filters of all members go out as one launch each)
+    // (a group's block: the exact-rotator fills, the symbol filters and the AGCs of all members go out as one launch each)
     if (!bp.defer && !rot_fills.empty() && !ar.put(rot_fills, &d_rot_fills)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
     if (!bp.defer && !symf.empty() && !ar.put(symf, &d_symf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
+    if (!bp.defer && !agcf.empty() && !ar.put(agcf, &bp.d_agcf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
     if (!audf.empty() && !ar.put(audf, &d_audf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
     return RCF_OK;
 }

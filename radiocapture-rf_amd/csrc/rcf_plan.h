@@ -51,10 +51,10 @@ struct BlockPlan {
 
     // how far back every consumer of a ring reaches beyond the block's new samples (a block's writes must not
     // overwrite what the same block's readers still need): derived channels T - 1 + D of source output, the
-    // discriminator one sample, the symbol filter its taps.  Every ring reaches back 1 (the discriminator); only
-    // sources of other channels and channels with a symbol filter reach further -- the map holds just those (with
-    // 131072 plain wideband channels it stays empty: a std::map entry per channel and block was a tenth of the
-    // host's schedule time).
+    // discriminator one sample, the symbol filter its taps, the AGC N - 1 IQ samples.  Every ring reaches back 1 (the
+    // discriminator); only sources of other channels and channels with a symbol filter or an AGC reach further -- the
+    // map holds just those (with 131072 plain wideband channels it stays empty: a std::map entry per channel and block
+    // was a tenth of the host's schedule time).
     const std::unordered_map<int, size_t> *reach_x = nullptr;   // source id (channel id / RCF_SRC_PFB_BIN0) -> samples (the handle's PlanCache)
     int max_depth = 0;
     int min_d0 = 0;                    // smallest decimation among the channels on the wideband stream (0: none)
@@ -69,6 +69,8 @@ struct BlockPlan {
     std::vector<DiscJob> disc_jobs;
     std::vector<FmFirLaunch> symf;     // symbol filters, all channels in one launch
     int symf_max_n = 0;
+    std::vector<AgcLaunch> agcf;       // feedforward AGCs, all channels in one launch
+    int agcf_max_n = 0, agcf_max_ns = 0;
     std::vector<RotFill> rot_fills;    // exact rotator: one record per launched channel, one launch before the FIRs
     std::vector<TapLaunch> tap_list;   // filterbank taps: copied out by the bank's kernel, finished by tap_finalize
     std::vector<int32_t> tap_bins;
@@ -84,6 +86,7 @@ struct BlockPlan {
     std::vector<TapLaunch> tap_ordered;
     const RotFill *d_rot_fills = nullptr;
     const FmFirLaunch *d_symf = nullptr;
+    const AgcLaunch *d_agcf = nullptr;
     const AudioLaunch *d_audf = nullptr;
     bool defer = false;                // a member of a group: mergeable records stay on the host (FirJob::host, DiscJob::host)
     bool history_done = false;         // launch_plan copied the history tail together with the launch records

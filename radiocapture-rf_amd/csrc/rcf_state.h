@@ -54,6 +54,7 @@ struct Chan {
     // exact rotator (rcf_set_rotator): phase ring + {phase, counter} state, one pool slice
     float2 *d_rot = nullptr;
     float *d_sym = nullptr;       // optional real FIR over gain * fm (P25 symbol filter), below
+    float2 *d_agc = nullptr;      // optional feedforward AGC over the IQ stream (P25 CQPSK front half), below
     // rotator model
     double extra_dangle = 0, extra_dlogmag = 0;   // added to the increment's own angle / log magnitude (filterbank taps)
     double dangle = 0, dlogmag = 0;
@@ -84,6 +85,10 @@ struct Chan {
     float sym_gain = 1.f;
     int64_t sym_from = 0;         // first relative output index the filter is defined for
     int64_t rd_sym = 0;
+    int agc_n = 0;                // feedforward_agc_cc(nsamples = agc_n, reference = agc_ref) (rcf_chan_agc)
+    float agc_ref = 1.f;
+    int64_t agc_from = 0;         // first relative output index the AGC is defined for (zero history before it)
+    int64_t rd_agc = 0;
     uint64_t many_stamp = 0;      // the rcf_chan_read_many call that last listed this channel
     double src_rate = 0, offset_hz = 0;
     uint64_t taps_version = 0;    // bumped whenever d_ctaps changes (bank-matrix cache key)
@@ -189,8 +194,8 @@ struct rcf {
     struct rcf_group *group = nullptr;
     hipStream_t own_stream = nullptr;
     std::map<int, std::unique_ptr<Chan>> chans;
-    uint64_t chans_epoch = 0;     // bumped whenever a channel is opened or closed or gains / loses a symbol filter or voice
-                                  // chain (cached Chan pointers: the pump's; the cached arena need below)
+    uint64_t chans_epoch = 0;     // bumped whenever a channel is opened or closed or gains / loses a symbol filter, AGC or
+                                  // voice chain (cached Chan pointers: the pump's; the cached arena need below)
     // What planning a block needs to know about the channel SET (not their counters), valid while epoch == chans_epoch:
     // the summary plan_arena() used to rebuild from a walk over every channel, and the (depth, D, T) classes plan_block()
     // used to re-bucket -- three passes of pointer chasing per block (20 us of a 30 us plan for a front-end with 256
@@ -334,6 +339,8 @@ int64_t ring_read_enqueue(rcf_t *h, const void *ring, size_t elem, int64_t produ
                           size_t max_items);
 int64_t ring_read(rcf_t *h, const void *ring, size_t elem, int64_t produced, int64_t *cursor, void *out,
                   size_t max_items);
+int64_t *chan_read_cursor(Chan *c, int what);             // RCF_READ_IQ / RCF_READ_FM / RCF_READ_AGC
+const void *chan_read_ring(const Chan *c, int what);
 
 // ---------------------------------------------------------------- rcf_plan.cpp / rcf_launch.cpp
 int process_block(rcf_t *h, size_t n);

@@ -33,6 +33,7 @@ SYMBOLS = [
     "rcf_scan_result", "rcf_scan_frames_done", "rcf_scan_result_device", "rcf_find_peaks",
     "rcf_peak_frequency", "rcf_scan_find_peaks", "rcf_timing_enable", "rcf_timing_read",
     "rcf_ingest_write", "rcf_push_raw", "rcf_chan_fm_filter", "rcf_chan_read_sym", "rcf_chan_fm_level",
+    "rcf_chan_agc", "rcf_chan_read_agc", "rcf_chan_agc_ring",
     "rcf_design_firdes", "rcf_design_optfir_low_pass", "rcf_design_fm_deemph", "rcf_design_resampler", "rcf_chan_audio_open",
     "rcf_chan_audio_close", "rcf_chan_audio_produced", "rcf_chan_read_audio",
     "rcf_host_alloc", "rcf_host_free", "rcf_comm_unique_id", "rcf_comm_init", "rcf_comm_destroy", "rcf_comm_size",
@@ -42,7 +43,7 @@ SYMBOLS = [
     "rcf_group_sync", "rcf_pump_start", "rcf_pump_stats", "rcf_pump_written", "rcf_pump_read", "rcf_pump_read_many", "rcf_pump_subscribe", "rcf_pump_unsubscribe", "rcf_pump_stop",
 ]
 FMT_CF32, FMT_U8, FMT_S8, FMT_S16 = 0, 1, 2, 3
-READ_IQ, READ_FM = 0, 1
+READ_IQ, READ_FM, READ_AGC = 0, 1, 2
 T_FIR, T_PFB, T_FIR_DERIVED, T_DISC, T_SCAN_FFT, T_SCAN_MOVSUM, T_HISTORY, T_FIR_MFMA, T_AUDIO, T_TAPS = range(10)
 
 
@@ -122,6 +123,9 @@ def lib():
         "rcf_push_raw": (C.c_int, [vp, vp, sz, C.c_int, C.c_float, C.c_float]),
         "rcf_chan_fm_filter": (C.c_int, [vp, C.c_int, C.c_float, fp, C.c_int]),
         "rcf_chan_read_sym": (i64, [vp, C.c_int, fp, sz]),
+        "rcf_chan_agc": (C.c_int, [vp, C.c_int, C.c_int, C.c_float]),
+        "rcf_chan_read_agc": (i64, [vp, C.c_int, fp, sz]),
+        "rcf_chan_agc_ring": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]),
         "rcf_chan_fm_level": (C.c_int, [vp, C.c_int, C.c_float, C.c_int, fp]),
         "rcf_design_firdes": (C.c_int, [C.c_int] + [C.c_double] * 4 + [C.c_int, C.c_double, fp, C.c_int]),
         "rcf_design_optfir_low_pass": (C.c_int, [C.c_double] * 6 + [fp, C.c_int]),
@@ -202,6 +206,15 @@ def lib():
         fn.argtypes = args
     _lib = L
     return L
+
+
+def _read_what(what):
+    """the batched readers' `what`: "iq", "agc", anything else the discriminator (as it always was)"""
+    return READ_IQ if what == "iq" else READ_AGC if what == "agc" else READ_FM
+
+
+def _read_dtype(what):
+    return np.float32 if _read_what(what) == READ_FM else np.complex64
 
 
 def _check(rc):
@@ -537,13 +550,13 @@ class Frontend:
         (views into `out`, a [len(cids), cap_each] complex64 / float32 array -- pass a PinnedArray's for overlapping
         copies), None where the channel no longer exists"""
         n = len(cids)
-        dt = np.complex64 if what == "iq" else np.float32
+        dt = _read_dtype(what)
         if out is None:
             out = np.empty((max(n, 1), cap_each), dtype=dt)
         out = out.reshape(-1, cap_each)
         ids = (C.c_int * max(n, 1))(*[int(c) for c in cids])
         counts = (C.c_int64 * max(n, 1))()
-        _check(lib().rcf_chan_read_many(self._h, 0 if what == "iq" else 1, ids, n, float(gain),
+        _check(lib().rcf_chan_read_many(self._h, _read_what(what), ids, n, float(gain),
                                         out.ctypes.data_as(C.c_void_p), int(cap_each), counts))
         return [None if counts[i] < 0 else out[i, :counts[i]] for i in range(n)]
 
@@ -553,14 +566,14 @@ class Frontend:
         counts an int64 array (negative: that channel is gone), out the [len(cids), cap_each] array the samples are in.
         Costs ~10 us of interpreter time per call instead of ~1 us per channel."""
         n = len(cids)
-        dt = np.complex64 if what == "iq" else np.float32
+        dt = _read_dtype(what)
         if out is None:
             out = np.empty((max(n, 1), cap_each), dtype=dt)
         out2 = out.reshape(-1, cap_each)
         ids = (C.c_int * max(n, 1))(*[int(c) for c in cids])
         counts = np.zeros(max(n, 1), dtype=np.int64)
         f = lib().rcf_chan_read_many
-        args = (self._h, 0 if what == "iq" else 1, ids, n, C.c_float(float(gain)), out2.ctypes.data_as(C.c_void_p),
+        args = (self._h, _read_what(what), ids, n, C.c_float(float(gain)), out2.ctypes.data_as(C.c_void_p),
                 C.c_size_t(int(cap_each)), counts.ctypes.data_as(C.POINTER(C.c_int64)))
 
         def call():
@@ -577,6 +590,22 @@ class Frontend:
         out = np.empty(max_samples, dtype=np.float32)
         n = _check(lib().rcf_chan_read_sym(self._h, cid, _fp(out), max_samples))
         return out[:n].copy()
+
+    def chan_agc(self, cid, nsamples=1024, reference=1.0):
+        """analog.feedforward_agc_cc(nsamples, reference) on the channel's IQ (rcf_chan_agc; p25_control_demod.py:149),
+        starting with zero history at the channel's next output; nsamples=0 switches it off"""
+        _check(lib().rcf_chan_agc(self._h, cid, int(nsamples), float(reference)))
+
+    def chan_read_agc(self, cid, max_samples=1 << 20) -> np.ndarray:
+        out = np.empty(max_samples, dtype=np.complex64)
+        n = _check(lib().rcf_chan_read_agc(self._h, cid, _fp(out.view(np.float32)), max_samples))
+        return out[:n].copy()
+
+    def chan_agc_ring(self, cid):
+        """(device pointer, capacity) of the channel's cf32 AGC ring (rcf_chan_agc_ring)"""
+        p, cap = C.c_void_p(), C.c_size_t()
+        _check(lib().rcf_chan_agc_ring(self._h, cid, C.byref(p), C.byref(cap)))
+        return p.value, cap.value
 
     def chan_fm_level(self, cid, gain, window=10000) -> float:
         v = C.c_float()
@@ -737,12 +766,12 @@ class Group:
         """pairs: [(member index, channel id), ...] -> list of arrays (None where the channel is gone), ONE gather launch
         and one synchronisation for all of them (rcf_group_read_many)"""
         n = len(pairs)
-        dt = np.complex64 if what == "iq" else np.float32
+        dt = _read_dtype(what)
         out = np.empty((max(n, 1), cap_each), dtype=dt)
         ms = (C.c_int * max(n, 1))(*[int(m) for m, _ in pairs])
         cs = (C.c_int * max(n, 1))(*[int(c) for _, c in pairs])
         counts = (C.c_int64 * max(n, 1))()
-        _check(lib().rcf_group_read_many(self._g, READ_IQ if what == "iq" else READ_FM, ms, cs, n, float(gain),
+        _check(lib().rcf_group_read_many(self._g, _read_what(what), ms, cs, n, float(gain),
                                          out.ctypes.data_as(C.c_void_p), int(cap_each), counts))
         return [None if counts[i] < 0 else out[i, :counts[i]].copy() for i in range(n)]
 

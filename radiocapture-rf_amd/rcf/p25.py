@@ -1,0 +1,63 @@
+"""The P25 control / voice demodulators' front halves behind a channel, built on the GPU (p25_control_demod.py:105-161,
+logging_receiver.py:278-332).  Both modulations start from the same pre-filter and split right after it:
+
+  C4FM   quadrature_demod_cf(channel_rate / (2 pi 600)) -> fir_filter_fff(1, (1/sps,)*sps) -> op25 fsk4_demod_ff
+  CQPSK  multiply_const_cc(1.0) -> feedforward_agc_cc(1024, 1.0) -> multiply_const_cc(1.0) -> op25 gardner_costas_cc
+
+The GPU half stops before the sequential op25 loop (fsk4_demod_ff, gardner_costas_cc): a demod reads the symbol
+filter's output (chan_read_sym) or the AGC's (chan_read_agc) and runs that loop itself."""
+import math
+
+from . import native
+
+SYMBOL_RATE = 4800           # p25_control_demod.py:82 (phase 1; logging_receiver.py:286 runs phase 2 at 6000)
+SYMBOL_DEVIATION = 600.0     # p25_control_demod.py:116
+
+
+def prefilter_taps(channel_rate):
+    """firdes.low_pass_2(1.0, 2 cr, cr / 2, 500, 30, WIN_BLACKMAN) (p25_control_demod.py:106-107): 69 taps at cr = 12500"""
+    rate = 2 * channel_rate
+    return native.design_low_pass_2(1.0, rate, channel_rate / 2.0, 500.0, 30.0, native.WIN_BLACKMAN)
+
+
+def fm_gain(channel_rate):
+    """quadrature_demod_cf gain of the C4FM path: 2 cr / (2 pi symbol_deviation) (p25_control_demod.py:120)"""
+    return 2 * channel_rate / (2.0 * math.pi * SYMBOL_DEVIATION)
+
+
+def symbol_taps(channel_rate, symbol_rate=SYMBOL_RATE):
+    """(1/sps,)*sps with sps = 2 cr // symbol_rate (p25_control_demod.py:129-131): five taps of 0.2 at cr = 12500"""
+    sps = (2 * channel_rate) // symbol_rate
+    return [1.0 / sps] * sps
+
+
+def _prefilter(fe, chan_id, channel_rate):
+    # freq_xlating_fir_filter_ccc(1, taps, 0, 2 cr) on the channel's output (p25_control_demod.py:108)
+    return fe.chan_open_taps(chan_id, 1, prefilter_taps(channel_rate), 0.0)
+
+
+def cqpsk_front_half(fe, chan_id, channel_rate, nsamples=1024, reference=1.0):
+    """the CQPSK (LSM / simulcast) front half on channel `chan_id` of Frontend `fe` (rate 2 channel_rate): the chained
+    pre-filter, then feedforward_agc_cc(1024, 1.0) (p25_control_demod.py:146-149).  Returns the pre-filter channel's
+    id: chan_read_agc on it gives what gardner_costas_cc consumes."""
+    cid = _prefilter(fe, chan_id, channel_rate)
+    fe.chan_agc(cid, nsamples, reference)
+    return cid
+
+
+def c4fm_front_half(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE):
+    """the C4FM front half on channel `chan_id` of Frontend `fe`: the chained pre-filter, its discriminator and the
+    boxcar symbol filter (p25_control_demod.py:118-133).  Returns the pre-filter channel's id: chan_read_sym on it gives
+    what fsk4_demod_ff consumes."""
+    cid = _prefilter(fe, chan_id, channel_rate)
+    fe.chan_fm_filter(cid, fm_gain(channel_rate), symbol_taps(channel_rate, symbol_rate))
+    return cid
+
+
+def front_half(fe, chan_id, channel_rate, modulation):
+    """the front half a demod of `modulation` ('C4FM' / 'CQPSK') runs, as p25_control_demod.py:118,136 picks it"""
+    if modulation == "C4FM":
+        return c4fm_front_half(fe, chan_id, channel_rate)
+    if modulation == "CQPSK":
+        return cqpsk_front_half(fe, chan_id, channel_rate)
+    raise ValueError("unknown P25 modulation %r" % (modulation,))
