@@ -103,9 +103,9 @@ void launch_copy8(void *dst, const void *src, size_t bytes, hipStream_t s)
                        static_cast<const unsigned long long *>(src), n8);
 }
 
-// rcf_chan_read_many: the new samples of many channel rings packed back to back into ONE staging buffer (pinned host
-// memory the device writes across PCIe) -- one launch and one synchronisation per egress pass instead of a device
-// round trip per channel.  Records live in pinned host memory too.  Units: 4-byte words.
+// host_read (every host read of a channel, bank or voice-chain ring): the new samples of many rings packed back to back into
+// ONE staging buffer (pinned host memory the device writes across PCIe) -- one launch and one synchronisation per egress
+// pass instead of a device round trip per channel.  Records live in pinned host memory too.  Units: 4-byte words.
 // A BOUNDED grid, like group_prep_kernel's and for the same reason: its stores cross PCIe, a workgroup whose stores wait for the
 // link holds its CU slot, and launched one workgroup per (record, part) -- tens of thousands for a group's read -- it
 // starved the filterbank launches of the other groups (rocprof of the real-time leg: a 20 us pfb5 launch averaging 183 us).
@@ -116,7 +116,7 @@ static __global__ __launch_bounds__(256) void gather_rings_kernel(const GatherRe
     for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
         const GatherRec r = recs[item / parts];
         const uint32_t stride = parts * 256;
-        // the destination is either linear (dst_mask_w = ~0: rows packed back to back, rcf_chan_read_many) or a ring of its
+        // the destination is either linear (dst_mask_w = ~0: rows packed back to back, host_read) or a ring of its
         // own (the real-time pump's per-channel host rings: dst_w = the ring's first word, dst_pos_w where this segment starts)
         for (uint32_t w = (item % parts) * 256 + threadIdx.x; w < r.n_w; w += stride) {
             const uint32_t i = (r.pos_w + w) & r.mask_w;
@@ -134,20 +134,6 @@ void launch_gather_rings(const GatherRec *d_recs, int n_recs, uint32_t *d_dst, u
     const unsigned parts = std::min<unsigned>((max_words + 255) / 256, 16);
     const unsigned items = parts * (unsigned)n_recs;
     hipLaunchKernelGGL(gather_rings_kernel, dim3(std::min(items, cap)), dim3(256), 0, s, d_recs, d_dst, (uint32_t)n_recs, parts);
-}
-
-// one bin's discriminator samples out of a frame-major ring of floats (rcf_pfb_read_fm): dst[i] = gain * base[((first + i) & mask) stride]
-static __global__ void gather_f32_kernel(const float *__restrict__ base, uint64_t mask, int64_t stride, int64_t first, float gain,
-                                         float *__restrict__ dst, size_t n)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = __fmul_rn(gain, base[((uint64_t)(first + (int64_t)i) & mask) * (uint64_t)stride]);
-}
-
-void launch_gather_f32(const float *base, uint64_t mask, int64_t stride, int64_t first, float gain, float *dst, size_t n, hipStream_t s)
-{
-    if (n == 0) return;
-    hipLaunchKernelGGL(gather_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, base, mask, stride, first, gain, dst, n);
 }
 
 void launch_gather_view(const StreamView &v, int64_t first, float2 *dst, size_t n, hipStream_t s)

@@ -3,6 +3,15 @@
 
 namespace rcfx {
 
+void pfb_release(rcf_t *h)
+{
+    Pfb &p = h->pfb;
+    for (void *q : {(void *)p.d_ptaps, (void *)p.d_tw, (void *)p.d_bins, (void *)p.d_fm, (void *)p.d_fm_inc, (void *)p.d_fm_edge,
+                    (void *)p.d_fm_flag, (void *)p.d_fm_err})
+        bury(h, q);
+    p = Pfb();
+}
+
 // The rotator increment's angle a discriminator-only channel on bin k of the bank carries (Chan::dangle of a tap opened
 // with rcf_pfb_tap_open(bin, gr_phase): rcf_chan.cpp) -- for every bin at once, uploaded and turned into float32 phasors
 // on the device (launch_pfb5_fm_inc: tap_finalize's own expression)
@@ -104,9 +113,7 @@ int rcf_pfb_close(rcf_t *h)
         if (it->second->src >= RCF_SRC_PFB_BIN0) { free_channel(h, it->second.get()); it = h->chans.erase(it); }
         else ++it;
     }
-    bury(h, p.d_ptaps); bury(h, p.d_tw); bury(h, p.d_bins); bury(h, p.d_stage);
-    bury(h, p.d_fm); bury(h, p.d_fm_inc); bury(h, p.d_fm_stage); bury(h, p.d_fm_edge); bury(h, p.d_fm_flag); bury(h, p.d_fm_err);
-    p = Pfb();
+    pfb_release(h);
     ++h->chans_epoch;
     return RCF_OK;
 }
@@ -143,18 +150,18 @@ int64_t rcf_pfb_read_bin(rcf_t *h, int bin, float *out, size_t max_samples)
     Pfb &p = h->pfb;
     if (!p.open || bin < 0 || bin >= p.NB) { set_error("no such PFB bin %d", bin); return RCF_EINVAL; }
     if (p.fm_mode == 2) { set_error("the bank writes its discriminator ring only (rcf_pfb_fm_enable mode 2): no bins to read"); return RCF_ESTATE; }
-    // one bin out of the bank's ring (tiled or frame-major): gather its unread samples into a contiguous staging buffer
-    int64_t avail = p.produced - p.rd[bin];
-    if (avail <= 0 || max_samples == 0) return 0;
-    if ((size_t)avail > h->out_cap) { p.rd[bin] = p.produced - (int64_t)h->out_cap; avail = (int64_t)h->out_cap; }
-    const int64_t n = std::min<int64_t>(avail, (int64_t)max_samples);
-    if (!p.d_stage) RCF_HIP(hipMalloc(&p.d_stage, sizeof(float2) * h->out_cap));
+    // one bin out of the bank's ring (tiled or frame-major -- not a strided ring: gather_view_kernel, not host_read) into the
+    // handle's pinned staging
+    const int64_t n = lag_clamp(h, &p.rd[bin], p.produced, p.produced, (int64_t)max_samples);
+    if (n == 0) return 0;
     SrcRange sr{};
     if (!source_range(h, RCF_SRC_PFB_BIN0 + bin, 0, 0, &sr)) return RCF_ESTATE;
-    launch_gather_view(sr.view, p.rd[bin], p.d_stage, (size_t)n, h->stream);
-    RCF_HIP(hipMemcpyAsync(out, p.d_stage, sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    const int rc = h->host_stage.ensure(sizeof(float2) * (size_t)n, h->stream);
+    if (rc != RCF_OK) return rc;
+    launch_gather_view(sr.view, p.rd[bin], reinterpret_cast<float2 *>(h->host_stage.d), (size_t)n, h->stream);
     RCF_HIP(hipStreamSynchronize(h->stream));
     free_graveyard_idle(h);
+    std::memcpy(out, h->host_stage.h, sizeof(float2) * (size_t)n);
     p.rd[bin] += n;
     return n;
 }
@@ -247,23 +254,11 @@ int64_t rcf_pfb_read_fm(rcf_t *h, int bin, float gain, float *out, size_t max_sa
     if (set_dev(h)) return RCF_EHIP;
     Pfb &p = h->pfb;
     if (!p.open || !p.d_fm || bin < 0 || bin >= p.NB) { set_error("no discriminator ring / no such bin %d", bin); return RCF_EINVAL; }
-    int64_t &rd = p.rd_fm[(size_t)bin];
+    // bin `bin` of the frame-major ring of floats: a stride of NB words.  While the discriminator is off, readers stop at the
+    // frame it was switched off at.
     const int64_t end = p.fm_mode ? p.produced : p.fm_until;
-    int64_t avail = end - rd;
-    if (avail <= 0 || max_samples == 0) return 0;
-    if (p.produced - rd > (int64_t)h->out_cap) {        // overwritten since: skip to the oldest frame the ring still holds
-        rd = p.produced - (int64_t)h->out_cap;
-        avail = end - rd;
-        if (avail <= 0) return 0;
-    }
-    const int64_t n = std::min<int64_t>(avail, (int64_t)max_samples);
-    if (!p.d_fm_stage) RCF_HIP(hipMalloc(&p.d_fm_stage, sizeof(float) * h->out_cap));
-    launch_gather_f32(p.d_fm + bin, h->ring_mask, p.NB, rd, gain, p.d_fm_stage, (size_t)n, h->stream);
-    RCF_HIP(hipMemcpyAsync(out, p.d_fm_stage, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    RCF_HIP(hipStreamSynchronize(h->stream));
-    free_graveyard_idle(h);
-    rd += n;
-    return n;
+    return read_one(h, RingStream{h, p.d_fm + bin, 1u, (uint32_t)p.NB, end, p.produced, &p.rd_fm[(size_t)bin]}, gain, out,
+                    max_samples);
 }
 
 int64_t rcf_pfb_fm_lost(rcf_t *h)

@@ -1,5 +1,7 @@
 // rcf_chan.cpp -- channels: lifecycle (channel.channel / set_offset / destroy of /root/reference/rc_frontend/channel.py),
-// ring reads, the P25 symbol filter and AGC, the analog voice chain, source shift.
+// the one read path of every host read, the P25 symbol filter and AGC, the analog voice chain, source shift.
+#include <atomic>
+
 #include "rcf_plan.h"
 
 namespace rcfx {
@@ -162,54 +164,118 @@ void free_channel(rcf_t *h, Chan *c)
     (void)h;
 }
 
-// queue the copies of one ring read on the handle's stream; the caller synchronises and then advances *cursor by the
-// count returned (ring_read does both for a single ring; rcf_chan_read_many batches many rings behind ONE sync)
-int64_t ring_read_enqueue(rcf_t *h, const void *ring, size_t elem, int64_t produced, int64_t *cursor, void *out,
-                          size_t max_items)
+// the stream table of a channel: RCF_READ_IQ, RCF_READ_FM, RCF_READ_AGC, kReadSym -> ring, words per item, reader, and what
+// a missing ring means
+int chan_stream(rcf_t *h, Chan *c, int kind, RingStream *s)
 {
-    int64_t avail = produced - *cursor;
-    if (avail <= 0 || max_items == 0) return 0;
-    if ((size_t)avail > h->out_cap) {           // reader lagged: oldest samples are gone
-        *cursor = produced - (int64_t)h->out_cap;
-        avail = (int64_t)h->out_cap;
-    }
-    const int64_t n = std::min<int64_t>(avail, (int64_t)max_items);
-    const size_t pos = (size_t)((uint64_t)*cursor & h->ring_mask);
-    const size_t first = std::min<size_t>((size_t)n, h->out_cap - pos);
-    const unsigned char *r = static_cast<const unsigned char *>(ring);
-    if (hipMemcpyAsync(out, r + pos * elem, first * elem, hipMemcpyDeviceToHost, h->stream) != hipSuccess) {
-        set_error("ring read failed");
-        return RCF_EHIP;
-    }
-    if ((size_t)n > first &&
-        hipMemcpyAsync(static_cast<unsigned char *>(out) + first * elem, r, ((size_t)n - first) * elem,
-                       hipMemcpyDeviceToHost, h->stream) != hipSuccess) {
-        set_error("ring read failed");
-        return RCF_EHIP;
-    }
-    return n;
+    const struct { const void *ring; uint32_t item_w; int64_t *cursor; const char *refusal; } t[4] = {
+        {c->fm_only ? nullptr : c->d_iq, 2, &c->rd_iq, "channel %d exposes its discriminator only (rcf_chan_set_fm_only)"},
+        {c->d_fm, 1, &c->rd_fm, "channel %d has no discriminator ring"},
+        {c->d_agc, 2, &c->rd_agc, "channel %d has no AGC"},
+        {c->d_sym, 1, &c->rd_sym, "channel %d has no fm filter"},
+    };
+    if (!t[kind].ring) { set_error(t[kind].refusal, c->id); return RCF_ESTATE; }
+    *s = RingStream{h, t[kind].ring, t[kind].item_w, 0u, c->produced, c->produced, t[kind].cursor};
+    return RCF_OK;
 }
 
-int64_t ring_read(rcf_t *h, const void *ring, size_t elem, int64_t produced, int64_t *cursor, void *out,
-                  size_t max_items)
+int PinnedStage::ensure(size_t need, hipStream_t stream)
 {
-    const int64_t n = ring_read_enqueue(h, ring, elem, produced, cursor, out, max_items);
-    if (n <= 0) return n;
-    if (hipStreamSynchronize(h->stream) != hipSuccess) { set_error("stream sync failed"); return RCF_EHIP; }
-    free_graveyard_idle(h);       // retuned / closed channels' old buffers: every read is a chance to release them
-    *cursor += n;
-    return n;
+    if (need <= cap) return RCF_OK;
+    if (h) { RCF_HIP(hipStreamSynchronize(stream)); release(); }
+    size_t ncap = 1 << 16;
+    while (ncap < need) ncap <<= 1;
+    void *p = nullptr, *dv = nullptr;
+    if (hipHostMalloc(&p, ncap, hipHostMallocDefault) != hipSuccess || hipHostGetDevicePointer(&dv, p, 0) != hipSuccess) {
+        if (p) (void)hipHostFree(p);
+        set_error("pinned staging of %zu bytes for the batched read failed", ncap);
+        return RCF_ENOMEM;
+    }
+    h = static_cast<unsigned char *>(p);
+    d = static_cast<unsigned char *>(dv);
+    cap = ncap;
+    return RCF_OK;
 }
 
-// the ring and reader position rcf_chan_read_many / rcf_group_read_many take for `what` (RCF_READ_*)
-int64_t *chan_read_cursor(Chan *c, int what)
+// One gather launch packs every entry's segment back to back into pinned host memory, one synchronisation, then the rows are
+// handed out.  (A device round trip per channel -- a single reader in a loop -- costs ~10 us each: 256 tapped bins of ten
+// front-ends are 25 ms per pass.)
+int host_read(PinnedStage &stage, hipStream_t stream, rcf_t *const *idle, size_t n_idle, ReadEntry *es, size_t n)
 {
-    return what == RCF_READ_IQ ? &c->rd_iq : what == RCF_READ_AGC ? &c->rd_agc : &c->rd_fm;
+    static std::atomic<uint64_t> calls{0};
+    const uint64_t stamp = ++calls;
+    uint64_t total = 0, total_w = 0;
+    uint32_t max_w = 0, n_recs = 0;
+    for (size_t i = 0; i < n; ++i) {
+        ReadEntry &e = es[i];
+        if (e.c) {
+            if (e.c->many_stamp == stamp) { *e.count = RCF_EINVAL; e.s.ring = nullptr; continue; }   // listed twice
+            e.c->many_stamp = stamp;
+        }
+        if (!e.s.ring) continue;
+        *e.count = lag_clamp(e.s.h, e.s.cursor, e.s.newest, e.s.end, e.max);
+        if (*e.count == 0) continue;
+        total += (uint64_t)*e.count;
+        total_w += (uint64_t)*e.count * e.s.item_w;
+        max_w = std::max<uint32_t>(max_w, (uint32_t)*e.count * e.s.item_w);
+        ++n_recs;
+    }
+    if (total == 0) return RCF_OK;
+    if (total_w > 0xffffffffull) { set_error("batched read of %llu items exceeds the 32-bit word range", (unsigned long long)total); return RCF_ECAP; }
+    const size_t rec_bytes = ((size_t)n_recs * sizeof(GatherRec) + 255) & ~(size_t)255;
+    const int rc = stage.ensure(rec_bytes + (size_t)total_w * 4, stream);
+    if (rc != RCF_OK) return rc;
+    GatherRec *recs = reinterpret_cast<GatherRec *>(stage.h);
+    uint32_t at_w = 0, k = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const ReadEntry &e = es[i];
+        if (!e.s.ring || *e.count == 0) continue;
+        recs[k++] = gather_rec(e.s, *e.count, at_w, 0u, ~0u, e.gain);
+        at_w += (uint32_t)*e.count * e.s.item_w;
+    }
+    launch_gather_rings(reinterpret_cast<const GatherRec *>(stage.d), (int)n_recs, reinterpret_cast<uint32_t *>(stage.d + rec_bytes),
+                        max_w, stream);
+    if (hipStreamSynchronize(stream) != hipSuccess) { set_error("stream sync failed"); return RCF_EHIP; }
+    for (size_t j = 0; j < n_idle; ++j) free_graveyard_idle(idle[j]);   // retuned / closed channels' old buffers
+    const unsigned char *src = stage.h + rec_bytes;
+    for (size_t i = 0; i < n; ++i) {
+        const ReadEntry &e = es[i];
+        if (!e.s.ring || *e.count == 0) continue;
+        const size_t bytes = (size_t)*e.count * e.s.item_w * 4;
+        std::memcpy(e.out, src, bytes);
+        src += bytes;
+        *e.s.cursor += *e.count;
+    }
+    return RCF_OK;
 }
 
-const void *chan_read_ring(const Chan *c, int what)
+int64_t read_one(rcf_t *h, const RingStream &s, float gain, void *out, size_t max_items)
 {
-    return what == RCF_READ_IQ ? (const void *)c->d_iq : what == RCF_READ_AGC ? (const void *)c->d_agc : (const void *)c->d_fm;
+    int64_t n = 0;
+    ReadEntry e{s, nullptr, gain, out, (int64_t)max_items, &n};
+    const int rc = host_read(h->host_stage, h->stream, &h, 1, &e, 1);
+    return rc != RCF_OK ? rc : n;
+}
+
+int read_many(PinnedStage &stage, hipStream_t stream, rcf_t *const *hs, size_t n_hs, const int *ms, const int *chan_ids, int n,
+              int what, float gain, void *out, size_t cap_each, int64_t *counts)
+{
+    const size_t row = cap_each * (what == RCF_READ_FM ? sizeof(float) : sizeof(float2));
+    std::vector<ReadEntry> es((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        ReadEntry &e = es[(size_t)i];
+        e.count = &counts[i];
+        const int m = ms ? ms[i] : 0;
+        if (m < 0 || (size_t)m >= n_hs) { counts[i] = RCF_EINVAL; continue; }
+        auto f = hs[m]->chans.find(chan_ids[i]);
+        if (f == hs[m]->chans.end()) { counts[i] = RCF_ENOCHAN; continue; }
+        e.c = f->second.get();
+        counts[i] = chan_stream(hs[m], e.c, what, &e.s);       // RCF_ESTATE: no such stream on this channel
+        e.gain = what == RCF_READ_FM ? gain : 1.0f;
+        e.out = static_cast<unsigned char *>(out) + (size_t)i * row;
+        e.max = (int64_t)cap_each;
+    }
+    return host_read(stage, stream, hs, n_hs, es.data(), es.size());
 }
 
 }  // namespace rcfx
@@ -317,6 +383,18 @@ int rcf_pfb_tap_open(rcf_t *h, int bin, int gr_phase, int *chan_id)
     if (it_ == (h)->chans.end()) { set_error("no such channel %d", id); return RCF_ENOCHAN; } \
     Chan *c = it_->second.get()
 
+// a single reader of a channel stream
+static int64_t chan_read_one(rcf_t *h, int chan_id, int kind, float gain, void *out, size_t max_items)
+{
+    if (!h || !out) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    RingStream s;
+    const int rc = chan_stream(h, c, kind, &s);
+    return rc != RCF_OK ? rc : read_one(h, s, gain, out, max_items);
+}
+
 int rcf_chan_set_offset(rcf_t *h, int chan_id, double offset_hz)
 {
     if (!h) return RCF_EINVAL;
@@ -370,24 +448,12 @@ int64_t rcf_chan_start(rcf_t *h, int chan_id)
 
 int64_t rcf_chan_read_iq(rcf_t *h, int chan_id, float *out, size_t max_samples)
 {
-    if (!h || !out) return RCF_EINVAL;
-    std::lock_guard<std::mutex> g(h->mu);
-    if (set_dev(h)) return RCF_EHIP;
-    FIND_CHAN(h, chan_id, c);
-    if (c->fm_only) { set_error("channel %d exposes its discriminator only (rcf_chan_set_fm_only)", chan_id); return RCF_ESTATE; }
-    return ring_read(h, c->d_iq, sizeof(float2), c->produced, &c->rd_iq, out, max_samples);
+    return chan_read_one(h, chan_id, RCF_READ_IQ, 1.0f, out, max_samples);
 }
 
 int64_t rcf_chan_read_fm(rcf_t *h, int chan_id, float gain, float *out, size_t max_samples)
 {
-    if (!h || !out) return RCF_EINVAL;
-    std::lock_guard<std::mutex> g(h->mu);
-    if (set_dev(h)) return RCF_EHIP;
-    FIND_CHAN(h, chan_id, c);
-    const int64_t n = ring_read(h, c->d_fm, sizeof(float), c->produced, &c->rd_fm, out, max_samples);
-    // quadrature_demod_cf: out = gain * fast_atan2f(...), one float32 multiply per sample
-    for (int64_t i = 0; i < n; ++i) out[i] = gain * out[i];
-    return n;
+    return chan_read_one(h, chan_id, RCF_READ_FM, gain, out, max_samples);
 }
 
 int rcf_chan_read_many(rcf_t *h, int what, const int *chan_ids, int n_chans, float gain, void *out, size_t cap_each,
@@ -399,101 +465,7 @@ int rcf_chan_read_many(rcf_t *h, int what, const int *chan_ids, int n_chans, flo
     }
     std::lock_guard<std::mutex> g(h->mu);
     if (set_dev(h)) return RCF_EHIP;
-    const size_t elem = what == RCF_READ_FM ? sizeof(float) : sizeof(float2);
-    const uint32_t ew = (uint32_t)(elem / 4);
-    // what every channel has to give, and where its reader stands
-    struct Item { Chan *c; int64_t *cur; const void *ring; int64_t n; size_t pos; };
-    std::vector<Item> items((size_t)n_chans);
-    size_t total = 0;
-    uint32_t max_w = 0;
-    const uint64_t stamp = ++h->many_stamp;
-    for (int i = 0; i < n_chans; ++i) {
-        Item &it = items[(size_t)i];
-        it = Item{nullptr, nullptr, nullptr, 0, 0};
-        auto f = h->chans.find(chan_ids[i]);
-        if (f == h->chans.end()) { counts[i] = RCF_ENOCHAN; continue; }
-        Chan *c = f->second.get();
-        if (c->many_stamp == stamp) { counts[i] = RCF_EINVAL; continue; }   // listed twice: one reader position per channel
-        c->many_stamp = stamp;
-        if (what == RCF_READ_IQ && c->fm_only) { counts[i] = RCF_ESTATE; continue; }   // discriminator only
-        if (what == RCF_READ_AGC && !c->d_agc) { counts[i] = RCF_ESTATE; continue; }   // no AGC on this channel
-        it.c = c;
-        it.cur = chan_read_cursor(c, what);
-        it.ring = chan_read_ring(c, what);
-        int64_t avail = c->produced - *it.cur;
-        if (avail > 0 && (size_t)avail > h->out_cap) {          // reader lagged: oldest samples are gone
-            *it.cur = c->produced - (int64_t)h->out_cap;
-            avail = (int64_t)h->out_cap;
-        }
-        it.n = avail <= 0 ? 0 : std::min<int64_t>(avail, (int64_t)cap_each);
-        it.pos = (size_t)((uint64_t)*it.cur & h->ring_mask);
-        counts[i] = it.n;
-        total += (size_t)it.n;
-        max_w = std::max<uint32_t>(max_w, (uint32_t)it.n * ew);
-    }
-    if (total == 0) return RCF_OK;
-    // One gather launch packs every ring segment back to back into pinned host memory, one synchronisation, then the
-    // rows are handed out.  (A device round trip per channel -- rcf_chan_read_iq in a loop -- costs ~10 us each: 256
-    // tapped bins of ten front-ends are 25 ms per pass.)
-    const size_t rec_bytes = ((size_t)n_chans * sizeof(GatherRec) + 255) & ~(size_t)255;
-    const size_t need = rec_bytes + total * elem;
-    if (need > h->many_cap && (uint64_t)total * ew <= 0xffffffffull) {
-        if (h->h_many) { (void)hipStreamSynchronize(h->stream); (void)hipHostFree(h->h_many); h->h_many = nullptr; h->many_cap = 0; }
-        size_t cap = 1 << 16;
-        while (cap < need) cap <<= 1;
-        void *p = nullptr, *dv = nullptr;
-        if (hipHostMalloc(&p, cap, hipHostMallocDefault) == hipSuccess && hipHostGetDevicePointer(&dv, p, 0) == hipSuccess) {
-            h->h_many = static_cast<unsigned char *>(p);
-            h->h_many_dev = static_cast<unsigned char *>(dv);
-            h->many_cap = cap;
-        } else if (p) {
-            (void)hipHostFree(p);
-        }
-    }
-    if (h->h_many && need <= h->many_cap && (uint64_t)total * ew <= 0xffffffffull) {     // (GatherRec counts 32-bit words)
-        GatherRec *recs = reinterpret_cast<GatherRec *>(h->h_many);
-        uint32_t at_w = 0;
-        int n_recs = 0;
-        for (int i = 0; i < n_chans; ++i) {
-            const Item &it = items[(size_t)i];
-            if (it.n <= 0) continue;
-            recs[n_recs++] = GatherRec{static_cast<const uint32_t *>(it.ring), (uint32_t)(it.pos * ew), (uint32_t)it.n * ew,
-                                       (uint32_t)(h->out_cap * ew - 1), at_w, 0u, ~0u, 1.0f, 0u};
-            at_w += (uint32_t)it.n * ew;
-        }
-        launch_gather_rings(reinterpret_cast<const GatherRec *>(h->h_many_dev), n_recs,
-                            reinterpret_cast<uint32_t *>(h->h_many_dev + rec_bytes), max_w, h->stream);
-        if (hipStreamSynchronize(h->stream) != hipSuccess) { set_error("stream sync failed"); return RCF_EHIP; }
-        const unsigned char *src = h->h_many + rec_bytes;
-        for (int i = 0; i < n_chans; ++i) {
-            const Item &it = items[(size_t)i];
-            if (it.n <= 0) continue;
-            std::memcpy(static_cast<unsigned char *>(out) + (size_t)i * cap_each * elem, src, (size_t)it.n * elem);
-            src += (size_t)it.n * elem;
-        }
-    } else {
-        // no mapped pinned memory: ring by ring, still behind one synchronisation
-        for (int i = 0; i < n_chans; ++i) {
-            const Item &it = items[(size_t)i];
-            if (it.n <= 0) continue;
-            int64_t cur = *it.cur;
-            const int64_t n = ring_read_enqueue(h, it.ring, elem, it.c->produced, &cur,
-                                                static_cast<unsigned char *>(out) + (size_t)i * cap_each * elem, (size_t)it.n);
-            if (n < 0) { (void)hipStreamSynchronize(h->stream); return (int)n; }
-        }
-        if (hipStreamSynchronize(h->stream) != hipSuccess) { set_error("stream sync failed"); return RCF_EHIP; }
-    }
-    free_graveyard_idle(h);
-    for (int i = 0; i < n_chans; ++i) {
-        const Item &it = items[(size_t)i];
-        if (it.n <= 0) continue;
-        *it.cur += it.n;
-        if (what == RCF_READ_FM) {
-            float *o = static_cast<float *>(out) + (size_t)i * cap_each;
-            for (int64_t k = 0; k < it.n; ++k) o[k] = gain * o[k];
-        }
-    }
-    return RCF_OK;
+    return read_many(h->host_stage, h->stream, &h, 1, nullptr, chan_ids, n_chans, what, gain, out, cap_each, counts);
 }
 
 int rcf_chan_fm_filter(rcf_t *h, int chan_id, float gain, const float *taps, int ntaps)
@@ -522,12 +494,7 @@ int rcf_chan_fm_filter(rcf_t *h, int chan_id, float gain, const float *taps, int
 
 int64_t rcf_chan_read_sym(rcf_t *h, int chan_id, float *out, size_t max_samples)
 {
-    if (!h || !out) return RCF_EINVAL;
-    std::lock_guard<std::mutex> g(h->mu);
-    if (set_dev(h)) return RCF_EHIP;
-    FIND_CHAN(h, chan_id, c);
-    if (!c->d_sym) { set_error("channel %d has no fm filter", chan_id); return RCF_ESTATE; }
-    return ring_read(h, c->d_sym, sizeof(float), c->produced, &c->rd_sym, out, max_samples);
+    return chan_read_one(h, chan_id, kReadSym, 1.0f, out, max_samples);
 }
 
 int rcf_chan_agc(rcf_t *h, int chan_id, int nsamples, float reference)
@@ -561,12 +528,7 @@ int rcf_chan_agc(rcf_t *h, int chan_id, int nsamples, float reference)
 
 int64_t rcf_chan_read_agc(rcf_t *h, int chan_id, float *out, size_t max_samples)
 {
-    if (!h || !out) return RCF_EINVAL;
-    std::lock_guard<std::mutex> g(h->mu);
-    if (set_dev(h)) return RCF_EHIP;
-    FIND_CHAN(h, chan_id, c);
-    if (!c->d_agc) { set_error("channel %d has no AGC", chan_id); return RCF_ESTATE; }
-    return ring_read(h, c->d_agc, sizeof(float2), c->produced, &c->rd_agc, out, max_samples);
+    return chan_read_one(h, chan_id, RCF_READ_AGC, 1.0f, out, max_samples);
 }
 
 int rcf_chan_agc_ring(rcf_t *h, int chan_id, void **agc_ring, size_t *capacity)
@@ -575,8 +537,10 @@ int rcf_chan_agc_ring(rcf_t *h, int chan_id, void **agc_ring, size_t *capacity)
     std::lock_guard<std::mutex> g(h->mu);
     if (set_dev(h)) return RCF_EHIP;                  // (zero-copy readers order themselves on rcf_stream: nothing stays deferred)
     FIND_CHAN(h, chan_id, c);
-    if (!c->d_agc) { set_error("channel %d has no AGC", chan_id); return RCF_ESTATE; }
-    if (agc_ring) *agc_ring = c->d_agc;
+    RingStream s;
+    const int rc = chan_stream(h, c, RCF_READ_AGC, &s);
+    if (rc != RCF_OK) return rc;
+    if (agc_ring) *agc_ring = const_cast<void *>(s.ring);
     if (capacity) *capacity = h->out_cap;
     return RCF_OK;
 }
@@ -670,7 +634,7 @@ int64_t rcf_chan_read_audio(rcf_t *h, int chan_id, float *out, size_t max_sample
     int64_t a = 0, u = 0;
     const int rc = audio_counts(h, c, &a, &u);
     if (rc != RCF_OK) return rc;
-    return ring_read(h, c->audio->d_rings + 3 * h->out_cap, sizeof(float), a, &c->audio->rd, out, max_samples);
+    return read_one(h, RingStream{h, c->audio->d_rings + 3 * h->out_cap, 1u, 0u, a, a, &c->audio->rd}, 1.0f, out, max_samples);
 }
 
 int rcf_chan_fm_level(rcf_t *h, int chan_id, float gain, int window, float *level)
@@ -726,8 +690,12 @@ int rcf_chan_rings(rcf_t *h, int chan_id, void **iq_ring, void **fm_ring, size_t
     std::lock_guard<std::mutex> g(h->mu);
     if (set_dev(h)) return RCF_EHIP;                  // (zero-copy readers order themselves on rcf_stream: nothing stays deferred)
     FIND_CHAN(h, chan_id, c);
-    if (iq_ring && c->fm_only) { set_error("channel %d exposes its discriminator only (rcf_chan_set_fm_only)", chan_id); return RCF_ESTATE; }
-    if (iq_ring) *iq_ring = c->d_iq;
+    RingStream s;
+    if (iq_ring) {
+        const int rc = chan_stream(h, c, RCF_READ_IQ, &s);
+        if (rc != RCF_OK) return rc;
+        *iq_ring = const_cast<void *>(s.ring);
+    }
     if (fm_ring) *fm_ring = c->d_fm;
     if (capacity) *capacity = h->out_cap;
     return RCF_OK;

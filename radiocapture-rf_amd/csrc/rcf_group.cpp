@@ -57,7 +57,6 @@ int rcfx::group_process(rcf_group *g, const std::vector<GroupItem> &items, int f
         need += arena_need_bound(h);
     }
     if (g->arenas.reserve(need, st) != RCF_OK) return RCF_EHIP;
-    if (!g->arenas.mapped) { set_error("group launches need device-mapped pinned memory for their records"); return RCF_ESTATE; }
     auto dbg_t1 = dbg_mark(0, dbg_t0);                          // set device + arena reserve
     auto tp = dbg_t0;
     RCF_PROF(8, "group: arena reserve", tp);
@@ -358,62 +357,6 @@ int rcfx::group_process(rcf_group *g, const std::vector<GroupItem> &items, int f
     return RCF_OK;
 }
 
-namespace {
-
-// ---------------------------------------------------------------- batched read over members
-struct ReadItem { rcf_t *h; Chan *c; int64_t *cur; const void *ring; int64_t n; size_t pos; };
-
-// what entry (member, chan) has to give; marks duplicates through the handle's many_stamp (stamps[] holds one fresh stamp
-// per member for this call)
-int resolve_read(rcf_group *g, int what, int member, int chan_id, size_t cap_each, const std::vector<uint64_t> &stamps,
-                 ReadItem &it, int64_t &count)
-{
-    it = ReadItem{nullptr, nullptr, nullptr, nullptr, 0, 0};
-    if (member < 0 || member >= (int)g->members.size()) { count = RCF_EINVAL; return 0; }
-    rcf_t *h = g->members[(size_t)member];
-    auto f = h->chans.find(chan_id);
-    if (f == h->chans.end()) { count = RCF_ENOCHAN; return 0; }
-    Chan *c = f->second.get();
-    if (c->many_stamp == stamps[(size_t)member]) { count = RCF_EINVAL; return 0; }     // listed twice
-    c->many_stamp = stamps[(size_t)member];
-    if (what == RCF_READ_IQ && c->fm_only) { count = RCF_ESTATE; return 0; }           // discriminator only
-    if (what == RCF_READ_AGC && !c->d_agc) { count = RCF_ESTATE; return 0; }           // no AGC on this channel
-    it.h = h;
-    it.c = c;
-    it.cur = chan_read_cursor(c, what);
-    it.ring = chan_read_ring(c, what);
-    int64_t avail = c->produced - *it.cur;
-    if (avail > 0 && (size_t)avail > h->out_cap) {              // reader lagged: oldest samples are gone
-        *it.cur = c->produced - (int64_t)h->out_cap;
-        avail = (int64_t)h->out_cap;
-    }
-    it.n = avail <= 0 ? 0 : std::min<int64_t>(avail, (int64_t)cap_each);
-    it.pos = (size_t)((uint64_t)*it.cur & h->ring_mask);
-    count = it.n;
-    return 1;
-}
-
-int ensure_many(rcf_group *g, size_t need)
-{
-    if (need <= g->many_cap) return RCF_OK;
-    if (g->h_many) { RCF_HIP(hipStreamSynchronize(g->stream)); (void)hipHostFree(g->h_many); g->h_many = nullptr; g->many_cap = 0; }
-    size_t cap = 1 << 16;
-    while (cap < need) cap <<= 1;
-    void *p = nullptr, *dv = nullptr;
-    if (hipHostMalloc(&p, cap, hipHostMallocDefault) != hipSuccess || hipHostGetDevicePointer(&dv, p, 0) != hipSuccess) {
-        if (p) (void)hipHostFree(p);
-        set_error("pinned staging of %zu bytes for the batched read failed", cap);
-        return RCF_ENOMEM;
-    }
-    g->h_many = static_cast<unsigned char *>(p);
-    g->h_many_dev = static_cast<unsigned char *>(dv);
-    g->many_cap = cap;
-    return RCF_OK;
-}
-
-}  // namespace
-
-
 // =================================================================== C ABI
 extern "C" {
 
@@ -483,7 +426,7 @@ int rcf_group_close(rcf_group_t *g)
         }
     }
     for (void *p : g->d_stage) if (p) (void)hipFree(p);
-    if (g->h_many) (void)hipHostFree(g->h_many);
+    g->host_stage.release();
     g->arenas.destroy();
     if (g->ingest_ev) (void)hipEventDestroy(g->ingest_ev);
     (void)hipStreamDestroy(g->stream);
@@ -547,51 +490,8 @@ int rcf_group_read_many(rcf_group_t *g, int what, const int *members, const int 
     MemberLocks ml(g->members);
     RCF_HIP(hipSetDevice(g->device));
     for (rcf_t *h : g->members) flush_lagged(h);            // (a member that was fed on its own meanwhile)
-    const size_t elem = what == RCF_READ_FM ? sizeof(float) : sizeof(float2);
-    const uint32_t ew = (uint32_t)(elem / 4);
-    std::vector<uint64_t> stamps(g->members.size());
-    for (size_t m = 0; m < g->members.size(); ++m) stamps[m] = ++g->members[m]->many_stamp;
-    std::vector<ReadItem> items((size_t)n);
-    size_t total = 0;
-    uint32_t max_w = 0;
-    for (int i = 0; i < n; ++i) {
-        resolve_read(g, what, members[i], chan_ids[i], cap_each, stamps, items[(size_t)i], counts[i]);
-        total += (size_t)items[(size_t)i].n;
-        max_w = std::max<uint32_t>(max_w, (uint32_t)items[(size_t)i].n * ew);
-    }
-    if (total == 0) return RCF_OK;
-    if ((uint64_t)total * ew > 0xffffffffull) { set_error("batched read of %zu items exceeds the 32-bit word range", total); return RCF_ECAP; }
-    const size_t rec_bytes = ((size_t)n * sizeof(GatherRec) + 255) & ~(size_t)255;
-    int rc = ensure_many(g, rec_bytes + total * elem);
-    if (rc != RCF_OK) return rc;
-    GatherRec *recs = reinterpret_cast<GatherRec *>(g->h_many);
-    uint32_t at_w = 0;
-    int n_recs = 0;
-    for (int i = 0; i < n; ++i) {
-        const ReadItem &it = items[(size_t)i];
-        if (it.n <= 0) continue;
-        recs[n_recs++] = GatherRec{static_cast<const uint32_t *>(it.ring), (uint32_t)(it.pos * ew), (uint32_t)it.n * ew,
-                                   (uint32_t)(it.h->out_cap * ew - 1), at_w, 0u, ~0u, 1.0f, 0u};
-        at_w += (uint32_t)it.n * ew;
-    }
-    launch_gather_rings(reinterpret_cast<const GatherRec *>(g->h_many_dev), n_recs,
-                        reinterpret_cast<uint32_t *>(g->h_many_dev + rec_bytes), max_w, g->stream);
-    RCF_HIP(hipStreamSynchronize(g->stream));
-    for (rcf_t *h : g->members) free_graveyard_idle(h);
-    const unsigned char *src = g->h_many + rec_bytes;
-    for (int i = 0; i < n; ++i) {
-        const ReadItem &it = items[(size_t)i];
-        if (it.n <= 0) continue;
-        unsigned char *o = static_cast<unsigned char *>(out) + (size_t)i * cap_each * elem;
-        std::memcpy(o, src, (size_t)it.n * elem);
-        src += (size_t)it.n * elem;
-        *it.cur += it.n;
-        if (what == RCF_READ_FM) {
-            float *f = reinterpret_cast<float *>(o);
-            for (int64_t k = 0; k < it.n; ++k) f[k] = gain * f[k];
-        }
-    }
-    return RCF_OK;
+    return read_many(g->host_stage, g->stream, g->members.data(), g->members.size(), members, chan_ids, n, what, gain, out, cap_each,
+                     counts);
 }
 
 }  // extern "C"

@@ -15,9 +15,7 @@ struct rcf_group {
     hipEvent_t ingest_ev = nullptr;            // the callers' buffers of the last push have been read
     std::vector<void *> d_stage;               // per member: staging for pageable source buffers
     std::vector<size_t> stage_cap;
-    // rcf_group_read_many: pinned staging the gather kernel writes (and reads its records from) across PCIe
-    unsigned char *h_many = nullptr, *h_many_dev = nullptr;
-    size_t many_cap = 0;
+    rcfx::PinnedStage host_stage;              // rcf_group_read_many (host_read)
     rcf_pump *pump = nullptr;
     std::mutex mu;
     // RCF_PUMP_DEBUG=1: the longest time one group block spent in each part of group_process (printed by rcf_pump_stop)

@@ -84,8 +84,8 @@ int ArenaSet::create()
         RCF_HIP(hipHostMalloc(&h[i], cap, hipHostMallocDefault));
         RCF_HIP(hipMalloc(&d[i], cap));
         void *dv = nullptr;
-        h_dev[i] = hipHostGetDevicePointer(&dv, h[i], 0) == hipSuccess ? static_cast<unsigned char *>(dv) : nullptr;
-        if (!h_dev[i]) mapped = false;
+        RCF_HIP(hipHostGetDevicePointer(&dv, h[i], 0));
+        h_dev[i] = static_cast<unsigned char *>(dv);
         RCF_HIP(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
     }
     return RCF_OK;
@@ -111,16 +111,16 @@ int ArenaSet::reserve(size_t need, hipStream_t stream)
         while (ncap < need) ncap *= 2;
         for (int i = 0; i < 2; ++i) {
             unsigned char *nh = nullptr, *nd = nullptr;
+            void *dv = nullptr;
             RCF_HIP(hipHostMalloc(&nh, ncap, hipHostMallocDefault));
             RCF_HIP(hipMalloc(&nd, ncap));
+            RCF_HIP(hipHostGetDevicePointer(&dv, nh, 0));
             (void)hipHostFree(h[i]);
             (void)hipFree(d[i]);
             h[i] = nh;
             d[i] = nd;
+            h_dev[i] = static_cast<unsigned char *>(dv);
             used[i] = false;
-            void *dv = nullptr;
-            h_dev[i] = hipHostGetDevicePointer(&dv, nh, 0) == hipSuccess ? static_cast<unsigned char *>(dv) : nullptr;
-            if (!h_dev[i]) mapped = false;
         }
         cap = ncap;
         fill = 0;
@@ -236,9 +236,7 @@ int rcf_close(rcf_t *h)
     (void)hipStreamSynchronize(h->stream);
     for (auto &kv : h->chans) free_channel(h, kv.second.get());
     h->chans.clear();
-    Pfb &p = h->pfb;
-    bury(h, p.d_ptaps); bury(h, p.d_tw); bury(h, p.d_bins); bury(h, p.d_stage);
-    bury(h, p.d_fm); bury(h, p.d_fm_inc); bury(h, p.d_fm_stage); bury(h, p.d_fm_edge); bury(h, p.d_fm_flag); bury(h, p.d_fm_err);
+    pfb_release(h);
     Scan &s = h->scan;
     bury(h, s.d_window); bury(h, s.d_vring); bury(h, s.d_sum); bury(h, s.d_out); bury(h, s.d_tw);
     bury(h, s.d_scratch); bury(h, s.d_peaks); bury(h, s.d_peak_ws);
@@ -251,7 +249,7 @@ int rcf_close(rcf_t *h)
         bury(h, h->d_buf[i]);
     }
     bury(h, h->d_gather);
-    if (h->h_many) (void)hipHostFree(h->h_many);
+    h->host_stage.release();
     bury(h, h->d_partial);
     bury(h, h->d_tapmat);
     drain_graveyard(h);
@@ -335,8 +333,7 @@ int rcf_push_iq(rcf_t *h, const float *iq, size_t n)
         // out of host memory -- no second stream, no cross-stream waits.  In order behind every kernel that read this
         // buffer, so no buf_done bookkeeping either.
         void *dv = nullptr;
-        if (n * sizeof(float2) <= kRawDirectBytes && h->copy_kernels &&
-            hipHostGetDevicePointer(&dv, const_cast<float *>(iq), 0) == hipSuccess && dv) {
+        if (n * sizeof(float2) <= kRawDirectBytes && hipHostGetDevicePointer(&dv, const_cast<float *>(iq), 0) == hipSuccess && dv) {
             launch_copy8(h->d_buf[h->cur] + h->hist_cap, dv, sizeof(float2) * n, h->stream);
             RCF_HIP(hipEventRecord(h->copy_ev, h->stream));
             int rc = process_block(h, n);

@@ -489,8 +489,9 @@ void launch_pfb5_fm_inc(const double *d_dangle, float2 *d_inc, int NB, hipStream
 inline bool pfb_frame_major(int NB) { return NB % 25 == 0; }
 // dst[i] = view sample (first + i), i < n (one bin's samples out of a bank ring; ingest.hip)
 void launch_gather_view(const StreamView &v, int64_t first, float2 *dst, size_t n, hipStream_t s);
-void launch_gather_f32(const float *base, uint64_t mask, int64_t stride, int64_t first, float gain, float *dst, size_t n, hipStream_t s);
-// one ring segment of a batched read (rcf_chan_read_many), in 4-byte words: dst[dst_w + w] = ring[(pos_w + w) & mask_w], w < n_w
+// one ring segment of a host read, in 4-byte words: dst[dst_w + w] = ring[(pos_w + w) & mask_w], w < n_w.  Every host read of a
+// channel, bank or voice-chain ring (host_read, rcf_state.h) and the real-time pump's delivery are made of these; gather_rec
+// builds them.
 //   dst_mask_w = ~0u, dst_pos_w = 0: rows packed back to back; otherwise the destination is a ring of dst_mask_w + 1 words that
 //   starts at word dst_w (the real-time pump's per-channel host rings), written from dst_pos_w on
 struct GatherRec {
@@ -498,7 +499,7 @@ struct GatherRec {
     uint32_t pos_w, n_w, mask_w, dst_w;
     uint32_t dst_pos_w, dst_mask_w;
     float gain;              // flags & 1: the words are float32 and leave multiplied by gain (quadrature_demod_cf's gain, one
-    uint32_t flags;          // float32 multiply -- what rcf_chan_read_fm does on the host)
+    uint32_t flags;          // float32 multiply, rounded to nearest, denormals kept)
     uint32_t stride_w;       // words between consecutive source items (0 / 1: contiguous); > 1: one bin of a frame-major ring of
                              // floats (the bank's fused discriminator ring: ring = its bin, stride = bins)
 };

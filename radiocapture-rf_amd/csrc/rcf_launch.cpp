@@ -65,7 +65,7 @@ int launch_plan(rcf_t *h, BlockPlan &bp)
         // ... or none at all: when the filterbank's launch is the first of the block that needs neither (no direct
         // channels, no exact-rotator fill before it, no tap matrix whose slot list the bank itself reads from the
         // arena), its first workgroups do both copies on the way in (PfbLaunch::rider_*)
-        const bool ride = h->copy_kernels && run_pfb && !d_rot_fills &&
+        const bool ride = run_pfb && !d_rot_fills &&
                           (fir_by_depth.empty() || fir_by_depth[0].empty()) && pl.n_taps == pl.tap_first &&
                           bytes / 8 < (1u << 31) && h->hist_cap < (1u << 28) && pfb_takes_rider(pl);
         if (ride) {
@@ -76,13 +76,11 @@ int launch_plan(rcf_t *h, BlockPlan &bp)
             pl.rider_src[1] = reinterpret_cast<const unsigned long long *>(h->d_buf[h->cur] + bp.n);
             pl.rider_n8[1] = (uint32_t)(sizeof(float2) * h->hist_cap / 8);
             bp.history_done = true;
-        } else if (h->copy_kernels) {
+        } else {
             Timed t(h, RCF_T_HISTORY);
             launch_copy8x2(ar.d + from, h->arenas.h_dev[a] + from, bytes, h->d_buf[h->cur ^ 1], h->d_buf[h->cur] + bp.n,
                            sizeof(float2) * h->hist_cap, st);
             bp.history_done = true;
-        } else if (bytes) {
-            RCF_HIP(hipMemcpyAsync(ar.d + from, ar.h + from, bytes, hipMemcpyHostToDevice, st));
         }
         if (bytes) h->arenas.fill = (ar.used + 63) & ~size_t(63);
     }
@@ -180,9 +178,7 @@ int finish_block(rcf_t *h, const BlockPlan &bp)
     const int other = h->cur ^ 1;
     if (!bp.history_done) {
         Timed t(h, RCF_T_HISTORY);
-        if (h->copy_kernels) launch_copy8(h->d_buf[other], h->d_buf[h->cur] + n, sizeof(float2) * h->hist_cap, st);
-        else RCF_HIP(hipMemcpyAsync(h->d_buf[other], h->d_buf[h->cur] + n, sizeof(float2) * h->hist_cap,
-                                    hipMemcpyDeviceToDevice, st));
+        launch_copy8(h->d_buf[other], h->d_buf[h->cur] + n, sizeof(float2) * h->hist_cap, st);
     }
     if (h->eager_buf_done) {
         RCF_HIP(hipEventRecord(h->buf_done[h->cur], st));    // everything that reads this buffer is queued

@@ -124,7 +124,6 @@ int plan_arena(rcf_t *h, BlockPlan &bp)
     // the one it lives in can come round again)
     if (h->lag.pending && (arena_need > h->arenas.cap || h->arenas.fill + arena_need > h->arenas.cap)) flush_lagged(h);
     if (h->arenas.reserve(arena_need, h->stream) != RCF_OK) return RCF_EHIP;
-    if (!h->arenas.mapped) h->copy_kernels = false;
     bp.a = h->arenas.cur;
     bp.arena_base = h->arenas.fill;
     bp.own_ar = Arena{h->arenas.h[bp.a], h->arenas.d[bp.a], bp.arena_base, h->arenas.cap};

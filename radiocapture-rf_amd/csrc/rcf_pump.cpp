@@ -247,6 +247,7 @@ void pump_main(rcf_pump *p)
                             epoch_of[(size_t)it.m] = h->chans_epoch;
                         }
                         for (int e : p->entries_of[(size_t)it.m]) {
+                            RingStream rs;
                             if (p->rd_chan[(size_t)e] >= RCF_SRC_PFB_BIN0) {
                                 // one bin of the bank's fused discriminator ring (rcf_pfb_fm_enable): frame-major floats,
                                 // read with a stride of n_bins words
@@ -256,48 +257,26 @@ void pump_main(rcf_pump *p)
                                 const int64_t end = pf.fm_mode ? pf.produced : pf.fm_until;
                                 int64_t &cur = p->bin_rd[(size_t)e];
                                 cur = std::max(cur, pf.fm_from);          // (switched off and on again: the frames between were never demodulated)
-                                int64_t avail = end - cur;
-                                if (avail <= 0) continue;
-                                if ((size_t)avail > h->out_cap) { cur = end - (int64_t)h->out_cap; avail = (int64_t)h->out_cap; }
-                                if ((size_t)avail > p->out_cap) { cur += avail - (int64_t)p->out_cap; avail = (int64_t)p->out_cap; }
-                                const float gain = p->rd_gain[(size_t)e];
-                                const uint64_t dst_pos = (uint64_t)queued[(size_t)e] & (p->out_cap - 1);
-                                queued[(size_t)e] += avail;
-                                p->out_queued[(size_t)e].store(queued[(size_t)e], std::memory_order_release);
-                                recs[n_recs++] = GatherRec{reinterpret_cast<const uint32_t *>(pf.d_fm + bin),
-                                                           (uint32_t)((uint64_t)cur & h->ring_mask), (uint32_t)avail,
-                                                           (uint32_t)(h->out_cap - 1), (uint32_t)((size_t)e * p->out_cap * slot_w),
-                                                           (uint32_t)dst_pos, (uint32_t)(p->out_cap - 1), gain, gain != 1.0f ? 1u : 0u,
-                                                           (uint32_t)pf.NB};
-                                max_w = std::max<uint32_t>(max_w, (uint32_t)avail);
-                                cur += avail;
-                                s.delivered.push_back({e, avail});
-                                continue;
+                                rs = RingStream{h, pf.d_fm + bin, 1u, (uint32_t)pf.NB, end, end, &cur};
+                            } else {
+                                Chan *c = chan_of[(size_t)e];
+                                if (!c) continue;                                  // closed under the pump: starves
+                                if (chan_stream(h, c, p->rd_what[(size_t)e], &rs) != RCF_OK) continue;   // (IQ of a discriminator-only tap)
                             }
-                            Chan *c = chan_of[(size_t)e];
-                            if (!c) continue;                                      // closed under the pump: starves
-                            const int what = p->rd_what[(size_t)e];
-                            const float gain = p->rd_gain[(size_t)e];
-                            const uint32_t ew = what == RCF_READ_IQ ? 2u : 1u;     // words per item of this slot's stream
-                            if (what == RCF_READ_IQ && c->fm_only) continue;       // discriminator only: no IQ stream to hand out
-                            if (what == RCF_READ_FM && !c->d_fm) continue;
-                            int64_t *cur = what == RCF_READ_IQ ? &c->rd_iq : &c->rd_fm;
-                            int64_t avail = c->produced - *cur;
-                            if (avail <= 0) continue;
-                            if ((size_t)avail > h->out_cap) { *cur = c->produced - (int64_t)h->out_cap; avail = (int64_t)h->out_cap; }
-                            if ((size_t)avail > p->out_cap) { *cur += avail - (int64_t)p->out_cap; avail = (int64_t)p->out_cap; }
+                            int64_t n = lag_clamp(h, rs.cursor, rs.newest, rs.end, INT64_MAX);
+                            if (n == 0) continue;
+                            if ((size_t)n > p->out_cap) { *rs.cursor += n - (int64_t)p->out_cap; n = (int64_t)p->out_cap; }
+                            const uint32_t ew = rs.item_w;                         // words per item of this slot's stream
                             const uint64_t dst_pos = (uint64_t)queued[(size_t)e] & (p->out_cap - 1);
-                            queued[(size_t)e] += avail;
+                            queued[(size_t)e] += n;
                             // (published BEFORE the launch: a reader that copied positions this gather overwrites finds out)
                             p->out_queued[(size_t)e].store(queued[(size_t)e], std::memory_order_release);
-                            recs[n_recs++] = GatherRec{static_cast<const uint32_t *>(what == RCF_READ_IQ ? (const void *)c->d_iq : (const void *)c->d_fm),
-                                                       (uint32_t)(((uint64_t)*cur & h->ring_mask) * ew), (uint32_t)avail * ew,
-                                                       (uint32_t)(h->out_cap * ew - 1), (uint32_t)((size_t)e * p->out_cap * slot_w),
-                                                       (uint32_t)(dst_pos * ew), (uint32_t)(p->out_cap * ew - 1), gain,
-                                                       (what == RCF_READ_FM && gain != 1.0f) ? 1u : 0u};
-                            max_w = std::max<uint32_t>(max_w, (uint32_t)avail * ew);
-                            *cur += avail;
-                            s.delivered.push_back({e, avail});
+                            recs[n_recs++] = gather_rec(rs, n, (uint32_t)((size_t)e * p->out_cap * slot_w), (uint32_t)(dst_pos * ew),
+                                                        (uint32_t)(p->out_cap * ew - 1),
+                                                        p->rd_what[(size_t)e] == RCF_READ_FM ? p->rd_gain[(size_t)e] : 1.0f);
+                            max_w = std::max<uint32_t>(max_w, (uint32_t)n * ew);
+                            *rs.cursor += n;
+                            s.delivered.push_back({e, n});
                         }
                     }
                     if (n_recs)

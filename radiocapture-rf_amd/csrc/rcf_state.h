@@ -1,7 +1,8 @@
 // rcf_state.h -- host-side state of librcf.so (the kernels never see it): the front-end handle with its channels,
 // filterbank, scanner, slab pools and launch arenas, and the helpers the host modules share.
 //   rcf_handle.cpp   open / close / sync, pools, wideband ingest        rcf_plan.cpp    the per-block schedule (host)
-//   rcf_launch.cpp   the block's launches in dependency order           rcf_chan.cpp    channels: lifecycle, reads, voice chain
+//   rcf_launch.cpp   the block's launches in dependency order           rcf_chan.cpp    channels, voice chain, and the one read
+//                                                                                       path of every host read (host_read)
 //   rcf_bank.cpp     filterbank + scanner ABI                           rcf_timing.cpp  HIP-event timing
 //   rcf_comm.cpp     RCCL peak-list exchange                            rcf_group.cpp   grouped launches over front-ends
 #pragma once
@@ -89,7 +90,7 @@ struct Chan {
     float agc_ref = 1.f;
     int64_t agc_from = 0;         // first relative output index the AGC is defined for (zero history before it)
     int64_t rd_agc = 0;
-    uint64_t many_stamp = 0;      // the rcf_chan_read_many call that last listed this channel
+    uint64_t many_stamp = 0;      // the host_read call that last listed this channel (batched reads: one reader per stream)
     double src_rate = 0, offset_hz = 0;
     uint64_t taps_version = 0;    // bumped whenever d_ctaps changes (bank-matrix cache key)
     std::vector<float> proto;     // prototype taps (host)
@@ -103,7 +104,6 @@ struct Pfb {
     float *d_ptaps = nullptr;
     float2 *d_tw = nullptr;
     float2 *d_bins = nullptr;
-    float2 *d_stage = nullptr;     // frame-major banks: contiguous staging for rcf_pfb_read_bin
     std::vector<int64_t> rd;       // per-bin read cursors
     int64_t start_sample = 0, n_abs0 = 0, produced = 0;
     int64_t produced_before = 0;   // value of `produced` before the current commit (for derived channels)
@@ -112,7 +112,6 @@ struct Pfb {
     int fm_gr_phase = 0;
     float *d_fm = nullptr;
     float2 *d_fm_inc = nullptr;    // [NB] per-bin rotator increment as a phasor
-    float *d_fm_stage = nullptr;   // contiguous staging for rcf_pfb_read_fm
     int64_t fm_from = 0;           // first relative frame the discriminator ring holds
     int64_t fm_until = 0;          // (fm_mode == 0) the frame the discriminator was switched off at
     // look-back form (pfb5_fmlb_kernel): edge rows + flags the chunks' workgroups hand their last frames over through
@@ -150,10 +149,18 @@ struct ArenaSet {
     bool used[2] = {false, false};
     int cur = 0;
     size_t fill = 0;              // bytes of the current arena taken by earlier commits
-    bool mapped = true;           // both pinned arenas are visible to the device (copy kernels can read them)
-    int create();
+    int create();                 // RCF_EHIP also when the pinned arenas cannot be mapped for the device (h_dev)
     void destroy();               // the stream that read them is idle
     int reserve(size_t need, hipStream_t stream);   // room for `need` more bytes in arena `cur` from `fill` on
+};
+
+// Pinned host memory that host_read's gather kernel reads its records from and writes the rows into, across PCIe (one per
+// front-end, one per group).  Grows by powers of two from 64 KiB.
+struct PinnedStage {
+    unsigned char *h = nullptr, *d = nullptr;     // host address / the same memory as the device sees it
+    size_t cap = 0;
+    int ensure(size_t need, hipStream_t stream);  // RCF_ENOMEM when no mapped pinned memory of that size can be had
+    void release() { if (h) (void)hipHostFree(h); h = d = nullptr; cap = 0; }
 };
 }  // namespace rcfx
 
@@ -179,7 +186,6 @@ struct rcf {
     void *d_raw = nullptr;        // wire-format staging (rcf_push_raw), block_cap * 4 bytes, lazily allocated
     // launch-parameter arenas (pinned host + device), double buffered
     rcfx::ArenaSet arenas;
-    bool copy_kernels = true;     // false (arenas not mapped): hipMemcpyAsync for the launch records and the history
     // Stage-2 lag (rcf_launch.cpp): the small-T FIR + discriminator launch of the last block has NOT been queued -- it rides
     // in the next block's filterbank launch (S2Rider), or goes out on its own as soon as anybody could look at its outputs
     // (every entry point that touches the stream flushes it: set_dev).  RCF_S2_LAG=0 / rcf_set_stage2_lag(h, 0): off.
@@ -239,10 +245,7 @@ struct rcf {
     int comm_rank = 0, comm_size = 1;
     int64_t *d_gather = nullptr;
     size_t gather_cap = 0;
-    // rcf_chan_read_many: pinned staging the gather kernel writes (and reads its records from) across PCIe
-    unsigned char *h_many = nullptr, *h_many_dev = nullptr;
-    size_t many_cap = 0;
-    uint64_t many_stamp = 0;
+    rcfx::PinnedStage host_stage; // the handle's host reads (host_read, rcf_pfb_read_bin)
     // optional per-kernel-class HIP-event timing (rcf_timing_*)
     bool timing = false;
     unsigned timing_mask = ~0u;
@@ -335,12 +338,62 @@ int pfb_fm_upload_increments(rcf_t *h);
 // tap: a frame-major bank's tap (rcf_pfb_tap_open), copied by the bank's kernel -- the one bin consumer mode 2 keeps
 int new_channel(rcf_t *h, int src, int D, const float *taps, int T, double offset_hz, int *chan_id, bool tap = false);
 void free_channel(rcf_t *h, Chan *c);
-int64_t ring_read_enqueue(rcf_t *h, const void *ring, size_t elem, int64_t produced, int64_t *cursor, void *out,
-                          size_t max_items);
-int64_t ring_read(rcf_t *h, const void *ring, size_t elem, int64_t produced, int64_t *cursor, void *out,
-                  size_t max_items);
-int64_t *chan_read_cursor(Chan *c, int what);             // RCF_READ_IQ / RCF_READ_FM / RCF_READ_AGC
-const void *chan_read_ring(const Chan *c, int what);
+
+// ---- the one read path.  A stream is a device ring of h->out_cap items (a power of two) of item_w 4-byte words:
+// item i at word (i & ring_mask) * stride_w of ring when stride_w > 1 (one bin of a frame-major ring of floats), else at
+// (i & ring_mask) * item_w.  The ring holds the out_cap items before `newest`; a reader at *cursor may take up to `end`.
+struct RingStream {
+    rcf_t *h = nullptr;
+    const void *ring = nullptr;
+    uint32_t item_w = 1, stride_w = 0;
+    int64_t end = 0, newest = 0;
+    int64_t *cursor = nullptr;
+};
+constexpr int kReadSym = 3;       // the symbol filter's stream: single reads only (the batched ABIs take RCF_READ_IQ / FM / AGC)
+// channel c's stream `kind` (RCF_READ_IQ / FM / AGC, kReadSym), or RCF_ESTATE with the refusal's message: IQ of a
+// discriminator-only tap, SYM without rcf_chan_fm_filter, AGC without rcf_chan_agc
+int chan_stream(rcf_t *h, Chan *c, int kind, RingStream *s);
+
+// A reader that has fallen more than a ring behind lost what the ring overwrote: its cursor is raised to the oldest item
+// the ring still holds.  Returns how many items [*cursor, end) it may take, at most max.
+inline int64_t lag_clamp(const rcf_t *h, int64_t *cursor, int64_t produced, int64_t end, int64_t max)
+{
+    *cursor = std::max(*cursor, produced - (int64_t)h->out_cap);
+    return std::max<int64_t>(0, std::min(end - *cursor, max));
+}
+
+// the gather record of the n items of s from *s.cursor on into the destination described by dst_* (GatherRec); float items
+// leave multiplied by gain unless it is 1
+inline GatherRec gather_rec(const RingStream &s, int64_t n, uint32_t dst_w, uint32_t dst_pos_w, uint32_t dst_mask_w, float gain)
+{
+    return GatherRec{static_cast<const uint32_t *>(s.ring), (uint32_t)(((uint64_t)*s.cursor & s.h->ring_mask) * s.item_w),
+                     (uint32_t)n * s.item_w, (uint32_t)(s.h->out_cap * s.item_w - 1), dst_w, dst_pos_w, dst_mask_w, gain,
+                     gain != 1.0f ? 1u : 0u, s.stride_w};
+}
+
+// one entry of a host read: a stream, the row its items go to and at most how many.  s.ring == nullptr: nothing to read
+// (*count holds the entry's error code already)
+struct ReadEntry {
+    RingStream s;
+    Chan *c = nullptr;            // batched reads: a channel listed twice in one call is refused (RCF_EINVAL)
+    float gain = 1.0f;
+    void *out = nullptr;
+    int64_t max = 0;
+    int64_t *count = nullptr;     // out: items read, or the entry's error code
+};
+// Every entry's new items in one gather_rings launch into `stage` and one synchronisation of `stream`; then the rows are
+// copied out, the cursors advanced and the graveyards of the idle handles (those on `stream`) released.  RCF_ECAP when the
+// words do not fit the records' 32 bits, RCF_ENOMEM when the staging cannot be had.
+int host_read(PinnedStage &stage, hipStream_t stream, rcf_t *const *idle, size_t n_idle, ReadEntry *es, size_t n);
+// a single reader: host_read of one entry on h's own stream and staging; the items read, or an error code
+int64_t read_one(rcf_t *h, const RingStream &s, float gain, void *out, size_t max_items);
+// rcf_chan_read_many (hs = the handle, ms = nullptr) and rcf_group_read_many (hs = the members): entry i is channel
+// chan_ids[i] of hs[ms[i]] as `what` (RCF_READ_IQ / FM x gain / AGC) into row i of out; counts[i] its items or its error
+int read_many(PinnedStage &stage, hipStream_t stream, rcf_t *const *hs, size_t n_hs, const int *ms, const int *chan_ids, int n,
+              int what, float gain, void *out, size_t cap_each, int64_t *counts);
+
+// ---------------------------------------------------------------- rcf_bank.cpp
+void pfb_release(rcf_t *h);          // the bank's device buffers go once the stream has passed them; the bank is closed
 
 // ---------------------------------------------------------------- rcf_plan.cpp / rcf_launch.cpp
 int process_block(rcf_t *h, size_t n);
