@@ -351,11 +351,16 @@ int rcf_pfb_fm_ring(rcf_t *h, void **fm_ring, size_t *capacity_frames, int64_t *
  * Supported shapes (anything else: RCF_EINVAL):
  *   n_bins in {64, 128, 256, 512, 1024}, n_bins / decim in {1, 2}, up to 16 taps per branch
  *   n_bins in {400, 800, 1600, 3200},    n_bins / decim = 1 with up to 4 taps per branch, 2 with up to 2, 4 with 1
- * The second family is what makes the bins the REFERENCE's channels: with the reference's own channel filter
+ *   n_bins in {160, 192, 480, 640, 960, 1280}, n_bins / decim = 2 with up to 2 taps per branch
+ * (rcf_pfb_shape_family tells which of the three a shape belongs to.)
+ * The second and third families are what makes the bins the REFERENCE's channels: with the reference's own channel filter
  * (rcf_channel_params: decim = int(fs/cr)/2, low_pass_2(1, fs, cr/2, cr/2, 20, HAMMING)) at fs = 20 Msps,
  * cr = 12.5 kHz -- decim 800, 2909 taps -- a 1600-bin bank is every 12.5 kHz-grid channel and a 3200-bin bank every
  * 6.25 kHz-grid channel rc_frontend/channel.py:31-35 could build, at the same 25 kS/s (10 Msps: 800 bins,
- * 5 Msps: 400).
+ * 5 Msps: 400).  The third family is the same rule at the rates the reference is deployed at -- 2, 2.4, 6, 8, 12 and
+ * 16 Msps on the 12.5 kHz grid (2.4 Msps: 192 bins, decim 96, 349 taps).  Its banks have bins, taps, stage-2 channels and
+ * rcf_pfb_read_bin like the second family's; rcf_pfb_fm_enable does NOT cover them (RCF_EINVAL: no fused-discriminator
+ * kernel for these shapes).
  */
 int rcf_pfb_open(rcf_t *h, int n_bins, int decim, const float *taps, int ntaps);
 int rcf_pfb_close(rcf_t *h);
@@ -366,7 +371,7 @@ int64_t rcf_pfb_read_bin(rcf_t *h, int bin, float *out_interleaved, size_t max_s
  * Power-of-two banks: tiles of 16 frames, sample n of bin k at bins_ring[(i >> 4) * tile_pitch + 16 * k + (i & 15)]
  * with tile_pitch = 16 * n_bins + 80 (a chunk of 16 frames is one contiguous run for the kernel that writes it, a bin's
  * 16 frames are one 128-byte line for whoever reads it; the padding keeps one bin's lines off a single memory channel),
- * and *pitch = 16 (frames per tile).  400 / 800 / 1600 / 3200-bin banks: ONE ring of whole frames, sample n of bin k at
+ * and *pitch = 16 (frames per tile).  All other banks (400 2^k bins and the 160 .. 1280-bin family): ONE ring of whole frames, sample n of bin k at
  * bins_ring[i * n_bins + k], and *pitch = 0. */
 int rcf_pfb_rings(rcf_t *h, void **bins_ring, size_t *capacity, size_t *pitch);
 /* stage 2 on one bin: channel.py's own rule at the bin rate -- decim2 = int(bin_rate/cr)/2,
@@ -410,6 +415,9 @@ int rcf_pfb_tap_leakage(double samp_rate, int n_bins, const float *taps, int nta
                         double *const_phase);
 /* 1 when rcf_pfb_open would accept this shape (no device needed) */
 int rcf_pfb_shape_supported(int n_bins, int decim, int ntaps);
+/* which kernel family rcf_pfb_open would run this shape on (no device needed): 0 none (the shape is not supported),
+ * 1 power-of-two bin counts, 2 400 2^k bins, 3 the mixed-radix family {160, 192, 480, 640, 960, 1280} */
+int rcf_pfb_shape_family(int n_bins, int decim, int ntaps);
 
 /* ------------------------------------------------------------------ scan (fft_vector.py + fft_peak_detection.py) */
 /*

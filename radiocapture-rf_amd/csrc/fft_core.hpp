@@ -6,7 +6,11 @@
 //
 // Not a dense contraction: butterflies run on the vector ALU, no MFMA (BASELINE.json north_star).
 #pragma once
+// RCF_FFT_CORE_HOST: the butterflies compiled for the host (tests/test_pfbm_host.py checks them against a double-precision
+// DFT); the includer then supplies float2, make_float2 and the __device__ / __forceinline__ spellings itself
+#ifndef RCF_FFT_CORE_HOST
 #include <hip/hip_runtime.h>
+#endif
 
 namespace rcfx {
 
@@ -189,6 +193,102 @@ template <int M, int SIGN> struct DftPfa5 {
     }
 };
 template <int SIGN> struct Dft<20, SIGN> : DftPfa5<4, SIGN> {};
+
+// 3-point DFT, natural order in and out
+template <int SIGN>
+__device__ __forceinline__ void dft3(cf &x0, cf &x1, cf &x2)
+{
+    const float s = 0.86602540378443865f;                                  // sin(2 pi/3)
+    const cf t = cadd(x1, x2), d = csub(x1, x2);
+    const cf m = make_float2(fmaf(-0.5f, t.x, x0.x), fmaf(-0.5f, t.y, x0.y));
+    const cf r = mul_si<SIGN>(make_float2(s * d.x, s * d.y));              // SIGN i sin(2 pi/3) (x1 - x2)
+    x0 = cadd(x0, t);
+    x1 = cadd(m, r);
+    x2 = csub(m, r);
+}
+template <int SIGN> struct Dft<3, SIGN> {
+    static __device__ __forceinline__ void run(cf (&v)[3]) { dft3<SIGN>(v[0], v[1], v[2]); }
+    static __device__ __forceinline__ constexpr int reg_of(int f) { return f; }
+};
+
+// A M points, A and M coprime and both covered by Dft<>: the Good-Thomas form of DftPfa5 for any first factor (the mixed-radix
+// banks of pfbm.hip: 10 = 5 x 2, 12 = 3 x 4, 24 = 3 x 8, 40 = 5 x 8).  DftPfa5 itself stays as it is: the 400 2^k banks'
+// instruction sequence is pinned by their bit-equality tests.
+//   n = (M a + A b) mod A M,  k = k1 (mod A) = k2 (mod M):   X[k] = sum_b W_M^{b k2} sum_a W_A^{a k1} x[n(a, b)]
+// Stage 1 leaves Y[b][k1] in register n(k1, b), stage 2 leaves X[k] in register n(k1, Dft<M>::reg_of(k2)).
+template <int A, int M, int SIGN> struct DftPfa {
+    static constexpr int R = A * M;
+    static __device__ __forceinline__ void run(cf (&v)[R])
+    {
+#pragma unroll
+        for (int b = 0; b < M; ++b) {
+            cf w[A];
+#pragma unroll
+            for (int a = 0; a < A; ++a) w[a] = v[(M * a + A * b) % R];
+            Dft<A, SIGN>::run(w);
+#pragma unroll
+            for (int a = 0; a < A; ++a) v[(M * a + A * b) % R] = w[Dft<A, SIGN>::reg_of(a)];
+        }
+#pragma unroll
+        for (int a = 0; a < A; ++a) {
+            cf w[M];
+#pragma unroll
+            for (int b = 0; b < M; ++b) w[b] = v[(M * a + A * b) % R];
+            Dft<M, SIGN>::run(w);
+#pragma unroll
+            for (int b = 0; b < M; ++b) v[(M * a + A * b) % R] = w[b];
+        }
+    }
+    static __device__ __forceinline__ constexpr int reg_of(int f)
+    {
+        return (M * (f % A) + A * Dft<M, SIGN>::reg_of(f % M)) % R;
+    }
+};
+template <int SIGN> struct Dft<10, SIGN> : DftPfa<5, 2, SIGN> {};
+template <int SIGN> struct Dft<12, SIGN> : DftPfa<3, 4, SIGN> {};
+template <int SIGN> struct Dft<24, SIGN> : DftPfa<3, 8, SIGN> {};
+template <int SIGN> struct Dft<40, SIGN> : DftPfa<5, 8, SIGN> {};
+
+// e^{SIGN * 2 pi i m / 32}, m = 0..31
+__device__ __forceinline__ cf w32(int m, int sign)
+{
+    const float c[9] = {1.0f, 0.98078528040323043f, 0.92387953251128674f, 0.83146961230254524f, 0.70710678118654752f,
+                        0.55557023301960218f, 0.38268343236508977f, 0.19509032201612825f, 0.0f};
+    int q = m & 7, o = (m >> 3) & 3;
+    float cr = c[q], sr = c[8 - q];          // angle q*pi/16 in the first quadrant
+    float x, y;
+    switch (o) {
+        case 0: x = cr;  y = sr;  break;
+        case 1: x = -sr; y = cr;  break;
+        case 2: x = -cr; y = -sr; break;
+        default: x = sr; y = -cr; break;
+    }
+    return make_float2(x, sign < 0 ? -y : y);
+}
+// 32 = 4 (n1) x 8 (n2): n = 8 n1 + n2, f = k1 + 4 k2 (Dft<16>'s scheme one size up)
+template <int SIGN> struct Dft<32, SIGN> {
+    static __device__ __forceinline__ void run(cf (&v)[32])
+    {
+#pragma unroll
+        for (int n2 = 0; n2 < 8; ++n2) dft4<SIGN>(v[n2], v[8 + n2], v[16 + n2], v[24 + n2]);
+        // now v[8 k1 + n2] = A[n2][k1]; twiddle by W32^{n2 k1}
+#pragma unroll
+        for (int k1 = 1; k1 < 4; ++k1)
+#pragma unroll
+            for (int n2 = 1; n2 < 8; ++n2) v[8 * k1 + n2] = cmul(v[8 * k1 + n2], w32(n2 * k1, SIGN));
+#pragma unroll
+        for (int k1 = 0; k1 < 4; ++k1) {
+            cf w[8];
+#pragma unroll
+            for (int n2 = 0; n2 < 8; ++n2) w[n2] = v[8 * k1 + n2];
+            Dft<8, SIGN>::run(w);
+#pragma unroll
+            for (int n2 = 0; n2 < 8; ++n2) v[8 * k1 + n2] = w[n2];
+        }
+    }
+    // register 8 k1 + Dft<8>::reg_of(k2) holds f = k1 + 4 k2
+    static __device__ __forceinline__ constexpr int reg_of(int f) { return 8 * (f & 3) + Dft<8, SIGN>::reg_of(f >> 2); }
+};
 
 // padded LDS index: one spare complex after every 16
 __device__ __forceinline__ int lds_pad(int i) { return i + (i >> 4); }

@@ -805,7 +805,10 @@ bool dispatch(const PfbLaunch &p, bool probe, hipStream_t s, const PfbLaunch *d_
         case 256:  return dispatch_nb<256>(p, OS, p.P, probe, s, d_pls, gm, sr);
         case 512:  return dispatch_nb<512>(p, OS, p.P, probe, s, d_pls, gm, sr);
         case 1024: return dispatch_nb<1024>(p, OS, p.P, probe, s, d_pls, gm, sr);
-        default:   return d_pls ? pfb5_dispatch_group(p, d_pls, *gm, s) : pfb5_dispatch(p, probe, s);      // 400 / 800 / 1600 / 3200 bins (pfb5.hip)
+        default:
+            if (pfbm_bins(p.NB))                          // 160 / 192 / 480 / 640 / 960 / 1280 bins (pfbm.hip)
+                return d_pls ? pfbm_dispatch_group(p, d_pls, *gm, s) : pfbm_dispatch(p, probe, s);
+            return d_pls ? pfb5_dispatch_group(p, d_pls, *gm, s) : pfb5_dispatch(p, probe, s);      // 400 / 800 / 1600 / 3200 bins (pfb5.hip)
     }
 }
 
@@ -822,6 +825,7 @@ bool pfb_supported(int NB, int D, int P)
 int pfb_padded_p(int NB, int D, int P)
 {
     if (NB % 25 == 0) return pfb5_padded_p(NB, D, P);
+    if (pfbm_bins(NB)) return pfbm_padded_p(NB, D, P);
     return round_p(P, D > 0 ? NB / D : 1);
 }
 
@@ -858,7 +862,18 @@ bool pfb_sees_zero_history(const PfbLaunch &p)
 }
 
 // frames per chunk (= per workgroup) of this shape's kernel
-int pfb_chunk_frames(int NB) { return pfb_frame_major(NB) ? 16 / (NB / 400) : F; }
+int pfb_chunk_frames(int NB)
+{
+    if (pfbm_bins(NB)) return pfbm_chunk_frames(NB);
+    return pfb_frame_major(NB) ? 16 / (NB / 400) : F;
+}
+
+int pfb_shape_family(int NB, int D, int P)
+{
+    if (!pfb_supported(NB, D, P)) return 0;
+    if (pfbm_bins(NB)) return 3;
+    return NB % 25 == 0 ? 2 : 1;
+}
 
 bool launch_pfb_group(const PfbLaunch &shape, const PfbLaunch *d_pls, const GroupMap &gm, hipStream_t s)
 {

@@ -135,6 +135,12 @@ int rcf_pfb_shape_supported(int n_bins, int decim, int ntaps)
     return pfb_supported(n_bins, decim, (ntaps + n_bins - 1) / n_bins) ? 1 : 0;
 }
 
+int rcf_pfb_shape_family(int n_bins, int decim, int ntaps)
+{
+    if (n_bins < 1 || decim < 1 || ntaps < 1 || n_bins % decim) return 0;
+    return pfb_shape_family(n_bins, decim, (ntaps + n_bins - 1) / n_bins);
+}
+
 int64_t rcf_pfb_produced(rcf_t *h)
 {
     if (!h) return RCF_EINVAL;

@@ -8,7 +8,7 @@
 // launches ONE kernel per stage:
 //   group_prep_kernel          wire format -> cf32 for every member (pinned host memory read in place), history tails
 //                              dual-written, the group's launch records host -> device        (ingest.hip)
-//   pfb_group_kernel_* / pfb5_group_kernel   the chunks of every member of one bank shape   (pfb.hip, pfb5.hip)
+//   pfb_group_kernel_* / pfb5_group_kernel / pfbm_group_kernel   the chunks of every member of one bank shape   (pfb.hip, pfb5.hip, pfbm.hip)
 //   fir_small_kernel / fir_bank_kernel       stage-2 channels of all members of one (D, T) class (records concatenated)
 //   tap_finalize_group_kernel  the tapped bins of every member                               (tapfin.hip)
 //   disc / fm_fir / agc / rot_fill   records concatenated

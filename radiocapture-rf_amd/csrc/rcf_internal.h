@@ -304,7 +304,7 @@ struct PfbLaunch {
     //   tiled (pfb.hip, power-of-two banks)   bins_ring[(i >> 4) tile_pitch + 16 k + (i & 15)]: a chunk of 16 frames is ONE
     //     contiguous run of 16 NB samples for the writer, and a bin's 16 frames are one 128-byte line for its readers
     //     (the first layout -- one ring per bin -- scattered a chunk over NB separate lines: 5 % slower)
-    //   frame_major (pfb5.hip)                bins_ring[i NB + k]: a chunk of 2-4 frames cannot fill 128-byte lines
+    //   frame_major (pfb5.hip, pfbm.hip)      bins_ring[i NB + k]: a chunk of 2-4 frames cannot fill 128-byte lines
     //     per bin; whole frames leave as contiguous rows
     int32_t frame_major;
     int32_t n_taps;
@@ -486,7 +486,16 @@ bool pfb5_fm_sees_zero_history(const PfbLaunch &p);
 bool pfb5_xcd_map_ok(int device, hipStream_t s);
 size_t pfb5_fm_history(int NB, int D, int P);
 void launch_pfb5_fm_inc(const double *d_dangle, float2 *d_inc, int NB, hipStream_t s);
-inline bool pfb_frame_major(int NB) { return NB % 25 == 0; }
+// bin counts of the mixed-radix family (pfbm.hip): 160, 192, 480, 640, 960, 1280 at D = NB / 2, <= 2 taps per branch -- the
+// reference's 2 / 2.4 / 6 / 8 / 12 / 16 Msps sources on the 12.5 kHz raster.  Frame-major like pfb5.hip's, no fused discriminator.
+bool pfbm_bins(int NB);
+bool pfbm_dispatch(const PfbLaunch &p, bool probe, hipStream_t s);
+bool pfbm_dispatch_group(const PfbLaunch &p, const PfbLaunch *d_pls, const GroupMap &gm, hipStream_t s);
+int pfbm_padded_p(int NB, int D, int P);
+int pfbm_chunk_frames(int NB);
+// which kernel family serves the shape: 0 none, 1 power of two (pfb.hip), 2 400 2^k (pfb5.hip), 3 mixed radix (pfbm.hip)
+int pfb_shape_family(int NB, int D, int P);
+inline bool pfb_frame_major(int NB) { return NB % 25 == 0 || pfbm_bins(NB); }
 // dst[i] = view sample (first + i), i < n (one bin's samples out of a bank ring; ingest.hip)
 void launch_gather_view(const StreamView &v, int64_t first, float2 *dst, size_t n, hipStream_t s);
 // one ring segment of a host read, in 4-byte words: dst[dst_w + w] = ring[(pos_w + w) & mask_w], w < n_w.  Every host read of a

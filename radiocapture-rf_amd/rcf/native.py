@@ -37,7 +37,7 @@ SYMBOLS = [
     "rcf_design_firdes", "rcf_design_optfir_low_pass", "rcf_design_fm_deemph", "rcf_design_resampler", "rcf_chan_audio_open",
     "rcf_chan_audio_close", "rcf_chan_audio_produced", "rcf_chan_read_audio",
     "rcf_host_alloc", "rcf_host_free", "rcf_comm_unique_id", "rcf_comm_init", "rcf_comm_destroy", "rcf_comm_size",
-    "rcf_allgather_peaks", "rcf_allreduce_max", "rcf_pfb_tap_open", "rcf_chan_set_fm_only", "rcf_pfb_shape_supported",
+    "rcf_allgather_peaks", "rcf_allreduce_max", "rcf_pfb_tap_open", "rcf_chan_set_fm_only", "rcf_pfb_shape_supported", "rcf_pfb_shape_family",
     "rcf_pfb_tap_leakage", "rcf_set_rotator", "rcf_timing_stride", "rcf_set_stage2_lag",
     "rcf_group_open", "rcf_group_close", "rcf_group_size", "rcf_group_push", "rcf_group_commit", "rcf_group_read_many",
     "rcf_group_sync", "rcf_pump_start", "rcf_pump_stats", "rcf_pump_written", "rcf_pump_read", "rcf_pump_read_many", "rcf_pump_subscribe", "rcf_pump_unsubscribe", "rcf_pump_stop",
@@ -162,6 +162,7 @@ def lib():
         "rcf_pfb_tap_open": (C.c_int, [vp, C.c_int, C.c_int, ip]),
         "rcf_chan_set_fm_only": (C.c_int, [vp, C.c_int, C.c_int]),
         "rcf_pfb_shape_supported": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+        "rcf_pfb_shape_family": (C.c_int, [C.c_int, C.c_int, C.c_int]),
         "rcf_pfb_tap_leakage": (C.c_int, [C.c_double, C.c_int, fp, C.c_int, C.c_int, C.POINTER(C.c_double),
                                           C.POINTER(C.c_double)]),
         "rcf_scan_start": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),
@@ -305,6 +306,11 @@ def channel_params(samp_rate, channel_rate, decim_rule=DECIM_EXACT):
 
 def pfb_shape_supported(n_bins, decim, ntaps) -> bool:
     return bool(lib().rcf_pfb_shape_supported(int(n_bins), int(decim), int(ntaps)))
+
+
+def pfb_shape_family(n_bins, decim, ntaps) -> int:
+    """kernel family of a bank shape: 0 none, 1 power-of-two bins, 2 400 * 2^k bins, 3 mixed radix (160 .. 1280 bins)"""
+    return int(lib().rcf_pfb_shape_family(int(n_bins), int(decim), int(ntaps)))
 
 
 def pfb_tap_leakage(samp_rate, n_bins, taps, bin):

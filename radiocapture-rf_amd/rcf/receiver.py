@@ -112,6 +112,10 @@ class receiver:
                               bins served by the bank; measure it as 10 log10(mean |x|^2 / carrier power)
           pfb_parity_gain     discriminator gain of the consumers (default P25's out_rate / (2 pi 600))
           pfb_parity_margin   measured / predicted safety factor (2.5)
+          pfb_mixed_radix     True: also open the banks of the mixed-radix family (native.pfb_shape_family == 3: 160, 192,
+                              480, 640, 960, 1280 bins -- 2, 2.4, 6, 8, 12, 16 Msps on the 12.5 kHz grid).  Default False:
+                              those rates were served by direct channels before the family existed, and a deployment does
+                              not change its serving path through a library upgrade
         How requests were routed is logged per channel and counted in metrics() (rcf_pfb_served_by_bank,
         rcf_pfb_direct_parity_budget, rcf_pfb_direct_off_grid)."""
         from . import native
@@ -124,6 +128,11 @@ class receiver:
         n_bins = samp_rate / grid
         if n_bins != int(n_bins) or int(n_bins) % decim or not native.pfb_shape_supported(int(n_bins), decim, ntaps):
             self.log.warning("no filterbank kernel for fs=%s grid=%s: direct channels only" % (samp_rate, grid))
+            return None
+        if native.pfb_shape_family(int(n_bins), decim, ntaps) == 3 and not getattr(self.config, "pfb_mixed_radix", False):
+            self.log.warning("no filterbank kernel for fs=%s grid=%s: direct channels only "
+                             "(a %d-bin mixed-radix bank exists: config.pfb_mixed_radix = True opens it)"
+                             % (samp_rate, grid, int(n_bins)))
             return None
         taps = native.design_low_pass_2(1.0, samp_rate, cr / 2, cr / 2, 20.0)
         fe.pfb_open(int(n_bins), decim, taps)
