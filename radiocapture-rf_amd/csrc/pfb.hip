@@ -657,23 +657,23 @@ __global__ __launch_bounds__(NH, MINW) void pfb_group_kernel_2b(const PfbLaunch 
     pfb_2b_chunk<NH, P, false>(p, wg, threadIdx.x, buf, tw_lds);
 }
 
-// The form of the kernel is a function of the shape:
+// The form of the kernel is a function of the shape (pfb_shape.h: pfb1_two_branch, pfb1_persistent):
 //   * critically sampled banks of >= 512 bins: the two-branch kernel (pfb_kernel_2b), zero history or not;
 //   * oversampled banks of >= 512 bins: the persistent kernel (pfb_kernel_pp; 2 / 1 workgroups per CU at 512 / 1024 bins:
 //     +2 % / +10 %), and the plain kernel's zero-history instantiation while the launch still sees zero history;
 //   * 256 bins and below: the plain kernel (pfb_kernel_os).  Four independent workgroups per CU already overlap their
 //     phases, and the persistent form's extra barrier per chunk cost 8 % (measured, block 2^25); 256 bins as 128-thread
 //     two-branch workgroups, eight per CU, reached 0.56-0.60 of the HBM peak against the plain kernel's 0.63.
-template <int NB, int OS> constexpr bool pfb_is_two_branch() { return OS == 1 && NB >= 512; }
-template <int NB, int OS> constexpr bool pfb_is_persistent() { return OS != 1 && NB >= 512; }
+static_assert(F == kPfb1ChunkFrames && kSmallThreads == kPfbS2Bins, "pfb_shape.h describes these kernels");
 
 // the stage-2 rider's batches, a multiple of 8 workgroups each (1 = all riders first).  Fused launch on one box, filterbank
 // alone 101.3 us: 1 batch 114.8, 4: 114.4, 16: 114.3, 64: 112.7 us (all riders LAST: the same as 64) -- the rider costs
 // its ~50 MB of traffic wherever it sits, the trailing launch cost 18 us
 constexpr int kS2RiderBatches = 64;
 
+// zh: the launch still sees zero history (the planner's pfb_zero_history) -- the masking instantiation
 template <int NB, int OS, int P, int MINW>
-void launch_os(const PfbLaunch &p, hipStream_t s, const S2Rider *sr_in)
+void launch_os(const PfbLaunch &p, bool zh, hipStream_t s, const S2Rider *sr_in)
 {
     const int n_wg = (p.n_frames + F - 1) / F;
     // RCF_PFB_NOREMAP=1: the plain and two-branch kernels without the XCD-aware chunk map (tools/pfb_probe.py).  Kept while
@@ -681,8 +681,7 @@ void launch_os(const PfbLaunch &p, hipStream_t s, const S2Rider *sr_in)
     static const bool no_remap = [] { const char *e = getenv("RCF_PFB_NOREMAP"); return e && atoi(e) != 0; }();
     const int arg = no_remap ? -n_wg : n_wg;
     const size_t lds = ((size_t)F * row_stride<NB>() + NB) * sizeof(cf);
-    const bool zh = (p.n_lo - (int64_t)OS * (P - 1)) * (NB / OS) - (NB - 1) < p.start_sample;
-    if constexpr (pfb_is_two_branch<NB, OS>()) {
+    if constexpr (pfb1_two_branch(NB, OS)) {
         constexpr int NH = NB / 2;
         // waves per SIMD the register budget is for: 3 / 2 workgroups per CU.  The zero-history instantiation (the
         // first launch after rcf_pfb_open only) masks rows and gets 256 VGPRs instead of spilling
@@ -699,7 +698,7 @@ void launch_os(const PfbLaunch &p, hipStream_t s, const S2Rider *sr_in)
     } else if (zh) {
         S2Rider none{};
         RCF_PFB_LAUNCH(p, (pfb_kernel_os<NB, OS, P, MINW, true>), dim3(n_wg), dim3(NB), lds, s, p, arg, none);
-    } else if constexpr (pfb_is_persistent<NB, OS>()) {
+    } else if constexpr (pfb1_persistent(NB, OS)) {
         constexpr int PF = NB >= 1024 ? 8 : 16;
         constexpr int wg_per_cu = NB == 512 ? 2 : 1;
         static const int cus = [] {
@@ -733,152 +732,77 @@ void launch_os(const PfbLaunch &p, hipStream_t s, const S2Rider *sr_in)
     }
 }
 
-// grouped launch of one shape; false: this shape has no grouped form (the oversampled persistent kernels), the caller
-// launches its members one by one
+// grouped launch of one shape (steady state only).  The oversampled persistent kernels have no grouped form
+// (PfbShape::grouped is false for them: rcf_group.cpp launches such members one by one and never comes here)
 template <int NB, int OS, int P, int MINW>
-bool launch_os_group(const PfbLaunch *d_pls, const GroupMap &gm, hipStream_t s)
+void launch_os_group(const PfbLaunch *d_pls, const GroupMap &gm, hipStream_t s)
 {
-    if constexpr (pfb_is_two_branch<NB, OS>()) {
+    if constexpr (pfb1_two_branch(NB, OS)) {
         constexpr int NH = NB / 2;
         constexpr int MW2 = NH == 256 ? 3 : 4;
         const size_t lds2 = ((size_t)F * row_stride<NH>() + NB) * sizeof(cf);
         static DynLdsAttr attr;
         attr.ensure((const void *)pfb_group_kernel_2b<NH, P, MW2>, lds2);
         hipLaunchKernelGGL((pfb_group_kernel_2b<NH, P, MW2>), dim3(gm.total_wg), dim3(NH), lds2, s, d_pls, gm);
-        return true;
-    } else if constexpr (pfb_is_persistent<NB, OS>()) {
-        return false;
-    } else {
+    } else if constexpr (!pfb1_persistent(NB, OS)) {
         const size_t lds = ((size_t)F * row_stride<NB>() + NB) * sizeof(cf);
         hipLaunchKernelGGL((pfb_group_kernel_os<NB, OS, P, MINW>), dim3(gm.total_wg), dim3(NB), lds, s, d_pls, gm);
-        return true;
     }
 }
 
-// taps per branch the kernels are instantiated for.  14 is what the reference's own low_pass_2 rule with a
-// Blackman-Harris window gives a critically sampled bank of ANY size (transition 0.2 bin, 60 dB -> 13.6 taps
-// per branch), so that case gets its exact row count instead of 16.
-int round_p(int P, int OS)
+// one (OS, rows) instantiation of a bin count; d_pls != nullptr: the grouped launch (gm the chunk map)
+template <int NB, int OS, int P>
+void launch_nb(const PfbLaunch &p, bool zh, hipStream_t s, const PfbLaunch *d_pls, const GroupMap *gm, const S2Rider *sr)
 {
-    if (P <= 4) return 4;
-    if (OS == 1 && P > 8 && P <= 14) return 14;
-    if (P <= 16) return 16;
-    return 0;
-}
-
-// d_pls != nullptr: the grouped launch of this shape (p is the members' common shape; gm the chunk map)
-template <int NB>
-bool dispatch_nb(const PfbLaunch &p, int OS, int P, bool probe, hipStream_t s, const PfbLaunch *d_pls = nullptr,
-                 const GroupMap *gm = nullptr, const S2Rider *sr = nullptr)
-{
-    const int PR = round_p(P, OS);
-    if (PR == 0 || (OS != 1 && OS != 2)) return false;
-    if (probe) return true;
     // waves per SIMD the register allocator must allow: 4 workgroups per CU is the LDS limit
     constexpr int MW = NB >= 1024 ? 4 : (NB >= 512 ? 4 : 4 * NB / 256 > 0 ? (4 * NB / 256 > 8 ? 8 : (4 * NB / 256 < 1 ? 1 : 4 * NB / 256)) : 1);
-    if (d_pls) {
-        if (OS == 1) {
-            if (PR == 4) return launch_os_group<NB, 1, 4, MW>(d_pls, *gm, s);
-            if (PR == 14) return launch_os_group<NB, 1, 14, MW>(d_pls, *gm, s);
-            return launch_os_group<NB, 1, 16, MW>(d_pls, *gm, s);
-        }
-        if (PR == 4) return launch_os_group<NB, 2, 4, MW>(d_pls, *gm, s);
-        return launch_os_group<NB, 2, 16, MW>(d_pls, *gm, s);
-    }
-    if (OS == 1) {
-        if (PR == 4) launch_os<NB, 1, 4, MW>(p, s, sr);
-        else if (PR == 14) launch_os<NB, 1, 14, MW>(p, s, sr);
-        else launch_os<NB, 1, 16, MW>(p, s, sr);
-    }
-    else         { if (PR == 4) launch_os<NB, 2, 4, MW>(p, s, sr); else launch_os<NB, 2, 16, MW>(p, s, sr); }
-    return true;
+    if (d_pls) launch_os_group<NB, OS, P, MW>(d_pls, *gm, s);
+    else       launch_os<NB, OS, P, MW>(p, zh, s, sr);
 }
 
-bool dispatch(const PfbLaunch &p, bool probe, hipStream_t s, const PfbLaunch *d_pls = nullptr, const GroupMap *gm = nullptr,
-              const S2Rider *sr = nullptr)
+// the row counts pfb1_round_p yields: 4, 14 (OS = 1 only), 16
+template <int NB>
+void dispatch_nb(const PfbShape &sh, const PfbLaunch &p, bool zh, hipStream_t s, const PfbLaunch *d_pls, const GroupMap *gm,
+                 const S2Rider *sr)
 {
-    if (p.D <= 0 || p.NB % p.D) return false;
-    const int OS = p.NB / p.D;
-    switch (p.NB) {
-        case 64:   return dispatch_nb<64>(p, OS, p.P, probe, s, d_pls, gm, sr);
-        case 128:  return dispatch_nb<128>(p, OS, p.P, probe, s, d_pls, gm, sr);
-        case 256:  return dispatch_nb<256>(p, OS, p.P, probe, s, d_pls, gm, sr);
-        case 512:  return dispatch_nb<512>(p, OS, p.P, probe, s, d_pls, gm, sr);
-        case 1024: return dispatch_nb<1024>(p, OS, p.P, probe, s, d_pls, gm, sr);
-        default:
-            if (pfbm_bins(p.NB))                          // 160 / 192 / 480 / 640 / 960 / 1280 bins (pfbm.hip)
-                return d_pls ? pfbm_dispatch_group(p, d_pls, *gm, s) : pfbm_dispatch(p, probe, s);
-            return d_pls ? pfb5_dispatch_group(p, d_pls, *gm, s) : pfb5_dispatch(p, probe, s);      // 400 / 800 / 1600 / 3200 bins (pfb5.hip)
+    if (sh.OS == 1) {
+        if (sh.Ppad == 4) launch_nb<NB, 1, 4>(p, zh, s, d_pls, gm, sr);
+        else if (sh.Ppad == 14) launch_nb<NB, 1, 14>(p, zh, s, d_pls, gm, sr);
+        else launch_nb<NB, 1, 16>(p, zh, s, d_pls, gm, sr);
+    } else {
+        if (sh.Ppad == 4) launch_nb<NB, 2, 4>(p, zh, s, d_pls, gm, sr);
+        else launch_nb<NB, 2, 16>(p, zh, s, d_pls, gm, sr);
+    }
+}
+
+void dispatch(const PfbShape &sh, const PfbLaunch &p, bool zh, hipStream_t s, const PfbLaunch *d_pls, const GroupMap *gm,
+              const S2Rider *sr)
+{
+    switch (sh.family) {
+        case 1:
+            switch (sh.NB) {
+#define RCF_X(NB_) case NB_: return dispatch_nb<NB_>(sh, p, zh, s, d_pls, gm, sr);
+                RCF_PFB1_SHAPES(RCF_X)
+#undef RCF_X
+            }
+            return;
+        case 2: return d_pls ? pfb5_launch_group(sh, p, d_pls, *gm, s) : pfb5_launch(sh, p, zh, s);
+        case 3: return d_pls ? pfbm_launch_group(sh, d_pls, *gm, s) : pfbm_launch(sh, p, zh, s);
     }
 }
 
 }  // namespace
 
-// taps buffer must hold round-up(P) rows: see pfb_padded_p()
-bool pfb_supported(int NB, int D, int P)
-{
-    PfbLaunch p{};
-    p.NB = NB; p.D = D; p.P = P;
-    return dispatch(p, true, nullptr);
-}
-
-int pfb_padded_p(int NB, int D, int P)
-{
-    if (NB % 25 == 0) return pfb5_padded_p(NB, D, P);
-    if (pfbm_bins(NB)) return pfbm_padded_p(NB, D, P);
-    return round_p(P, D > 0 ? NB / D : 1);
-}
-
-bool pfb_takes_rider(const PfbLaunch &p)
-{
-    if (pfb_frame_major(p.NB)) return false;            // pfb5_kernel: measured, +5.7 us on the 1600-bin launch for 4.7 saved
-    // every form but the persistent one (oversampled banks of >= 512 bins).  A launch that still sees zero history runs
-    // the plain form whatever the bin count: being wrong about that one launch costs a late start, nothing else
-    return p.NB < 512 || (p.D > 0 ? p.NB / p.D : 1) == 1;
-}
-
-void launch_pfb(const PfbLaunch &p, hipStream_t s, const S2Rider *sr)
+void launch_pfb(const PfbShape &sh, const PfbLaunch &p, bool zero_history, hipStream_t s, const S2Rider *sr)
 {
     if (p.n_frames <= 0) return;
-    dispatch(p, false, s, nullptr, nullptr, sr);
+    dispatch(sh, p, zero_history, s, nullptr, nullptr, sr);
 }
 
-// whether THIS launch runs the kernel that can carry a stage-2 rider: the 256-bin steady-state kernel (its workgroups have
-// the small-T tile's 256 threads)
-bool pfb_can_carry_s2(const PfbLaunch &p)
+void launch_pfb_group(const PfbShape &sh, const PfbLaunch &member, const PfbLaunch *d_pls, const GroupMap &gm, hipStream_t s)
 {
-    if (p.NB != kSmallThreads || pfb_frame_major(p.NB) || p.D <= 0 || p.n_frames <= 0) return false;
-    const int OS = p.NB / p.D;
-    if ((OS != 1 && OS != 2) || round_p(p.P, OS) == 0) return false;
-    return !pfb_sees_zero_history(p);
-}
-
-// whether this launch still reaches samples before the bank's start (it then runs the masking instantiation, alone)
-bool pfb_sees_zero_history(const PfbLaunch &p)
-{
-    const int OS = p.D > 0 ? p.NB / p.D : 1;
-    const int P = pfb_padded_p(p.NB, p.D, p.P);
-    return (p.n_lo - (int64_t)OS * (P - 1)) * (int64_t)p.D - (p.NB - 1) < p.start_sample;
-}
-
-// frames per chunk (= per workgroup) of this shape's kernel
-int pfb_chunk_frames(int NB)
-{
-    if (pfbm_bins(NB)) return pfbm_chunk_frames(NB);
-    return pfb_frame_major(NB) ? 16 / (NB / 400) : F;
-}
-
-int pfb_shape_family(int NB, int D, int P)
-{
-    if (!pfb_supported(NB, D, P)) return 0;
-    if (pfbm_bins(NB)) return 3;
-    return NB % 25 == 0 ? 2 : 1;
-}
-
-bool launch_pfb_group(const PfbLaunch &shape, const PfbLaunch *d_pls, const GroupMap &gm, hipStream_t s)
-{
-    if (gm.total_wg <= 0) return true;
-    return dispatch(shape, false, s, d_pls, &gm);
+    if (gm.total_wg <= 0) return;
+    dispatch(sh, member, false, s, d_pls, &gm, nullptr);
 }
 
 }  // namespace rcfx

@@ -826,8 +826,10 @@ int pfb5_fm_span_for(int n_chunks)
     return best;
 }
 
+// zh: zero history also when the HALO chunk before the launch's first frame reaches before the stream's start (the planner's
+// pfb_zero_history with one chunk of halo)
 template <int R, int R3, int OS, int P>
-void launch5_fm(const PfbLaunch &p0, hipStream_t s)
+void launch5_fm(const PfbLaunch &p0, bool zh, hipStream_t s)
 {
     constexpr int NB = R * R * R3, F = 16 / R3;
     PfbLaunch p = p0;
@@ -835,8 +837,6 @@ void launch5_fm(const PfbLaunch &p0, hipStream_t s)
     if (p.fm_span <= 0) p.fm_span = pfb5_fm_span_for(n_chunks);
     const int n_wg = (n_chunks + p.fm_span - 1) / p.fm_span;
     const size_t lds = (size_t)pfb5_buf(NB, R, F, OS, P) * sizeof(cf);
-    // zero history also when the HALO chunk before the launch's first frame reaches before the stream's start
-    const bool zh = (p.n_lo - F - (int64_t)OS * (P - 1)) * (NB / OS) - (NB - 1) < p.start_sample;
 #define RCF_FM_GO(ZH_, FM_)                                                                                       \
     do {                                                                                                           \
         static DynLdsAttr attr;                                                                                    \
@@ -861,7 +861,7 @@ void launch5_fm(const PfbLaunch &p0, hipStream_t s)
 }
 
 template <int R, int R3, int OS, int P>
-void launch5(const PfbLaunch &p, hipStream_t s)
+void launch5(const PfbLaunch &p, bool zh, hipStream_t s)
 {
     constexpr int NB = R * R * R3, F = 16 / R3;
     const int n_wg = (p.n_frames + F - 1) / F;
@@ -869,81 +869,49 @@ void launch5(const PfbLaunch &p, hipStream_t s)
     static DynLdsAttr attr_f, attr_t;
     attr_f.ensure(reinterpret_cast<const void *>(pfb5_kernel<R, R3, OS, P, false>), lds);
     attr_t.ensure(reinterpret_cast<const void *>(pfb5_kernel<R, R3, OS, P, true>), lds);
-    const bool zh = (p.n_lo - (int64_t)OS * (P - 1)) * (NB / OS) - (NB - 1) < p.start_sample;
     if (zh) RCF_PFB_LAUNCH(p, (pfb5_kernel<R, R3, OS, P, true>), dim3(n_wg), dim3(kThreads5), lds, s, p, n_wg);
     else    RCF_PFB_LAUNCH(p, (pfb5_kernel<R, R3, OS, P, false>), dim3(n_wg), dim3(kThreads5), lds, s, p, n_wg);
 }
 
+// one row of RCF_PFB5_SHAPES: the kernels it has are the ones its flags name, and only those are instantiated
+template <int R, int R3, int OS, int P, bool FUSED>
+void launch5_row(const PfbLaunch &p, bool zh, hipStream_t s)
+{
+    if constexpr (FUSED) {
+        if (p.fm_ring) return launch5_fm<R, R3, OS, P>(p, zh, s);
+    }
+    launch5<R, R3, OS, P>(p, zh, s);
+}
+
+template <int R, int R3, int OS, int P, bool GROUPED, bool FUSED>
+void launch5_row_group(const PfbLaunch &member, const PfbLaunch *d_pls, const GroupMap &gm, hipStream_t s)
+{
+    if (member.fm_ring) {
+        if constexpr (FUSED) launch5_fmlb_group<R, R3, OS, P>(member, d_pls, gm, s);
+    } else {
+        if constexpr (GROUPED) launch5_group<R, R3, OS, P>(d_pls, gm, s);
+    }
+}
+
 }  // namespace
 
-// shapes: (NB, OS) with taps per branch P <= 2 (OS 2, 4) or <= 4 (OS 1); the reference's own prototype gives
-// P = ceil(3.64 D / NB) = 2 at OS = 2 and 1 at OS = 4
-bool pfb5_dispatch(const PfbLaunch &p, bool probe, hipStream_t s)
+// sh: a family-2 shape (pfb_shape.h); a launch with fm_ring set is a fused one (rcf_pfb_fm_enable: PfbShape::fused only)
+void pfb5_launch(const PfbShape &sh, const PfbLaunch &p, bool zh, hipStream_t s)
 {
-    if (p.D <= 0 || p.NB % p.D) return false;
-    const int OS = p.NB / p.D;
-    const int PR = pfb5_padded_p(p.NB, p.D, p.P);
-    if (PR == 0) return false;
-#define RCF_PFB5(R_, R3_, OS_, P_)                                  \
-    if (p.NB == R_ * R_ * R3_ && OS == OS_ && PR == P_) {            \
-        if (!probe) launch5<R_, R3_, OS_, P_>(p, s);                 \
-        return true;                                                 \
-    }
-    if (p.fm_ring) {
-        // the discriminator fused in: the shapes the reference's channel rule produces (OS = 2: 12.5 kHz raster, OS = 4: 6.25 kHz)
-#define RCF_PFB5F(R_, R3_, OS_, P_)                                 \
-        if (p.NB == R_ * R_ * R3_ && OS == OS_ && PR == P_) {        \
-            if (!probe) launch5_fm<R_, R3_, OS_, P_>(p, s);          \
-            return true;                                             \
-        }
-        RCF_PFB5F(20, 4, 2, 2) RCF_PFB5F(20, 8, 4, 1) RCF_PFB5F(20, 2, 2, 2) RCF_PFB5F(20, 1, 2, 2)
-#undef RCF_PFB5F
-        return false;
-    }
-    RCF_PFB5(20, 4, 2, 2) RCF_PFB5(20, 4, 2, 1) RCF_PFB5(20, 4, 1, 4) RCF_PFB5(20, 4, 4, 1)      // 1600 bins
-    RCF_PFB5(20, 8, 4, 1) RCF_PFB5(20, 8, 2, 2) RCF_PFB5(20, 8, 2, 1) RCF_PFB5(20, 8, 1, 4)      // 3200 bins
-    RCF_PFB5(20, 2, 2, 2) RCF_PFB5(20, 2, 2, 1) RCF_PFB5(20, 2, 1, 4) RCF_PFB5(20, 2, 4, 1)      // 800 bins
-    RCF_PFB5(20, 1, 2, 2) RCF_PFB5(20, 1, 2, 1) RCF_PFB5(20, 1, 1, 4) RCF_PFB5(20, 1, 4, 1)      // 400 bins
-#undef RCF_PFB5
-    return false;
+#define RCF_X(R_, R3_, OS_, P_, G_, F_) \
+    if (sh.NB == R_ * R_ * R3_ && sh.OS == OS_ && sh.Ppad == P_) return launch5_row<R_, R3_, OS_, P_, F_>(p, zh, s);
+    RCF_PFB5_SHAPES(RCF_X)
+#undef RCF_X
 }
 
-bool pfb5_dispatch_group(const PfbLaunch &p, const PfbLaunch *d_pls, const GroupMap &gm, hipStream_t s)
+// member: any member's record (fused or not, which mode).  The caller has asked PfbShape::grouped / grouped_fused, and
+// groups a fused bank in its look-back form only (the span form has no grouped kernel).
+void pfb5_launch_group(const PfbShape &sh, const PfbLaunch &member, const PfbLaunch *d_pls, const GroupMap &gm, hipStream_t s)
 {
-    if (p.D <= 0 || p.NB % p.D) return false;
-    const int OS = p.NB / p.D;
-    const int PR = pfb5_padded_p(p.NB, p.D, p.P);
-    if (PR == 0) return false;
-    if (p.fm_ring) {
-        if (!p.fm_edge) return false;                    // (the span form has no grouped kernel: one by one)
-#define RCF_PFB5FG(R_, R3_, OS_, P_)                                \
-        if (p.NB == R_ * R_ * R3_ && OS == OS_ && PR == P_) {        \
-            launch5_fmlb_group<R_, R3_, OS_, P_>(p, d_pls, gm, s);   \
-            return true;                                             \
-        }
-        RCF_PFB5FG(20, 4, 2, 2) RCF_PFB5FG(20, 8, 4, 1) RCF_PFB5FG(20, 2, 2, 2) RCF_PFB5FG(20, 1, 2, 2)
-#undef RCF_PFB5FG
-        return false;
-    }
-#define RCF_PFB5G(R_, R3_, OS_, P_)                                 \
-    if (p.NB == R_ * R_ * R3_ && OS == OS_ && PR == P_) {            \
-        launch5_group<R_, R3_, OS_, P_>(d_pls, gm, s);               \
-        return true;                                                 \
-    }
-    // the shapes the reference's channel rule produces (OS = 2: 12.5 kHz raster, OS = 4: 6.25 kHz) -- the others run one by one
-    RCF_PFB5G(20, 4, 2, 2) RCF_PFB5G(20, 8, 4, 1) RCF_PFB5G(20, 8, 2, 2) RCF_PFB5G(20, 2, 2, 2) RCF_PFB5G(20, 1, 2, 2)
-#undef RCF_PFB5G
-    return false;
-}
-
-// whether the launch's halo chunks (the chunk before its first frame, recomputed by the workgroups that have no predecessor
-// inside the launch) reach before the stream's start: such a launch takes the zero-history kernel, alone
-bool pfb5_fm_sees_zero_history(const PfbLaunch &p)
-{
-    if (p.D <= 0 || p.NB % p.D || p.NB % 400) return true;
-    const int R3 = p.NB / 400, F = 16 / R3, OS = p.NB / p.D;
-    const int PR = pfb5_padded_p(p.NB, p.D, p.P);
-    return (p.n_lo - F - (int64_t)OS * (PR - 1)) * (int64_t)p.D - (p.NB - 1) < p.start_sample;
+#define RCF_X(R_, R3_, OS_, P_, G_, F_) \
+    if (sh.NB == R_ * R_ * R3_ && sh.OS == OS_ && sh.Ppad == P_) return launch5_row_group<R_, R3_, OS_, P_, G_, F_>(member, d_pls, gm, s);
+    RCF_PFB5_SHAPES(RCF_X)
+#undef RCF_X
 }
 
 namespace {
@@ -990,22 +958,6 @@ bool pfb5_xcd_map_ok(int device, hipStream_t s)
     return ok;
 }
 
-bool pfb5_fm_supported(int NB, int D, int P)
-{
-    PfbLaunch p{};
-    p.NB = NB; p.D = D; p.P = P;
-    p.fm_ring = reinterpret_cast<float *>(0x1);          // (never dereferenced: probe)
-    return pfb5_dispatch(p, true, nullptr);
-}
-
-// samples of input history the halo chunk of a launch's first workgroup reaches back over: F + OS (P - 1) + 1 frames and
-// the prototype's span
-size_t pfb5_fm_history(int NB, int D, int P)
-{
-    const int R3 = NB / 400, F = 16 / (R3 > 0 ? R3 : 1), OS = NB / D;
-    return (size_t)(F + OS * (pfb5_padded_p(NB, D, P) - 1) + 2) * (size_t)D + (size_t)NB;
-}
-
 namespace {
 __global__ void pfb5_fm_inc_kernel(const double *__restrict__ dangle, float2 *__restrict__ inc, int NB)
 {
@@ -1024,18 +976,6 @@ __global__ void pfb5_fm_inc_kernel(const double *__restrict__ dangle, float2 *__
 void launch_pfb5_fm_inc(const double *d_dangle, float2 *d_inc, int NB, hipStream_t s)
 {
     hipLaunchKernelGGL(pfb5_fm_inc_kernel, dim3((NB + 255) / 256), dim3(256), 0, s, d_dangle, d_inc, NB);
-}
-
-// rows of the polyphase table the instantiation for (NB / D, P) reads (zero padded by rcf_pfb_open); 0: no kernel.
-// Instantiated: OS = 1 with 4 taps per branch, OS = 2 with 1 or 2, OS = 4 with 1 -- fewer taps run the next larger one.
-int pfb5_padded_p(int NB, int D, int P)
-{
-    if (D <= 0 || NB % D || P < 1) return 0;
-    const int OS = NB / D;
-    if (OS == 1) return P <= 4 ? 4 : 0;
-    if (OS == 2) return P <= 1 ? 1 : (P <= 2 ? 2 : 0);
-    if (OS == 4) return P <= 1 ? 1 : 0;
-    return 0;
 }
 
 }  // namespace rcfx

@@ -30,7 +30,7 @@
 // same run; 16 to 47 times faster than the NB - 1 direct channels that give the same outputs.  These rates need real-time
 // factors in the thousands at most, and nothing was spent on the last of it (no direct-to-LDS window DMA, prototype rows
 // from L2).
-// No rider and no fused discriminator (pfb_takes_rider, rcf_pfb_fm_enable refuse frame-major banks without those forms).
+// No rider and no fused discriminator (PfbShape::takes_rider and ::fused are false for this family).
 // Build: pfb5.hip's flags -- no SLP vectoriser, no implicit contraction, the FMAs spelled out (RCF_EXPLICIT_FMA): the
 // single, grouped and zero-history instantiations round alike.
 #define RCF_EXPLICIT_FMA 1
@@ -45,10 +45,8 @@ namespace {
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kStoreAuxM = 2;          // non-temporal
-constexpr int kP = 2;                   // taps per branch the kernel reads (pfbm_padded_p): what the channel rule gives at OS = 2
-
-// frames per chunk
-constexpr int pfbm_frames(int NB) { return NB <= 192 ? 16 : (NB <= 640 ? 8 : 4); }
+constexpr int kP = kPfbmP;              // taps per branch the kernel reads (PfbShape::Ppad): what the channel rule gives at OS = 2
+// (frames per chunk: pfbm_frames, pfb_shape.h)
 // padded extent of one frame in LDS (one spare complex after every R1): odd, so the copy-out's and the taps' column walks
 // (stride = one row) spread over the banks as well
 constexpr int pfbm_row_stride(int R1, int R2) { return R1 * R2 + R2 - 1; }
@@ -214,12 +212,11 @@ __global__ __launch_bounds__(pfbm_frames(R1 * R2) * R2) void pfbm_group_kernel(c
 }
 
 template <int R1, int R2>
-void launchm(const PfbLaunch &p, hipStream_t s)
+void launchm(const PfbLaunch &p, bool zh, hipStream_t s)
 {
     constexpr int NB = R1 * R2, F = pfbm_frames(NB), TPB = F * R2;
     const int n_wg = (p.n_frames + F - 1) / F;
     const size_t lds = (size_t)pfbm_buf(R1, R2) * sizeof(cf);
-    const bool zh = (p.n_lo - (int64_t)2 * (kP - 1)) * (NB / 2) - (NB - 1) < p.start_sample;
     if (zh) RCF_PFB_LAUNCH(p, (pfbm_kernel<R1, R2, true>), dim3(n_wg), dim3(TPB), lds, s, p, n_wg);
     else    RCF_PFB_LAUNCH(p, (pfbm_kernel<R1, R2, false>), dim3(n_wg), dim3(TPB), lds, s, p, n_wg);
 }
@@ -234,47 +231,21 @@ void launchm_group(const PfbLaunch *d_pls, const GroupMap &gm, hipStream_t s)
 
 }  // namespace
 
-bool pfbm_bins(int NB) { return NB == 160 || NB == 192 || NB == 480 || NB == 640 || NB == 960 || NB == 1280; }
-
-// rows of the polyphase table the kernel reads (zero padded by rcf_pfb_open); 0: no kernel.  D = NB / 2 only, and ONE
-// instantiation per bin count: the channel rule always gives two taps per branch, a shorter prototype runs as two with
-// a row of zeros
-int pfbm_padded_p(int NB, int D, int P)
+// sh: a family-3 shape (pfb_shape.h)
+void pfbm_launch(const PfbShape &sh, const PfbLaunch &p, bool zh, hipStream_t s)
 {
-    if (!pfbm_bins(NB) || D * 2 != NB || P < 1) return 0;
-    return P <= 2 ? 2 : 0;
+#define RCF_X(R1_, R2_) \
+    if (sh.NB == R1_ * R2_) return launchm<R1_, R2_>(p, zh, s);
+    RCF_PFBM_SHAPES(RCF_X)
+#undef RCF_X
 }
 
-int pfbm_chunk_frames(int NB) { return pfbm_frames(NB); }
-
-#define RCF_PFBM_SHAPES(X) X(10, 16) X(12, 16) X(20, 24) X(20, 32) X(24, 40) X(32, 40)
-
-bool pfbm_dispatch(const PfbLaunch &p, bool probe, hipStream_t s)
+void pfbm_launch_group(const PfbShape &sh, const PfbLaunch *d_pls, const GroupMap &gm, hipStream_t s)
 {
-    const int PR = pfbm_padded_p(p.NB, p.D, p.P);
-    if (PR == 0 || p.fm_ring) return false;              // (no fused discriminator for this family)
-#define RCF_PFBM(R1_, R2_)                                           \
-    if (p.NB == R1_ * R2_) {                                         \
-        if (!probe) launchm<R1_, R2_>(p, s);                         \
-        return true;                                                 \
-    }
-    RCF_PFBM_SHAPES(RCF_PFBM)
-#undef RCF_PFBM
-    return false;
-}
-
-bool pfbm_dispatch_group(const PfbLaunch &p, const PfbLaunch *d_pls, const GroupMap &gm, hipStream_t s)
-{
-    const int PR = pfbm_padded_p(p.NB, p.D, p.P);
-    if (PR == 0 || p.fm_ring) return false;
-#define RCF_PFBMG(R1_, R2_)                                          \
-    if (p.NB == R1_ * R2_) {                                         \
-        launchm_group<R1_, R2_>(d_pls, gm, s);                       \
-        return true;                                                 \
-    }
-    RCF_PFBM_SHAPES(RCF_PFBMG)
-#undef RCF_PFBMG
-    return false;
+#define RCF_X(R1_, R2_) \
+    if (sh.NB == R1_ * R2_) return launchm_group<R1_, R2_>(d_pls, gm, s);
+    RCF_PFBM_SHAPES(RCF_X)
+#undef RCF_X
 }
 
 }  // namespace rcfx

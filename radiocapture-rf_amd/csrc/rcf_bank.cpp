@@ -60,11 +60,12 @@ int rcf_pfb_open(rcf_t *h, int n_bins, int decim, const float *taps, int ntaps)
     if (set_dev(h)) return RCF_EHIP;
     if (h->pfb.open) { set_error("PFB already open"); return RCF_ESTATE; }
     const int P = (ntaps + n_bins - 1) / n_bins;
-    if (n_bins % decim || !pfb_supported(n_bins, decim, P)) {
+    const PfbShape sh = pfb_shape(n_bins, decim, P);
+    if (!sh.family) {
         set_error("unsupported PFB shape: bins=%d decim=%d taps/branch=%d", n_bins, decim, P);
         return RCF_EINVAL;
     }
-    const bool fm = pfb_frame_major(n_bins);
+    const bool fm = sh.frame_major;
     if (!fm && h->out_cap < (size_t(1) << kPfbTileLog2)) { set_error("output capacity %zu < one ring tile", h->out_cap); return RCF_ECAP; }
     const size_t ring_samples = fm ? (size_t)n_bins * h->out_cap : (size_t)(h->out_cap >> kPfbTileLog2) * (size_t)pfb_tile_pitch(n_bins);
     // 32-bit buffer offsets: the wideband buffer, and the tiled ring of the power-of-two banks (one descriptor for the
@@ -76,10 +77,10 @@ int rcf_pfb_open(rcf_t *h, int n_bins, int decim, const float *taps, int ntaps)
     }
     if ((size_t)P * n_bins + (size_t)decim > h->hist_cap) { set_error("history capacity %zu < P*bins", h->hist_cap); return RCF_ECAP; }
     Pfb &p = h->pfb;
+    p.shape = sh;
     p.NB = n_bins; p.D = decim; p.T = ntaps; p.P = P;
     p.proto.assign(taps, taps + ntaps);
-    p.Ppad = pfb_padded_p(n_bins, decim, P);
-    std::vector<float> pt((size_t)p.Ppad * n_bins, 0.f);
+    std::vector<float> pt((size_t)sh.Ppad * n_bins, 0.f);
     for (int i = 0; i < ntaps; ++i) pt[i] = taps[i];          // pt[p*NB + rho] = h[NB p + rho]
     std::vector<float> tw(2 * (size_t)n_bins);
     for (int i = 0; i < n_bins; ++i) {
@@ -91,7 +92,6 @@ int rcf_pfb_open(rcf_t *h, int n_bins, int decim, const float *taps, int ntaps)
     RCF_HIP(hipMemcpy(p.d_ptaps, pt.data(), sizeof(float) * pt.size(), hipMemcpyHostToDevice));
     RCF_HIP(hipMalloc(&p.d_tw, sizeof(float2) * (size_t)n_bins));
     RCF_HIP(hipMemcpy(p.d_tw, tw.data(), sizeof(float2) * (size_t)n_bins, hipMemcpyHostToDevice));
-    p.frame_major = fm;
     RCF_HIP(hipMalloc(&p.d_bins, sizeof(float2) * ring_samples));
     RCF_HIP(hipMemsetAsync(p.d_bins, 0, sizeof(float2) * ring_samples, h->stream));
     p.rd.assign(n_bins, 0);
@@ -131,14 +131,14 @@ int rcf_pfb_tap_leakage(double samp_rate, int n_bins, const float *taps, int nta
 
 int rcf_pfb_shape_supported(int n_bins, int decim, int ntaps)
 {
-    if (n_bins < 1 || decim < 1 || ntaps < 1 || n_bins % decim) return 0;
-    return pfb_supported(n_bins, decim, (ntaps + n_bins - 1) / n_bins) ? 1 : 0;
+    if (n_bins < 1 || ntaps < 1) return 0;
+    return pfb_shape(n_bins, decim, (ntaps + n_bins - 1) / n_bins).family ? 1 : 0;
 }
 
 int rcf_pfb_shape_family(int n_bins, int decim, int ntaps)
 {
-    if (n_bins < 1 || decim < 1 || ntaps < 1 || n_bins % decim) return 0;
-    return pfb_shape_family(n_bins, decim, (ntaps + n_bins - 1) / n_bins);
+    if (n_bins < 1 || ntaps < 1) return 0;
+    return pfb_shape(n_bins, decim, (ntaps + n_bins - 1) / n_bins).family;
 }
 
 int64_t rcf_pfb_produced(rcf_t *h)
@@ -195,11 +195,11 @@ int rcf_pfb_fm_enable(rcf_t *h, int mode, int gr_phase)
         p.fm_mode = 0;
         return RCF_OK;
     }
-    if (!p.frame_major || !pfb5_fm_supported(p.NB, p.D, p.P)) {
+    if (!p.shape.fused) {
         set_error("no fused-discriminator kernel for bins=%d decim=%d taps/branch=%d", p.NB, p.D, p.P);
         return RCF_EINVAL;
     }
-    const size_t need = pfb5_fm_history(p.NB, p.D, p.P);
+    const size_t need = p.shape.fused_history;
     if (need > h->hist_cap) { set_error("history capacity %zu < %zu (the fused discriminator's halo chunk)", h->hist_cap, need); return RCF_ECAP; }
     if (!p.d_fm) {
         // The look-back form's hand-over rows (RCF_PFB5_FM_LOOKBACK=0: the span form, which needs none).  Chunk c of a launch
@@ -210,7 +210,7 @@ int rcf_pfb_fm_enable(rcf_t *h, int mode, int gr_phase)
         // one's: launches of one bank run in stream order and every launch has its own tag (plan_pfb).
         static const bool lookback = [] { const char *e = getenv("RCF_PFB5_FM_LOOKBACK"); return !e || atoi(e) != 0; }();
         const int64_t max_frames = std::min<int64_t>((int64_t)h->out_cap, ceil_div((int64_t)h->block_cap, p.D));
-        const int64_t slots = lookback ? ceil_div(max_frames, pfb_chunk_frames(p.NB)) : 0;
+        const int64_t slots = lookback ? ceil_div(max_frames, p.shape.chunk_frames) : 0;
         if (slots > (int64_t(1) << 27)) { set_error("output capacity %zu: too many hand-over rows for the fused discriminator", h->out_cap); return RCF_ECAP; }
         p.rd_fm.assign((size_t)p.NB, p.produced);
         // all or nothing: every buffer goes into a local first, the bank takes them only once all of them exist
@@ -302,7 +302,7 @@ int rcf_pfb_rings(rcf_t *h, void **bins_ring, size_t *capacity, size_t *pitch)
     if (h->pfb.fm_mode == 2) { set_error("the bank writes its discriminator ring only (rcf_pfb_fm_enable mode 2): no bins ring"); return RCF_ESTATE; }
     if (bins_ring) *bins_ring = h->pfb.d_bins;
     if (capacity) *capacity = h->out_cap;
-    if (pitch) *pitch = h->pfb.frame_major ? 0 : (size_t(1) << kPfbTileLog2);   // frames per tile (0: frame-major)
+    if (pitch) *pitch = h->pfb.shape.frame_major ? 0 : (size_t(1) << kPfbTileLog2);   // frames per tile (0: frame-major)
     return RCF_OK;
 }
 

@@ -20,7 +20,7 @@ bool source_range(rcf_t *h, int src, int64_t S0, int64_t S1, SrcRange *out)
     if (src >= RCF_SRC_PFB_BIN0) {
         if (!h->pfb.open) return false;
         const int bin = src - RCF_SRC_PFB_BIN0;
-        if (h->pfb.frame_major) {                           // bins_ring[i NB + bin]
+        if (h->pfb.shape.frame_major) {                           // bins_ring[i NB + bin]
             out->view.base = h->pfb.d_bins + bin;
             out->view.stride = h->pfb.NB;
             out->view.tshift = 0;
@@ -333,9 +333,9 @@ int rcf_pfb_tap_open(rcf_t *h, int bin, int gr_phase, int *chan_id)
     Pfb &p = h->pfb;
     if (!p.open || bin < 0 || bin >= p.NB) { set_error("no such PFB bin %d", bin); return RCF_EINVAL; }
     const float one = 1.0f;
-    int rc = new_channel(h, RCF_SRC_PFB_BIN0 + bin, 1, &one, 1, 0.0, chan_id, p.frame_major);
+    int rc = new_channel(h, RCF_SRC_PFB_BIN0 + bin, 1, &one, 1, 0.0, chan_id, p.shape.frame_major);
     if (rc != RCF_OK) return rc;
-    h->chans[*chan_id]->is_tap = p.frame_major;     // power-of-two banks: an ordinary D = 1, T = 1 channel on the bin's ring
+    h->chans[*chan_id]->is_tap = p.shape.frame_major;     // power-of-two banks: an ordinary D = 1, T = 1 channel on the bin's ring
     ++h->chans_epoch;                                // (the planning summary counts taps and FIR channels differently)
     if (gr_phase) {
         // What GNU Radio's freq_xlating_fir_filter_ccc(D, h, f_k, fs) would have done differently from the bank's

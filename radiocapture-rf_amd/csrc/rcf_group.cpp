@@ -108,26 +108,31 @@ int rcfx::group_process(rcf_group *g, const std::vector<GroupItem> &items, int f
     auto oom = [&]() { set_error("launch arena exhausted"); return fail_all(RCF_ENOMEM); };
 
     // ---- 4. what goes out together
-    // filterbanks: members of one shape in steady state share a launch
-    struct BankGroup { std::vector<size_t> idx; const PfbLaunch *d_pls = nullptr; GroupMap gm{}; };
-    std::map<std::tuple<int, int, int, int>, BankGroup> banks;       // (bins, decimation, taps per branch, fused-discriminator mode)
+    // filterbanks: members of one shape in steady state share a launch -- where the shape has a grouped kernel (pfb_shape.h);
+    // the members of a bucket without one go out one by one at the bucket's place
+    struct BankGroup { std::vector<size_t> idx; const PfbLaunch *d_pls = nullptr; GroupMap gm{}; bool grouped = false; };
+    std::map<std::tuple<int, int, int, int>, BankGroup> banks;       // (bins, decimation, rows of the kernel, fused-discriminator mode)
     std::vector<size_t> bank_singles;
     for (size_t i = 0; i < NI; ++i) {
         BlockPlan &bp = *plans[i];
         if (!bp.run_pfb) continue;
         bp.pl.ev_start = bp.pl.ev_stop = nullptr;
-        // (a fused-discriminator bank joins a grouped launch in its look-back form only, and not while the chunk before
-        // its first frame -- which its first workgroup recomputes -- reaches before the stream's start)
-        if (pfb_sees_zero_history(bp.pl) || (bp.pl.fm_ring && (!bp.pl.fm_edge || pfb5_fm_sees_zero_history(bp.pl)))) {
+        // (the grouped kernels have no masking form: plan_pfb's answer -- for a fused bank it covers the chunk before its
+        // first frame, which its first workgroup recomputes; and such a bank joins in its look-back form only)
+        if (bp.pfb_zero_history || (bp.pl.fm_ring && !bp.pl.fm_edge)) {
             bank_singles.push_back(i);
             continue;
         }
-        banks[std::make_tuple(bp.pl.NB, bp.pl.D, pfb_padded_p(bp.pl.NB, bp.pl.D, bp.pl.P), bp.pl.fm_ring ? bp.pl.fm_mode : 0)].idx.push_back(i);
+        const PfbShape &sh = bp.shape;
+        BankGroup &bg = banks[std::make_tuple(sh.NB, sh.D, sh.Ppad, bp.pl.fm_ring ? bp.pl.fm_mode : 0)];
+        bg.grouped = bp.pl.fm_ring ? sh.grouped_fused : sh.grouped;
+        bg.idx.push_back(i);
     }
     for (auto it = banks.begin(); it != banks.end();) {
         BankGroup &bg = it->second;
         if (bg.idx.size() < 2) { bank_singles.push_back(bg.idx[0]); it = banks.erase(it); continue; }
-        const int F = pfb_chunk_frames(std::get<0>(it->first));
+        if (!bg.grouped) { ++it; continue; }
+        const int F = plans[bg.idx[0]]->shape.chunk_frames;
         std::vector<PfbLaunch> pls;
         std::vector<int32_t> first;
         pls.reserve(bg.idx.size());
@@ -310,14 +315,19 @@ int rcfx::group_process(rcf_group *g, const std::vector<GroupItem> &items, int f
             }
     };
     launch_depth(0, RCF_T_FIR);
+    auto launch_single = [&](const std::vector<size_t> &idx) {
+        for (size_t i : idx) {
+            Timed t(g->members[(size_t)items[i].m], RCF_T_PFB);
+            launch_pfb(plans[i]->shape, plans[i]->pl, plans[i]->pfb_zero_history, st);
+        }
+    };
     for (auto &kv : banks) {
         BankGroup &bg = kv.second;
-        bool done;
-        { Timed t(h0, RCF_T_PFB); done = launch_pfb_group(plans[bg.idx[0]]->pl, bg.d_pls, bg.gm, st); }
-        if (!done)                                             // a shape without a grouped kernel: one by one
-            for (size_t i : bg.idx) { Timed t(g->members[(size_t)items[i].m], RCF_T_PFB); launch_pfb(plans[i]->pl, st); }
+        const BlockPlan &b0 = *plans[bg.idx[0]];
+        if (bg.grouped) { Timed t(h0, RCF_T_PFB); launch_pfb_group(b0.shape, b0.pl, bg.d_pls, bg.gm, st); }
+        else launch_single(bg.idx);
     }
-    for (size_t i : bank_singles) { Timed t(g->members[(size_t)items[i].m], RCF_T_PFB); launch_pfb(plans[i]->pl, st); }
+    launch_single(bank_singles);
     if (d_tap_args) {
         Timed t(h0, RCF_T_TAPS);
         launch_tap_finalize_group(d_tap_args, (int)tap_args.size(), tap_max_taps, tap_max_rows, h0->ring_mask, h0->d_atan, st);

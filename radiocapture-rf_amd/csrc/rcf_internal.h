@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/rcf.h"
+#include "pfb_shape.h"
 
 namespace rcfx {
 
@@ -362,12 +363,8 @@ struct PfbLaunch {
         else               hipLaunchKernelGGL(kernel, grid, block, lds, s, __VA_ARGS__);                            \
     } while (0)
 constexpr int kPfbRiderWgs = 64;    // of thousands: the few microseconds the pinned-memory reads take are lost in the first round
-// whether this launch's kernel takes the rider (pfb_kernel_os does: step of the timed configuration 128.5 -> 124.5 us,
-// kernel unchanged): the persistent form of the 512 / 1024-bin banks does not -- its
-// workgroups are ONE resident round, and 64 of them starting late set the whole launch back by what the copy launch
-// cost (cfg5: kernel +2.8 us, step unchanged; spread over all 512 workgroups: every one waits for its pinned-memory
-// word, 1600 bins +7 us)
-bool pfb_takes_rider(const PfbLaunch &p);
+// which launches take the rider: PfbShape::takes_rider (pfb_kernel_os does: step of the timed configuration 128.5 -> 124.5 us,
+// kernel unchanged)
 #ifdef __HIPCC__
 __device__ __forceinline__ void pfb_copy_rider(const PfbLaunch &p, int wg, int n_wgs, int tid, int n_threads)
 {
@@ -455,12 +452,6 @@ __device__ __forceinline__ void group_resolve(const GroupMap &m, int b, int &fe,
     wg = __builtin_amdgcn_readfirstlane(wg);
 }
 #endif
-// d_pls: the members' launch records (device); shape: any member's record (NB, D, P select the kernel).  false: this shape
-// has no grouped kernel -- launch the members one by one
-bool launch_pfb_group(const PfbLaunch &shape, const PfbLaunch *d_pls, const GroupMap &gm, hipStream_t s);
-bool pfb5_dispatch_group(const PfbLaunch &p, const PfbLaunch *d_pls, const GroupMap &gm, hipStream_t s);
-bool pfb_sees_zero_history(const PfbLaunch &p);
-int pfb_chunk_frames(int NB);
 // Stage-2 rider of a filterbank launch (pfb.hip): the small-T FIR + discriminator launch of the PREVIOUS block, run by the
 // first n_wgs workgroups of this block's filterbank kernel (its records are already in the device arena)
 struct S2Rider {
@@ -472,30 +463,24 @@ struct S2Rider {
     int32_t n_wgs;               // rider workgroups in the grid (n_batches * batch_wgs); 0: no rider
     int32_t n_batches, batch_wgs, period;   // set by the launcher: batch q occupies blocks [q period, q period + batch_wgs)
 };
-bool pfb_can_carry_s2(const PfbLaunch &p);
-bool pfb_supported(int NB, int D, int P);
-int pfb_padded_p(int NB, int D, int P);   // rows the kernel instantiation reads from ptaps (zero padded)
-void launch_pfb(const PfbLaunch &p, hipStream_t s, const S2Rider *sr = nullptr);
-// bin counts with a factor 25 (pfb5.hip): 400, 800, 1600, 3200
-bool pfb5_dispatch(const PfbLaunch &p, bool probe, hipStream_t s);
-// the fused-discriminator form of a frame-major bank (rcf_pfb_fm_enable): whether the shape has one, the input history its
-// halo chunk reaches back over, and the per-bin increment table inc[k] = (float)(cos, sin)(dangle[k]) -- computed on the
-// device with tap_finalize's own sincos_fast, so that both paths turn the discriminator's product by the same bits
-bool pfb5_fm_supported(int NB, int D, int P);
-bool pfb5_fm_sees_zero_history(const PfbLaunch &p);
+// The launchers.  sh: the bank's row of the shape table (pfb_shape.h: which kernel, how many rows of ptaps it reads);
+// zero_history: the planner's pfb_zero_history for this launch -- plan_pfb decides, nothing here derives it again.
+// sr: a stage-2 rider (PfbShape::carries_s2, steady state only).
+void launch_pfb(const PfbShape &sh, const PfbLaunch &p, bool zero_history, hipStream_t s, const S2Rider *sr = nullptr);
+// grouped launch of one shape's members in steady state (PfbShape::grouped, or ::grouped_fused for banks with the
+// discriminator fused in).  d_pls: the members' launch records (device); member: any one of them (fused or not, which mode)
+void launch_pfb_group(const PfbShape &sh, const PfbLaunch &member, const PfbLaunch *d_pls, const GroupMap &gm, hipStream_t s);
+// the families' own dispatchers (launch_pfb / launch_pfb_group call them): pfb5.hip, pfbm.hip
+void pfb5_launch(const PfbShape &sh, const PfbLaunch &p, bool zero_history, hipStream_t s);
+void pfb5_launch_group(const PfbShape &sh, const PfbLaunch &member, const PfbLaunch *d_pls, const GroupMap &gm, hipStream_t s);
+void pfbm_launch(const PfbShape &sh, const PfbLaunch &p, bool zero_history, hipStream_t s);
+void pfbm_launch_group(const PfbShape &sh, const PfbLaunch *d_pls, const GroupMap &gm, hipStream_t s);
+// the fused-discriminator form of a frame-major bank (rcf_pfb_fm_enable; PfbShape::fused, ::fused_history): whether the
+// device deals blocks to XCDs the way the look-back hand-over assumes, and the per-bin increment table
+// inc[k] = (float)(cos, sin)(dangle[k]) -- computed on the device with tap_finalize's own sincos_fast, so that both paths
+// turn the discriminator's product by the same bits
 bool pfb5_xcd_map_ok(int device, hipStream_t s);
-size_t pfb5_fm_history(int NB, int D, int P);
 void launch_pfb5_fm_inc(const double *d_dangle, float2 *d_inc, int NB, hipStream_t s);
-// bin counts of the mixed-radix family (pfbm.hip): 160, 192, 480, 640, 960, 1280 at D = NB / 2, <= 2 taps per branch -- the
-// reference's 2 / 2.4 / 6 / 8 / 12 / 16 Msps sources on the 12.5 kHz raster.  Frame-major like pfb5.hip's, no fused discriminator.
-bool pfbm_bins(int NB);
-bool pfbm_dispatch(const PfbLaunch &p, bool probe, hipStream_t s);
-bool pfbm_dispatch_group(const PfbLaunch &p, const PfbLaunch *d_pls, const GroupMap &gm, hipStream_t s);
-int pfbm_padded_p(int NB, int D, int P);
-int pfbm_chunk_frames(int NB);
-// which kernel family serves the shape: 0 none, 1 power of two (pfb.hip), 2 400 2^k (pfb5.hip), 3 mixed radix (pfbm.hip)
-int pfb_shape_family(int NB, int D, int P);
-inline bool pfb_frame_major(int NB) { return NB % 25 == 0 || pfbm_bins(NB); }
 // dst[i] = view sample (first + i), i < n (one bin's samples out of a bank ring; ingest.hip)
 void launch_gather_view(const StreamView &v, int64_t first, float2 *dst, size_t n, hipStream_t s);
 // one ring segment of a host read, in 4-byte words: dst[dst_w + w] = ring[(pos_w + w) & mask_w], w < n_w.  Every host read of a
@@ -534,7 +519,6 @@ void launch_group_prep(const PrepRec *d_recs, int n_recs, uint32_t total_tiles, 
 // dst[0, bytes) = src[0, bytes), both 8-byte aligned, bytes rounded up to 8; src may be pinned (device-mapped) host memory
 void launch_copy8(void *dst, const void *src, size_t bytes, hipStream_t s);
 void launch_copy8x2(void *d0, const void *s0, size_t bytes0, void *d1, const void *s1, size_t bytes1, hipStream_t s);
-int pfb5_padded_p(int NB, int D, int P);
 
 // ---------------------------------------------------------------- scan
 struct ScanLaunch {

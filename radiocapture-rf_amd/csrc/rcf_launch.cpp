@@ -36,7 +36,7 @@ int launch_plan(rcf_t *h, BlockPlan &bp)
     // when that launch is the kernel that can carry it and the bank's ring has room for both blocks' frames; otherwise it
     // goes out now, ahead of everything of this block.
     const size_t pfb_reach = bp.reach(RCF_SRC_PFB_BIN0);
-    const bool carry = run_pfb && pfb_can_carry_s2(pl);
+    const bool carry = run_pfb && bp.shape.carries_s2 && !bp.pfb_zero_history;
     if (h->lag.pending && !(carry && (size_t)(pl.n_frames + h->lag.frames) + pfb_reach <= h->out_cap)) flush_lagged(h);
     S2Rider sr{};
     if (h->lag.pending) {
@@ -67,7 +67,7 @@ int launch_plan(rcf_t *h, BlockPlan &bp)
         // arena), its first workgroups do both copies on the way in (PfbLaunch::rider_*)
         const bool ride = run_pfb && !d_rot_fills &&
                           (fir_by_depth.empty() || fir_by_depth[0].empty()) && pl.n_taps == pl.tap_first &&
-                          bytes / 8 < (1u << 31) && h->hist_cap < (1u << 28) && pfb_takes_rider(pl);
+                          bytes / 8 < (1u << 31) && h->hist_cap < (1u << 28) && bp.shape.takes_rider;
         if (ride) {
             pl.rider_dst[0] = reinterpret_cast<unsigned long long *>(ar.d + from);
             pl.rider_src[0] = reinterpret_cast<const unsigned long long *>(h->arenas.h_dev[a] + from);
@@ -94,7 +94,7 @@ int launch_plan(rcf_t *h, BlockPlan &bp)
             Timed t(h, j.dims.mfma ? RCF_T_FIR_MFMA : RCF_T_FIR);
             launch_fir_bank(j.dev, j.dims, st);
         }
-    if (run_pfb) { TimedAttached t(h, RCF_T_PFB, pl); launch_pfb(pl, st, sr.n_wgs ? &sr : nullptr); }
+    if (run_pfb) { TimedAttached t(h, RCF_T_PFB, pl); launch_pfb(bp.shape, pl, bp.pfb_zero_history, st, sr.n_wgs ? &sr : nullptr); }
     if (run_pfb && pl.n_taps > 0) {
         Timed t(h, RCF_T_TAPS);
         launch_tap_finalize(d_tap_list, pl.n_taps, pl.tap_mat, pl.tap_pitch, pl.n_frames, pl.n_lo - pl.n_abs0,

@@ -150,19 +150,19 @@ int plan_pfb(rcf_t *h, BlockPlan &bp)
                           (long long)cnt, bp.reach_x && bp.reach_x->count(RCF_SRC_PFB_BIN0) ? bp.reach_x->at(RCF_SRC_PFB_BIN0) : (size_t)0, h->out_cap);
                 return RCF_ECAP;
             }
-            if (p.fm_mode && p.d_fm_edge && ceil_div(cnt, pfb_chunk_frames(p.NB)) > p.fm_slots) {
+            if (p.fm_mode && p.d_fm_edge && ceil_div(cnt, p.shape.chunk_frames) > p.fm_slots) {
                 // the look-back form's invariant: one hand-over row and flag per chunk of the launch (rcf_pfb_fm_enable
                 // sizes them for the largest launch the handle accepts, so this does not fire); two chunks of one launch on
                 // one row would wait for a tag that was overwritten and take a wrong predecessor frame
                 set_error("block yields %lld chunks of the fused discriminator > %d hand-over rows",
-                          (long long)ceil_div(cnt, pfb_chunk_frames(p.NB)), p.fm_slots);
+                          (long long)ceil_div(cnt, p.shape.chunk_frames), p.fm_slots);
                 return RCF_ECAP;
             }
             pl.src.base = h->d_buf[h->cur];
             pl.src.mask = ~0ull;
             pl.src.origin = S0 - (int64_t)h->hist_cap;
             pl.src.stride = 1;
-            pl.frame_major = p.frame_major ? 1 : 0;
+            pl.frame_major = p.shape.frame_major ? 1 : 0;
             pl.ptaps = p.d_ptaps;
             pl.tw = p.d_tw;
             pl.bins_ring = p.d_bins;
@@ -197,6 +197,10 @@ int plan_pfb(rcf_t *h, BlockPlan &bp)
                 pl.fm_edge = nullptr;
                 pl.fm_mode = 0;
             }
+            // the one place a launch's zero-history question is asked: the launchers and the group take the answer.  A fused
+            // launch also recomputes the chunk before its first frame (the halo)
+            bp.shape = p.shape;
+            bp.pfb_zero_history = pfb_zero_history(p.shape, n_lo, p.start_sample, p.fm_mode ? p.shape.chunk_frames : 0);
             run_pfb = true;
             p.produced = n_hi - p.n_abs0 + 1;
         }

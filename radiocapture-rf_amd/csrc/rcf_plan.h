@@ -80,6 +80,8 @@ struct BlockPlan {
     int audf_num = 1, audf_den = 1;
     PfbLaunch pl{};
     bool run_pfb = false;
+    PfbShape shape;                    // run_pfb: the bank's shape, and whether this launch still reaches before its start
+    bool pfb_zero_history = false;     // (plan_pfb; with the fused discriminator: of the launch and its halo chunk)
     const TapLaunch *d_tap_list = nullptr;
     const int32_t *d_group_bin0 = nullptr;   // per group of 16 tap slots: first bin of a run read straight from the ring, or -1
     std::vector<int32_t> tap_first_of_bin;

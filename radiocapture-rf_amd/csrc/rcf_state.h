@@ -98,8 +98,8 @@ struct Chan {
 
 struct Pfb {
     bool open = false;
-    bool frame_major = false;      // output ring layout (PfbLaunch.frame_major)
-    int NB = 0, D = 0, T = 0, P = 0, Ppad = 0;
+    PfbShape shape;                // the bank's row of the shape table (pfb_shape.h), resolved once by rcf_pfb_open
+    int NB = 0, D = 0, T = 0, P = 0;   // bins, decimation, prototype taps, taps per branch (= shape.NB, .D, .P)
     std::vector<float> proto;      // prototype taps (host): rcf_pfb_tap_open's GNU-Radio phase model needs them
     float *d_ptaps = nullptr;
     float2 *d_tw = nullptr;

@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 
 # fs -> bins (rc_frontend/channel.py:31-33: D = int(fs / 12500) / 2 = bins / 2, T = odd(int(fs / 6875)))
 SHAPES = [(2.0e6, 160), (2.4e6, 192), (6e6, 480), (8e6, 640), (12e6, 960), (16e6, 1280)]
-# frames per chunk of each shape's kernel (pfb_chunk_frames): the ragged cuts below are sized against it
+# frames per chunk of each shape's kernel (PfbShape::chunk_frames): the ragged cuts below are sized against it
 CHUNK = {160: 16, 192: 16, 480: 8, 640: 8, 960: 4, 1280: 4}
 
 
