@@ -24,122 +24,147 @@ using namespace rcfx;
 
 namespace {
 
+using ShapeKey = std::tuple<int, int, int, int>;
+
 struct MergedFir {
     FirLaunchDims dims{};
     std::vector<ChanLaunch> recs;
     const ChanLaunch *dev = nullptr;
 };
 
-}  // namespace
+// filterbanks of one shape in steady state: one launch where the shape has a grouped kernel (pfb_shape.h), one by one at the
+// bucket's place where it has none
+struct BankGroup { std::vector<size_t> idx; const PfbLaunch *d_pls = nullptr; GroupMap gm{}; bool grouped = false; };
 
-// (declared in rcf_group.h: the pump calls it)
-int rcfx::group_process(rcf_group *g, const std::vector<GroupItem> &items, int fmt, float scale, float offset, bool wait)
+// One group block on its way through the stages below, in the order group_process() calls them.
+struct GroupBlock {
+    rcf_group *g;
+    const std::vector<GroupItem> &items;
+    int fmt; float scale, offset;
+    hipStream_t st;
+    rcf_t *h0;                                 // merged launches are timed on the first member (rcf_timing_* of that handle)
+    int a = 0;                                 // the group's arena in use, where this block's records start in it ...
+    size_t base = 0;
+    Arena ga{nullptr, nullptr, 0, 0};          // ... and the members' planners and the merge stages put them
+    std::vector<const void *> dsrc;            // per item: its source as the device reads it (nullptr: resident)
+    std::vector<std::unique_ptr<BlockPlan>> plans;
+    std::vector<BlockUndo> undo;
+    std::map<ShapeKey, BankGroup> banks;       // (bins, decimation, rows of the kernel, fused-discriminator mode)
+    std::vector<size_t> bank_singles;
+    std::vector<TapFinArgs> tap_args;
+    const TapFinArgs *d_tap_args = nullptr;
+    int tap_max_taps = 0, tap_max_rows = 0;
+    std::vector<std::map<ShapeKey, MergedFir>> merged;   // per depth: (D, T, small, KT) -> the members' records of that class
+    DiscJob disc{nullptr, 0, 0, {}};           // the members' discriminator, symbol-filter, AGC and rotator-fill records
+    std::vector<FmFirLaunch> symf;
+    std::vector<AgcLaunch> agcf;
+    std::vector<RotFill> rots;
+    const FmFirLaunch *d_symf = nullptr;
+    const AgcLaunch *d_agcf = nullptr;
+    const RotFill *d_rots = nullptr;
+    int symf_max_n = 0, agcf_max_n = 0, agcf_max_ns = 0;
+    std::vector<PrepRec> prep;                 // the ingest launch's records, kPrepMaxRecs per launch
+    std::vector<uint32_t> prep_tiles;
+    const PrepRec *prep_mapped = nullptr;
+
+    size_t size() const { return items.size(); }
+    rcf_t *member(size_t i) const { return g->members[(size_t)items[i].m]; }
+};
+
+int oom() { set_error("launch arena exhausted"); return RCF_ENOMEM; }
+
+// room in the group's arena for every member's records and the group's own
+int reserve_arena(GroupBlock &b)
 {
-    if (items.empty()) return RCF_OK;
-    const auto dbg_t0 = std::chrono::steady_clock::now();
-    auto dbg_mark = [&](int i, std::chrono::steady_clock::time_point from) {
-        const double ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - from).count() * 1e3;
-        if (ms > g->dbg_ms[i]) g->dbg_ms[i] = ms;
-        return std::chrono::steady_clock::now();
-    };
-    RCF_HIP(hipSetDevice(g->device));
-    hipStream_t st = g->stream;
-    const size_t bps = group_sample_bytes(fmt);
-    const size_t NI = items.size();
-    rcf_t *h0 = g->members[0];                  // merged launches are timed on the first member (rcf_timing_* of that handle)
-
-    // ---- 1. room in the group's arena for every member's records and the group's own
-    size_t need = 16384 + NI * (3 * sizeof(PrepRec) + sizeof(PfbLaunch) + sizeof(TapFinArgs) + 4 * sizeof(int32_t) + 512);
-    for (const GroupItem &it : items) {
-        rcf_t *h = g->members[(size_t)it.m];
+    size_t need = 16384 + b.size() * (3 * sizeof(PrepRec) + sizeof(PfbLaunch) + sizeof(TapFinArgs) + 4 * sizeof(int32_t) + 512);
+    for (size_t i = 0; i < b.size(); ++i) {
+        rcf_t *h = b.member(i);
         flush_lagged(h);                                       // (a member that was fed on its own before: nothing lags inside a group)
         if (h->graveyard.size() > 512) drain_graveyard(h);
         need += arena_need_bound(h);
     }
-    if (g->arenas.reserve(need, st) != RCF_OK) return RCF_EHIP;
-    auto dbg_t1 = dbg_mark(0, dbg_t0);                          // set device + arena reserve
-    auto tp = dbg_t0;
-    RCF_PROF(8, "group: arena reserve", tp);
-    const int a = g->arenas.cur;
-    const size_t base = g->arenas.fill;
-    Arena ga{g->arenas.h[a], g->arenas.d[a], base, g->arenas.cap};
+    ArenaSet &as = b.g->arenas;
+    if (as.reserve(need, b.st) != RCF_OK) return RCF_EHIP;
+    b.a = as.cur;
+    b.base = as.fill;
+    b.ga = Arena{as.h[b.a], as.d[b.a], b.base, as.cap};
+    return RCF_OK;
+}
 
-    // ---- 2. where the device reads each source: pinned memory in place, pageable memory through a staging copy
-    std::vector<const void *> dsrc(NI, nullptr);
-    for (size_t i = 0; i < NI; ++i) {
-        const GroupItem &it = items[i];
+// where the device reads each source: pinned memory in place, pageable memory through a staging copy
+int stage_sources(GroupBlock &b)
+{
+    const size_t bps = group_sample_bytes(b.fmt);
+    b.dsrc.assign(b.size(), nullptr);
+    for (size_t i = 0; i < b.size(); ++i) {
+        const GroupItem &it = b.items[i];
         if (!it.src) continue;
-        if (it.dsrc) { dsrc[i] = it.dsrc; continue; }
+        if (it.dsrc) { b.dsrc[i] = it.dsrc; continue; }
         void *dv = nullptr;
-        if (hipHostGetDevicePointer(&dv, const_cast<void *>(it.src), 0) == hipSuccess && dv) { dsrc[i] = dv; continue; }
+        if (hipHostGetDevicePointer(&dv, const_cast<void *>(it.src), 0) == hipSuccess && dv) { b.dsrc[i] = dv; continue; }
         (void)hipGetLastError();                               // (pageable memory: not an error)
         const size_t bytes = it.n * bps;
-        if (g->stage_cap[(size_t)it.m] < bytes) {
+        void *&stage = b.g->d_stage[(size_t)it.m];
+        if (b.g->stage_cap[(size_t)it.m] < bytes) {
             void *nd = nullptr;
             RCF_HIP(hipMalloc(&nd, bytes));
-            if (g->d_stage[(size_t)it.m]) { RCF_HIP(hipStreamSynchronize(st)); (void)hipFree(g->d_stage[(size_t)it.m]); }
-            g->d_stage[(size_t)it.m] = nd;
-            g->stage_cap[(size_t)it.m] = bytes;
+            if (stage) { RCF_HIP(hipStreamSynchronize(b.st)); (void)hipFree(stage); }
+            stage = nd;
+            b.g->stage_cap[(size_t)it.m] = bytes;
         }
-        RCF_HIP(hipMemcpyAsync(g->d_stage[(size_t)it.m], it.src, bytes, hipMemcpyHostToDevice, st));
-        dsrc[i] = g->d_stage[(size_t)it.m];
+        RCF_HIP(hipMemcpyAsync(stage, it.src, bytes, hipMemcpyHostToDevice, b.st));
+        b.dsrc[i] = stage;
     }
+    return RCF_OK;
+}
 
-    // ---- 3. every member's block planned by the per-front-end planner into the group's arena; all or none
-    std::vector<std::unique_ptr<BlockPlan>> plans(NI);
-    std::vector<BlockUndo> undo(NI);
-    for (size_t i = 0; i < NI; ++i) {
-        rcf_t *h = g->members[(size_t)items[i].m];
-        plans[i].reset(new BlockPlan);
-        plans[i]->defer = true;
-        plans[i]->ar = &ga;
-        const int rc = plan_block(h, items[i].n, *plans[i], undo[i]);
-        if (rc != RCF_OK) {
-            for (size_t j = 0; j < i; ++j) undo_block(g->members[(size_t)items[j].m], undo[j]);
-            return rc;
-        }
+// every member's block planned by the per-front-end planner into the group's arena.  (A refusal leaves the refused member as
+// it was; group_process takes back the ones planned before it.)
+int plan_members(GroupBlock &b)
+{
+    b.plans.resize(b.size());
+    b.undo.resize(b.size());
+    for (size_t i = 0; i < b.size(); ++i) {
+        b.plans[i].reset(new BlockPlan);
+        b.plans[i]->defer = true;
+        b.plans[i]->ar = &b.ga;
+        const int rc = plan_block(b.member(i), b.items[i].n, *b.plans[i], b.undo[i]);
+        if (rc != RCF_OK) return rc;
     }
-    dbg_t1 = dbg_mark(1, dbg_t1);                               // planning
-    RCF_PROF(9, "group: planning (all)", tp);
-    auto fail_all = [&](int code) {
-        for (size_t j = 0; j < NI; ++j) undo_block(g->members[(size_t)items[j].m], undo[j]);
-        return code;
-    };
-    auto oom = [&]() { set_error("launch arena exhausted"); return fail_all(RCF_ENOMEM); };
+    return RCF_OK;
+}
 
-    // ---- 4. what goes out together
-    // filterbanks: members of one shape in steady state share a launch -- where the shape has a grouped kernel (pfb_shape.h);
-    // the members of a bucket without one go out one by one at the bucket's place
-    struct BankGroup { std::vector<size_t> idx; const PfbLaunch *d_pls = nullptr; GroupMap gm{}; bool grouped = false; };
-    std::map<std::tuple<int, int, int, int>, BankGroup> banks;       // (bins, decimation, rows of the kernel, fused-discriminator mode)
-    std::vector<size_t> bank_singles;
-    for (size_t i = 0; i < NI; ++i) {
-        BlockPlan &bp = *plans[i];
+// filterbanks: members of one shape in steady state share a bucket; a bucket of one, and every bank that cannot join one,
+// goes out alone after the buckets
+int merge_banks(GroupBlock &b)
+{
+    for (size_t i = 0; i < b.size(); ++i) {
+        BlockPlan &bp = *b.plans[i];
         if (!bp.run_pfb) continue;
         bp.pl.ev_start = bp.pl.ev_stop = nullptr;
         // (the grouped kernels have no masking form: plan_pfb's answer -- for a fused bank it covers the chunk before its
         // first frame, which its first workgroup recomputes; and such a bank joins in its look-back form only)
         if (bp.pfb_zero_history || (bp.pl.fm_ring && !bp.pl.fm_edge)) {
-            bank_singles.push_back(i);
+            b.bank_singles.push_back(i);
             continue;
         }
         const PfbShape &sh = bp.shape;
-        BankGroup &bg = banks[std::make_tuple(sh.NB, sh.D, sh.Ppad, bp.pl.fm_ring ? bp.pl.fm_mode : 0)];
+        BankGroup &bg = b.banks[std::make_tuple(sh.NB, sh.D, sh.Ppad, bp.pl.fm_ring ? bp.pl.fm_mode : 0)];
         bg.grouped = bp.pl.fm_ring ? sh.grouped_fused : sh.grouped;
         bg.idx.push_back(i);
     }
-    for (auto it = banks.begin(); it != banks.end();) {
+    for (auto it = b.banks.begin(); it != b.banks.end();) {
         BankGroup &bg = it->second;
-        if (bg.idx.size() < 2) { bank_singles.push_back(bg.idx[0]); it = banks.erase(it); continue; }
+        if (bg.idx.size() < 2) { b.bank_singles.push_back(bg.idx[0]); it = b.banks.erase(it); continue; }
         if (!bg.grouped) { ++it; continue; }
-        const int F = plans[bg.idx[0]]->shape.chunk_frames;
+        const int F = b.plans[bg.idx[0]]->shape.chunk_frames;
         std::vector<PfbLaunch> pls;
         std::vector<int32_t> first;
         pls.reserve(bg.idx.size());
         first.reserve(bg.idx.size() + 1);
         int32_t total = 0, uniform = -1;
         for (size_t i : bg.idx) {
-            const PfbLaunch &pl = plans[i]->pl;
+            const PfbLaunch &pl = b.plans[i]->pl;
             const int32_t nwg = (pl.n_frames + F - 1) / F;
             uniform = uniform < 0 ? nwg : (uniform == nwg ? uniform : 0);
             first.push_back(total);
@@ -147,221 +172,247 @@ int rcfx::group_process(rcf_group *g, const std::vector<GroupItem> &items, int f
             pls.push_back(pl);
         }
         first.push_back(total);
-        if (!ga.put(pls, &bg.d_pls) || !ga.put(first, &bg.gm.wg_first)) return oom();
+        if (!b.ga.put(pls, &bg.d_pls) || !b.ga.put(first, &bg.gm.wg_first)) return oom();
         bg.gm.n_fe = (int32_t)bg.idx.size();
         bg.gm.total_wg = total;
         bg.gm.uniform_nwg = uniform > 0 ? uniform : 0;
         ++it;
     }
-    std::sort(bank_singles.begin(), bank_singles.end());
-    // taps
-    std::vector<TapFinArgs> tap_args;
-    int tap_max_taps = 0, tap_max_rows = 0;
-    for (size_t i = 0; i < NI; ++i) {
-        const BlockPlan &bp = *plans[i];
+    std::sort(b.bank_singles.begin(), b.bank_singles.end());
+    return RCF_OK;
+}
+
+// the tapped bins of every member: one tap-finalize launch
+int merge_taps(GroupBlock &b)
+{
+    for (auto &p : b.plans) {
+        const BlockPlan &bp = *p;
         if (!bp.run_pfb || bp.pl.n_taps <= 0) continue;
         const PfbLaunch &pl = bp.pl;
-        tap_args.push_back(TapFinArgs{bp.d_tap_list, pl.tap_mat, bp.d_group_bin0, pl.bins_ring, pl.n_lo - pl.n_abs0, pl.n_taps,
-                                      pl.tap_pitch, pl.n_frames, pl.tap_first, pl.NB, 0});
-        tap_max_taps = std::max(tap_max_taps, (int)pl.n_taps);
-        tap_max_rows = std::max(tap_max_rows, (int)pl.n_frames);
+        b.tap_args.push_back(TapFinArgs{bp.d_tap_list, pl.tap_mat, bp.d_group_bin0, pl.bins_ring, pl.n_lo - pl.n_abs0, pl.n_taps,
+                                        pl.tap_pitch, pl.n_frames, pl.tap_first, pl.NB, 0});
+        b.tap_max_taps = std::max(b.tap_max_taps, (int)pl.n_taps);
+        b.tap_max_rows = std::max(b.tap_max_rows, (int)pl.n_frames);
     }
-    const TapFinArgs *d_tap_args = nullptr;
-    if (!tap_args.empty() && !ga.put(tap_args, &d_tap_args)) return oom();
-    // FIR jobs whose records are self-contained: one launch per depth and (D, T) class
-    int max_depth = 0;
-    for (auto &bp : plans) max_depth = std::max(max_depth, (int)bp->fir_by_depth.size() - 1);
-    std::vector<std::map<std::tuple<int, int, int, int>, MergedFir>> merged((size_t)max_depth + 1);
-    for (auto &bp : plans)
+    if (!b.tap_args.empty() && !b.ga.put(b.tap_args, &b.d_tap_args)) return oom();
+    return RCF_OK;
+}
+
+// FIR jobs whose records are self-contained: one launch per depth and (D, T) class
+int merge_firs(GroupBlock &b)
+{
+    size_t depths = 1;
+    for (auto &bp : b.plans) depths = std::max(depths, bp->fir_by_depth.size());
+    b.merged.resize(depths);
+    for (auto &bp : b.plans)
         for (size_t d = 0; d < bp->fir_by_depth.size(); ++d)
             for (FirJob &j : bp->fir_by_depth[d]) {
                 if (j.host.empty()) continue;
-                MergedFir &mf = merged[d][std::make_tuple(j.dims.D, j.dims.T, j.dims.small, j.dims.KT)];
-                if (mf.recs.empty()) { mf.dims = j.dims; mf.dims.max_n_k = 0; mf.dims.atan_tab = h0->d_atan; }
+                MergedFir &mf = b.merged[d][std::make_tuple(j.dims.D, j.dims.T, j.dims.small, j.dims.KT)];
+                if (mf.recs.empty()) { mf.dims = j.dims; mf.dims.max_n_k = 0; mf.dims.atan_tab = b.h0->d_atan; }
                 mf.dims.max_n_k = std::max(mf.dims.max_n_k, j.dims.max_n_k);
                 mf.recs.insert(mf.recs.end(), j.host.begin(), j.host.end());
             }
-    for (auto &lvl : merged)
+    for (auto &lvl : b.merged)
         for (auto &kv : lvl) {
             kv.second.dims.n_chans = (int)kv.second.recs.size();
-            if (!ga.put(kv.second.recs, &kv.second.dev)) return oom();
+            if (!b.ga.put(kv.second.recs, &kv.second.dev)) return oom();
         }
-    // discriminators, symbol filters, AGCs, exact-rotator fills
-    std::vector<DiscLaunch> discs;
-    std::vector<FmFirLaunch> symf;
-    std::vector<AgcLaunch> agcf;
-    std::vector<RotFill> rots;
-    int disc_max_n = 0, symf_max_n = 0, agcf_max_n = 0, agcf_max_ns = 0;
-    for (auto &bp : plans) {
-        for (DiscJob &dj : bp->disc_jobs) {
-            discs.insert(discs.end(), dj.host.begin(), dj.host.end());
-            disc_max_n = std::max(disc_max_n, dj.max_n);
-        }
-        symf.insert(symf.end(), bp->symf.begin(), bp->symf.end());
-        symf_max_n = std::max(symf_max_n, bp->symf_max_n);
-        agcf.insert(agcf.end(), bp->agcf.begin(), bp->agcf.end());
-        agcf_max_n = std::max(agcf_max_n, bp->agcf_max_n);
-        agcf_max_ns = std::max(agcf_max_ns, bp->agcf_max_ns);
-        rots.insert(rots.end(), bp->rot_fills.begin(), bp->rot_fills.end());
-    }
-    const DiscLaunch *d_discs = nullptr;
-    const FmFirLaunch *d_symf = nullptr;
-    const AgcLaunch *d_agcf = nullptr;
-    const RotFill *d_rots = nullptr;
-    if ((!discs.empty() && !ga.put(discs, &d_discs)) || (!symf.empty() && !ga.put(symf, &d_symf)) ||
-        (!agcf.empty() && !ga.put(agcf, &d_agcf)) || (!rots.empty() && !ga.put(rots, &d_rots)))
-        return oom();
+    return RCF_OK;
+}
 
-    // ---- 5. the prep launch's records, last: one of them uploads everything put so far
-    std::vector<PrepRec> prep;
-    prep.reserve(2 * NI + 1);
-    uint32_t prep_max = 0;
-    for (size_t i = 0; i < NI; ++i) {
-        rcf_t *h = g->members[(size_t)items[i].m];
-        const size_t n = items[i].n, H = h->hist_cap;
+// discriminators, symbol filters, AGCs, exact-rotator fills: the members' records one after the other
+int merge_tails(GroupBlock &b)
+{
+    for (auto &bp : b.plans) {
+        for (DiscJob &dj : bp->disc_jobs) {
+            b.disc.host.insert(b.disc.host.end(), dj.host.begin(), dj.host.end());
+            b.disc.max_n = std::max(b.disc.max_n, dj.max_n);
+        }
+        b.symf.insert(b.symf.end(), bp->symf.begin(), bp->symf.end());
+        b.symf_max_n = std::max(b.symf_max_n, bp->symf_max_n);
+        b.agcf.insert(b.agcf.end(), bp->agcf.begin(), bp->agcf.end());
+        b.agcf_max_n = std::max(b.agcf_max_n, bp->agcf_max_n);
+        b.agcf_max_ns = std::max(b.agcf_max_ns, bp->agcf_max_ns);
+        b.rots.insert(b.rots.end(), bp->rot_fills.begin(), bp->rot_fills.end());
+    }
+    b.disc.n = (int)b.disc.host.size();
+    if ((b.disc.n && !b.ga.put(b.disc.host, &b.disc.dev)) || (!b.symf.empty() && !b.ga.put(b.symf, &b.d_symf)) ||
+        (!b.agcf.empty() && !b.ga.put(b.agcf, &b.d_agcf)) || (!b.rots.empty() && !b.ga.put(b.rots, &b.d_rots)))
+        return oom();
+    return RCF_OK;
+}
+
+void push_copy_rec(GroupBlock &b, const void *src, float2 *dst, size_t n8)
+{
+    PrepRec c{};
+    c.src = src;
+    c.dst = dst;
+    c.n = (uint32_t)n8;
+    c.fmt = -1;
+    b.prep.push_back(c);
+}
+
+// The ingest launch's records, last: per member its conversion and the history of its next block, then the one that uploads
+// everything put into the arena so far.  Block sample k sits at buffer index H + k; the next block's history is buffer
+// [n, n + H): sample k lands at other[H + k - n] once that is >= 0.
+int build_prep(GroupBlock &b)
+{
+    const size_t bps = group_sample_bytes(b.fmt);
+    b.prep.reserve(2 * b.size() + 1);
+    for (size_t i = 0; i < b.size(); ++i) {
+        rcf_t *h = b.member(i);
+        const size_t n = b.items[i].n, H = h->hist_cap;
         float2 *curb = h->d_buf[h->cur], *oth = h->d_buf[h->cur ^ 1];
-        PrepRec r{};
-        if (dsrc[i]) {
-            // block sample i sits at buffer index H + i; the next block's history is buffer [n, n + H): sample i lands at
-            // other[H + i - n] once that is >= 0
-            r.src = dsrc[i];
+        if (b.dsrc[i]) {
+            PrepRec r{};
+            r.src = b.dsrc[i];
             r.dst = curb + H;
             r.n = (uint32_t)n;
             r.hist_from = n >= H ? (uint32_t)(n - H) : 0u;
             r.hist_dst = n >= H ? oth : oth + (H - n);
-            r.fmt = fmt;
-            r.scale = scale;
-            r.offset = offset;
-            const size_t item = fmt == RCF_FMT_CF32 ? 4 : bps / 2;      // bytes per raw value
+            r.fmt = b.fmt;
+            r.scale = b.scale;
+            r.offset = b.offset;
+            const size_t item = b.fmt == RCF_FMT_CF32 ? 4 : bps / 2;    // bytes per raw value
             r.aligned = ((uintptr_t)r.src % (4 * item)) == 0 ? 1 : 0;
             r.dst_aligned = ((uintptr_t)r.dst % 16) == 0 ? 1 : 0;
-            prep.push_back(r);
-            prep_max = std::max(prep_max, r.n);
-            if (n < H) {                                       // the part of the history that is older than this block
-                PrepRec c{};
-                c.src = curb + n;
-                c.dst = oth;
-                c.n = (uint32_t)(H - n);
-                c.fmt = -1;
-                prep.push_back(c);
-                prep_max = std::max(prep_max, c.n);
-            }
-        } else {                                               // resident data: only the history moves
-            r.src = curb + n;
-            r.dst = oth;
-            r.n = (uint32_t)H;
-            r.fmt = -1;
-            prep.push_back(r);
-            prep_max = std::max(prep_max, r.n);
+            b.prep.push_back(r);
+            if (n < H) push_copy_rec(b, curb + n, oth, H - n);          // the part of the history that is older than this block
+        } else {
+            push_copy_rec(b, curb + n, oth, H);                         // resident data: only the history moves
         }
-        plans[i]->history_done = true;
+        b.plans[i]->history_done = true;
     }
-    {
-        const size_t from = base & ~size_t(63);
-        const size_t bytes = ga.used > base ? ((ga.used + 63) & ~size_t(63)) - from : 0;
-        if (bytes) {
-            PrepRec c{};
-            c.src = g->arenas.h_dev[a] + from;
-            c.dst = reinterpret_cast<float2 *>(ga.d + from);
-            c.n = (uint32_t)(bytes / 8);
-            c.fmt = -1;
-            prep.push_back(c);
-            prep_max = std::max(prep_max, c.n);
-        }
-    }
-    // (at most kPrepMaxRecs records per launch: more go out as further launches)
-    std::vector<uint32_t> prep_tiles;
-    for (size_t at = 0; at < prep.size(); at += kPrepMaxRecs)
-        prep_tiles.push_back(fill_prep_tiles(prep.data() + at, (int)std::min<size_t>(kPrepMaxRecs, prep.size() - at)));
+    unsigned char *h_dev = b.g->arenas.h_dev[b.a];                      // the pinned arena as the device sees it
+    const UploadSpan up = arena_upload_span(b.base, b.ga.used);
+    if (up.bytes) push_copy_rec(b, h_dev + up.from, reinterpret_cast<float2 *>(b.ga.d + up.from), up.bytes / 8);
+    for (size_t at = 0; at < b.prep.size(); at += kPrepMaxRecs)
+        b.prep_tiles.push_back(fill_prep_tiles(b.prep.data() + at, (int)std::min<size_t>(kPrepMaxRecs, b.prep.size() - at)));
     const PrepRec *d_prep = nullptr;
-    if (!ga.put(prep, &d_prep)) return oom();
-    // (the kernel reads ITS records where the host wrote them: the pinned arena as the device sees it)
-    const PrepRec *prep_mapped = reinterpret_cast<const PrepRec *>(
-        g->arenas.h_dev[a] + (reinterpret_cast<const unsigned char *>(d_prep) - ga.d));
-    g->arenas.fill = (ga.used + 63) & ~size_t(63);
+    if (!b.ga.put(b.prep, &d_prep)) return oom();
+    // (the kernel reads ITS records where the host wrote them, not their device copy)
+    b.prep_mapped = reinterpret_cast<const PrepRec *>(h_dev + (reinterpret_cast<const unsigned char *>(d_prep) - b.ga.d));
+    b.g->arenas.fill = (b.ga.used + 63) & ~size_t(63);
+    return RCF_OK;
+}
 
-    dbg_t1 = dbg_mark(2, dbg_t1);                               // merging + records
-    RCF_PROF(10, "group: merging + records", tp);
-    // ---- 6. launches, in dependency order.  From here on a failure leaves queued work behind: no roll-back.
-    for (size_t at = 0, li = 0; at < prep.size(); at += kPrepMaxRecs, ++li)
-        launch_group_prep(prep_mapped + at, (int)std::min<size_t>(kPrepMaxRecs, prep.size() - at), prep_tiles[li], st);
-    dbg_t1 = dbg_mark(3, dbg_t1);                               // the prep launch
-    RCF_PROF(11, "group: prep launch", tp);
-    // (past this point every listed member's channel counters have been advanced by the planning and the prep kernel has
-    // written its buffers: a failure no longer returns at once -- the bookkeeping of every member is finished, the members
-    // are marked faulted, and the error is returned at the end)
-    int rc_late = RCF_OK;
-    if (wait && hipEventRecord(g->ingest_ev, st) != hipSuccess) { set_error("group: event record failed"); rc_late = RCF_EHIP; }
-    if (d_rots) launch_rot_fill(d_rots, (int)rots.size(), h0->ring_mask, st);
-    auto launch_depth = [&](size_t d, int timing_class_default) {
-        for (size_t i = 0; i < NI; ++i) {
-            rcf_t *h = g->members[(size_t)items[i].m];
-            BlockPlan &bp = *plans[i];
-            if (d >= bp.fir_by_depth.size()) continue;
-            for (FirJob &j : bp.fir_by_depth[d]) {
-                if (!j.host.empty()) continue;                 // merged below
-                if (j.repack) {
-                    launch_fir_pack(j.dev, j.dims.n_chans, j.dims.T, const_cast<float *>(j.dims.bank), j.dirty, st);
-                    if (j.bc) j.bc->key = std::move(j.key);
-                }
-                Timed t(h, d == 0 ? (j.dims.mfma ? RCF_T_FIR_MFMA : RCF_T_FIR) : timing_class_default);
-                launch_fir_bank(j.dev, j.dims, st);
-            }
-        }
-        if (d < merged.size())
-            for (auto &kv : merged[d]) {
-                Timed t(h0, d == 0 ? RCF_T_FIR : timing_class_default);
-                launch_fir_bank(kv.second.dev, kv.second.dims, st);
-            }
-    };
-    launch_depth(0, RCF_T_FIR);
-    auto launch_single = [&](const std::vector<size_t> &idx) {
-        for (size_t i : idx) {
-            Timed t(g->members[(size_t)items[i].m], RCF_T_PFB);
-            launch_pfb(plans[i]->shape, plans[i]->pl, plans[i]->pfb_zero_history, st);
-        }
-    };
-    for (auto &kv : banks) {
+void launch_prep(const GroupBlock &b)
+{
+    for (size_t at = 0, li = 0; at < b.prep.size(); at += kPrepMaxRecs, ++li)
+        launch_group_prep(b.prep_mapped + at, (int)std::min<size_t>(kPrepMaxRecs, b.prep.size() - at), b.prep_tiles[li], b.st);
+}
+
+// one depth of FIRs: every member's own jobs, then the merged classes
+void launch_fir_depth(GroupBlock &b, size_t d)
+{
+    for (size_t i = 0; i < b.size(); ++i) {
+        BlockPlan &bp = *b.plans[i];
+        if (d >= bp.fir_by_depth.size()) continue;
+        for (FirJob &j : bp.fir_by_depth[d])
+            if (j.host.empty())                                         // (the others were merged)
+                launch_fir_job(b.member(i), j, d ? RCF_T_FIR_DERIVED : (j.dims.mfma ? RCF_T_FIR_MFMA : RCF_T_FIR), b.st);
+    }
+    for (auto &kv : b.merged[d]) {
+        Timed t(b.h0, d ? RCF_T_FIR_DERIVED : RCF_T_FIR);
+        launch_fir_bank(kv.second.dev, kv.second.dims, b.st);
+    }
+}
+
+void launch_banks_alone(GroupBlock &b, const std::vector<size_t> &idx)
+{
+    for (size_t i : idx) {
+        Timed t(b.member(i), RCF_T_PFB);
+        launch_pfb(b.plans[i]->shape, b.plans[i]->pl, b.plans[i]->pfb_zero_history, b.st);
+    }
+}
+
+// Everything behind the prep launch, in dependency order (launch_plan's, rcf_launch.cpp).  The first error is returned, and
+// the launching goes on: finish_members has every member's bookkeeping to do either way.
+int launch_block(GroupBlock &b, bool wait)
+{
+    rcf_t *h0 = b.h0;
+    hipStream_t st = b.st;
+    int rc = RCF_OK;
+    if (wait && hipEventRecord(b.g->ingest_ev, st) != hipSuccess) { set_error("group: event record failed"); rc = RCF_EHIP; }
+    if (b.d_rots) launch_rot_fill(b.d_rots, (int)b.rots.size(), h0->ring_mask, st);
+    launch_fir_depth(b, 0);
+    for (auto &kv : b.banks) {
         BankGroup &bg = kv.second;
-        const BlockPlan &b0 = *plans[bg.idx[0]];
+        const BlockPlan &b0 = *b.plans[bg.idx[0]];
         if (bg.grouped) { Timed t(h0, RCF_T_PFB); launch_pfb_group(b0.shape, b0.pl, bg.d_pls, bg.gm, st); }
-        else launch_single(bg.idx);
+        else launch_banks_alone(b, bg.idx);
     }
-    launch_single(bank_singles);
-    if (d_tap_args) {
+    launch_banks_alone(b, b.bank_singles);
+    if (b.d_tap_args) {
         Timed t(h0, RCF_T_TAPS);
-        launch_tap_finalize_group(d_tap_args, (int)tap_args.size(), tap_max_taps, tap_max_rows, h0->ring_mask, h0->d_atan, st);
+        launch_tap_finalize_group(b.d_tap_args, (int)b.tap_args.size(), b.tap_max_taps, b.tap_max_rows, h0->ring_mask, h0->d_atan, st);
     }
-    for (size_t d = 1; d <= (size_t)max_depth; ++d) launch_depth(d, RCF_T_FIR_DERIVED);
-    if (d_discs) { Timed t(h0, RCF_T_DISC); launch_discriminator(d_discs, (int)discs.size(), disc_max_n, h0->ring_mask, h0->d_atan, st); }
-    if (d_symf) { Timed t(h0, RCF_T_DISC); launch_fm_fir(d_symf, (int)symf.size(), symf_max_n, h0->ring_mask, st); }
-    if (d_agcf) { Timed t(h0, RCF_T_DISC); launch_agc(d_agcf, (int)agcf.size(), agcf_max_n, agcf_max_ns, h0->ring_mask, st); }
-    for (size_t i = 0; i < NI; ++i) {
-        rcf_t *h = g->members[(size_t)items[i].m];
-        BlockPlan &bp = *plans[i];
-        if (bp.d_audf) {
-            Timed t(h, RCF_T_AUDIO);
-            launch_audio(bp.d_audf, (int)bp.audf.size(), bp.audf_max_n, bp.audf_num, bp.audf_den, h->ring_mask, h->d_atan, st);
-        }
-        const int rc = run_scan(h, bp);
-        if (rc != RCF_OK && rc_late == RCF_OK) rc_late = rc;
-        h->buf_dirty[h->cur] = true;                           // (rcf_push_iq on this member later orders its copy behind these reads)
-        h->cur ^= 1;
-        h->total_in = bp.S1;
+    for (size_t d = 1; d < b.merged.size(); ++d) launch_fir_depth(b, d);
+    launch_tail(h0, TailRecs{&b.disc, b.disc.dev ? size_t(1) : 0, b.d_symf, (int)b.symf.size(), b.symf_max_n,
+                             b.d_agcf, (int)b.agcf.size(), b.agcf_max_n, b.agcf_max_ns}, st);
+    for (size_t i = 0; i < b.size(); ++i) {
+        launch_member_audio(b.member(i), *b.plans[i], st);
+        const int rs = run_scan(b.member(i), *b.plans[i]);
+        if (rs != RCF_OK && rc == RCF_OK) rc = rs;
     }
-    if (rc_late == RCF_OK) {
+    if (rc == RCF_OK) {
         const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { set_error("group launch failed: %s", hipGetErrorString(e)); rc_late = RCF_EHIP; }
+        if (e != hipSuccess) { set_error("group launch failed: %s", hipGetErrorString(e)); rc = RCF_EHIP; }
     }
-    if (rc_late != RCF_OK) {
-        for (size_t i = 0; i < NI; ++i) {
-            rcf_t *h = g->members[(size_t)items[i].m];
-            h->fault = rc_late;
-            std::snprintf(h->fault_text, sizeof h->fault_text, "group block failed: %s", rcf_last_error());
-        }
-        return rc_late;
+    return rc;
+}
+
+// Every member's buffers flip and its counters advance: the prep kernel has written them whatever came of the launches
+// after it, and after an error among those every member is faulted.  Not finish_block (rcf_launch.cpp): the history went
+// out with the prep launch, and a member of a group records no buf_done event -- rcf_push_iq on it later orders its copy
+// behind these reads through buf_dirty.
+int finish_members(GroupBlock &b, int rc)
+{
+    for (size_t i = 0; i < b.size(); ++i) {
+        rcf_t *h = b.member(i);
+        h->buf_dirty[h->cur] = true;
+        h->cur ^= 1;
+        h->total_in = b.plans[i]->S1;
+        if (rc == RCF_OK) continue;
+        h->fault = rc;
+        std::snprintf(h->fault_text, sizeof h->fault_text, "group block failed: %s", rcf_last_error());
     }
-    dbg_t1 = dbg_mark(4, dbg_t1);                               // the other launches
+    return rc;
+}
+
+}  // namespace
+
+// (declared in rcf_group.h: the pump calls it)
+int rcfx::group_process(rcf_group *g, const std::vector<GroupItem> &items, int fmt, float scale, float offset, bool wait)
+{
+    if (items.empty()) return RCF_OK;
+    auto tp = std::chrono::steady_clock::now();
+    RCF_HIP(hipSetDevice(g->device));
+    GroupBlock b{g, items, fmt, scale, offset, g->stream, g->members[0]};
+
+    // Until the prep launch nothing is queued: a stage that fails returns its code, and what the planning advanced in the
+    // members is taken back here, once.
+    int rc = reserve_arena(b);
+    if (rc == RCF_OK) { RCF_PROF(8, "group: arena reserve", tp); rc = stage_sources(b); }
+    if (rc == RCF_OK) rc = plan_members(b);
+    if (rc == RCF_OK) { RCF_PROF(9, "group: planning (all)", tp); rc = merge_banks(b); }
+    if (rc == RCF_OK) rc = merge_taps(b);
+    if (rc == RCF_OK) rc = merge_firs(b);
+    if (rc == RCF_OK) rc = merge_tails(b);
+    if (rc == RCF_OK) rc = build_prep(b);
+    if (rc != RCF_OK) {
+        for (size_t i = 0; i < b.undo.size(); ++i) undo_block(b.member(i), b.undo[i]);
+        return rc;
+    }
+    RCF_PROF(10, "group: merging + records", tp);
+
+    // From the prep launch on every listed member's counters have been advanced and its buffers written, and a failure
+    // leaves queued work behind: no roll-back.  Errors are collected, every member is finished and -- after an error -- faulted.
+    launch_prep(b);
+    RCF_PROF(11, "group: prep launch", tp);
+    rc = finish_members(b, launch_block(b, wait));
+    if (rc != RCF_OK) return rc;
     RCF_PROF(12, "group: other launches", tp);
     if (wait) (void)hipEventSynchronize(g->ingest_ev);
     return RCF_OK;

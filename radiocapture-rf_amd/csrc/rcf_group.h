@@ -18,8 +18,6 @@ struct rcf_group {
     rcfx::PinnedStage host_stage;              // rcf_group_read_many (host_read)
     rcf_pump *pump = nullptr;
     std::mutex mu;
-    // RCF_PUMP_DEBUG=1: the longest time one group block spent in each part of group_process (printed by rcf_pump_stop)
-    double dbg_ms[6] = {0, 0, 0, 0, 0, 0};
 };
 
 namespace rcfx {

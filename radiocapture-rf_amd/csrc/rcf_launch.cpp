@@ -11,26 +11,47 @@ void flush_lagged(rcf_t *h)
     launch_fir_bank(h->lag.dev, h->lag.dims, h->stream);
 }
 
+// ---- the steps one front-end's block and a group block (rcf_group.cpp) launch the same way
+UploadSpan arena_upload_span(size_t base, size_t used)
+{
+    const size_t from = base & ~size_t(63);
+    return UploadSpan{from, used > base ? ((used + 63) & ~size_t(63)) - from : 0};
+}
+
+void launch_fir_job(rcf_t *h, FirJob &j, int timing_class, hipStream_t st)
+{
+    if (j.repack) {
+        launch_fir_pack(j.dev, j.dims.n_chans, j.dims.T, const_cast<float *>(j.dims.bank), j.dirty, st);
+        if (j.bc) j.bc->key = std::move(j.key);
+    }
+    Timed t(h, timing_class);
+    launch_fir_bank(j.dev, j.dims, st);
+}
+
+void launch_tail(rcf_t *h, const TailRecs &r, hipStream_t st)
+{
+    for (size_t i = 0; i < r.n_disc; ++i) {
+        Timed t(h, RCF_T_DISC);
+        launch_discriminator(r.disc[i].dev, r.disc[i].n, r.disc[i].max_n, h->ring_mask, h->d_atan, st);
+    }
+    if (r.symf) { Timed t(h, RCF_T_DISC); launch_fm_fir(r.symf, r.n_symf, r.symf_max_n, h->ring_mask, st); }
+    if (r.agcf) { Timed t(h, RCF_T_DISC); launch_agc(r.agcf, r.n_agcf, r.agcf_max_n, r.agcf_max_ns, h->ring_mask, st); }
+}
+
+void launch_member_audio(rcf_t *h, const BlockPlan &bp, hipStream_t st)
+{
+    if (!bp.d_audf) return;
+    Timed t(h, RCF_T_AUDIO);
+    launch_audio(bp.d_audf, (int)bp.audf.size(), bp.audf_max_n, bp.audf_num, bp.audf_den, h->ring_mask, h->d_atan, st);
+}
+
 // upload all launch parameters in one copy, then launch in dependency order
 int launch_plan(rcf_t *h, BlockPlan &bp)
 {
     hipStream_t st = h->stream;
-    Arena &ar = *bp.ar;
-    const int a = bp.a;
-    const size_t arena_base = bp.arena_base;
     auto &fir_by_depth = bp.fir_by_depth;
-    auto &disc_jobs = bp.disc_jobs;
-    auto &symf = bp.symf;
-    auto &audf = bp.audf;
-    auto &rot_fills = bp.rot_fills;
     PfbLaunch &pl = bp.pl;
     const bool run_pfb = bp.run_pfb;
-    const TapLaunch *d_tap_list = bp.d_tap_list;
-    const RotFill *d_rot_fills = bp.d_rot_fills;
-    const FmFirLaunch *d_symf = bp.d_symf;
-    const AgcLaunch *d_agcf = bp.d_agcf;
-    const AudioLaunch *d_audf = bp.d_audf;
-    const int symf_max_n = bp.symf_max_n, audf_max_n = bp.audf_max_n, audf_num = bp.audf_num, audf_den = bp.audf_den;
 
     // ---- stage-2 lag.  The previous block's small-T launch, if it is still pending, rides in THIS block's filterbank launch
     // when that launch is the kernel that can carry it and the bank's ring has room for both blocks' frames; otherwise it
@@ -54,50 +75,42 @@ int launch_plan(rcf_t *h, BlockPlan &bp)
     // ... and this block's own: ONE small-T job on the bank's bins, nothing that consumes its outputs within the block
     FirJob *lag_job = nullptr;
     if (h->lag_enabled && carry && fir_by_depth.size() == 2 && fir_by_depth[1].size() == 1 && fir_by_depth[1][0].dims.small &&
-        fir_by_depth[1][0].dev && fir_by_depth[1][0].bank_src && !d_symf && !d_agcf && !d_audf && (size_t)pl.n_frames * 2 + pfb_reach <= h->out_cap)
+        fir_by_depth[1][0].dev && fir_by_depth[1][0].bank_src && !bp.d_symf && !bp.d_agcf && !bp.d_audf &&
+        (size_t)pl.n_frames * 2 + pfb_reach <= h->out_cap)
         lag_job = &fir_by_depth[1][0];
     {
         // the block's launch records host -> device, and -- in the same launch -- its history tail behind the OTHER input
         // buffer's block (nothing in this block reads that place, and the kernels that did read it are earlier in
         // the stream): one small launch per block instead of two
-        const size_t from = arena_base & ~size_t(63);
-        const size_t bytes = ar.used > arena_base ? ((ar.used + 63) & ~size_t(63)) - from : 0;
+        const UploadSpan up = arena_upload_span(bp.arena_base, bp.ar->used);
+        unsigned char *dst = bp.ar->d + up.from, *src = h->arenas.h_dev[bp.a] + up.from;
         // ... or none at all: when the filterbank's launch is the first of the block that needs neither (no direct
         // channels, no exact-rotator fill before it, no tap matrix whose slot list the bank itself reads from the
         // arena), its first workgroups do both copies on the way in (PfbLaunch::rider_*)
-        const bool ride = run_pfb && !d_rot_fills &&
+        const bool ride = run_pfb && !bp.d_rot_fills &&
                           (fir_by_depth.empty() || fir_by_depth[0].empty()) && pl.n_taps == pl.tap_first &&
-                          bytes / 8 < (1u << 31) && h->hist_cap < (1u << 28) && bp.shape.takes_rider;
+                          up.bytes / 8 < (1u << 31) && h->hist_cap < (1u << 28) && bp.shape.takes_rider;
         if (ride) {
-            pl.rider_dst[0] = reinterpret_cast<unsigned long long *>(ar.d + from);
-            pl.rider_src[0] = reinterpret_cast<const unsigned long long *>(h->arenas.h_dev[a] + from);
-            pl.rider_n8[0] = (uint32_t)((bytes + 7) / 8);
+            pl.rider_dst[0] = reinterpret_cast<unsigned long long *>(dst);
+            pl.rider_src[0] = reinterpret_cast<const unsigned long long *>(src);
+            pl.rider_n8[0] = (uint32_t)((up.bytes + 7) / 8);
             pl.rider_dst[1] = reinterpret_cast<unsigned long long *>(h->d_buf[h->cur ^ 1]);
             pl.rider_src[1] = reinterpret_cast<const unsigned long long *>(h->d_buf[h->cur] + bp.n);
             pl.rider_n8[1] = (uint32_t)(sizeof(float2) * h->hist_cap / 8);
-            bp.history_done = true;
         } else {
             Timed t(h, RCF_T_HISTORY);
-            launch_copy8x2(ar.d + from, h->arenas.h_dev[a] + from, bytes, h->d_buf[h->cur ^ 1], h->d_buf[h->cur] + bp.n,
-                           sizeof(float2) * h->hist_cap, st);
-            bp.history_done = true;
+            launch_copy8x2(dst, src, up.bytes, h->d_buf[h->cur ^ 1], h->d_buf[h->cur] + bp.n, sizeof(float2) * h->hist_cap, st);
         }
-        if (bytes) h->arenas.fill = (ar.used + 63) & ~size_t(63);
+        bp.history_done = true;
+        if (up.bytes) h->arenas.fill = (bp.ar->used + 63) & ~size_t(63);
     }
-    if (d_rot_fills) launch_rot_fill(d_rot_fills, (int)rot_fills.size(), h->ring_mask, st);
+    if (bp.d_rot_fills) launch_rot_fill(bp.d_rot_fills, (int)bp.rot_fills.size(), h->ring_mask, st);
     if (!fir_by_depth.empty())
-        for (auto &j : fir_by_depth[0]) {
-            if (j.repack) {
-                launch_fir_pack(j.dev, j.dims.n_chans, j.dims.T, const_cast<float *>(j.dims.bank), j.dirty, st);
-                if (j.bc) j.bc->key = std::move(j.key);
-            }
-            Timed t(h, j.dims.mfma ? RCF_T_FIR_MFMA : RCF_T_FIR);
-            launch_fir_bank(j.dev, j.dims, st);
-        }
+        for (auto &j : fir_by_depth[0]) launch_fir_job(h, j, j.dims.mfma ? RCF_T_FIR_MFMA : RCF_T_FIR, st);
     if (run_pfb) { TimedAttached t(h, RCF_T_PFB, pl); launch_pfb(bp.shape, pl, bp.pfb_zero_history, st, sr.n_wgs ? &sr : nullptr); }
     if (run_pfb && pl.n_taps > 0) {
         Timed t(h, RCF_T_TAPS);
-        launch_tap_finalize(d_tap_list, pl.n_taps, pl.tap_mat, pl.tap_pitch, pl.n_frames, pl.n_lo - pl.n_abs0,
+        launch_tap_finalize(bp.d_tap_list, pl.n_taps, pl.tap_mat, pl.tap_pitch, pl.n_frames, pl.n_lo - pl.n_abs0,
                             h->ring_mask, h->d_atan, bp.d_group_bin0, pl.tap_first, pl.bins_ring, pl.NB, st);
     }
     for (size_t d = 1; d < fir_by_depth.size(); ++d)
@@ -112,22 +125,9 @@ int launch_plan(rcf_t *h, BlockPlan &bp)
             Timed t(h, RCF_T_FIR_DERIVED);
             launch_fir_bank(j.dev, j.dims, st);
         }
-    for (auto &dj : disc_jobs) {
-        Timed t(h, RCF_T_DISC);
-        launch_discriminator(dj.dev, dj.n, dj.max_n, h->ring_mask, h->d_atan, st);
-    }
-    if (d_symf) {
-        Timed t(h, RCF_T_DISC);
-        launch_fm_fir(d_symf, (int)symf.size(), symf_max_n, h->ring_mask, st);
-    }
-    if (d_agcf) {
-        Timed t(h, RCF_T_DISC);
-        launch_agc(d_agcf, (int)bp.agcf.size(), bp.agcf_max_n, bp.agcf_max_ns, h->ring_mask, st);
-    }
-    if (d_audf) {
-        Timed t(h, RCF_T_AUDIO);
-        launch_audio(d_audf, (int)audf.size(), audf_max_n, audf_num, audf_den, h->ring_mask, h->d_atan, st);
-    }
+    launch_tail(h, TailRecs{bp.disc_jobs.data(), bp.disc_jobs.size(), bp.d_symf, (int)bp.symf.size(), bp.symf_max_n,
+                            bp.d_agcf, (int)bp.agcf.size(), bp.agcf_max_n, bp.agcf_max_ns}, st);
+    launch_member_audio(h, bp, st);
     return RCF_OK;
 }
 

@@ -11,14 +11,15 @@ namespace rcfx {
 namespace {
 std::atomic<uint64_t> g_prof_ns[PlanProf::N];
 std::atomic<uint64_t> g_prof_cnt[PlanProf::N];
+std::atomic<uint64_t> g_prof_max[PlanProf::N];
 const char *g_prof_name[PlanProf::N];
 void prof_dump()
 {
     for (int i = 0; i < PlanProf::N; ++i)
         if (g_prof_cnt[i].load())
-            fprintf(stderr, "RCF_PLAN_PROF %-28s %10.3f ms  %9llu calls  %8.3f us/call\n", g_prof_name[i] ? g_prof_name[i] : "?",
-                    g_prof_ns[i].load() * 1e-6, (unsigned long long)g_prof_cnt[i].load(),
-                    g_prof_ns[i].load() * 1e-3 / (double)g_prof_cnt[i].load());
+            fprintf(stderr, "RCF_PLAN_PROF %-28s %10.3f ms  %9llu calls  %8.3f us/call  %10.3f us longest\n",
+                    g_prof_name[i] ? g_prof_name[i] : "?", g_prof_ns[i].load() * 1e-6, (unsigned long long)g_prof_cnt[i].load(),
+                    g_prof_ns[i].load() * 1e-3 / (double)g_prof_cnt[i].load(), g_prof_max[i].load() * 1e-3);
 }
 }  // namespace
 
@@ -36,8 +37,10 @@ bool PlanProf::on()
 void PlanProf::add(int slot, const char *name, std::chrono::steady_clock::time_point &from)
 {
     const auto now = std::chrono::steady_clock::now();
-    g_prof_ns[slot] += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(now - from).count();
+    const uint64_t ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(now - from).count();
+    g_prof_ns[slot] += ns;
     g_prof_cnt[slot] += 1;
+    for (uint64_t m = g_prof_max[slot].load(); ns > m && !g_prof_max[slot].compare_exchange_weak(m, ns);) {}   // (several pump threads)
     g_prof_name[slot] = name;
     from = now;
 }

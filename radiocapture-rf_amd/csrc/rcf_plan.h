@@ -119,7 +119,8 @@ struct BlockUndo {
     bool armed = false;
 };
 
-// RCF_PLAN_PROF=1: cumulative host time per planning section, printed at exit (tools/rt_probe.py runs with it)
+// RCF_PLAN_PROF=1: host time per planning section -- total, calls, mean and the longest call -- printed at exit
+// (tools/rt_probe.py runs with it)
 struct PlanProf {
     static constexpr int N = 16;
     static bool on();
@@ -140,6 +141,18 @@ int plan_tail(rcf_t *h, BlockPlan &bp);
 int check_block_capacity(rcf_t *h, const BlockPlan &bp);
 // rcf_launch.cpp
 int launch_plan(rcf_t *h, BlockPlan &bp);
+// ... and the steps a group block (rcf_group.cpp) launches the same way.  h: the handle whose timing, ring mask and
+// arctangent table the launch uses -- the front-end itself, or the group's first member for what the group merged.
+struct UploadSpan { size_t from, bytes; };             // the arena bytes [base, used) as the 64-byte blocks that hold them
+UploadSpan arena_upload_span(size_t base, size_t used);
+void launch_fir_job(rcf_t *h, FirJob &j, int timing_class, hipStream_t st);   // an unmerged FIR job, its repack first
+struct TailRecs {                                      // what follows the derived FIRs, every launch timed as RCF_T_DISC
+    const DiscJob *disc; size_t n_disc;                // one discriminator launch per job
+    const FmFirLaunch *symf; int n_symf, symf_max_n;
+    const AgcLaunch *agcf; int n_agcf, agcf_max_n, agcf_max_ns;
+};
+void launch_tail(rcf_t *h, const TailRecs &t, hipStream_t st);
+void launch_member_audio(rcf_t *h, const BlockPlan &bp, hipStream_t st);
 int run_scan(rcf_t *h, const BlockPlan &bp);
 int finish_block(rcf_t *h, const BlockPlan &bp);
 

@@ -614,9 +614,6 @@ int rcf_pump_stop(rcf_pump_t *p)
     p->stop.store(true);
     if (p->th.joinable()) p->th.join();
     rcf_group *g = p->g;
-    if (getenv("RCF_PUMP_DEBUG"))
-        fprintf(stderr, "pump: longest group block by part, ms: reserve %.2f plan %.2f merge %.2f prep-launch %.2f launches %.2f\n",
-                g->dbg_ms[0], g->dbg_ms[1], g->dbg_ms[2], g->dbg_ms[3], g->dbg_ms[4]);
     {
         std::lock_guard<std::mutex> gl(g->mu);
         (void)hipSetDevice(g->device);

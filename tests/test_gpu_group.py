@@ -198,6 +198,73 @@ def test_group_with_direct_channels_scan_and_exact_rotator_members(gpu_required)
         assert a is not None and len(a) > 0 and _same_bits(a, b)
 
 
+def test_group_ungrouped_bucket_beside_a_grouped_one_with_filters_across_members(gpu_required):
+    """what the other grouped tests leave out, in one group of five at 12.8 Msps: three 512-bin banks at D = 256 (oversampled:
+    no grouped kernel, so the bucket's members go out one by one at the bucket's place) beside two 256-bin banks at D = 256
+    (one grouped launch); the third 512-bin bank opened one round late (alone while it sees zero history, in its bucket
+    afterwards); symbol filters and AGCs on channels of different members (their records concatenated into one launch each);
+    member 1 left out of round 2 (the 512-bin bucket is then members 0 and 4).  Every stream of every member has the bits
+    of the same front-end fed alone with the same cuts."""
+    nat = gpu_required
+    fs, D = 12.8e6, 256
+    #          bins  bank opened before round   symbol filter / AGC on its second channel
+    members = [(512, 0, "sym"), (512, 0, "agc"), (256, 0, "agc"), (256, 0, "sym"), (512, 1, "sym")]
+    frames = [[48, 33, 48, 33, 48], [33, 48, 33, 48, 33], [48, 0, 33, 48, 48], [33, 48, 48, 33, 33]]
+    extra = [[7, 0, 131, 0, 255], [0, 19, 0, 200, 1], [3, 0, 0, 77, 0], [100, 5, 64, 0, 9]]        # cuts inside a frame
+    M = len(members)
+    lens = [[D * f + e if f else 0 for f, e in zip(fr, ex)] for fr, ex in zip(frames, extra)]
+    rng = np.random.default_rng(77)
+    xs = [synth.awgn(rng, sum(l[m] for l in lens)) for m in range(M)]
+    i512 = np.arange(4 * 512 - 3) - (4 * 512 - 4) / 2.0
+    protos = {256: _proto(fs, 256), 512: (np.sinc(i512 / 512) * np.hamming(len(i512)) / 512).astype(np.float32)}
+
+    def open_bank(fe, m):
+        nb, _, kind = members[m]
+        fe.pfb_open(nb, D, protos[nb])
+        ids = [fe.pfb_chan_open(5 + 3 * m, 12500, 0.0), fe.pfb_chan_open(nb - 9 - m, 12500, 2500.0)]
+        if kind == "sym":
+            fe.chan_fm_filter(ids[1], 5.0, np.full(5, 0.2, dtype=np.float32))
+        else:
+            fe.chan_agc(ids[1], 64 + m, 1.0)
+        return ids
+
+    def drive(grouped):
+        fes = [nat.Frontend(fs, 0.0, device=0, block_capacity=1 << 14, hist_capacity=1 << 14, out_capacity=1 << 11)
+               for _ in range(M)]
+        grp = nat.Group(fes) if grouped else None
+        try:
+            ids, at = [None] * M, [0] * M
+            for r, l in enumerate(lens):
+                for m in range(M):
+                    if members[m][1] == r:
+                        ids[m] = open_bank(fes[m], m)
+                blocks = [xs[m][at[m]:at[m] + l[m]] if l[m] else None for m in range(M)]
+                at = [a + n for a, n in zip(at, l)]
+                if grouped:
+                    grp.push(blocks, nat.FMT_CF32)
+                else:
+                    for fe, blk in zip(fes, blocks):
+                        if blk is not None:
+                            fe.push(blk)
+            out = []
+            for m, fe in enumerate(fes):
+                for c in ids[m]:
+                    out += [fe.chan_read_iq(c), fe.chan_read_fm(c, 5.0)]
+                out.append(fe.chan_read_sym(ids[m][1]) if members[m][2] == "sym" else fe.chan_read_agc(ids[m][1]))
+                out.append(fe.pfb_read_bin(7))
+            return out
+        finally:
+            if grp is not None:
+                grp.close()
+            for fe in fes:
+                fe.close()
+
+    got, alone = drive(True), drive(False)
+    assert len(got) == len(alone) == 6 * M
+    for k, (a, b) in enumerate(zip(got, alone)):
+        assert len(a) > 40 and _same_bits(a, b), (k // 6, k % 6, len(a), len(b))
+
+
 def test_group_refusals_leave_every_member_untouched(gpu_required):
     nat = gpu_required
     fs = 20e6
