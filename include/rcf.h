@@ -80,6 +80,15 @@ int rcf_design_fm_deemph(double fs, double tau, double btaps[2], double ataps[2]
  * reduces by the gcd and designs firdes.low_pass(I, I, mid, width, WIN_KAISER, 7.0) with fractional_bw 0.4.
  * Writes the reduced ratio; same return convention for the taps. */
 int rcf_design_resampler(int interpolation, int decimation, int *interp_out, int *decim_out, float *taps, int cap);
+/* The MMSE fractional-delay interpolator bank of rcf_chan_clock_mm: nsteps + 1 rows of ntaps floats, row-major; row s, for
+ * mu = s / nsteps, is the least-squares solution R h = r of minimising
+ *     int_{-bw}^{bw} | sum_j h_j e^{-i 2 pi f j} - e^{-i 2 pi f (ntaps / 2 - mu)} |^2 df
+ *     R[j][l] = 2 bw sinc(2 bw (j - l)),  r[j] = 2 bw sinc(2 bw (j - ntaps / 2 + mu)),  sinc(x) = sin(pi x) / (pi x)
+ * solved in extended precision and rounded to float; rows 0 and nsteps are the unit rows e_{ntaps/2} and e_{ntaps/2 - 1}.
+ * (8, 128, 0.25) has the shape, indexing and objective of GNU Radio's interpolator_taps.h, which a numerical minimiser
+ * produced and which is printed to 6 digits: the two tables are not the same numbers, and how far apart they are has not
+ * been measured.  ntaps even, 2 .. 64; nsteps 1 .. 4096; 0 < bw <= 0.5.  Same return convention as rcf_design_low_pass_2. */
+int rcf_design_mmse_interpolator(int ntaps, int nsteps, double bw, float *taps, int cap);
 /* rc_frontend/channel.py:31-33: decim = int(fs/cr)/2 (must be integral -> else RCF_ERANGE) and the
  * tap count of low_pass_2(1.0, fs, cr/2, cr/2, 20.0, WIN_HAMMING). */
 int rcf_channel_params(double samp_rate, int channel_rate, int *decim, int *ntaps);
@@ -149,7 +158,8 @@ int rcf_device(rcf_t *h);
 #define RCF_T_FIR_MFMA     7   /* the same bank on the FP32 matrix cores (>= 8 channels on one source) */
 #define RCF_T_AUDIO        8   /* analog voice chain (squelch/demod/de-emphasis walk, FIRs, resampler) */
 #define RCF_T_TAPS         9   /* filterbank taps: tap matrix -> channel rings, rotator + discriminator fused */
-#define RCF_T_COUNT        10
+#define RCF_T_CLOCK        10  /* symbol clocks (rcf_chan_clock_mm): one launch per block for every clocked channel */
+#define RCF_T_COUNT        11
 /* on = 0: off; 1: every class; otherwise a mask with bit (class + 1) set for each class to time -- every timed
  * launch costs two event records on the stream (~10 us of gap), so a throughput run times only what it reports.  The
  * filterbank's launch carries its two events attached to the dispatch (one barrier packet less inside the measured
@@ -274,6 +284,54 @@ int64_t rcf_chan_read_agc(rcf_t *h, int chan_id, float *out_interleaved, size_t 
 /* device pointer of the AGC's cf32 ring and its capacity (zero-copy, like rcf_chan_rings): output n lives at index
  * n & (capacity-1), n counted as rcf_chan_produced counts the channel's outputs */
 int rcf_chan_agc_ring(rcf_t *h, int chan_id, void **agc_ring, size_t *capacity);
+/* The SmartNet and EDACS control demodulators behind the discriminator (moto_control_demod.py:105-132,
+ * edacs_control_demod.py:82-112):
+ *     quadrature_demod_cf(5) -> clock_recovery_mm_ff(rate / symbol_rate, 1.4395919, 0.5, 0.05, 0.005) -> binary_slicer_fb
+ * digital.clock_recovery_mm_ff(omega, gain_omega, mu, gain_mu, omega_relative_limit) (moto_control_demod.py:113,
+ * edacs_control_demod.py:85), the Mueller and Mueller symbol clock, as a per-channel stage on the GPU.  Per channel, all
+ * state in float: mu, omega, last (initially 0) and the 64-bit input position p.  The input is u[m] = gain * fm[m], fm the
+ * channel's unit-gain discriminator stream (one float product, the one rcf_chan_read_fm(gain) delivers), u[m] = 0 before
+ * the stage's first input (the block's history of 8 taps, zero at the start); counted from that input p starts at -7.
+ * T is the interpolator bank, 129 rows of 8 floats.  With omega_mid = omega and omega_lim = omega_mid *
+ * omega_relative_limit rounded to float once, symbol k is produced as soon as u[p .. p + 7] all exist:
+ *     imu  = (int)rintf(mu * 128.0f)
+ *     y    = sum over j = 0 .. 7, in that order, from 0, of  T[imu][7 - j] * u[p + j]
+ *     mm   = slice(last) * y - slice(y) * last                         slice(x) = x < 0 ? -1.0f : 1.0f
+ *     last = y
+ *     omega = omega + gain_omega * mm
+ *     omega = omega_mid + 0.5f * (fabsf((omega - omega_mid) + omega_lim) - fabsf((omega - omega_mid) - omega_lim))
+ *     mu   = mu + omega + gain_mu * mm                                 (left to right)
+ *     step = (int)floorf(mu);  mu = mu - floorf(mu);  p += step        (a step beyond the int range saturates)
+ *     out[k] = y;  bit k = y >= 0
+ * every product and sum rounded to float on its own (no fused multiply-add).  Two guards keep the loop bounded on any
+ * input, where GNU Radio reads out of bounds or asserts: a step < 1 advances p by 1; a mu or omega that is not finite after
+ * the update puts the state back to (mu, omega_mid, last = 0) of the call and advances p by (int)ceilf(omega_mid).  Both
+ * count in `slips`; neither happens on a signal a locked loop sees.  The outputs depend on the input stream only, never on
+ * how it was cut into blocks: a symbol whose window crosses a block boundary comes with the block that completes it.
+ * Against GNU Radio itself the stage is "parity unpinned" (DESIGN.md 2): its 8-tap sum is a volk dot product of unknown
+ * order, its build may contract, and its table is not this one unless the caller passes it.
+ * p == NULL switches the stage off.  It starts, with zero history, at the channel's next output (again on every call:
+ * symbol 0 is the first of the call); applies from the next block on, on every channel kind (direct, chained, stage-2,
+ * filterbank tap, discriminator-only taps included: it reads the discriminator ring, not the IQ); a retune keeps it,
+ * closing the channel releases it.  Packet framing behind the slicer stays with the consumer.
+ * RCF_EINVAL: a non-finite parameter, omega * (1 - omega_relative_limit) < 2 (GNU Radio's documented domain), omega > 4096,
+ * mu outside 0 .. 1; RCF_ENOCHAN: no such channel; RCF_ECAP: out_capacity < 16 -- and at a block that yields more outputs
+ * than the ring holds beside the 7 samples of look-back (nothing is queued then). */
+typedef struct rcf_clock_mm_params {
+    float gain;                 /* quadrature_demod_cf gain in front (5 in both demods) */
+    float omega, gain_omega, mu, gain_mu, omega_relative_limit;
+    int reserved_;
+    const float *interp_taps;   /* 129 x 8, row-major; NULL = rcf_design_mmse_interpolator(8, 128, 0.25) */
+} rcf_clock_mm_params_t;
+int rcf_chan_clock_mm(rcf_t *h, int chan_id, const rcf_clock_mm_params_t *p);
+/* soft symbols produced since the stage was (last) enabled, and how often its guards fired; syncs the stream, like
+ * rcf_chan_audio_produced.  RCF_ESTATE without the stage (here and in the two calls below) */
+int rcf_chan_clock_produced(rcf_t *h, int chan_id, int64_t *n_symbols, int64_t *n_slips);
+/* unread soft symbols (float32), oldest first; the bit of a symbol is (out[i] >= 0) */
+int64_t rcf_chan_read_clock(rcf_t *h, int chan_id, float *out, size_t max_symbols);
+/* device pointer of the soft-symbol ring and its capacity (zero-copy, like rcf_chan_rings): symbol k lives at index
+ * k & (capacity-1); rcf_chan_clock_produced gives the count */
+int rcf_chan_clock_ring(rcf_t *h, int chan_id, void **sym_ring, size_t *capacity);
 /* drift probe of p25_control_demod.py:123-127: moving_average_ff(window, 1) * (1/window) of the
  * discriminator output (window = 10000 there) == mean of gain*fm over the last `window` samples; this is
  * the value demod_watcher hands to frontend_connector.report_offset */

@@ -1,5 +1,6 @@
 // rcf_chan.cpp -- channels: lifecycle (channel.channel / set_offset / destroy of /root/reference/rc_frontend/channel.py),
-// the one read path of every host read, the P25 symbol filter and AGC, the analog voice chain, source shift.
+// the one read path of every host read, the P25 symbol filter and AGC, the SmartNet / EDACS symbol clock, the analog voice
+// chain, source shift.
 #include <atomic>
 
 #include "rcf_plan.h"
@@ -155,6 +156,9 @@ void free_channel(rcf_t *h, Chan *c)
     bury(h, c->d_symtaps);
     bury(h, c->d_agc);
     c->d_agc = nullptr;
+    bury(h, c->d_clk);                                    // ring, state and the caller's bank: one allocation
+    c->d_clk = nullptr;
+    c->d_clk_taps = nullptr;
     if (c->audio) { bury(h, c->audio->d_state); bury(h, c->audio->d_rings); bury(h, c->audio->d_taps); c->audio.reset(); }
     c->d_sym = nullptr;
     c->d_symtaps = nullptr;
@@ -541,6 +545,118 @@ int rcf_chan_agc_ring(rcf_t *h, int chan_id, void **agc_ring, size_t *capacity)
     const int rc = chan_stream(h, c, RCF_READ_AGC, &s);
     if (rc != RCF_OK) return rc;
     if (agc_ring) *agc_ring = const_cast<void *>(s.ring);
+    if (capacity) *capacity = h->out_cap;
+    return RCF_OK;
+}
+
+// ---- clock_recovery_mm_ff behind the discriminator (clock.hip)
+static int clock_state(rcf_t *h, Chan *c, ClockState *st)
+{
+    RCF_HIP(hipMemcpyAsync(st, c->d_clk + h->out_cap, sizeof(*st), hipMemcpyDeviceToHost, h->stream));
+    RCF_HIP(hipStreamSynchronize(h->stream));
+    return RCF_OK;
+}
+
+int rcf_chan_clock_mm(rcf_t *h, int chan_id, const rcf_clock_mm_params_t *p)
+{
+    if (!h) return RCF_EINVAL;
+    if (p) {
+        if (!std::isfinite(p->gain) || !std::isfinite(p->omega) || !std::isfinite(p->gain_omega) || !std::isfinite(p->mu) ||
+            !std::isfinite(p->gain_mu) || !std::isfinite(p->omega_relative_limit)) {
+            set_error("clock recovery: non-finite parameter");
+            return RCF_EINVAL;
+        }
+        // GNU Radio's documented domain (omega stays >= 2 samples per symbol at its lower limit); mu selects a row of the bank
+        if ((double)p->omega * (1.0 - (double)p->omega_relative_limit) < 2.0 || p->omega > 4096.f || p->mu < 0.f || p->mu > 1.f) {
+            set_error("clock recovery: omega %g (relative limit %g) outside 2 / (1 - limit) .. 4096, or mu %g outside 0 .. 1",
+                      p->omega, p->omega_relative_limit, p->mu);
+            return RCF_EINVAL;
+        }
+    }
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!p) {                           // off: ring, state and bank go once the stream has passed them
+        if (c->d_clk) {
+            bury(h, c->d_clk);
+            c->d_clk = nullptr;
+            c->d_clk_taps = nullptr;
+            ++h->chans_epoch;
+        }
+        return RCF_OK;
+    }
+    if ((size_t)kClockTaps * 2 > h->out_cap) { set_error("ring of %zu too small for the clock's %d-sample window", h->out_cap, kClockTaps); return RCF_ECAP; }
+    constexpr size_t kBank = (size_t)(kClockSteps + 1) * kClockTaps;
+    if (!p->interp_taps && !h->d_mmse) {
+        const std::vector<float> t = design_mmse_interpolator(kClockTaps, kClockSteps, 0.25);
+        float *d = nullptr;
+        RCF_HIP(hipMalloc(&d, sizeof(float) * kBank));
+        if (!hip_ok(hipMemcpy(d, t.data(), sizeof(float) * kBank, hipMemcpyHostToDevice), "hipMemcpy(interpolator bank)")) { (void)hipFree(d); return RCF_EHIP; }
+        h->d_mmse = d;
+    }
+    // every call is a new GR block: a fresh ring and state (symbol 0 is the first of this call), zero history
+    const size_t state_at = h->out_cap, bank_at = h->out_cap + 64;       // in floats; the state record has 256 bytes to itself
+    float *fresh = nullptr;
+    RCF_HIP(hipMalloc(&fresh, sizeof(float) * (bank_at + (p->interp_taps ? kBank : 0))));
+    Chan::ClockMm k;
+    k.gain = p->gain; k.mu0 = p->mu; k.omega_mid = p->omega;
+    k.omega_lim = k.omega_mid * p->omega_relative_limit;                 // (one float product)
+    k.gain_omega = p->gain_omega; k.gain_mu = p->gain_mu;
+    k.adv0 = (int)std::ceil(k.omega_mid);
+    ClockState st0{};
+    st0.p = c->produced - (kClockTaps - 1);                              // the first window: seven zeros and u[first]
+    st0.mu = k.mu0; st0.omega = k.omega_mid; st0.last = 0.f;
+    if (!hip_ok(hipMemcpy(fresh + state_at, &st0, sizeof(st0), hipMemcpyHostToDevice), "hipMemcpy(clock state)") ||
+        (p->interp_taps && !hip_ok(hipMemcpy(fresh + bank_at, p->interp_taps, sizeof(float) * kBank, hipMemcpyHostToDevice), "hipMemcpy(interpolator bank)"))) {
+        (void)hipFree(fresh);
+        return RCF_EHIP;
+    }
+    bury(h, c->d_clk);
+    c->d_clk = fresh;
+    c->d_clk_taps = p->interp_taps ? fresh + bank_at : h->d_mmse;
+    c->clk = k;
+    c->clk_from = c->produced;
+    c->rd_clk = 0;
+    ++h->chans_epoch;
+    return RCF_OK;
+}
+
+int rcf_chan_clock_produced(rcf_t *h, int chan_id, int64_t *n_symbols, int64_t *n_slips)
+{
+    if (!h || !n_symbols) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!c->d_clk) { set_error("channel %d has no symbol clock", chan_id); return RCF_ESTATE; }
+    ClockState st{};
+    const int rc = clock_state(h, c, &st);
+    if (rc != RCF_OK) return rc;
+    *n_symbols = st.n_out;
+    if (n_slips) *n_slips = st.slips;
+    return RCF_OK;
+}
+
+int64_t rcf_chan_read_clock(rcf_t *h, int chan_id, float *out, size_t max_symbols)
+{
+    if (!h || !out) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!c->d_clk) { set_error("channel %d has no symbol clock", chan_id); return RCF_ESTATE; }
+    ClockState st{};
+    const int rc = clock_state(h, c, &st);
+    if (rc != RCF_OK) return rc;
+    return read_one(h, RingStream{h, c->d_clk, 1u, 0u, st.n_out, st.n_out, &c->rd_clk}, 1.0f, out, max_symbols);
+}
+
+int rcf_chan_clock_ring(rcf_t *h, int chan_id, void **sym_ring, size_t *capacity)
+{
+    if (!h) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;                  // (zero-copy readers order themselves on rcf_stream: nothing stays deferred)
+    FIND_CHAN(h, chan_id, c);
+    if (!c->d_clk) { set_error("channel %d has no symbol clock", chan_id); return RCF_ESTATE; }
+    if (sym_ring) *sym_ring = c->d_clk;
     if (capacity) *capacity = h->out_cap;
     return RCF_OK;
 }

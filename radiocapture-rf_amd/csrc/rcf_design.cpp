@@ -392,4 +392,48 @@ bool design_optfir_low_pass(double gain, double fs, double f1, double f2, double
     return true;
 }
 
+// The MMSE fractional interpolator bank of the symbol clocks (clock.hip): row s of nsteps + 1, for mu = s / nsteps, is the
+// ntaps-tap FIR h that minimises  int_{-bw}^{bw} | sum_j h_j e^{-i 2 pi f j} - e^{-i 2 pi f (ntaps / 2 - mu)} |^2 df,
+// i.e. the solution of the normal equations R h = r with
+//   R[j][l] = 2 bw sinc(2 bw (j - l)),   r[j] = 2 bw sinc(2 bw (j - ntaps / 2 + mu)),   sinc(x) = sin(pi x) / (pi x)
+// (GNU Radio's interpolator_taps.h comes from a numerical minimiser of the same objective).  R does not depend on mu: one
+// elimination with partial pivoting, in long double, serves every row.  At mu = 0 and mu = 1 r is a column of R and the
+// solution a unit row -- written as such, not as 1 +- an elimination's rounding.
+std::vector<float> design_mmse_interpolator(int ntaps, int nsteps, double bw)
+{
+    typedef long double ld;
+    const ld pi = 3.14159265358979323846264338327950288L;
+    auto sinc = [&](ld x) { return x == 0 ? (ld)1 : std::sin(pi * x) / (pi * x); };
+    const int N = ntaps, S = nsteps + 1;
+    std::vector<ld> A((size_t)N * N), B((size_t)N * S);          // R, and one right-hand side per row of the bank
+    for (int j = 0; j < N; ++j) {
+        for (int l = 0; l < N; ++l) A[(size_t)j * N + l] = 2 * (ld)bw * sinc(2 * (ld)bw * (ld)(j - l));
+        for (int s = 0; s < S; ++s) B[(size_t)j * S + s] = 2 * (ld)bw * sinc(2 * (ld)bw * ((ld)(j - N / 2) + (ld)s / (ld)nsteps));
+    }
+    for (int k = 0; k < N; ++k) {
+        int piv = k;
+        for (int j = k + 1; j < N; ++j) if (std::fabs(A[(size_t)j * N + k]) > std::fabs(A[(size_t)piv * N + k])) piv = j;
+        if (piv != k) {
+            for (int l = 0; l < N; ++l) std::swap(A[(size_t)k * N + l], A[(size_t)piv * N + l]);
+            for (int s = 0; s < S; ++s) std::swap(B[(size_t)k * S + s], B[(size_t)piv * S + s]);
+        }
+        for (int j = k + 1; j < N; ++j) {
+            const ld f = A[(size_t)j * N + k] / A[(size_t)k * N + k];
+            for (int l = k; l < N; ++l) A[(size_t)j * N + l] -= f * A[(size_t)k * N + l];
+            for (int s = 0; s < S; ++s) B[(size_t)j * S + s] -= f * B[(size_t)k * S + s];
+        }
+    }
+    for (int k = N - 1; k >= 0; --k)
+        for (int s = 0; s < S; ++s) {
+            ld v = B[(size_t)k * S + s];
+            for (int l = k + 1; l < N; ++l) v -= A[(size_t)k * N + l] * B[(size_t)l * S + s];
+            B[(size_t)k * S + s] = v / A[(size_t)k * N + k];
+        }
+    std::vector<float> taps((size_t)S * N);
+    for (int s = 0; s < S; ++s)
+        for (int j = 0; j < N; ++j)
+            taps[(size_t)s * N + j] = s == 0 ? (j == N / 2 ? 1.f : 0.f) : s == nsteps ? (j == N / 2 - 1 ? 1.f : 0.f) : (float)(double)B[(size_t)j * S + s];
+    return taps;
+}
+
 }  // namespace rcfx

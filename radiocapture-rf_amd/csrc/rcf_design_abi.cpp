@@ -102,4 +102,17 @@ int rcf_design_resampler(int interpolation, int decimation, int *interp_out, int
     return n;
 }
 
+int rcf_design_mmse_interpolator(int ntaps, int nsteps, double bw, float *taps, int cap)
+{
+    if (ntaps < 2 || ntaps > 64 || (ntaps & 1) || nsteps < 1 || nsteps > 4096 || !(bw > 0) || !(bw <= 0.5)) {
+        set_error("bad interpolator arguments");
+        return RCF_EINVAL;
+    }
+    const int n = (nsteps + 1) * ntaps;
+    if (!taps || cap < n) return -n;
+    const std::vector<float> t = design_mmse_interpolator(ntaps, nsteps, bw);
+    std::memcpy(taps, t.data(), sizeof(float) * (size_t)n);
+    return n;
+}
+
 }  // extern "C"

@@ -245,6 +245,7 @@ int rcf_close(rcf_t *h)
     bury(h, h->d_atan);
     bury(h, h->d_raw);
     bury(h, h->d_level);
+    bury(h, h->d_mmse);
     for (int i = 0; i < 2; ++i) {
         bury(h, h->d_buf[i]);
     }

@@ -256,6 +256,30 @@ struct AgcLaunch {
     int32_t pad_;
 };
 void launch_agc(const AgcLaunch *d_items, int n_items, int max_n_k, int max_nsamples, uint64_t ring_mask, hipStream_t s);
+// GNU Radio's clock_recovery_mm_ff on gain * fm (clock.hip; the SmartNet / EDACS control demodulators,
+// moto_control_demod.py:113, edacs_control_demod.py:85; definition: include/rcf.h at rcf_chan_clock_mm).
+// per-channel running state, device resident, owned by clock_mm_kernel
+struct ClockState {
+    int64_t p;               // relative fm index of the next symbol's window start u[p .. p + 7]
+    int64_t n_out;           // soft symbols written so far (symbol k at sym_ring[k & ring_mask])
+    int64_t slips;           // times one of the two guards fired
+    float mu, omega, last;
+    int32_t pad_;
+};
+constexpr int kClockTaps = 8, kClockSteps = 128;      // the interpolator bank: (kClockSteps + 1) rows of kClockTaps floats
+struct ClockLaunch {
+    const float *fm_ring;
+    float *sym_ring;
+    ClockState *st;
+    const float *taps;       // the bank, row-major (device)
+    int64_t n_lo;            // first relative fm index that is new in this launch
+    int64_t n_first;         // inputs before this index count as zero (the stage's start)
+    int32_t n_k;
+    int32_t adv0;            // (int)ceilf(omega_mid): the advance after a reset
+    float gain, mu0, omega_mid, omega_lim, gain_omega, gain_mu;
+};
+void launch_clock_mm(const ClockLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
+std::vector<float> design_mmse_interpolator(int ntaps, int nsteps, double bw);
 // mean of gain * fm over the last `window` samples ending at n_end (exclusive), one workgroup
 void launch_fm_level(const float *fm_ring, int64_t n_end, int window, float gain, uint64_t ring_mask, float *d_out,
                      hipStream_t s);

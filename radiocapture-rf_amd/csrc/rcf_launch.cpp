@@ -36,6 +36,7 @@ void launch_tail(rcf_t *h, const TailRecs &r, hipStream_t st)
     }
     if (r.symf) { Timed t(h, RCF_T_DISC); launch_fm_fir(r.symf, r.n_symf, r.symf_max_n, h->ring_mask, st); }
     if (r.agcf) { Timed t(h, RCF_T_DISC); launch_agc(r.agcf, r.n_agcf, r.agcf_max_n, r.agcf_max_ns, h->ring_mask, st); }
+    if (r.clkf) { Timed t(h, RCF_T_CLOCK); launch_clock_mm(r.clkf, r.n_clkf, r.clkf_max_n, h->ring_mask, st); }
 }
 
 void launch_member_audio(rcf_t *h, const BlockPlan &bp, hipStream_t st)
@@ -75,7 +76,7 @@ int launch_plan(rcf_t *h, BlockPlan &bp)
     // ... and this block's own: ONE small-T job on the bank's bins, nothing that consumes its outputs within the block
     FirJob *lag_job = nullptr;
     if (h->lag_enabled && carry && fir_by_depth.size() == 2 && fir_by_depth[1].size() == 1 && fir_by_depth[1][0].dims.small &&
-        fir_by_depth[1][0].dev && fir_by_depth[1][0].bank_src && !bp.d_symf && !bp.d_agcf && !bp.d_audf &&
+        fir_by_depth[1][0].dev && fir_by_depth[1][0].bank_src && !bp.d_symf && !bp.d_agcf && !bp.d_clkf && !bp.d_audf &&
         (size_t)pl.n_frames * 2 + pfb_reach <= h->out_cap)
         lag_job = &fir_by_depth[1][0];
     {
@@ -126,7 +127,8 @@ int launch_plan(rcf_t *h, BlockPlan &bp)
             launch_fir_bank(j.dev, j.dims, st);
         }
     launch_tail(h, TailRecs{bp.disc_jobs.data(), bp.disc_jobs.size(), bp.d_symf, (int)bp.symf.size(), bp.symf_max_n,
-                            bp.d_agcf, (int)bp.agcf.size(), bp.agcf_max_n, bp.agcf_max_ns}, st);
+                            bp.d_agcf, (int)bp.agcf.size(), bp.agcf_max_n, bp.agcf_max_ns,
+                            bp.d_clkf, (int)bp.clkf.size(), bp.clkf_max_n}, st);
     launch_member_audio(h, bp, st);
     return RCF_OK;
 }

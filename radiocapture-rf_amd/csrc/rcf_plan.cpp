@@ -63,6 +63,7 @@ const rcf_t::PlanCache &plan_cache(rcf_t *h)
         n_fir += c.is_tap ? 0 : 1;
         if (c.d_sym) need += sizeof(FmFirLaunch);
         if (c.d_agc) need += sizeof(AgcLaunch);
+        if (c.d_clk) need += sizeof(ClockLaunch);
         if (c.audio) need += sizeof(AudioLaunch);
         pc.max_depth = std::max(pc.max_depth, c.depth);
         if (c.src < 0 && (pc.min_d0 == 0 || c.D < pc.min_d0)) pc.min_d0 = c.D;
@@ -71,6 +72,11 @@ const rcf_t::PlanCache &plan_cache(rcf_t *h)
         if (c.d_agc) {                                // the AGC's window reaches N - 1 samples behind the block's first output
             size_t &own = pc.reach_x[c.id];
             own = std::max<size_t>(own, std::max<size_t>(1, (size_t)c.agc_n - 1));
+            pc.max_reach = std::max(pc.max_reach, own);
+        }
+        if (c.d_clk) {                                // a symbol's window starts up to 7 samples behind the block's first output
+            size_t &own = pc.reach_x[c.id];
+            own = std::max<size_t>(own, (size_t)kClockTaps - 1);
             pc.max_reach = std::max(pc.max_reach, own);
         }
         if (c.src >= RCF_SRC_PFB_BIN0) {              // (the bank's ring: one entry for all of its consumers, set after the loop)
@@ -211,7 +217,7 @@ int plan_pfb(rcf_t *h, BlockPlan &bp)
     return RCF_OK;
 }
 
-// one channel's launch records (FIR / tap, discriminator, symbol filter, AGC, voice chain, exact rotator) and the advance of
+// one channel's launch records (FIR / tap, discriminator, symbol filter, AGC, symbol clock, voice chain, exact rotator) and the advance of
 // its state.  Returns RCF_OK also when the channel has nothing to do in this block.
 int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c, int D)
 {
@@ -339,6 +345,23 @@ int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c, int D)
             agcf.push_back(al);
             bp.agcf_max_n = std::max(bp.agcf_max_n, (int)al.n_k);
             bp.agcf_max_ns = std::max(bp.agcf_max_ns, c->agc_n);
+        }
+    }
+    if (c->d_clk) {
+        ClockLaunch cl{};
+        cl.fm_ring = c->d_fm;
+        cl.sym_ring = c->d_clk;
+        cl.st = reinterpret_cast<ClockState *>(c->d_clk + h->out_cap);
+        cl.taps = c->d_clk_taps;
+        cl.n_lo = std::max(dl.n_lo, c->clk_from);
+        cl.n_first = c->clk_from;
+        cl.n_k = (int32_t)(dl.n_lo + dl.n_k - cl.n_lo);
+        cl.adv0 = c->clk.adv0;
+        cl.gain = c->clk.gain; cl.mu0 = c->clk.mu0; cl.omega_mid = c->clk.omega_mid; cl.omega_lim = c->clk.omega_lim;
+        cl.gain_omega = c->clk.gain_omega; cl.gain_mu = c->clk.gain_mu;
+        if (cl.n_k > 0) {
+            bp.clkf.push_back(cl);
+            bp.clkf_max_n = std::max(bp.clkf_max_n, (int)cl.n_k);
         }
     }
     if (c->audio) {
@@ -621,10 +644,12 @@ int plan_tail(rcf_t *h, BlockPlan &bp)
         pl.tap_pitch = (int32_t)mat_pitch;
         pl.n_taps = (int32_t)tap_list.size();
     }
-    // (a group's block: the exact-rotator fills, the symbol filters and the AGCs of all members go out as one launch each)
+    // (a group's block: the exact-rotator fills, the symbol filters, the AGCs and the symbol clocks of all members go out as
+    // one launch each)
     if (!bp.defer && !rot_fills.empty() && !ar.put(rot_fills, &d_rot_fills)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
     if (!bp.defer && !symf.empty() && !ar.put(symf, &d_symf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
     if (!bp.defer && !agcf.empty() && !ar.put(agcf, &bp.d_agcf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
+    if (!bp.defer && !bp.clkf.empty() && !ar.put(bp.clkf, &bp.d_clkf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
     if (!audf.empty() && !ar.put(audf, &d_audf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
     return RCF_OK;
 }

@@ -56,6 +56,8 @@ struct Chan {
     float2 *d_rot = nullptr;
     float *d_sym = nullptr;       // optional real FIR over gain * fm (P25 symbol filter), below
     float2 *d_agc = nullptr;      // optional feedforward AGC over the IQ stream (P25 CQPSK front half), below
+    float *d_clk = nullptr;       // optional symbol clock over gain * fm (SmartNet / EDACS), below: soft-symbol ring of out_cap
+                                  // floats | ClockState | the caller's interpolator bank, if it passed one
     // rotator model
     double extra_dangle = 0, extra_dlogmag = 0;   // added to the increment's own angle / log magnitude (filterbank taps)
     double dangle = 0, dlogmag = 0;
@@ -90,6 +92,11 @@ struct Chan {
     float agc_ref = 1.f;
     int64_t agc_from = 0;         // first relative output index the AGC is defined for (zero history before it)
     int64_t rd_agc = 0;
+    // clock_recovery_mm_ff (rcf_chan_clock_mm): the constants as the kernel takes them, rounded to float once
+    struct ClockMm { float gain = 1.f, mu0 = 0.f, omega_mid = 0.f, omega_lim = 0.f, gain_omega = 0.f, gain_mu = 0.f; int adv0 = 1; } clk;
+    const float *d_clk_taps = nullptr;   // the bank the stage reads: the handle's default (rcf::d_mmse) or the caller's, inside d_clk
+    int64_t clk_from = 0;         // first relative output index the stage reads (zero history before it)
+    int64_t rd_clk = 0;           // soft symbols handed to the reader
     uint64_t many_stamp = 0;      // the host_read call that last listed this channel (batched reads: one reader per stream)
     double src_rate = 0, offset_hz = 0;
     uint64_t taps_version = 0;    // bumped whenever d_ctaps changes (bank-matrix cache key)
@@ -183,6 +190,7 @@ struct rcf {
     double shift_hz = 0;          // accumulated rcf_source_shift
     float *d_atan = nullptr;
     float *d_level = nullptr;     // rcf_chan_fm_level result
+    float *d_mmse = nullptr;      // rcf_design_mmse_interpolator(8, 128, 0.25): the symbol clocks' default bank, built at first use
     void *d_raw = nullptr;        // wire-format staging (rcf_push_raw), block_cap * 4 bytes, lazily allocated
     // launch-parameter arenas (pinned host + device), double buffered
     rcfx::ArenaSet arenas;
@@ -200,8 +208,8 @@ struct rcf {
     struct rcf_group *group = nullptr;
     hipStream_t own_stream = nullptr;
     std::map<int, std::unique_ptr<Chan>> chans;
-    uint64_t chans_epoch = 0;     // bumped whenever a channel is opened or closed or gains / loses a symbol filter, AGC or
-                                  // voice chain (cached Chan pointers: the pump's; the cached arena need below)
+    uint64_t chans_epoch = 0;     // bumped whenever a channel is opened or closed or gains / loses a symbol filter, AGC,
+                                  // symbol clock or voice chain (cached Chan pointers: the pump's; the cached arena need below)
     // What planning a block needs to know about the channel SET (not their counters), valid while epoch == chans_epoch:
     // the summary plan_arena() used to rebuild from a walk over every channel, and the (depth, D, T) classes plan_block()
     // used to re-bucket -- three passes of pointer chasing per block (20 us of a 30 us plan for a front-end with 256

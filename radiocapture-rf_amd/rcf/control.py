@@ -1,0 +1,39 @@
+"""The SmartNet and EDACS control demodulators behind a channel, on the GPU up to the slicer
+(moto_control_demod.py:105-132, edacs_control_demod.py:82-112).  Both have one shape:
+
+  quadrature_demod_cf(5) -> clock_recovery_mm_ff(rate / symbol_rate, 1.4395919, 0.5, 0.05, 0.005)
+                         -> binary_slicer_fb -> unpacked_to_packed_bb(1, MSB_FIRST)
+
+The discriminator and the Mueller and Mueller clock run per channel on the GPU (rcf_chan_clock_mm): a demod reads soft
+symbols at 3600 or 9600 per second (chan_read_clock), slices and packs them (pack_bits) and does the packet framing."""
+import numpy as np
+
+QUAD_GAIN = 5.0              # moto_control_demod.py:105, edacs_control_demod.py:84
+GAIN_OMEGA = 1.4395919       # moto_control_demod.py:113, edacs_control_demod.py:85 (the four constants below too)
+MU = 0.5
+GAIN_MU = 0.05
+OMEGA_RELATIVE_LIMIT = 0.005
+
+
+def smartnet_clock(fe, cid, channel_rate=25000, symbol_rate=3600.0):
+    """clock_recovery_mm_ff(channel_rate / symbol_rate, ...) behind quadrature_demod_cf(5) on channel `cid` of Frontend
+    `fe` (moto_control_demod.py:103-113: channel_rate = 2 x 12500, symbol_rate = 3600.0 at :50)"""
+    fe.chan_clock_mm(cid, channel_rate / symbol_rate, GAIN_OMEGA, MU, GAIN_MU, OMEGA_RELATIVE_LIMIT, QUAD_GAIN)
+
+
+def edacs_clock(fe, cid, receive_rate=25000, symbol_rate=9600.0):
+    """the same behind an EDACS control channel (edacs_control_demod.py:76,85: receive_rate = 2 x 12500, symbol_rate
+    the system's, 9600 or 4800)"""
+    fe.chan_clock_mm(cid, receive_rate / symbol_rate, GAIN_OMEGA, MU, GAIN_MU, OMEGA_RELATIVE_LIMIT, QUAD_GAIN)
+
+
+def pack_bits(soft, carry=None):
+    """binary_slicer_fb -> unpacked_to_packed_bb(1, GR_MSB_FIRST) (moto_control_demod.py:114-115,
+    edacs_control_demod.py:86-90) over the soft symbols of one read: bit = soft >= 0, eight bits per byte, first bit in
+    the byte's top place.  `carry` holds the 0 .. 7 bits the call before left over (a uint8 array of 0 / 1); returns
+    (bytes as a uint8 array, the new carry)."""
+    bits = (np.asarray(soft, dtype=np.float32) >= 0).astype(np.uint8)
+    if carry is not None and len(carry):
+        bits = np.concatenate([np.asarray(carry, dtype=np.uint8), bits])
+    whole = len(bits) // 8 * 8
+    return np.packbits(bits[:whole]), bits[whole:].copy()

@@ -34,6 +34,7 @@ SYMBOLS = [
     "rcf_peak_frequency", "rcf_scan_find_peaks", "rcf_timing_enable", "rcf_timing_read",
     "rcf_ingest_write", "rcf_push_raw", "rcf_chan_fm_filter", "rcf_chan_read_sym", "rcf_chan_fm_level",
     "rcf_chan_agc", "rcf_chan_read_agc", "rcf_chan_agc_ring",
+    "rcf_chan_clock_mm", "rcf_chan_clock_produced", "rcf_chan_read_clock", "rcf_chan_clock_ring", "rcf_design_mmse_interpolator",
     "rcf_design_firdes", "rcf_design_optfir_low_pass", "rcf_design_fm_deemph", "rcf_design_resampler", "rcf_chan_audio_open",
     "rcf_chan_audio_close", "rcf_chan_audio_produced", "rcf_chan_read_audio",
     "rcf_host_alloc", "rcf_host_free", "rcf_comm_unique_id", "rcf_comm_init", "rcf_comm_destroy", "rcf_comm_size",
@@ -44,7 +45,7 @@ SYMBOLS = [
 ]
 FMT_CF32, FMT_U8, FMT_S8, FMT_S16 = 0, 1, 2, 3
 READ_IQ, READ_FM, READ_AGC = 0, 1, 2
-T_FIR, T_PFB, T_FIR_DERIVED, T_DISC, T_SCAN_FFT, T_SCAN_MOVSUM, T_HISTORY, T_FIR_MFMA, T_AUDIO, T_TAPS = range(10)
+T_FIR, T_PFB, T_FIR_DERIVED, T_DISC, T_SCAN_FFT, T_SCAN_MOVSUM, T_HISTORY, T_FIR_MFMA, T_AUDIO, T_TAPS, T_CLOCK = range(11)
 
 
 class AudioParams(C.Structure):
@@ -54,6 +55,13 @@ class AudioParams(C.Structure):
                 ("lpf_taps", C.POINTER(C.c_float)), ("n_lpf", C.c_int), ("n_hpf", C.c_int),
                 ("hpf_taps", C.POINTER(C.c_float)), ("rs_taps", C.POINTER(C.c_float)), ("n_rs", C.c_int),
                 ("interpolation", C.c_int), ("decimation", C.c_int), ("reserved2_", C.c_int)]
+
+
+class ClockMmParams(C.Structure):
+    """rcf_clock_mm_params_t (include/rcf.h)"""
+    _fields_ = [("gain", C.c_float), ("omega", C.c_float), ("gain_omega", C.c_float), ("mu", C.c_float),
+                ("gain_mu", C.c_float), ("omega_relative_limit", C.c_float), ("reserved_", C.c_int),
+                ("interp_taps", C.POINTER(C.c_float))]
 
 
 class PumpConfig(C.Structure):
@@ -126,6 +134,11 @@ def lib():
         "rcf_chan_agc": (C.c_int, [vp, C.c_int, C.c_int, C.c_float]),
         "rcf_chan_read_agc": (i64, [vp, C.c_int, fp, sz]),
         "rcf_chan_agc_ring": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]),
+        "rcf_chan_clock_mm": (C.c_int, [vp, C.c_int, C.POINTER(ClockMmParams)]),
+        "rcf_chan_clock_produced": (C.c_int, [vp, C.c_int, C.POINTER(i64), C.POINTER(i64)]),
+        "rcf_chan_read_clock": (i64, [vp, C.c_int, fp, sz]),
+        "rcf_chan_clock_ring": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]),
+        "rcf_design_mmse_interpolator": (C.c_int, [C.c_int, C.c_int, C.c_double, fp, C.c_int]),
         "rcf_chan_fm_level": (C.c_int, [vp, C.c_int, C.c_float, C.c_int, fp]),
         "rcf_design_firdes": (C.c_int, [C.c_int] + [C.c_double] * 4 + [C.c_int, C.c_double, fp, C.c_int]),
         "rcf_design_optfir_low_pass": (C.c_int, [C.c_double] * 6 + [fp, C.c_int]),
@@ -286,6 +299,18 @@ def design_resampler(interpolation, decimation):
     taps = np.empty(n, dtype=np.float32)
     _check(L.rcf_design_resampler(int(interpolation), int(decimation), C.byref(i), C.byref(d), _fp(taps), n))
     return i.value, d.value, taps
+
+
+def design_mmse_interpolator(ntaps=8, nsteps=128, bw=0.25) -> np.ndarray:
+    """[nsteps + 1, ntaps] MMSE fractional-delay interpolator bank (rcf_design_mmse_interpolator): row s interpolates at
+    mu = s / nsteps; the default is the bank rcf_chan_clock_mm uses when the caller passes none"""
+    L = lib()
+    n = -L.rcf_design_mmse_interpolator(int(ntaps), int(nsteps), float(bw), None, 0)
+    if n <= 0:
+        _check(-n if n else RCF_EINVAL)
+    taps = np.empty(n, dtype=np.float32)
+    _check(L.rcf_design_mmse_interpolator(int(ntaps), int(nsteps), float(bw), _fp(taps), n))
+    return taps.reshape(int(nsteps) + 1, int(ntaps))
 
 
 def design_window(window, n) -> np.ndarray:
@@ -611,6 +636,44 @@ class Frontend:
         """(device pointer, capacity) of the channel's cf32 AGC ring (rcf_chan_agc_ring)"""
         p, cap = C.c_void_p(), C.c_size_t()
         _check(lib().rcf_chan_agc_ring(self._h, cid, C.byref(p), C.byref(cap)))
+        return p.value, cap.value
+
+    def chan_clock_mm(self, cid, omega, gain_omega=1.4395919, mu=0.5, gain_mu=0.05, omega_relative_limit=0.005, gain=5.0,
+                      interp_taps=None):
+        """digital.clock_recovery_mm_ff(omega, gain_omega, mu, gain_mu, omega_relative_limit) on quadrature_demod_cf(gain)
+        of the channel (rcf_chan_clock_mm; moto_control_demod.py:113, edacs_control_demod.py:85), starting with zero
+        history at the channel's next output; omega=None switches it off.  interp_taps: a [129, 8] interpolator bank
+        (GNU Radio's, for a caller who has it); None = design_mmse_interpolator()"""
+        if omega is None:
+            _check(lib().rcf_chan_clock_mm(self._h, cid, None))
+            return
+        p = ClockMmParams()
+        p.gain, p.omega, p.gain_omega, p.mu = float(gain), float(omega), float(gain_omega), float(mu)
+        p.gain_mu, p.omega_relative_limit = float(gain_mu), float(omega_relative_limit)
+        taps = None
+        if interp_taps is not None:
+            taps = np.ascontiguousarray(interp_taps, dtype=np.float32)
+            if taps.shape != (129, 8):
+                raise ValueError("interp_taps must be a [129, 8] array")
+            p.interp_taps = _fp(taps)
+        _check(lib().rcf_chan_clock_mm(self._h, cid, C.byref(p)))
+
+    def chan_clock_produced(self, cid):
+        """(soft symbols produced since the clock was enabled, times its guards fired) (rcf_chan_clock_produced)"""
+        n, s = C.c_int64(), C.c_int64()
+        _check(lib().rcf_chan_clock_produced(self._h, cid, C.byref(n), C.byref(s)))
+        return n.value, s.value
+
+    def chan_read_clock(self, cid, max_symbols=1 << 20) -> np.ndarray:
+        """unread soft symbols of the channel's clock, oldest first; the bits are (out >= 0)"""
+        out = np.empty(max_symbols, dtype=np.float32)
+        n = _check(lib().rcf_chan_read_clock(self._h, cid, _fp(out), max_symbols))
+        return out[:n].copy()
+
+    def chan_clock_ring(self, cid):
+        """(device pointer, capacity) of the channel's float32 soft-symbol ring (rcf_chan_clock_ring)"""
+        p, cap = C.c_void_p(), C.c_size_t()
+        _check(lib().rcf_chan_clock_ring(self._h, cid, C.byref(p), C.byref(cap)))
         return p.value, cap.value
 
     def chan_fm_level(self, cid, gain, window=10000) -> float:
