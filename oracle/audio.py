@@ -227,6 +227,8 @@ def fir_filter_fff(x: np.ndarray, taps: np.ndarray) -> np.ndarray:
     """decimation 1, zero history; float64 accumulation rounded once (VOLK's summation order is unspecified)."""
     x64 = np.asarray(x, dtype=np.float64)
     t64 = np.asarray(taps, dtype=np.float64)
+    if len(x64) == 0:                                           # (a squelch that never opened: np.convolve refuses)
+        return np.zeros(0, dtype=f32)
     return np.convolve(x64, t64)[: len(x64)].astype(f32)
 
 
@@ -266,9 +268,10 @@ def rational_resampler_fff(x: np.ndarray, interpolation: int, decimation: int, t
 
 
 # ------------------------------------------------------------------ the whole chain
-def analog_chain(iq: np.ndarray, rate: float, stages=False):
-    """logging_receiver.py:211-222 on one channel's complex stream at `rate` samples/s -> 8 kHz float audio"""
-    g = pwr_squelch_cc(iq, -100.0, 0.01, True)
+def analog_chain(iq: np.ndarray, rate: float, stages=False, squelch_db=-100.0, squelch_alpha=0.01):
+    """logging_receiver.py:211-222 on one channel's complex stream at `rate` samples/s -> 8 kHz float audio
+    (squelch_db, squelch_alpha: pwr_squelch_cc's arguments, the reference's by default)"""
+    g = pwr_squelch_cc(iq, squelch_db, squelch_alpha, True)
     k = rate / (2 * math.pi * 15000)
     fm = G.quadrature_demod_cf(g, f32(k))
     b, a = fm_deemph_taps(rate, 75e-6)

@@ -373,3 +373,64 @@ def test_bounded_on_hostile_input(gpu_required, bank):
             assert np.isfinite(sym).all()
             if k in (1, 2, 3):
                 assert slips > 0, k
+
+
+def test_mixed_channel_rates_in_one_wave(gpu_required, bank):
+    """six clocked channels at 12.5, 25 and 50 kS/s in one wave: n_k = 250, 500 and 1000 per block, so the lanes leave the
+    chunk loop at different trips, each with its own omega; one is enabled two blocks late"""
+    nat = gpu_required
+    blk, K = 48000, 6
+    rng = np.random.default_rng(6)
+    # (chan_open's channel rate, baud, offset): omega = 2 * channel rate / baud = 3.47, 6.94, 2.60, 5.21, 13.9, 3.47
+    shapes = [(6250, 3600.0, -700000.0), (12500, 3600.0, -400000.0), (12500, 9600.0, -100000.0),
+              (25000, 9600.0, 200000.0), (25000, 3600.0, 500000.0), (6250, 3600.0, 800000.0)]
+    sent = {k: _carrier(rng, shapes[k][1], blk * K, shapes[k][2]) for k in (1, 3)}
+    x = (0.05 * synth.awgn(rng, blk * K) + sent[1][0] + sent[3][0]).astype(np.complex64)
+    omega = [2 * cr / baud for cr, baud, _ in shapes]
+    late = 4
+    with nat.Frontend(FS, device=0, block_capacity=blk) as fe:
+        cids = [fe.chan_open(cr, off) for cr, _, off in shapes]
+        fe.timing_enable(True, classes=[nat.T_CLOCK])
+        for k, c in enumerate(cids):
+            if k != late:
+                fe.chan_clock_mm(c, omega[k])
+        _push_blocks(fe, x[:2 * blk], blk)
+        f_late = fe.chan_produced(cids[late])
+        fe.chan_clock_mm(cids[late], omega[late])
+        _push_blocks(fe, x[2 * blk:], blk)
+        assert fe.timing_read(nat.T_CLOCK)[1] == K                   # one launch per block carries all six
+        assert f_late == 2 * blk // 48
+        for k, c in enumerate(cids):
+            sym, slips, fm = _check_clock(fe, c, omega[k], bank, ("mixed rates", k), fm_from=f_late if k == late else 0)
+            assert len(fm) == K * blk * 2 * shapes[k][0] // int(FS)
+            if k in sent:
+                assert slips == 0 and M.align_bits(sym >= 0, sent[k][1], skip=100)[1] == 0
+
+
+def test_symbol_ring_wraps(gpu_required, bank):
+    """out_capacity 1024 and more than 2500 symbols: the soft-symbol ring (and the discriminator ring it reads) wraps at
+    least twice; read after every push, the concatenation is the restatement of the concatenated discriminator stream"""
+    nat = gpu_required
+    blk, K = 96 * 1000, 7                                            # 1000 channel samples a block: 1000 + 7 <= 1024
+    omega = 25000 / 9600.0
+    rng = np.random.default_rng(1024)
+    car, sent = _carrier(rng, 9600.0, blk * K, 250000.0)
+    x = (0.05 * synth.awgn(rng, blk * K) + car).astype(np.complex64)
+    syms, fms = [], []
+    with nat.Frontend(FS, device=0, block_capacity=96 * 1100, out_capacity=1 << 10) as fe:
+        c = fe.chan_open(12500, 250000.0)
+        fe.chan_clock_mm(c, omega)
+        assert fe.chan_clock_ring(c)[1] == 1024
+        for b in range(K):
+            fe.push(x[b * blk:(b + 1) * blk])
+            fms.append(fe.chan_read_fm(c, 5.0))
+            syms.append(fe.chan_read_clock(c))
+        n, slips = fe.chan_clock_produced(c)
+    fm, sym = np.concatenate(fms), np.concatenate(syms)
+    want, wslips = M.clock_recovery_mm(fm, omega, taps=bank, unit_gain_input=False)
+    print("wrapped ring: %d inputs, %d symbols (restatement %d), slips %d (%d)" % (len(fm), n, len(want), slips, wslips))
+    assert len(fm) == K * 1000 and len(want) > 2500 and all(0 < len(s) < 1024 for s in syms)
+    assert n == len(want) == len(sym)
+    _same_bits(sym, want, "wrapped ring")
+    assert slips == wslips == 0
+    assert M.align_bits(sym >= 0, sent, skip=100)[1] == 0
