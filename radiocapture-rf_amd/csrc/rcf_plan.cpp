@@ -61,24 +61,19 @@ const rcf_t::PlanCache &plan_cache(rcf_t *h)
         // zero-history fix-up --, a discriminator record, an exact-rotator fill, its bank-matrix dirty flag)
         need += c.is_tap ? sizeof(TapLaunch) + 8 : 2 * sizeof(ChanLaunch) + sizeof(DiscLaunch) + sizeof(RotFill) + 12 + 128;
         n_fir += c.is_tap ? 0 : 1;
-        if (c.d_sym) need += sizeof(FmFirLaunch);
-        if (c.d_agc) need += sizeof(AgcLaunch);
-        if (c.d_clk) need += sizeof(ClockLaunch);
-        if (c.audio) need += sizeof(AudioLaunch);
+        // a stage: its launch record, and how far behind a block's first output it reads the channel's own rings (the voice
+        // chain's reach is into its own rings: the widest window only)
+        auto stage = [&](size_t rec_bytes, size_t reach, bool own_rings = false) {
+            need += rec_bytes;
+            if (!own_rings) { size_t &own = pc.reach_x[c.id]; own = std::max(own, reach); }
+            pc.max_reach = std::max(pc.max_reach, reach);
+        };
+        if (c.sym) stage(sizeof(FmFirLaunch), c.sym->reach());
+        if (c.agc) stage(sizeof(AgcLaunch), c.agc->reach());
+        if (c.clock) stage(sizeof(ClockLaunch), c.clock->reach());
+        if (c.audio) stage(sizeof(AudioLaunch), c.audio->reach(), true);
         pc.max_depth = std::max(pc.max_depth, c.depth);
         if (c.src < 0 && (pc.min_d0 == 0 || c.D < pc.min_d0)) pc.min_d0 = c.D;
-        if (c.audio) pc.max_reach = std::max<size_t>(pc.max_reach, (size_t)std::max(std::max(c.audio->n_lpf, c.audio->n_hpf), c.audio->nt_rs));
-        if (c.d_sym) { size_t &own = pc.reach_x[c.id]; own = std::max<size_t>(own, std::max<size_t>(1, (size_t)c.sym_ntaps)); }
-        if (c.d_agc) {                                // the AGC's window reaches N - 1 samples behind the block's first output
-            size_t &own = pc.reach_x[c.id];
-            own = std::max<size_t>(own, std::max<size_t>(1, (size_t)c.agc_n - 1));
-            pc.max_reach = std::max(pc.max_reach, own);
-        }
-        if (c.d_clk) {                                // a symbol's window starts up to 7 samples behind the block's first output
-            size_t &own = pc.reach_x[c.id];
-            own = std::max<size_t>(own, (size_t)kClockTaps - 1);
-            pc.max_reach = std::max(pc.max_reach, own);
-        }
         if (c.src >= RCF_SRC_PFB_BIN0) {              // (the bank's ring: one entry for all of its consumers, set after the loop)
             pfb_reach = std::max<size_t>(pfb_reach, (size_t)(c.T - 1 + c.D));
         } else if (c.src >= 0) {
@@ -86,7 +81,6 @@ const rcf_t::PlanCache &plan_cache(rcf_t *h)
             r = std::max<size_t>(r, (size_t)(c.T - 1 + c.D));
             pc.max_reach = std::max(pc.max_reach, r);
         }
-        if (c.d_sym) pc.max_reach = std::max<size_t>(pc.max_reach, (size_t)c.sym_ntaps);
     }
     if (pfb_reach) {
         size_t &r = pc.reach_x[RCF_SRC_PFB_BIN0];
@@ -231,13 +225,6 @@ int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c, int D)
     auto &rot_fills = bp.rot_fills;
     auto &tap_list = bp.tap_list;
     auto &tap_bins = bp.tap_bins;
-    auto &symf = bp.symf;
-    int &symf_max_n = bp.symf_max_n;
-    auto &agcf = bp.agcf;
-    auto &audf = bp.audf;
-    int &audf_max_n = bp.audf_max_n;
-    double &audf_ratio = bp.audf_ratio;
-    int &audf_num = bp.audf_num, &audf_den = bp.audf_den;
     auto reach = [&](int id) { return bp.reach(id); };
 
     SrcRange sr{};
@@ -319,46 +306,45 @@ int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c, int D)
         discs.push_back(dl);
         max_n = std::max(max_n, (int)cnt);
     }
-    if (c->d_sym) {
+    // a stage's share of the block: the new outputs from the stage's start on -> (n_lo, n_k); n_k <= 0: nothing yet
+    auto since = [&dl](int64_t from, int64_t *n_lo) { *n_lo = std::max(dl.n_lo, from); return (int32_t)(dl.n_lo + dl.n_k - *n_lo); };
+    if (const Chan::Sym *sy = c->sym.get()) {
         FmFirLaunch fl{};
         fl.fm_ring = c->d_fm;
-        fl.sym_ring = c->d_sym;
-        fl.taps = c->d_symtaps;
-        fl.gain = c->sym_gain;
-        fl.ntaps = c->sym_ntaps;
-        fl.n_lo = std::max(dl.n_lo, c->sym_from);
-        fl.n_first = c->sym_from;
-        fl.n_k = (int32_t)(dl.n_lo + dl.n_k - fl.n_lo);
-        if (fl.n_k > 0) symf.push_back(fl);
-        symf_max_n = std::max(symf_max_n, (int)cnt);
+        fl.sym_ring = sy->d_ring;
+        fl.taps = sy->d_taps;
+        fl.gain = sy->gain;
+        fl.ntaps = sy->ntaps;
+        fl.n_first = sy->from;
+        fl.n_k = since(sy->from, &fl.n_lo);
+        if (fl.n_k > 0) bp.symf.push_back(fl);
+        bp.symf_max_n = std::max(bp.symf_max_n, (int)cnt);
     }
-    if (c->d_agc) {
+    if (const Chan::Agc *ag = c->agc.get()) {
         AgcLaunch al{};
         al.iq_ring = c->d_iq;
-        al.agc_ring = c->d_agc;
-        al.reference = c->agc_ref;
-        al.nsamples = c->agc_n;
-        al.n_lo = std::max(dl.n_lo, c->agc_from);
-        al.n_first = c->agc_from;
-        al.n_k = (int32_t)(dl.n_lo + dl.n_k - al.n_lo);
+        al.agc_ring = ag->d_ring;
+        al.reference = ag->ref;
+        al.nsamples = ag->n;
+        al.n_first = ag->from;
+        al.n_k = since(ag->from, &al.n_lo);
         if (al.n_k > 0) {
-            agcf.push_back(al);
+            bp.agcf.push_back(al);
             bp.agcf_max_n = std::max(bp.agcf_max_n, (int)al.n_k);
-            bp.agcf_max_ns = std::max(bp.agcf_max_ns, c->agc_n);
+            bp.agcf_max_ns = std::max(bp.agcf_max_ns, ag->n);
         }
     }
-    if (c->d_clk) {
+    if (const Chan::Clock *ck = c->clock.get()) {
         ClockLaunch cl{};
         cl.fm_ring = c->d_fm;
-        cl.sym_ring = c->d_clk;
-        cl.st = reinterpret_cast<ClockState *>(c->d_clk + h->out_cap);
-        cl.taps = c->d_clk_taps;
-        cl.n_lo = std::max(dl.n_lo, c->clk_from);
-        cl.n_first = c->clk_from;
-        cl.n_k = (int32_t)(dl.n_lo + dl.n_k - cl.n_lo);
-        cl.adv0 = c->clk.adv0;
-        cl.gain = c->clk.gain; cl.mu0 = c->clk.mu0; cl.omega_mid = c->clk.omega_mid; cl.omega_lim = c->clk.omega_lim;
-        cl.gain_omega = c->clk.gain_omega; cl.gain_mu = c->clk.gain_mu;
+        cl.sym_ring = ck->d_ring;
+        cl.st = ck->d_state;
+        cl.taps = ck->d_bank;
+        cl.n_first = ck->from;
+        cl.n_k = since(ck->from, &cl.n_lo);
+        cl.adv0 = ck->adv0;
+        cl.gain = ck->gain; cl.mu0 = ck->mu0; cl.omega_mid = ck->omega_mid; cl.omega_lim = ck->omega_lim;
+        cl.gain_omega = ck->gain_omega; cl.gain_mu = ck->gain_mu;
         if (cl.n_k > 0) {
             bp.clkf.push_back(cl);
             bp.clkf_max_n = std::max(bp.clkf_max_n, (int)cl.n_k);
@@ -377,22 +363,20 @@ int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c, int D)
         al.lpf = au.d_taps;
         al.hpf = au.d_taps + au.n_lpf;
         al.rs = au.d_taps + au.n_lpf + au.n_hpf;
-        al.n_lo = std::max(dl.n_lo, au.from);
-        al.n_k = (int32_t)(dl.n_lo + dl.n_k - al.n_lo);
+        al.n_k = since(au.from, &al.n_lo);
         al.n_lpf = au.n_lpf; al.n_hpf = au.n_hpf; al.nt_rs = au.nt_rs;
         al.interp = au.interp; al.decim = au.decim;
         al.gain = au.gain;
         al.thr = au.thr; al.alpha = au.alpha; al.b0 = au.b0; al.b1 = au.b1; al.fb1 = au.fb1;
         if (al.n_k > 0) {
-            const size_t reach = (size_t)std::max(std::max(au.n_lpf, au.n_hpf), au.nt_rs);
-            if ((size_t)al.n_k + reach > h->out_cap) {
+            if ((size_t)al.n_k + au.reach() > h->out_cap) {
                 set_error("block yields %d channel samples: audio rings of %zu too small", al.n_k, h->out_cap);
                 return RCF_ECAP;
             }
-            audf.push_back(al);
-            audf_max_n = std::max(audf_max_n, (int)al.n_k);
-            if ((double)au.interp / au.decim > audf_ratio) {
-                audf_ratio = (double)au.interp / au.decim; audf_num = au.interp; audf_den = au.decim;
+            bp.audf.push_back(al);
+            bp.audf_max_n = std::max(bp.audf_max_n, (int)al.n_k);
+            if ((double)au.interp / au.decim > bp.audf_ratio) {
+                bp.audf_ratio = (double)au.interp / au.decim; bp.audf_num = au.interp; bp.audf_den = au.decim;
             }
         }
     }
@@ -691,8 +675,7 @@ int check_block_capacity(rcf_t *h, const BlockPlan &bp)
                 const int64_t n_lo = k_lo - c.k_abs0;
                 const int64_t a_lo = std::max<int64_t>(n_lo, au.from);
                 const int64_t a_n = n_lo + cnt - a_lo;
-                const size_t reach = (size_t)std::max(std::max(au.n_lpf, au.n_hpf), au.nt_rs);
-                if (a_n > 0 && (size_t)a_n + reach > h->out_cap) {
+                if (a_n > 0 && (size_t)a_n + au.reach() > h->out_cap) {
                     set_error("block yields %lld channel samples: audio rings of %zu too small", (long long)a_n, h->out_cap);
                     return RCF_ECAP;
                 }

@@ -446,7 +446,8 @@ int rcf_pump_start(rcf_group_t *g, const rcf_pump_config_t *cfg, rcf_pump_t **ou
             }
             auto f = h->chans.find(p->rd_chan[(size_t)e]);
             if (f == h->chans.end()) continue;
-            (cfg->what == RCF_READ_IQ ? f->second->rd_iq : f->second->rd_fm) = f->second->produced;
+            RingStream rs;
+            if (chan_stream(h, f->second.get(), cfg->what, &rs) == RCF_OK) *rs.cursor = rs.end;
         }
     }
     p->running.store(true);

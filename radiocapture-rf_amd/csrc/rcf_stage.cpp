@@ -1,0 +1,201 @@
+// rcf_stage.cpp -- the optional stages behind a channel's rings (the records of Chan, rcf_state.h): the P25 symbol filter,
+// the feed-forward AGC, the SmartNet / EDACS symbol clock and the analog voice chain.  Attach, off, and what they produced.
+// An attach function allocates into Fresh<> holders and builds the new record completely; only then is it swapped into
+// the channel and the old one released.  A HIP call that fails before that leaves the channel as it was.
+#include "rcf_plan.h"
+
+namespace rcfx {
+
+void Chan::Sym::release(rcf_t *h) { bury(h, d_ring); bury(h, d_taps); d_ring = d_taps = nullptr; }
+void Chan::Agc::release(rcf_t *h) { bury(h, d_ring); d_ring = nullptr; }
+void Chan::Clock::release(rcf_t *h) { bury(h, d_ring); d_ring = nullptr; d_state = nullptr; d_bank = nullptr; }   // one allocation
+void Chan::Audio::release(rcf_t *h) { bury(h, d_state); bury(h, d_rings); bury(h, d_taps); d_state = nullptr; d_rings = d_taps = nullptr; }
+
+}  // namespace rcfx
+
+using namespace rcfx;
+
+extern "C" {
+
+int rcf_chan_fm_filter(rcf_t *h, int chan_id, float gain, const float *taps, int ntaps)
+{
+    if (!h || !taps || ntaps < 1 || ntaps > 4096) { set_error("bad fm filter arguments"); return RCF_EINVAL; }
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if ((size_t)ntaps * 2 > h->out_cap) { set_error("ring too small for %d taps", ntaps); return RCF_ECAP; }
+    Fresh<float> d_taps, d_ring;
+    RCF_HIP(d_taps.alloc((size_t)ntaps));
+    RCF_HIP(hipMemcpy(d_taps.p, taps, sizeof(float) * (size_t)ntaps, hipMemcpyHostToDevice));
+    if (!c->sym) {
+        RCF_HIP(d_ring.alloc(h->out_cap));
+        RCF_HIP(hipMemsetAsync(d_ring.p, 0, sizeof(float) * h->out_cap, h->stream));
+        c->sym.reset(new Chan::Sym);
+        c->sym->d_ring = d_ring.take();
+        c->sym->from = c->sym->rd = c->produced;     // a new GR block starts with zero history
+    }
+    bury(h, c->sym->d_taps);                         // a second call: new taps and gain from the next block on, nothing else
+    c->sym->d_taps = d_taps.take();
+    c->sym->ntaps = ntaps;
+    c->sym->gain = gain;
+    ++h->chans_epoch;
+    return RCF_OK;
+}
+
+int rcf_chan_agc(rcf_t *h, int chan_id, int nsamples, float reference)
+{
+    if (!h || nsamples < 0 || nsamples > 4096 || !std::isfinite(reference)) { set_error("bad AGC arguments"); return RCF_EINVAL; }
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (nsamples == 0) {                // off
+        if (c->agc) { drop_stage(h, c->agc); ++h->chans_epoch; }
+        return RCF_OK;
+    }
+    if (c->fm_only) { set_error("channel %d exposes its discriminator only: the AGC reads IQ", chan_id); return RCF_ESTATE; }
+    if ((size_t)nsamples * 2 > h->out_cap) { set_error("ring of %zu too small for a %d-sample AGC window", h->out_cap, nsamples); return RCF_ECAP; }
+    if (!c->agc) {
+        Fresh<float2> d_ring;
+        RCF_HIP(d_ring.alloc(h->out_cap));
+        RCF_HIP(hipMemsetAsync(d_ring.p, 0, sizeof(float2) * h->out_cap, h->stream));
+        c->agc.reset(new Chan::Agc);
+        c->agc->d_ring = d_ring.take();
+    }
+    c->agc->n = nsamples;
+    c->agc->ref = reference;
+    c->agc->from = c->agc->rd = c->produced;         // a new GR block starts with zero history
+    ++h->chans_epoch;
+    return RCF_OK;
+}
+
+// ---- clock_recovery_mm_ff behind the discriminator (clock.hip)
+int rcf_chan_clock_mm(rcf_t *h, int chan_id, const rcf_clock_mm_params_t *p)
+{
+    if (!h) return RCF_EINVAL;
+    if (p) {
+        if (!std::isfinite(p->gain) || !std::isfinite(p->omega) || !std::isfinite(p->gain_omega) || !std::isfinite(p->mu) ||
+            !std::isfinite(p->gain_mu) || !std::isfinite(p->omega_relative_limit)) {
+            set_error("clock recovery: non-finite parameter");
+            return RCF_EINVAL;
+        }
+        // GNU Radio's documented domain (omega stays >= 2 samples per symbol at its lower limit); mu selects a row of the bank
+        if ((double)p->omega * (1.0 - (double)p->omega_relative_limit) < 2.0 || p->omega > 4096.f || p->mu < 0.f || p->mu > 1.f) {
+            set_error("clock recovery: omega %g (relative limit %g) outside 2 / (1 - limit) .. 4096, or mu %g outside 0 .. 1",
+                      p->omega, p->omega_relative_limit, p->mu);
+            return RCF_EINVAL;
+        }
+    }
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!p) {                           // off
+        if (c->clock) { drop_stage(h, c->clock); ++h->chans_epoch; }
+        return RCF_OK;
+    }
+    if ((size_t)kClockTaps * 2 > h->out_cap) { set_error("ring of %zu too small for the clock's %d-sample window", h->out_cap, kClockTaps); return RCF_ECAP; }
+    constexpr size_t kBank = (size_t)(kClockSteps + 1) * kClockTaps;
+    if (!p->interp_taps && !h->d_mmse) {
+        const std::vector<float> t = design_mmse_interpolator(kClockTaps, kClockSteps, 0.25);
+        Fresh<float> d;
+        RCF_HIP(d.alloc(kBank));
+        if (!hip_ok(hipMemcpy(d.p, t.data(), sizeof(float) * kBank, hipMemcpyHostToDevice), "hipMemcpy(interpolator bank)")) return RCF_EHIP;
+        h->d_mmse = d.take();
+    }
+    // every call is a new GR block: a fresh ring and state (symbol 0 is the first of this call), zero history
+    const size_t state_at = h->out_cap, bank_at = h->out_cap + 64;       // in floats; the state record has 256 bytes to itself
+    Fresh<float> fresh;
+    RCF_HIP(fresh.alloc(bank_at + (p->interp_taps ? kBank : 0)));
+    std::unique_ptr<Chan::Clock> k(new Chan::Clock);
+    k->gain = p->gain; k->mu0 = p->mu; k->omega_mid = p->omega;
+    k->omega_lim = k->omega_mid * p->omega_relative_limit;               // (one float product)
+    k->gain_omega = p->gain_omega; k->gain_mu = p->gain_mu;
+    k->adv0 = (int)std::ceil(k->omega_mid);
+    ClockState st0{};
+    st0.p = c->produced - (kClockTaps - 1);                              // the first window: seven zeros and u[first]
+    st0.mu = k->mu0; st0.omega = k->omega_mid; st0.last = 0.f;
+    if (!hip_ok(hipMemcpy(fresh.p + state_at, &st0, sizeof(st0), hipMemcpyHostToDevice), "hipMemcpy(clock state)") ||
+        (p->interp_taps && !hip_ok(hipMemcpy(fresh.p + bank_at, p->interp_taps, sizeof(float) * kBank, hipMemcpyHostToDevice), "hipMemcpy(interpolator bank)")))
+        return RCF_EHIP;
+    k->d_ring = fresh.take();
+    k->d_state = reinterpret_cast<ClockState *>(k->d_ring + state_at);
+    k->d_bank = p->interp_taps ? k->d_ring + bank_at : h->d_mmse;
+    k->from = c->produced;
+    drop_stage(h, c->clock);
+    c->clock = std::move(k);
+    ++h->chans_epoch;
+    return RCF_OK;
+}
+
+int rcf_chan_audio_open(rcf_t *h, int chan_id, const rcf_audio_params_t *p)
+{
+    if (!h || !p || !p->lpf_taps || !p->hpf_taps || !p->rs_taps || p->n_lpf < 1 || p->n_hpf < 1 || p->n_rs < 1 ||
+        p->interpolation < 1 || p->decimation < 1 || p->deemph_a[0] == 0.0) {
+        set_error("bad audio chain arguments");
+        return RCF_EINVAL;
+    }
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (c->fm_only) { set_error("channel %d exposes its discriminator only: the voice chain reads IQ", chan_id); return RCF_ESTATE; }
+    const int I = p->interpolation;
+    const int n_rs_pad = (p->n_rs + I - 1) / I * I;              // rational_resampler_base: pad to a multiple of I
+    const size_t reach = (size_t)std::max(std::max(p->n_lpf, p->n_hpf), n_rs_pad / I);
+    if (reach * 2 > h->out_cap) { set_error("ring of %zu too small for %zu-tap audio filters", h->out_cap, reach); return RCF_ECAP; }
+    std::unique_ptr<Chan::Audio> au(new Chan::Audio);
+    au->n_lpf = p->n_lpf; au->n_hpf = p->n_hpf; au->nt_rs = n_rs_pad / I;
+    au->interp = I; au->decim = p->decimation;
+    au->gain = p->quad_gain;
+    au->thr = std::pow(10.0, p->squelch_db / 10);                // pwr_squelch_cc::set_threshold
+    au->alpha = p->squelch_alpha;
+    // iir_filter(fftaps, fbtaps, oldstyle = false): feedback taps are negated, a[0] must be 1
+    au->b0 = p->deemph_b[0]; au->b1 = p->deemph_b[1]; au->fb1 = -p->deemph_a[1];
+    std::vector<float> taps((size_t)p->n_lpf + p->n_hpf + n_rs_pad, 0.0f);
+    std::memcpy(taps.data(), p->lpf_taps, sizeof(float) * (size_t)p->n_lpf);
+    std::memcpy(taps.data() + p->n_lpf, p->hpf_taps, sizeof(float) * (size_t)p->n_hpf);
+    std::memcpy(taps.data() + p->n_lpf + p->n_hpf, p->rs_taps, sizeof(float) * (size_t)p->n_rs);
+    Fresh<float> d_taps, d_rings;
+    Fresh<AudioState> d_state;
+    RCF_HIP(d_taps.alloc(taps.size()));
+    RCF_HIP(hipMemcpy(d_taps.p, taps.data(), sizeof(float) * taps.size(), hipMemcpyHostToDevice));
+    RCF_HIP(d_rings.alloc(6 * h->out_cap));
+    RCF_HIP(hipMemsetAsync(d_rings.p, 0, sizeof(float) * 6 * h->out_cap, h->stream));
+    AudioState st0{};
+    st0.muted = 1;                                               // squelch_base_cc starts in ST_MUTED
+    RCF_HIP(d_state.alloc(1));
+    RCF_HIP(hipMemcpy(d_state.p, &st0, sizeof(st0), hipMemcpyHostToDevice));
+    au->d_taps = d_taps.take(); au->d_rings = d_rings.take(); au->d_state = d_state.take();
+    au->from = c->produced;                                      // a new flowgraph: zero state from here on
+    drop_stage(h, c->audio);
+    c->audio = std::move(au);
+    ++h->chans_epoch;
+    return RCF_OK;
+}
+
+int rcf_chan_audio_close(rcf_t *h, int chan_id)
+{
+    if (!h) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    drop_stage(h, c->audio);
+    ++h->chans_epoch;
+    return RCF_OK;
+}
+
+// what a stage has produced so far: the end of its stream and the counter beside it (chan_stream)
+static int stage_produced(rcf_t *h, int chan_id, int kind, int64_t *n, int64_t *beside)
+{
+    if (!h || !n) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    RingStream s;
+    const int rc = chan_stream(h, c, kind, &s, beside);
+    if (rc == RCF_OK) *n = s.end;
+    return rc;
+}
+
+int rcf_chan_clock_produced(rcf_t *h, int chan_id, int64_t *n_symbols, int64_t *n_slips) { return stage_produced(h, chan_id, kReadClock, n_symbols, n_slips); }
+int rcf_chan_audio_produced(rcf_t *h, int chan_id, int64_t *n_audio, int64_t *n_ungated) { return stage_produced(h, chan_id, kReadAudio, n_audio, n_ungated); }
+
+}  // extern "C"

@@ -1,8 +1,9 @@
 // rcf_state.h -- host-side state of librcf.so (the kernels never see it): the front-end handle with its channels,
 // filterbank, scanner, slab pools and launch arenas, and the helpers the host modules share.
 //   rcf_handle.cpp   open / close / sync, pools, wideband ingest        rcf_plan.cpp    the per-block schedule (host)
-//   rcf_launch.cpp   the block's launches in dependency order           rcf_chan.cpp    channels, voice chain, and the one read
-//                                                                                       path of every host read (host_read)
+//   rcf_launch.cpp   the block's launches in dependency order           rcf_chan.cpp    channels: lifecycle, taps, queries
+//   rcf_stage.cpp    a channel's optional stages: symbol filter, AGC,   rcf_read.cpp    the stream table of a channel and the
+//                    symbol clock, voice chain (attach / off / counts)                  one read path of every host read
 //   rcf_bank.cpp     filterbank + scanner ABI                           rcf_timing.cpp  HIP-event timing
 //   rcf_comm.cpp     RCCL peak-list exchange                            rcf_group.cpp   grouped launches over front-ends
 #pragma once
@@ -27,6 +28,18 @@ static const double kTwoPi = 6.283185307179586476925286766559;
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return a >= 0 ? (a + b - 1) / b : -((-a) / b); }
 static inline int64_t floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+
+// A fresh device allocation that is freed again unless somebody takes it: what an attach function allocates is its own
+// until the finished record is swapped into the channel, so a call that fails half way leaks nothing and changes nothing.
+template <class T> struct Fresh {
+    T *p = nullptr;
+    Fresh() = default;
+    Fresh(const Fresh &) = delete;
+    Fresh &operator=(const Fresh &) = delete;
+    ~Fresh() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t n) { return hipMalloc(&p, sizeof(T) * n); }
+    T *take() { T *r = p; p = nullptr; return r; }
+};
 
 static size_t pow2_at_least(size_t v)
 {
@@ -54,10 +67,6 @@ struct Chan {
     int64_t produced = 0;         // relative output count
     // exact rotator (rcf_set_rotator): phase ring + {phase, counter} state, one pool slice
     float2 *d_rot = nullptr;
-    float *d_sym = nullptr;       // optional real FIR over gain * fm (P25 symbol filter), below
-    float2 *d_agc = nullptr;      // optional feedforward AGC over the IQ stream (P25 CQPSK front half), below
-    float *d_clk = nullptr;       // optional symbol clock over gain * fm (SmartNet / EDACS), below: soft-symbol ring of out_cap
-                                  // floats | ClockState | the caller's interpolator bank, if it passed one
     // rotator model
     double extra_dangle = 0, extra_dlogmag = 0;   // added to the increment's own angle / log magnitude (filterbank taps)
     double dangle = 0, dlogmag = 0;
@@ -69,34 +78,60 @@ struct Chan {
     uint64_t blk_serial = 0;
     int64_t blk_before = 0, blk_after = 0;
     int64_t rd_iq = 0, rd_fm = 0;
-    // analog voice chain (rcf_chan_audio_open)
-    struct Audio {
+    // ---- the optional stages behind the rings, one record each; null = the channel has no such stage.  What a second
+    // call of the attaching function means:
+    //   stage                                  ring on re-call       from         read cursor
+    //   symbol filter (rcf_chan_fm_filter)     kept                  kept         kept          (new taps and gain only)
+    //   AGC           (rcf_chan_agc)           kept                  `produced`   `produced`
+    //   symbol clock  (rcf_chan_clock_mm)      new ring and state    `produced`   0
+    //   voice chain   (rcf_chan_audio_open)    new                   `produced`   0
+    // `from`: the first relative channel output the stage is defined for (a new GR block: zero history before it); `rd`:
+    // items handed to the stage's reader; reach(): how far behind a block's first output the stage reads the channel's
+    // rings; release(): the device buffers go once the stream has passed them (rcf_stage.cpp)
+    struct Sym {                        // real FIR over gain * fm (the P25 symbol filter)
+        float *d_ring = nullptr, *d_taps = nullptr;
+        int ntaps = 0;
+        float gain = 1.f;
+        int64_t from = 0, rd = 0;
+        size_t reach() const { return (size_t)std::max(1, ntaps); }
+        void release(rcf_t *h);
+    };
+    struct Agc {                        // feedforward_agc_cc(nsamples = n, reference = ref) over the IQ stream (P25 CQPSK front half)
+        float2 *d_ring = nullptr;
+        int n = 0;
+        float ref = 1.f;
+        int64_t from = 0, rd = 0;
+        size_t reach() const { return (size_t)std::max(1, n - 1); }     // the window reaches n - 1 samples behind
+        void release(rcf_t *h);
+    };
+    struct Clock {                      // clock_recovery_mm_ff over gain * fm (SmartNet / EDACS)
+        float *d_ring = nullptr;        // one allocation: soft-symbol ring of out_cap floats | ClockState | the caller's bank, if any
+        ClockState *d_state = nullptr;
+        const float *d_bank = nullptr;  // the interpolator bank the stage reads: the caller's (inside d_ring's allocation) or rcf::d_mmse
+        // the constants as the kernel takes them, rounded to float once
+        float gain = 1.f, mu0 = 0.f, omega_mid = 0.f, omega_lim = 0.f, gain_omega = 0.f, gain_mu = 0.f;
+        int adv0 = 1;
+        int64_t from = 0, rd = 0;
+        size_t reach() const { return (size_t)kClockTaps - 1; }         // a symbol's window starts up to 7 samples behind
+        void release(rcf_t *h);
+    };
+    struct Audio {                      // the analog voice chain
         AudioState *d_state = nullptr;
         float *d_rings = nullptr;       // a | l | h | o | c (cf32), out_cap samples each
         float *d_taps = nullptr;        // lpf | hpf | rs (padded)
         int n_lpf = 0, n_hpf = 0, nt_rs = 0, interp = 1, decim = 1;
         float gain = 1.f;
         double thr = 0, alpha = 0, b0 = 1, b1 = 0, fb1 = 0;
-        int64_t from = 0;               // first relative channel output the chain consumes
-        int64_t rd = 0;                 // audio samples handed to the reader
+        int64_t from = 0, rd = 0;       // rd: audio samples handed to the reader
+        size_t reach() const { return (size_t)std::max(std::max(n_lpf, n_hpf), nt_rs); }   // in the chain's own rings
+        void release(rcf_t *h);
     };
+    std::unique_ptr<Sym> sym;
+    std::unique_ptr<Agc> agc;
+    std::unique_ptr<Clock> clock;
     std::unique_ptr<Audio> audio;
     // ---- the rest
     float incr[2] = {1.f, 0.f};   // exact rotator: what GNU Radio iterates
-    float *d_symtaps = nullptr;
-    int sym_ntaps = 0;
-    float sym_gain = 1.f;
-    int64_t sym_from = 0;         // first relative output index the filter is defined for
-    int64_t rd_sym = 0;
-    int agc_n = 0;                // feedforward_agc_cc(nsamples = agc_n, reference = agc_ref) (rcf_chan_agc)
-    float agc_ref = 1.f;
-    int64_t agc_from = 0;         // first relative output index the AGC is defined for (zero history before it)
-    int64_t rd_agc = 0;
-    // clock_recovery_mm_ff (rcf_chan_clock_mm): the constants as the kernel takes them, rounded to float once
-    struct ClockMm { float gain = 1.f, mu0 = 0.f, omega_mid = 0.f, omega_lim = 0.f, gain_omega = 0.f, gain_mu = 0.f; int adv0 = 1; } clk;
-    const float *d_clk_taps = nullptr;   // the bank the stage reads: the handle's default (rcf::d_mmse) or the caller's, inside d_clk
-    int64_t clk_from = 0;         // first relative output index the stage reads (zero history before it)
-    int64_t rd_clk = 0;           // soft symbols handed to the reader
     uint64_t many_stamp = 0;      // the host_read call that last listed this channel (batched reads: one reader per stream)
     double src_rate = 0, offset_hz = 0;
     uint64_t taps_version = 0;    // bumped whenever d_ctaps changes (bank-matrix cache key)
@@ -334,6 +369,11 @@ struct TimedAttached {
 };
 
 // ---------------------------------------------------------------- rcf_chan.cpp
+#define FIND_CHAN(h, id, c)                                                 \
+    auto it_ = (h)->chans.find(id);                                         \
+    if (it_ == (h)->chans.end()) { set_error("no such channel %d", id); return RCF_ENOCHAN; } \
+    Chan *c = it_->second.get()
+
 // source description for one commit
 struct SrcRange {
     StreamView view;
@@ -345,8 +385,11 @@ double pfb_tap_gr_dangle(const rcf_t *h, int bin);
 int pfb_fm_upload_increments(rcf_t *h);
 // tap: a frame-major bank's tap (rcf_pfb_tap_open), copied by the bank's kernel -- the one bin consumer mode 2 keeps
 int new_channel(rcf_t *h, int src, int D, const float *taps, int T, double offset_hz, int *chan_id, bool tap = false);
-void free_channel(rcf_t *h, Chan *c);
+void free_channel(rcf_t *h, Chan *c);                 // c's device buffers go once the stream has passed them; the caller erases c
+// a stage goes (switched off, replaced, or with its channel): release() its buffers, then the record
+template <class R> void drop_stage(rcf_t *h, std::unique_ptr<R> &r) { if (r) { r->release(h); r.reset(); } }
 
+// ---------------------------------------------------------------- rcf_read.cpp
 // ---- the one read path.  A stream is a device ring of h->out_cap items (a power of two) of item_w 4-byte words:
 // item i at word (i & ring_mask) * stride_w of ring when stride_w > 1 (one bin of a frame-major ring of floats), else at
 // (i & ring_mask) * item_w.  The ring holds the out_cap items before `newest`; a reader at *cursor may take up to `end`.
@@ -357,10 +400,14 @@ struct RingStream {
     int64_t end = 0, newest = 0;
     int64_t *cursor = nullptr;
 };
-constexpr int kReadSym = 3;       // the symbol filter's stream: single reads only (the batched ABIs take RCF_READ_IQ / FM / AGC)
-// channel c's stream `kind` (RCF_READ_IQ / FM / AGC, kReadSym), or RCF_ESTATE with the refusal's message: IQ of a
-// discriminator-only tap, SYM without rcf_chan_fm_filter, AGC without rcf_chan_agc
-int chan_stream(rcf_t *h, Chan *c, int kind, RingStream *s);
+// the stages' streams: single reads only (the batched ABIs and the pump take RCF_READ_IQ / FM / AGC)
+constexpr int kReadSym = 3, kReadClock = 4, kReadAudio = 5;
+// The stream table of a channel: c's stream `kind` (RCF_READ_IQ / FM / AGC, kReadSym / Clock / Audio), or RCF_ESTATE with
+// the refusal's message (IQ of a discriminator-only tap, a stage the channel does not carry).  The first four end at
+// c->produced.  The clock's and the voice chain's end at their stage's device counter: one asynchronous copy and one
+// synchronisation of the stream (RCF_EHIP); *aux, if given, takes the counter beside it (the clock's slips, the samples
+// that passed the voice chain's squelch).
+int chan_stream(rcf_t *h, Chan *c, int kind, RingStream *s, int64_t *aux = nullptr);
 
 // A reader that has fallen more than a ring behind lost what the ring overwrote: its cursor is raised to the oldest item
 // the ring still holds.  Returns how many items [*cursor, end) it may take, at most max.
