@@ -159,7 +159,8 @@ int rcf_device(rcf_t *h);
 #define RCF_T_AUDIO        8   /* analog voice chain (squelch/demod/de-emphasis walk, FIRs, resampler) */
 #define RCF_T_TAPS         9   /* filterbank taps: tap matrix -> channel rings, rotator + discriminator fused */
 #define RCF_T_CLOCK        10  /* symbol clocks (rcf_chan_clock_mm): one launch per block for every clocked channel */
-#define RCF_T_COUNT        11
+#define RCF_T_COSTAS       11  /* Gardner / Costas loops (rcf_chan_costas): one launch per block for every channel with the stage */
+#define RCF_T_COUNT        12
 /* on = 0: off; 1: every class; otherwise a mask with bit (class + 1) set for each class to time -- every timed
  * launch costs two event records on the stream (~10 us of gap), so a throughput run times only what it reports.  The
  * filterbank's launch carries its two events attached to the dispatch (one barrier packet less inside the measured
@@ -273,11 +274,12 @@ int64_t rcf_chan_read_sym(rcf_t *h, int chan_id, float *out, size_t max_samples)
  * Bit-identical to GNU Radio's naive loop restated in float (every step is exactly rounded).  nsamples = 0 switches it off.
  * Starts, with zero history, at the channel's next output (again on every call); applies from the next block on, on every
  * channel kind (direct, chained, stage-2, filterbank tap); a retune keeps it, closing the channel releases it.  The
- * sequential loops behind it (op25 gardner_costas_cc, diff_phasor_cc) stay with the consumer.
+ * sequential loops behind it (op25 gardner_costas_cc, diff_phasor_cc) are rcf_chan_costas, below.
  * RCF_EINVAL: nsamples outside 0 .. 4096 or a non-finite reference; RCF_ENOCHAN: no such channel; RCF_ESTATE: a
  * discriminator-only tap (rcf_chan_set_fm_only: no IQ; switching that on is refused while an AGC reads the channel);
  * RCF_ECAP: out_capacity < 2 nsamples -- and at a block that yields more outputs than the ring holds beside the N - 1
- * samples of look-back (nothing is queued then). */
+ * samples of look-back (nothing is queued then).  nsamples = 0 on a channel that carries rcf_chan_costas: RCF_ESTATE (that
+ * stage reads the AGC ring and must be switched off first; calling again with a window is allowed). */
 int rcf_chan_agc(rcf_t *h, int chan_id, int nsamples, float reference);
 /* unread AGC outputs (cf32), oldest first, at the channel's rate; RCF_ESTATE without an AGC */
 int64_t rcf_chan_read_agc(rcf_t *h, int chan_id, float *out_interleaved, size_t max_samples);
@@ -332,6 +334,71 @@ int64_t rcf_chan_read_clock(rcf_t *h, int chan_id, float *out, size_t max_symbol
 /* device pointer of the soft-symbol ring and its capacity (zero-copy, like rcf_chan_rings): symbol k lives at index
  * k & (capacity-1); rcf_chan_clock_produced gives the count */
 int rcf_chan_clock_ring(rcf_t *h, int chan_id, void **sym_ring, size_t *capacity);
+/* The back half of the P25 CQPSK (LSM / simulcast) demodulators behind the AGC (p25_control_demod.py:150-183,
+ * logging_receiver.py:282-332):
+ *     repeater.gardner_costas_cc(omega, gain_mu, gain_omega, alpha, beta, fmax, -fmax) -> digital.diff_phasor_cc
+ *         -> blocks.complex_to_arg -> multiply_const_ff(4 / pi)           [-> op25.fsk4_slicer_fb([-2, 0, 2, 4]) at the consumer]
+ * as a per-channel stage on the GPU that reads the channel's AGC ring (rcf_chan_agc) and writes float32 soft symbols
+ * (+-1, +-3 on a locked signal).  op25's source is not part of the reference tree, so this comment DEFINES the stage: it
+ * restates the published gardner_costas_cc algorithm and is "parity unpinned"  against any particular op25
+ * build -- unpinned against op25.
+ * State per channel, all float: mu, omega, phase, freq, the complex `last`, the last 32 derotated samples, and 64-bit
+ * counts of symbols and slips.  Constants: th = (float)(pi / 4), r = (float)0.70710678118654752, 2 pi as float,
+ * omega_mid = omega, L = max(2 ceil(omega), floor(omega / 2) + 9) (12 at 25000 / 4800 as in op25, 11 at 25000 / 6000; the lower
+ * bound keeps both interpolator windows inside samples that exist).  Initially mu = omega = omega_mid, phase = freq = 0,
+ * last = 0, all 32 samples 0.  T is the interpolator bank of rcf_chan_clock_mm, 129 rows of 8 floats.  Every product and
+ * sum is rounded to float on its own (no fused multiply-add); a complex product (a + jb)(c + jd) is (ac - bd) + j(ad + bc),
+ * four products and two sums; |v| = sqrtf(re re + im im), correctly rounded; cosf, sinf and atan2f are the precise
+ * functions; clamp(v, +-l) = v < -l ? -l : v > l ? l : v (a NaN passes).  For every AGC output x[m] from the stage's
+ * start on:
+ *   1. phase = phase + freq;  if phase > 2 pi: phase -= 2 pi;  if phase < -2 pi: phase += 2 pi
+ *   2. a = phase + th;  push (cosf(a) + j sinf(a)) * x[m]        (W[0] oldest .. W[L-1] newest of the last L pushed)
+ *   3. mu = mu - 1;  if mu > 1: next input
+ *   4. half = omega * 0.5f;  hs = (int)floorf(half);  hm = (mu + half) - (float)hs;  if hm > 1: hm -= 1, hs += 1
+ *      hs = min(hs, L - 8)                                        (never taken at P25's parameters: the window stays in W)
+ *      I(v, m) = sum over j = 0 .. 7, in that order, from 0, of  T[clamp((int)rintf(m * 128.0f), 0, 128)][7 - j] * v[j]
+ *                                                                 (real and imaginary part apart)
+ *      mid = I(W[0 .. 7], mu);  y = I(W[hs .. hs + 7], hm)
+ *      e = (last.re - y.re) * mid.re + (last.im - y.im) * mid.im;  a NaN counts as 0;  e = clamp(e, +-1)
+ *      d = y * conj(last) = (y.re last.re + y.im last.im) + j (y.im last.re - y.re last.im);  last = y
+ *      omega = omega + (gain_omega * e) * |y|;  omega = omega_mid + clamp(omega - omega_mid, +-omega_limit)
+ *      mu = (mu + omega) + gain_mu * e
+ *      z = d * (r + j r);  pe = |z.re| > |z.im| ? (z.re > 0 ? -z.im : z.im) : (z.im > 0 ? z.re : -z.re)
+ *      freq = freq + (beta * pe) * |z|;  phase = (phase + freq) + (alpha * pe) * |z|, wrapped once as in 1
+ *      freq = clamp(freq, +-max_freq)
+ *      out[k] = atan2f(d.im, d.re) * (float)(4 / pi)
+ * One guard, counted in n_slips: if after step 4 mu, omega, phase, freq or last is not finite, or mu <= 1, the state goes
+ * back to the initial one (the 32 samples stay).  It does not fire on a signal.  At most one symbol per input; the outputs
+ * depend on the input stream only, never on how it was cut into blocks.  freq is the carrier loop's estimate in radians
+ * per channel sample, of the sign opposite to the carrier's offset: what a drift reporter needs.
+ * p == NULL switches the stage off.  It starts, with zero history, at the channel's next output (again on every call: a
+ * fresh ring and state, symbol 0 is the first of the call); applies from the next block on, on every channel kind that can
+ * carry an AGC; a retune keeps it, closing the channel releases it.  The slicer and the framing stay with the consumer.
+ * RCF_EINVAL: a parameter that is not finite, omega outside 2 .. 16, omega - omega_limit - gain_mu < 2 (so that mu > 1
+ * after every symbol), a negative omega_limit or max_freq, max_freq >= pi; RCF_ENOCHAN: no such channel; RCF_ESTATE: the
+ * channel has no AGC; RCF_ECAP: out_capacity < 64. */
+typedef struct rcf_costas_params {
+    float omega;                /* channel samples per symbol: 25000 / 4800 (phase 1) or 25000 / 6000 (phase 2) */
+    float gain_mu, gain_omega;  /* 0.025, 0.1 gain_mu^2 (p25_control_demod.py:152-153) */
+    float alpha, beta;          /* 0.04, 0.125 alpha^2 */
+    float max_freq;             /* 2 pi 1200 / rate; the reference passes +fmax and -fmax */
+    float omega_limit;          /* 0.005 in op25: omega stays within omega_mid +- omega_limit */
+    int reserved_;
+    const float *interp_taps;   /* 129 x 8, row-major; NULL = rcf_design_mmse_interpolator(8, 128, 0.25) */
+} rcf_costas_params_t;
+int rcf_chan_costas(rcf_t *h, int chan_id, const rcf_costas_params_t *p);
+/* the loop's state as of the last block; syncs the stream, like rcf_chan_clock_produced.  RCF_ESTATE without the stage
+ * (here and in the two calls below) */
+typedef struct rcf_costas_state {
+    int64_t n_symbols, n_slips; /* soft symbols produced since the stage was (last) attached, times the guard fired */
+    float mu, omega, freq, phase;
+} rcf_costas_state_t;
+int rcf_chan_costas_state(rcf_t *h, int chan_id, rcf_costas_state_t *out);
+/* unread soft symbols (float32), oldest first */
+int64_t rcf_chan_read_costas(rcf_t *h, int chan_id, float *out, size_t max_symbols);
+/* device pointer of the soft-symbol ring and its capacity (zero-copy, like rcf_chan_rings): symbol k lives at index
+ * k & (capacity-1); rcf_chan_costas_state gives the count */
+int rcf_chan_costas_ring(rcf_t *h, int chan_id, void **sym_ring, size_t *capacity);
 /* drift probe of p25_control_demod.py:123-127: moving_average_ff(window, 1) * (1/window) of the
  * discriminator output (window = 10000 there) == mean of gain*fm over the last `window` samples; this is
  * the value demod_watcher hands to frontend_connector.report_offset */

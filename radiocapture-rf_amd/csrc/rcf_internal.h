@@ -280,6 +280,29 @@ struct ClockLaunch {
 };
 void launch_clock_mm(const ClockLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
 std::vector<float> design_mmse_interpolator(int ntaps, int nsteps, double bw);
+// Gardner / Costas symbol recovery on a channel's AGC ring (costas.hip; the back half of the P25 CQPSK demodulators,
+// p25_control_demod.py:150-183; definition: include/rcf.h at rcf_chan_costas).
+// per-channel running state, device resident, owned by costas_kernel
+constexpr int kCostasHist = 32;
+struct CostasState {
+    int64_t n_out;           // soft symbols written so far (symbol k at sym_ring[k & ring_mask])
+    int64_t slips;           // times the guard fired
+    float mu, omega, phase, freq;
+    float2 last;
+    float2 hist[kCostasHist];   // the last 32 derotated samples, newest last
+};
+struct CostasLaunch {
+    const float2 *agc_ring;
+    float *sym_ring;
+    CostasState *st;
+    const float *taps;       // the bank, row-major (device)
+    int64_t n_lo;            // first relative AGC output that is new in this launch
+    int32_t n_k;
+    int32_t window;          // L = max(2 ceil(omega), floor(omega / 2) + 9), 10 .. 32
+    float omega_mid, omega_lim, gain_omega, gain_mu, alpha, beta, max_freq;
+    int32_t pad_;
+};
+void launch_costas(const CostasLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
 // mean of gain * fm over the last `window` samples ending at n_end (exclusive), one workgroup
 void launch_fm_level(const float *fm_ring, int64_t n_end, int window, float gain, uint64_t ring_mask, float *d_out,
                      hipStream_t s);

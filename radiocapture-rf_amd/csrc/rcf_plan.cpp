@@ -71,6 +71,7 @@ const rcf_t::PlanCache &plan_cache(rcf_t *h)
         if (c.sym) stage(sizeof(FmFirLaunch), c.sym->reach());
         if (c.agc) stage(sizeof(AgcLaunch), c.agc->reach());
         if (c.clock) stage(sizeof(ClockLaunch), c.clock->reach());
+        if (c.costas) stage(sizeof(CostasLaunch), c.costas->reach());
         if (c.audio) stage(sizeof(AudioLaunch), c.audio->reach(), true);
         pc.max_depth = std::max(pc.max_depth, c.depth);
         if (c.src < 0 && (pc.min_d0 == 0 || c.D < pc.min_d0)) pc.min_d0 = c.D;
@@ -211,7 +212,7 @@ int plan_pfb(rcf_t *h, BlockPlan &bp)
     return RCF_OK;
 }
 
-// one channel's launch records (FIR / tap, discriminator, symbol filter, AGC, symbol clock, voice chain, exact rotator) and the advance of
+// one channel's launch records (FIR / tap, discriminator, symbol filter, AGC, symbol clock, Gardner / Costas loop, voice chain, exact rotator) and the advance of
 // its state.  Returns RCF_OK also when the channel has nothing to do in this block.
 int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c, int D)
 {
@@ -348,6 +349,21 @@ int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c, int D)
         if (cl.n_k > 0) {
             bp.clkf.push_back(cl);
             bp.clkf_max_n = std::max(bp.clkf_max_n, (int)cl.n_k);
+        }
+    }
+    if (const Chan::Costas *gc = c->costas.get()) {
+        CostasLaunch gl{};
+        gl.agc_ring = c->agc->d_ring;                // (attached only behind an AGC, which cannot go before it: rcf_stage.cpp)
+        gl.sym_ring = gc->d_ring;
+        gl.st = gc->d_state;
+        gl.taps = gc->d_bank;
+        gl.n_k = since(std::max(gc->from, c->agc->from), &gl.n_lo);
+        gl.window = gc->window;
+        gl.omega_mid = gc->omega_mid; gl.omega_lim = gc->omega_lim; gl.gain_omega = gc->gain_omega; gl.gain_mu = gc->gain_mu;
+        gl.alpha = gc->alpha; gl.beta = gc->beta; gl.max_freq = gc->max_freq;
+        if (gl.n_k > 0) {
+            bp.gcf.push_back(gl);
+            bp.gcf_max_n = std::max(bp.gcf_max_n, (int)gl.n_k);
         }
     }
     if (c->audio) {
@@ -628,12 +644,13 @@ int plan_tail(rcf_t *h, BlockPlan &bp)
         pl.tap_pitch = (int32_t)mat_pitch;
         pl.n_taps = (int32_t)tap_list.size();
     }
-    // (a group's block: the exact-rotator fills, the symbol filters, the AGCs and the symbol clocks of all members go out as
+    // (a group's block: the exact-rotator fills, the symbol filters, the AGCs, the symbol clocks and the Gardner / Costas loops of all members go out as
     // one launch each)
     if (!bp.defer && !rot_fills.empty() && !ar.put(rot_fills, &d_rot_fills)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
     if (!bp.defer && !symf.empty() && !ar.put(symf, &d_symf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
     if (!bp.defer && !agcf.empty() && !ar.put(agcf, &bp.d_agcf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
     if (!bp.defer && !bp.clkf.empty() && !ar.put(bp.clkf, &bp.d_clkf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
+    if (!bp.defer && !bp.gcf.empty() && !ar.put(bp.gcf, &bp.d_gcf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
     if (!audf.empty() && !ar.put(audf, &d_audf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
     return RCF_OK;
 }

@@ -1,5 +1,6 @@
 // rcf_stage.cpp -- the optional stages behind a channel's rings (the records of Chan, rcf_state.h): the P25 symbol filter,
-// the feed-forward AGC, the SmartNet / EDACS symbol clock and the analog voice chain.  Attach, off, and what they produced.
+// the feed-forward AGC, the SmartNet / EDACS symbol clock, the P25 CQPSK Gardner / Costas loop and the analog voice chain.
+// Attach, off, and what they produced.
 // An attach function allocates into Fresh<> holders and builds the new record completely; only then is it swapped into
 // the channel and the old one released.  A HIP call that fails before that leaves the channel as it was.
 #include "rcf_plan.h"
@@ -9,6 +10,7 @@ namespace rcfx {
 void Chan::Sym::release(rcf_t *h) { bury(h, d_ring); bury(h, d_taps); d_ring = d_taps = nullptr; }
 void Chan::Agc::release(rcf_t *h) { bury(h, d_ring); d_ring = nullptr; }
 void Chan::Clock::release(rcf_t *h) { bury(h, d_ring); d_ring = nullptr; d_state = nullptr; d_bank = nullptr; }   // one allocation
+void Chan::Costas::release(rcf_t *h) { bury(h, d_ring); d_ring = nullptr; d_state = nullptr; d_bank = nullptr; }  // one allocation
 void Chan::Audio::release(rcf_t *h) { bury(h, d_state); bury(h, d_rings); bury(h, d_taps); d_state = nullptr; d_rings = d_taps = nullptr; }
 
 }  // namespace rcfx
@@ -49,6 +51,7 @@ int rcf_chan_agc(rcf_t *h, int chan_id, int nsamples, float reference)
     if (set_dev(h)) return RCF_EHIP;
     FIND_CHAN(h, chan_id, c);
     if (nsamples == 0) {                // off
+        if (c->costas) { set_error("channel %d: the Gardner / Costas stage reads the AGC (switch it off first)", chan_id); return RCF_ESTATE; }
         if (c->agc) { drop_stage(h, c->agc); ++h->chans_epoch; }
         return RCF_OK;
     }
@@ -65,6 +68,19 @@ int rcf_chan_agc(rcf_t *h, int chan_id, int nsamples, float reference)
     c->agc->ref = reference;
     c->agc->from = c->agc->rd = c->produced;         // a new GR block starts with zero history
     ++h->chans_epoch;
+    return RCF_OK;
+}
+
+// the interpolator bank the symbol clocks and the Gardner / Costas loops share unless the caller brings one: built at first use
+static int default_bank(rcf_t *h)
+{
+    if (h->d_mmse) return RCF_OK;
+    constexpr size_t kBank = (size_t)(kClockSteps + 1) * kClockTaps;
+    const std::vector<float> t = design_mmse_interpolator(kClockTaps, kClockSteps, 0.25);
+    Fresh<float> d;
+    RCF_HIP(d.alloc(kBank));
+    if (!hip_ok(hipMemcpy(d.p, t.data(), sizeof(float) * kBank, hipMemcpyHostToDevice), "hipMemcpy(interpolator bank)")) return RCF_EHIP;
+    h->d_mmse = d.take();
     return RCF_OK;
 }
 
@@ -94,13 +110,7 @@ int rcf_chan_clock_mm(rcf_t *h, int chan_id, const rcf_clock_mm_params_t *p)
     }
     if ((size_t)kClockTaps * 2 > h->out_cap) { set_error("ring of %zu too small for the clock's %d-sample window", h->out_cap, kClockTaps); return RCF_ECAP; }
     constexpr size_t kBank = (size_t)(kClockSteps + 1) * kClockTaps;
-    if (!p->interp_taps && !h->d_mmse) {
-        const std::vector<float> t = design_mmse_interpolator(kClockTaps, kClockSteps, 0.25);
-        Fresh<float> d;
-        RCF_HIP(d.alloc(kBank));
-        if (!hip_ok(hipMemcpy(d.p, t.data(), sizeof(float) * kBank, hipMemcpyHostToDevice), "hipMemcpy(interpolator bank)")) return RCF_EHIP;
-        h->d_mmse = d.take();
-    }
+    if (!p->interp_taps) { const int rc = default_bank(h); if (rc != RCF_OK) return rc; }
     // every call is a new GR block: a fresh ring and state (symbol 0 is the first of this call), zero history
     const size_t state_at = h->out_cap, bank_at = h->out_cap + 64;       // in floats; the state record has 256 bytes to itself
     Fresh<float> fresh;
@@ -123,6 +133,72 @@ int rcf_chan_clock_mm(rcf_t *h, int chan_id, const rcf_clock_mm_params_t *p)
     drop_stage(h, c->clock);
     c->clock = std::move(k);
     ++h->chans_epoch;
+    return RCF_OK;
+}
+
+// ---- Gardner / Costas symbol recovery behind the AGC (costas.hip)
+int rcf_chan_costas(rcf_t *h, int chan_id, const rcf_costas_params_t *p)
+{
+    if (!h) return RCF_EINVAL;
+    if (p) {
+        const float v[7] = {p->omega, p->gain_mu, p->gain_omega, p->alpha, p->beta, p->max_freq, p->omega_limit};
+        for (float x : v)
+            if (!std::isfinite(x)) { set_error("Gardner / Costas: non-finite parameter"); return RCF_EINVAL; }
+        // mu > 1 after every symbol (the loop consumes at least one input per symbol) and both windows inside 32 samples
+        if (p->omega < 2.f || p->omega > 16.f || p->omega_limit < 0.f || p->max_freq < 0.f || (double)p->max_freq >= kTwoPi / 2 ||
+            (double)p->omega - (double)p->omega_limit - (double)p->gain_mu < 2.0) {
+            set_error("Gardner / Costas: omega %g outside 2 .. 16, omega - omega_limit %g - gain_mu %g < 2, a negative limit, or max_freq %g outside 0 .. pi",
+                      p->omega, p->omega_limit, p->gain_mu, p->max_freq);
+            return RCF_EINVAL;
+        }
+    }
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!p) {                           // off
+        if (c->costas) { drop_stage(h, c->costas); ++h->chans_epoch; }
+        return RCF_OK;
+    }
+    if (!c->agc) { set_error("channel %d has no AGC for the Gardner / Costas stage to read", chan_id); return RCF_ESTATE; }
+    if (h->out_cap < 64) { set_error("ring of %zu too small for the Gardner / Costas stage", h->out_cap); return RCF_ECAP; }
+    constexpr size_t kBank = (size_t)(kClockSteps + 1) * kClockTaps;
+    if (!p->interp_taps) { const int rc = default_bank(h); if (rc != RCF_OK) return rc; }
+    // every call is a new block: a fresh ring and state (symbol 0 is the first of this call), zero history
+    constexpr size_t kStateFloats = (sizeof(CostasState) + 255) / 256 * 256 / sizeof(float);
+    const size_t state_at = h->out_cap, bank_at = h->out_cap + kStateFloats;     // in floats
+    Fresh<float> fresh;
+    RCF_HIP(fresh.alloc(bank_at + (p->interp_taps ? kBank : 0)));
+    std::unique_ptr<Chan::Costas> k(new Chan::Costas);
+    k->omega_mid = p->omega; k->omega_lim = p->omega_limit; k->gain_omega = p->gain_omega; k->gain_mu = p->gain_mu;
+    k->alpha = p->alpha; k->beta = p->beta; k->max_freq = p->max_freq;
+    k->window = std::max(2 * (int)std::ceil(k->omega_mid), (int)std::floor(k->omega_mid / 2) + 9);
+    CostasState st0{};
+    st0.mu = st0.omega = k->omega_mid;
+    if (!hip_ok(hipMemcpy(fresh.p + state_at, &st0, sizeof(st0), hipMemcpyHostToDevice), "hipMemcpy(Gardner / Costas state)") ||
+        (p->interp_taps && !hip_ok(hipMemcpy(fresh.p + bank_at, p->interp_taps, sizeof(float) * kBank, hipMemcpyHostToDevice), "hipMemcpy(interpolator bank)")))
+        return RCF_EHIP;
+    k->d_ring = fresh.take();
+    k->d_state = reinterpret_cast<CostasState *>(k->d_ring + state_at);
+    k->d_bank = p->interp_taps ? k->d_ring + bank_at : h->d_mmse;
+    k->from = c->produced;
+    drop_stage(h, c->costas);
+    c->costas = std::move(k);
+    ++h->chans_epoch;
+    return RCF_OK;
+}
+
+int rcf_chan_costas_state(rcf_t *h, int chan_id, rcf_costas_state_t *out)
+{
+    if (!h || !out) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!c->costas) { set_error("channel %d has no Gardner / Costas stage", chan_id); return RCF_ESTATE; }
+    CostasState st{};
+    RCF_HIP(hipMemcpyAsync(&st, c->costas->d_state, offsetof(CostasState, hist), hipMemcpyDeviceToHost, h->stream));
+    RCF_HIP(hipStreamSynchronize(h->stream));
+    out->n_symbols = st.n_out; out->n_slips = st.slips;
+    out->mu = st.mu; out->omega = st.omega; out->freq = st.freq; out->phase = st.phase;
     return RCF_OK;
 }
 

@@ -35,6 +35,7 @@ SYMBOLS = [
     "rcf_ingest_write", "rcf_push_raw", "rcf_chan_fm_filter", "rcf_chan_read_sym", "rcf_chan_fm_level",
     "rcf_chan_agc", "rcf_chan_read_agc", "rcf_chan_agc_ring",
     "rcf_chan_clock_mm", "rcf_chan_clock_produced", "rcf_chan_read_clock", "rcf_chan_clock_ring", "rcf_design_mmse_interpolator",
+    "rcf_chan_costas", "rcf_chan_costas_state", "rcf_chan_read_costas", "rcf_chan_costas_ring",
     "rcf_design_firdes", "rcf_design_optfir_low_pass", "rcf_design_fm_deemph", "rcf_design_resampler", "rcf_chan_audio_open",
     "rcf_chan_audio_close", "rcf_chan_audio_produced", "rcf_chan_read_audio",
     "rcf_host_alloc", "rcf_host_free", "rcf_comm_unique_id", "rcf_comm_init", "rcf_comm_destroy", "rcf_comm_size",
@@ -45,7 +46,7 @@ SYMBOLS = [
 ]
 FMT_CF32, FMT_U8, FMT_S8, FMT_S16 = 0, 1, 2, 3
 READ_IQ, READ_FM, READ_AGC = 0, 1, 2
-T_FIR, T_PFB, T_FIR_DERIVED, T_DISC, T_SCAN_FFT, T_SCAN_MOVSUM, T_HISTORY, T_FIR_MFMA, T_AUDIO, T_TAPS, T_CLOCK = range(11)
+T_FIR, T_PFB, T_FIR_DERIVED, T_DISC, T_SCAN_FFT, T_SCAN_MOVSUM, T_HISTORY, T_FIR_MFMA, T_AUDIO, T_TAPS, T_CLOCK, T_COSTAS = range(12)
 
 
 class AudioParams(C.Structure):
@@ -62,6 +63,33 @@ class ClockMmParams(C.Structure):
     _fields_ = [("gain", C.c_float), ("omega", C.c_float), ("gain_omega", C.c_float), ("mu", C.c_float),
                 ("gain_mu", C.c_float), ("omega_relative_limit", C.c_float), ("reserved_", C.c_int),
                 ("interp_taps", C.POINTER(C.c_float))]
+
+
+class CostasParams(C.Structure):
+    """rcf_costas_params_t (include/rcf.h)"""
+    _fields_ = [("omega", C.c_float), ("gain_mu", C.c_float), ("gain_omega", C.c_float), ("alpha", C.c_float),
+                ("beta", C.c_float), ("max_freq", C.c_float), ("omega_limit", C.c_float), ("reserved_", C.c_int),
+                ("interp_taps", C.POINTER(C.c_float))]
+
+
+class CostasState(C.Structure):
+    """rcf_costas_state_t (include/rcf.h)"""
+    _fields_ = [("n_symbols", C.c_int64), ("n_slips", C.c_int64), ("mu", C.c_float), ("omega", C.c_float),
+                ("freq", C.c_float), ("phase", C.c_float)]
+
+
+def costas_params_struct(omega, gain_mu, gain_omega, alpha, beta, max_freq, omega_limit, interp_taps=None):
+    """-> (CostasParams, the array its interp_taps points into or None: keep it while the struct is in use)"""
+    p = CostasParams()
+    p.omega, p.gain_mu, p.gain_omega, p.alpha = float(omega), float(gain_mu), float(gain_omega), float(alpha)
+    p.beta, p.max_freq, p.omega_limit = float(beta), float(max_freq), float(omega_limit)
+    taps = None
+    if interp_taps is not None:
+        taps = np.ascontiguousarray(interp_taps, dtype=np.float32)
+        if taps.shape != (129, 8):
+            raise ValueError("interp_taps must be a [129, 8] array")
+        p.interp_taps = taps.ctypes.data_as(C.POINTER(C.c_float))
+    return p, taps
 
 
 class PumpConfig(C.Structure):
@@ -138,6 +166,10 @@ def lib():
         "rcf_chan_clock_produced": (C.c_int, [vp, C.c_int, C.POINTER(i64), C.POINTER(i64)]),
         "rcf_chan_read_clock": (i64, [vp, C.c_int, fp, sz]),
         "rcf_chan_clock_ring": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]),
+        "rcf_chan_costas": (C.c_int, [vp, C.c_int, C.POINTER(CostasParams)]),
+        "rcf_chan_costas_state": (C.c_int, [vp, C.c_int, C.POINTER(CostasState)]),
+        "rcf_chan_read_costas": (i64, [vp, C.c_int, fp, sz]),
+        "rcf_chan_costas_ring": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]),
         "rcf_design_mmse_interpolator": (C.c_int, [C.c_int, C.c_int, C.c_double, fp, C.c_int]),
         "rcf_chan_fm_level": (C.c_int, [vp, C.c_int, C.c_float, C.c_int, fp]),
         "rcf_design_firdes": (C.c_int, [C.c_int] + [C.c_double] * 4 + [C.c_int, C.c_double, fp, C.c_int]),
@@ -674,6 +706,38 @@ class Frontend:
         """(device pointer, capacity) of the channel's float32 soft-symbol ring (rcf_chan_clock_ring)"""
         p, cap = C.c_void_p(), C.c_size_t()
         _check(lib().rcf_chan_clock_ring(self._h, cid, C.byref(p), C.byref(cap)))
+        return p.value, cap.value
+
+    def chan_costas(self, cid, omega, gain_mu=0.025, gain_omega=6.25e-5, alpha=0.04, beta=2e-4, max_freq=0.0, omega_limit=0.005,
+                    interp_taps=None):
+        """op25's repeater.gardner_costas_cc(omega, gain_mu, gain_omega, alpha, beta, max_freq, -max_freq) -> diff_phasor_cc
+        -> complex_to_arg -> multiply_const_ff(4 / pi) on the channel's AGC ring (rcf_chan_costas, which defines the
+        stage: unpinned against op25; p25_control_demod.py:150-183), starting with zero history at the channel's next
+        output; omega=None switches it off.  The channel must carry an AGC (chan_agc).  interp_taps: a [129, 8]
+        interpolator bank; None = design_mmse_interpolator()"""
+        if omega is None:
+            _check(lib().rcf_chan_costas(self._h, cid, None))
+            return
+        p, _keep = costas_params_struct(omega, gain_mu, gain_omega, alpha, beta, max_freq, omega_limit, interp_taps)
+        _check(lib().rcf_chan_costas(self._h, cid, C.byref(p)))
+
+    def chan_costas_state(self, cid) -> dict:
+        """the loop's state as of the last block: n_symbols, n_slips, mu, omega, freq (radians per channel sample, of the
+        sign opposite to the carrier's offset), phase (rcf_chan_costas_state; syncs the stream)"""
+        st = CostasState()
+        _check(lib().rcf_chan_costas_state(self._h, cid, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in CostasState._fields_}
+
+    def chan_read_costas(self, cid, max_symbols=1 << 20) -> np.ndarray:
+        """unread soft symbols of the channel's Gardner / Costas stage (+-1, +-3 on a locked signal), oldest first"""
+        out = np.empty(max_symbols, dtype=np.float32)
+        n = _check(lib().rcf_chan_read_costas(self._h, cid, _fp(out), max_symbols))
+        return out[:n].copy()
+
+    def chan_costas_ring(self, cid):
+        """(device pointer, capacity) of the stage's float32 soft-symbol ring (rcf_chan_costas_ring)"""
+        p, cap = C.c_void_p(), C.c_size_t()
+        _check(lib().rcf_chan_costas_ring(self._h, cid, C.byref(p), C.byref(cap)))
         return p.value, cap.value
 
     def chan_fm_level(self, cid, gain, window=10000) -> float:

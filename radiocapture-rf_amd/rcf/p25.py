@@ -3,10 +3,16 @@ logging_receiver.py:278-332).  Both modulations start from the same pre-filter a
 
   C4FM   quadrature_demod_cf(channel_rate / (2 pi 600)) -> fir_filter_fff(1, (1/sps,)*sps) -> op25 fsk4_demod_ff
   CQPSK  multiply_const_cc(1.0) -> feedforward_agc_cc(1024, 1.0) -> multiply_const_cc(1.0) -> op25 gardner_costas_cc
+         -> diff_phasor_cc -> complex_to_arg -> multiply_const_ff(4 / pi) -> op25 fsk4_slicer_fb([-2, 0, 2, 4])
 
-The GPU half stops before the sequential op25 loop (fsk4_demod_ff, gardner_costas_cc): a demod reads the symbol
-filter's output (chan_read_sym) or the AGC's (chan_read_agc) and runs that loop itself."""
+The C4FM half stops before the sequential op25 loop (fsk4_demod_ff): a demod reads the symbol filter's output
+(chan_read_sym) and runs that loop itself.  The CQPSK chain runs on the GPU up to the slicer (cqpsk_demod): the
+Gardner / Costas loop is the stage rcf_chan_costas, which include/rcf.h defines from the published algorithm -- op25's
+source is not in the reference tree, so the stage is unpinned against op25 --, and a demod reads soft dibits at the
+symbol rate (chan_read_costas) and slices them (slice_dibits)."""
 import math
+
+import numpy as np
 
 from . import native
 
@@ -43,6 +49,30 @@ def cqpsk_front_half(fe, chan_id, channel_rate, nsamples=1024, reference=1.0):
     cid = _prefilter(fe, chan_id, channel_rate)
     fe.chan_agc(cid, nsamples, reference)
     return cid
+
+
+def costas_params(channel_rate, symbol_rate=SYMBOL_RATE):
+    """gardner_costas_cc's arguments as p25_control_demod.py:150-160 and logging_receiver.py:282-296 compute them, at a
+    channel of 2 channel_rate samples per second: keyword arguments of Frontend.chan_costas"""
+    rate = 2.0 * channel_rate
+    gain_mu, alpha = 0.025, 0.04
+    return dict(omega=rate / symbol_rate, gain_mu=gain_mu, gain_omega=0.1 * gain_mu * gain_mu, alpha=alpha,
+                beta=0.125 * alpha * alpha, max_freq=2.0 * math.pi * 1200.0 / rate, omega_limit=0.005)
+
+
+def cqpsk_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE):
+    """the whole CQPSK chain up to the slicer on channel `chan_id` of Frontend `fe`: the front half, then the Gardner /
+    Costas stage (p25_control_demod.py:136-183).  Returns the pre-filter channel's id: chan_read_costas on it gives soft
+    dibits at symbol_rate (slice_dibits turns them into dibits), chan_costas_state its carrier estimate."""
+    cid = cqpsk_front_half(fe, chan_id, channel_rate)
+    fe.chan_costas(cid, **costas_params(channel_rate, symbol_rate))
+    return cid
+
+
+def slice_dibits(soft, levels=(-2.0, 0.0, 2.0, 4.0)):
+    """op25.fsk4_slicer_fb(levels) (p25_control_demod.py:161): < levels[0] -> 3, < levels[1] -> 2, < levels[2] -> 0, else 1"""
+    s = np.asarray(soft)
+    return np.where(s < levels[0], 3, np.where(s < levels[1], 2, np.where(s < levels[2], 0, 1))).astype(np.uint8)
 
 
 def c4fm_front_half(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE):
