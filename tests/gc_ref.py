@@ -37,6 +37,8 @@ class GardnerCostas:
         self.hr = np.zeros(HIST, dtype=f)                                     # the last 32 derotated samples, newest last
         self.hi = np.zeros(HIST, dtype=f)
         self.n_symbols = self.n_slips = 0
+        self.n_clamped = 0                                                    # times hs exceeded L - 8 before the min
+        self.clamped = []                                                     # ... and the indices of those symbols
         self._reset()
 
     def _reset(self):
@@ -89,6 +91,9 @@ class GardnerCostas:
                 if hm > one:
                     hm = f(hm - one)
                     hs += 1
+                if hs > self.L - NTAPS:
+                    self.n_clamped += 1
+                    self.clamped.append(self.n_symbols)
                 hs = min(hs, self.L - NTAPS)
                 mid_re, mid_im = self._interp(0, self.mu)
                 y_re, y_im = self._interp(hs, hm)
@@ -151,6 +156,19 @@ def angle_diff_mod8(a, b):
     """a - b for soft symbols (angles in units of pi / 4, period 8), folded into [-4, 4)"""
     d = np.asarray(a, dtype=np.float64) - np.asarray(b, dtype=np.float64)
     return (d + 4.0) % 8.0 - 4.0
+
+
+def distance(a, b, lo=0, hi=None, mask=None):
+    """-> (rms, largest) absolute angle_diff_mod8(a, b) over the symbols [lo, hi) (hi None: the shorter length) that the
+    boolean `mask` (indexed like a and b) keeps.  Non-finite symbols have to be masked out by the caller: one that is left
+    in makes both measures NaN, which no comparison passes"""
+    hi = min(len(a), len(b)) if hi is None else hi
+    assert 0 <= lo < hi <= min(len(a), len(b)), (lo, hi, len(a), len(b))
+    d = np.abs(angle_diff_mod8(a[lo:hi], b[lo:hi]))
+    if mask is not None:
+        d = d[np.asarray(mask[lo:hi], dtype=bool)]
+    assert len(d) > 0
+    return (float(np.sqrt(np.mean(d ** 2))), float(np.max(d))) if np.isfinite(d).all() else (float("nan"), float("nan"))
 
 
 def raised_cosine(t, alpha=0.2):
@@ -217,3 +235,94 @@ def chain_delay(omega, chan_ntaps, decim, pre_ntaps=69, agc_n=AGC_N):
     """whole symbols the chain in front of the loop holds a symbol back: the channel filter's and the pre-filter's group
     delays and the AGC's N - 1 samples, in channel samples, over omega, rounded down"""
     return int(((chan_ntaps - 1) / 2.0 / decim + (pre_ntaps - 1) / 2.0 + (agc_n - 1)) / omega)
+
+
+# ---- mixed rates and the omega range in one wave (test_mixed_rates_and_omega_range_in_one_wave): eight direct channels
+# of one 400 kS/s front-end, feedforward_agc_cc(64, 1.0) and the loop on each, six blocks of 16000 inputs, so that n_k is
+# 500, 1000 or 2000 and the lanes leave the kernel's chunk loop at different trips.  The rates interleave across the lanes.
+# (chan_open's rate, baud, channel offset, carrier offset, timing, the block the loop is attached before, a caller's
+#  bank, decodes after `skip` symbols or None: tests/test_costas_cpu.py decides the last column)
+MIXED_BLK, MIXED_BLOCKS, MIXED_AGC_N = 16000, 6, 64
+MIXED = [
+    (25000, 9600, -130000.0, 80.0, 0.5, 2, False, 500),       # omega 5.2083 at 50 kS/s, two blocks late
+    (6250, 2400, 20000.0, 60.0, 0.5, 0, False, 200),          # omega 5.2083 at 12.5 kS/s
+    (12500, 3125, -75000.0, 100.0, 0.5, 0, False, 500),       # omega 8, L = 16
+    (25000, 3125, 150000.0, 70.0, 0.5, 0, False, 200),        # omega 16, L = 32: the window is the whole history
+    (6250, 6000, 50000.0, 90.0, 0.5, 0, False, None),         # omega 2.0833, L = 10: too narrow a channel to decode
+    (12500, 4800, -25000.0, 100.0, 0.5, 0, False, 300),       # the P25 shape
+    (12500, 6000, 90000.0, -80.0, 0.5, 0, True, None),        # a caller's bank (linear): a second pass in the wave
+    (6250, 2400, -190000.0, -60.0, 0.4, 0, False, 200),
+]
+
+
+def mixed_signal():
+    """-> (x complex64 of MIXED_BLOCKS blocks, per channel the dibits sent): the eight carriers over weak noise"""
+    n = MIXED_BLK * MIXED_BLOCKS
+    rng = np.random.default_rng(816)
+    x = 0.002 * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
+    sent = []
+    for cr, baud, off, cfo, timing, _, _, _ in MIXED:
+        d = rng.integers(0, 4, n * baud // int(FS) + 2).astype(np.uint8)
+        x = x + dqpsk_carrier(d, baud, FS, off + cfo, timing, amplitude=0.1, n_samples=n)
+        sent.append(d)
+    return x.astype(np.complex64), sent
+
+
+def comparable_prefix(s_a, gc_a, s_b, gc_b, tol=0.05):
+    """-> (P, the clamp hits inside it): the longest prefix of symbols over which two runs of the restatement on one input
+    are the same loop up to rounding: every symbol k < P differs by less than tol (a run that was one symbol ahead of the
+    other would not), and both runs took the window clamp at the same symbols k < P"""
+    n = min(len(s_a), len(s_b))
+    far = np.flatnonzero(~(np.abs(angle_diff_mod8(s_a[:n], s_b[:n])) < tol))
+    P = int(far[0]) if len(far) else n
+    odd = sorted(set(gc_a.clamped) ^ set(gc_b.clamped))
+    if odd and odd[0] < P:
+        P = odd[0]
+    return P, [k for k in gc_a.clamped if k < P]
+
+
+# ---- non-finite bursts (test_coming_back_from_non_finite_input): standard-chain signals of 2500 symbols with a few
+# front-end input samples overwritten.  (case of CASES, the value, the first overwritten input, how many, the dibit
+# errors of the restatement later than SKIP symbols after the burst: tests/test_costas_cpu.py decides the last column)
+N_BURST_SYMBOLS = 2500
+BURSTS = [(CASES[0], complex(float("nan"), float("nan")), 100003, 1, 0), (CASES[3], complex(float("inf"), 0.0), 80005, 3, 0)]
+BURST_CLEAN = CASES[1]
+
+
+def burst_signal(case, value=None, at=0, count=0):
+    x, sent = case_signal(*case, n_symbols=N_BURST_SYMBOLS)
+    if count:
+        x = x.copy()
+        x[at:at + count] = value
+    return x, sent
+
+
+def burst_span(agc, omega):
+    """-> (first, last) symbol index a burst can have touched directly: the AGC outputs that are not finite or exactly
+    zero (a gain of 1 / inf) in the middle half of the stream, over omega, widened by 8 symbols either way (the loop's
+    omega stays within 0.1 % of the nominal one, every slip moves the count by less than one symbol)"""
+    n = len(agc)
+    bad = np.flatnonzero(~np.isfinite(agc) | (agc == 0))
+    bad = bad[(bad > n // 4) & (bad < 3 * n // 4)]
+    assert len(bad) > 0
+    return int(bad[0] / omega) - 8, int(bad[-1] / omega) + 8
+
+
+def symbols_before_first_slip(x, params, taps, dtype=np.float32):
+    """the number of symbols the restatement has produced when its guard first fires (None: it never does)"""
+    gc = GardnerCostas(taps=taps, dtype=dtype, **params)
+    for m in range(len(x)):
+        gc.work(x[m:m + 1])
+        if gc.n_slips:
+            return gc.n_symbols
+    return None
+
+
+# ---- the window clamp (test_window_clamp): a 6250-baud carrier in the standard chain and a loop whose negative gain_omega
+# pins omega at its upper limit, 4.15 > 4: hs reaches 3 > L - 8 = 2.  Such a loop is chaotic; only a prefix is comparable
+CLAMP_CASE = (6250, 100.0, 0.5)
+CLAMP_PARAMS = dict(omega=3.95, omega_limit=0.2, gain_omega=-1e-2)
+
+# ---- the guard's mu <= 1 arm (test_guard_through_mu): CASES[0] cut to 600 symbols on a direct channel with
+# feedforward_agc_cc(64, 1.0), and a gain_mu that throws mu below 1 (-40) or far away (-3e38: the loop sleeps)
+MU_SYMBOLS, MU_AGC_N, MU_GAINS = 600, 64, (-40.0, -3e38)

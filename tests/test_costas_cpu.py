@@ -3,6 +3,7 @@ argument checks, the reference's loop parameters, the slicer rule, and the resta
 the oracle chain (xlating_fir_ccc twice, feedforward_agc): it decodes what was sent, does not depend on how its input is
 cut, and its float32 and float64 runs stay within rounding noise of each other -- the distance the GPU test
 (tests/test_gpu_costas.py) takes as its yardstick.  The stage is defined by include/rcf.h and unpinned against op25."""
+import hashlib
 import math
 
 import numpy as np
@@ -10,6 +11,7 @@ import pytest
 
 import agc_ref as A
 import gc_ref as R
+import mm_ref as M
 from oracle import grspec as G
 from rcf import native, p25
 
@@ -124,3 +126,184 @@ def test_float32_and_float64_runs_differ_by_rounding_noise(chain, case):
     print("%s: float32 against float64 restatement: rms %.3e soft-symbol units over %d symbols" % (case, rms, n - R.SKIP))
     # both are the same loop on the same input: far below the 1.0 that separates a symbol from the slicer's levels
     assert 0 < rms < 0.05
+
+
+# ---- the inputs of the GPU tests beyond the P25 operating point: each case is decided here, on the oracle chain, by the
+# conditions its test names; the yardsticks printed are those of the oracle chain's stream (the GPU tests take theirs from
+# the GPU's own AGC stream)
+
+CASES_F32_SHA256 = "2073803575fac8fe94791b88a04b7687848831646eca818786dcda26fa764562"
+
+
+def test_float32_outputs_on_the_cases_are_the_recorded_bits(chain):
+    """the restatement counts the window clamp and nothing else about it has changed: the float32 soft symbols of the
+    five CASES, concatenated, hash to what they did before the counter went in"""
+    h = hashlib.sha256()
+    for case in R.CASES:
+        h.update(np.ascontiguousarray(chain[case]["s32"], dtype=f32).tobytes())
+        assert chain[case]["g32"].n_clamped == 0 and chain[case]["g32"].clamped == []
+    assert h.hexdigest() == CASES_F32_SHA256
+
+
+def _standard_chain(x):
+    """the channel filter and the pre-filter of the standard chain -> what the AGC reads, and the channel samples the chain
+    with its AGC holds a symbol back"""
+    D, taps = G.channel_params(R.FS, R.CHANNEL_RATE)
+    pre = G.low_pass_2(1.0, 2 * R.CHANNEL_RATE, R.CHANNEL_RATE / 2, 500, 30, G.WIN_BLACKMAN)
+    with np.errstate(all="ignore"):
+        y1 = G.xlating_fir_ccc(x, D, taps, R.CHANNEL_OFFSET, R.FS)
+        return G.xlating_fir_ccc(y1, 1, pre, 0.0, 2.0 * R.CHANNEL_RATE), R.chain_delay(1.0, len(taps), D, len(pre))
+
+
+def _agc_dropping_nan(y, n):
+    """feedforward_agc_cc as GNU Radio's loop and the GPU's fmaxf run it on non-finite input: a NaN envelope never wins
+    the window's maximum (agc_ref.feedforward_agc_naive does the same; numpy's max in feedforward_agc would spread it)"""
+    env = A.envelope(y)
+    g = f32(1.0) / A.window_max(np.where(np.isnan(env), f32(0), env), n)
+    yd = np.concatenate([np.zeros(n - 1, dtype=np.complex64), y])[:len(y)]
+    out = np.empty(len(y), dtype=np.complex64)
+    with np.errstate(all="ignore"):
+        out.real = yd.real * g
+        out.imag = yd.imag * g
+    return out
+
+
+@pytest.mark.parametrize("case", R.CASES)
+def test_the_start_has_a_yardstick_too(chain, case):
+    """symbols [0, SKIP) and the first 16, which the GPU parity test compares as well.  The AGC of 1024 delivers zeros for
+    its first 1023 outputs, about 196 symbols: the first 16 are 0 in both runs, and what that range checks is that a loop
+    fed zeros puts out zeros.  Symbols that follow a start on a live signal are those of the AGC-64 cases (the mixed-rate
+    lanes, the lanes of the 130-channel test, gain_mu -40), compared from symbol 0"""
+    c = chain[case]
+    rms, mx = R.distance(c["s32"], c["s64"], 0, R.SKIP)
+    _, mx16 = R.distance(c["s32"], c["s64"], 0, 16)
+    print("%s: float32 against float64 restatement over [0, %d): rms %.3e, max %.3e; max over the first 16: %.3e"
+          % (case, R.SKIP, rms, mx, mx16))
+    assert 0 < rms < 0.05 and mx16 <= mx < 0.05
+
+
+@pytest.fixture(scope="module")
+def mixed(bank):
+    x, sent = R.mixed_signal()
+    out = []
+    for k, (cr, baud, off, cfo, timing, late, own, skip) in enumerate(R.MIXED):
+        D, taps = G.channel_params(R.FS, cr)
+        agc = A.feedforward_agc(G.xlating_fir_ccc(x, D, taps, off, R.FS), R.MIXED_AGC_N, 1.0)
+        a = agc[late * R.MIXED_BLK // D:]                     # the loop starts at the channel's next output
+        params = p25.costas_params(cr, baud)
+        T = M.linear_bank() if own else bank
+        s32, g32 = R.gardner_costas(a, params, T)
+        s64, g64 = R.gardner_costas(a, params, T, dtype=np.float64)
+        out.append(dict(n_in=len(a), params=params, s32=s32, g32=g32, s64=s64, g64=g64,
+                        sent=sent[k][late * R.MIXED_BLK * baud // int(R.FS):],
+                        delay=R.chain_delay(params["omega"], len(taps), D, pre_ntaps=1, agc_n=R.MIXED_AGC_N)))
+    return out
+
+
+def test_mixed_rate_cases_meet_their_conditions(mixed):
+    rows = R.MIXED
+    assert len(rows) <= 8 and {2 * r[0] for r in rows} == {12500, 25000, 50000}
+    assert [r[0] for r in rows[:3]] == [25000, 6250, 12500]   # the rates interleave across the lanes
+    assert sum(r[5] > 0 for r in rows) == 1 and sum(r[6] for r in rows) == 1
+    for a in rows:
+        for b in rows:                                        # 50 kS/s neighbours at least 50 kHz apart
+            assert a is b or 25000 not in (a[0], b[0]) or abs(a[2] - b[2]) >= 50000.0
+    seen = set()
+    for k, (row, m) in enumerate(zip(rows, mixed)):
+        cr, baud, off, cfo, timing, late, own, skip = row
+        omega, L = m["params"]["omega"], m["g32"].L
+        seen.add((2 * cr, baud))
+        assert m["n_in"] == (R.MIXED_BLOCKS - late) * R.MIXED_BLK * 2 * cr // int(R.FS)
+        rms, mx = R.distance(m["s32"], m["s64"])
+        errs = None if skip is None else R.decode_errors(m["s32"], m["sent"], m["delay"], skip=skip)
+        print("mixed %d: %d S/s, %d baud, omega %.4f, L %d, %d symbols in both runs, slips %d, clamped %d; float32 against "
+              "float64 from symbol 0: rms %.3e, max %.3e; (lag, dibit errors) after %s: %s"
+              % (k, 2 * cr, baud, omega, L, len(m["s32"]), m["g32"].n_slips, m["g32"].n_clamped, rms, mx, skip, errs))
+        assert len(m["s32"]) == len(m["s64"]) <= 2500
+        assert m["g32"].n_slips == m["g64"].n_slips == 0
+        assert 0 < rms < 0.05
+        if skip is not None:
+            assert errs[1] == 0 and R.decode_errors(m["s64"], m["sent"], m["delay"], skip=skip)[1] == 0
+            assert len(m["s32"]) - skip >= 70
+    # the table's rows and the P25 shape
+    assert {(12500, 2400), (25000, 3125), (50000, 9600), (50000, 3125), (12500, 6000), (25000, 4800)} <= seen
+    assert mixed[3]["params"]["omega"] == 16.0 and mixed[3]["g32"].L == 32
+    assert abs(mixed[4]["params"]["omega"] - 2.0833) < 1e-4 and mixed[4]["g32"].L == 10
+    assert mixed[2]["g32"].L == 16 and mixed[0]["g32"].L == mixed[1]["g32"].L == 12
+
+
+def test_window_clamp_case_is_comparable_over_a_prefix(bank):
+    x, _ = R.case_signal(*R.CLAMP_CASE)
+    y, _ = _standard_chain(x)
+    agc = A.feedforward_agc(y, R.AGC_N, 1.0)
+    params = dict(p25.costas_params(R.CHANNEL_RATE, R.CLAMP_CASE[0]), **R.CLAMP_PARAMS)
+    s32, g32 = R.gardner_costas(agc, params, bank)
+    s64, g64 = R.gardner_costas(agc, params, bank, dtype=np.float64)
+    P, hits = R.comparable_prefix(s32, g32, s64, g64)
+    _, mx = R.distance(s32, s64, 0, P)
+    print("window clamp %s %s: L %d, %d / %d symbols, clamp taken %d / %d times; comparable prefix P = %d with %d hits, "
+          "the first at %s; float32 against float64 over [0, P): max %.3e"
+          % (R.CLAMP_CASE, R.CLAMP_PARAMS, g32.L, len(s32), len(s64), g32.n_clamped, g64.n_clamped, P, len(hits), hits[:3], mx))
+    assert g32.L - R.NTAPS == 2 and params["omega"] - params["omega_limit"] - params["gain_mu"] >= 2
+    assert P >= 64 and len(hits) >= 3 and mx < 0.05
+    assert abs(len(s32) - len(s64)) <= 2 and np.isfinite(s32).all() and g32.n_slips == 0
+    assert abs(float(g32.omega) - float(g32.omega_mid)) <= float(g32.omega_limit) * (1 + 1e-6)
+
+
+@pytest.mark.parametrize("k", range(len(R.BURSTS)))
+def test_burst_cases_come_back_alike_in_both_runs(bank, k):
+    case, value, at, count, tail_errors = R.BURSTS[k]
+    x, sent = R.burst_signal(case, value, at, count)
+    y, delay1 = _standard_chain(x)
+    params = p25.costas_params(R.CHANNEL_RATE, case[0])
+    delay = int(delay1 / params["omega"])
+    assert 0 < (~np.isfinite(y)).sum() < 100
+    # the oracle's FIR (complex128 products) turns inf + 0j into NaN, which the AGC drops; a filter that keeps an Inf
+    # zeroes the AGC's gain for the window in front of it instead.  Both are run: the drop-out is the second
+    streams = [y] + ([np.where(np.isfinite(y), y, np.complex64(complex(np.inf, 0.0)))] if np.isinf(value.real) else [])
+    assert any(np.isinf(b[1].real) for b in R.BURSTS) and any(np.isnan(b[1].real) for b in R.BURSTS)
+    for y in streams:
+        agc = _agc_dropping_nan(y, R.AGC_N)
+        s32, g32 = R.gardner_costas(agc, params, bank)
+        s64, g64 = R.gardner_costas(agc, params, bank, dtype=np.float64)
+        bad32, bad64 = np.flatnonzero(~np.isfinite(s32)), np.flatnonzero(~np.isfinite(s64))
+        a, b = R.burst_span(agc, params["omega"])
+        assert len(s32) == len(s64) and g32.n_slips == g64.n_slips > 0
+        assert np.array_equal(bad32, bad64) and 0 < len(bad32) < 0.02 * len(s32) and a <= bad32[0] and bad32[-1] <= b
+        fin = np.isfinite(s32)
+        before, after = R.distance(s32, s64, 0, a, fin), R.distance(s32, s64, b + R.SKIP, None, fin)
+        lag, errs = R.decode_errors(s32, sent, delay, skip=b + R.SKIP)
+        print("burst %s, %d x %s at input %d (%d AGC outputs zeroed): %d symbols, %d slips, %d non-finite symbols in %d .. %d "
+              "in both runs; float32 against float64 before symbol %d: rms %.3e, max %.3e; after symbol %d: rms %.3e; "
+              "lag %d, %d dibit errors in the tail of %d"
+              % (case, count, value, at, int((agc[len(agc) // 4:] == 0).sum()), len(s32), g32.n_slips, len(bad32), bad32[0], bad32[-1],
+                 a, before[0], before[1], b + R.SKIP, after[0], lag, errs, len(s32) - b - R.SKIP))
+        assert a > 1000 and len(s32) - b - R.SKIP > 200
+        assert 0 < before[0] < 0.05 and 0 < after[0] < 0.05
+        assert errs == tail_errors and R.decode_errors(s64, sent, delay, skip=b + R.SKIP)[1] == tail_errors
+        assert all(np.isfinite(v) for v in (g32.mu, g32.omega, g32.phase, g32.freq))
+    assert any(b[4] == 0 for b in R.BURSTS)
+
+
+@pytest.mark.parametrize("gain_mu", R.MU_GAINS)
+def test_mu_guard_cases_agree_in_both_runs(bank, gain_mu):
+    x, _ = R.case_signal(*R.CASES[0], n_symbols=R.MU_SYMBOLS)
+    D, taps = G.channel_params(R.FS, R.CHANNEL_RATE)
+    agc = A.feedforward_agc(G.xlating_fir_ccc(x, D, taps, R.CHANNEL_OFFSET, R.FS), R.MU_AGC_N, 1.0)
+    params = dict(p25.costas_params(R.CHANNEL_RATE, R.CASES[0][0]), gain_mu=gain_mu)
+    s32, g32 = R.gardner_costas(agc, params, bank)
+    s64, g64 = R.gardner_costas(agc, params, bank, dtype=np.float64)
+    first = R.symbols_before_first_slip(agc, params, bank)
+    print("gain_mu %g: %d / %d symbols of %d sent, %d / %d slips, the first after symbol %s; mu at the end %g"
+          % (gain_mu, len(s32), len(s64), R.MU_SYMBOLS, g32.n_slips, g64.n_slips, first, g32.mu))
+    assert len(s32) == len(s64) and g32.n_slips == g64.n_slips and np.isfinite(s32).all()
+    assert first == R.symbols_before_first_slip(agc, params, bank, dtype=np.float64)
+    if gain_mu == -40.0:
+        assert g32.n_slips > 0 and 16 <= first < len(s32) < R.MU_SYMBOLS
+        _, mx = R.distance(s32, s64, 0, first)
+        print("    float32 against float64 over the %d symbols before the first slip: max %.3e" % (first, mx))
+        assert 0 < mx < 0.05
+    else:                                                     # one huge step of mu, and no input brings it back
+        assert g32.n_slips == 0 and first is None and len(s32) < 32 and g32.mu > 1e30
+        again, g = R.gardner_costas(np.concatenate([agc, agc]), params, bank)
+        assert len(again) == len(s32) and g.n_slips == 0
