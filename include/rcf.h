@@ -160,7 +160,8 @@ int rcf_device(rcf_t *h);
 #define RCF_T_TAPS         9   /* filterbank taps: tap matrix -> channel rings, rotator + discriminator fused */
 #define RCF_T_CLOCK        10  /* symbol clocks (rcf_chan_clock_mm): one launch per block for every clocked channel */
 #define RCF_T_COSTAS       11  /* Gardner / Costas loops (rcf_chan_costas): one launch per block for every channel with the stage */
-#define RCF_T_COUNT        12
+#define RCF_T_FSK4         12  /* C4FM symbol loops (rcf_chan_fsk4): one launch per block for every channel with the stage */
+#define RCF_T_COUNT        13
 /* on = 0: off; 1: every class; otherwise a mask with bit (class + 1) set for each class to time -- every timed
  * launch costs two event records on the stream (~10 us of gap), so a throughput run times only what it reports.  The
  * filterbank's launch carries its two events attached to the dispatch (one barrier packet less inside the measured
@@ -261,7 +262,8 @@ int rcf_chan_read_many(rcf_t *h, int what, const int *chan_ids, int n_chans, flo
 /* P25 C4FM front half after the discriminator (p25_control_demod.py:129-133, logging_receiver.py:240-244):
  * filter.fir_filter_fff(1, taps) over quadrature_demod_cf(gain) -- e.g. the 5-tap boxcar symbol filter
  * (1/sps,)*sps.  Enabled per channel; applies from the next block on; output read with rcf_chan_read_sym
- * at the channel's rate (the sequential symbol-timing loop, op25 fsk4_demod_ff, stays on the host). */
+ * at the channel's rate (the sequential symbol-timing loop behind it, op25 fsk4_demod_ff, is rcf_chan_fsk4, below; a
+ * second call -- new taps -- keeps that stage running). */
 int rcf_chan_fm_filter(rcf_t *h, int chan_id, float gain, const float *taps, int ntaps);
 int64_t rcf_chan_read_sym(rcf_t *h, int chan_id, float *out, size_t max_samples);
 /* P25 CQPSK front half after the pre-filter (p25_control_demod.py:146-149,182-183; logging_receiver.py:278-332 runs the
@@ -399,6 +401,71 @@ int64_t rcf_chan_read_costas(rcf_t *h, int chan_id, float *out, size_t max_symbo
 /* device pointer of the soft-symbol ring and its capacity (zero-copy, like rcf_chan_rings): symbol k lives at index
  * k & (capacity-1); rcf_chan_costas_state gives the count */
 int rcf_chan_costas_ring(rcf_t *h, int chan_id, void **sym_ring, size_t *capacity);
+/* The back half of the P25 C4FM demodulators behind the symbol filter (p25_control_demod.py:118-135,
+ * logging_receiver.py:231-251):
+ *     op25.fsk4_demod_ff(autotuneq, sample_rate, symbol_rate)            [-> op25.fsk4_slicer_fb([-2, 0, 2, 4]) at the consumer]
+ * as a per-channel stage on the GPU that reads the channel's symbol-filter ring (rcf_chan_fm_filter) and writes float32
+ * soft symbols at the symbol rate (+-1, +-3 on a locked signal).  op25's source is not part of the reference tree, so this
+ * comment DEFINES the stage: it restates the published fsk4_demod_ff tracking loop and is "parity unpinned" 
+ * against any particular op25 build -- unpinned against op25.
+ * All state is double, as in op25.  Every product, sum and quotient is rounded on its own (no fused multiply-add); a
+ * division is the IEEE division.  time = symbol_rate / sample_rate (one double division).  T is the interpolator bank of
+ * rcf_chan_clock_mm, 129 rows of 8 floats.  State per channel: clock = 0, spread = 2, fine = 0, coarse = 0, the last 8
+ * inputs h[0 .. 7] (float, all 0 at the start, h[7] the newest), and 64-bit counts of symbols and slips.  For every
+ * symbol-filter output u[m] from the stage's start on:
+ *   1. clock = clock + time;  h[0 .. 6] = h[1 .. 7];  h[7] = u[m]
+ *   2. if not (clock > 1): next input
+ *   3. clock = clock - 1
+ *      v = floor(0.5 + 128 * (clock / time));  imu = v < 0 ? 0 : v > 127 ? 127 : (int)v      (a NaN gives 0)
+ *      a = sum over j = 0 .. 7, in that order, from 0.0, of (double)(T[imu][j] * h[j])       (float product, double sum;
+ *                                                                                             the taps are NOT reversed)
+ *      b = the same sum with row imu + 1
+ *      a = a - fine;  b = b - fine
+ *      out[k] = (float)((2 * a) / spread)
+ *      if      a < -spread:  e = a + 1.5 * spread;  spread = spread - (e * 0.5) * k_spread
+ *      else if a < 0:        e = a + 0.5 * spread;  spread = spread - e * k_spread
+ *      else if a < spread:   e = a - 0.5 * spread;  spread = spread + e * k_spread
+ *      else:                 e = a - 1.5 * spread;  spread = spread + (e * 0.5) * k_spread    (a NaN lands here)
+ *      clock  = b < a ? clock + e * k_timing : clock - e * k_timing
+ *      spread = spread < spread_min ? spread_min : spread;  spread = spread > spread_max ? spread_max : spread   (a NaN passes)
+ *      coarse = coarse + (fine - coarse) * k_coarse
+ *      fine   = fine + e * k_fine
+ * One guard, counted in n_slips: if after step 3 clock, spread, fine or coarse is not finite, or clock is outside
+ * -1 .. 2, the four go back to their initial values (the 8 inputs stay).  op25 has no such guard -- there a NaN stops the
+ * loop for good.  It does not fire on a signal.  At most one symbol per input; the outputs depend on the input stream
+ * only, never on how it was cut into blocks.
+ * coarse is what op25 posts to its autotune queue: the slow average of the level offset, in units of the discriminator's
+ * output, where one level step is symbol_deviation Hz at the gain of p25_control_demod.py:120 (rcf.p25.fm_gain).  It has
+ * the sign of the carrier's offset and is the value adjust_channel_offset (p25_control_demod.py:205-212) would scale.
+ * p == NULL switches the stage off.  It starts, with zero history, at the channel's next output (again on every call: a
+ * fresh ring and state, symbol 0 is the first of the call); applies from the next block on, on every channel kind that can
+ * carry a symbol filter (direct, chained, stage-2, filterbank tap -- a discriminator-only tap too: the stage reads no
+ * IQ); a retune keeps it, a second rcf_chan_fm_filter call keeps it, closing the channel releases it.  The slicer and the
+ * framing stay with the consumer.
+ * RCF_EINVAL: a parameter that is not finite, sample_rate / symbol_rate outside 2 .. 4096, spread_min or spread_max not
+ * 0 < spread_min <= 2 <= spread_max; RCF_ENOCHAN: no such channel; RCF_ESTATE: the channel has no symbol filter;
+ * RCF_ECAP: out_capacity < 16. */
+typedef struct rcf_fsk4_params {
+    double sample_rate, symbol_rate;    /* the channel's rate and 4800 (phase 1) or 6000 (phase 2): time = symbol_rate / sample_rate */
+    double k_spread, k_timing;          /* 0.01, 0.025 in op25 */
+    double k_fine, k_coarse;            /* 0.125, 0.00125 */
+    double spread_min, spread_max;      /* 1.6, 2.4: the distance of two levels stays within 20 % of the nominal 2 */
+    const float *interp_taps;           /* 129 x 8, row-major; NULL = rcf_design_mmse_interpolator(8, 128, 0.25) */
+    int reserved_;
+} rcf_fsk4_params_t;
+int rcf_chan_fsk4(rcf_t *h, int chan_id, const rcf_fsk4_params_t *p);
+/* the loop's state as of the last block; syncs the stream, like rcf_chan_costas_state.  RCF_ESTATE without the stage
+ * (here and in the two calls below) */
+typedef struct rcf_fsk4_state {
+    int64_t n_symbols, n_slips; /* soft symbols produced since the stage was (last) attached, times the guard fired */
+    double clock, spread, fine, coarse;
+} rcf_fsk4_state_t;
+int rcf_chan_fsk4_state(rcf_t *h, int chan_id, rcf_fsk4_state_t *out);
+/* unread soft symbols (float32), oldest first */
+int64_t rcf_chan_read_fsk4(rcf_t *h, int chan_id, float *out, size_t max_symbols);
+/* device pointer of the soft-symbol ring and its capacity (zero-copy, like rcf_chan_rings): symbol k lives at index
+ * k & (capacity-1); rcf_chan_fsk4_state gives the count */
+int rcf_chan_fsk4_ring(rcf_t *h, int chan_id, void **sym_ring, size_t *capacity);
 /* drift probe of p25_control_demod.py:123-127: moving_average_ff(window, 1) * (1/window) of the
  * discriminator output (window = 10000 there) == mean of gain*fm over the last `window` samples; this is
  * the value demod_watcher hands to frontend_connector.report_offset */

@@ -160,6 +160,7 @@ void free_channel(rcf_t *h, Chan *c)
     drop_stage(h, c->agc);
     drop_stage(h, c->clock);
     drop_stage(h, c->costas);
+    drop_stage(h, c->fsk4);
     drop_stage(h, c->audio);
 }
 

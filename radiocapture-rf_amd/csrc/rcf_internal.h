@@ -303,6 +303,27 @@ struct CostasLaunch {
     int32_t pad_;
 };
 void launch_costas(const CostasLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
+// The C4FM symbol loop on a channel's symbol-filter ring (fsk4.hip; op25's fsk4_demod_ff, the back half of the P25 C4FM
+// demodulators, p25_control_demod.py:118-135; definition: include/rcf.h at rcf_chan_fsk4).
+// per-channel running state, device resident, owned by fsk4_kernel
+struct Fsk4State {
+    int64_t n_out;           // soft symbols written so far (symbol k at out_ring[k & ring_mask])
+    int64_t slips;           // times the guard fired
+    double clock, spread, fine, coarse;
+    float hist[kClockTaps];  // the last 8 inputs, newest last
+};
+struct Fsk4Launch {
+    const float *sym_ring;   // the symbol filter's output (rcf_chan_fm_filter)
+    float *out_ring;
+    Fsk4State *st;
+    const float *taps;       // the bank, row-major (device)
+    int64_t n_lo;            // first relative symbol-filter output that is new in this launch
+    int32_t n_k;
+    int32_t pad_;
+    double time;             // symbol_rate / sample_rate
+    double k_spread, k_timing, k_fine, k_coarse, spread_min, spread_max;
+};
+void launch_fsk4(const Fsk4Launch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
 // mean of gain * fm over the last `window` samples ending at n_end (exclusive), one workgroup
 void launch_fm_level(const float *fm_ring, int64_t n_end, int window, float gain, uint64_t ring_mask, float *d_out,
                      hipStream_t s);

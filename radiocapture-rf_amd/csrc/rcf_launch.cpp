@@ -38,6 +38,7 @@ void launch_tail(rcf_t *h, const TailRecs &r, hipStream_t st)
     if (r.agcf) { Timed t(h, RCF_T_DISC); launch_agc(r.agcf, r.n_agcf, r.agcf_max_n, r.agcf_max_ns, h->ring_mask, st); }
     if (r.clkf) { Timed t(h, RCF_T_CLOCK); launch_clock_mm(r.clkf, r.n_clkf, r.clkf_max_n, h->ring_mask, st); }
     if (r.gcf) { Timed t(h, RCF_T_COSTAS); launch_costas(r.gcf, r.n_gcf, r.gcf_max_n, h->ring_mask, st); }
+    if (r.f4f) { Timed t(h, RCF_T_FSK4); launch_fsk4(r.f4f, r.n_f4f, r.f4f_max_n, h->ring_mask, st); }
 }
 
 void launch_member_audio(rcf_t *h, const BlockPlan &bp, hipStream_t st)
@@ -130,7 +131,8 @@ int launch_plan(rcf_t *h, BlockPlan &bp)
     launch_tail(h, TailRecs{bp.disc_jobs.data(), bp.disc_jobs.size(), bp.d_symf, (int)bp.symf.size(), bp.symf_max_n,
                             bp.d_agcf, (int)bp.agcf.size(), bp.agcf_max_n, bp.agcf_max_ns,
                             bp.d_clkf, (int)bp.clkf.size(), bp.clkf_max_n,
-                            bp.d_gcf, (int)bp.gcf.size(), bp.gcf_max_n}, st);
+                            bp.d_gcf, (int)bp.gcf.size(), bp.gcf_max_n,
+                            bp.d_f4f, (int)bp.f4f.size(), bp.f4f_max_n}, st);
     launch_member_audio(h, bp, st);
     return RCF_OK;
 }

@@ -72,6 +72,7 @@ const rcf_t::PlanCache &plan_cache(rcf_t *h)
         if (c.agc) stage(sizeof(AgcLaunch), c.agc->reach());
         if (c.clock) stage(sizeof(ClockLaunch), c.clock->reach());
         if (c.costas) stage(sizeof(CostasLaunch), c.costas->reach());
+        if (c.fsk4) stage(sizeof(Fsk4Launch), c.fsk4->reach());
         if (c.audio) stage(sizeof(AudioLaunch), c.audio->reach(), true);
         pc.max_depth = std::max(pc.max_depth, c.depth);
         if (c.src < 0 && (pc.min_d0 == 0 || c.D < pc.min_d0)) pc.min_d0 = c.D;
@@ -212,7 +213,7 @@ int plan_pfb(rcf_t *h, BlockPlan &bp)
     return RCF_OK;
 }
 
-// one channel's launch records (FIR / tap, discriminator, symbol filter, AGC, symbol clock, Gardner / Costas loop, voice chain, exact rotator) and the advance of
+// one channel's launch records (FIR / tap, discriminator, symbol filter, AGC, symbol clock, Gardner / Costas loop, C4FM loop, voice chain, exact rotator) and the advance of
 // its state.  Returns RCF_OK also when the channel has nothing to do in this block.
 int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c, int D)
 {
@@ -364,6 +365,20 @@ int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c, int D)
         if (gl.n_k > 0) {
             bp.gcf.push_back(gl);
             bp.gcf_max_n = std::max(bp.gcf_max_n, (int)gl.n_k);
+        }
+    }
+    if (const Chan::Fsk4 *fk = c->fsk4.get()) {
+        Fsk4Launch fl{};
+        fl.sym_ring = c->sym->d_ring;                // (attached only behind a symbol filter, which is never taken away: rcf_stage.cpp)
+        fl.out_ring = fk->d_ring;
+        fl.st = fk->d_state;
+        fl.taps = fk->d_bank;
+        fl.n_k = since(std::max(fk->from, c->sym->from), &fl.n_lo);
+        fl.time = fk->time; fl.k_spread = fk->k_spread; fl.k_timing = fk->k_timing; fl.k_fine = fk->k_fine;
+        fl.k_coarse = fk->k_coarse; fl.spread_min = fk->spread_min; fl.spread_max = fk->spread_max;
+        if (fl.n_k > 0) {
+            bp.f4f.push_back(fl);
+            bp.f4f_max_n = std::max(bp.f4f_max_n, (int)fl.n_k);
         }
     }
     if (c->audio) {
@@ -644,13 +659,14 @@ int plan_tail(rcf_t *h, BlockPlan &bp)
         pl.tap_pitch = (int32_t)mat_pitch;
         pl.n_taps = (int32_t)tap_list.size();
     }
-    // (a group's block: the exact-rotator fills, the symbol filters, the AGCs, the symbol clocks and the Gardner / Costas loops of all members go out as
+    // (a group's block: the exact-rotator fills, the symbol filters, the AGCs, the symbol clocks, the Gardner / Costas loops and the C4FM loops of all members go out as
     // one launch each)
     if (!bp.defer && !rot_fills.empty() && !ar.put(rot_fills, &d_rot_fills)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
     if (!bp.defer && !symf.empty() && !ar.put(symf, &d_symf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
     if (!bp.defer && !agcf.empty() && !ar.put(agcf, &bp.d_agcf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
     if (!bp.defer && !bp.clkf.empty() && !ar.put(bp.clkf, &bp.d_clkf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
     if (!bp.defer && !bp.gcf.empty() && !ar.put(bp.gcf, &bp.d_gcf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
+    if (!bp.defer && !bp.f4f.empty() && !ar.put(bp.f4f, &bp.d_f4f)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
     if (!audf.empty() && !ar.put(audf, &d_audf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
     return RCF_OK;
 }

@@ -52,7 +52,7 @@ struct BlockPlan {
     // how far back every consumer of a ring reaches beyond the block's new samples (a block's writes must not
     // overwrite what the same block's readers still need): derived channels T - 1 + D of source output, the
     // discriminator one sample, the symbol filter its taps, the AGC N - 1 IQ samples, the symbol clock 7 of the
-    // discriminator's (the Gardner / Costas loop none: its history is in its state record).  Every ring reaches back 1 (the discriminator); only sources of other channels and channels with a
+    // discriminator's (the Gardner / Costas loop and the C4FM loop none: their history is in their state records).  Every ring reaches back 1 (the discriminator); only sources of other channels and channels with a
     // symbol filter, an AGC or a symbol clock reach further -- the
     // map holds just those (with 131072 plain wideband channels it stays empty: a std::map entry per channel and block
     // was a tenth of the host's schedule time).
@@ -76,6 +76,8 @@ struct BlockPlan {
     int clkf_max_n = 0;
     std::vector<CostasLaunch> gcf;     // Gardner / Costas loops, all channels in one launch
     int gcf_max_n = 0;
+    std::vector<Fsk4Launch> f4f;       // C4FM symbol loops, all channels in one launch
+    int f4f_max_n = 0;
     std::vector<RotFill> rot_fills;    // exact rotator: one record per launched channel, one launch before the FIRs
     std::vector<TapLaunch> tap_list;   // filterbank taps: copied out by the bank's kernel, finished by tap_finalize
     std::vector<int32_t> tap_bins;
@@ -96,6 +98,7 @@ struct BlockPlan {
     const AgcLaunch *d_agcf = nullptr;
     const ClockLaunch *d_clkf = nullptr;
     const CostasLaunch *d_gcf = nullptr;
+    const Fsk4Launch *d_f4f = nullptr;
     const AudioLaunch *d_audf = nullptr;
     bool defer = false;                // a member of a group: mergeable records stay on the host (FirJob::host, DiscJob::host)
     bool history_done = false;         // launch_plan copied the history tail together with the launch records
@@ -153,12 +156,13 @@ int launch_plan(rcf_t *h, BlockPlan &bp);
 struct UploadSpan { size_t from, bytes; };             // the arena bytes [base, used) as the 64-byte blocks that hold them
 UploadSpan arena_upload_span(size_t base, size_t used);
 void launch_fir_job(rcf_t *h, FirJob &j, int timing_class, hipStream_t st);   // an unmerged FIR job, its repack first
-struct TailRecs {                                      // what follows the derived FIRs, timed as RCF_T_DISC (the clocks: RCF_T_CLOCK, RCF_T_COSTAS)
+struct TailRecs {                                      // what follows the derived FIRs, timed as RCF_T_DISC (the loops: RCF_T_CLOCK, RCF_T_COSTAS, RCF_T_FSK4)
     const DiscJob *disc; size_t n_disc;                // one discriminator launch per job
     const FmFirLaunch *symf; int n_symf, symf_max_n;
     const AgcLaunch *agcf; int n_agcf, agcf_max_n, agcf_max_ns;
     const ClockLaunch *clkf; int n_clkf, clkf_max_n;   // behind the discriminators: they read the rings those wrote
     const CostasLaunch *gcf; int n_gcf, gcf_max_n;     // behind the AGCs: they read the AGC rings
+    const Fsk4Launch *f4f; int n_f4f, f4f_max_n;       // behind the symbol filters: they read the symbol-filter rings
 };
 void launch_tail(rcf_t *h, const TailRecs &t, hipStream_t st);
 void launch_member_audio(rcf_t *h, const BlockPlan &bp, hipStream_t st);

@@ -1,4 +1,4 @@
-// rcf_read.cpp -- the stream table of a channel (chan_stream: seven streams, one row each) and the one read path of every
+// rcf_read.cpp -- the stream table of a channel (chan_stream: eight streams, one row each) and the one read path of every
 // host read (host_read: one gather launch, one synchronisation), with the read and ring entry points of the C ABI.
 #include <atomic>
 
@@ -15,7 +15,8 @@ static int stream_row(rcf_t *h, Chan *c, int kind, StreamRow *r)
     Chan::Clock *ck = c->clock.get();
     Chan::Audio *au = c->audio.get();
     Chan::Costas *gc = c->costas.get();
-    const StreamRow t[7] = {
+    Chan::Fsk4 *fk = c->fsk4.get();
+    const StreamRow t[8] = {
         {c->fm_only ? nullptr : c->d_iq, 2, &c->rd_iq, "channel %d exposes its discriminator only (rcf_chan_set_fm_only)"},
         {c->d_fm, 1, &c->rd_fm, "channel %d has no discriminator ring"},
         {ag ? ag->d_ring : nullptr, 2, ag ? &ag->rd : nullptr, "channel %d has no AGC"},
@@ -23,6 +24,7 @@ static int stream_row(rcf_t *h, Chan *c, int kind, StreamRow *r)
         {ck ? ck->d_ring : nullptr, 1, ck ? &ck->rd : nullptr, "channel %d has no symbol clock"},
         {au ? au->d_rings + 3 * h->out_cap : nullptr, 1, au ? &au->rd : nullptr, "channel %d has no audio chain"},
         {gc ? gc->d_ring : nullptr, 1, gc ? &gc->rd : nullptr, "channel %d has no Gardner / Costas stage"},
+        {fk ? fk->d_ring : nullptr, 1, fk ? &fk->rd : nullptr, "channel %d has no C4FM symbol loop (rcf_chan_fsk4)"},
     };
     if (!t[kind].ring) { set_error(t[kind].refusal, c->id); return RCF_ESTATE; }
     *r = t[kind];
@@ -51,6 +53,11 @@ int chan_stream(rcf_t *h, Chan *c, int kind, RingStream *s, int64_t *aux)
     } else if (kind == kReadCostas) {
         CostasState st{};                            // (the counters at its front, not the history behind them)
         if ((rc = stage_state(h, c->costas->d_state, &st, offsetof(CostasState, hist))) != RCF_OK) return rc;
+        end = st.n_out;
+        beside = st.slips;
+    } else if (kind == kReadFsk4) {
+        Fsk4State st{};
+        if ((rc = stage_state(h, c->fsk4->d_state, &st, offsetof(Fsk4State, hist))) != RCF_OK) return rc;
         end = st.n_out;
         beside = st.slips;
     } else if (kind == kReadAudio) {
@@ -188,6 +195,7 @@ int64_t rcf_chan_read_sym(rcf_t *h, int chan_id, float *out, size_t n) { return 
 int64_t rcf_chan_read_agc(rcf_t *h, int chan_id, float *out, size_t n) { return chan_read_one(h, chan_id, RCF_READ_AGC, 1.0f, out, n); }
 int64_t rcf_chan_read_clock(rcf_t *h, int chan_id, float *out, size_t n) { return chan_read_one(h, chan_id, kReadClock, 1.0f, out, n); }
 int64_t rcf_chan_read_costas(rcf_t *h, int chan_id, float *out, size_t n) { return chan_read_one(h, chan_id, kReadCostas, 1.0f, out, n); }
+int64_t rcf_chan_read_fsk4(rcf_t *h, int chan_id, float *out, size_t n) { return chan_read_one(h, chan_id, kReadFsk4, 1.0f, out, n); }
 int64_t rcf_chan_read_audio(rcf_t *h, int chan_id, float *out, size_t n) { return chan_read_one(h, chan_id, kReadAudio, 1.0f, out, n); }
 
 int rcf_chan_read_many(rcf_t *h, int what, const int *chan_ids, int n_chans, float gain, void *out, size_t cap_each,
@@ -225,5 +233,6 @@ int rcf_chan_rings(rcf_t *h, int chan_id, void **iq_ring, void **fm_ring, size_t
 int rcf_chan_agc_ring(rcf_t *h, int chan_id, void **agc_ring, size_t *capacity) { return chan_rings(h, chan_id, RCF_READ_AGC, true, agc_ring, nullptr, capacity); }
 int rcf_chan_clock_ring(rcf_t *h, int chan_id, void **sym_ring, size_t *capacity) { return chan_rings(h, chan_id, kReadClock, true, sym_ring, nullptr, capacity); }
 int rcf_chan_costas_ring(rcf_t *h, int chan_id, void **sym_ring, size_t *capacity) { return chan_rings(h, chan_id, kReadCostas, true, sym_ring, nullptr, capacity); }
+int rcf_chan_fsk4_ring(rcf_t *h, int chan_id, void **sym_ring, size_t *capacity) { return chan_rings(h, chan_id, kReadFsk4, true, sym_ring, nullptr, capacity); }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // rcf_stage.cpp -- the optional stages behind a channel's rings (the records of Chan, rcf_state.h): the P25 symbol filter,
-// the feed-forward AGC, the SmartNet / EDACS symbol clock, the P25 CQPSK Gardner / Costas loop and the analog voice chain.
+// the feed-forward AGC, the SmartNet / EDACS symbol clock, the P25 CQPSK Gardner / Costas loop, the P25 C4FM symbol loop and
+// the analog voice chain.
 // Attach, off, and what they produced.
 // An attach function allocates into Fresh<> holders and builds the new record completely; only then is it swapped into
 // the channel and the old one released.  A HIP call that fails before that leaves the channel as it was.
@@ -11,6 +12,7 @@ void Chan::Sym::release(rcf_t *h) { bury(h, d_ring); bury(h, d_taps); d_ring = d
 void Chan::Agc::release(rcf_t *h) { bury(h, d_ring); d_ring = nullptr; }
 void Chan::Clock::release(rcf_t *h) { bury(h, d_ring); d_ring = nullptr; d_state = nullptr; d_bank = nullptr; }   // one allocation
 void Chan::Costas::release(rcf_t *h) { bury(h, d_ring); d_ring = nullptr; d_state = nullptr; d_bank = nullptr; }  // one allocation
+void Chan::Fsk4::release(rcf_t *h) { bury(h, d_ring); d_ring = nullptr; d_state = nullptr; d_bank = nullptr; }    // one allocation
 void Chan::Audio::release(rcf_t *h) { bury(h, d_state); bury(h, d_rings); bury(h, d_taps); d_state = nullptr; d_rings = d_taps = nullptr; }
 
 }  // namespace rcfx
@@ -71,7 +73,7 @@ int rcf_chan_agc(rcf_t *h, int chan_id, int nsamples, float reference)
     return RCF_OK;
 }
 
-// the interpolator bank the symbol clocks and the Gardner / Costas loops share unless the caller brings one: built at first use
+// the interpolator bank the symbol clocks, the Gardner / Costas loops and the C4FM loops share unless the caller brings one: built at first use
 static int default_bank(rcf_t *h)
 {
     if (h->d_mmse) return RCF_OK;
@@ -199,6 +201,71 @@ int rcf_chan_costas_state(rcf_t *h, int chan_id, rcf_costas_state_t *out)
     RCF_HIP(hipStreamSynchronize(h->stream));
     out->n_symbols = st.n_out; out->n_slips = st.slips;
     out->mu = st.mu; out->omega = st.omega; out->freq = st.freq; out->phase = st.phase;
+    return RCF_OK;
+}
+
+// ---- op25 fsk4_demod_ff behind the symbol filter (fsk4.hip)
+int rcf_chan_fsk4(rcf_t *h, int chan_id, const rcf_fsk4_params_t *p)
+{
+    if (!h) return RCF_EINVAL;
+    if (p) {
+        const double v[8] = {p->sample_rate, p->symbol_rate, p->k_spread, p->k_timing, p->k_fine, p->k_coarse, p->spread_min, p->spread_max};
+        for (double x : v)
+            if (!std::isfinite(x)) { set_error("C4FM loop: non-finite parameter"); return RCF_EINVAL; }
+        const double sps = p->sample_rate / p->symbol_rate;
+        if (!(sps >= 2.0 && sps <= 4096.0) || !(p->spread_min > 0.0 && p->spread_min <= 2.0 && p->spread_max >= 2.0)) {
+            set_error("C4FM loop: sample_rate %g / symbol_rate %g outside 2 .. 4096, or not 0 < spread_min %g <= 2 <= spread_max %g",
+                      p->sample_rate, p->symbol_rate, p->spread_min, p->spread_max);
+            return RCF_EINVAL;
+        }
+    }
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!p) {                           // off
+        if (c->fsk4) { drop_stage(h, c->fsk4); ++h->chans_epoch; }
+        return RCF_OK;
+    }
+    if (!c->sym) { set_error("channel %d has no symbol filter (rcf_chan_fm_filter) for the C4FM loop to read", chan_id); return RCF_ESTATE; }
+    if (h->out_cap < 16) { set_error("ring of %zu too small for the C4FM loop", h->out_cap); return RCF_ECAP; }
+    constexpr size_t kBank = (size_t)(kClockSteps + 1) * kClockTaps;
+    if (!p->interp_taps) { const int rc = default_bank(h); if (rc != RCF_OK) return rc; }
+    // every call is a new block: a fresh ring and state (symbol 0 is the first of this call), zero history
+    constexpr size_t kStateFloats = (sizeof(Fsk4State) + 255) / 256 * 256 / sizeof(float);
+    const size_t state_at = (h->out_cap + 1) / 2 * 2, bank_at = state_at + kStateFloats;     // in floats; the record's doubles 8-byte aligned
+    Fresh<float> fresh;
+    RCF_HIP(fresh.alloc(bank_at + (p->interp_taps ? kBank : 0)));
+    std::unique_ptr<Chan::Fsk4> k(new Chan::Fsk4);
+    k->time = p->symbol_rate / p->sample_rate;
+    k->k_spread = p->k_spread; k->k_timing = p->k_timing; k->k_fine = p->k_fine; k->k_coarse = p->k_coarse;
+    k->spread_min = p->spread_min; k->spread_max = p->spread_max;
+    Fsk4State st0{};
+    st0.spread = 2.0;
+    if (!hip_ok(hipMemcpy(fresh.p + state_at, &st0, sizeof(st0), hipMemcpyHostToDevice), "hipMemcpy(C4FM loop state)") ||
+        (p->interp_taps && !hip_ok(hipMemcpy(fresh.p + bank_at, p->interp_taps, sizeof(float) * kBank, hipMemcpyHostToDevice), "hipMemcpy(interpolator bank)")))
+        return RCF_EHIP;
+    k->d_ring = fresh.take();
+    k->d_state = reinterpret_cast<Fsk4State *>(k->d_ring + state_at);
+    k->d_bank = p->interp_taps ? k->d_ring + bank_at : h->d_mmse;
+    k->from = c->produced;
+    drop_stage(h, c->fsk4);
+    c->fsk4 = std::move(k);
+    ++h->chans_epoch;
+    return RCF_OK;
+}
+
+int rcf_chan_fsk4_state(rcf_t *h, int chan_id, rcf_fsk4_state_t *out)
+{
+    if (!h || !out) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!c->fsk4) { set_error("channel %d has no C4FM symbol loop (rcf_chan_fsk4)", chan_id); return RCF_ESTATE; }
+    Fsk4State st{};
+    RCF_HIP(hipMemcpyAsync(&st, c->fsk4->d_state, offsetof(Fsk4State, hist), hipMemcpyDeviceToHost, h->stream));
+    RCF_HIP(hipStreamSynchronize(h->stream));
+    out->n_symbols = st.n_out; out->n_slips = st.slips;
+    out->clock = st.clock; out->spread = st.spread; out->fine = st.fine; out->coarse = st.coarse;
     return RCF_OK;
 }
 

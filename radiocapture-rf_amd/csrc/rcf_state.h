@@ -3,7 +3,7 @@
 //   rcf_handle.cpp   open / close / sync, pools, wideband ingest        rcf_plan.cpp    the per-block schedule (host)
 //   rcf_launch.cpp   the block's launches in dependency order           rcf_chan.cpp    channels: lifecycle, taps, queries
 //   rcf_stage.cpp    a channel's optional stages: symbol filter, AGC,   rcf_read.cpp    the stream table of a channel and the
-//                    symbol clocks, voice chain (attach / off / counts)                 one read path of every host read
+//                    symbol loops, voice chain (attach / off / counts)                  one read path of every host read
 //   rcf_bank.cpp     filterbank + scanner ABI                           rcf_timing.cpp  HIP-event timing
 //   rcf_comm.cpp     RCCL peak-list exchange                            rcf_group.cpp   grouped launches over front-ends
 #pragma once
@@ -85,6 +85,7 @@ struct Chan {
     //   AGC           (rcf_chan_agc)           kept                  `produced`   `produced`
     //   symbol clock  (rcf_chan_clock_mm)      new ring and state    `produced`   0
     //   Gardner/Costas (rcf_chan_costas)       new ring and state    `produced`   0
+    //   C4FM loop     (rcf_chan_fsk4)          new ring and state    `produced`   0
     //   voice chain   (rcf_chan_audio_open)    new                   `produced`   0
     // `from`: the first relative channel output the stage is defined for (a new GR block: zero history before it); `rd`:
     // items handed to the stage's reader; reach(): how far behind a block's first output the stage reads the channel's
@@ -126,6 +127,15 @@ struct Chan {
         size_t reach() const { return 0; }                               // the history is in the state record: no look-back
         void release(rcf_t *h);
     };
+    struct Fsk4 {                       // the C4FM symbol loop over the symbol-filter ring (P25 C4FM back half)
+        float *d_ring = nullptr;        // one allocation: soft-symbol ring of out_cap floats | Fsk4State | the caller's bank, if any
+        Fsk4State *d_state = nullptr;
+        const float *d_bank = nullptr;  // the caller's (inside d_ring's allocation) or rcf::d_mmse
+        double time = 0, k_spread = 0, k_timing = 0, k_fine = 0, k_coarse = 0, spread_min = 0, spread_max = 0;
+        int64_t from = 0, rd = 0;
+        size_t reach() const { return 0; }                               // the history is in the state record: no look-back
+        void release(rcf_t *h);
+    };
     struct Audio {                      // the analog voice chain
         AudioState *d_state = nullptr;
         float *d_rings = nullptr;       // a | l | h | o | c (cf32), out_cap samples each
@@ -141,6 +151,7 @@ struct Chan {
     std::unique_ptr<Agc> agc;
     std::unique_ptr<Clock> clock;
     std::unique_ptr<Costas> costas;
+    std::unique_ptr<Fsk4> fsk4;
     std::unique_ptr<Audio> audio;
     // ---- the rest
     float incr[2] = {1.f, 0.f};   // exact rotator: what GNU Radio iterates
@@ -237,7 +248,7 @@ struct rcf {
     double shift_hz = 0;          // accumulated rcf_source_shift
     float *d_atan = nullptr;
     float *d_level = nullptr;     // rcf_chan_fm_level result
-    float *d_mmse = nullptr;      // rcf_design_mmse_interpolator(8, 128, 0.25): the default bank of the symbol clocks and the Gardner / Costas loops, built at first use
+    float *d_mmse = nullptr;      // rcf_design_mmse_interpolator(8, 128, 0.25): the default bank of the symbol clocks, the Gardner / Costas and the C4FM loops, built at first use
     void *d_raw = nullptr;        // wire-format staging (rcf_push_raw), block_cap * 4 bytes, lazily allocated
     // launch-parameter arenas (pinned host + device), double buffered
     rcfx::ArenaSet arenas;
@@ -256,7 +267,7 @@ struct rcf {
     hipStream_t own_stream = nullptr;
     std::map<int, std::unique_ptr<Chan>> chans;
     uint64_t chans_epoch = 0;     // bumped whenever a channel is opened or closed or gains / loses a symbol filter, AGC,
-                                  // symbol clock, Gardner / Costas loop or voice chain (cached Chan pointers: the pump's; the cached arena need below)
+                                  // symbol clock, Gardner / Costas loop, C4FM loop or voice chain (cached Chan pointers: the pump's; the cached arena need below)
     // What planning a block needs to know about the channel SET (not their counters), valid while epoch == chans_epoch:
     // the summary plan_arena() used to rebuild from a walk over every channel, and the (depth, D, T) classes plan_block()
     // used to re-bucket -- three passes of pointer chasing per block (20 us of a 30 us plan for a front-end with 256
@@ -413,10 +424,10 @@ struct RingStream {
     int64_t *cursor = nullptr;
 };
 // the stages' streams: single reads only (the batched ABIs and the pump take RCF_READ_IQ / FM / AGC)
-constexpr int kReadSym = 3, kReadClock = 4, kReadAudio = 5, kReadCostas = 6;
-// The stream table of a channel: c's stream `kind` (RCF_READ_IQ / FM / AGC, kReadSym / Clock / Audio / Costas), or RCF_ESTATE with
+constexpr int kReadSym = 3, kReadClock = 4, kReadAudio = 5, kReadCostas = 6, kReadFsk4 = 7;
+// The stream table of a channel: c's stream `kind` (RCF_READ_IQ / FM / AGC, kReadSym / Clock / Audio / Costas / Fsk4), or RCF_ESTATE with
 // the refusal's message (IQ of a discriminator-only tap, a stage the channel does not carry).  The first four end at
-// c->produced.  The clock's, the voice chain's and the Gardner / Costas loop's end at their stage's device counter: one
+// c->produced.  The clock's, the voice chain's, the Gardner / Costas loop's and the C4FM loop's end at their stage's device counter: one
 // asynchronous copy and one synchronisation of the stream (RCF_EHIP); *aux, if given, takes the counter beside it (the
 // loops' slips, the samples that passed the voice chain's squelch).
 int chan_stream(rcf_t *h, Chan *c, int kind, RingStream *s, int64_t *aux = nullptr);

@@ -36,6 +36,7 @@ SYMBOLS = [
     "rcf_chan_agc", "rcf_chan_read_agc", "rcf_chan_agc_ring",
     "rcf_chan_clock_mm", "rcf_chan_clock_produced", "rcf_chan_read_clock", "rcf_chan_clock_ring", "rcf_design_mmse_interpolator",
     "rcf_chan_costas", "rcf_chan_costas_state", "rcf_chan_read_costas", "rcf_chan_costas_ring",
+    "rcf_chan_fsk4", "rcf_chan_fsk4_state", "rcf_chan_read_fsk4", "rcf_chan_fsk4_ring",
     "rcf_design_firdes", "rcf_design_optfir_low_pass", "rcf_design_fm_deemph", "rcf_design_resampler", "rcf_chan_audio_open",
     "rcf_chan_audio_close", "rcf_chan_audio_produced", "rcf_chan_read_audio",
     "rcf_host_alloc", "rcf_host_free", "rcf_comm_unique_id", "rcf_comm_init", "rcf_comm_destroy", "rcf_comm_size",
@@ -46,7 +47,7 @@ SYMBOLS = [
 ]
 FMT_CF32, FMT_U8, FMT_S8, FMT_S16 = 0, 1, 2, 3
 READ_IQ, READ_FM, READ_AGC = 0, 1, 2
-T_FIR, T_PFB, T_FIR_DERIVED, T_DISC, T_SCAN_FFT, T_SCAN_MOVSUM, T_HISTORY, T_FIR_MFMA, T_AUDIO, T_TAPS, T_CLOCK, T_COSTAS = range(12)
+T_FIR, T_PFB, T_FIR_DERIVED, T_DISC, T_SCAN_FFT, T_SCAN_MOVSUM, T_HISTORY, T_FIR_MFMA, T_AUDIO, T_TAPS, T_CLOCK, T_COSTAS, T_FSK4 = range(13)
 
 
 class AudioParams(C.Structure):
@@ -83,6 +84,33 @@ def costas_params_struct(omega, gain_mu, gain_omega, alpha, beta, max_freq, omeg
     p = CostasParams()
     p.omega, p.gain_mu, p.gain_omega, p.alpha = float(omega), float(gain_mu), float(gain_omega), float(alpha)
     p.beta, p.max_freq, p.omega_limit = float(beta), float(max_freq), float(omega_limit)
+    taps = None
+    if interp_taps is not None:
+        taps = np.ascontiguousarray(interp_taps, dtype=np.float32)
+        if taps.shape != (129, 8):
+            raise ValueError("interp_taps must be a [129, 8] array")
+        p.interp_taps = taps.ctypes.data_as(C.POINTER(C.c_float))
+    return p, taps
+
+
+class Fsk4Params(C.Structure):
+    """rcf_fsk4_params_t (include/rcf.h)"""
+    _fields_ = [("sample_rate", C.c_double), ("symbol_rate", C.c_double), ("k_spread", C.c_double), ("k_timing", C.c_double),
+                ("k_fine", C.c_double), ("k_coarse", C.c_double), ("spread_min", C.c_double), ("spread_max", C.c_double),
+                ("interp_taps", C.POINTER(C.c_float)), ("reserved_", C.c_int)]
+
+
+class Fsk4State(C.Structure):
+    """rcf_fsk4_state_t (include/rcf.h)"""
+    _fields_ = [("n_symbols", C.c_int64), ("n_slips", C.c_int64), ("clock", C.c_double), ("spread", C.c_double),
+                ("fine", C.c_double), ("coarse", C.c_double)]
+
+
+def fsk4_params_struct(sample_rate, symbol_rate, k_spread, k_timing, k_fine, k_coarse, spread_min, spread_max, interp_taps=None):
+    """-> (Fsk4Params, the array its interp_taps points into or None: keep it while the struct is in use)"""
+    p = Fsk4Params()
+    p.sample_rate, p.symbol_rate, p.k_spread, p.k_timing = float(sample_rate), float(symbol_rate), float(k_spread), float(k_timing)
+    p.k_fine, p.k_coarse, p.spread_min, p.spread_max = float(k_fine), float(k_coarse), float(spread_min), float(spread_max)
     taps = None
     if interp_taps is not None:
         taps = np.ascontiguousarray(interp_taps, dtype=np.float32)
@@ -170,6 +198,10 @@ def lib():
         "rcf_chan_costas_state": (C.c_int, [vp, C.c_int, C.POINTER(CostasState)]),
         "rcf_chan_read_costas": (i64, [vp, C.c_int, fp, sz]),
         "rcf_chan_costas_ring": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]),
+        "rcf_chan_fsk4": (C.c_int, [vp, C.c_int, C.POINTER(Fsk4Params)]),
+        "rcf_chan_fsk4_state": (C.c_int, [vp, C.c_int, C.POINTER(Fsk4State)]),
+        "rcf_chan_read_fsk4": (i64, [vp, C.c_int, fp, sz]),
+        "rcf_chan_fsk4_ring": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]),
         "rcf_design_mmse_interpolator": (C.c_int, [C.c_int, C.c_int, C.c_double, fp, C.c_int]),
         "rcf_chan_fm_level": (C.c_int, [vp, C.c_int, C.c_float, C.c_int, fp]),
         "rcf_design_firdes": (C.c_int, [C.c_int] + [C.c_double] * 4 + [C.c_int, C.c_double, fp, C.c_int]),
@@ -738,6 +770,39 @@ class Frontend:
         """(device pointer, capacity) of the stage's float32 soft-symbol ring (rcf_chan_costas_ring)"""
         p, cap = C.c_void_p(), C.c_size_t()
         _check(lib().rcf_chan_costas_ring(self._h, cid, C.byref(p), C.byref(cap)))
+        return p.value, cap.value
+
+    def chan_fsk4(self, cid, sample_rate, symbol_rate=4800.0, k_spread=0.01, k_timing=0.025, k_fine=0.125, k_coarse=0.00125,
+                  spread_min=1.6, spread_max=2.4, interp_taps=None):
+        """op25's fsk4_demod_ff(queue, sample_rate, symbol_rate) on the channel's symbol-filter ring (rcf_chan_fsk4, which
+        defines the stage: unpinned against op25; p25_control_demod.py:118-135), starting with zero history at the
+        channel's next output; sample_rate=None switches it off.  The channel must carry a symbol filter
+        (chan_fm_filter).  interp_taps: a [129, 8] interpolator bank; None = design_mmse_interpolator()"""
+        if sample_rate is None:
+            _check(lib().rcf_chan_fsk4(self._h, cid, None))
+            return
+        p, _keep = fsk4_params_struct(sample_rate, symbol_rate, k_spread, k_timing, k_fine, k_coarse, spread_min, spread_max,
+                                      interp_taps)
+        _check(lib().rcf_chan_fsk4(self._h, cid, C.byref(p)))
+
+    def chan_fsk4_state(self, cid) -> dict:
+        """the loop's state as of the last block: n_symbols, n_slips, clock, spread, fine, coarse (the slow average of the
+        level offset, of the carrier offset's sign: what op25 posts to its autotune queue) (rcf_chan_fsk4_state; syncs
+        the stream)"""
+        st = Fsk4State()
+        _check(lib().rcf_chan_fsk4_state(self._h, cid, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in Fsk4State._fields_}
+
+    def chan_read_fsk4(self, cid, max_symbols=1 << 20) -> np.ndarray:
+        """unread soft symbols of the channel's C4FM loop (+-1, +-3 on a locked signal), oldest first"""
+        out = np.empty(max_symbols, dtype=np.float32)
+        n = _check(lib().rcf_chan_read_fsk4(self._h, cid, _fp(out), max_symbols))
+        return out[:n].copy()
+
+    def chan_fsk4_ring(self, cid):
+        """(device pointer, capacity) of the stage's float32 soft-symbol ring (rcf_chan_fsk4_ring)"""
+        p, cap = C.c_void_p(), C.c_size_t()
+        _check(lib().rcf_chan_fsk4_ring(self._h, cid, C.byref(p), C.byref(cap)))
         return p.value, cap.value
 
     def chan_fm_level(self, cid, gain, window=10000) -> float:

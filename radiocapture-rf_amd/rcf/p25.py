@@ -1,15 +1,16 @@
-"""The P25 control / voice demodulators' front halves behind a channel, built on the GPU (p25_control_demod.py:105-161,
-logging_receiver.py:278-332).  Both modulations start from the same pre-filter and split right after it:
+"""The P25 control / voice demodulators behind a channel, built on the GPU up to the slicer (p25_control_demod.py:105-183,
+logging_receiver.py:231-332).  Both modulations start from the same pre-filter and split right after it:
 
   C4FM   quadrature_demod_cf(channel_rate / (2 pi 600)) -> fir_filter_fff(1, (1/sps,)*sps) -> op25 fsk4_demod_ff
+         -> op25 fsk4_slicer_fb([-2, 0, 2, 4])
   CQPSK  multiply_const_cc(1.0) -> feedforward_agc_cc(1024, 1.0) -> multiply_const_cc(1.0) -> op25 gardner_costas_cc
          -> diff_phasor_cc -> complex_to_arg -> multiply_const_ff(4 / pi) -> op25 fsk4_slicer_fb([-2, 0, 2, 4])
 
-The C4FM half stops before the sequential op25 loop (fsk4_demod_ff): a demod reads the symbol filter's output
-(chan_read_sym) and runs that loop itself.  The CQPSK chain runs on the GPU up to the slicer (cqpsk_demod): the
-Gardner / Costas loop is the stage rcf_chan_costas, which include/rcf.h defines from the published algorithm -- op25's
-source is not in the reference tree, so the stage is unpinned against op25 --, and a demod reads soft dibits at the
-symbol rate (chan_read_costas) and slices them (slice_dibits)."""
+Both chains run on the GPU up to the slicer (c4fm_demod, cqpsk_demod).  The two sequential op25 loops are the stages
+rcf_chan_fsk4 (fsk4_demod_ff) and rcf_chan_costas (gardner_costas_cc ... multiply_const_ff), which include/rcf.h defines
+from the published algorithms -- op25's source is not in the reference tree, so both stages are unpinned against op25 --,
+and a demod reads soft dibits at the symbol rate (chan_read_fsk4, chan_read_costas) and slices them (slice_dibits).  A
+consumer that runs op25's own loop reads the front half's output instead (chan_read_sym, chan_read_agc)."""
 import math
 
 import numpy as np
@@ -77,10 +78,26 @@ def slice_dibits(soft, levels=(-2.0, 0.0, 2.0, 4.0)):
 
 def c4fm_front_half(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE):
     """the C4FM front half on channel `chan_id` of Frontend `fe`: the chained pre-filter, its discriminator and the
-    boxcar symbol filter (p25_control_demod.py:118-133).  Returns the pre-filter channel's id: chan_read_sym on it gives
+    boxcar symbol filter (p25_control_demod.py:118-135).  Returns the pre-filter channel's id: chan_read_sym on it gives
     what fsk4_demod_ff consumes."""
     cid = _prefilter(fe, chan_id, channel_rate)
     fe.chan_fm_filter(cid, fm_gain(channel_rate), symbol_taps(channel_rate, symbol_rate))
+    return cid
+
+
+def fsk4_params(channel_rate, symbol_rate=SYMBOL_RATE):
+    """fsk4_demod_ff's arguments (p25_control_demod.py:135, logging_receiver.py:247: the rate 2 channel_rate and the symbol
+    rate) and op25's loop constants: keyword arguments of Frontend.chan_fsk4"""
+    return dict(sample_rate=2.0 * channel_rate, symbol_rate=float(symbol_rate), k_spread=0.01, k_timing=0.025, k_fine=0.125,
+                k_coarse=0.00125, spread_min=1.6, spread_max=2.4)
+
+
+def c4fm_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE):
+    """the whole C4FM chain up to the slicer on channel `chan_id` of Frontend `fe`: the front half, then the symbol loop
+    (p25_control_demod.py:118-135).  Returns the pre-filter channel's id: chan_read_fsk4 on it gives soft dibits at
+    symbol_rate (slice_dibits turns them into dibits), chan_fsk4_state its offset estimate (`coarse`)."""
+    cid = c4fm_front_half(fe, chan_id, channel_rate, symbol_rate)
+    fe.chan_fsk4(cid, **fsk4_params(channel_rate, symbol_rate))
     return cid
 
 
