@@ -22,35 +22,17 @@
 // chunk, carried over from the row's end after that).  Each lane then walks ITS row: a `for` over the chunk's samples --
 // the trip count is the block's, never the data's -- that produces a symbol when the window's last sample is the one it
 // stands on, at most one per sample.  Symbols go to the channel's ring as they are produced.
-// The bank sits in LDS, loaded once per workgroup, at a row pitch of 9 floats: a lane reads row imu, column 7 - j, with
-// imu varying from lane to lane, and ds_read_b32 banks on (address / 4) mod 32 -- at the natural pitch of 8 the 129 rows
-// fall on four bank offsets per column (an 8-way conflict on average), at 9 (odd) 32 consecutive rows cover all 32 banks.
-// Channels with a caller's bank of their own are walked in a pass of their own per distinct bank in the wave.
-#include "rcf_internal.h"
+// The bank sits in LDS, loaded once per workgroup, at a row pitch of 9 floats (loop_wave.hpp says why, and holds the wave's
+// scaffolding that costas.hip and fsk4.hip share).  Channels with a caller's bank of their own are walked in a pass of
+// their own per distinct bank in the wave.
+#include "loop_wave.hpp"
 
 namespace rcfx {
 
 namespace {
 
-constexpr int kChunk = 64;
 constexpr int kBack = kClockTaps - 1;                // samples of look-back in front of a chunk
 constexpr int kRow = kBack + kChunk;                 // 71: odd, spreads a column over the banks
-constexpr int kTapRow = kClockTaps + 1;              // 9: see above
-constexpr int kRows = kClockSteps + 1;
-
-__device__ __forceinline__ int rl32(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
-__device__ __forceinline__ long long rl64(long long v, int src)
-{
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, src);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)v >> 32), src);
-    return (long long)(((unsigned long long)hi << 32) | lo);
-}
-
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 __device__ __forceinline__ float slice(float x) { return x < 0.f ? -1.0f : 1.0f; }
 
@@ -91,21 +73,12 @@ __global__ __launch_bounds__(64) void clock_mm_kernel(const ClockLaunch *__restr
         }
         // the whole next chunk (one coalesced 256-byte load per channel) is in flight while the current one is walked
         float pre[64];
-        auto prefetch = [&](int i0) {
-#pragma unroll
-            for (int c = 0; c < 64; ++c) {
-                const int cc = c < nc ? c : nc - 1;
-                const float *src = reinterpret_cast<const float *>((uintptr_t)rl64(my_src, cc));
-                const int i = i0 + lane < rl32(my_nk, cc) ? i0 + lane : 0;
-                pre[c] = src[(uint64_t)(rl64(my_lo, cc) + i) & ring_mask];
-            }
-        };
-        prefetch(0);
+        prefetch_rows(pre, my_src, my_lo, my_nk, nc, 0, lane, ring_mask);
         for (int i0 = 0; i0 < max_nk; i0 += kChunk) {
 #pragma unroll
             for (int c = 0; c < 64; ++c) xs[c * kRow + kBack + lane] = pre[c];
             wave_lds_sync();
-            if (i0 + kChunk < max_nk) prefetch(i0 + kChunk);
+            if (i0 + kChunk < max_nk) prefetch_rows(pre, my_src, my_lo, my_nk, nc, i0 + kChunk, lane, ring_mask);
             const int n_here = min(kChunk, my_nk - i0);
             for (int i = 0; i < n_here; ++i) {
                 if (q != i0 + i) continue;
@@ -154,8 +127,7 @@ __global__ __launch_bounds__(64) void clock_mm_kernel(const ClockLaunch *__restr
 
 void launch_clock_mm(const ClockLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s)
 {
-    if (n_items <= 0 || max_n_k <= 0) return;
-    hipLaunchKernelGGL(clock_mm_kernel, dim3((n_items + 63) / 64), dim3(64), 0, s, d_items, n_items, ring_mask);
+    launch_loop(clock_mm_kernel, d_items, n_items, max_n_k, ring_mask, s);
 }
 
 }  // namespace rcfx

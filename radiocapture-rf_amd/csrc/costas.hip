@@ -24,33 +24,16 @@
 // the derotated history and both interpolator windows are plain row reads; the row's last 32 samples move to the front
 // for the next chunk, and come from / go to the state record at the launch's ends (no look-back into the AGC ring).  The
 // row pitch is 97 float2 (odd: ds_read_b64 banks on the float2 index mod 32, the lanes of a half-wave cover all 32), the
-// bank sits at a row pitch of 9 floats as in clock.hip, and channels with a caller's bank of their own are walked in a
+// bank sits at a row pitch of 9 floats (loop_wave.hpp), and channels with a caller's bank of their own are walked in a
 // pass of their own per distinct bank in the wave.
-#include "rcf_internal.h"
+#include "loop_wave.hpp"
 
 namespace rcfx {
 
 namespace {
 
-constexpr int kChunk = 64;
 constexpr int kBack = kCostasHist;                   // 32 columns of derotated history in front of a chunk
 constexpr int kRow = kBack + kChunk + 1;             // 97 float2: odd, spreads a column over the banks
-constexpr int kTapRow = kClockTaps + 1;              // 9: see clock.hip
-constexpr int kRows = kClockSteps + 1;
-
-__device__ __forceinline__ int rl32(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
-__device__ __forceinline__ long long rl64(long long v, int src)
-{
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, src);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)v >> 32), src);
-    return (long long)(((unsigned long long)hi << 32) | lo);
-}
-
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 __device__ __forceinline__ float mul(float a, float b) { return __fmul_rn(a, b); }
 __device__ __forceinline__ float add(float a, float b) { return __fadd_rn(a, b); }
@@ -203,8 +186,7 @@ __global__ __launch_bounds__(64) void costas_kernel(const CostasLaunch *__restri
 
 void launch_costas(const CostasLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s)
 {
-    if (n_items <= 0 || max_n_k <= 0) return;
-    hipLaunchKernelGGL(costas_kernel, dim3((n_items + 63) / 64), dim3(64), 0, s, d_items, n_items, ring_mask);
+    launch_loop(costas_kernel, d_items, n_items, max_n_k, ring_mask, s);
 }
 
 }  // namespace rcfx

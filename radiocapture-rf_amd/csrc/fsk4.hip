@@ -24,33 +24,16 @@
 // end at the sample the walk stands on.  Columns 0 .. 7 of a row are the 8 inputs before the chunk: they come from the
 // state record at the launch's start, from the row's end after every chunk, and go back to the record at the launch's end
 // (no look-back into the symbol-filter ring).  The row pitch is 73 floats (odd: a column spreads over the banks), the bank
-// sits at a row pitch of 9 floats as in clock.hip, and channels with a caller's bank of their own are walked in a pass of
+// sits at a row pitch of 9 floats (loop_wave.hpp), and channels with a caller's bank of their own are walked in a pass of
 // their own per distinct bank in the wave.
-#include "rcf_internal.h"
+#include "loop_wave.hpp"
 
 namespace rcfx {
 
 namespace {
 
-constexpr int kChunk = 64;
 constexpr int kBack = kClockTaps;                    // 8 columns of history in front of a chunk
 constexpr int kRow = kBack + kChunk + 1;             // 73 floats: odd, spreads a column over the banks
-constexpr int kTapRow = kClockTaps + 1;              // 9: see clock.hip
-constexpr int kRows = kClockSteps + 1;
-
-__device__ __forceinline__ int rl32(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
-__device__ __forceinline__ long long rl64(long long v, int src)
-{
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, src);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)v >> 32), src);
-    return (long long)(((unsigned long long)hi << 32) | lo);
-}
-
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 __device__ __forceinline__ double mul(double a, double b) { return __dmul_rn(a, b); }
 __device__ __forceinline__ double add(double a, double b) { return __dadd_rn(a, b); }
@@ -103,21 +86,12 @@ __global__ __launch_bounds__(64) void fsk4_kernel(const Fsk4Launch *__restrict__
         }
         // the whole next chunk (one coalesced 256-byte load per channel) is in flight while the current one is walked
         float pre[64];
-        auto prefetch = [&](int i0) {
-#pragma unroll
-            for (int c = 0; c < 64; ++c) {
-                const int cc = c < nc ? c : nc - 1;
-                const float *src = reinterpret_cast<const float *>((uintptr_t)rl64(my_src, cc));
-                const int i = i0 + lane < rl32(my_nk, cc) ? i0 + lane : 0;
-                pre[c] = src[(uint64_t)(rl64(my_lo, cc) + i) & ring_mask];
-            }
-        };
-        prefetch(0);
+        prefetch_rows(pre, my_src, my_lo, my_nk, nc, 0, lane, ring_mask);
         for (int i0 = 0; i0 < max_nk; i0 += kChunk) {
 #pragma unroll
             for (int c = 0; c < 64; ++c) xs[c * kRow + kBack + lane] = pre[c];
             wave_lds_sync();
-            if (i0 + kChunk < max_nk) prefetch(i0 + kChunk);
+            if (i0 + kChunk < max_nk) prefetch_rows(pre, my_src, my_lo, my_nk, nc, i0 + kChunk, lane, ring_mask);
             const int n_here = min(kChunk, max(my_nk - i0, 0));
             for (int i = 0; i < n_here; ++i) {
                 // 1, 2: the input is in the row already; h[0 .. 7] are the columns that end at it
@@ -177,8 +151,7 @@ __global__ __launch_bounds__(64) void fsk4_kernel(const Fsk4Launch *__restrict__
 
 void launch_fsk4(const Fsk4Launch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s)
 {
-    if (n_items <= 0 || max_n_k <= 0) return;
-    hipLaunchKernelGGL(fsk4_kernel, dim3((n_items + 63) / 64), dim3(64), 0, s, d_items, n_items, ring_mask);
+    launch_loop(fsk4_kernel, d_items, n_items, max_n_k, ring_mask, s);
 }
 
 }  // namespace rcfx

@@ -156,12 +156,7 @@ void free_channel(rcf_t *h, Chan *c)
     bury(h, c->d_ctaps, slice_round(sizeof(float2) * (size_t)c->T));
     bury(h, c->d_iq, slice_round(12 * h->out_cap));       // d_fm lives in the same slice
     bury(h, c->d_rot, slice_round(sizeof(float2) * h->out_cap + 256));
-    drop_stage(h, c->sym);
-    drop_stage(h, c->agc);
-    drop_stage(h, c->clock);
-    drop_stage(h, c->costas);
-    drop_stage(h, c->fsk4);
-    drop_stage(h, c->audio);
+    c->for_each_stage([h](auto &stage, size_t, bool) { drop_stage(h, stage); });
 }
 
 }  // namespace rcfx

@@ -11,7 +11,8 @@
 //   pfb_group_kernel_* / pfb5_group_kernel / pfbm_group_kernel   the chunks of every member of one bank shape   (pfb.hip, pfb5.hip, pfbm.hip)
 //   fir_small_kernel / fir_bank_kernel       stage-2 channels of all members of one (D, T) class (records concatenated)
 //   tap_finalize_group_kernel  the tapped bins of every member                               (tapfin.hip)
-//   disc / fm_fir / agc / clock_mm / costas / fsk4 / rot_fill   records concatenated
+//   disc / rot_fill, and the tail stages (TailStages, rcf_plan.h: fm_fir / agc / clock_mm / costas / fsk4)   records
+//                              concatenated: the group's table is the members' tables appended
 //   gather_rings_kernel        the read: new output of any channels of any members -> pinned host memory, one launch
 // What is not concatenable (matrix-core banks with their per-handle tap slabs, voice chains, scans, banks that still see
 // zero history) follows per member on the same stream, in dependency order.  The bits are those of the members run alone.
@@ -55,20 +56,10 @@ struct GroupBlock {
     const TapFinArgs *d_tap_args = nullptr;
     int tap_max_taps = 0, tap_max_rows = 0;
     std::vector<std::map<ShapeKey, MergedFir>> merged;   // per depth: (D, T, small, KT) -> the members' records of that class
-    DiscJob disc{nullptr, 0, 0, {}};           // the members' discriminator, symbol-filter, AGC, symbol-clock and rotator-fill records
-    std::vector<FmFirLaunch> symf;
-    std::vector<AgcLaunch> agcf;
-    std::vector<ClockLaunch> clkf;
-    std::vector<CostasLaunch> gcf;
-    std::vector<Fsk4Launch> f4f;
+    DiscJob disc;                              // the members' discriminator, tail-stage and rotator-fill records
+    TailStages tails;
     std::vector<RotFill> rots;
-    const FmFirLaunch *d_symf = nullptr;
-    const AgcLaunch *d_agcf = nullptr;
-    const ClockLaunch *d_clkf = nullptr;
-    const CostasLaunch *d_gcf = nullptr;
-    const Fsk4Launch *d_f4f = nullptr;
     const RotFill *d_rots = nullptr;
-    int symf_max_n = 0, agcf_max_n = 0, agcf_max_ns = 0, clkf_max_n = 0, gcf_max_n = 0, f4f_max_n = 0;
     std::vector<PrepRec> prep;                 // the ingest launch's records, kPrepMaxRecs per launch
     std::vector<uint32_t> prep_tiles;
     const PrepRec *prep_mapped = nullptr;
@@ -227,34 +218,15 @@ int merge_firs(GroupBlock &b)
     return RCF_OK;
 }
 
-// discriminators, symbol filters, AGCs, symbol clocks, Gardner / Costas loops, C4FM loops, exact-rotator fills: the
-// members' records one after the other
+// discriminators, tail stages (TailStages, rcf_plan.h), exact-rotator fills: the members' records one after the other
 int merge_tails(GroupBlock &b)
 {
     for (auto &bp : b.plans) {
-        for (DiscJob &dj : bp->disc_jobs) {
-            b.disc.host.insert(b.disc.host.end(), dj.host.begin(), dj.host.end());
-            b.disc.max_n = std::max(b.disc.max_n, dj.max_n);
-        }
-        b.symf.insert(b.symf.end(), bp->symf.begin(), bp->symf.end());
-        b.symf_max_n = std::max(b.symf_max_n, bp->symf_max_n);
-        b.agcf.insert(b.agcf.end(), bp->agcf.begin(), bp->agcf.end());
-        b.agcf_max_n = std::max(b.agcf_max_n, bp->agcf_max_n);
-        b.agcf_max_ns = std::max(b.agcf_max_ns, bp->agcf_max_ns);
-        b.clkf.insert(b.clkf.end(), bp->clkf.begin(), bp->clkf.end());
-        b.clkf_max_n = std::max(b.clkf_max_n, bp->clkf_max_n);
-        b.gcf.insert(b.gcf.end(), bp->gcf.begin(), bp->gcf.end());
-        b.gcf_max_n = std::max(b.gcf_max_n, bp->gcf_max_n);
-        b.f4f.insert(b.f4f.end(), bp->f4f.begin(), bp->f4f.end());
-        b.f4f_max_n = std::max(b.f4f_max_n, bp->f4f_max_n);
+        for (const DiscJob &dj : bp->disc_jobs) b.disc.append(dj);
+        b.tails.append(bp->tails);
         b.rots.insert(b.rots.end(), bp->rot_fills.begin(), bp->rot_fills.end());
     }
-    b.disc.n = (int)b.disc.host.size();
-    if ((b.disc.n && !b.ga.put(b.disc.host, &b.disc.dev)) || (!b.symf.empty() && !b.ga.put(b.symf, &b.d_symf)) ||
-        (!b.agcf.empty() && !b.ga.put(b.agcf, &b.d_agcf)) || (!b.clkf.empty() && !b.ga.put(b.clkf, &b.d_clkf)) ||
-        (!b.gcf.empty() && !b.ga.put(b.gcf, &b.d_gcf)) || (!b.f4f.empty() && !b.ga.put(b.f4f, &b.d_f4f)) ||
-        (!b.rots.empty() && !b.ga.put(b.rots, &b.d_rots)))
-        return oom();
+    if (!b.disc.upload(b.ga) || !b.tails.upload(b.ga) || (!b.rots.empty() && !b.ga.put(b.rots, &b.d_rots))) return oom();
     return RCF_OK;
 }
 
@@ -364,11 +336,7 @@ int launch_block(GroupBlock &b, bool wait)
         launch_tap_finalize_group(b.d_tap_args, (int)b.tap_args.size(), b.tap_max_taps, b.tap_max_rows, h0->ring_mask, h0->d_atan, st);
     }
     for (size_t d = 1; d < b.merged.size(); ++d) launch_fir_depth(b, d);
-    launch_tail(h0, TailRecs{&b.disc, b.disc.dev ? size_t(1) : 0, b.d_symf, (int)b.symf.size(), b.symf_max_n,
-                             b.d_agcf, (int)b.agcf.size(), b.agcf_max_n, b.agcf_max_ns,
-                             b.d_clkf, (int)b.clkf.size(), b.clkf_max_n,
-                             b.d_gcf, (int)b.gcf.size(), b.gcf_max_n,
-                             b.d_f4f, (int)b.f4f.size(), b.f4f_max_n}, st);
+    launch_tail(h0, &b.disc, b.disc.dev ? 1 : 0, b.tails, st);
     for (size_t i = 0; i < b.size(); ++i) {
         launch_member_audio(b.member(i), *b.plans[i], st);
         const int rs = run_scan(b.member(i), *b.plans[i]);

@@ -28,17 +28,28 @@ void launch_fir_job(rcf_t *h, FirJob &j, int timing_class, hipStream_t st)
     launch_fir_bank(j.dev, j.dims, st);
 }
 
-void launch_tail(rcf_t *h, const TailRecs &r, hipStream_t st)
+// a stage's launch by its launcher's signature: (records, count, largest n_k, ring mask, stream), the AGC's with its longest window
+template <class Rec>
+static void launch_stage(const StageRecs<Rec> &s, void (*launch)(const Rec *, int, int, uint64_t, hipStream_t), uint64_t ring_mask, hipStream_t st)
 {
-    for (size_t i = 0; i < r.n_disc; ++i) {
-        Timed t(h, RCF_T_DISC);
-        launch_discriminator(r.disc[i].dev, r.disc[i].n, r.disc[i].max_n, h->ring_mask, h->d_atan, st);
+    launch(s.dev, s.n(), s.max_n, ring_mask, st);
+}
+static void launch_stage(const AgcRecs &s, void (*launch)(const AgcLaunch *, int, int, int, uint64_t, hipStream_t), uint64_t ring_mask, hipStream_t st)
+{
+    launch(s.dev, s.n(), s.max_n, s.max_ns, ring_mask, st);
+}
+
+void launch_tail(rcf_t *h, const DiscJob *disc, size_t n_disc, const TailStages &t, hipStream_t st)
+{
+    for (size_t i = 0; i < n_disc; ++i) {
+        Timed tm(h, RCF_T_DISC);
+        launch_discriminator(disc[i].dev, disc[i].n(), disc[i].max_n, h->ring_mask, h->d_atan, st);
     }
-    if (r.symf) { Timed t(h, RCF_T_DISC); launch_fm_fir(r.symf, r.n_symf, r.symf_max_n, h->ring_mask, st); }
-    if (r.agcf) { Timed t(h, RCF_T_DISC); launch_agc(r.agcf, r.n_agcf, r.agcf_max_n, r.agcf_max_ns, h->ring_mask, st); }
-    if (r.clkf) { Timed t(h, RCF_T_CLOCK); launch_clock_mm(r.clkf, r.n_clkf, r.clkf_max_n, h->ring_mask, st); }
-    if (r.gcf) { Timed t(h, RCF_T_COSTAS); launch_costas(r.gcf, r.n_gcf, r.gcf_max_n, h->ring_mask, st); }
-    if (r.f4f) { Timed t(h, RCF_T_FSK4); launch_fsk4(r.f4f, r.n_f4f, r.f4f_max_n, h->ring_mask, st); }
+    TailStages::each([&](int timing_class, auto launch, const auto &s) {
+        if (!s.dev) return;
+        Timed tm(h, timing_class);
+        launch_stage(s, launch, h->ring_mask, st);
+    }, t);
 }
 
 void launch_member_audio(rcf_t *h, const BlockPlan &bp, hipStream_t st)
@@ -75,10 +86,11 @@ int launch_plan(rcf_t *h, BlockPlan &bp)
 
         h->lag.pending = false;
     }
-    // ... and this block's own: ONE small-T job on the bank's bins, nothing that consumes its outputs within the block
+    // ... and this block's own: ONE small-T job on the bank's bins, nothing that consumes its outputs within the block (a
+    // record of any tail stage, a voice chain: they read rings the lagged launch has not written)
     FirJob *lag_job = nullptr;
     if (h->lag_enabled && carry && fir_by_depth.size() == 2 && fir_by_depth[1].size() == 1 && fir_by_depth[1][0].dims.small &&
-        fir_by_depth[1][0].dev && fir_by_depth[1][0].bank_src && !bp.d_symf && !bp.d_agcf && !bp.d_clkf && !bp.d_audf &&
+        fir_by_depth[1][0].dev && fir_by_depth[1][0].bank_src && !bp.tails.any() && !bp.d_audf &&
         (size_t)pl.n_frames * 2 + pfb_reach <= h->out_cap)
         lag_job = &fir_by_depth[1][0];
     {
@@ -128,11 +140,7 @@ int launch_plan(rcf_t *h, BlockPlan &bp)
             Timed t(h, RCF_T_FIR_DERIVED);
             launch_fir_bank(j.dev, j.dims, st);
         }
-    launch_tail(h, TailRecs{bp.disc_jobs.data(), bp.disc_jobs.size(), bp.d_symf, (int)bp.symf.size(), bp.symf_max_n,
-                            bp.d_agcf, (int)bp.agcf.size(), bp.agcf_max_n, bp.agcf_max_ns,
-                            bp.d_clkf, (int)bp.clkf.size(), bp.clkf_max_n,
-                            bp.d_gcf, (int)bp.gcf.size(), bp.gcf_max_n,
-                            bp.d_f4f, (int)bp.f4f.size(), bp.f4f_max_n}, st);
+    launch_tail(h, bp.disc_jobs.data(), bp.disc_jobs.size(), bp.tails, st);
     launch_member_audio(h, bp, st);
     return RCF_OK;
 }

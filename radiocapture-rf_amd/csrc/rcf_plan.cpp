@@ -56,24 +56,20 @@ const rcf_t::PlanCache &plan_cache(rcf_t *h)
     // pointer chasing)
     size_t need = 4096, pfb_reach = 0, n_fir = 0;
     for (auto &kv : h->chans) {
-        const Chan &c = *kv.second;
+        Chan &c = *kv.second;
         // (a filterbank tap has one short record; a FIR channel up to two launch records -- matrix-core launch and
         // zero-history fix-up --, a discriminator record, an exact-rotator fill, its bank-matrix dirty flag)
         need += c.is_tap ? sizeof(TapLaunch) + 8 : 2 * sizeof(ChanLaunch) + sizeof(DiscLaunch) + sizeof(RotFill) + 12 + 128;
         n_fir += c.is_tap ? 0 : 1;
         // a stage: its launch record, and how far behind a block's first output it reads the channel's own rings (the voice
         // chain's reach is into its own rings: the widest window only)
-        auto stage = [&](size_t rec_bytes, size_t reach, bool own_rings = false) {
+        c.for_each_stage([&](const auto &stage, size_t rec_bytes, bool own_rings) {
+            if (!stage) return;
+            const size_t reach = stage->reach();
             need += rec_bytes;
             if (!own_rings) { size_t &own = pc.reach_x[c.id]; own = std::max(own, reach); }
             pc.max_reach = std::max(pc.max_reach, reach);
-        };
-        if (c.sym) stage(sizeof(FmFirLaunch), c.sym->reach());
-        if (c.agc) stage(sizeof(AgcLaunch), c.agc->reach());
-        if (c.clock) stage(sizeof(ClockLaunch), c.clock->reach());
-        if (c.costas) stage(sizeof(CostasLaunch), c.costas->reach());
-        if (c.fsk4) stage(sizeof(Fsk4Launch), c.fsk4->reach());
-        if (c.audio) stage(sizeof(AudioLaunch), c.audio->reach(), true);
+        });
         pc.max_depth = std::max(pc.max_depth, c.depth);
         if (c.src < 0 && (pc.min_d0 == 0 || c.D < pc.min_d0)) pc.min_d0 = c.D;
         if (c.src >= RCF_SRC_PFB_BIN0) {              // (the bank's ring: one entry for all of its consumers, set after the loop)
@@ -319,8 +315,7 @@ int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c, int D)
         fl.ntaps = sy->ntaps;
         fl.n_first = sy->from;
         fl.n_k = since(sy->from, &fl.n_lo);
-        if (fl.n_k > 0) bp.symf.push_back(fl);
-        bp.symf_max_n = std::max(bp.symf_max_n, (int)cnt);
+        if (fl.n_k > 0) bp.tails.symf.add(fl);       // (Sym::from never exceeds `produced`: n_k is the block's count)
     }
     if (const Chan::Agc *ag = c->agc.get()) {
         AgcLaunch al{};
@@ -330,11 +325,7 @@ int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c, int D)
         al.nsamples = ag->n;
         al.n_first = ag->from;
         al.n_k = since(ag->from, &al.n_lo);
-        if (al.n_k > 0) {
-            bp.agcf.push_back(al);
-            bp.agcf_max_n = std::max(bp.agcf_max_n, (int)al.n_k);
-            bp.agcf_max_ns = std::max(bp.agcf_max_ns, ag->n);
-        }
+        if (al.n_k > 0) bp.tails.agcf.add(al);
     }
     if (const Chan::Clock *ck = c->clock.get()) {
         ClockLaunch cl{};
@@ -347,10 +338,7 @@ int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c, int D)
         cl.adv0 = ck->adv0;
         cl.gain = ck->gain; cl.mu0 = ck->mu0; cl.omega_mid = ck->omega_mid; cl.omega_lim = ck->omega_lim;
         cl.gain_omega = ck->gain_omega; cl.gain_mu = ck->gain_mu;
-        if (cl.n_k > 0) {
-            bp.clkf.push_back(cl);
-            bp.clkf_max_n = std::max(bp.clkf_max_n, (int)cl.n_k);
-        }
+        if (cl.n_k > 0) bp.tails.clkf.add(cl);
     }
     if (const Chan::Costas *gc = c->costas.get()) {
         CostasLaunch gl{};
@@ -362,10 +350,7 @@ int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c, int D)
         gl.window = gc->window;
         gl.omega_mid = gc->omega_mid; gl.omega_lim = gc->omega_lim; gl.gain_omega = gc->gain_omega; gl.gain_mu = gc->gain_mu;
         gl.alpha = gc->alpha; gl.beta = gc->beta; gl.max_freq = gc->max_freq;
-        if (gl.n_k > 0) {
-            bp.gcf.push_back(gl);
-            bp.gcf_max_n = std::max(bp.gcf_max_n, (int)gl.n_k);
-        }
+        if (gl.n_k > 0) bp.tails.gcf.add(gl);
     }
     if (const Chan::Fsk4 *fk = c->fsk4.get()) {
         Fsk4Launch fl{};
@@ -376,10 +361,7 @@ int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c, int D)
         fl.n_k = since(std::max(fk->from, c->sym->from), &fl.n_lo);
         fl.time = fk->time; fl.k_spread = fk->k_spread; fl.k_timing = fk->k_timing; fl.k_fine = fk->k_fine;
         fl.k_coarse = fk->k_coarse; fl.spread_min = fk->spread_min; fl.spread_max = fk->spread_max;
-        if (fl.n_k > 0) {
-            bp.f4f.push_back(fl);
-            bp.f4f_max_n = std::max(bp.f4f_max_n, (int)fl.n_k);
-        }
+        if (fl.n_k > 0) bp.tails.f4f.add(fl);
     }
     if (c->audio) {
         Chan::Audio &au = *c->audio;
@@ -584,10 +566,10 @@ int plan_class_jobs(rcf_t *h, BlockPlan &bp, ClassPlan &cp, int depth, std::pair
         fir_by_depth[depth].push_back(std::move(job));
     }
     if (!(job.dims.small && clean.empty())) {   // the small-T kernel writes the discriminator ring itself
-        DiscJob dj{};
-        dj.n = (int)discs.size(); dj.max_n = max_n;
-        if (bp.defer) dj.host.swap(discs);
-        else if (!ar.put(discs, &dj.dev)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
+        DiscJob dj;
+        dj.host.swap(discs);
+        dj.max_n = max_n;
+        if (!bp.defer && !dj.upload(ar)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
         disc_jobs.push_back(std::move(dj));
     }
     return RCF_OK;
@@ -600,14 +582,11 @@ int plan_tail(rcf_t *h, BlockPlan &bp)
     auto &tap_list = bp.tap_list;
     auto &tap_bins = bp.tap_bins;
     auto &rot_fills = bp.rot_fills;
-    auto &symf = bp.symf;
-    auto &agcf = bp.agcf;
     auto &audf = bp.audf;
     PfbLaunch &pl = bp.pl;
     const bool run_pfb = bp.run_pfb;
     const TapLaunch *&d_tap_list = bp.d_tap_list;
     const RotFill *&d_rot_fills = bp.d_rot_fills;
-    const FmFirLaunch *&d_symf = bp.d_symf;
     const AudioLaunch *&d_audf = bp.d_audf;
 
     if (!tap_list.empty() && run_pfb) {
@@ -659,14 +638,9 @@ int plan_tail(rcf_t *h, BlockPlan &bp)
         pl.tap_pitch = (int32_t)mat_pitch;
         pl.n_taps = (int32_t)tap_list.size();
     }
-    // (a group's block: the exact-rotator fills, the symbol filters, the AGCs, the symbol clocks, the Gardner / Costas loops and the C4FM loops of all members go out as
-    // one launch each)
+    // (a group's block: the exact-rotator fills and the tail stages of all members go out as one launch each)
     if (!bp.defer && !rot_fills.empty() && !ar.put(rot_fills, &d_rot_fills)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
-    if (!bp.defer && !symf.empty() && !ar.put(symf, &d_symf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
-    if (!bp.defer && !agcf.empty() && !ar.put(agcf, &bp.d_agcf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
-    if (!bp.defer && !bp.clkf.empty() && !ar.put(bp.clkf, &bp.d_clkf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
-    if (!bp.defer && !bp.gcf.empty() && !ar.put(bp.gcf, &bp.d_gcf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
-    if (!bp.defer && !bp.f4f.empty() && !ar.put(bp.f4f, &bp.d_f4f)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
+    if (!bp.defer && !bp.tails.upload(ar)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
     if (!audf.empty() && !ar.put(audf, &d_audf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
     return RCF_OK;
 }

@@ -1,4 +1,6 @@
-// rcf_plan.h -- the per-block schedule: what one commit of one front-end launches, built on the host first.
+// rcf_plan.h -- the per-block schedule: what one commit of one front-end launches, built on the host first.  The stages
+// behind the FIRs (symbol filters, AGCs, the three symbol loops) are one table, TailStages: a block's plan and a group's
+// block each hold one, and the planner, the group's merge and the launcher visit it through TailStages::each.
 #pragma once
 #include <chrono>
 
@@ -43,7 +45,55 @@ struct FirJob {
     std::vector<ChanLaunch> host;      // BlockPlan::defer: records not yet in the arena (the group merges them first)
     bool bank_src = false;             // every channel of the job reads a bin of the filterbank (what the stage-2 lag may defer)
 };
-struct DiscJob { const DiscLaunch *dev; int n; int max_n; std::vector<DiscLaunch> host; };
+
+// The records of one stage in one block, all channels (a group's block: of all members) in one launch: on the host, and in
+// the arena once uploaded (BlockPlan::defer: the group uploads what it merged)
+template <class Rec> struct StageRecs {
+    std::vector<Rec> host;
+    const Rec *dev = nullptr;
+    int max_n = 0;                     // the largest n_k
+    int n() const { return (int)host.size(); }
+    void add(const Rec &r) { host.push_back(r); max_n = std::max(max_n, (int)r.n_k); }
+    void append(const StageRecs &o) { host.insert(host.end(), o.host.begin(), o.host.end()); max_n = std::max(max_n, o.max_n); }
+    bool upload(Arena &ar) { return host.empty() || ar.put(host, &dev); }
+};
+typedef StageRecs<DiscLaunch> DiscJob;     // the discriminators of one (depth, D, T) class
+struct AgcRecs : StageRecs<AgcLaunch> {
+    int max_ns = 0;                    // the longest window
+    void add(const AgcLaunch &r) { StageRecs::add(r); max_ns = std::max(max_ns, (int)r.nsamples); }
+    void append(const AgcRecs &o) { StageRecs::append(o); max_ns = std::max(max_ns, o.max_ns); }
+};
+
+// The stages that follow the derived FIRs and the discriminators, in launch order.  each() is the one list of them: it
+// calls f(timing class, launcher, the stage of every table given).
+struct TailStages {
+    StageRecs<FmFirLaunch> symf;       // symbol filters: they read the rings the discriminators wrote
+    AgcRecs agcf;                      // feedforward AGCs
+    StageRecs<ClockLaunch> clkf;       // symbol clocks, behind the discriminators
+    StageRecs<CostasLaunch> gcf;       // Gardner / Costas loops, behind the AGCs: they read the AGC rings
+    StageRecs<Fsk4Launch> f4f;         // C4FM loops, behind the symbol filters: they read the symbol-filter rings
+    template <class F, class... T> static void each(F &&f, T &...t)
+    {
+        f(RCF_T_DISC, launch_fm_fir, t.symf...);
+        f(RCF_T_DISC, launch_agc, t.agcf...);
+        f(RCF_T_CLOCK, launch_clock_mm, t.clkf...);
+        f(RCF_T_COSTAS, launch_costas, t.gcf...);
+        f(RCF_T_FSK4, launch_fsk4, t.f4f...);
+    }
+    void append(const TailStages &o) { each([](int, auto, auto &mine, const auto &theirs) { mine.append(theirs); }, *this, o); }
+    bool upload(Arena &ar)
+    {
+        bool ok = true;
+        each([&](int, auto, auto &s) { ok = ok && s.upload(ar); }, *this);
+        return ok;
+    }
+    bool any() const                   // a record of any stage in this block
+    {
+        bool v = false;
+        each([&](int, auto, const auto &s) { v = v || !s.host.empty(); }, *this);
+        return v;
+    }
+};
 
 struct BlockPlan {
     int64_t S0 = 0, S1 = 0;            // the block's samples [S0, S1)
@@ -68,16 +118,7 @@ struct BlockPlan {
     uint64_t serial = 0;               // Chan::blk_before / blk_after of this block carry it
     std::vector<std::vector<FirJob>> fir_by_depth;
     std::vector<DiscJob> disc_jobs;
-    std::vector<FmFirLaunch> symf;     // symbol filters, all channels in one launch
-    int symf_max_n = 0;
-    std::vector<AgcLaunch> agcf;       // feedforward AGCs, all channels in one launch
-    int agcf_max_n = 0, agcf_max_ns = 0;
-    std::vector<ClockLaunch> clkf;     // symbol clocks, all channels in one launch
-    int clkf_max_n = 0;
-    std::vector<CostasLaunch> gcf;     // Gardner / Costas loops, all channels in one launch
-    int gcf_max_n = 0;
-    std::vector<Fsk4Launch> f4f;       // C4FM symbol loops, all channels in one launch
-    int f4f_max_n = 0;
+    TailStages tails;                  // symbol filters, AGCs, symbol loops: all channels of a stage in one launch
     std::vector<RotFill> rot_fills;    // exact rotator: one record per launched channel, one launch before the FIRs
     std::vector<TapLaunch> tap_list;   // filterbank taps: copied out by the bank's kernel, finished by tap_finalize
     std::vector<int32_t> tap_bins;
@@ -94,13 +135,8 @@ struct BlockPlan {
     std::vector<int32_t> tap_first_of_bin;
     std::vector<TapLaunch> tap_ordered;
     const RotFill *d_rot_fills = nullptr;
-    const FmFirLaunch *d_symf = nullptr;
-    const AgcLaunch *d_agcf = nullptr;
-    const ClockLaunch *d_clkf = nullptr;
-    const CostasLaunch *d_gcf = nullptr;
-    const Fsk4Launch *d_f4f = nullptr;
     const AudioLaunch *d_audf = nullptr;
-    bool defer = false;                // a member of a group: mergeable records stay on the host (FirJob::host, DiscJob::host)
+    bool defer = false;                // a member of a group: mergeable records stay on the host (FirJob::host, disc_jobs, tails)
     bool history_done = false;         // launch_plan copied the history tail together with the launch records
 
     size_t reach(int id) const
@@ -156,15 +192,8 @@ int launch_plan(rcf_t *h, BlockPlan &bp);
 struct UploadSpan { size_t from, bytes; };             // the arena bytes [base, used) as the 64-byte blocks that hold them
 UploadSpan arena_upload_span(size_t base, size_t used);
 void launch_fir_job(rcf_t *h, FirJob &j, int timing_class, hipStream_t st);   // an unmerged FIR job, its repack first
-struct TailRecs {                                      // what follows the derived FIRs, timed as RCF_T_DISC (the loops: RCF_T_CLOCK, RCF_T_COSTAS, RCF_T_FSK4)
-    const DiscJob *disc; size_t n_disc;                // one discriminator launch per job
-    const FmFirLaunch *symf; int n_symf, symf_max_n;
-    const AgcLaunch *agcf; int n_agcf, agcf_max_n, agcf_max_ns;
-    const ClockLaunch *clkf; int n_clkf, clkf_max_n;   // behind the discriminators: they read the rings those wrote
-    const CostasLaunch *gcf; int n_gcf, gcf_max_n;     // behind the AGCs: they read the AGC rings
-    const Fsk4Launch *f4f; int n_f4f, f4f_max_n;       // behind the symbol filters: they read the symbol-filter rings
-};
-void launch_tail(rcf_t *h, const TailRecs &t, hipStream_t st);
+// what follows the derived FIRs: one discriminator launch per job, then the uploaded stages of t
+void launch_tail(rcf_t *h, const DiscJob *disc, size_t n_disc, const TailStages &t, hipStream_t st);
 void launch_member_audio(rcf_t *h, const BlockPlan &bp, hipStream_t st);
 int run_scan(rcf_t *h, const BlockPlan &bp);
 int finish_block(rcf_t *h, const BlockPlan &bp);

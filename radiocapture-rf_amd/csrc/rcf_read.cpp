@@ -31,8 +31,7 @@ static int stream_row(rcf_t *h, Chan *c, int kind, StreamRow *r)
     return RCF_OK;
 }
 
-// a stage's device counters: one asynchronous copy behind everything queued, one synchronisation
-static int stage_state(rcf_t *h, const void *d_state, void *st, size_t bytes)
+int stage_state(rcf_t *h, const void *d_state, void *st, size_t bytes)
 {
     RCF_HIP(hipMemcpyAsync(st, d_state, bytes, hipMemcpyDeviceToHost, h->stream));
     RCF_HIP(hipStreamSynchronize(h->stream));
@@ -45,21 +44,13 @@ int chan_stream(rcf_t *h, Chan *c, int kind, RingStream *s, int64_t *aux)
     int rc = stream_row(h, c, kind, &r);
     if (rc != RCF_OK) return rc;
     int64_t end = c->produced, beside = 0;
-    if (kind == kReadClock) {
-        ClockState st{};
-        if ((rc = stage_state(h, c->clock->d_state, &st, sizeof(st))) != RCF_OK) return rc;
-        end = st.n_out;
-        beside = st.slips;
-    } else if (kind == kReadCostas) {
-        CostasState st{};                            // (the counters at its front, not the history behind them)
-        if ((rc = stage_state(h, c->costas->d_state, &st, offsetof(CostasState, hist))) != RCF_OK) return rc;
-        end = st.n_out;
-        beside = st.slips;
-    } else if (kind == kReadFsk4) {
-        Fsk4State st{};
-        if ((rc = stage_state(h, c->fsk4->d_state, &st, offsetof(Fsk4State, hist))) != RCF_OK) return rc;
-        end = st.n_out;
-        beside = st.slips;
+    const void *loop = kind == kReadClock ? c->clock->counters() : kind == kReadCostas ? c->costas->counters()
+                     : kind == kReadFsk4 ? c->fsk4->counters() : nullptr;
+    if (loop) {                                      // the three loops alike
+        int64_t n_out_slips[2] = {0, 0};
+        if ((rc = stage_state(h, loop, n_out_slips, sizeof(n_out_slips))) != RCF_OK) return rc;
+        end = n_out_slips[0];
+        beside = n_out_slips[1];
     } else if (kind == kReadAudio) {
         AudioState st{};
         if ((rc = stage_state(h, c->audio->d_state, &st, sizeof(st))) != RCF_OK) return rc;

@@ -4,20 +4,66 @@
 // Attach, off, and what they produced.
 // An attach function allocates into Fresh<> holders and builds the new record completely; only then is it swapped into
 // the channel and the old one released.  A HIP call that fails before that leaves the channel as it was.
+// The three symbol loops share their record (Chan::Loop) and one attach path, attach_loop: an entry point validates its
+// parameters, checks what the loop reads and the ring's size, and fills in its own constants and initial state.
 #include "rcf_plan.h"
 
 namespace rcfx {
 
 void Chan::Sym::release(rcf_t *h) { bury(h, d_ring); bury(h, d_taps); d_ring = d_taps = nullptr; }
 void Chan::Agc::release(rcf_t *h) { bury(h, d_ring); d_ring = nullptr; }
-void Chan::Clock::release(rcf_t *h) { bury(h, d_ring); d_ring = nullptr; d_state = nullptr; d_bank = nullptr; }   // one allocation
-void Chan::Costas::release(rcf_t *h) { bury(h, d_ring); d_ring = nullptr; d_state = nullptr; d_bank = nullptr; }  // one allocation
-void Chan::Fsk4::release(rcf_t *h) { bury(h, d_ring); d_ring = nullptr; d_state = nullptr; d_bank = nullptr; }    // one allocation
 void Chan::Audio::release(rcf_t *h) { bury(h, d_state); bury(h, d_rings); bury(h, d_taps); d_state = nullptr; d_rings = d_taps = nullptr; }
 
 }  // namespace rcfx
 
 using namespace rcfx;
+
+// a stage switched off: nothing to do when the channel has none
+template <class R> static int stage_off(rcf_t *h, std::unique_ptr<R> &stage)
+{
+    if (stage) { drop_stage(h, stage); ++h->chans_epoch; }
+    return RCF_OK;
+}
+
+// the interpolator bank the symbol clocks, the Gardner / Costas loops and the C4FM loops share unless the caller brings one: built at first use
+static int default_bank(rcf_t *h)
+{
+    if (h->d_mmse) return RCF_OK;
+    constexpr size_t kBank = (size_t)(kClockSteps + 1) * kClockTaps;
+    const std::vector<float> t = design_mmse_interpolator(kClockTaps, kClockSteps, 0.25);
+    Fresh<float> d;
+    RCF_HIP(d.alloc(kBank));
+    if (!hip_ok(hipMemcpy(d.p, t.data(), sizeof(float) * kBank, hipMemcpyHostToDevice), "hipMemcpy(interpolator bank)")) return RCF_EHIP;
+    h->d_mmse = d.take();
+    return RCF_OK;
+}
+
+// What attaching a symbol loop comes to once its entry point has built the record k (its constants) and the initial state:
+// one allocation -- soft-symbol ring of out_cap floats | the state record, in a slot of whole 256 bytes | the caller's bank,
+// if any (out_cap is a power of two: the record's 64-bit fields are aligned) --, the two copies, and the swap.  Every call
+// is a new block: a fresh ring and state (symbol 0 is the first of this call), zero history before the channel's next output.
+template <class R>
+static int attach_loop(rcf_t *h, Chan *c, std::unique_ptr<R> &stage, std::unique_ptr<R> k, const typename R::State &st0,
+                       const float *interp_taps, const char *state_copy)
+{
+    constexpr size_t kBank = (size_t)(kClockSteps + 1) * kClockTaps;
+    constexpr size_t kStateFloats = (sizeof(typename R::State) + 255) / 256 * 256 / sizeof(float);
+    if (!interp_taps) { const int rc = default_bank(h); if (rc != RCF_OK) return rc; }
+    const size_t state_at = h->out_cap, bank_at = state_at + kStateFloats;       // in floats
+    Fresh<float> fresh;
+    RCF_HIP(fresh.alloc(bank_at + (interp_taps ? kBank : 0)));
+    if (!hip_ok(hipMemcpy(fresh.p + state_at, &st0, sizeof(st0), hipMemcpyHostToDevice), state_copy) ||
+        (interp_taps && !hip_ok(hipMemcpy(fresh.p + bank_at, interp_taps, sizeof(float) * kBank, hipMemcpyHostToDevice), "hipMemcpy(interpolator bank)")))
+        return RCF_EHIP;
+    k->d_ring = fresh.take();
+    k->d_state = reinterpret_cast<typename R::State *>(k->d_ring + state_at);
+    k->d_bank = interp_taps ? k->d_ring + bank_at : h->d_mmse;
+    k->from = c->produced;
+    drop_stage(h, stage);
+    stage = std::move(k);
+    ++h->chans_epoch;
+    return RCF_OK;
+}
 
 extern "C" {
 
@@ -54,8 +100,7 @@ int rcf_chan_agc(rcf_t *h, int chan_id, int nsamples, float reference)
     FIND_CHAN(h, chan_id, c);
     if (nsamples == 0) {                // off
         if (c->costas) { set_error("channel %d: the Gardner / Costas stage reads the AGC (switch it off first)", chan_id); return RCF_ESTATE; }
-        if (c->agc) { drop_stage(h, c->agc); ++h->chans_epoch; }
-        return RCF_OK;
+        return stage_off(h, c->agc);
     }
     if (c->fm_only) { set_error("channel %d exposes its discriminator only: the AGC reads IQ", chan_id); return RCF_ESTATE; }
     if ((size_t)nsamples * 2 > h->out_cap) { set_error("ring of %zu too small for a %d-sample AGC window", h->out_cap, nsamples); return RCF_ECAP; }
@@ -70,19 +115,6 @@ int rcf_chan_agc(rcf_t *h, int chan_id, int nsamples, float reference)
     c->agc->ref = reference;
     c->agc->from = c->agc->rd = c->produced;         // a new GR block starts with zero history
     ++h->chans_epoch;
-    return RCF_OK;
-}
-
-// the interpolator bank the symbol clocks, the Gardner / Costas loops and the C4FM loops share unless the caller brings one: built at first use
-static int default_bank(rcf_t *h)
-{
-    if (h->d_mmse) return RCF_OK;
-    constexpr size_t kBank = (size_t)(kClockSteps + 1) * kClockTaps;
-    const std::vector<float> t = design_mmse_interpolator(kClockTaps, kClockSteps, 0.25);
-    Fresh<float> d;
-    RCF_HIP(d.alloc(kBank));
-    if (!hip_ok(hipMemcpy(d.p, t.data(), sizeof(float) * kBank, hipMemcpyHostToDevice), "hipMemcpy(interpolator bank)")) return RCF_EHIP;
-    h->d_mmse = d.take();
     return RCF_OK;
 }
 
@@ -106,17 +138,8 @@ int rcf_chan_clock_mm(rcf_t *h, int chan_id, const rcf_clock_mm_params_t *p)
     std::lock_guard<std::mutex> g(h->mu);
     if (set_dev(h)) return RCF_EHIP;
     FIND_CHAN(h, chan_id, c);
-    if (!p) {                           // off
-        if (c->clock) { drop_stage(h, c->clock); ++h->chans_epoch; }
-        return RCF_OK;
-    }
+    if (!p) return stage_off(h, c->clock);
     if ((size_t)kClockTaps * 2 > h->out_cap) { set_error("ring of %zu too small for the clock's %d-sample window", h->out_cap, kClockTaps); return RCF_ECAP; }
-    constexpr size_t kBank = (size_t)(kClockSteps + 1) * kClockTaps;
-    if (!p->interp_taps) { const int rc = default_bank(h); if (rc != RCF_OK) return rc; }
-    // every call is a new GR block: a fresh ring and state (symbol 0 is the first of this call), zero history
-    const size_t state_at = h->out_cap, bank_at = h->out_cap + 64;       // in floats; the state record has 256 bytes to itself
-    Fresh<float> fresh;
-    RCF_HIP(fresh.alloc(bank_at + (p->interp_taps ? kBank : 0)));
     std::unique_ptr<Chan::Clock> k(new Chan::Clock);
     k->gain = p->gain; k->mu0 = p->mu; k->omega_mid = p->omega;
     k->omega_lim = k->omega_mid * p->omega_relative_limit;               // (one float product)
@@ -125,17 +148,7 @@ int rcf_chan_clock_mm(rcf_t *h, int chan_id, const rcf_clock_mm_params_t *p)
     ClockState st0{};
     st0.p = c->produced - (kClockTaps - 1);                              // the first window: seven zeros and u[first]
     st0.mu = k->mu0; st0.omega = k->omega_mid; st0.last = 0.f;
-    if (!hip_ok(hipMemcpy(fresh.p + state_at, &st0, sizeof(st0), hipMemcpyHostToDevice), "hipMemcpy(clock state)") ||
-        (p->interp_taps && !hip_ok(hipMemcpy(fresh.p + bank_at, p->interp_taps, sizeof(float) * kBank, hipMemcpyHostToDevice), "hipMemcpy(interpolator bank)")))
-        return RCF_EHIP;
-    k->d_ring = fresh.take();
-    k->d_state = reinterpret_cast<ClockState *>(k->d_ring + state_at);
-    k->d_bank = p->interp_taps ? k->d_ring + bank_at : h->d_mmse;
-    k->from = c->produced;
-    drop_stage(h, c->clock);
-    c->clock = std::move(k);
-    ++h->chans_epoch;
-    return RCF_OK;
+    return attach_loop(h, c, c->clock, std::move(k), st0, p->interp_taps, "hipMemcpy(clock state)");
 }
 
 // ---- Gardner / Costas symbol recovery behind the AGC (costas.hip)
@@ -157,36 +170,16 @@ int rcf_chan_costas(rcf_t *h, int chan_id, const rcf_costas_params_t *p)
     std::lock_guard<std::mutex> g(h->mu);
     if (set_dev(h)) return RCF_EHIP;
     FIND_CHAN(h, chan_id, c);
-    if (!p) {                           // off
-        if (c->costas) { drop_stage(h, c->costas); ++h->chans_epoch; }
-        return RCF_OK;
-    }
+    if (!p) return stage_off(h, c->costas);
     if (!c->agc) { set_error("channel %d has no AGC for the Gardner / Costas stage to read", chan_id); return RCF_ESTATE; }
     if (h->out_cap < 64) { set_error("ring of %zu too small for the Gardner / Costas stage", h->out_cap); return RCF_ECAP; }
-    constexpr size_t kBank = (size_t)(kClockSteps + 1) * kClockTaps;
-    if (!p->interp_taps) { const int rc = default_bank(h); if (rc != RCF_OK) return rc; }
-    // every call is a new block: a fresh ring and state (symbol 0 is the first of this call), zero history
-    constexpr size_t kStateFloats = (sizeof(CostasState) + 255) / 256 * 256 / sizeof(float);
-    const size_t state_at = h->out_cap, bank_at = h->out_cap + kStateFloats;     // in floats
-    Fresh<float> fresh;
-    RCF_HIP(fresh.alloc(bank_at + (p->interp_taps ? kBank : 0)));
     std::unique_ptr<Chan::Costas> k(new Chan::Costas);
     k->omega_mid = p->omega; k->omega_lim = p->omega_limit; k->gain_omega = p->gain_omega; k->gain_mu = p->gain_mu;
     k->alpha = p->alpha; k->beta = p->beta; k->max_freq = p->max_freq;
     k->window = std::max(2 * (int)std::ceil(k->omega_mid), (int)std::floor(k->omega_mid / 2) + 9);
     CostasState st0{};
     st0.mu = st0.omega = k->omega_mid;
-    if (!hip_ok(hipMemcpy(fresh.p + state_at, &st0, sizeof(st0), hipMemcpyHostToDevice), "hipMemcpy(Gardner / Costas state)") ||
-        (p->interp_taps && !hip_ok(hipMemcpy(fresh.p + bank_at, p->interp_taps, sizeof(float) * kBank, hipMemcpyHostToDevice), "hipMemcpy(interpolator bank)")))
-        return RCF_EHIP;
-    k->d_ring = fresh.take();
-    k->d_state = reinterpret_cast<CostasState *>(k->d_ring + state_at);
-    k->d_bank = p->interp_taps ? k->d_ring + bank_at : h->d_mmse;
-    k->from = c->produced;
-    drop_stage(h, c->costas);
-    c->costas = std::move(k);
-    ++h->chans_epoch;
-    return RCF_OK;
+    return attach_loop(h, c, c->costas, std::move(k), st0, p->interp_taps, "hipMemcpy(Gardner / Costas state)");
 }
 
 int rcf_chan_costas_state(rcf_t *h, int chan_id, rcf_costas_state_t *out)
@@ -196,9 +189,9 @@ int rcf_chan_costas_state(rcf_t *h, int chan_id, rcf_costas_state_t *out)
     if (set_dev(h)) return RCF_EHIP;
     FIND_CHAN(h, chan_id, c);
     if (!c->costas) { set_error("channel %d has no Gardner / Costas stage", chan_id); return RCF_ESTATE; }
-    CostasState st{};
-    RCF_HIP(hipMemcpyAsync(&st, c->costas->d_state, offsetof(CostasState, hist), hipMemcpyDeviceToHost, h->stream));
-    RCF_HIP(hipStreamSynchronize(h->stream));
+    CostasState st{};                   // (its front, not the history behind it)
+    const int rc = stage_state(h, c->costas->d_state, &st, offsetof(CostasState, hist));
+    if (rc != RCF_OK) return rc;
     out->n_symbols = st.n_out; out->n_slips = st.slips;
     out->mu = st.mu; out->omega = st.omega; out->freq = st.freq; out->phase = st.phase;
     return RCF_OK;
@@ -222,36 +215,16 @@ int rcf_chan_fsk4(rcf_t *h, int chan_id, const rcf_fsk4_params_t *p)
     std::lock_guard<std::mutex> g(h->mu);
     if (set_dev(h)) return RCF_EHIP;
     FIND_CHAN(h, chan_id, c);
-    if (!p) {                           // off
-        if (c->fsk4) { drop_stage(h, c->fsk4); ++h->chans_epoch; }
-        return RCF_OK;
-    }
+    if (!p) return stage_off(h, c->fsk4);
     if (!c->sym) { set_error("channel %d has no symbol filter (rcf_chan_fm_filter) for the C4FM loop to read", chan_id); return RCF_ESTATE; }
     if (h->out_cap < 16) { set_error("ring of %zu too small for the C4FM loop", h->out_cap); return RCF_ECAP; }
-    constexpr size_t kBank = (size_t)(kClockSteps + 1) * kClockTaps;
-    if (!p->interp_taps) { const int rc = default_bank(h); if (rc != RCF_OK) return rc; }
-    // every call is a new block: a fresh ring and state (symbol 0 is the first of this call), zero history
-    constexpr size_t kStateFloats = (sizeof(Fsk4State) + 255) / 256 * 256 / sizeof(float);
-    const size_t state_at = (h->out_cap + 1) / 2 * 2, bank_at = state_at + kStateFloats;     // in floats; the record's doubles 8-byte aligned
-    Fresh<float> fresh;
-    RCF_HIP(fresh.alloc(bank_at + (p->interp_taps ? kBank : 0)));
     std::unique_ptr<Chan::Fsk4> k(new Chan::Fsk4);
     k->time = p->symbol_rate / p->sample_rate;
     k->k_spread = p->k_spread; k->k_timing = p->k_timing; k->k_fine = p->k_fine; k->k_coarse = p->k_coarse;
     k->spread_min = p->spread_min; k->spread_max = p->spread_max;
     Fsk4State st0{};
     st0.spread = 2.0;
-    if (!hip_ok(hipMemcpy(fresh.p + state_at, &st0, sizeof(st0), hipMemcpyHostToDevice), "hipMemcpy(C4FM loop state)") ||
-        (p->interp_taps && !hip_ok(hipMemcpy(fresh.p + bank_at, p->interp_taps, sizeof(float) * kBank, hipMemcpyHostToDevice), "hipMemcpy(interpolator bank)")))
-        return RCF_EHIP;
-    k->d_ring = fresh.take();
-    k->d_state = reinterpret_cast<Fsk4State *>(k->d_ring + state_at);
-    k->d_bank = p->interp_taps ? k->d_ring + bank_at : h->d_mmse;
-    k->from = c->produced;
-    drop_stage(h, c->fsk4);
-    c->fsk4 = std::move(k);
-    ++h->chans_epoch;
-    return RCF_OK;
+    return attach_loop(h, c, c->fsk4, std::move(k), st0, p->interp_taps, "hipMemcpy(C4FM loop state)");
 }
 
 int rcf_chan_fsk4_state(rcf_t *h, int chan_id, rcf_fsk4_state_t *out)
@@ -262,8 +235,8 @@ int rcf_chan_fsk4_state(rcf_t *h, int chan_id, rcf_fsk4_state_t *out)
     FIND_CHAN(h, chan_id, c);
     if (!c->fsk4) { set_error("channel %d has no C4FM symbol loop (rcf_chan_fsk4)", chan_id); return RCF_ESTATE; }
     Fsk4State st{};
-    RCF_HIP(hipMemcpyAsync(&st, c->fsk4->d_state, offsetof(Fsk4State, hist), hipMemcpyDeviceToHost, h->stream));
-    RCF_HIP(hipStreamSynchronize(h->stream));
+    const int rc = stage_state(h, c->fsk4->d_state, &st, offsetof(Fsk4State, hist));
+    if (rc != RCF_OK) return rc;
     out->n_symbols = st.n_out; out->n_slips = st.slips;
     out->clock = st.clock; out->spread = st.spread; out->fine = st.fine; out->coarse = st.coarse;
     return RCF_OK;

@@ -83,9 +83,8 @@ struct Chan {
     //   stage                                  ring on re-call       from         read cursor
     //   symbol filter (rcf_chan_fm_filter)     kept                  kept         kept          (new taps and gain only)
     //   AGC           (rcf_chan_agc)           kept                  `produced`   `produced`
-    //   symbol clock  (rcf_chan_clock_mm)      new ring and state    `produced`   0
-    //   Gardner/Costas (rcf_chan_costas)       new ring and state    `produced`   0
-    //   C4FM loop     (rcf_chan_fsk4)          new ring and state    `produced`   0
+    //   symbol loops  (rcf_chan_clock_mm,      new ring and state    `produced`   0
+    //                  rcf_chan_costas, rcf_chan_fsk4: one record shape, Loop, and one attach path, rcf_stage.cpp)
     //   voice chain   (rcf_chan_audio_open)    new                   `produced`   0
     // `from`: the first relative channel output the stage is defined for (a new GR block: zero history before it); `rd`:
     // items handed to the stage's reader; reach(): how far behind a block's first output the stage reads the channel's
@@ -106,35 +105,36 @@ struct Chan {
         size_t reach() const { return (size_t)std::max(1, n - 1); }     // the window reaches n - 1 samples behind
         void release(rcf_t *h);
     };
-    struct Clock {                      // clock_recovery_mm_ff over gain * fm (SmartNet / EDACS)
-        float *d_ring = nullptr;        // one allocation: soft-symbol ring of out_cap floats | ClockState | the caller's bank, if any
-        ClockState *d_state = nullptr;
+    // what the three symbol loops share.  One allocation: soft-symbol ring of out_cap floats | the state record, in a
+    // slot of whole 256 bytes | the caller's bank, if any (attach_loop, rcf_stage.cpp)
+    template <class State_> struct Loop {
+        typedef State_ State;
+        float *d_ring = nullptr;
+        State *d_state = nullptr;
         const float *d_bank = nullptr;  // the interpolator bank the stage reads: the caller's (inside d_ring's allocation) or rcf::d_mmse
+        int64_t from = 0, rd = 0;
+        size_t reach() const { return 0; }                               // the history is in the state record: no look-back
+        // the record's two counters on the device, n_out then slips (ClockState keeps them behind `p`: moving them to the
+        // front, where the other two have them, changes clock_mm_kernel's code)
+        const void *counters() const
+        {
+            static_assert(offsetof(State, slips) == offsetof(State, n_out) + sizeof(int64_t), "n_out, then slips");
+            return &d_state->n_out;
+        }
+        void release(rcf_t *h);
+    };
+    struct Clock : Loop<ClockState> {   // clock_recovery_mm_ff over gain * fm (SmartNet / EDACS)
         // the constants as the kernel takes them, rounded to float once
         float gain = 1.f, mu0 = 0.f, omega_mid = 0.f, omega_lim = 0.f, gain_omega = 0.f, gain_mu = 0.f;
         int adv0 = 1;
-        int64_t from = 0, rd = 0;
         size_t reach() const { return (size_t)kClockTaps - 1; }         // a symbol's window starts up to 7 samples behind
-        void release(rcf_t *h);
     };
-    struct Costas {                     // Gardner / Costas symbol recovery over the AGC ring (P25 CQPSK back half)
-        float *d_ring = nullptr;        // one allocation: soft-symbol ring of out_cap floats | CostasState | the caller's bank, if any
-        CostasState *d_state = nullptr;
-        const float *d_bank = nullptr;  // the caller's (inside d_ring's allocation) or rcf::d_mmse
+    struct Costas : Loop<CostasState> { // Gardner / Costas symbol recovery over the AGC ring (P25 CQPSK back half)
         float omega_mid = 0.f, omega_lim = 0.f, gain_omega = 0.f, gain_mu = 0.f, alpha = 0.f, beta = 0.f, max_freq = 0.f;
         int window = 0;                 // L
-        int64_t from = 0, rd = 0;
-        size_t reach() const { return 0; }                               // the history is in the state record: no look-back
-        void release(rcf_t *h);
     };
-    struct Fsk4 {                       // the C4FM symbol loop over the symbol-filter ring (P25 C4FM back half)
-        float *d_ring = nullptr;        // one allocation: soft-symbol ring of out_cap floats | Fsk4State | the caller's bank, if any
-        Fsk4State *d_state = nullptr;
-        const float *d_bank = nullptr;  // the caller's (inside d_ring's allocation) or rcf::d_mmse
+    struct Fsk4 : Loop<Fsk4State> {     // the C4FM symbol loop over the symbol-filter ring (P25 C4FM back half)
         double time = 0, k_spread = 0, k_timing = 0, k_fine = 0, k_coarse = 0, spread_min = 0, spread_max = 0;
-        int64_t from = 0, rd = 0;
-        size_t reach() const { return 0; }                               // the history is in the state record: no look-back
-        void release(rcf_t *h);
     };
     struct Audio {                      // the analog voice chain
         AudioState *d_state = nullptr;
@@ -153,6 +153,13 @@ struct Chan {
     std::unique_ptr<Costas> costas;
     std::unique_ptr<Fsk4> fsk4;
     std::unique_ptr<Audio> audio;
+    // the one list of them: f(the stage's holder -- null when the channel has no such stage --, the bytes of its launch
+    // record, whether its reach() is into rings of its own instead of the channel's)
+    template <class F> void for_each_stage(F &&f)
+    {
+        f(sym, sizeof(FmFirLaunch), false); f(agc, sizeof(AgcLaunch), false); f(clock, sizeof(ClockLaunch), false);
+        f(costas, sizeof(CostasLaunch), false); f(fsk4, sizeof(Fsk4Launch), false); f(audio, sizeof(AudioLaunch), true);
+    }
     // ---- the rest
     float incr[2] = {1.f, 0.f};   // exact rotator: what GNU Radio iterates
     uint64_t many_stamp = 0;      // the host_read call that last listed this channel (batched reads: one reader per stream)
@@ -411,6 +418,7 @@ int new_channel(rcf_t *h, int src, int D, const float *taps, int T, double offse
 void free_channel(rcf_t *h, Chan *c);                 // c's device buffers go once the stream has passed them; the caller erases c
 // a stage goes (switched off, replaced, or with its channel): release() its buffers, then the record
 template <class R> void drop_stage(rcf_t *h, std::unique_ptr<R> &r) { if (r) { r->release(h); r.reset(); } }
+template <class State> void Chan::Loop<State>::release(rcf_t *h) { bury(h, d_ring); d_ring = nullptr; d_state = nullptr; d_bank = nullptr; }   // one allocation
 
 // ---------------------------------------------------------------- rcf_read.cpp
 // ---- the one read path.  A stream is a device ring of h->out_cap items (a power of two) of item_w 4-byte words:
@@ -431,6 +439,8 @@ constexpr int kReadSym = 3, kReadClock = 4, kReadAudio = 5, kReadCostas = 6, kRe
 // asynchronous copy and one synchronisation of the stream (RCF_EHIP); *aux, if given, takes the counter beside it (the
 // loops' slips, the samples that passed the voice chain's squelch).
 int chan_stream(rcf_t *h, Chan *c, int kind, RingStream *s, int64_t *aux = nullptr);
+// the front `bytes` of a stage's device state record: one asynchronous copy behind everything queued, one synchronisation
+int stage_state(rcf_t *h, const void *d_state, void *st, size_t bytes);
 
 // A reader that has fallen more than a ring behind lost what the ring overwrote: its cursor is raised to the oldest item
 // the ring still holds.  Returns how many items [*cursor, end) it may take, at most max.

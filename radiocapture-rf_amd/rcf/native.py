@@ -79,16 +79,29 @@ class CostasState(C.Structure):
                 ("freq", C.c_float), ("phase", C.c_float)]
 
 
+def _bank_arg(interp_taps):
+    """a caller's [129, 8] interpolator bank as the contiguous float32 array a params struct points into (keep it while
+    the struct is in use), or None"""
+    if interp_taps is None:
+        return None
+    taps = np.ascontiguousarray(interp_taps, dtype=np.float32)
+    if taps.shape != (129, 8):
+        raise ValueError("interp_taps must be a [129, 8] array")
+    return taps
+
+
+def _state_dict(st):
+    """a ctypes state struct as a dict of its fields"""
+    return {k: getattr(st, k) for k, _ in st._fields_}
+
+
 def costas_params_struct(omega, gain_mu, gain_omega, alpha, beta, max_freq, omega_limit, interp_taps=None):
     """-> (CostasParams, the array its interp_taps points into or None: keep it while the struct is in use)"""
     p = CostasParams()
     p.omega, p.gain_mu, p.gain_omega, p.alpha = float(omega), float(gain_mu), float(gain_omega), float(alpha)
     p.beta, p.max_freq, p.omega_limit = float(beta), float(max_freq), float(omega_limit)
-    taps = None
-    if interp_taps is not None:
-        taps = np.ascontiguousarray(interp_taps, dtype=np.float32)
-        if taps.shape != (129, 8):
-            raise ValueError("interp_taps must be a [129, 8] array")
+    taps = _bank_arg(interp_taps)
+    if taps is not None:
         p.interp_taps = taps.ctypes.data_as(C.POINTER(C.c_float))
     return p, taps
 
@@ -111,11 +124,8 @@ def fsk4_params_struct(sample_rate, symbol_rate, k_spread, k_timing, k_fine, k_c
     p = Fsk4Params()
     p.sample_rate, p.symbol_rate, p.k_spread, p.k_timing = float(sample_rate), float(symbol_rate), float(k_spread), float(k_timing)
     p.k_fine, p.k_coarse, p.spread_min, p.spread_max = float(k_fine), float(k_coarse), float(spread_min), float(spread_max)
-    taps = None
-    if interp_taps is not None:
-        taps = np.ascontiguousarray(interp_taps, dtype=np.float32)
-        if taps.shape != (129, 8):
-            raise ValueError("interp_taps must be a [129, 8] array")
+    taps = _bank_arg(interp_taps)
+    if taps is not None:
         p.interp_taps = taps.ctypes.data_as(C.POINTER(C.c_float))
     return p, taps
 
@@ -630,10 +640,20 @@ class Frontend:
     def chan_produced(self, cid):
         return _check(lib().rcf_chan_produced(self._h, cid))
 
-    def chan_read_iq(self, cid, max_samples=1 << 20) -> np.ndarray:
-        out = np.empty(max_samples, dtype=np.complex64)
-        n = _check(lib().rcf_chan_read_iq(self._h, cid, _fp(out.view(np.float32)), max_samples))
+    def _read_ring(self, fn, cid, n, dtype):
+        """the unread items of one of channel cid's rings through its single reader fn(h, cid, out, max): at most n"""
+        out = np.empty(n, dtype=dtype)
+        n = _check(fn(self._h, cid, _fp(out.view(np.float32)), n))
         return out[:n].copy()
+
+    def _ring_of(self, fn, cid):
+        """(device pointer, capacity) of one of channel cid's rings through fn(h, cid, &pointer, &capacity)"""
+        p, cap = C.c_void_p(), C.c_size_t()
+        _check(fn(self._h, cid, C.byref(p), C.byref(cap)))
+        return p.value, cap.value
+
+    def chan_read_iq(self, cid, max_samples=1 << 20) -> np.ndarray:
+        return self._read_ring(lib().rcf_chan_read_iq, cid, max_samples, np.complex64)
 
     def chan_read_fm(self, cid, gain, max_samples=1 << 20) -> np.ndarray:
         out = np.empty(max_samples, dtype=np.float32)
@@ -682,9 +702,7 @@ class Frontend:
         _check(lib().rcf_chan_fm_filter(self._h, cid, float(gain), _fp(taps), len(taps)))
 
     def chan_read_sym(self, cid, max_samples=1 << 20) -> np.ndarray:
-        out = np.empty(max_samples, dtype=np.float32)
-        n = _check(lib().rcf_chan_read_sym(self._h, cid, _fp(out), max_samples))
-        return out[:n].copy()
+        return self._read_ring(lib().rcf_chan_read_sym, cid, max_samples, np.float32)
 
     def chan_agc(self, cid, nsamples=1024, reference=1.0):
         """analog.feedforward_agc_cc(nsamples, reference) on the channel's IQ (rcf_chan_agc; p25_control_demod.py:149),
@@ -692,15 +710,11 @@ class Frontend:
         _check(lib().rcf_chan_agc(self._h, cid, int(nsamples), float(reference)))
 
     def chan_read_agc(self, cid, max_samples=1 << 20) -> np.ndarray:
-        out = np.empty(max_samples, dtype=np.complex64)
-        n = _check(lib().rcf_chan_read_agc(self._h, cid, _fp(out.view(np.float32)), max_samples))
-        return out[:n].copy()
+        return self._read_ring(lib().rcf_chan_read_agc, cid, max_samples, np.complex64)
 
     def chan_agc_ring(self, cid):
         """(device pointer, capacity) of the channel's cf32 AGC ring (rcf_chan_agc_ring)"""
-        p, cap = C.c_void_p(), C.c_size_t()
-        _check(lib().rcf_chan_agc_ring(self._h, cid, C.byref(p), C.byref(cap)))
-        return p.value, cap.value
+        return self._ring_of(lib().rcf_chan_agc_ring, cid)
 
     def chan_clock_mm(self, cid, omega, gain_omega=1.4395919, mu=0.5, gain_mu=0.05, omega_relative_limit=0.005, gain=5.0,
                       interp_taps=None):
@@ -714,11 +728,8 @@ class Frontend:
         p = ClockMmParams()
         p.gain, p.omega, p.gain_omega, p.mu = float(gain), float(omega), float(gain_omega), float(mu)
         p.gain_mu, p.omega_relative_limit = float(gain_mu), float(omega_relative_limit)
-        taps = None
-        if interp_taps is not None:
-            taps = np.ascontiguousarray(interp_taps, dtype=np.float32)
-            if taps.shape != (129, 8):
-                raise ValueError("interp_taps must be a [129, 8] array")
+        taps = _bank_arg(interp_taps)
+        if taps is not None:
             p.interp_taps = _fp(taps)
         _check(lib().rcf_chan_clock_mm(self._h, cid, C.byref(p)))
 
@@ -730,15 +741,11 @@ class Frontend:
 
     def chan_read_clock(self, cid, max_symbols=1 << 20) -> np.ndarray:
         """unread soft symbols of the channel's clock, oldest first; the bits are (out >= 0)"""
-        out = np.empty(max_symbols, dtype=np.float32)
-        n = _check(lib().rcf_chan_read_clock(self._h, cid, _fp(out), max_symbols))
-        return out[:n].copy()
+        return self._read_ring(lib().rcf_chan_read_clock, cid, max_symbols, np.float32)
 
     def chan_clock_ring(self, cid):
         """(device pointer, capacity) of the channel's float32 soft-symbol ring (rcf_chan_clock_ring)"""
-        p, cap = C.c_void_p(), C.c_size_t()
-        _check(lib().rcf_chan_clock_ring(self._h, cid, C.byref(p), C.byref(cap)))
-        return p.value, cap.value
+        return self._ring_of(lib().rcf_chan_clock_ring, cid)
 
     def chan_costas(self, cid, omega, gain_mu=0.025, gain_omega=6.25e-5, alpha=0.04, beta=2e-4, max_freq=0.0, omega_limit=0.005,
                     interp_taps=None):
@@ -758,19 +765,15 @@ class Frontend:
         sign opposite to the carrier's offset), phase (rcf_chan_costas_state; syncs the stream)"""
         st = CostasState()
         _check(lib().rcf_chan_costas_state(self._h, cid, C.byref(st)))
-        return {k: getattr(st, k) for k, _ in CostasState._fields_}
+        return _state_dict(st)
 
     def chan_read_costas(self, cid, max_symbols=1 << 20) -> np.ndarray:
         """unread soft symbols of the channel's Gardner / Costas stage (+-1, +-3 on a locked signal), oldest first"""
-        out = np.empty(max_symbols, dtype=np.float32)
-        n = _check(lib().rcf_chan_read_costas(self._h, cid, _fp(out), max_symbols))
-        return out[:n].copy()
+        return self._read_ring(lib().rcf_chan_read_costas, cid, max_symbols, np.float32)
 
     def chan_costas_ring(self, cid):
         """(device pointer, capacity) of the stage's float32 soft-symbol ring (rcf_chan_costas_ring)"""
-        p, cap = C.c_void_p(), C.c_size_t()
-        _check(lib().rcf_chan_costas_ring(self._h, cid, C.byref(p), C.byref(cap)))
-        return p.value, cap.value
+        return self._ring_of(lib().rcf_chan_costas_ring, cid)
 
     def chan_fsk4(self, cid, sample_rate, symbol_rate=4800.0, k_spread=0.01, k_timing=0.025, k_fine=0.125, k_coarse=0.00125,
                   spread_min=1.6, spread_max=2.4, interp_taps=None):
@@ -791,19 +794,15 @@ class Frontend:
         the stream)"""
         st = Fsk4State()
         _check(lib().rcf_chan_fsk4_state(self._h, cid, C.byref(st)))
-        return {k: getattr(st, k) for k, _ in Fsk4State._fields_}
+        return _state_dict(st)
 
     def chan_read_fsk4(self, cid, max_symbols=1 << 20) -> np.ndarray:
         """unread soft symbols of the channel's C4FM loop (+-1, +-3 on a locked signal), oldest first"""
-        out = np.empty(max_symbols, dtype=np.float32)
-        n = _check(lib().rcf_chan_read_fsk4(self._h, cid, _fp(out), max_symbols))
-        return out[:n].copy()
+        return self._read_ring(lib().rcf_chan_read_fsk4, cid, max_symbols, np.float32)
 
     def chan_fsk4_ring(self, cid):
         """(device pointer, capacity) of the stage's float32 soft-symbol ring (rcf_chan_fsk4_ring)"""
-        p, cap = C.c_void_p(), C.c_size_t()
-        _check(lib().rcf_chan_fsk4_ring(self._h, cid, C.byref(p), C.byref(cap)))
-        return p.value, cap.value
+        return self._ring_of(lib().rcf_chan_fsk4_ring, cid)
 
     def chan_fm_level(self, cid, gain, window=10000) -> float:
         v = C.c_float()
@@ -836,9 +835,7 @@ class Frontend:
         return a.value, u.value
 
     def chan_read_audio(self, cid, max_samples=1 << 20) -> np.ndarray:
-        out = np.empty(max_samples, dtype=np.float32)
-        n = _check(lib().rcf_chan_read_audio(self._h, cid, _fp(out), max_samples))
-        return out[:n].copy()
+        return self._read_ring(lib().rcf_chan_read_audio, cid, max_samples, np.float32)
 
     def source_shift(self, delta_hz):
         _check(lib().rcf_source_shift(self._h, float(delta_hz)))
