@@ -116,7 +116,7 @@ int new_channel(rcf_t *h, int src, int D, const float *taps, int T, double offse
         if (it == h->chans.end()) { set_error("no such source channel %d", src); return RCF_ENOCHAN; }
         if (it->second->fm_only) { set_error("channel %d exposes its discriminator only: no IQ stream to chain on", src); return RCF_ESTATE; }
         c->src_rate = it->second->src_rate / it->second->D;
-        c->start_sample = it->second->produced;
+        c->start_sample = it->second->pos.produced;
         c->depth = it->second->depth + 1;
     }
     if (src >= 0 && (size_t)(T + D) * 2 > h->out_cap) { set_error("source ring too small for T=%d", T); return RCF_ECAP; }
@@ -238,7 +238,7 @@ int rcf_pfb_tap_open(rcf_t *h, int bin, int gr_phase, int *chan_id)
         const int64_t n0 = p.n_abs0 + c->k_abs0;
         const int64_t kd = (((int64_t)ks * p.D) % p.NB + p.NB) % p.NB;
         const int64_t turn = (kd * (n0 % p.NB)) % p.NB;
-        c->angle0 = (long double)cphase +
+        c->pos.angle0 = (long double)cphase +
                     remainderl(2.0L * 3.14159265358979323846264338327950288L * (long double)turn / (long double)p.NB,
                                2.0L * 3.14159265358979323846264338327950288L);
         rc = upload_composite(h, c);
@@ -296,7 +296,7 @@ int64_t rcf_chan_produced(rcf_t *h, int chan_id)
     std::lock_guard<std::mutex> g(h->mu);
     if (set_dev(h)) return RCF_EHIP;                  // (the count includes the deferred stage-2 block: it is queued first)
     FIND_CHAN(h, chan_id, c);
-    return c->produced;
+    return c->pos.produced;
 }
 
 int64_t rcf_chan_start(rcf_t *h, int chan_id)
@@ -315,7 +315,7 @@ int rcf_chan_fm_level(rcf_t *h, int chan_id, float gain, int window, float *leve
     FIND_CHAN(h, chan_id, c);
     if ((size_t)window > h->out_cap) { set_error("window %d exceeds the ring", window); return RCF_ECAP; }
     if (!h->d_level) RCF_HIP(hipMalloc(&h->d_level, sizeof(float)));
-    launch_fm_level(c->d_fm, c->produced, window, gain, h->ring_mask, h->d_level, h->stream);
+    launch_fm_level(c->d_fm, c->pos.produced, window, gain, h->ring_mask, h->d_level, h->stream);
     RCF_HIP(hipMemcpyAsync(level, h->d_level, sizeof(float), hipMemcpyDeviceToHost, h->stream));
     RCF_HIP(hipStreamSynchronize(h->stream));
     return RCF_OK;
@@ -334,18 +334,18 @@ int rcf_chan_set_fm_only(rcf_t *h, int chan_id, int on)
         for (auto &kv : h->chans)
             if (kv.second->src == chan_id) { set_error("channel %d reads channel %d's IQ stream", kv.first, chan_id); return RCF_ESTATE; }
     } else if (c->fm_only) {
-        c->rd_iq = c->produced;                  // what lies behind was never written
+        c->rd_iq = c->pos.produced;                  // what lies behind was never written
     }
-    if ((on != 0) != c->fm_only && c->produced > 0) {
+    if ((on != 0) != c->fm_only && c->pos.produced > 0) {
         // The newest ring sample is the "output before" of the next block's first discriminator sample, and the two modes
         // keep it differently: rotated by the channel's rotator (ordinary tap) or as the bare bin (discriminator only: that
         // path never rotates, it turns the conjugate product by the rotator's increment instead).  Convert the one sample,
         // so that no discriminator sample straddles two conventions.  Only its angle matters to the discriminator.
         RCF_HIP(hipStreamSynchronize(h->stream));
-        float2 *at = c->d_iq + ((uint64_t)(c->produced - 1) & h->ring_mask);
+        float2 *at = c->d_iq + ((uint64_t)(c->pos.produced - 1) & h->ring_mask);
         float2 v;
         RCF_HIP(hipMemcpy(&v, at, sizeof(v), hipMemcpyDeviceToHost));
-        const long double ang = c->angle0 + (long double)(c->produced - 1 - c->n_seg0) * (long double)c->dangle;
+        const long double ang = c->pos.angle0 + (long double)(c->pos.produced - 1 - c->pos.n_seg0) * (long double)c->dangle;
         const double pr = std::cos((double)ang), pi = (on ? -1.0 : 1.0) * std::sin((double)ang);
         const float2 w = make_float2((float)(v.x * pr - v.y * pi), (float)(v.x * pi + v.y * pr));
         RCF_HIP(hipMemcpy(at, &w, sizeof(w), hipMemcpyHostToDevice));

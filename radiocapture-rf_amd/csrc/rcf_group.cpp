@@ -68,8 +68,6 @@ struct GroupBlock {
     rcf_t *member(size_t i) const { return g->members[(size_t)items[i].m]; }
 };
 
-int oom() { set_error("launch arena exhausted"); return RCF_ENOMEM; }
-
 // room in the group's arena for every member's records and the group's own
 int reserve_arena(GroupBlock &b)
 {
@@ -169,7 +167,7 @@ int merge_banks(GroupBlock &b)
             pls.push_back(pl);
         }
         first.push_back(total);
-        if (!b.ga.put(pls, &bg.d_pls) || !b.ga.put(first, &bg.gm.wg_first)) return oom();
+        if (!b.ga.put(pls, &bg.d_pls) || !b.ga.put(first, &bg.gm.wg_first)) return arena_full();
         bg.gm.n_fe = (int32_t)bg.idx.size();
         bg.gm.total_wg = total;
         bg.gm.uniform_nwg = uniform > 0 ? uniform : 0;
@@ -191,7 +189,7 @@ int merge_taps(GroupBlock &b)
         b.tap_max_taps = std::max(b.tap_max_taps, (int)pl.n_taps);
         b.tap_max_rows = std::max(b.tap_max_rows, (int)pl.n_frames);
     }
-    if (!b.tap_args.empty() && !b.ga.put(b.tap_args, &b.d_tap_args)) return oom();
+    if (!b.tap_args.empty() && !b.ga.put(b.tap_args, &b.d_tap_args)) return arena_full();
     return RCF_OK;
 }
 
@@ -213,7 +211,7 @@ int merge_firs(GroupBlock &b)
     for (auto &lvl : b.merged)
         for (auto &kv : lvl) {
             kv.second.dims.n_chans = (int)kv.second.recs.size();
-            if (!b.ga.put(kv.second.recs, &kv.second.dev)) return oom();
+            if (!b.ga.put(kv.second.recs, &kv.second.dev)) return arena_full();
         }
     return RCF_OK;
 }
@@ -226,7 +224,7 @@ int merge_tails(GroupBlock &b)
         b.tails.append(bp->tails);
         b.rots.insert(b.rots.end(), bp->rot_fills.begin(), bp->rot_fills.end());
     }
-    if (!b.disc.upload(b.ga) || !b.tails.upload(b.ga) || (!b.rots.empty() && !b.ga.put(b.rots, &b.d_rots))) return oom();
+    if (!b.disc.upload(b.ga) || !b.tails.upload(b.ga) || (!b.rots.empty() && !b.ga.put(b.rots, &b.d_rots))) return arena_full();
     return RCF_OK;
 }
 
@@ -277,7 +275,7 @@ int build_prep(GroupBlock &b)
     for (size_t at = 0; at < b.prep.size(); at += kPrepMaxRecs)
         b.prep_tiles.push_back(fill_prep_tiles(b.prep.data() + at, (int)std::min<size_t>(kPrepMaxRecs, b.prep.size() - at)));
     const PrepRec *d_prep = nullptr;
-    if (!b.ga.put(b.prep, &d_prep)) return oom();
+    if (!b.ga.put(b.prep, &d_prep)) return arena_full();
     // (the kernel reads ITS records where the host wrote them, not their device copy)
     b.prep_mapped = reinterpret_cast<const PrepRec *>(h_dev + (reinterpret_cast<const unsigned char *>(d_prep) - b.ga.d));
     b.g->arenas.fill = (b.ga.used + 63) & ~size_t(63);

@@ -63,15 +63,12 @@ void launch_member_audio(rcf_t *h, const BlockPlan &bp, hipStream_t st)
 int launch_plan(rcf_t *h, BlockPlan &bp)
 {
     hipStream_t st = h->stream;
-    auto &fir_by_depth = bp.fir_by_depth;
     PfbLaunch &pl = bp.pl;
-    const bool run_pfb = bp.run_pfb;
-
     // ---- stage-2 lag.  The previous block's small-T launch, if it is still pending, rides in THIS block's filterbank launch
     // when that launch is the kernel that can carry it and the bank's ring has room for both blocks' frames; otherwise it
     // goes out now, ahead of everything of this block.
     const size_t pfb_reach = bp.reach(RCF_SRC_PFB_BIN0);
-    const bool carry = run_pfb && bp.shape.carries_s2 && !bp.pfb_zero_history;
+    const bool carry = bp.run_pfb && bp.shape.carries_s2 && !bp.pfb_zero_history;
     if (h->lag.pending && !(carry && (size_t)(pl.n_frames + h->lag.frames) + pfb_reach <= h->out_cap)) flush_lagged(h);
     S2Rider sr{};
     if (h->lag.pending) {
@@ -89,10 +86,10 @@ int launch_plan(rcf_t *h, BlockPlan &bp)
     // ... and this block's own: ONE small-T job on the bank's bins, nothing that consumes its outputs within the block (a
     // record of any tail stage, a voice chain: they read rings the lagged launch has not written)
     FirJob *lag_job = nullptr;
-    if (h->lag_enabled && carry && fir_by_depth.size() == 2 && fir_by_depth[1].size() == 1 && fir_by_depth[1][0].dims.small &&
-        fir_by_depth[1][0].dev && fir_by_depth[1][0].bank_src && !bp.tails.any() && !bp.d_audf &&
+    if (h->lag_enabled && carry && bp.fir_by_depth.size() == 2 && bp.fir_by_depth[1].size() == 1 && bp.fir_by_depth[1][0].dims.small &&
+        bp.fir_by_depth[1][0].dev && bp.fir_by_depth[1][0].bank_src && !bp.tails.any() && !bp.d_audf &&
         (size_t)pl.n_frames * 2 + pfb_reach <= h->out_cap)
-        lag_job = &fir_by_depth[1][0];
+        lag_job = &bp.fir_by_depth[1][0];
     {
         // the block's launch records host -> device, and -- in the same launch -- its history tail behind the OTHER input
         // buffer's block (nothing in this block reads that place, and the kernels that did read it are earlier in
@@ -102,8 +99,8 @@ int launch_plan(rcf_t *h, BlockPlan &bp)
         // ... or none at all: when the filterbank's launch is the first of the block that needs neither (no direct
         // channels, no exact-rotator fill before it, no tap matrix whose slot list the bank itself reads from the
         // arena), its first workgroups do both copies on the way in (PfbLaunch::rider_*)
-        const bool ride = run_pfb && !bp.d_rot_fills &&
-                          (fir_by_depth.empty() || fir_by_depth[0].empty()) && pl.n_taps == pl.tap_first &&
+        const bool ride = bp.run_pfb && !bp.d_rot_fills &&
+                          (bp.fir_by_depth.empty() || bp.fir_by_depth[0].empty()) && pl.n_taps == pl.tap_first &&
                           up.bytes / 8 < (1u << 31) && h->hist_cap < (1u << 28) && bp.shape.takes_rider;
         if (ride) {
             pl.rider_dst[0] = reinterpret_cast<unsigned long long *>(dst);
@@ -120,16 +117,16 @@ int launch_plan(rcf_t *h, BlockPlan &bp)
         if (up.bytes) h->arenas.fill = (bp.ar->used + 63) & ~size_t(63);
     }
     if (bp.d_rot_fills) launch_rot_fill(bp.d_rot_fills, (int)bp.rot_fills.size(), h->ring_mask, st);
-    if (!fir_by_depth.empty())
-        for (auto &j : fir_by_depth[0]) launch_fir_job(h, j, j.dims.mfma ? RCF_T_FIR_MFMA : RCF_T_FIR, st);
-    if (run_pfb) { TimedAttached t(h, RCF_T_PFB, pl); launch_pfb(bp.shape, pl, bp.pfb_zero_history, st, sr.n_wgs ? &sr : nullptr); }
-    if (run_pfb && pl.n_taps > 0) {
+    if (!bp.fir_by_depth.empty())
+        for (auto &j : bp.fir_by_depth[0]) launch_fir_job(h, j, j.dims.mfma ? RCF_T_FIR_MFMA : RCF_T_FIR, st);
+    if (bp.run_pfb) { TimedAttached t(h, RCF_T_PFB, pl); launch_pfb(bp.shape, pl, bp.pfb_zero_history, st, sr.n_wgs ? &sr : nullptr); }
+    if (bp.run_pfb && pl.n_taps > 0) {
         Timed t(h, RCF_T_TAPS);
         launch_tap_finalize(bp.d_tap_list, pl.n_taps, pl.tap_mat, pl.tap_pitch, pl.n_frames, pl.n_lo - pl.n_abs0,
                             h->ring_mask, h->d_atan, bp.d_group_bin0, pl.tap_first, pl.bins_ring, pl.NB, st);
     }
-    for (size_t d = 1; d < fir_by_depth.size(); ++d)
-        for (auto &j : fir_by_depth[d]) {
+    for (size_t d = 1; d < bp.fir_by_depth.size(); ++d)
+        for (auto &j : bp.fir_by_depth[d]) {
             if (&j == lag_job) {                            // not queued: it rides in the next block's filterbank launch
                 h->lag.pending = true;
                 h->lag.dims = j.dims;

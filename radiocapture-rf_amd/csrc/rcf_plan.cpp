@@ -88,7 +88,7 @@ const rcf_t::PlanCache &plan_cache(rcf_t *h)
     need += 64 * (n_fir / 4 + 64);                        // per-class alignment slack
     pc.arena_need = need;
     // channels by depth, then by (D, T) class (a front-end has a handful of classes: linear search, then sorted -- the
-    // order classes are launched in is the key order, channels inside a class in id order, as it always was)
+    // order classes are launched in is the key order, channels inside a class in id order)
     pc.by_depth.assign((size_t)pc.max_depth + 1, {});
     for (auto &kv : h->chans) {
         Chan *c = kv.second.get();
@@ -209,368 +209,331 @@ int plan_pfb(rcf_t *h, BlockPlan &bp)
     return RCF_OK;
 }
 
-// one channel's launch records (FIR / tap, discriminator, symbol filter, AGC, symbol clock, Gardner / Costas loop, C4FM loop, voice chain, exact rotator) and the advance of
-// its state.  Returns RCF_OK also when the channel has nothing to do in this block.
-int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c, int D)
-{
-    const int64_t S0 = bp.S0, S1 = bp.S1;
-    const uint64_t serial = bp.serial;
-    auto &launches = cp.launches;
-    auto &launched = cp.launched;
-    auto &discs = cp.discs;
-    int &max_n = cp.max_n;
-    bool &shared_src = cp.shared_src;
-    auto &rot_fills = bp.rot_fills;
-    auto &tap_list = bp.tap_list;
-    auto &tap_bins = bp.tap_bins;
-    auto reach = [&](int id) { return bp.reach(id); };
+// ---- a channel's share of a block, in two steps: its source's new range, then what the channel makes of it.  plan_channel()
+// and the dry pass (check_block_capacity) both take them, so the pass that refuses and the pass that plans cannot disagree.
+namespace {
 
-    SrcRange sr{};
-    if (c->src >= 0 && c->src < RCF_SRC_PFB_BIN0) {
-        auto it = h->chans.find(c->src);
-        if (it == h->chans.end()) return RCF_OK;            // source closed: channel starves
-        const Chan &sc_ = *it->second;
-        const bool fresh = sc_.blk_serial == serial;
-        sr.view.base = sc_.d_iq;
-        sr.view.mask = h->ring_mask;
-        sr.view.origin = 0;
-        sr.view.stride = 1;
-        sr.p0 = fresh ? sc_.blk_before : sc_.produced;
-        sr.p1 = fresh ? sc_.blk_after : sc_.produced;
-    } else if (!source_range(h, c->src, S0, S1, &sr)) {
-        return RCF_OK;
-    }
-    if (c->src >= 0) shared_src = false;
-    if (c->src < RCF_SRC_PFB_BIN0) cp.all_bank_src = false;
-    const int64_t k_lo = std::max(ceil_div(sr.p0, D), c->k_abs0);
-    const int64_t k_hi = floor_div(sr.p1 - 1, D);
-    const int64_t before = c->produced;
-    if (sr.p1 <= sr.p0 || k_hi < k_lo) { c->blk_serial = serial; c->blk_before = c->blk_after = before; return RCF_OK; }
-    const int64_t cnt = k_hi - k_lo + 1;
-    if ((size_t)cnt + reach(c->id) > h->out_cap) {
+typedef std::pair<int64_t, int64_t> Range;     // [first, second)
+
+// c's source in this block -- the wideband stream, a filterbank bin or another channel: its new samples and the view a
+// kernel reads them through.  false: the source is closed, c starves.  What the block gave a source CHANNEL is the one
+// thing the two passes know differently: chained(source) says it.
+template <class Chained> bool block_source(rcf_t *h, const BlockPlan &bp, const Chan &c, Chained &&chained, SrcRange *sr)
+{
+    if (c.src < 0 || c.src >= RCF_SRC_PFB_BIN0) return source_range(h, c.src, bp.S0, bp.S1, sr);
+    auto it = h->chans.find(c.src);
+    if (it == h->chans.end()) return false;
+    sr->view.base = it->second->d_iq;
+    sr->view.mask = h->ring_mask;
+    sr->view.origin = 0;
+    sr->view.stride = 1;
+    const Range r = chained(*it->second);
+    sr->p0 = r.first;
+    sr->p1 = r.second;
+    return true;
+}
+
+struct Share {
+    int64_t k_lo = 0, cnt = 0;      // outputs k_lo .. k_lo + cnt - 1 in the channel's absolute index; cnt == 0: none in this block
+    int64_t n_lo = 0;               // k_lo relative to the channel's first output
+    int64_t a_lo = 0, a_n = 0;      // a voice chain's part of them, from its start on (a_n <= 0: nothing yet)
+};
+
+// What c makes of its source's new samples [p0, p1) -- and the one place a block is refused for a ring too small: the
+// channel's own (its outputs plus what its consumers still read behind them) or its voice chain's.  *s: a fresh Share.
+// (Inlined: plan_channel takes this step for every channel of every block.)
+__forceinline__ int block_share(const rcf_t *h, const BlockPlan &bp, const Chan &c, int64_t p0, int64_t p1, Share *s)
+{
+    const int64_t k_lo = std::max(ceil_div(p0, c.D), c.k_abs0);
+    const int64_t k_hi = floor_div(p1 - 1, c.D);
+    if (p1 <= p0 || k_hi < k_lo) return RCF_OK;
+    s->k_lo = k_lo;
+    s->cnt = k_hi - k_lo + 1;
+    s->n_lo = k_lo - c.k_abs0;
+    if ((size_t)s->cnt + bp.reach(c.id) > h->out_cap) {
         set_error("block yields %lld outputs (+%zu of history its consumers need) > ring capacity %zu",
-                  (long long)cnt, reach(c->id), h->out_cap);
+                  (long long)s->cnt, bp.reach(c.id), h->out_cap);
         return RCF_ECAP;
     }
+    if (c.audio) {
+        s->a_lo = std::max(s->n_lo, c.audio->from);
+        s->a_n = s->n_lo + s->cnt - s->a_lo;
+        if (s->a_n > 0 && (size_t)s->a_n + c.audio->reach() > h->out_cap) {
+            set_error("block yields %lld channel samples: audio rings of %zu too small", (long long)s->a_n, h->out_cap);
+            return RCF_ECAP;
+        }
+    }
+    return RCF_OK;
+}
+
+}  // namespace
+
+// one channel's launch records and the advance of its state: range -> tap record or FIR record (+ exact-rotator fill) and
+// discriminator record -> stages -> advance.  Returns RCF_OK also when the channel has nothing to do in this block.
+int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c)
+{
+    Chan::Pos &pos = c->pos;
+    SrcRange sr{};
+    const auto live = [&bp](const Chan &sc) {      // the source was planned before c (a smaller depth): its counters say
+        const Chan::Pos &q = sc.pos;
+        return q.blk_serial == bp.serial ? Range{q.blk_before, q.blk_after} : Range{q.produced, q.produced};
+    };
+    if (!block_source(h, bp, *c, live, &sr)) return RCF_OK;
+    if (c->src >= 0) cp.shared_src = false;
+    if (c->src < RCF_SRC_PFB_BIN0) cp.all_bank_src = false;
+    Share s;
+    const int rc = block_share(h, bp, *c, sr.p0, sr.p1, &s);
+    if (rc != RCF_OK) return rc;
+    const int64_t before = pos.produced;
+    if (s.cnt == 0) { pos.blk_serial = bp.serial; pos.blk_before = pos.blk_after = before; return RCF_OK; }
     if (c->is_tap) {                            // served through the tap matrix, not by a FIR launch: its own short record
         TapLaunch tl{};
         tl.iq_ring = c->d_iq;
         tl.fm_ring = c->d_fm;
-        tl.k_lo = k_lo; tl.k_abs0 = c->k_abs0; tl.n_seg0 = c->n_seg0;
-        tl.angle0 = (double)c->angle0; tl.dangle = c->dangle; tl.logmag0 = c->logmag0; tl.dlogmag = c->dlogmag;
-        tl.n_k = (int32_t)cnt;
+        tl.k_lo = s.k_lo; tl.k_abs0 = c->k_abs0; tl.n_seg0 = pos.n_seg0;
+        tl.angle0 = (double)pos.angle0; tl.dangle = c->dangle; tl.logmag0 = pos.logmag0; tl.dlogmag = c->dlogmag;
+        tl.n_k = (int32_t)s.cnt;
         tl.bin = c->src - RCF_SRC_PFB_BIN0;
         tl.fm_only = c->fm_only ? 1 : 0;
-        tap_list.push_back(tl);
-        tap_bins.push_back(tl.bin);
+        bp.tap_list.push_back(tl);
+        bp.tap_bins.push_back(tl.bin);
+    } else {
+        ChanLaunch L{};
+        L.ctaps = c->d_ctaps;
+        L.fm_ring = c->d_fm;
+        L.iq_ring = c->d_iq;
+        L.src = sr.view;
+        L.k_lo = s.k_lo;
+        L.k_abs0 = c->k_abs0;
+        L.start_sample = c->start_sample;
+        L.n_seg0 = pos.n_seg0;
+        L.angle0 = (double)pos.angle0;
+        L.dangle = c->dangle;
+        L.logmag0 = pos.logmag0;
+        L.dlogmag = c->dlogmag;
+        L.n_k = (int32_t)s.cnt;
+        // exact rotator: plain channels only (a filterbank tap's rotator carries the bank's own phases too)
+        if (c->d_rot && c->extra_dangle == 0.0 && c->extra_dlogmag == 0.0) {
+            L.rot_ring = c->d_rot;
+            L.rot_mask = h->ring_mask;
+            RotFill rf{};
+            rf.ring = c->d_rot;
+            rf.state = reinterpret_cast<float *>(c->d_rot + h->out_cap);
+            rf.n_from = s.n_lo;
+            rf.n_k = (int32_t)s.cnt;
+            rf.incr_re = c->incr[0];
+            rf.incr_im = c->incr[1];
+            bp.rot_fills.push_back(rf);
+        }
+        DiscLaunch dl{};
+        dl.iq_ring = c->d_iq;
+        dl.fm_ring = c->d_fm;
+        dl.n_lo = s.n_lo;
+        dl.n_k = (int32_t)s.cnt;
+        cp.launches.push_back(L);
+        cp.launched.push_back(c);
+        cp.discs.push_back(dl);
+        cp.max_n = std::max(cp.max_n, (int)s.cnt);
     }
-    ChanLaunch L{};
-    if (!c->is_tap) {
-    L.ctaps = c->d_ctaps;
-    L.fm_ring = c->d_fm;
-    L.iq_ring = c->d_iq;
-    L.src = sr.view;
-    L.k_lo = k_lo;
-    L.k_abs0 = c->k_abs0;
-    L.start_sample = c->start_sample;
-    L.n_seg0 = c->n_seg0;
-    L.angle0 = (double)c->angle0;
-    L.dangle = c->dangle;
-    L.logmag0 = c->logmag0;
-    L.dlogmag = c->dlogmag;
-    L.n_k = (int32_t)cnt;
-    // exact rotator: plain channels only (a filterbank tap's rotator carries the bank's own phases too)
-    if (c->d_rot && !c->is_tap && c->extra_dangle == 0.0 && c->extra_dlogmag == 0.0) {
-        L.rot_ring = c->d_rot;
-        L.rot_mask = h->ring_mask;
-        RotFill rf{};
-        rf.ring = c->d_rot;
-        rf.state = reinterpret_cast<float *>(c->d_rot + h->out_cap);
-        rf.n_from = k_lo - c->k_abs0;
-        rf.n_k = (int32_t)cnt;
-        rf.incr_re = c->incr[0];
-        rf.incr_im = c->incr[1];
-        rot_fills.push_back(rf);
-    }
-    }
-    DiscLaunch dl{};
-    dl.iq_ring = c->d_iq;
-    dl.fm_ring = c->d_fm;
-    dl.n_lo = k_lo - c->k_abs0;
-    dl.n_k = (int32_t)cnt;
-    if (!c->is_tap) {
-        launches.push_back(L);
-        launched.push_back(c);
-        discs.push_back(dl);
-        max_n = std::max(max_n, (int)cnt);
-    }
-    // a stage's share of the block: the new outputs from the stage's start on -> (n_lo, n_k); n_k <= 0: nothing yet
-    auto since = [&dl](int64_t from, int64_t *n_lo) { *n_lo = std::max(dl.n_lo, from); return (int32_t)(dl.n_lo + dl.n_k - *n_lo); };
-    if (const Chan::Sym *sy = c->sym.get()) {
-        FmFirLaunch fl{};
-        fl.fm_ring = c->d_fm;
-        fl.sym_ring = sy->d_ring;
-        fl.taps = sy->d_taps;
-        fl.gain = sy->gain;
-        fl.ntaps = sy->ntaps;
-        fl.n_first = sy->from;
-        fl.n_k = since(sy->from, &fl.n_lo);
-        if (fl.n_k > 0) bp.tails.symf.add(fl);       // (Sym::from never exceeds `produced`: n_k is the block's count)
-    }
-    if (const Chan::Agc *ag = c->agc.get()) {
-        AgcLaunch al{};
-        al.iq_ring = c->d_iq;
-        al.agc_ring = ag->d_ring;
-        al.reference = ag->ref;
-        al.nsamples = ag->n;
-        al.n_first = ag->from;
-        al.n_k = since(ag->from, &al.n_lo);
-        if (al.n_k > 0) bp.tails.agcf.add(al);
-    }
-    if (const Chan::Clock *ck = c->clock.get()) {
-        ClockLaunch cl{};
-        cl.fm_ring = c->d_fm;
-        cl.sym_ring = ck->d_ring;
-        cl.st = ck->d_state;
-        cl.taps = ck->d_bank;
-        cl.n_first = ck->from;
-        cl.n_k = since(ck->from, &cl.n_lo);
-        cl.adv0 = ck->adv0;
-        cl.gain = ck->gain; cl.mu0 = ck->mu0; cl.omega_mid = ck->omega_mid; cl.omega_lim = ck->omega_lim;
-        cl.gain_omega = ck->gain_omega; cl.gain_mu = ck->gain_mu;
-        if (cl.n_k > 0) bp.tails.clkf.add(cl);
-    }
-    if (const Chan::Costas *gc = c->costas.get()) {
-        CostasLaunch gl{};
-        gl.agc_ring = c->agc->d_ring;                // (attached only behind an AGC, which cannot go before it: rcf_stage.cpp)
-        gl.sym_ring = gc->d_ring;
-        gl.st = gc->d_state;
-        gl.taps = gc->d_bank;
-        gl.n_k = since(std::max(gc->from, c->agc->from), &gl.n_lo);
-        gl.window = gc->window;
-        gl.omega_mid = gc->omega_mid; gl.omega_lim = gc->omega_lim; gl.gain_omega = gc->gain_omega; gl.gain_mu = gc->gain_mu;
-        gl.alpha = gc->alpha; gl.beta = gc->beta; gl.max_freq = gc->max_freq;
-        if (gl.n_k > 0) bp.tails.gcf.add(gl);
-    }
-    if (const Chan::Fsk4 *fk = c->fsk4.get()) {
-        Fsk4Launch fl{};
-        fl.sym_ring = c->sym->d_ring;                // (attached only behind a symbol filter, which is never taken away: rcf_stage.cpp)
-        fl.out_ring = fk->d_ring;
-        fl.st = fk->d_state;
-        fl.taps = fk->d_bank;
-        fl.n_k = since(std::max(fk->from, c->sym->from), &fl.n_lo);
-        fl.time = fk->time; fl.k_spread = fk->k_spread; fl.k_timing = fk->k_timing; fl.k_fine = fk->k_fine;
-        fl.k_coarse = fk->k_coarse; fl.spread_min = fk->spread_min; fl.spread_max = fk->spread_max;
-        if (fl.n_k > 0) bp.tails.f4f.add(fl);
-    }
-    if (c->audio) {
-        Chan::Audio &au = *c->audio;
-        AudioLaunch al{};
-        al.iq_ring = c->d_iq;
-        al.st = au.d_state;
-        al.a_ring = au.d_rings;
-        al.l_ring = au.d_rings + h->out_cap;
-        al.h_ring = au.d_rings + 2 * h->out_cap;
-        al.o_ring = au.d_rings + 3 * h->out_cap;
-        al.c_ring = reinterpret_cast<float2 *>(au.d_rings + 4 * h->out_cap);
-        al.lpf = au.d_taps;
-        al.hpf = au.d_taps + au.n_lpf;
-        al.rs = au.d_taps + au.n_lpf + au.n_hpf;
-        al.n_k = since(au.from, &al.n_lo);
-        al.n_lpf = au.n_lpf; al.n_hpf = au.n_hpf; al.nt_rs = au.nt_rs;
-        al.interp = au.interp; al.decim = au.decim;
-        al.gain = au.gain;
-        al.thr = au.thr; al.alpha = au.alpha; al.b0 = au.b0; al.b1 = au.b1; al.fb1 = au.fb1;
-        if (al.n_k > 0) {
-            if ((size_t)al.n_k + au.reach() > h->out_cap) {
-                set_error("block yields %d channel samples: audio rings of %zu too small", al.n_k, h->out_cap);
-                return RCF_ECAP;
-            }
-            bp.audf.push_back(al);
-            bp.audf_max_n = std::max(bp.audf_max_n, (int)al.n_k);
-            if ((double)au.interp / au.decim > bp.audf_ratio) {
-                bp.audf_ratio = (double)au.interp / au.decim; bp.audf_num = au.interp; bp.audf_den = au.decim;
-            }
+    // a stage's step: its record as attached, the new outputs from the stage's start on -> (n_lo, n_k); n_k <= 0: nothing yet
+    const auto stage = [&s](auto rec, int64_t from, auto &recs) {
+        rec.n_lo = std::max(s.n_lo, from);
+        rec.n_k = (int32_t)(s.n_lo + s.cnt - rec.n_lo);
+        if (rec.n_k > 0) recs.add(rec);
+    };
+    if (c->sym) stage(c->sym->rec, c->sym->from, bp.tails.symf);       // (Sym::from never exceeds `produced`: n_k is the block's count)
+    if (c->agc) stage(c->agc->rec, c->agc->from, bp.tails.agcf);
+    if (c->clock) stage(c->clock->rec, c->clock->from, bp.tails.clkf);
+    // (the two loops behind another stage start where both have started: the AGC's start moves on a re-call)
+    if (c->costas) stage(c->costas->rec, std::max(c->costas->from, c->agc->from), bp.tails.gcf);
+    if (c->fsk4) stage(c->fsk4->rec, std::max(c->fsk4->from, c->sym->from), bp.tails.f4f);
+    if (c->audio && s.a_n > 0) {
+        AudioLaunch al = c->audio->rec;
+        al.n_lo = s.a_lo;
+        al.n_k = (int32_t)s.a_n;
+        bp.audf.push_back(al);
+        bp.audf_max_n = std::max(bp.audf_max_n, (int)al.n_k);
+        if ((double)al.interp / al.decim > bp.audf_ratio) {
+            bp.audf_ratio = (double)al.interp / al.decim; bp.audf_num = al.interp; bp.audf_den = al.decim;
         }
     }
     // advance channel state: rebase the rotator model at the next output index
-    const int64_t n_next = k_hi - c->k_abs0 + 1;
+    const int64_t n_next = s.n_lo + s.cnt;
     const int64_t r512 = n_next & ~(int64_t)511;
-    const long double adv = (long double)(n_next - c->n_seg0) * (long double)c->dangle;
-    c->logmag0 = (r512 > c->n_seg0) ? (double)(n_next - r512) * c->dlogmag
-                                    : c->logmag0 + (double)(n_next - c->n_seg0) * c->dlogmag;
-    c->angle0 = fmodl(c->angle0 + adv, (long double)kTwoPi);
-    c->n_seg0 = n_next;
-    c->produced = n_next;
-    c->blk_serial = serial; c->blk_before = before; c->blk_after = n_next;
+    const long double adv = (long double)(n_next - pos.n_seg0) * (long double)c->dangle;
+    pos.logmag0 = (r512 > pos.n_seg0) ? (double)(n_next - r512) * c->dlogmag
+                                      : pos.logmag0 + (double)(n_next - pos.n_seg0) * c->dlogmag;
+    pos.angle0 = fmodl(pos.angle0 + adv, (long double)kTwoPi);
+    pos.n_seg0 = n_next;
+    pos.produced = n_next;
+    pos.blk_serial = bp.serial; pos.blk_before = before; pos.blk_after = n_next;
     return RCF_OK;
 }
 
-// the launches of one (depth, D, T) class: matrix-core job (+ zero-history fix-ups), vector job, discriminator job
+// ---- the launches of one (depth, D, T) class, three decisions: which channels take the matrix-core launch (split_class),
+// the bank matrix that launch reads (plan_bank_matrix), and the jobs that result (plan_class_jobs)
+namespace {
+
+struct ClassSplit {
+    std::vector<ChanLaunch> clean, fixups, rest;    // matrix-core launch, its zero-history fix-ups, vector launch
+    std::vector<Chan *> clean_ch;
+    int n_common = 0;                               // outputs per channel of the matrix-core launch
+};
+
+// Matrix-core path: channels on one shared source with one common output range.  A channel that was just
+// opened still has outputs whose taps reach before its start (GR zero history) -- at most ceil((T-1)/D)
+// of them, four for the reference's shapes.  It joins the matrix-core launch anyway (which computes those
+// few outputs from real history, i.e. wrongly) and a vector-kernel launch AFTER it on the same stream
+// rewrites just those outputs with the per-tap mask: opening 16384 channels at once used to put one
+// whole block (70 ms) on the vector kernel.  Channels that start later inside the block keep the vector
+// kernel for that block.
+ClassSplit split_class(const rcf_t *h, ClassPlan &cp, int depth, int D, int T)
+{
+    ClassSplit sp;
+    sp.n_common = cp.max_n;
+    if (!(cp.shared_src && depth == 0 && mfma2_applicable(D, T, h->hist_cap, h->hist_cap + h->block_cap))) {
+        sp.rest.swap(cp.launches);
+        return sp;
+    }
+    int64_t k_common = -1;
+    for (auto &L : cp.launches)                                 // the range most channels share: the earliest
+        if (k_common < 0 || L.k_lo < k_common) { k_common = L.k_lo; sp.n_common = L.n_k; }
+    const auto common = [&](const ChanLaunch &L) { return L.k_lo == k_common && L.n_k == sp.n_common; };
+    const size_t n_ok = (size_t)std::count_if(cp.launches.begin(), cp.launches.end(), common);
+    if (n_ok == cp.launches.size()) {              // the steady state: the whole class, no record copied
+        sp.clean.swap(cp.launches);
+        sp.clean_ch.swap(cp.launched);
+    } else {
+        sp.clean.reserve(n_ok);
+        sp.clean_ch.reserve(n_ok);
+        for (size_t i = 0; i < cp.launches.size(); ++i) {
+            const ChanLaunch &L = cp.launches[i];
+            if (!common(L)) { sp.rest.push_back(L); continue; }
+            sp.clean.push_back(L);
+            sp.clean_ch.push_back(cp.launched[i]);
+        }
+    }
+    for (const ChanLaunch &L : sp.clean)
+        if (L.k_lo * D - L.start_sample < (int64_t)(T - 1)) {
+            // outputs k with k D - (T-1) < start: k < ceil((start + T - 1) / D)
+            const int64_t k_end = ceil_div(L.start_sample + (int64_t)(T - 1), D);
+            ChanLaunch F = L;
+            F.n_k = (int32_t)std::min<int64_t>(L.n_k, std::max<int64_t>(0, k_end - L.k_lo));
+            if (F.n_k > 0) sp.fixups.push_back(F);
+        }
+    // (no size limit on a class: every group of 32 channels has its own tap slab)
+    if ((int)sp.clean.size() < kM2MinChans) {
+        sp.rest.insert(sp.rest.end(), sp.clean.begin(), sp.clean.end());   // (order within a vector launch is free)
+        sp.clean.clear();
+        sp.clean_ch.clear();
+        sp.fixups.clear();
+    }
+    return sp;
+}
+
+// The class's bank matrix for the matrix-core job mj over `chans`: as cached when membership and taps are what it was built
+// from; else the job's pack launch rebuilds it -- all of it when it had to grow, otherwise the groups of 32 that changed.
+int plan_bank_matrix(rcf_t *h, Arena &ar, std::pair<int, int> cls_key, const std::vector<Chan *> &chans, FirJob &mj)
+{
+    const int T = cls_key.second;
+    rcf::BankCache &bc = h->banks[cls_key];
+    std::vector<std::pair<int, uint64_t>> key;
+    key.reserve(chans.size());
+    for (Chan *c : chans) key.push_back({c->id, c->taps_version});
+    mj.bc = nullptr;
+    mj.dirty = nullptr;
+    mj.repack = key != bc.key;
+    if (mj.repack) {
+        const size_t ng = (chans.size() + kM2Group - 1) / kM2Group;
+        // + one chunk of slack: the kernel prefetches one chunk past a group's last
+        const size_t need = ng * bank2_group_floats(T) + (size_t)kM2ChunkSteps * 1024;
+        const bool fresh = need > bc.cap;
+        // grow with headroom: a class that gains channels one by one must not reallocate each time
+        const int rc = grow_buried(h, bc.d, bc.cap, need, std::max(need, bc.cap + bc.cap / 2));
+        if (rc != RCF_OK) return rc;
+        if (!fresh) {
+            // rebuild only the groups of 32 whose membership or taps changed
+            std::vector<unsigned char> dirty(ng, 0);
+            for (size_t i = 0; i < key.size(); ++i)
+                if (i >= bc.key.size() || bc.key[i] != key[i]) dirty[i / kM2Group] = 1;
+            if (bc.key.size() > key.size())                      // the class shrank: its last group lost rows
+                dirty[ng - 1] = 1;
+            if (!ar.put(dirty, &mj.dirty)) return arena_full();
+        }
+        bc.key.clear();                           // stale until the pack launch is queued (FirJob::bc)
+        mj.bc = &bc;
+        mj.key = std::move(key);
+    }
+    mj.dims.bank = bc.d;
+    return RCF_OK;
+}
+
+}  // namespace
+
+// the jobs of the class: matrix-core job (+ zero-history fix-ups behind it), vector job, discriminator job
 int plan_class_jobs(rcf_t *h, BlockPlan &bp, ClassPlan &cp, int depth, std::pair<int, int> cls_key)
 {
+    if (cp.launches.empty()) return RCF_OK;
     const int D = cls_key.first, T = cls_key.second;
-    const size_t n = bp.n;
     Arena &ar = *bp.ar;
-    auto &fir_by_depth = bp.fir_by_depth;
-    auto &disc_jobs = bp.disc_jobs;
-    auto &launches = cp.launches;
-    auto &launched = cp.launched;
-    auto &discs = cp.discs;
-    const int max_n = cp.max_n;
-    const bool shared_src = cp.shared_src;
-
-    if (launches.empty()) return RCF_OK;
     FirJob job{};
     job.bank_src = cp.all_bank_src;
     job.dims.D = D; job.dims.T = T; job.dims.KT = choose_kt(D, T);
-    job.dims.chans_per_wg = shared_src ? 16 : 1;
-    job.dims.max_n_k = max_n;
+    job.dims.chans_per_wg = cp.shared_src ? 16 : 1;
+    job.dims.max_n_k = cp.max_n;
     job.dims.ring_mask = h->ring_mask;
     job.dims.atan_tab = h->d_atan;
-    // Matrix-core path: channels on one shared source with one common output range.  A channel that was just
-    // opened still has outputs whose taps reach before its start (GR zero history) -- at most ceil((T-1)/D)
-    // of them, four for the reference's shapes.  It joins the matrix-core launch anyway (which computes those
-    // few outputs from real history, i.e. wrongly) and a vector-kernel launch AFTER it on the same stream
-    // rewrites just those outputs with the per-tap mask: opening 16384 channels at once used to put one
-    // whole block (70 ms) on the vector kernel.  Channels that start later inside the block keep the vector
-    // kernel for that block.
-    std::vector<ChanLaunch> clean, rest, fixups;
-    std::vector<Chan *> clean_ch;
-    int n_common_of_clean = max_n;
-    if (shared_src && depth == 0 && mfma2_applicable(D, T, h->hist_cap, h->hist_cap + h->block_cap)) {
-        int64_t k_common = -1;
-        int32_t n_common = 0;
-        for (auto &L : launches)                                   // the range most channels share: the earliest
-            if (k_common < 0 || L.k_lo < k_common) { k_common = L.k_lo; n_common = L.n_k; }
-        n_common_of_clean = n_common;
-        size_t n_ok = 0;
-        for (const ChanLaunch &L : launches) n_ok += (L.k_lo == k_common && L.n_k == n_common) ? 1 : 0;
-        if (n_ok == launches.size()) {              // the steady state: the whole class, no record copied
-            clean.swap(launches);
-            clean_ch.swap(launched);
-        } else {
-            clean.reserve(n_ok);
-            clean_ch.reserve(n_ok);
-            for (size_t i = 0; i < launches.size(); ++i) {
-                const ChanLaunch &L = launches[i];
-                const bool ok = L.k_lo == k_common && L.n_k == n_common;
-                if (!ok) { rest.push_back(L); continue; }
-                clean.push_back(L);
-                clean_ch.push_back(launched[i]);
-            }
-        }
-        for (const ChanLaunch &L : clean)
-            if (L.k_lo * D - L.start_sample < (int64_t)(T - 1)) {
-                // outputs k with k D - (T-1) < start: k < ceil((start + T - 1) / D)
-                const int64_t k_end = ceil_div(L.start_sample + (int64_t)(T - 1), D);
-                ChanLaunch F = L;
-                F.n_k = (int32_t)std::min<int64_t>(L.n_k, std::max<int64_t>(0, k_end - L.k_lo));
-                if (F.n_k > 0) fixups.push_back(F);
-            }
-        // (no size limit on a class: every group of 32 channels has its own tap slab)
-        if ((int)clean.size() < kM2MinChans) {
-            rest.insert(rest.end(), clean.begin(), clean.end());   // (order within a vector launch is free)
-            clean.clear();
-            clean_ch.clear();
-            fixups.clear();
-        }
-    } else {
-        rest.swap(launches);
-    }
-    if (!clean.empty()) {
+    ClassSplit sp = split_class(h, cp, depth, D, T);
+    int rc;
+    if (!sp.clean.empty()) {
         FirJob mj = job;
-        mj.bc = nullptr;
-        rcf::BankCache &bc = h->banks[cls_key];
-        std::vector<std::pair<int, uint64_t>> key;
-        key.reserve(clean_ch.size());
-        for (Chan *c : clean_ch) key.push_back({c->id, c->taps_version});
-        mj.repack = key != bc.key;
-        mj.dirty = nullptr;
-        if (mj.repack) {
-            // + one chunk of slack: the kernel prefetches one chunk past a group's last
-            const size_t need = (size_t)((clean.size() + kM2Group - 1) / kM2Group) * bank2_group_floats(T) +
-                                (size_t)kM2ChunkSteps * 1024;
-            bool fresh = false;
-            if (need > bc.cap) {
-                // grow with headroom: a class that gains channels one by one must not reallocate each time
-                const size_t want = std::max(need, bc.cap + bc.cap / 2);
-                float *nd = nullptr;
-                RCF_HIP(hipMalloc(&nd, sizeof(float) * want));
-                bury(h, bc.d);
-                bc.d = nd;
-                bc.cap = want;
-                fresh = true;
-            }
-            if (!fresh) {
-                // rebuild only the groups of 32 whose membership or taps changed
-                const size_t ng = (clean.size() + kM2Group - 1) / kM2Group;
-                std::vector<unsigned char> dirty(ng, 0);
-                for (size_t i = 0; i < key.size(); ++i)
-                    if (i >= bc.key.size() || bc.key[i] != key[i]) dirty[i / kM2Group] = 1;
-                if (bc.key.size() > key.size())                      // the class shrank: its last group lost rows
-                    dirty[ng - 1] = 1;
-                if (!ar.put(dirty, &mj.dirty)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
-            }
-            bc.key.clear();                           // stale until the pack launch below is queued
-            mj.bc = &bc;
-            mj.key = key;
-        }
-        mj.dims.n_chans = (int)clean.size();
+        if ((rc = plan_bank_matrix(h, ar, cls_key, sp.clean_ch, mj)) != RCF_OK) return rc;
+        mj.dims.n_chans = (int)sp.clean.size();
         mj.dims.mfma = 1;
         mj.dims.chans_per_wg = 128;
-        mj.dims.bank = bc.d;
-        mj.dims.max_n_k = n_common_of_clean;
-        mj.dims.src_len = (int64_t)(h->hist_cap + n);
-        {
-            const MfmaPlan plan = mfma_plan((int)clean.size(), n_common_of_clean, T);
-            mj.dims.mfma_nt = plan.nt;
-            mj.dims.mfma_parts = plan.parts;
-            mj.dims.partial = nullptr;
-            if (plan.parts > 1) {
-                const size_t need = (size_t)plan.parts * clean.size() * (size_t)n_common_of_clean;
-                if (need > h->partial_cap) {
-                    float2 *np_ = nullptr;
-                    RCF_HIP(hipMalloc(&np_, sizeof(float2) * need));
-                    bury(h, h->d_partial);
-                    h->d_partial = np_;
-                    h->partial_cap = need;
-                }
-                mj.dims.partial = h->d_partial;
-            }
+        mj.dims.max_n_k = sp.n_common;
+        mj.dims.src_len = (int64_t)(h->hist_cap + bp.n);
+        const MfmaPlan plan = mfma_plan((int)sp.clean.size(), sp.n_common, T);
+        mj.dims.mfma_nt = plan.nt;
+        mj.dims.mfma_parts = plan.parts;
+        mj.dims.partial = nullptr;
+        if (plan.parts > 1) {                       // split-K: one slab of partial sums per part
+            const size_t need = (size_t)plan.parts * sp.clean.size() * (size_t)sp.n_common;
+            if ((rc = grow_buried(h, h->d_partial, h->partial_cap, need, need)) != RCF_OK) return rc;
+            mj.dims.partial = h->d_partial;
         }
-        if (!ar.put(clean, &mj.dev)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
-        fir_by_depth[depth].push_back(mj);
+        if (!ar.put(sp.clean, &mj.dev)) return arena_full();
+        bp.fir_by_depth[depth].push_back(mj);
     }
-    if (!fixups.empty()) {                          // queued behind the matrix-core launch: see above
+    if (!sp.fixups.empty()) {                       // queued behind the matrix-core launch: see split_class
         FirJob fj = job;
         fj.bc = nullptr;
         fj.repack = false;
         fj.dirty = nullptr;
-        fj.dims.n_chans = (int)fixups.size();
+        fj.dims.n_chans = (int)sp.fixups.size();
         fj.dims.max_n_k = 0;
-        for (auto &F : fixups) fj.dims.max_n_k = std::max(fj.dims.max_n_k, (int)F.n_k);
+        for (auto &F : sp.fixups) fj.dims.max_n_k = std::max(fj.dims.max_n_k, (int)F.n_k);
         fj.dims.small = 0;
         fj.dims.mfma = 0;
         fj.dims.chans_per_wg = 1;                   // per-channel n_k differ: one channel per workgroup
-        if (!ar.put(fixups, &fj.dev)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
-        fir_by_depth[depth].push_back(fj);
+        if (!ar.put(sp.fixups, &fj.dev)) return arena_full();
+        bp.fir_by_depth[depth].push_back(fj);
     }
-    if (!rest.empty()) {
-        job.dims.n_chans = (int)rest.size();
-        job.dims.small = (!shared_src && fir_small_outputs(D, T) > 0) ? 1 : 0;
+    if (!sp.rest.empty()) {
+        job.dims.n_chans = (int)sp.rest.size();
+        job.dims.small = (!cp.shared_src && fir_small_outputs(D, T) > 0) ? 1 : 0;
         // a group's block: launches whose records are self-contained (every channel its own source view) are merged
         // with the same class of the other front-ends -- the records stay on the host until the group has them all
-        if (bp.defer && job.dims.chans_per_wg == 1) job.host.swap(rest);
-        else if (!ar.put(rest, &job.dev)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
-        fir_by_depth[depth].push_back(std::move(job));
+        if (bp.defer && job.dims.chans_per_wg == 1) job.host.swap(sp.rest);
+        else if (!ar.put(sp.rest, &job.dev)) return arena_full();
+        bp.fir_by_depth[depth].push_back(std::move(job));
     }
-    if (!(job.dims.small && clean.empty())) {   // the small-T kernel writes the discriminator ring itself
+    if (!(job.dims.small && sp.clean.empty())) {   // the small-T kernel writes the discriminator ring itself
         DiscJob dj;
-        dj.host.swap(discs);
-        dj.max_n = max_n;
-        if (!bp.defer && !dj.upload(ar)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
-        disc_jobs.push_back(std::move(dj));
+        dj.host.swap(cp.discs);
+        dj.max_n = cp.max_n;
+        if (!bp.defer && !dj.upload(ar)) return arena_full();
+        bp.disc_jobs.push_back(std::move(dj));
     }
     return RCF_OK;
 }
@@ -579,28 +542,19 @@ int plan_class_jobs(rcf_t *h, BlockPlan &bp, ClassPlan &cp, int depth, std::pair
 int plan_tail(rcf_t *h, BlockPlan &bp)
 {
     Arena &ar = *bp.ar;
-    auto &tap_list = bp.tap_list;
-    auto &tap_bins = bp.tap_bins;
-    auto &rot_fills = bp.rot_fills;
-    auto &audf = bp.audf;
     PfbLaunch &pl = bp.pl;
-    const bool run_pfb = bp.run_pfb;
-    const TapLaunch *&d_tap_list = bp.d_tap_list;
-    const RotFill *&d_rot_fills = bp.d_rot_fills;
-    const AudioLaunch *&d_audf = bp.d_audf;
-
-    if (!tap_list.empty() && run_pfb) {
-        const size_t pitch = (tap_list.size() + 15) & ~size_t(15);      // slots, whole groups of 16
+    if (!bp.tap_list.empty() && bp.run_pfb) {
+        const size_t pitch = (bp.tap_list.size() + 15) & ~size_t(15);      // slots, whole groups of 16
         // Slot order: first every aligned run of 16 bins that is tapped completely (tap_finalize reads those from the
         // bank's ring: PfbLaunch::tap_first), then the remaining taps, which go through the matrix.
         const int NB = pl.NB;
         auto &first = bp.tap_first_of_bin;
         first.assign((size_t)NB, -1);
-        for (size_t i = 0; i < tap_list.size(); ++i)
-            if (first[tap_list[i].bin] < 0) first[tap_list[i].bin] = (int32_t)i;
+        for (size_t i = 0; i < bp.tap_list.size(); ++i)
+            if (first[bp.tap_list[i].bin] < 0) first[bp.tap_list[i].bin] = (int32_t)i;
         auto &ordered = bp.tap_ordered;
         ordered.clear();
-        ordered.reserve(tap_list.size());
+        ordered.reserve(bp.tap_list.size());
         std::vector<int32_t> group_bin0;
         group_bin0.reserve(pitch / 16);
         for (int b0 = 0; b0 + 16 <= NB && pl.fm_mode != 2; b0 += 16) {     // (fm_mode 2: the bank writes no bins ring to read runs from)
@@ -608,86 +562,58 @@ int plan_tail(rcf_t *h, BlockPlan &bp)
             for (int j = 0; j < 16 && full; ++j) full = first[b0 + j] >= 0;
             if (!full) continue;
             for (int j = 0; j < 16; ++j) {
-                ordered.push_back(tap_list[first[b0 + j]]);
-                tap_list[first[b0 + j]].bin = -1;               // taken
+                ordered.push_back(bp.tap_list[first[b0 + j]]);
+                bp.tap_list[first[b0 + j]].bin = -1;            // taken
             }
             group_bin0.push_back(b0);
         }
         pl.tap_first = (int32_t)ordered.size();
-        for (const TapLaunch &t : tap_list)
+        for (const TapLaunch &t : bp.tap_list)
             if (t.bin >= 0) ordered.push_back(t);
-        tap_list.swap(ordered);
+        bp.tap_list.swap(ordered);
         group_bin0.resize(pitch / 16, -1);
-        for (size_t i = 0; i < tap_list.size(); ++i) tap_bins[i] = tap_list[i].bin;
-        if (!ar.put(tap_bins, &pl.tap_bins) || !ar.put(tap_list, &d_tap_list) || !ar.put(group_bin0, &bp.d_group_bin0)) {
-            set_error("launch arena exhausted");
-            return RCF_ENOMEM;
-        }
+        for (size_t i = 0; i < bp.tap_list.size(); ++i) bp.tap_bins[i] = bp.tap_list[i].bin;
+        if (!ar.put(bp.tap_bins, &pl.tap_bins) || !ar.put(bp.tap_list, &bp.d_tap_list) || !ar.put(group_bin0, &bp.d_group_bin0))
+            return arena_full();
         // the matrix holds the slots from tap_first on and nothing else (every bin of a 1600-bin bank tapped, 2^25-sample
         // blocks: no matrix at all instead of 537 MB of it)
         const size_t mat_pitch = pitch - (size_t)pl.tap_first;
         const size_t need = mat_pitch * (size_t)pl.n_frames;
-        if (need > h->tapmat_cap) {
-            float2 *nm = nullptr;
-            RCF_HIP(hipMalloc(&nm, sizeof(float2) * need));
-            bury(h, h->d_tapmat);
-            h->d_tapmat = nm;
-            h->tapmat_cap = need;
-        }
+        const int rc = grow_buried(h, h->d_tapmat, h->tapmat_cap, need, need);
+        if (rc != RCF_OK) return rc;
         pl.tap_mat = h->d_tapmat;
         pl.tap_pitch = (int32_t)mat_pitch;
-        pl.n_taps = (int32_t)tap_list.size();
+        pl.n_taps = (int32_t)bp.tap_list.size();
     }
     // (a group's block: the exact-rotator fills and the tail stages of all members go out as one launch each)
-    if (!bp.defer && !rot_fills.empty() && !ar.put(rot_fills, &d_rot_fills)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
-    if (!bp.defer && !bp.tails.upload(ar)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
-    if (!audf.empty() && !ar.put(audf, &d_audf)) { set_error("launch arena exhausted"); return RCF_ENOMEM; }
+    if (!bp.defer && !bp.rot_fills.empty() && !ar.put(bp.rot_fills, &bp.d_rot_fills)) return arena_full();
+    if (!bp.defer && !bp.tails.upload(ar)) return arena_full();
+    if (!bp.audf.empty() && !ar.put(bp.audf, &bp.d_audf)) return arena_full();
     return RCF_OK;
 }
 
 // plan_channel() advances a channel's state as it goes, so a block must not be refused half way through the schedule
 // (the channels planned before the refusal would have counted outputs nobody computed).  The one refusal that depends on
 // the block is a ring too small for what the block yields: this pass walks the channels in dependency order WITHOUT
-// touching them and reports it first.  It only runs when the cheap bound in process_block() says a ring could overflow.
+// touching them -- what the block gives each one is kept in `dry`, where a channel chained on it finds its source range --
+// and reports it first.  It only runs when the cheap bound in plan_block() says a ring could overflow.
 int check_block_capacity(rcf_t *h, const BlockPlan &bp)
 {
-    std::unordered_map<int, std::pair<int64_t, int64_t>> dry;      // channel id -> produced (before, after) this block
+    std::unordered_map<int, Range> dry;            // channel id -> produced (before, after) this block
+    const auto in_dry = [&dry](const Chan &sc) {
+        auto it = dry.find(sc.id);
+        return it == dry.end() ? Range{sc.pos.produced, sc.pos.produced} : it->second;
+    };
     for (int depth = 0; depth <= bp.max_depth; ++depth)
         for (auto &kv : h->chans) {
             const Chan &c = *kv.second;
             if (c.depth != depth) continue;
-            int64_t p0, p1;
-            if (c.src < 0) { p0 = bp.S0; p1 = bp.S1; }
-            else if (c.src >= RCF_SRC_PFB_BIN0) {
-                if (!h->pfb.open) continue;
-                p0 = h->pfb.produced_before; p1 = h->pfb.produced;
-            } else {
-                auto sit = h->chans.find(c.src);
-                if (sit == h->chans.end()) continue;
-                auto dit = dry.find(c.src);
-                p0 = dit == dry.end() ? sit->second->produced : dit->second.first;
-                p1 = dit == dry.end() ? sit->second->produced : dit->second.second;
-            }
-            const int64_t k_lo = std::max(ceil_div(p0, c.D), c.k_abs0);
-            const int64_t k_hi = floor_div(p1 - 1, c.D);
-            if (p1 <= p0 || k_hi < k_lo) { dry[c.id] = {c.produced, c.produced}; continue; }
-            const int64_t cnt = k_hi - k_lo + 1;
-            if ((size_t)cnt + bp.reach(c.id) > h->out_cap) {
-                set_error("block yields %lld outputs (+%zu of history its consumers need) > ring capacity %zu",
-                          (long long)cnt, bp.reach(c.id), h->out_cap);
-                return RCF_ECAP;
-            }
-            if (c.audio) {
-                const Chan::Audio &au = *c.audio;
-                const int64_t n_lo = k_lo - c.k_abs0;
-                const int64_t a_lo = std::max<int64_t>(n_lo, au.from);
-                const int64_t a_n = n_lo + cnt - a_lo;
-                if (a_n > 0 && (size_t)a_n + au.reach() > h->out_cap) {
-                    set_error("block yields %lld channel samples: audio rings of %zu too small", (long long)a_n, h->out_cap);
-                    return RCF_ECAP;
-                }
-            }
-            dry[c.id] = {c.produced, k_hi - c.k_abs0 + 1};
+            SrcRange sr{};
+            if (!block_source(h, bp, c, in_dry, &sr)) continue;
+            Share s;
+            const int rc = block_share(h, bp, c, sr.p0, sr.p1, &s);
+            if (rc != RCF_OK) return rc;
+            dry[c.id] = {c.pos.produced, s.cnt ? s.n_lo + s.cnt : c.pos.produced};
         }
     return RCF_OK;
 }
@@ -695,10 +621,7 @@ int check_block_capacity(rcf_t *h, const BlockPlan &bp)
 void undo_block(rcf_t *h, BlockUndo &u)
 {
     if (!u.armed) return;
-    for (const BlockUndo::Saved &s : u.saved) {
-        s.c->produced = s.produced; s.c->n_seg0 = s.n_seg0; s.c->blk_before = s.blk_before; s.c->blk_after = s.blk_after;
-        s.c->blk_serial = s.blk_serial; s.c->angle0 = s.angle0; s.c->logmag0 = s.logmag0;
-    }
+    for (const BlockUndo::Saved &s : u.saved) s.c->pos = s.pos;
     if (h->pfb.open) h->pfb.produced = h->pfb.produced_before;
     h->blk_serial = u.serial_before;
     u.armed = false;
@@ -754,8 +677,8 @@ int plan_block(rcf_t *h, size_t n, BlockPlan &bp, BlockUndo &undo)
                     const char *nx = reinterpret_cast<const char *>(cls.second[ci + 6]);
                     __builtin_prefetch(nx); __builtin_prefetch(nx + 64); __builtin_prefetch(nx + 128); __builtin_prefetch(nx + 192);
                 }
-                undo.saved.push_back(BlockUndo::Saved{c, c->produced, c->n_seg0, c->blk_before, c->blk_after, c->blk_serial, c->angle0, c->logmag0});
-                if ((rc = plan_channel(h, bp, cp, c, cls.first.first)) != RCF_OK) return roll_back(rc);
+                undo.saved.push_back(BlockUndo::Saved{c, c->pos});
+                if ((rc = plan_channel(h, bp, cp, c)) != RCF_OK) return roll_back(rc);
             }
             RCF_PROF(3, "plan_channel (class)", tp);
             if ((rc = plan_class_jobs(h, bp, cp, depth, cls.first)) != RCF_OK) return roll_back(rc);

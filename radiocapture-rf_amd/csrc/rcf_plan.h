@@ -23,6 +23,20 @@ struct Arena {
         return true;
     }
 };
+inline int arena_full() { set_error("launch arena exhausted"); return RCF_ENOMEM; }     // what a failed put() comes to
+
+// A device buffer of the handle that has to hold `need` items: when it does not, one of `want` (>= need) is allocated in
+// its place and the old one buried -- launches queued earlier may still read it.
+template <class T> int grow_buried(rcf_t *h, T *&d, size_t &cap, size_t need, size_t want)
+{
+    if (need <= cap) return RCF_OK;
+    T *nd = nullptr;
+    RCF_HIP(hipMalloc(&nd, sizeof(T) * want));
+    bury(h, d);
+    d = nd;
+    cap = want;
+    return RCF_OK;
+}
 
 inline int choose_kt(int D, int T)
 {
@@ -115,7 +129,7 @@ struct BlockPlan {
     size_t arena_base = 0;
     Arena own_ar{nullptr, nullptr, 0, 0};
     Arena *ar = &own_ar;               // a member of a group plans into the group's arena instead
-    uint64_t serial = 0;               // Chan::blk_before / blk_after of this block carry it
+    uint64_t serial = 0;               // Chan::Pos::blk_before / blk_after of this block carry it
     std::vector<std::vector<FirJob>> fir_by_depth;
     std::vector<DiscJob> disc_jobs;
     TailStages tails;                  // symbol filters, AGCs, symbol loops: all channels of a stage in one launch
@@ -159,7 +173,7 @@ struct ClassPlan {
 
 // what planning a block changed in the handle, so that it can be taken back while nothing has been queued
 struct BlockUndo {
-    struct Saved { Chan *c; int64_t produced, n_seg0, blk_before, blk_after; uint64_t blk_serial; long double angle0; double logmag0; };
+    struct Saved { Chan *c; Chan::Pos pos; };
     std::vector<Saved> saved;
     uint64_t serial_before = 0;
     bool armed = false;
@@ -181,7 +195,7 @@ size_t arena_need_bound(rcf_t *h);
 const rcf_t::PlanCache &plan_cache(rcf_t *h);
 int plan_arena(rcf_t *h, BlockPlan &bp);
 int plan_pfb(rcf_t *h, BlockPlan &bp);
-int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c, int D);
+int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c);
 int plan_class_jobs(rcf_t *h, BlockPlan &bp, ClassPlan &cp, int depth, std::pair<int, int> cls_key);
 int plan_tail(rcf_t *h, BlockPlan &bp);
 int check_block_capacity(rcf_t *h, const BlockPlan &bp);

@@ -8,7 +8,7 @@ namespace rcfx {
 
 // ring, words per item, reader, and what a missing ring means
 struct StreamRow { const void *ring; uint32_t item_w; int64_t *cursor; const char *refusal; };
-static int stream_row(rcf_t *h, Chan *c, int kind, StreamRow *r)
+static int stream_row(Chan *c, int kind, StreamRow *r)
 {
     Chan::Agc *ag = c->agc.get();
     Chan::Sym *sy = c->sym.get();
@@ -19,12 +19,12 @@ static int stream_row(rcf_t *h, Chan *c, int kind, StreamRow *r)
     const StreamRow t[8] = {
         {c->fm_only ? nullptr : c->d_iq, 2, &c->rd_iq, "channel %d exposes its discriminator only (rcf_chan_set_fm_only)"},
         {c->d_fm, 1, &c->rd_fm, "channel %d has no discriminator ring"},
-        {ag ? ag->d_ring : nullptr, 2, ag ? &ag->rd : nullptr, "channel %d has no AGC"},
-        {sy ? sy->d_ring : nullptr, 1, sy ? &sy->rd : nullptr, "channel %d has no fm filter"},
-        {ck ? ck->d_ring : nullptr, 1, ck ? &ck->rd : nullptr, "channel %d has no symbol clock"},
-        {au ? au->d_rings + 3 * h->out_cap : nullptr, 1, au ? &au->rd : nullptr, "channel %d has no audio chain"},
-        {gc ? gc->d_ring : nullptr, 1, gc ? &gc->rd : nullptr, "channel %d has no Gardner / Costas stage"},
-        {fk ? fk->d_ring : nullptr, 1, fk ? &fk->rd : nullptr, "channel %d has no C4FM symbol loop (rcf_chan_fsk4)"},
+        {ag ? ag->rec.agc_ring : nullptr, 2, ag ? &ag->rd : nullptr, "channel %d has no AGC"},
+        {sy ? sy->rec.sym_ring : nullptr, 1, sy ? &sy->rd : nullptr, "channel %d has no fm filter"},
+        {ck ? ck->ring() : nullptr, 1, ck ? &ck->rd : nullptr, "channel %d has no symbol clock"},
+        {au ? au->rec.o_ring : nullptr, 1, au ? &au->rd : nullptr, "channel %d has no audio chain"},
+        {gc ? gc->ring() : nullptr, 1, gc ? &gc->rd : nullptr, "channel %d has no Gardner / Costas stage"},
+        {fk ? fk->ring() : nullptr, 1, fk ? &fk->rd : nullptr, "channel %d has no C4FM symbol loop (rcf_chan_fsk4)"},
     };
     if (!t[kind].ring) { set_error(t[kind].refusal, c->id); return RCF_ESTATE; }
     *r = t[kind];
@@ -41,9 +41,9 @@ int stage_state(rcf_t *h, const void *d_state, void *st, size_t bytes)
 int chan_stream(rcf_t *h, Chan *c, int kind, RingStream *s, int64_t *aux)
 {
     StreamRow r;
-    int rc = stream_row(h, c, kind, &r);
+    int rc = stream_row(c, kind, &r);
     if (rc != RCF_OK) return rc;
-    int64_t end = c->produced, beside = 0;
+    int64_t end = c->pos.produced, beside = 0;
     const void *loop = kind == kReadClock ? c->clock->counters() : kind == kReadCostas ? c->costas->counters()
                      : kind == kReadFsk4 ? c->fsk4->counters() : nullptr;
     if (loop) {                                      // the three loops alike
@@ -53,8 +53,8 @@ int chan_stream(rcf_t *h, Chan *c, int kind, RingStream *s, int64_t *aux)
         beside = n_out_slips[1];
     } else if (kind == kReadAudio) {
         AudioState st{};
-        if ((rc = stage_state(h, c->audio->d_state, &st, sizeof(st))) != RCF_OK) return rc;
-        const int64_t I = c->audio->interp, D = c->audio->decim;
+        if ((rc = stage_state(h, c->audio->rec.st, &st, sizeof(st))) != RCF_OK) return rc;
+        const int64_t I = c->audio->rec.interp, D = c->audio->rec.decim;
         end = (st.n_a * I + D - 1) / D;
         beside = st.n_a;
     }
@@ -211,7 +211,7 @@ static int chan_rings(rcf_t *h, int chan_id, int kind, bool always, void **ring,
     FIND_CHAN(h, chan_id, c);
     if (ring || always) {
         StreamRow r;
-        const int rc = stream_row(h, c, kind, &r);
+        const int rc = stream_row(c, kind, &r);
         if (rc != RCF_OK) return rc;
         if (ring) *ring = const_cast<void *>(r.ring);
     }

@@ -10,9 +10,9 @@
 
 namespace rcfx {
 
-void Chan::Sym::release(rcf_t *h) { bury(h, d_ring); bury(h, d_taps); d_ring = d_taps = nullptr; }
-void Chan::Agc::release(rcf_t *h) { bury(h, d_ring); d_ring = nullptr; }
-void Chan::Audio::release(rcf_t *h) { bury(h, d_state); bury(h, d_rings); bury(h, d_taps); d_state = nullptr; d_rings = d_taps = nullptr; }
+void Chan::Sym::release(rcf_t *h) { bury(h, rec.sym_ring); bury(h, const_cast<float *>(rec.taps)); rec.sym_ring = nullptr; rec.taps = nullptr; }
+void Chan::Agc::release(rcf_t *h) { bury(h, rec.agc_ring); rec.agc_ring = nullptr; }
+void Chan::Audio::release(rcf_t *h) { bury(h, rec.st); bury(h, rec.a_ring); bury(h, const_cast<float *>(rec.lpf)); rec = AudioLaunch{}; }
 
 }  // namespace rcfx
 
@@ -55,10 +55,10 @@ static int attach_loop(rcf_t *h, Chan *c, std::unique_ptr<R> &stage, std::unique
     if (!hip_ok(hipMemcpy(fresh.p + state_at, &st0, sizeof(st0), hipMemcpyHostToDevice), state_copy) ||
         (interp_taps && !hip_ok(hipMemcpy(fresh.p + bank_at, interp_taps, sizeof(float) * kBank, hipMemcpyHostToDevice), "hipMemcpy(interpolator bank)")))
         return RCF_EHIP;
-    k->d_ring = fresh.take();
-    k->d_state = reinterpret_cast<typename R::State *>(k->d_ring + state_at);
-    k->d_bank = interp_taps ? k->d_ring + bank_at : h->d_mmse;
-    k->from = c->produced;
+    k->ring() = fresh.take();
+    k->rec.st = reinterpret_cast<typename R::State *>(k->ring() + state_at);
+    k->rec.taps = interp_taps ? k->ring() + bank_at : h->d_mmse;
+    k->from = c->pos.produced;
     drop_stage(h, stage);
     stage = std::move(k);
     ++h->chans_epoch;
@@ -81,13 +81,15 @@ int rcf_chan_fm_filter(rcf_t *h, int chan_id, float gain, const float *taps, int
         RCF_HIP(d_ring.alloc(h->out_cap));
         RCF_HIP(hipMemsetAsync(d_ring.p, 0, sizeof(float) * h->out_cap, h->stream));
         c->sym.reset(new Chan::Sym);
-        c->sym->d_ring = d_ring.take();
-        c->sym->from = c->sym->rd = c->produced;     // a new GR block starts with zero history
+        c->sym->rec.fm_ring = c->d_fm;
+        c->sym->rec.sym_ring = d_ring.take();
+        c->sym->from = c->sym->rec.n_first = c->sym->rd = c->pos.produced;     // a new GR block starts with zero history
     }
-    bury(h, c->sym->d_taps);                         // a second call: new taps and gain from the next block on, nothing else
-    c->sym->d_taps = d_taps.take();
-    c->sym->ntaps = ntaps;
-    c->sym->gain = gain;
+    FmFirLaunch &rec = c->sym->rec;
+    bury(h, const_cast<float *>(rec.taps));          // a second call: new taps and gain from the next block on, nothing else
+    rec.taps = d_taps.take();
+    rec.ntaps = ntaps;
+    rec.gain = gain;
     ++h->chans_epoch;
     return RCF_OK;
 }
@@ -109,11 +111,12 @@ int rcf_chan_agc(rcf_t *h, int chan_id, int nsamples, float reference)
         RCF_HIP(d_ring.alloc(h->out_cap));
         RCF_HIP(hipMemsetAsync(d_ring.p, 0, sizeof(float2) * h->out_cap, h->stream));
         c->agc.reset(new Chan::Agc);
-        c->agc->d_ring = d_ring.take();
+        c->agc->rec.iq_ring = c->d_iq;
+        c->agc->rec.agc_ring = d_ring.take();
     }
-    c->agc->n = nsamples;
-    c->agc->ref = reference;
-    c->agc->from = c->agc->rd = c->produced;         // a new GR block starts with zero history
+    c->agc->rec.nsamples = nsamples;
+    c->agc->rec.reference = reference;
+    c->agc->from = c->agc->rec.n_first = c->agc->rd = c->pos.produced;         // a new GR block starts with zero history
     ++h->chans_epoch;
     return RCF_OK;
 }
@@ -141,13 +144,16 @@ int rcf_chan_clock_mm(rcf_t *h, int chan_id, const rcf_clock_mm_params_t *p)
     if (!p) return stage_off(h, c->clock);
     if ((size_t)kClockTaps * 2 > h->out_cap) { set_error("ring of %zu too small for the clock's %d-sample window", h->out_cap, kClockTaps); return RCF_ECAP; }
     std::unique_ptr<Chan::Clock> k(new Chan::Clock);
-    k->gain = p->gain; k->mu0 = p->mu; k->omega_mid = p->omega;
-    k->omega_lim = k->omega_mid * p->omega_relative_limit;               // (one float product)
-    k->gain_omega = p->gain_omega; k->gain_mu = p->gain_mu;
-    k->adv0 = (int)std::ceil(k->omega_mid);
+    ClockLaunch &r = k->rec;                                             // the constants as the kernel takes them, rounded to float once
+    r.fm_ring = c->d_fm;
+    r.n_first = c->pos.produced;                                         // (== Loop::from: attach_loop)
+    r.gain = p->gain; r.mu0 = p->mu; r.omega_mid = p->omega;
+    r.omega_lim = r.omega_mid * p->omega_relative_limit;                 // (one float product)
+    r.gain_omega = p->gain_omega; r.gain_mu = p->gain_mu;
+    r.adv0 = (int)std::ceil(r.omega_mid);
     ClockState st0{};
-    st0.p = c->produced - (kClockTaps - 1);                              // the first window: seven zeros and u[first]
-    st0.mu = k->mu0; st0.omega = k->omega_mid; st0.last = 0.f;
+    st0.p = c->pos.produced - (kClockTaps - 1);                          // the first window: seven zeros and u[first]
+    st0.mu = r.mu0; st0.omega = r.omega_mid; st0.last = 0.f;
     return attach_loop(h, c, c->clock, std::move(k), st0, p->interp_taps, "hipMemcpy(clock state)");
 }
 
@@ -174,11 +180,13 @@ int rcf_chan_costas(rcf_t *h, int chan_id, const rcf_costas_params_t *p)
     if (!c->agc) { set_error("channel %d has no AGC for the Gardner / Costas stage to read", chan_id); return RCF_ESTATE; }
     if (h->out_cap < 64) { set_error("ring of %zu too small for the Gardner / Costas stage", h->out_cap); return RCF_ECAP; }
     std::unique_ptr<Chan::Costas> k(new Chan::Costas);
-    k->omega_mid = p->omega; k->omega_lim = p->omega_limit; k->gain_omega = p->gain_omega; k->gain_mu = p->gain_mu;
-    k->alpha = p->alpha; k->beta = p->beta; k->max_freq = p->max_freq;
-    k->window = std::max(2 * (int)std::ceil(k->omega_mid), (int)std::floor(k->omega_mid / 2) + 9);
+    CostasLaunch &r = k->rec;
+    r.agc_ring = c->agc->rec.agc_ring;                                   // (the AGC keeps its ring on a re-call and cannot go before this stage: rcf_chan_agc)
+    r.omega_mid = p->omega; r.omega_lim = p->omega_limit; r.gain_omega = p->gain_omega; r.gain_mu = p->gain_mu;
+    r.alpha = p->alpha; r.beta = p->beta; r.max_freq = p->max_freq;
+    r.window = std::max(2 * (int)std::ceil(r.omega_mid), (int)std::floor(r.omega_mid / 2) + 9);
     CostasState st0{};
-    st0.mu = st0.omega = k->omega_mid;
+    st0.mu = st0.omega = r.omega_mid;
     return attach_loop(h, c, c->costas, std::move(k), st0, p->interp_taps, "hipMemcpy(Gardner / Costas state)");
 }
 
@@ -190,7 +198,7 @@ int rcf_chan_costas_state(rcf_t *h, int chan_id, rcf_costas_state_t *out)
     FIND_CHAN(h, chan_id, c);
     if (!c->costas) { set_error("channel %d has no Gardner / Costas stage", chan_id); return RCF_ESTATE; }
     CostasState st{};                   // (its front, not the history behind it)
-    const int rc = stage_state(h, c->costas->d_state, &st, offsetof(CostasState, hist));
+    const int rc = stage_state(h, c->costas->rec.st, &st, offsetof(CostasState, hist));
     if (rc != RCF_OK) return rc;
     out->n_symbols = st.n_out; out->n_slips = st.slips;
     out->mu = st.mu; out->omega = st.omega; out->freq = st.freq; out->phase = st.phase;
@@ -219,9 +227,11 @@ int rcf_chan_fsk4(rcf_t *h, int chan_id, const rcf_fsk4_params_t *p)
     if (!c->sym) { set_error("channel %d has no symbol filter (rcf_chan_fm_filter) for the C4FM loop to read", chan_id); return RCF_ESTATE; }
     if (h->out_cap < 16) { set_error("ring of %zu too small for the C4FM loop", h->out_cap); return RCF_ECAP; }
     std::unique_ptr<Chan::Fsk4> k(new Chan::Fsk4);
-    k->time = p->symbol_rate / p->sample_rate;
-    k->k_spread = p->k_spread; k->k_timing = p->k_timing; k->k_fine = p->k_fine; k->k_coarse = p->k_coarse;
-    k->spread_min = p->spread_min; k->spread_max = p->spread_max;
+    Fsk4Launch &r = k->rec;
+    r.sym_ring = c->sym->rec.sym_ring;                                   // (the symbol filter keeps its ring on a re-call and is never taken away)
+    r.time = p->symbol_rate / p->sample_rate;
+    r.k_spread = p->k_spread; r.k_timing = p->k_timing; r.k_fine = p->k_fine; r.k_coarse = p->k_coarse;
+    r.spread_min = p->spread_min; r.spread_max = p->spread_max;
     Fsk4State st0{};
     st0.spread = 2.0;
     return attach_loop(h, c, c->fsk4, std::move(k), st0, p->interp_taps, "hipMemcpy(C4FM loop state)");
@@ -235,7 +245,7 @@ int rcf_chan_fsk4_state(rcf_t *h, int chan_id, rcf_fsk4_state_t *out)
     FIND_CHAN(h, chan_id, c);
     if (!c->fsk4) { set_error("channel %d has no C4FM symbol loop (rcf_chan_fsk4)", chan_id); return RCF_ESTATE; }
     Fsk4State st{};
-    const int rc = stage_state(h, c->fsk4->d_state, &st, offsetof(Fsk4State, hist));
+    const int rc = stage_state(h, c->fsk4->rec.st, &st, offsetof(Fsk4State, hist));
     if (rc != RCF_OK) return rc;
     out->n_symbols = st.n_out; out->n_slips = st.slips;
     out->clock = st.clock; out->spread = st.spread; out->fine = st.fine; out->coarse = st.coarse;
@@ -258,13 +268,14 @@ int rcf_chan_audio_open(rcf_t *h, int chan_id, const rcf_audio_params_t *p)
     const size_t reach = (size_t)std::max(std::max(p->n_lpf, p->n_hpf), n_rs_pad / I);
     if (reach * 2 > h->out_cap) { set_error("ring of %zu too small for %zu-tap audio filters", h->out_cap, reach); return RCF_ECAP; }
     std::unique_ptr<Chan::Audio> au(new Chan::Audio);
-    au->n_lpf = p->n_lpf; au->n_hpf = p->n_hpf; au->nt_rs = n_rs_pad / I;
-    au->interp = I; au->decim = p->decimation;
-    au->gain = p->quad_gain;
-    au->thr = std::pow(10.0, p->squelch_db / 10);                // pwr_squelch_cc::set_threshold
-    au->alpha = p->squelch_alpha;
+    AudioLaunch &r = au->rec;
+    r.n_lpf = p->n_lpf; r.n_hpf = p->n_hpf; r.nt_rs = n_rs_pad / I;
+    r.interp = I; r.decim = p->decimation;
+    r.gain = p->quad_gain;
+    r.thr = std::pow(10.0, p->squelch_db / 10);                  // pwr_squelch_cc::set_threshold
+    r.alpha = p->squelch_alpha;
     // iir_filter(fftaps, fbtaps, oldstyle = false): feedback taps are negated, a[0] must be 1
-    au->b0 = p->deemph_b[0]; au->b1 = p->deemph_b[1]; au->fb1 = -p->deemph_a[1];
+    r.b0 = p->deemph_b[0]; r.b1 = p->deemph_b[1]; r.fb1 = -p->deemph_a[1];
     std::vector<float> taps((size_t)p->n_lpf + p->n_hpf + n_rs_pad, 0.0f);
     std::memcpy(taps.data(), p->lpf_taps, sizeof(float) * (size_t)p->n_lpf);
     std::memcpy(taps.data() + p->n_lpf, p->hpf_taps, sizeof(float) * (size_t)p->n_hpf);
@@ -279,8 +290,14 @@ int rcf_chan_audio_open(rcf_t *h, int chan_id, const rcf_audio_params_t *p)
     st0.muted = 1;                                               // squelch_base_cc starts in ST_MUTED
     RCF_HIP(d_state.alloc(1));
     RCF_HIP(hipMemcpy(d_state.p, &st0, sizeof(st0), hipMemcpyHostToDevice));
-    au->d_taps = d_taps.take(); au->d_rings = d_rings.take(); au->d_state = d_state.take();
-    au->from = c->produced;                                      // a new flowgraph: zero state from here on
+    r.iq_ring = c->d_iq;
+    r.st = d_state.take();
+    r.a_ring = d_rings.take();                                   // a | l | h | o | c (cf32), out_cap samples each
+    r.l_ring = r.a_ring + h->out_cap; r.h_ring = r.a_ring + 2 * h->out_cap; r.o_ring = r.a_ring + 3 * h->out_cap;
+    r.c_ring = reinterpret_cast<float2 *>(r.a_ring + 4 * h->out_cap);
+    r.lpf = d_taps.take();                                       // lpf | hpf | rs (padded)
+    r.hpf = r.lpf + r.n_lpf; r.rs = r.hpf + r.n_hpf;
+    au->from = c->pos.produced;                                  // a new flowgraph: zero state from here on
     drop_stage(h, c->audio);
     c->audio = std::move(au);
     ++h->chans_epoch;

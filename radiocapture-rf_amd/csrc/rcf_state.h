@@ -49,8 +49,9 @@ static size_t pow2_at_least(size_t v)
 }
 
 struct Chan {
-    // ---- what planning a block reads and writes, together at the front of the object (three cache lines; plan_block
-    // prefetches them): with a thousand front-ends x 256 channels the planner's time is the cache misses of this walk
+    // ---- what planning a block reads and writes, together at the front of the object: the four cache lines plan_block
+    // prefetches (with a thousand front-ends x 256 channels the planner's time is the cache misses of this walk).  The
+    // static_asserts behind the struct hold the condition.
     int id = -1;
     int src = -1;                 // -1 wideband; RCF_SRC_PFB_BIN0 + bin; else source channel id
     int D = 0, T = 0;
@@ -64,19 +65,23 @@ struct Chan {
     float *d_fm = nullptr;
     int64_t start_sample = 0;     // in source index space
     int64_t k_abs0 = 0;
-    int64_t produced = 0;         // relative output count
     // exact rotator (rcf_set_rotator): phase ring + {phase, counter} state, one pool slice
     float2 *d_rot = nullptr;
     // rotator model
     double extra_dangle = 0, extra_dlogmag = 0;   // added to the increment's own angle / log magnitude (filterbank taps)
     double dangle = 0, dlogmag = 0;
-    long double angle0 = 0;
-    double logmag0 = 0;
-    int64_t n_seg0 = 0;
-    // output range [blk_before, blk_after) the block with serial blk_serial gave this channel (its derived channels'
-    // input range; process_block)
-    uint64_t blk_serial = 0;
-    int64_t blk_before = 0, blk_after = 0;
+    // Everything planning a block advances, and nothing else: plan_block saves it before plan_channel touches the channel,
+    // undo_block puts it back -- one assignment each, so a field added here cannot be missed by either.
+    struct Pos {
+        long double angle0 = 0;   // rotator model at output n_seg0
+        double logmag0 = 0;
+        int64_t n_seg0 = 0;
+        int64_t produced = 0;     // relative output count
+        // output range [blk_before, blk_after) the block with serial blk_serial gave this channel (its derived channels'
+        // input range)
+        int64_t blk_before = 0, blk_after = 0;
+        uint64_t blk_serial = 0;
+    } pos;
     int64_t rd_iq = 0, rd_fm = 0;
     // ---- the optional stages behind the rings, one record each; null = the channel has no such stage.  What a second
     // call of the attaching function means:
@@ -86,65 +91,55 @@ struct Chan {
     //   symbol loops  (rcf_chan_clock_mm,      new ring and state    `produced`   0
     //                  rcf_chan_costas, rcf_chan_fsk4: one record shape, Loop, and one attach path, rcf_stage.cpp)
     //   voice chain   (rcf_chan_audio_open)    new                   `produced`   0
-    // `from`: the first relative channel output the stage is defined for (a new GR block: zero history before it); `rd`:
-    // items handed to the stage's reader; reach(): how far behind a block's first output the stage reads the channel's
-    // rings; release(): the device buffers go once the stream has passed them (rcf_stage.cpp)
+    // rec: the stage's launch record with everything that does not change from block to block -- rings, state, bank, taps,
+    // constants as the kernel takes them -- filled at attach and nowhere else; the planner copies it and sets (n_lo, n_k).
+    // `from`: the first relative channel output the stage is defined for (a new GR block: zero history before it; a record
+    // with an n_first carries the same value); `rd`: items handed to the stage's reader; reach(): how far behind a block's
+    // first output the stage reads the channel's rings; release(): the device buffers go once the stream has passed them
+    // (rcf_stage.cpp)
     struct Sym {                        // real FIR over gain * fm (the P25 symbol filter)
-        float *d_ring = nullptr, *d_taps = nullptr;
-        int ntaps = 0;
-        float gain = 1.f;
+        FmFirLaunch rec{};              // owns sym_ring and taps
         int64_t from = 0, rd = 0;
-        size_t reach() const { return (size_t)std::max(1, ntaps); }
+        size_t reach() const { return (size_t)std::max(1, rec.ntaps); }
         void release(rcf_t *h);
     };
-    struct Agc {                        // feedforward_agc_cc(nsamples = n, reference = ref) over the IQ stream (P25 CQPSK front half)
-        float2 *d_ring = nullptr;
-        int n = 0;
-        float ref = 1.f;
+    struct Agc {                        // feedforward_agc_cc(nsamples, reference) over the IQ stream (P25 CQPSK front half)
+        AgcLaunch rec{};                // owns agc_ring
         int64_t from = 0, rd = 0;
-        size_t reach() const { return (size_t)std::max(1, n - 1); }     // the window reaches n - 1 samples behind
+        size_t reach() const { return (size_t)std::max(1, rec.nsamples - 1); }     // the window reaches n - 1 samples behind
         void release(rcf_t *h);
     };
-    // what the three symbol loops share.  One allocation: soft-symbol ring of out_cap floats | the state record, in a
-    // slot of whole 256 bytes | the caller's bank, if any (attach_loop, rcf_stage.cpp)
-    template <class State_> struct Loop {
+    // what the three symbol loops share.  One allocation, which starts at the record's output ring (Ring): soft-symbol ring
+    // of out_cap floats | the state record (rec.st), in a slot of whole 256 bytes | the caller's bank, if any (attach_loop,
+    // rcf_stage.cpp).  rec.taps: the interpolator bank the stage reads, the caller's or rcf::d_mmse
+    template <class State_, class Rec_, float *Rec_::*Ring> struct Loop {
         typedef State_ State;
-        float *d_ring = nullptr;
-        State *d_state = nullptr;
-        const float *d_bank = nullptr;  // the interpolator bank the stage reads: the caller's (inside d_ring's allocation) or rcf::d_mmse
+        Rec_ rec{};
         int64_t from = 0, rd = 0;
+        float *&ring() { return rec.*Ring; }
         size_t reach() const { return 0; }                               // the history is in the state record: no look-back
         // the record's two counters on the device, n_out then slips (ClockState keeps them behind `p`: moving them to the
         // front, where the other two have them, changes clock_mm_kernel's code)
         const void *counters() const
         {
             static_assert(offsetof(State, slips) == offsetof(State, n_out) + sizeof(int64_t), "n_out, then slips");
-            return &d_state->n_out;
+            return &rec.st->n_out;
         }
         void release(rcf_t *h);
     };
-    struct Clock : Loop<ClockState> {   // clock_recovery_mm_ff over gain * fm (SmartNet / EDACS)
-        // the constants as the kernel takes them, rounded to float once
-        float gain = 1.f, mu0 = 0.f, omega_mid = 0.f, omega_lim = 0.f, gain_omega = 0.f, gain_mu = 0.f;
-        int adv0 = 1;
+    struct Clock : Loop<ClockState, ClockLaunch, &ClockLaunch::sym_ring> {   // clock_recovery_mm_ff over gain * fm (SmartNet / EDACS)
         size_t reach() const { return (size_t)kClockTaps - 1; }         // a symbol's window starts up to 7 samples behind
     };
-    struct Costas : Loop<CostasState> { // Gardner / Costas symbol recovery over the AGC ring (P25 CQPSK back half)
-        float omega_mid = 0.f, omega_lim = 0.f, gain_omega = 0.f, gain_mu = 0.f, alpha = 0.f, beta = 0.f, max_freq = 0.f;
-        int window = 0;                 // L
-    };
-    struct Fsk4 : Loop<Fsk4State> {     // the C4FM symbol loop over the symbol-filter ring (P25 C4FM back half)
-        double time = 0, k_spread = 0, k_timing = 0, k_fine = 0, k_coarse = 0, spread_min = 0, spread_max = 0;
-    };
+    // Gardner / Costas symbol recovery over the AGC ring (P25 CQPSK back half)
+    struct Costas : Loop<CostasState, CostasLaunch, &CostasLaunch::sym_ring> {};
+    // the C4FM symbol loop over the symbol-filter ring (P25 C4FM back half)
+    struct Fsk4 : Loop<Fsk4State, Fsk4Launch, &Fsk4Launch::out_ring> {};
     struct Audio {                      // the analog voice chain
-        AudioState *d_state = nullptr;
-        float *d_rings = nullptr;       // a | l | h | o | c (cf32), out_cap samples each
-        float *d_taps = nullptr;        // lpf | hpf | rs (padded)
-        int n_lpf = 0, n_hpf = 0, nt_rs = 0, interp = 1, decim = 1;
-        float gain = 1.f;
-        double thr = 0, alpha = 0, b0 = 1, b1 = 0, fb1 = 0;
+        // owns st, the rings (one allocation from a_ring on: a | l | h | o | c (cf32), out_cap samples each) and the taps
+        // (one allocation from lpf on: lpf | hpf | rs (padded))
+        AudioLaunch rec{};
         int64_t from = 0, rd = 0;       // rd: audio samples handed to the reader
-        size_t reach() const { return (size_t)std::max(std::max(n_lpf, n_hpf), nt_rs); }   // in the chain's own rings
+        size_t reach() const { return (size_t)std::max(std::max(rec.n_lpf, rec.n_hpf), rec.nt_rs); }   // in the chain's own rings
         void release(rcf_t *h);
     };
     std::unique_ptr<Sym> sym;
@@ -167,6 +162,12 @@ struct Chan {
     uint64_t taps_version = 0;    // bumped whenever d_ctaps changes (bank-matrix cache key)
     std::vector<float> proto;     // prototype taps (host)
 };
+// (offsetof of a class with non-trivial members: conditionally supported, and both compilers of this tree support it)
+#pragma GCC diagnostic push
+#pragma GCC diagnostic ignored "-Winvalid-offsetof"
+static_assert(offsetof(Chan, pos) + sizeof(Chan::Pos) <= 192, "what plan_channel advances: inside the first three cache lines");
+static_assert(offsetof(Chan, audio) + sizeof(std::unique_ptr<Chan::Audio>) <= 256, "what plan_channel reads: inside the four prefetched lines");
+#pragma GCC diagnostic pop
 
 struct Pfb {
     bool open = false;
@@ -418,7 +419,7 @@ int new_channel(rcf_t *h, int src, int D, const float *taps, int T, double offse
 void free_channel(rcf_t *h, Chan *c);                 // c's device buffers go once the stream has passed them; the caller erases c
 // a stage goes (switched off, replaced, or with its channel): release() its buffers, then the record
 template <class R> void drop_stage(rcf_t *h, std::unique_ptr<R> &r) { if (r) { r->release(h); r.reset(); } }
-template <class State> void Chan::Loop<State>::release(rcf_t *h) { bury(h, d_ring); d_ring = nullptr; d_state = nullptr; d_bank = nullptr; }   // one allocation
+template <class S, class R, float *R::*Ring> void Chan::Loop<S, R, Ring>::release(rcf_t *h) { bury(h, ring()); ring() = nullptr; rec.st = nullptr; rec.taps = nullptr; }   // one allocation
 
 // ---------------------------------------------------------------- rcf_read.cpp
 // ---- the one read path.  A stream is a device ring of h->out_cap items (a power of two) of item_w 4-byte words:

@@ -209,6 +209,49 @@ np.savez(sys.argv[1], *got)
         assert len(a[k]) == len(b[k]) > 0 and np.array_equal(a[k], b[k]), k
 
 
+def test_a_block_refused_through_a_chained_channel_leaves_no_trace(gpu_required):
+    """A block that fits the direct channel's ring (600 outputs + the 69 its consumer reaches back) and not the ring of the
+    channel chained on it (the same 600 + the AGC's 511) is refused before either has counted an output -- the refusal is
+    found through the chained channel's source range, which only the dry pass derives without planning the source.  The
+    same samples in two pushes that fit are then, bit for bit, what a front-end that never saw the refused push computes,
+    and the AGC stream is the restatement (tests/agc_ref.py) of the chained channel's IQ."""
+    import agc_ref as A
+    from rcf import p25
+    nat = gpu_required
+    fs, f, out_cap, agc_n = 2.4e6, 100000.0, 1024, 512
+    D, _ = G.channel_params(fs, 12500)
+    taps2 = p25.prefilter_taps(12500)
+    assert D == 96 and len(taps2) == 69
+    # the refused push: c1's ring takes it, c2's does not; the first accepted push: c2's takes it (c2 decimates by 1)
+    assert 600 + (len(taps2) - 1 + 1) <= out_cap and 600 + (agc_n - 1) > out_cap and 500 + (agc_n - 1) <= out_cap
+    rng = np.random.default_rng(41)
+    x = synth.awgn(rng, D * 600)
+    x = (x + 0.5 * np.exp(2j * np.pi * (f + 300.0) * np.arange(len(x)) / fs)).astype(np.complex64)
+
+    def run(refuse_first):
+        with nat.Frontend(fs, block_capacity=D * 700, out_capacity=out_cap) as fe:
+            c1 = fe.chan_open(12500, f)
+            c2 = fe.chan_open_taps(c1, 1, taps2, 0.0)
+            fe.chan_agc(c2, agc_n, 1.0)
+            if refuse_first:
+                before = (fe.chan_produced(c1), fe.chan_produced(c2), fe.samples_in)
+                with pytest.raises(nat.RcfError) as e:
+                    fe.push(x)
+                assert e.value.code == nat.RCF_ECAP and "600 outputs (+511 of history" in str(e.value), e.value   # c2's ring
+                assert (fe.chan_produced(c1), fe.chan_produced(c2), fe.samples_in) == before == (0, 0, 0)
+                assert len(fe.chan_read_iq(c1)) == len(fe.chan_read_iq(c2)) == len(fe.chan_read_agc(c2)) == 0   # nothing queued
+            fe.push(x[:D * 500])
+            fe.push(x[D * 500:])
+            return fe.chan_read_iq(c1), fe.chan_read_iq(c2), fe.chan_read_agc(c2)
+
+    got, want = run(True), run(False)
+    for name, a, b in zip(("c1 IQ", "c2 IQ", "c2 AGC"), got, want):
+        assert len(a) == len(b) == 600, (name, len(a), len(b))
+        np.testing.assert_array_equal(a.view(np.uint32), b.view(np.uint32), err_msg=name)
+    agc = A.feedforward_agc(got[1], agc_n, 1.0)
+    np.testing.assert_array_equal(got[2].view(np.uint32), np.ascontiguousarray(agc, dtype=np.complex64).view(np.uint32))
+
+
 @pytest.mark.parametrize("fmt_name", ["u8", "s16"])
 def test_raw_blocks_from_pinned_memory_are_converted_in_place_and_equal_the_staged_copy(gpu_required, fmt_name):
     """rcf_push_raw has two ingest paths since round 4: a pinned block of <= 4 MiB is converted straight out of host
