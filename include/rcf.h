@@ -253,10 +253,21 @@ int64_t rcf_chan_read_fm(rcf_t *h, int chan_id, float gain, float *out, size_t m
  * (out = float2[n_chans][cap_each], the AGC ring of rcf_chan_agc); counts[i] = samples copied for chan_ids[i] (0: nothing
  * new; RCF_ENOCHAN: no such channel, RCF_EINVAL: a channel listed a second time -- it has one reader position per stream;
  * RCF_ESTATE: the channel has no such stream -- IQ of a discriminator-only tap, AGC of a channel without one; the others
- * are still served).  `out` may be pinned memory (rcf_host_alloc): the copies then overlap each other. */
+ * are still served).  `out` may be pinned memory (rcf_host_alloc): the copies then overlap each other.
+ *   The streams of a channel's stages are batched the same way: RCF_READ_SYM .. RCF_READ_AUDIO, out =
+ * float[n_chans][cap_each], gain ignored, RCF_ESTATE for a channel without that stage.  How many soft symbols or audio
+ * samples a stage has produced only the device knows, so the gather reads the stage's counter itself: still one launch
+ * and one synchronisation for the whole call.  The reader position is the one rcf_chan_read_sym / _clock / _costas /
+ * _fsk4 / _audio use: batched and single reads of one channel interleave without loss or repeat.  Values 3 .. 15 of
+ * `what` are not streams (RCF_EINVAL). */
 #define RCF_READ_IQ 0
 #define RCF_READ_FM 1
-#define RCF_READ_AGC 2    /* rcf_chan_read_many / rcf_group_read_many: cf32 rows from the AGC ring (rcf_chan_agc) */
+#define RCF_READ_AGC 2    /* cf32 rows from the AGC ring (rcf_chan_agc); the pump delivers it too */
+#define RCF_READ_SYM     16   /* float32, symbol-filter ring (rcf_chan_fm_filter) */
+#define RCF_READ_CLOCK   17   /* float32 soft symbols of rcf_chan_clock_mm */
+#define RCF_READ_COSTAS  18   /* float32 soft symbols of rcf_chan_costas */
+#define RCF_READ_FSK4    19   /* float32 soft symbols of rcf_chan_fsk4 */
+#define RCF_READ_AUDIO   20   /* float32 audio of the voice chain */
 int rcf_chan_read_many(rcf_t *h, int what, const int *chan_ids, int n_chans, float gain, void *out, size_t cap_each,
                        int64_t *counts);
 /* P25 C4FM front half after the discriminator (p25_control_demod.py:129-133, logging_receiver.py:240-244):
@@ -723,7 +734,7 @@ typedef struct rcf_pump_config {
     const size_t *ring_blocks;           /* [group size] */
     const double *phase_s;               /* [group size] or NULL */
     const volatile uint64_t *const *written;   /* [group size] or NULL */
-    int what;                            /* RCF_READ_IQ / RCF_READ_FM: what the subscribed channels deliver */
+    int what;                            /* RCF_READ_IQ / FM / AGC / SYM .. AUDIO: what the subscribed channels deliver */
     float gain;                          /* RCF_READ_FM: quadrature_demod_cf gain */
     const int *read_members;             /* [n_read] subscribed channels: member index ... */
     const int *read_chans;               /* ... and channel id */
@@ -776,10 +787,17 @@ int64_t rcf_pump_read(rcf_pump_t *p, int entry, int64_t *cursor, void *out, size
 int rcf_pump_read_many(rcf_pump_t *p, const int *entries, int64_t *cursors, int n, void *out, size_t cap_each, int64_t *counts);
 /* Channels come and go while a channelizer runs (rc_frontend/receiver.py:296-342 connect_channel builds and starts a
  * channel flowgraph under the running top block, :424-435 / :635-648 release and destroy it): a running pump takes a new
- * subscription -- channel chan_id of member `member`, delivered as `what` (RCF_READ_IQ / RCF_READ_FM x gain) from where
+ * subscription -- channel chan_id of member `member`, delivered as `what` (RCF_READ_IQ, RCF_READ_FM x gain, or a stage's stream: below) from where
  * the channel's own reader stands (a channel nobody has read: its first output, as far as its device ring still holds
  * it) -- into a free slot.  Returns the slot (>= 0; use it as `entry` above) and in *cursor where in
- * the slot's item count the new stream begins; RCF_ECAP when all max_read slots are taken. */
+ * the slot's item count the new stream begins; RCF_ECAP when all max_read slots are taken.
+ *   what = RCF_READ_AGC (cf32) and RCF_READ_SYM .. RCF_READ_AUDIO (float32) deliver a stage's stream the same way.  The
+ * soft symbols of a loop and the voice chain's audio (RCF_READ_CLOCK / COSTAS / FSK4 / AUDIO) are counted on the device,
+ * and the pump never waits for it: while such a slot is subscribed IT owns the stream's cursor, on the device, starting
+ * where the channel's own reader stood; the channel's host-side reader position is left alone (an rcf_chan_read_costas
+ * beside the subscription reads the same symbols again).  A stage switched off under its subscription starves the slot, as
+ * a closed channel does; attached again (a fresh ring, symbol 0) the slot goes on with symbol 0 of the new attachment,
+ * appended to its item count without a gap. */
 int rcf_pump_subscribe(rcf_pump_t *p, int member, int chan_id, int what, float gain, int64_t *cursor);
 /* chan_id = RCF_SRC_PFB_BIN0 + bin (here and in rcf_pump_config_t.read_chans) with what = RCF_READ_FM subscribes ONE BIN of the
  * member's fused discriminator ring (rcf_pfb_fm_enable: every bin of the bank demodulated inside its launch) instead of a

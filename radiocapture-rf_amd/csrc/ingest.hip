@@ -136,6 +136,46 @@ void launch_gather_rings(const GatherRec *d_recs, int n_recs, uint32_t *d_dst, u
     hipLaunchKernelGGL(gather_rings_kernel, dim3(std::min(items, cap)), dim3(256), 0, s, d_recs, d_dst, (uint32_t)n_recs, parts);
 }
 
+// The counted gather (CountedRec, rcf_internal.h): gather_rings_kernel for streams whose end is a device counter.  Every
+// workgroup of a record reads the same counter and the same {cursor, pos} -- nothing in this launch writes either -- and so
+// derives the same segment; the record's first workgroup publishes where the segment ended.  The grid is bounded like
+// gather_rings_kernel's, for its reason.
+static __global__ __launch_bounds__(256) void gather_counted_kernel(const CountedRec *__restrict__ recs, uint32_t *__restrict__ dst,
+                                                                    uint32_t n_recs, uint32_t parts)
+{
+    const uint32_t n_items = n_recs * parts;
+    for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const CountedRec r = recs[item / parts];
+        const int64_t c = *r.counter;
+        const int64_t end = r.interp == r.decim ? c : (c * (int64_t)r.interp + (int64_t)r.decim - 1) / (int64_t)r.decim;
+        int64_t cur = (r.flags & 1u) ? r.cursor0 : r.state_in[0];
+        const int64_t pos = (r.flags & 2u) ? r.pos0 : r.state_in[1];
+        cur = max(cur, end - (int64_t)r.cap);                        // a reader more than a ring behind lost what was overwritten
+        int64_t avail = max((int64_t)0, end - cur);
+        const int64_t room = (int64_t)r.dst_mask_w + 1;              // a destination ring keeps the newest `room` items
+        if (avail > room) { cur += avail - room; avail = room; }
+        const uint32_t n = (uint32_t)min(avail, (int64_t)r.max_n);
+        const uint32_t first = (uint32_t)((uint64_t)cur & (r.cap - 1u)), at = (uint32_t)(uint64_t)pos;
+        for (uint32_t w = (item % parts) * 256 + threadIdx.x; w < n; w += parts * 256)
+            dst[r.dst_w + ((at + w) & r.dst_mask_w)] = r.ring[(first + w) & (r.cap - 1u)];
+        if (item % parts == 0 && threadIdx.x == 0) {
+            r.result[0] = pos + n;
+            r.result[1] = cur + n;
+            if (r.state_out) { r.state_out[0] = cur + n; r.state_out[1] = pos + n; }
+        }
+    }
+}
+
+// max_items: the largest max_n among the records (the segments' true lengths are the device's to know)
+void launch_gather_counted(const CountedRec *d_recs, int n_recs, uint32_t *d_dst, uint32_t max_items, hipStream_t s)
+{
+    if (n_recs <= 0) return;
+    constexpr unsigned cap = 128;
+    const unsigned parts = std::max(1u, std::min<unsigned>((max_items + 255) / 256, 16));   // (a result is published whatever n is)
+    const unsigned items = parts * (unsigned)n_recs;
+    hipLaunchKernelGGL(gather_counted_kernel, dim3(std::min(items, cap)), dim3(256), 0, s, d_recs, d_dst, (uint32_t)n_recs, parts);
+}
+
 void launch_gather_view(const StreamView &v, int64_t first, float2 *dst, size_t n, hipStream_t s)
 {
     if (n == 0) return;

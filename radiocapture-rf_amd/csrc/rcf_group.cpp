@@ -527,7 +527,7 @@ int rcf_group_sync(rcf_group_t *g)
 int rcf_group_read_many(rcf_group_t *g, int what, const int *members, const int *chan_ids, int n, float gain, void *out,
                         size_t cap_each, int64_t *counts)
 {
-    if (!g || !members || !chan_ids || !out || !counts || n < 0 || (what != RCF_READ_IQ && what != RCF_READ_FM && what != RCF_READ_AGC)) {
+    if (!g || !members || !chan_ids || !out || !counts || n < 0 || stream_kind(what) < 0) {
         set_error("bad batched read arguments");
         return RCF_EINVAL;
     }

@@ -566,6 +566,31 @@ struct GatherRec {
                              // floats (the bank's fused discriminator ring: ring = its bin, stride = bins)
 };
 void launch_gather_rings(const GatherRec *d_recs, int n_recs, uint32_t *d_dst, uint32_t max_words, hipStream_t s);
+// The counted gather: a ring segment whose LENGTH only the device knows -- the soft symbols of a symbol loop (n_out of
+// ClockState / CostasState / Fsk4State) or the voice chain's audio (n_a of AudioState).  The kernel reads the stage's counter
+// itself (stable: the launch is queued behind the block's stage launches), applies the reader's lag clamp and copies
+//   end = ceil(*counter * interp / decim)            (interp == decim: the counter itself)
+//   cur = max(cursor, end - cap)                     (lag_clamp, rcf_state.h)
+//   n   = min(end - cur, max_n), after the items a destination ring of dst_mask_w + 1 cannot hold were skipped
+//   dst[dst_w + ((pos + i) & dst_mask_w)] = ring[(cur + i) & (cap - 1)], i < n          (float32 items: words)
+// and one lane publishes result = {pos + n, cur + n}.  cursor and pos (the items the destination has taken so far) come
+// from the host (flags) or from device memory, where the gather before this one left them: the real-time pump keeps two
+// group blocks in flight and cannot know gather n's count when it writes the record of gather n + 1.  state_in and
+// state_out are DIFFERENT copies, so that no workgroup of a launch sees what a sibling has already advanced.
+struct CountedRec {
+    const uint32_t *ring;
+    const int64_t *counter;  // the stage's device counter
+    const int64_t *state_in; // {cursor, pos} as the slot's previous gather left them (unread where both flags are set)
+    int64_t *state_out;      // {cursor, pos} after this gather; nullptr: not kept (host reads: the host owns the cursor)
+    int64_t *result;         // pinned host memory as the device sees it: {pos + n, cur + n}
+    int64_t cursor0, pos0;   // flags & 1: the cursor is cursor0; flags & 2: pos is pos0
+    uint32_t interp, decim;  // the count transform (the voice chain's resampler; 1, 1 for the loops)
+    uint32_t cap;            // ring capacity in items, a power of two
+    uint32_t max_n;          // most items to take
+    uint32_t dst_w, dst_mask_w;   // as in GatherRec (dst_mask_w = ~0u: a linear row)
+    uint32_t flags, pad_;
+};
+void launch_gather_counted(const CountedRec *d_recs, int n_recs, uint32_t *d_dst, uint32_t max_items, hipStream_t s);
 // one record of the grouped ingest launch (group_prep_kernel, ingest.hip): a block of one front-end, or a plain copy
 struct PrepRec {
     const void *src;         // wire-format / cf32 samples (pinned host memory as the device sees it, or device memory)

@@ -25,13 +25,26 @@ struct rcf_pump {
     std::vector<double> phase;
     std::vector<const volatile uint64_t *> written;
     // subscription slots (guarded by g->mu): slot e delivers channel rd_chan[e] of member rd_member[e] (-1: free) as
-    // rd_what[e] (RCF_READ_IQ / RCF_READ_FM x rd_gain[e]).  Slots are fixed at start (cfg.n_read of them subscribed, room
+    // stream rd_kind[e] of the channel's stream table (stream_kind of the subscription's `what`; RCF_READ_FM x rd_gain[e]).
+    // Slots are fixed at start (cfg.n_read of them subscribed, room
     // for max_read): rcf_pump_subscribe / rcf_pump_unsubscribe move channels in and out while the thread runs
-    std::vector<int> rd_member, rd_chan, rd_what;
+    std::vector<int> rd_member, rd_chan, rd_kind;
     std::vector<float> rd_gain;
     std::vector<std::vector<int>> entries_of;      // member -> indices into rd_*
     std::vector<int64_t> bin_rd;                   // slots on a BIN of a member's fused discriminator ring (rd_chan >= RCF_SRC_PFB_BIN0): frames delivered
     std::vector<int64_t> queued;                   // items ever queued for the host ring of each slot
+    // Counted slots (kind_counted: a symbol loop's soft symbols, the voice chain's audio).  How many items a gather takes
+    // only the device knows, and with two group blocks in flight the host cannot wait for it: the slot's cursor in the
+    // stage's stream and its item count live in d_cstate, {cursor, items} twice per slot -- a gather reads the copy
+    // c_par[e] and writes the other (CountedRec).  `queued` of such a slot is an UPPER bound: every gather adds the most
+    // it may take, and its completion puts the bound back on the true count its result words report.
+    int64_t *d_cstate = nullptr;
+    std::vector<uint8_t> c_par;                    // the copy the slot's next gather reads
+    std::vector<uint8_t> c_fresh;                  // the next gather takes cursor and item count from the host: a new subscription
+    std::vector<uint8_t> c_last;                   // the slot's last tenant was counted (its count is the bound, not exact)
+    std::vector<uint64_t> c_serial;                // the attachment of the stage the device cursor belongs to (Chan::Loop::serial)
+    std::vector<uint32_t> c_gen;                   // bumped by every subscription: gathers of an earlier tenant no longer count
+    unsigned char *h_crecs = nullptr, *h_crecs_dev = nullptr;   // pinned, per in-flight block: CountedRec[recs_cap] | result words[recs_cap][2]
     std::vector<Chan *> chan_of;                   // subscribed channels, resolved once per channel-set epoch
     std::vector<uint64_t> epoch_of;                // per member: the epoch chan_of was resolved at (~0: resolve again)
     size_t out_cap = 0;                            // host ring length per slot (items, power of two)
@@ -58,12 +71,15 @@ struct rcf_pump {
     int64_t nivcsw = 0;
     std::chrono::steady_clock::time_point t_start, t_end;
     char err_text[256] = "";
-    size_t item_bytes(int e) const { return rd_what[(size_t)e] == RCF_READ_IQ ? sizeof(float2) : sizeof(float); }
+    size_t item_bytes(int e) const { return stream_item_bytes(rd_kind[(size_t)e]); }
+    size_t crecs_bytes() const { return recs_cap * (sizeof(CountedRec) + 2 * sizeof(int64_t)); }   // of one in-flight block
     ~rcf_pump()
     {
         // (also what an rcf_pump_start that fails half-way leaves through: pinned rings, records, events)
         for (int i = 0; i < 2; ++i) if (slot_ev[i]) (void)hipEventDestroy(slot_ev[i]);
         if (h_recs) (void)hipHostFree(h_recs);
+        if (h_crecs) (void)hipHostFree(h_crecs);
+        if (d_cstate) (void)hipFree(d_cstate);
         if (h_out) (void)hipHostFree(h_out);
     }
 };
@@ -79,6 +95,8 @@ struct InFlight {
     std::vector<double> due;           // per member: when its block was complete (seconds since t0)
     std::vector<int64_t> kidx;         // per member: which of its blocks
     std::vector<std::pair<int, int64_t>> delivered;   // (entry, items) to publish once the gather has run
+    struct Counted { int entry; uint32_t gen; int64_t bound; int rec; };
+    std::vector<Counted> counted;      // counted slots: the tenant the gather was for, the most it takes, its result words
 };
 
 // nanoseconds this thread has spent runnable without a CPU (second field of /proc/thread-self/schedstat); -1: unreadable
@@ -151,6 +169,24 @@ void pump_main(rcf_pump *p)
         const double t_done = secs(now - t0);
         int64_t items_out = 0;
         for (auto &d : s.delivered) { p->out_written[(size_t)d.first].fetch_add(d.second, std::memory_order_release); items_out += d.second; }
+        if (!s.counted.empty()) {
+            // what the counted gathers took: the slot's true item count from its result words; the bound goes back on it,
+            // plus what the other block in flight may still take (under the lock that guards `queued`)
+            std::lock_guard<std::mutex> gl(g->mu);
+            const int64_t *res = reinterpret_cast<const int64_t *>(p->h_crecs + (size_t)head * p->crecs_bytes() + p->recs_cap * sizeof(CountedRec));
+            const InFlight &other = slots[head ^ 1];
+            for (const InFlight::Counted &c : s.counted) {
+                const size_t e = (size_t)c.entry;
+                if (c.gen != p->c_gen[e]) continue;                           // the slot has a new tenant, whose stream began above this
+                const int64_t now_at = res[2 * c.rec];
+                int64_t ahead = 0;
+                if (other.busy) for (const InFlight::Counted &o : other.counted) if (o.entry == c.entry && o.gen == c.gen) ahead += o.bound;
+                items_out += now_at - p->out_written[e].load(std::memory_order_relaxed);
+                p->out_written[e].store(now_at, std::memory_order_release);
+                queued[e] = now_at + ahead;
+                p->out_queued[e].store(queued[e], std::memory_order_release);
+            }
+        }
         {
             std::lock_guard<std::mutex> l(p->st_mu);
             p->wait_ms += secs(now - w0) * 1e3;
@@ -220,6 +256,7 @@ void pump_main(rcf_pump *p)
             s.kidx.clear();
             s.due = due;
             s.delivered.clear();
+            s.counted.clear();
             int n_over = 0;
             for (size_t i = 0; i < items.size(); ++i) {
                 s.members.push_back(items[i].m);
@@ -234,8 +271,10 @@ void pump_main(rcf_pump *p)
                 if (rc == RCF_OK) {
                     // the read of this batch: every subscribed channel of its members, straight into the host rings
                     GatherRec *recs = reinterpret_cast<GatherRec *>(p->h_recs + (size_t)slot * p->recs_cap * sizeof(GatherRec));
-                    int n_recs = 0;
-                    uint32_t max_w = 0;
+                    CountedRec *crecs = reinterpret_cast<CountedRec *>(p->h_crecs + (size_t)slot * p->crecs_bytes());
+                    unsigned char *crecs_dev = p->h_crecs_dev + (size_t)slot * p->crecs_bytes();
+                    int n_recs = 0, n_crecs = 0;
+                    uint32_t max_w = 0, max_c = 0;
                     for (const GroupItem &it : items) {
                         rcf_t *h = g->members[(size_t)it.m];
                         if (epoch_of[(size_t)it.m] != h->chans_epoch) {            // channels were opened / closed: look them up again
@@ -261,7 +300,39 @@ void pump_main(rcf_pump *p)
                             } else {
                                 Chan *c = chan_of[(size_t)e];
                                 if (!c) continue;                                  // closed under the pump: starves
-                                if (chan_stream(h, c, p->rd_what[(size_t)e], &rs) != RCF_OK) continue;   // (IQ of a discriminator-only tap)
+                                const int kind = p->rd_kind[(size_t)e];
+                                if (kind_counted(kind)) {
+                                    CountedStream cs;
+                                    if (counted_stream(c, kind, &cs) != RCF_OK) continue;      // the stage is off: starves
+                                    // a new subscription starts at the channel's own reader and at the slot's item count; a stage
+                                    // attached again (the host did it, under the member's lock) at symbol 0 of the new ring
+                                    const bool fresh = p->c_fresh[(size_t)e] != 0, again = !fresh && p->c_serial[(size_t)e] != cs.serial;
+                                    p->c_fresh[(size_t)e] = 0;
+                                    p->c_serial[(size_t)e] = cs.serial;
+                                    // the most this gather may take (the kernel holds it to that; a rest waits for the next
+                                    // block): steady state, what the block made -- at most one symbol per stage input,
+                                    // ceil(n_k interp / decim) + 1 audio samples; a first gather, whatever the ring holds
+                                    const int64_t n_k = std::max<int64_t>(0, c->pos.blk_after - c->pos.blk_before);
+                                    int64_t bound = kind == kReadAudio ? (n_k * cs.interp + cs.decim - 1) / cs.decim + 1 : n_k + 1;
+                                    if (fresh || again) bound = (int64_t)h->out_cap;
+                                    bound = std::min<int64_t>(bound, (int64_t)p->out_cap);
+                                    int64_t *st = p->d_cstate + (size_t)e * 4;
+                                    const int par = p->c_par[(size_t)e];
+                                    p->c_par[(size_t)e] ^= 1;
+                                    crecs[n_crecs] = CountedRec{static_cast<const uint32_t *>(cs.ring), cs.counter, st + 2 * par, st + 2 * (par ^ 1),
+                                                                reinterpret_cast<int64_t *>(crecs_dev + p->recs_cap * sizeof(CountedRec)) + 2 * n_crecs,
+                                                                fresh ? *cs.cursor : 0, queued[(size_t)e], cs.interp, cs.decim, (uint32_t)h->out_cap,
+                                                                (uint32_t)bound, (uint32_t)((size_t)e * p->out_cap * slot_w), (uint32_t)(p->out_cap - 1),
+                                                                fresh ? 3u : again ? 1u : 0u, 0u};
+                                    s.counted.push_back({e, p->c_gen[(size_t)e], bound, n_crecs});
+                                    ++n_crecs;
+                                    max_c = std::max<uint32_t>(max_c, (uint32_t)bound);
+                                    queued[(size_t)e] += bound;
+                                    // (published BEFORE the launch, like a plain slot's: covers all this gather may write)
+                                    p->out_queued[(size_t)e].store(queued[(size_t)e], std::memory_order_release);
+                                    continue;
+                                }
+                                if (chan_stream(h, c, kind, &rs) != RCF_OK) continue;   // (IQ of a discriminator-only tap, a channel without that stage)
                             }
                             int64_t n = lag_clamp(h, rs.cursor, rs.newest, rs.end, INT64_MAX);
                             if (n == 0) continue;
@@ -273,7 +344,7 @@ void pump_main(rcf_pump *p)
                             p->out_queued[(size_t)e].store(queued[(size_t)e], std::memory_order_release);
                             recs[n_recs++] = gather_rec(rs, n, (uint32_t)((size_t)e * p->out_cap * slot_w), (uint32_t)(dst_pos * ew),
                                                         (uint32_t)(p->out_cap * ew - 1),
-                                                        p->rd_what[(size_t)e] == RCF_READ_FM ? p->rd_gain[(size_t)e] : 1.0f);
+                                                        p->rd_kind[(size_t)e] == RCF_READ_FM ? p->rd_gain[(size_t)e] : 1.0f);
                             max_w = std::max<uint32_t>(max_w, (uint32_t)n * ew);
                             *rs.cursor += n;
                             s.delivered.push_back({e, n});
@@ -282,6 +353,9 @@ void pump_main(rcf_pump *p)
                     if (n_recs)
                         launch_gather_rings(reinterpret_cast<const GatherRec *>(p->h_recs_dev + (size_t)slot * p->recs_cap * sizeof(GatherRec)),
                                             n_recs, reinterpret_cast<uint32_t *>(p->h_out_dev), max_w, g->stream);
+                    if (n_crecs)
+                        launch_gather_counted(reinterpret_cast<const CountedRec *>(crecs_dev), n_crecs, reinterpret_cast<uint32_t *>(p->h_out_dev),
+                                              max_c, g->stream);
                     if (hipEventRecord(p->slot_ev[slot], g->stream) != hipSuccess) { set_error("pump: event record failed"); rc = RCF_EHIP; }
                 }
             }
@@ -357,7 +431,7 @@ int rcf_pump_start(rcf_group_t *g, const rcf_pump_config_t *cfg, rcf_pump_t **ou
 {
     if (!g || !cfg || !out || cfg->block_samples == 0 || !(cfg->samp_rate > 0) || !cfg->rings || !cfg->ring_blocks ||
         cfg->n_read < 0 || (cfg->n_read && (!cfg->read_members || !cfg->read_chans)) ||
-        (cfg->what != RCF_READ_IQ && cfg->what != RCF_READ_FM) || group_sample_bytes(cfg->fmt) == 0) {
+        stream_kind(cfg->what) < 0 || group_sample_bytes(cfg->fmt) == 0) {
         set_error("bad pump configuration");
         return RCF_EINVAL;
     }
@@ -383,7 +457,12 @@ int rcf_pump_start(rcf_group_t *g, const rcf_pump_config_t *cfg, rcf_pump_t **ou
     p->entries_of.resize(G);
     p->rd_member.assign((size_t)n_slots, -1);
     p->rd_chan.assign((size_t)n_slots, -1);
-    p->rd_what.assign((size_t)n_slots, cfg->what);
+    p->rd_kind.assign((size_t)n_slots, stream_kind(cfg->what));
+    p->c_par.assign((size_t)n_slots, 0);
+    p->c_fresh.assign((size_t)n_slots, 1);
+    p->c_last.assign((size_t)n_slots, 0);
+    p->c_serial.assign((size_t)n_slots, 0);
+    p->c_gen.assign((size_t)n_slots, 0);
     p->rd_gain.assign((size_t)n_slots, cfg->gain);
     p->queued.assign((size_t)n_slots, 0);
     p->bin_rd.assign((size_t)n_slots, 0);
@@ -394,6 +473,7 @@ int rcf_pump_start(rcf_group_t *g, const rcf_pump_config_t *cfg, rcf_pump_t **ou
         p->rd_member[(size_t)e] = cfg->read_members[e];
         p->rd_chan[(size_t)e] = cfg->read_chans[e];
         p->entries_of[(size_t)cfg->read_members[e]].push_back(e);
+        p->c_last[(size_t)e] = cfg->read_chans[e] < RCF_SRC_PFB_BIN0 && kind_counted(p->rd_kind[(size_t)e]) ? 1 : 0;
     }
     // the configuration's arrays belong to the caller: from here on the pump's own copies are used
     p->cfg.rings = nullptr; p->cfg.ring_blocks = nullptr; p->cfg.phase_s = nullptr; p->cfg.written = nullptr;
@@ -424,6 +504,17 @@ int rcf_pump_start(rcf_group_t *g, const rcf_pump_config_t *cfg, rcf_pump_t **ou
     }
     p->h_recs = static_cast<unsigned char *>(hp);
     p->h_recs_dev = static_cast<unsigned char *>(dv);
+    hp = dv = nullptr;
+    if (hipHostMalloc(&hp, 2 * p->crecs_bytes(), hipHostMallocDefault) != hipSuccess || hipHostGetDevicePointer(&dv, hp, 0) != hipSuccess) {
+        if (hp) (void)hipHostFree(hp);
+        (void)hipGetLastError();
+        set_error("pinned counted-gather records failed");
+        return RCF_ENOMEM;
+    }
+    p->h_crecs = static_cast<unsigned char *>(hp);
+    p->h_crecs_dev = static_cast<unsigned char *>(dv);
+    RCF_HIP(hipMalloc(&p->d_cstate, (size_t)n_slots * 4 * sizeof(int64_t)));
+    RCF_HIP(hipMemset(p->d_cstate, 0, (size_t)n_slots * 4 * sizeof(int64_t)));
     for (int i = 0; i < 2; ++i) RCF_HIP(hipEventCreateWithFlags(&p->slot_ev[i], hipEventDisableTiming));
     // room in the group's arena for a group block of ALL members at once (after a hiccup everything that is complete goes
     // out together): growing the arena means a stream synchronisation and pinned allocations -- not in the middle of a run
@@ -440,14 +531,16 @@ int rcf_pump_start(rcf_group_t *g, const rcf_pump_config_t *cfg, rcf_pump_t **ou
         for (int e = 0; e < cfg->n_read; ++e) {
             rcf_t *h = g->members[(size_t)p->rd_member[(size_t)e]];
             if (p->rd_chan[(size_t)e] >= RCF_SRC_PFB_BIN0) {              // a bin of the fused discriminator ring
-                p->rd_what[(size_t)e] = RCF_READ_FM;
+                p->rd_kind[(size_t)e] = RCF_READ_FM;
                 p->bin_rd[(size_t)e] = h->pfb.produced;
                 continue;
             }
             auto f = h->chans.find(p->rd_chan[(size_t)e]);
             if (f == h->chans.end()) continue;
             RingStream rs;
-            if (chan_stream(h, f->second.get(), cfg->what, &rs) == RCF_OK) *rs.cursor = rs.end;
+            // (a counted stream's end is fetched from the device here -- the one place the pump may wait for the stream; the
+            // slot's first gather takes the cursor from there)
+            if (chan_stream(h, f->second.get(), p->rd_kind[(size_t)e], &rs) == RCF_OK) *rs.cursor = rs.end;
         }
     }
     p->running.store(true);
@@ -557,7 +650,7 @@ int rcf_pump_read_many(rcf_pump_t *p, const int *entries, int64_t *cursors, int 
 
 int rcf_pump_subscribe(rcf_pump_t *p, int member, int chan_id, int what, float gain, int64_t *cursor)
 {
-    if (!p || (what != RCF_READ_IQ && what != RCF_READ_FM)) { set_error("bad subscription"); return RCF_EINVAL; }
+    if (!p || stream_kind(what) < 0) { set_error("bad subscription"); return RCF_EINVAL; }
     rcf_group *g = p->g;
     std::lock_guard<std::mutex> gl(g->mu);
     if (member < 0 || member >= (int)g->members.size()) { set_error("no such member %d", member); return RCF_EINVAL; }
@@ -584,8 +677,14 @@ int rcf_pump_subscribe(rcf_pump_t *p, int member, int chan_id, int what, float g
     }
     p->rd_member[(size_t)e] = member;
     p->rd_chan[(size_t)e] = chan_id;
-    p->rd_what[(size_t)e] = what;
+    p->rd_kind[(size_t)e] = stream_kind(what);
     p->rd_gain[(size_t)e] = gain;
+    // gathers still in flight for a COUNTED previous tenant no longer count (c_gen): the new stream starts at the bound they
+    // stay below, and the slot's item count jumps there
+    ++p->c_gen[(size_t)e];
+    if (p->c_last[(size_t)e]) p->out_written[(size_t)e].store(p->queued[(size_t)e], std::memory_order_release);
+    p->c_last[(size_t)e] = kind_counted(p->rd_kind[(size_t)e]) ? 1 : 0;
+    p->c_fresh[(size_t)e] = 1;
     p->chan_of[(size_t)e] = nullptr;
     p->entries_of[(size_t)member].push_back(e);
     p->epoch_of[(size_t)member] = ~0ull;               // resolved at the member's next block

@@ -1,5 +1,6 @@
-// rcf_read.cpp -- the stream table of a channel (chan_stream: eight streams, one row each) and the one read path of every
-// host read (host_read: one gather launch, one synchronisation), with the read and ring entry points of the C ABI.
+// rcf_read.cpp -- the stream table of a channel (chan_stream: eight streams, one row each; counted_stream: the four whose end
+// is a device counter, without the round trip) and the one read path of every host read (host_read: one gather launch, one
+// synchronisation), with the read and ring entry points of the C ABI.
 #include <atomic>
 
 #include "rcf_plan.h"
@@ -38,25 +39,38 @@ int stage_state(rcf_t *h, const void *d_state, void *st, size_t bytes)
     return RCF_OK;
 }
 
+int counted_stream(Chan *c, int kind, CountedStream *s)
+{
+    StreamRow r;
+    const int rc = stream_row(c, kind, &r);
+    if (rc != RCF_OK) return rc;
+    *s = CountedStream{r.ring, nullptr, 1u, 1u, r.cursor, 0};
+    switch (kind) {
+        case kReadClock:  s->counter = static_cast<const int64_t *>(c->clock->counters()); s->serial = c->clock->serial; break;
+        case kReadCostas: s->counter = static_cast<const int64_t *>(c->costas->counters()); s->serial = c->costas->serial; break;
+        case kReadFsk4:   s->counter = static_cast<const int64_t *>(c->fsk4->counters()); s->serial = c->fsk4->serial; break;
+        default:                                         // kReadAudio: ceil(n_a * interp / decim), as chan_stream has it
+            s->counter = &c->audio->rec.st->n_a;
+            s->interp = (uint32_t)c->audio->rec.interp; s->decim = (uint32_t)c->audio->rec.decim;
+            s->serial = c->audio->serial;
+    }
+    return RCF_OK;
+}
+
 int chan_stream(rcf_t *h, Chan *c, int kind, RingStream *s, int64_t *aux)
 {
     StreamRow r;
     int rc = stream_row(c, kind, &r);
     if (rc != RCF_OK) return rc;
     int64_t end = c->pos.produced, beside = 0;
-    const void *loop = kind == kReadClock ? c->clock->counters() : kind == kReadCostas ? c->costas->counters()
-                     : kind == kReadFsk4 ? c->fsk4->counters() : nullptr;
-    if (loop) {                                      // the three loops alike
-        int64_t n_out_slips[2] = {0, 0};
-        if ((rc = stage_state(h, loop, n_out_slips, sizeof(n_out_slips))) != RCF_OK) return rc;
-        end = n_out_slips[0];
-        beside = n_out_slips[1];
-    } else if (kind == kReadAudio) {
-        AudioState st{};
-        if ((rc = stage_state(h, c->audio->rec.st, &st, sizeof(st))) != RCF_OK) return rc;
-        const int64_t I = c->audio->rec.interp, D = c->audio->rec.decim;
-        end = (st.n_a * I + D - 1) / D;
-        beside = st.n_a;
+    if (kind_counted(kind)) {
+        // the counter and the word behind it: the loops' {n_out, slips}, the voice chain's {n_a, n_prev}
+        static_assert(offsetof(AudioState, n_prev) == offsetof(AudioState, n_a) + sizeof(int64_t), "n_a, then n_prev");
+        CountedStream cs;
+        int64_t two[2] = {0, 0};
+        if ((rc = counted_stream(c, kind, &cs)) != RCF_OK || (rc = stage_state(h, cs.counter, two, sizeof(two))) != RCF_OK) return rc;
+        end = (two[0] * cs.interp + cs.decim - 1) / cs.decim;
+        beside = kind == kReadAudio ? two[0] : two[1];
     }
     if (aux) *aux = beside;
     *s = RingStream{h, r.ring, r.item_w, 0u, end, end, r.cursor};
@@ -83,13 +97,16 @@ int PinnedStage::ensure(size_t need, hipStream_t stream)
 
 // One gather launch packs every entry's segment back to back into pinned host memory, one synchronisation, then the rows are
 // handed out.  (A device round trip per channel -- a single reader in a loop -- costs ~10 us each: 256 tapped bins of ten
-// front-ends are 25 ms per pass.)
+// front-ends are 25 ms per pass.)  Counted entries ride in a launch of their own kind behind the same synchronisation: the
+// host does not know their lengths, so each reserves the most it may take -- min(max, out_cap) -- and the launch's result
+// words {items, cursor after} say what came.
+// Staging: GatherRec[] | CountedRec[] | result words | the plain entries' rows | the counted entries' rows
 int host_read(PinnedStage &stage, hipStream_t stream, rcf_t *const *idle, size_t n_idle, ReadEntry *es, size_t n)
 {
     static std::atomic<uint64_t> calls{0};
     const uint64_t stamp = ++calls;
-    uint64_t total = 0, total_w = 0;
-    uint32_t max_w = 0, n_recs = 0;
+    uint64_t total = 0, total_w = 0, counted_w = 0;
+    uint32_t max_w = 0, n_recs = 0, max_c = 0, n_crecs = 0;
     for (size_t i = 0; i < n; ++i) {
         ReadEntry &e = es[i];
         if (e.c) {
@@ -97,6 +114,15 @@ int host_read(PinnedStage &stage, hipStream_t stream, rcf_t *const *idle, size_t
             e.c->many_stamp = stamp;
         }
         if (!e.s.ring) continue;
+        if (e.counter) {
+            *e.count = 0;
+            e.max = std::min<int64_t>(e.max, (int64_t)e.s.h->out_cap);
+            if (e.max <= 0) { e.s.ring = nullptr; continue; }
+            counted_w += (uint64_t)e.max;
+            max_c = std::max<uint32_t>(max_c, (uint32_t)e.max);
+            ++n_crecs;
+            continue;
+        }
         *e.count = lag_clamp(e.s.h, e.s.cursor, e.s.newest, e.s.end, e.max);
         if (*e.count == 0) continue;
         total += (uint64_t)*e.count;
@@ -104,31 +130,56 @@ int host_read(PinnedStage &stage, hipStream_t stream, rcf_t *const *idle, size_t
         max_w = std::max<uint32_t>(max_w, (uint32_t)*e.count * e.s.item_w);
         ++n_recs;
     }
-    if (total == 0) return RCF_OK;
-    if (total_w > 0xffffffffull) { set_error("batched read of %llu items exceeds the 32-bit word range", (unsigned long long)total); return RCF_ECAP; }
-    const size_t rec_bytes = ((size_t)n_recs * sizeof(GatherRec) + 255) & ~(size_t)255;
-    const int rc = stage.ensure(rec_bytes + (size_t)total_w * 4, stream);
+    if (total == 0 && n_crecs == 0) return RCF_OK;
+    if (total_w + counted_w > 0xffffffffull) { set_error("batched read of %llu items exceeds the 32-bit word range", (unsigned long long)(total + counted_w)); return RCF_ECAP; }
+    const auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t rec_bytes = pad((size_t)n_recs * sizeof(GatherRec)), crec_at = rec_bytes;
+    const size_t res_at = crec_at + pad((size_t)n_crecs * sizeof(CountedRec)), data_at = res_at + pad((size_t)n_crecs * 2 * sizeof(int64_t));
+    const int rc = stage.ensure(data_at + (size_t)(total_w + counted_w) * 4, stream);
     if (rc != RCF_OK) return rc;
     GatherRec *recs = reinterpret_cast<GatherRec *>(stage.h);
+    CountedRec *crecs = reinterpret_cast<CountedRec *>(stage.h + crec_at);
+    const int64_t *res = reinterpret_cast<const int64_t *>(stage.h + res_at);
     uint32_t at_w = 0, k = 0;
     for (size_t i = 0; i < n; ++i) {
         const ReadEntry &e = es[i];
-        if (!e.s.ring || *e.count == 0) continue;
+        if (!e.s.ring || e.counter || *e.count == 0) continue;
         recs[k++] = gather_rec(e.s, *e.count, at_w, 0u, ~0u, e.gain);
         at_w += (uint32_t)*e.count * e.s.item_w;
     }
-    launch_gather_rings(reinterpret_cast<const GatherRec *>(stage.d), (int)n_recs, reinterpret_cast<uint32_t *>(stage.d + rec_bytes),
-                        max_w, stream);
-    if (hipStreamSynchronize(stream) != hipSuccess) { set_error("stream sync failed"); return RCF_EHIP; }
-    for (size_t j = 0; j < n_idle; ++j) free_graveyard_idle(idle[j]);   // retuned / closed channels' old buffers
-    const unsigned char *src = stage.h + rec_bytes;
+    k = 0;
     for (size_t i = 0; i < n; ++i) {
         const ReadEntry &e = es[i];
-        if (!e.s.ring || *e.count == 0) continue;
+        if (!e.s.ring || !e.counter) continue;
+        crecs[k] = CountedRec{static_cast<const uint32_t *>(e.s.ring), e.counter, nullptr, nullptr,
+                              reinterpret_cast<int64_t *>(stage.d + res_at) + 2 * k, *e.s.cursor, 0, e.interp, e.decim,
+                              (uint32_t)e.s.h->out_cap, (uint32_t)e.max, at_w, ~0u, 3u, 0u};
+        ++k;
+        at_w += (uint32_t)e.max;
+    }
+    uint32_t *d_dst = reinterpret_cast<uint32_t *>(stage.d + data_at);
+    launch_gather_rings(reinterpret_cast<const GatherRec *>(stage.d), (int)n_recs, d_dst, max_w, stream);
+    if (n_crecs) launch_gather_counted(reinterpret_cast<const CountedRec *>(stage.d + crec_at), (int)n_crecs, d_dst, max_c, stream);
+    if (hipStreamSynchronize(stream) != hipSuccess) { set_error("stream sync failed"); return RCF_EHIP; }
+    for (size_t j = 0; j < n_idle; ++j) free_graveyard_idle(idle[j]);   // retuned / closed channels' old buffers
+    const unsigned char *src = stage.h + data_at;
+    for (size_t i = 0; i < n; ++i) {
+        const ReadEntry &e = es[i];
+        if (!e.s.ring || e.counter || *e.count == 0) continue;
         const size_t bytes = (size_t)*e.count * e.s.item_w * 4;
         std::memcpy(e.out, src, bytes);
         src += bytes;
         *e.s.cursor += *e.count;
+    }
+    k = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const ReadEntry &e = es[i];
+        if (!e.s.ring || !e.counter) continue;
+        *e.count = res[2 * k];                            // (pos0 = 0: the items copied)
+        *e.s.cursor = res[2 * k + 1];
+        ++k;
+        std::memcpy(e.out, src, (size_t)*e.count * 4);
+        src += (size_t)e.max * 4;
     }
     return RCF_OK;
 }
@@ -144,7 +195,8 @@ int64_t read_one(rcf_t *h, const RingStream &s, float gain, void *out, size_t ma
 int read_many(PinnedStage &stage, hipStream_t stream, rcf_t *const *hs, size_t n_hs, const int *ms, const int *chan_ids, int n,
               int what, float gain, void *out, size_t cap_each, int64_t *counts)
 {
-    const size_t row = cap_each * (what == RCF_READ_FM ? sizeof(float) : sizeof(float2));
+    const int kind = stream_kind(what);
+    const size_t row = cap_each * stream_item_bytes(kind);
     std::vector<ReadEntry> es((size_t)n);
     for (int i = 0; i < n; ++i) {
         ReadEntry &e = es[(size_t)i];
@@ -154,8 +206,16 @@ int read_many(PinnedStage &stage, hipStream_t stream, rcf_t *const *hs, size_t n
         auto f = hs[m]->chans.find(chan_ids[i]);
         if (f == hs[m]->chans.end()) { counts[i] = RCF_ENOCHAN; continue; }
         e.c = f->second.get();
-        counts[i] = chan_stream(hs[m], e.c, what, &e.s);       // RCF_ESTATE: no such stream on this channel
-        e.gain = what == RCF_READ_FM ? gain : 1.0f;
+        if (kind_counted(kind)) {                              // the device finds the stream's end: no round trip here
+            CountedStream cs;
+            if ((counts[i] = counted_stream(e.c, kind, &cs)) == RCF_OK) {
+                e.s = RingStream{hs[m], cs.ring, 1u, 0u, 0, 0, cs.cursor};
+                e.counter = cs.counter; e.interp = cs.interp; e.decim = cs.decim;
+            }
+        } else {
+            counts[i] = chan_stream(hs[m], e.c, kind, &e.s);   // RCF_ESTATE: no such stream on this channel
+        }
+        e.gain = kind == RCF_READ_FM ? gain : 1.0f;
         e.out = static_cast<unsigned char *>(out) + (size_t)i * row;
         e.max = (int64_t)cap_each;
     }
@@ -192,7 +252,7 @@ int64_t rcf_chan_read_audio(rcf_t *h, int chan_id, float *out, size_t n) { retur
 int rcf_chan_read_many(rcf_t *h, int what, const int *chan_ids, int n_chans, float gain, void *out, size_t cap_each,
                        int64_t *counts)
 {
-    if (!h || !chan_ids || !out || !counts || n_chans < 0 || (what != RCF_READ_IQ && what != RCF_READ_FM && what != RCF_READ_AGC)) {
+    if (!h || !chan_ids || !out || !counts || n_chans < 0 || stream_kind(what) < 0) {
         set_error("bad batched read arguments");
         return RCF_EINVAL;
     }

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -46,6 +47,15 @@ static size_t pow2_at_least(size_t v)
     size_t p = 1;
     while (p < v) p <<= 1;
     return p;
+}
+
+// one number per attachment of a counted stage (a symbol loop, the voice chain): a reader that keeps a position of its own
+// in the stage's stream -- the pump's counted slots -- sees by it that the stage was attached again (a ring's address may
+// come back from the allocator; this does not)
+inline uint64_t next_stage_serial()
+{
+    static std::atomic<uint64_t> n{0};
+    return ++n;
 }
 
 struct Chan {
@@ -116,6 +126,7 @@ struct Chan {
         typedef State_ State;
         Rec_ rec{};
         int64_t from = 0, rd = 0;
+        const uint64_t serial = next_stage_serial();
         float *&ring() { return rec.*Ring; }
         size_t reach() const { return 0; }                               // the history is in the state record: no look-back
         // the record's two counters on the device, n_out then slips (ClockState keeps them behind `p`: moving them to the
@@ -139,6 +150,7 @@ struct Chan {
         // (one allocation from lpf on: lpf | hpf | rs (padded))
         AudioLaunch rec{};
         int64_t from = 0, rd = 0;       // rd: audio samples handed to the reader
+        const uint64_t serial = next_stage_serial();
         size_t reach() const { return (size_t)std::max(std::max(rec.n_lpf, rec.n_hpf), rec.nt_rs); }   // in the chain's own rings
         void release(rcf_t *h);
     };
@@ -432,13 +444,41 @@ struct RingStream {
     int64_t end = 0, newest = 0;
     int64_t *cursor = nullptr;
 };
-// the stages' streams: single reads only (the batched ABIs and the pump take RCF_READ_IQ / FM / AGC)
+// the stages' rows of the stream table.  These are table indices, not ABI values: the batched ABIs and the pump name the
+// same streams RCF_READ_SYM .. RCF_READ_AUDIO (16 .. 20), and stream_kind() maps `what` to the row (-1: no such stream;
+// 3 .. 15 stay refused)
 constexpr int kReadSym = 3, kReadClock = 4, kReadAudio = 5, kReadCostas = 6, kReadFsk4 = 7;
+inline int stream_kind(int what)
+{
+    switch (what) {
+        case RCF_READ_IQ: case RCF_READ_FM: case RCF_READ_AGC: return what;
+        case RCF_READ_SYM: return kReadSym;
+        case RCF_READ_CLOCK: return kReadClock;
+        case RCF_READ_COSTAS: return kReadCostas;
+        case RCF_READ_FSK4: return kReadFsk4;
+        case RCF_READ_AUDIO: return kReadAudio;
+        default: return -1;
+    }
+}
+inline size_t stream_item_bytes(int kind) { return kind == RCF_READ_IQ || kind == RCF_READ_AGC ? sizeof(float2) : sizeof(float); }
+// A counted stream -- a symbol loop's or the voice chain's: its end is ceil(*counter * interp / decim) of a DEVICE counter.
+// chan_stream fetches it (a round trip); the batched readers and the pump hand the counter to the counted gather instead
+// (CountedRec, rcf_internal.h).  serial: which attachment of the stage this is (a re-attached stage starts a new stream)
+struct CountedStream {
+    const void *ring = nullptr;
+    const int64_t *counter = nullptr;
+    uint32_t interp = 1, decim = 1;
+    int64_t *cursor = nullptr;
+    uint64_t serial = 0;
+};
+inline bool kind_counted(int kind) { return kind == kReadClock || kind == kReadCostas || kind == kReadFsk4 || kind == kReadAudio; }
+int counted_stream(Chan *c, int kind, CountedStream *s);   // kind_counted(kind); RCF_ESTATE: the channel has no such stage
 // The stream table of a channel: c's stream `kind` (RCF_READ_IQ / FM / AGC, kReadSym / Clock / Audio / Costas / Fsk4), or RCF_ESTATE with
 // the refusal's message (IQ of a discriminator-only tap, a stage the channel does not carry).  The first four end at
 // c->produced.  The clock's, the voice chain's, the Gardner / Costas loop's and the C4FM loop's end at their stage's device counter: one
 // asynchronous copy and one synchronisation of the stream (RCF_EHIP); *aux, if given, takes the counter beside it (the
-// loops' slips, the samples that passed the voice chain's squelch).
+// loops' slips, the samples that passed the voice chain's squelch).  That round trip is the single readers' and the
+// produced / state queries'; read_many and the pump use counted_stream instead.
 int chan_stream(rcf_t *h, Chan *c, int kind, RingStream *s, int64_t *aux = nullptr);
 // the front `bytes` of a stage's device state record: one asynchronous copy behind everything queued, one synchronisation
 int stage_state(rcf_t *h, const void *d_state, void *st, size_t bytes);
@@ -461,7 +501,8 @@ inline GatherRec gather_rec(const RingStream &s, int64_t n, uint32_t dst_w, uint
 }
 
 // one entry of a host read: a stream, the row its items go to and at most how many.  s.ring == nullptr: nothing to read
-// (*count holds the entry's error code already)
+// (*count holds the entry's error code already).  counter != nullptr: a counted stream (CountedStream) -- s carries its ring
+// and cursor, the device finds its end
 struct ReadEntry {
     RingStream s;
     Chan *c = nullptr;            // batched reads: a channel listed twice in one call is refused (RCF_EINVAL)
@@ -469,15 +510,20 @@ struct ReadEntry {
     void *out = nullptr;
     int64_t max = 0;
     int64_t *count = nullptr;     // out: items read, or the entry's error code
+    const int64_t *counter = nullptr;
+    uint32_t interp = 1, decim = 1;
 };
-// Every entry's new items in one gather_rings launch into `stage` and one synchronisation of `stream`; then the rows are
+// Every entry's new items in one gather launch (gather_rings; gather_counted for counted entries, which reserve
+// min(max, out_cap) items of staging each and learn their counts and cursors from the launch's result words) into `stage`
+// and one synchronisation of `stream`; then the rows are
 // copied out, the cursors advanced and the graveyards of the idle handles (those on `stream`) released.  RCF_ECAP when the
 // words do not fit the records' 32 bits, RCF_ENOMEM when the staging cannot be had.
 int host_read(PinnedStage &stage, hipStream_t stream, rcf_t *const *idle, size_t n_idle, ReadEntry *es, size_t n);
 // a single reader: host_read of one entry on h's own stream and staging; the items read, or an error code
 int64_t read_one(rcf_t *h, const RingStream &s, float gain, void *out, size_t max_items);
 // rcf_chan_read_many (hs = the handle, ms = nullptr) and rcf_group_read_many (hs = the members): entry i is channel
-// chan_ids[i] of hs[ms[i]] as `what` (RCF_READ_IQ / FM x gain / AGC) into row i of out; counts[i] its items or its error
+// chan_ids[i] of hs[ms[i]] as `what` (RCF_READ_IQ / FM x gain / AGC / SYM .. AUDIO; the caller has checked it with
+// stream_kind) into row i of out; counts[i] its items or its error
 int read_many(PinnedStage &stage, hipStream_t stream, rcf_t *const *hs, size_t n_hs, const int *ms, const int *chan_ids, int n,
               int what, float gain, void *out, size_t cap_each, int64_t *counts);
 

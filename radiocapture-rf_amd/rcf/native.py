@@ -47,6 +47,9 @@ SYMBOLS = [
 ]
 FMT_CF32, FMT_U8, FMT_S8, FMT_S16 = 0, 1, 2, 3
 READ_IQ, READ_FM, READ_AGC = 0, 1, 2
+# the streams of a channel's stages (RCF_READ_SYM .. RCF_READ_AUDIO): float32 rows of the batched readers and the pump
+READ_SYM, READ_CLOCK, READ_COSTAS, READ_FSK4, READ_AUDIO = 16, 17, 18, 19, 20
+_STAGE_WHAT = {"sym": READ_SYM, "clock": READ_CLOCK, "costas": READ_COSTAS, "fsk4": READ_FSK4, "audio": READ_AUDIO}
 T_FIR, T_PFB, T_FIR_DERIVED, T_DISC, T_SCAN_FFT, T_SCAN_MOVSUM, T_HISTORY, T_FIR_MFMA, T_AUDIO, T_TAPS, T_CLOCK, T_COSTAS, T_FSK4 = range(13)
 
 
@@ -296,13 +299,18 @@ def lib():
     return L
 
 
-def _read_what(what):
-    """the batched readers' `what`: "iq", "agc", anything else the discriminator (as it always was)"""
+def _read_what(what, stages=False):
+    """the batched readers' and the pump's `what`: "iq", "agc", anything else the discriminator (as it always was).
+    stages=True -- how every reader of this module calls it -- also names the stages' streams: "sym", "clock", "costas",
+    "fsk4", "audio".  The one-argument form keeps its old answers ("sym" was never a stream there: the discriminator)."""
+    if stages and what in _STAGE_WHAT:
+        return _STAGE_WHAT[what]
     return READ_IQ if what == "iq" else READ_AGC if what == "agc" else READ_FM
 
 
 def _read_dtype(what):
-    return np.float32 if _read_what(what) == READ_FM else np.complex64
+    """item type of stream `what` as the readers deliver it: cf32 for "iq" and "agc", float32 for everything else"""
+    return np.complex64 if _read_what(what, True) in (READ_IQ, READ_AGC) else np.float32
 
 
 def _check(rc):
@@ -663,7 +671,8 @@ class Frontend:
     def chan_read_many(self, cids, what="iq", gain=1.0, cap_each=1 << 14, out=None):
         """new samples of many channels behind ONE device synchronisation (rcf_chan_read_many) -> list of arrays
         (views into `out`, a [len(cids), cap_each] complex64 / float32 array -- pass a PinnedArray's for overlapping
-        copies), None where the channel no longer exists"""
+        copies), None where the channel no longer exists (or lacks the stream).  what: "iq", "fm" (x gain), "agc", or a
+        stage's stream -- "sym", "clock", "costas", "fsk4", "audio": float32, from where that stage's single reader stands"""
         n = len(cids)
         dt = _read_dtype(what)
         if out is None:
@@ -671,7 +680,7 @@ class Frontend:
         out = out.reshape(-1, cap_each)
         ids = (C.c_int * max(n, 1))(*[int(c) for c in cids])
         counts = (C.c_int64 * max(n, 1))()
-        _check(lib().rcf_chan_read_many(self._h, _read_what(what), ids, n, float(gain),
+        _check(lib().rcf_chan_read_many(self._h, _read_what(what, True), ids, n, float(gain),
                                         out.ctypes.data_as(C.c_void_p), int(cap_each), counts))
         return [None if counts[i] < 0 else out[i, :counts[i]] for i in range(n)]
 
@@ -688,7 +697,7 @@ class Frontend:
         ids = (C.c_int * max(n, 1))(*[int(c) for c in cids])
         counts = np.zeros(max(n, 1), dtype=np.int64)
         f = lib().rcf_chan_read_many
-        args = (self._h, _read_what(what), ids, n, C.c_float(float(gain)), out2.ctypes.data_as(C.c_void_p),
+        args = (self._h, _read_what(what, True), ids, n, C.c_float(float(gain)), out2.ctypes.data_as(C.c_void_p),
                 C.c_size_t(int(cap_each)), counts.ctypes.data_as(C.POINTER(C.c_int64)))
 
         def call():
@@ -966,7 +975,7 @@ class Group:
         ms = (C.c_int * max(n, 1))(*[int(m) for m, _ in pairs])
         cs = (C.c_int * max(n, 1))(*[int(c) for _, c in pairs])
         counts = (C.c_int64 * max(n, 1))()
-        _check(lib().rcf_group_read_many(self._g, _read_what(what), ms, cs, n, float(gain),
+        _check(lib().rcf_group_read_many(self._g, _read_what(what, True), ms, cs, n, float(gain),
                                          out.ctypes.data_as(C.c_void_p), int(cap_each), counts))
         return [None if counts[i] < 0 else out[i, :counts[i]].copy() for i in range(n)]
 
@@ -978,7 +987,7 @@ class Pump:
     cyclically at `samp_rate` of wall-clock time, block boundaries shifted by phase_s[i], or, where `written[i]` is a
     one-element uint64 array, taken block by block as its producer counts them complete.  Subscriptions may be given at
     start ((member, channel id) pairs delivered as `what` x `gain`) and change while it runs (subscribe / unsubscribe, up to
-    `max_read` at a time)."""
+    `max_read` at a time).  what: "iq", "fm", "agc" or a stage's stream ("sym", "clock", "costas", "fsk4", "audio")."""
 
     def __init__(self, group, rings, block_samples, samp_rate, subscriptions=(), fmt=FMT_U8, scale=1.0, offset=0.0,
                  what="fm", gain=1.0, phase_s=None, out_ring_samples=4096, n_blocks=0, warm_blocks=0, max_batch=0,
@@ -1016,7 +1025,7 @@ class Pump:
         cfg.block_samples, cfg.fmt, cfg.scale, cfg.offset = int(block_samples), int(fmt), float(scale), float(offset)
         cfg.samp_rate = float(samp_rate)
         cfg.rings, cfg.ring_blocks, cfg.phase_s, cfg.written = rp, rb, ph, wr
-        cfg.what, cfg.gain = (READ_IQ if what == "iq" else READ_FM), float(gain)
+        cfg.what, cfg.gain = _read_what(what, True), float(gain)
         cfg.read_members, cfg.read_chans, cfg.n_read = ms, cs, ne
         cfg.out_ring_samples, cfg.n_blocks, cfg.warm_blocks = int(out_ring_samples), int(n_blocks), int(warm_blocks)
         cfg.max_batch, cfg.cpu, cfg.start_delay_s = int(max_batch), int(cpu), float(start_delay_s)
@@ -1060,7 +1069,7 @@ class Pump:
     def subscribe(self, member, chan_id, what="iq", gain=1.0):
         """channel `chan_id` of member `member` from its next output on -> the slot (rcf_pump_subscribe)"""
         cur = C.c_int64(0)
-        e = _check(lib().rcf_pump_subscribe(self._p, int(member), int(chan_id), READ_IQ if what == "iq" else READ_FM,
+        e = _check(lib().rcf_pump_subscribe(self._p, int(member), int(chan_id), _read_what(what, True),
                                             float(gain), C.byref(cur)))
         self._cursors[e] = cur
         self._what[e] = what
@@ -1077,7 +1086,7 @@ class Pump:
         return _check(lib().rcf_pump_written(self._p, int(entry)))
 
     def read(self, entry, max_items=1 << 16):
-        dt = np.complex64 if self._what[entry] == "iq" else np.float32
+        dt = _read_dtype(self._what[entry])
         out = np.empty(max_items, dtype=dt)
         n = _check(lib().rcf_pump_read(self._p, int(entry), C.byref(self._cursors[entry]),
                                        out.ctypes.data_as(C.c_void_p), int(max_items)))
@@ -1092,7 +1101,7 @@ class Pump:
         counts = (C.c_int64 * max(n, 1))()
         out = np.empty((max(n, 1), cap_each), dtype=np.complex64)
         outf = out.view(np.float32)
-        is_iq = [self._what[e] == "iq" for e in entries]
+        is_iq = [_read_dtype(self._what[e]) == np.complex64 for e in entries]   # cf32 rows ("iq", "agc")
         fn, pp, op = lib().rcf_pump_read_many, self._p, out.ctypes.data_as(C.c_void_p)
 
         def call():
