@@ -1546,3 +1546,173 @@ def test_random_batched_reads_equal_single_reads_under_churn(gpu_required, seed)
                     continue
                 one = a.chan_read_iq(ia[i], cap) if what == "iq" else a.chan_read_fm(ia[i], 2.5, cap)
                 assert len(one) == len(got[pos]) and np.array_equal(one, got[pos]), (seed, blk, what, cap, i, len(one), len(got[pos]))
+
+
+@pytest.mark.parametrize("seed", _seeds())
+def test_random_stage_streams_batched_reads_equal_single_reads(gpu_required, seed):
+    """The stages' streams (symbol filter, the three symbol loops, the voice chain) through rcf_chan_read_many against the
+    single readers on a twin front-end fed the same stream, under a random lifecycle: direct channels of 12.5 and 25 kHz
+    opened and closed, stages attached, attached again (a fresh ring) and switched off at random block boundaries, ragged
+    pushes, rings of 2^8 .. 2^11 (wraps and lagging readers), random capacities per call, random list orders with the id
+    of a channel closed since the last read left in, single reads of a few items in between.  Bit for bit; refused
+    positions by their code.  A block is held to what the smallest ring takes -- (ring - 64) / 2 samples of a 12.5 kHz
+    channel, at most 1200: a 25 kHz channel makes twice as many and the AGC's window sits behind them.  The voice chain
+    is the DSD feed (48/25 and 24/25), whose filters fit rings of 256.  Every draw depends on earlier draws only, never on
+    what the device returned: a failing seed replays."""
+    from rcf import audio as host_audio
+    from rcf import p25
+    nat = gpu_required
+    rng = np.random.default_rng(41000 + seed)
+    fs, D = 2.4e6, 96
+    cap = 1 << int(rng.integers(8, 12))
+    most = min(1200, (cap - 64) // 2)
+    n_blocks = int(rng.integers(6, 13))
+    sizes = [int(rng.integers(1, 3 * D + 1)) if rng.random() < 0.2 else int(rng.integers(most * D // 2, most * D + 1))
+             for _ in range(n_blocks)]
+    slots = [(int(rng.choice([12500, 25000])), -100e3 + 25e3 * i) for i in range(9)]
+    x = synth.awgn(rng, int(np.sum(sizes))).astype(np.complex128)
+    for i in range(4):
+        x += synth.nbfm_carrier(len(x), fs, slots[i][1] + 200.0, 700.0 + 90 * i, 2500.0, 0.4)
+    x = x.astype(np.complex64)
+    whats = ("sym", "clock", "costas", "fsk4", "audio")
+    single = {"sym": "chan_read_sym", "clock": "chan_read_clock", "costas": "chan_read_costas", "fsk4": "chan_read_fsk4",
+              "audio": "chan_read_audio"}
+    stages = ("fsk4", "costas", "clock", "audio")
+    feeds = {cr: host_audio.dsd_feed_params(2 * cr, 0.4) for cr in (12500, 25000)}
+    items = {w: 0 for w in whats}
+    refused = [0]
+
+    def bits(v):
+        return np.ascontiguousarray(v).view(np.uint32)
+
+    with nat.Frontend(fs, block_capacity=max(sizes) + 16, out_capacity=cap) as a, \
+            nat.Frontend(fs, block_capacity=max(sizes) + 16, out_capacity=cap) as b:
+        live, pending_dead = {}, []                          # slot -> dict(ia, ib, cr, has); (ia, ib) closed since the last read
+
+        def both(L, fn):
+            codes = []
+            for fe, cid in ((a, L["ia"]), (b, L["ib"])):
+                try:
+                    fn(fe, cid)
+                    codes.append(0)
+                except nat.RcfError as e:
+                    codes.append(e.code)
+            assert codes[0] == codes[1], (seed, codes)
+            return codes[0] == 0
+
+        def attach(L, st):
+            cr = L["cr"]
+            if st == "fsk4":
+                if "sym" not in L["has"] and both(L, lambda fe, c: fe.chan_fm_filter(c, p25.fm_gain(cr), p25.symbol_taps(cr))):
+                    L["has"].add("sym")
+                ok = both(L, lambda fe, c: fe.chan_fsk4(c, **p25.fsk4_params(cr)))
+            elif st == "costas":
+                if "agc" not in L["has"] and both(L, lambda fe, c: fe.chan_agc(c, 16, 1.0)):
+                    L["has"].add("agc")
+                ok = both(L, lambda fe, c: fe.chan_costas(c, **p25.costas_params(cr)))
+            elif st == "clock":
+                ok = both(L, lambda fe, c: fe.chan_clock_mm(c, 2 * cr / 3600.0))
+            else:
+                if "audio" in L["has"]:
+                    both(L, lambda fe, c: fe.chan_audio_close(c))
+                    L["has"].discard("audio")
+                ok = both(L, lambda fe, c: fe.chan_audio_open(c, **feeds[cr]))
+            if ok:
+                L["has"].add(st)
+
+        def switch_off(L, st):
+            off = {"fsk4": lambda fe, c: fe.chan_fsk4(c, None), "costas": lambda fe, c: fe.chan_costas(c, None),
+                   "clock": lambda fe, c: fe.chan_clock_mm(c, None), "audio": lambda fe, c: fe.chan_audio_close(c)}[st]
+            if both(L, off):
+                L["has"].discard(st)
+
+        def open_slot(i):
+            cr, f = slots[i]
+            live[i] = dict(ia=a.chan_open(cr, f), ib=b.chan_open(cr, f), cr=cr, has=set())
+            return live[i]
+
+        def act():
+            u = rng.random()
+            free = [i for i in range(len(slots)) if i not in live]
+            if (u < 0.3 or not live) and free:
+                open_slot(free[int(rng.integers(0, len(free)))])
+                return
+            if not live:
+                return
+            keys = sorted(live)
+            i = keys[int(rng.integers(0, len(keys)))]
+            L = live[i]
+            have = [st for st in stages if st in L["has"]]
+            if u < 0.6:
+                for st in stages:
+                    if rng.random() < 0.5:
+                        attach(L, st)
+            elif u < 0.75:
+                if have:
+                    attach(L, have[int(rng.integers(0, len(have)))])        # again: a fresh ring, item 0
+            elif u < 0.9:
+                if have:
+                    switch_off(L, have[int(rng.integers(0, len(have)))])
+            else:
+                a.chan_close(L["ia"])
+                b.chan_close(L["ib"])
+                pending_dead.append((L["ia"], L["ib"]))
+                del live[i]
+
+        def compare(what, cap_each, lst):
+            counts, out = b.chan_read_many_plan([ib for _, ib in lst], what, cap_each=cap_each)()
+            for j, (ia, ib) in enumerate(lst):
+                try:
+                    one = getattr(a, single[what])(ia, cap_each)
+                except nat.RcfError as e:
+                    assert counts[j] == e.code, (seed, what, cap_each, j, counts[j], e.code)
+                    refused[0] += 1
+                    continue
+                assert counts[j] == len(one) and np.array_equal(bits(out[j, :counts[j]]), bits(one)), \
+                    (seed, what, cap_each, j, int(counts[j]), len(one))
+                items[what] += len(one)
+
+        at = 0
+        for blk, n in enumerate(sizes):
+            if blk == 0:                                     # a population to begin with: six channels carrying every stage
+                for i in range(6):
+                    L = open_slot(i)
+                    for st in stages:
+                        attach(L, st)
+            for _ in range(int(rng.integers(0, 4))):
+                act()
+            a.push(x[at:at + n])
+            b.push(x[at:at + n])
+            at += n
+            if rng.random() >= 0.7:
+                continue                                     # nobody reads this block: lag, perhaps past the ring
+            what = whats[int(rng.integers(0, len(whats)))]
+            cap_each = int(rng.choice([7, 64, 257, cap, 4096]))
+            lst = [(L["ia"], L["ib"]) for _, L in sorted(live.items())]
+            if pending_dead and rng.random() < 0.7:
+                lst.append(pending_dead[-1])
+            pending_dead.clear()
+            lst = [lst[i] for i in rng.permutation(len(lst))]
+            if lst and rng.random() < 0.3:                   # a single read of a few items first, on both twins
+                ia, ib = lst[int(rng.integers(0, len(lst)))]
+                few = int(rng.integers(1, 12))
+                res = []
+                for fe, cid in ((a, ia), (b, ib)):
+                    try:
+                        res.append(getattr(fe, single[what])(cid, few))
+                    except nat.RcfError as e:
+                        res.append(e.code)
+                if isinstance(res[0], np.ndarray):
+                    assert isinstance(res[1], np.ndarray) and np.array_equal(bits(res[0]), bits(res[1])), (seed, blk, what)
+                else:
+                    assert res[0] == res[1], (seed, blk, what, res)
+            if lst:
+                compare(what, cap_each, lst)
+        lst = [(L["ia"], L["ib"]) for _, L in sorted(live.items())]
+        for what in whats:                                   # and every stream once more, a ring's worth
+            if lst:
+                compare(what, cap, lst)
+    counted = sorted((items[w] for w in ("clock", "costas", "fsk4", "audio")), reverse=True)
+    if os.environ.get("RCF_FUZZ_DEBUG"):
+        print("DBG", seed, "ring", cap, "blocks", n_blocks, "items", items, "refused", refused[0])
+    assert sum(items.values()) > 1000 and counted[1] > 100, (seed, cap, n_blocks, items, refused[0])
