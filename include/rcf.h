@@ -161,7 +161,8 @@ int rcf_device(rcf_t *h);
 #define RCF_T_CLOCK        10  /* symbol clocks (rcf_chan_clock_mm): one launch per block for every clocked channel */
 #define RCF_T_COSTAS       11  /* Gardner / Costas loops (rcf_chan_costas): one launch per block for every channel with the stage */
 #define RCF_T_FSK4         12  /* C4FM symbol loops (rcf_chan_fsk4): one launch per block for every channel with the stage */
-#define RCF_T_COUNT        13
+#define RCF_T_SLICE        13  /* hard decisions (rcf_chan_slicer): one launch per block for every channel with the stage */
+#define RCF_T_COUNT        14
 /* on = 0: off; 1: every class; otherwise a mask with bit (class + 1) set for each class to time -- every timed
  * launch costs two event records on the stream (~10 us of gap), so a throughput run times only what it reports.  The
  * filterbank's launch carries its two events attached to the dispatch (one barrier packet less inside the measured
@@ -268,6 +269,11 @@ int64_t rcf_chan_read_fm(rcf_t *h, int chan_id, float gain, float *out, size_t m
 #define RCF_READ_COSTAS  18   /* float32 soft symbols of rcf_chan_costas */
 #define RCF_READ_FSK4    19   /* float32 soft symbols of rcf_chan_fsk4 */
 #define RCF_READ_AUDIO   20   /* float32 audio of the voice chain */
+/* The two streams of rcf_chan_slicer, batched the same way: out = uint32[n_chans][cap_each], gain ignored, RCF_ESTATE for a
+ * channel without the stage; the reader positions are those of rcf_chan_read_hard / rcf_chan_read_sync.  They are not float
+ * streams and the real-time pump does not deliver them (rcf_pump_start / rcf_pump_subscribe: RCF_EINVAL). */
+#define RCF_HARD_BITS    32   /* uint32 words of packed decisions */
+#define RCF_HARD_SYNC    33   /* uint32 sync hits, (distance << 26) | (k & 0x3ffffff) */
 int rcf_chan_read_many(rcf_t *h, int what, const int *chan_ids, int n_chans, float gain, void *out, size_t cap_each,
                        int64_t *counts);
 /* P25 C4FM front half after the discriminator (p25_control_demod.py:129-133, logging_receiver.py:240-244):
@@ -328,7 +334,8 @@ int rcf_chan_agc_ring(rcf_t *h, int chan_id, void **agc_ring, size_t *capacity);
  * p == NULL switches the stage off.  It starts, with zero history, at the channel's next output (again on every call:
  * symbol 0 is the first of the call); applies from the next block on, on every channel kind (direct, chained, stage-2,
  * filterbank tap, discriminator-only taps included: it reads the discriminator ring, not the IQ); a retune keeps it,
- * closing the channel releases it.  Packet framing behind the slicer stays with the consumer.
+ * closing the channel releases it.  The slicer and the packing are rcf_chan_slicer, below (which this
+ * call detaches: its source starts again at symbol 0); packet framing stays with the consumer.
  * RCF_EINVAL: a non-finite parameter, omega * (1 - omega_relative_limit) < 2 (GNU Radio's documented domain), omega > 4096,
  * mu outside 0 .. 1; RCF_ENOCHAN: no such channel; RCF_ECAP: out_capacity < 16 -- and at a block that yields more outputs
  * than the ring holds beside the 7 samples of look-back (nothing is queued then). */
@@ -386,7 +393,8 @@ int rcf_chan_clock_ring(rcf_t *h, int chan_id, void **sym_ring, size_t *capacity
  * per channel sample, of the sign opposite to the carrier's offset: what a drift reporter needs.
  * p == NULL switches the stage off.  It starts, with zero history, at the channel's next output (again on every call: a
  * fresh ring and state, symbol 0 is the first of the call); applies from the next block on, on every channel kind that can
- * carry an AGC; a retune keeps it, closing the channel releases it.  The slicer and the framing stay with the consumer.
+ * carry an AGC; a retune keeps it, closing the channel releases it.  The slicer is rcf_chan_slicer, below (which
+ * this call detaches: its source starts again at symbol 0); the framing stays with the consumer.
  * RCF_EINVAL: a parameter that is not finite, omega outside 2 .. 16, omega - omega_limit - gain_mu < 2 (so that mu > 1
  * after every symbol), a negative omega_limit or max_freq, max_freq >= pi; RCF_ENOCHAN: no such channel; RCF_ESTATE: the
  * channel has no AGC; RCF_ECAP: out_capacity < 64. */
@@ -451,8 +459,8 @@ int rcf_chan_costas_ring(rcf_t *h, int chan_id, void **sym_ring, size_t *capacit
  * p == NULL switches the stage off.  It starts, with zero history, at the channel's next output (again on every call: a
  * fresh ring and state, symbol 0 is the first of the call); applies from the next block on, on every channel kind that can
  * carry a symbol filter (direct, chained, stage-2, filterbank tap -- a discriminator-only tap too: the stage reads no
- * IQ); a retune keeps it, a second rcf_chan_fm_filter call keeps it, closing the channel releases it.  The slicer and the
- * framing stay with the consumer.
+ * IQ); a retune keeps it, a second rcf_chan_fm_filter call keeps it, closing the channel releases it.  The slicer is
+ * rcf_chan_slicer, below (which this call detaches: its source starts again at symbol 0); the framing stays with the consumer.
  * RCF_EINVAL: a parameter that is not finite, sample_rate / symbol_rate outside 2 .. 4096, spread_min or spread_max not
  * 0 < spread_min <= 2 <= spread_max; RCF_ENOCHAN: no such channel; RCF_ESTATE: the channel has no symbol filter;
  * RCF_ECAP: out_capacity < 16. */
@@ -477,6 +485,63 @@ int64_t rcf_chan_read_fsk4(rcf_t *h, int chan_id, float *out, size_t max_symbols
 /* device pointer of the soft-symbol ring and its capacity (zero-copy, like rcf_chan_rings): symbol k lives at index
  * k & (capacity-1); rcf_chan_fsk4_state gives the count */
 int rcf_chan_fsk4_ring(rcf_t *h, int chan_id, void **sym_ring, size_t *capacity);
+/* Hard decisions behind a symbol loop: the step that follows the soft symbols in every demodulator chain of the reference,
+ *     op25.fsk4_slicer_fb([-2, 0, 2, 4])                                   (p25_control_demod.py:167-168, logging_receiver.py:250-251,307-308)
+ *     digital.binary_slicer_fb -> blocks.unpacked_to_packed_bb(1, GR_MSB_FIRST)   (moto_control_demod.py:114-115, edacs_control_demod.py:86-90)
+ * and the consumers' search for the frame-sync word (p25_control_demod.py:337 5575f5ff77ff, moto_control_demod.py:216
+ * 10101100, edacs_control_demod.py:523 its 48-bit word), as one more optional stage per channel on the GPU.  It reads the
+ * soft-symbol ring of ONE of the channel's symbol loops and writes two streams: packed decisions and sync hits.  All of it is
+ * integer work on the loop's float32 outputs: the streams are exactly what the rules below give for the soft symbols the
+ * loop's own reader delivers.
+ * Decision d[k] of soft symbol s[k]:
+ *     RCF_SLICE_BINARY   d = s >= 0 ? 1 : 0                                                       (a NaN gives 0)
+ *     RCF_SLICE_FSK4     d = s < levels[0] ? 3 : s < levels[1] ? 2 : s < levels[2] ? 0 : 1        (a NaN gives 1; levels[3] decides nothing, as in op25)
+ * k counts from the stage's start: the loop's n_symbols at the moment of the call (which reads that counter and so
+ * synchronises the stream, as rcf_chan_fsk4_state does).
+ * Bit stream: per symbol the 1 or 2 bits of d (bps), the higher one first; bits fill bytes from the top place down --
+ * unpacked_to_packed_bb(bps, GR_MSB_FIRST) -- and bytes fill 32-bit words in memory order: byte j of the stream is byte
+ * j & 3 of word j >> 2 (little-endian), so a uint8 view of the word ring is GNU Radio's byte stream and a frame-aligned P25
+ * stream shows 55 75 f5 ff 77 ff as it stands.  The stream's items are whole words, 32 / bps symbols each; the unfinished
+ * word stays in the stage's state and leaves when it is full (at most 15 dibits, 3.3 ms at 4800 baud, late).
+ * Sync hits: L = sync_bits / bps.  For every k >= L - 1, dist = popcount((window ^ sync_word) & (2^sync_bits - 1)), window =
+ * the last sync_bits bits of the bit stream ending with symbol k, the oldest bit highest.  If dist <= sync_max_errors one
+ * item is appended to the hit ring: uint32 = (dist << 26) | (k & 0x3ffffff), k the LAST symbol of the window; items are in
+ * increasing k.  A reader widens k against n_symbols: the largest value <= n_symbols - 1 with those low 26 bits.  Neither
+ * stream depends on how the input was cut into blocks.  The word ring has out_capacity words, the hit ring hit_capacity
+ * items; a reader that falls more than a ring behind loses the oldest.
+ * p == NULL switches the stage off.  It applies from the next block on, on every channel kind its source loop supports; a
+ * retune keeps it, calling again starts it afresh (new rings and state, k = 0 at the loop's next symbol), closing the
+ * channel releases it.  Switching the source loop off, or attaching it again (a fresh ring, symbol 0), DETACHES the slicer:
+ * it must be attached again behind the new loop.  A channel has at most one slicer.
+ * RCF_EINVAL: an unknown source or mode, levels that are not finite or not non-decreasing (RCF_SLICE_FSK4), sync_bits not 0
+ * or 8 .. 64 and a multiple of the bits per symbol, sync_max_errors outside 0 .. sync_bits - 1 (0 without a search),
+ * hit_capacity not 0 or a power of two >= 16 (at most 2^26); RCF_ENOCHAN: no such channel; RCF_ESTATE: the channel does not
+ * carry the named loop; RCF_ECAP: out_capacity < 64. */
+#define RCF_SLICE_BINARY 1
+#define RCF_SLICE_FSK4   2
+typedef struct rcf_slicer_params {
+    int source;            /* RCF_READ_CLOCK, RCF_READ_COSTAS or RCF_READ_FSK4: the loop whose soft symbols are sliced */
+    int mode;              /* RCF_SLICE_BINARY (1 bit per symbol) / RCF_SLICE_FSK4 (2 bits per symbol) */
+    float levels[4];       /* RCF_SLICE_FSK4 only: -2, 0, 2, 4 in the reference */
+    uint64_t sync_word;    /* the low sync_bits bits, first-received bit highest */
+    int sync_bits;         /* 0: no search; else 8 .. 64 and a multiple of the bits per symbol */
+    int sync_max_errors;   /* a hit is a Hamming distance <= this, 0 .. sync_bits - 1 (63 at most) */
+    int hit_capacity;      /* items of the hit ring, a power of two >= 16; 0 = 256 */
+    int reserved_;
+} rcf_slicer_params_t;
+int rcf_chan_slicer(rcf_t *h, int chan_id, const rcf_slicer_params_t *p);
+/* the stage's counters as of the last block; syncs the stream.  RCF_ESTATE without the stage (here and in the calls below) */
+typedef struct rcf_slicer_state {
+    int64_t n_symbols, n_words, n_hits;   /* symbols sliced, whole words written, hits appended since the stage was (last) attached */
+} rcf_slicer_state_t;
+int rcf_chan_slicer_state(rcf_t *h, int chan_id, rcf_slicer_state_t *out);
+/* unread words of packed decisions / unread sync hits, oldest first (one round trip each) */
+int64_t rcf_chan_read_hard(rcf_t *h, int chan_id, uint32_t *out, size_t max_words);
+int64_t rcf_chan_read_sync(rcf_t *h, int chan_id, uint32_t *out, size_t max_hits);
+/* device pointers of the word ring and the hit ring and their capacities (zero-copy, like rcf_chan_fsk4_ring): word i lives
+ * at index i & (word_capacity - 1), hit i at i & (hit_capacity - 1); rcf_chan_slicer_state gives the counts.  Any of the
+ * four may be NULL. */
+int rcf_chan_slicer_rings(rcf_t *h, int chan_id, void **word_ring, size_t *word_capacity, void **hit_ring, size_t *hit_capacity);
 /* drift probe of p25_control_demod.py:123-127: moving_average_ff(window, 1) * (1/window) of the
  * discriminator output (window = 10000 there) == mean of gain*fm over the last `window` samples; this is
  * the value demod_watcher hands to frontend_connector.report_offset */

@@ -324,6 +324,33 @@ struct Fsk4Launch {
     double k_spread, k_timing, k_fine, k_coarse, spread_min, spread_max;
 };
 void launch_fsk4(const Fsk4Launch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
+// Hard decisions behind a symbol loop (slice.hip; binary_slicer_fb / op25 fsk4_slicer_fb -> unpacked_to_packed_bb(MSB_FIRST)
+// and the consumers' frame-sync search; definition: include/rcf.h at rcf_chan_slicer).
+// per-channel running state, device resident, owned by slice_kernel
+struct SliceState {
+    int64_t n_words;         // whole words written so far (word i at word_ring[i & word_mask])
+    int64_t n_symbols;       // soft symbols sliced so far: symbol k of the stage is symbol src0 + k of the loop
+    int64_t n_hits;          // sync hits appended so far (hit i at hit_ring[i & hit_mask])
+    uint32_t partial;        // the unfinished word in stream order (first-received bit = bit 31), its missing bits 0
+    uint32_t pad_;
+    uint64_t tail;           // the last 64 bits of the bit stream, the newest lowest
+};
+struct SliceLaunch {
+    const float *soft_ring;  // the source loop's soft-symbol ring
+    const int64_t *src_n_out;   // the source loop's n_out (device)
+    SliceState *st;
+    uint32_t *word_ring;
+    uint32_t *hit_ring;
+    uint64_t sync_word;
+    int64_t src0;            // the loop's n_out when the stage was attached
+    uint32_t soft_mask, word_mask, hit_mask;
+    int32_t n_k;             // the source loop's n_k of this block: at most that many new symbols
+    int32_t bps;             // bits per symbol: 1 (RCF_SLICE_BINARY) or 2 (RCF_SLICE_FSK4)
+    int32_t sync_bits;       // 0: no search
+    int32_t sync_max_errors;
+    float levels[3];         // bps 2: the decision levels (the fourth of rcf_slicer_params_t decides nothing)
+};
+void launch_slice(const SliceLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
 // mean of gain * fm over the last `window` samples ending at n_end (exclusive), one workgroup
 void launch_fm_level(const float *fm_ring, int64_t n_end, int window, float gain, uint64_t ring_mask, float *d_out,
                      hipStream_t s);

@@ -347,6 +347,14 @@ int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c)
     // (the two loops behind another stage start where both have started: the AGC's start moves on a re-call)
     if (c->costas) stage(c->costas->rec, std::max(c->costas->from, c->agc->from), bp.tails.gcf);
     if (c->fsk4) stage(c->fsk4->rec, std::max(c->fsk4->from, c->sym->from), bp.tails.f4f);
+    if (c->slicer) {                   // bounded by its source loop's n_k of this block: a loop makes at most one symbol per input
+        const int src = c->slicer->source;
+        const int64_t from = src == RCF_READ_CLOCK ? c->clock->from : src == RCF_READ_COSTAS ? std::max(c->costas->from, c->agc->from)
+                                                                                              : std::max(c->fsk4->from, c->sym->from);
+        SliceLaunch rec = c->slicer->rec;
+        rec.n_k = (int32_t)(s.n_lo + s.cnt - std::max(s.n_lo, from));
+        if (rec.n_k > 0) bp.tails.slf.add(rec);
+    }
     if (c->audio && s.a_n > 0) {
         AudioLaunch al = c->audio->rec;
         al.n_lo = s.a_lo;

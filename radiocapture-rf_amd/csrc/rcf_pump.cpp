@@ -431,7 +431,7 @@ int rcf_pump_start(rcf_group_t *g, const rcf_pump_config_t *cfg, rcf_pump_t **ou
 {
     if (!g || !cfg || !out || cfg->block_samples == 0 || !(cfg->samp_rate > 0) || !cfg->rings || !cfg->ring_blocks ||
         cfg->n_read < 0 || (cfg->n_read && (!cfg->read_members || !cfg->read_chans)) ||
-        stream_kind(cfg->what) < 0 || group_sample_bytes(cfg->fmt) == 0) {
+        stream_kind(cfg->what) < 0 || kind_hard(stream_kind(cfg->what)) || group_sample_bytes(cfg->fmt) == 0) {   // (the slicer's streams: not delivered)
         set_error("bad pump configuration");
         return RCF_EINVAL;
     }
@@ -650,7 +650,7 @@ int rcf_pump_read_many(rcf_pump_t *p, const int *entries, int64_t *cursors, int 
 
 int rcf_pump_subscribe(rcf_pump_t *p, int member, int chan_id, int what, float gain, int64_t *cursor)
 {
-    if (!p || stream_kind(what) < 0) { set_error("bad subscription"); return RCF_EINVAL; }
+    if (!p || stream_kind(what) < 0 || kind_hard(stream_kind(what))) { set_error("bad subscription"); return RCF_EINVAL; }
     rcf_group *g = p->g;
     std::lock_guard<std::mutex> gl(g->mu);
     if (member < 0 || member >= (int)g->members.size()) { set_error("no such member %d", member); return RCF_EINVAL; }

@@ -1,4 +1,4 @@
-// rcf_read.cpp -- the stream table of a channel (chan_stream: eight streams, one row each; counted_stream: the four whose end
+// rcf_read.cpp -- the stream table of a channel (chan_stream: ten streams, one row each; counted_stream: the six whose end
 // is a device counter, without the round trip) and the one read path of every host read (host_read: one gather launch, one
 // synchronisation), with the read and ring entry points of the C ABI.
 #include <atomic>
@@ -17,7 +17,8 @@ static int stream_row(Chan *c, int kind, StreamRow *r)
     Chan::Audio *au = c->audio.get();
     Chan::Costas *gc = c->costas.get();
     Chan::Fsk4 *fk = c->fsk4.get();
-    const StreamRow t[8] = {
+    Chan::Slicer *sl = c->slicer.get();
+    const StreamRow t[10] = {
         {c->fm_only ? nullptr : c->d_iq, 2, &c->rd_iq, "channel %d exposes its discriminator only (rcf_chan_set_fm_only)"},
         {c->d_fm, 1, &c->rd_fm, "channel %d has no discriminator ring"},
         {ag ? ag->rec.agc_ring : nullptr, 2, ag ? &ag->rd : nullptr, "channel %d has no AGC"},
@@ -26,6 +27,8 @@ static int stream_row(Chan *c, int kind, StreamRow *r)
         {au ? au->rec.o_ring : nullptr, 1, au ? &au->rd : nullptr, "channel %d has no audio chain"},
         {gc ? gc->ring() : nullptr, 1, gc ? &gc->rd : nullptr, "channel %d has no Gardner / Costas stage"},
         {fk ? fk->ring() : nullptr, 1, fk ? &fk->rd : nullptr, "channel %d has no C4FM symbol loop (rcf_chan_fsk4)"},
+        {sl ? sl->rec.word_ring : nullptr, 1, sl ? &sl->rd_words : nullptr, "channel %d has no slicer (rcf_chan_slicer)"},
+        {sl ? sl->rec.hit_ring : nullptr, 1, sl ? &sl->rd_hits : nullptr, "channel %d has no slicer (rcf_chan_slicer)"},
     };
     if (!t[kind].ring) { set_error(t[kind].refusal, c->id); return RCF_ESTATE; }
     *r = t[kind];
@@ -49,6 +52,8 @@ int counted_stream(Chan *c, int kind, CountedStream *s)
         case kReadClock:  s->counter = static_cast<const int64_t *>(c->clock->counters()); s->serial = c->clock->serial; break;
         case kReadCostas: s->counter = static_cast<const int64_t *>(c->costas->counters()); s->serial = c->costas->serial; break;
         case kReadFsk4:   s->counter = static_cast<const int64_t *>(c->fsk4->counters()); s->serial = c->fsk4->serial; break;
+        case kHardBits:   s->counter = &c->slicer->rec.st->n_words; break;
+        case kHardSync:   s->counter = &c->slicer->rec.st->n_hits; s->cap = c->slicer->hit_cap; break;
         default:                                         // kReadAudio: ceil(n_a * interp / decim), as chan_stream has it
             s->counter = &c->audio->rec.st->n_a;
             s->interp = (uint32_t)c->audio->rec.interp; s->decim = (uint32_t)c->audio->rec.decim;
@@ -116,7 +121,8 @@ int host_read(PinnedStage &stage, hipStream_t stream, rcf_t *const *idle, size_t
         if (!e.s.ring) continue;
         if (e.counter) {
             *e.count = 0;
-            e.max = std::min<int64_t>(e.max, (int64_t)e.s.h->out_cap);
+            if (!e.cap) e.cap = (uint32_t)e.s.h->out_cap;
+            e.max = std::min<int64_t>(e.max, (int64_t)e.cap);
             if (e.max <= 0) { e.s.ring = nullptr; continue; }
             counted_w += (uint64_t)e.max;
             max_c = std::max<uint32_t>(max_c, (uint32_t)e.max);
@@ -153,7 +159,7 @@ int host_read(PinnedStage &stage, hipStream_t stream, rcf_t *const *idle, size_t
         if (!e.s.ring || !e.counter) continue;
         crecs[k] = CountedRec{static_cast<const uint32_t *>(e.s.ring), e.counter, nullptr, nullptr,
                               reinterpret_cast<int64_t *>(stage.d + res_at) + 2 * k, *e.s.cursor, 0, e.interp, e.decim,
-                              (uint32_t)e.s.h->out_cap, (uint32_t)e.max, at_w, ~0u, 3u, 0u};
+                              e.cap, (uint32_t)e.max, at_w, ~0u, 3u, 0u};
         ++k;
         at_w += (uint32_t)e.max;
     }
@@ -210,7 +216,7 @@ int read_many(PinnedStage &stage, hipStream_t stream, rcf_t *const *hs, size_t n
             CountedStream cs;
             if ((counts[i] = counted_stream(e.c, kind, &cs)) == RCF_OK) {
                 e.s = RingStream{hs[m], cs.ring, 1u, 0u, 0, 0, cs.cursor};
-                e.counter = cs.counter; e.interp = cs.interp; e.decim = cs.decim;
+                e.counter = cs.counter; e.interp = cs.interp; e.decim = cs.decim; e.cap = cs.cap;
             }
         } else {
             counts[i] = chan_stream(hs[m], e.c, kind, &e.s);   // RCF_ESTATE: no such stream on this channel
@@ -235,6 +241,15 @@ static int64_t chan_read_one(rcf_t *h, int chan_id, int kind, float gain, void *
     std::lock_guard<std::mutex> g(h->mu);
     if (set_dev(h)) return RCF_EHIP;
     FIND_CHAN(h, chan_id, c);
+    if (kind_hard(kind)) {            // the slicer's streams: a counted entry (the device finds the end; the hit ring's own capacity)
+        CountedStream cs;
+        int64_t n = 0;
+        int rc = counted_stream(c, kind, &cs);
+        if (rc != RCF_OK) return rc;
+        ReadEntry e{RingStream{h, cs.ring, 1u, 0u, 0, 0, cs.cursor}, nullptr, 1.0f, out, (int64_t)max_items, &n, cs.counter, cs.interp, cs.decim, cs.cap};
+        rc = host_read(h->host_stage, h->stream, &h, 1, &e, 1);
+        return rc != RCF_OK ? rc : n;
+    }
     RingStream s;
     const int rc = chan_stream(h, c, kind, &s);
     return rc != RCF_OK ? rc : read_one(h, s, gain, out, max_items);
@@ -248,6 +263,8 @@ int64_t rcf_chan_read_clock(rcf_t *h, int chan_id, float *out, size_t n) { retur
 int64_t rcf_chan_read_costas(rcf_t *h, int chan_id, float *out, size_t n) { return chan_read_one(h, chan_id, kReadCostas, 1.0f, out, n); }
 int64_t rcf_chan_read_fsk4(rcf_t *h, int chan_id, float *out, size_t n) { return chan_read_one(h, chan_id, kReadFsk4, 1.0f, out, n); }
 int64_t rcf_chan_read_audio(rcf_t *h, int chan_id, float *out, size_t n) { return chan_read_one(h, chan_id, kReadAudio, 1.0f, out, n); }
+int64_t rcf_chan_read_hard(rcf_t *h, int chan_id, uint32_t *out, size_t n) { return chan_read_one(h, chan_id, kHardBits, 1.0f, out, n); }
+int64_t rcf_chan_read_sync(rcf_t *h, int chan_id, uint32_t *out, size_t n) { return chan_read_one(h, chan_id, kHardSync, 1.0f, out, n); }
 
 int rcf_chan_read_many(rcf_t *h, int what, const int *chan_ids, int n_chans, float gain, void *out, size_t cap_each,
                        int64_t *counts)
@@ -285,5 +302,16 @@ int rcf_chan_agc_ring(rcf_t *h, int chan_id, void **agc_ring, size_t *capacity) 
 int rcf_chan_clock_ring(rcf_t *h, int chan_id, void **sym_ring, size_t *capacity) { return chan_rings(h, chan_id, kReadClock, true, sym_ring, nullptr, capacity); }
 int rcf_chan_costas_ring(rcf_t *h, int chan_id, void **sym_ring, size_t *capacity) { return chan_rings(h, chan_id, kReadCostas, true, sym_ring, nullptr, capacity); }
 int rcf_chan_fsk4_ring(rcf_t *h, int chan_id, void **sym_ring, size_t *capacity) { return chan_rings(h, chan_id, kReadFsk4, true, sym_ring, nullptr, capacity); }
+int rcf_chan_slicer_rings(rcf_t *h, int chan_id, void **word_ring, size_t *word_capacity, void **hit_ring, size_t *hit_capacity)
+{
+    const int rc = chan_rings(h, chan_id, kHardBits, true, word_ring, nullptr, word_capacity);
+    if (rc != RCF_OK) return rc;
+    std::lock_guard<std::mutex> g(h->mu);
+    FIND_CHAN(h, chan_id, c);
+    if (!c->slicer) { set_error("channel %d has no slicer (rcf_chan_slicer)", chan_id); return RCF_ESTATE; }   // (closed in between)
+    if (hit_ring) *hit_ring = c->slicer->rec.hit_ring;
+    if (hit_capacity) *hit_capacity = c->slicer->hit_cap;
+    return RCF_OK;
+}
 
 }  // extern "C"

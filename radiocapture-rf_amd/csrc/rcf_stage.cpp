@@ -1,6 +1,6 @@
 // rcf_stage.cpp -- the optional stages behind a channel's rings (the records of Chan, rcf_state.h): the P25 symbol filter,
 // the feed-forward AGC, the SmartNet / EDACS symbol clock, the P25 CQPSK Gardner / Costas loop, the P25 C4FM symbol loop and
-// the analog voice chain.
+// the analog voice chain, and the slicer behind one of the loops.
 // Attach, off, and what they produced.
 // An attach function allocates into Fresh<> holders and builds the new record completely; only then is it swapped into
 // the channel and the old one released.  A HIP call that fails before that leaves the channel as it was.
@@ -12,6 +12,7 @@ namespace rcfx {
 
 void Chan::Sym::release(rcf_t *h) { bury(h, rec.sym_ring); bury(h, const_cast<float *>(rec.taps)); rec.sym_ring = nullptr; rec.taps = nullptr; }
 void Chan::Agc::release(rcf_t *h) { bury(h, rec.agc_ring); rec.agc_ring = nullptr; }
+void Chan::Slicer::release(rcf_t *h) { bury(h, rec.word_ring); rec = SliceLaunch{}; }     // one allocation
 void Chan::Audio::release(rcf_t *h) { bury(h, rec.st); bury(h, rec.a_ring); bury(h, const_cast<float *>(rec.lpf)); rec = AudioLaunch{}; }
 
 }  // namespace rcfx
@@ -23,6 +24,18 @@ template <class R> static int stage_off(rcf_t *h, std::unique_ptr<R> &stage)
 {
     if (stage) { drop_stage(h, stage); ++h->chans_epoch; }
     return RCF_OK;
+}
+
+// A slicer reads the ring and the counter of ONE loop: when that loop goes, or starts again with a fresh ring at symbol 0,
+// the slicer goes with it (rcf.h says so: the caller attaches it again behind the new loop)
+template <class R> static void detach_slicer_of(rcf_t *h, Chan *c)
+{
+    if (c->slicer && c->slicer->source == R::kWhat) drop_stage(h, c->slicer);
+}
+template <class R> static int loop_off(rcf_t *h, Chan *c, std::unique_ptr<R> &stage)
+{
+    detach_slicer_of<R>(h, c);
+    return stage_off(h, stage);
 }
 
 // the interpolator bank the symbol clocks, the Gardner / Costas loops and the C4FM loops share unless the caller brings one: built at first use
@@ -59,6 +72,7 @@ static int attach_loop(rcf_t *h, Chan *c, std::unique_ptr<R> &stage, std::unique
     k->rec.st = reinterpret_cast<typename R::State *>(k->ring() + state_at);
     k->rec.taps = interp_taps ? k->ring() + bank_at : h->d_mmse;
     k->from = c->pos.produced;
+    detach_slicer_of<R>(h, c);
     drop_stage(h, stage);
     stage = std::move(k);
     ++h->chans_epoch;
@@ -141,7 +155,7 @@ int rcf_chan_clock_mm(rcf_t *h, int chan_id, const rcf_clock_mm_params_t *p)
     std::lock_guard<std::mutex> g(h->mu);
     if (set_dev(h)) return RCF_EHIP;
     FIND_CHAN(h, chan_id, c);
-    if (!p) return stage_off(h, c->clock);
+    if (!p) return loop_off(h, c, c->clock);
     if ((size_t)kClockTaps * 2 > h->out_cap) { set_error("ring of %zu too small for the clock's %d-sample window", h->out_cap, kClockTaps); return RCF_ECAP; }
     std::unique_ptr<Chan::Clock> k(new Chan::Clock);
     ClockLaunch &r = k->rec;                                             // the constants as the kernel takes them, rounded to float once
@@ -176,7 +190,7 @@ int rcf_chan_costas(rcf_t *h, int chan_id, const rcf_costas_params_t *p)
     std::lock_guard<std::mutex> g(h->mu);
     if (set_dev(h)) return RCF_EHIP;
     FIND_CHAN(h, chan_id, c);
-    if (!p) return stage_off(h, c->costas);
+    if (!p) return loop_off(h, c, c->costas);
     if (!c->agc) { set_error("channel %d has no AGC for the Gardner / Costas stage to read", chan_id); return RCF_ESTATE; }
     if (h->out_cap < 64) { set_error("ring of %zu too small for the Gardner / Costas stage", h->out_cap); return RCF_ECAP; }
     std::unique_ptr<Chan::Costas> k(new Chan::Costas);
@@ -223,7 +237,7 @@ int rcf_chan_fsk4(rcf_t *h, int chan_id, const rcf_fsk4_params_t *p)
     std::lock_guard<std::mutex> g(h->mu);
     if (set_dev(h)) return RCF_EHIP;
     FIND_CHAN(h, chan_id, c);
-    if (!p) return stage_off(h, c->fsk4);
+    if (!p) return loop_off(h, c, c->fsk4);
     if (!c->sym) { set_error("channel %d has no symbol filter (rcf_chan_fm_filter) for the C4FM loop to read", chan_id); return RCF_ESTATE; }
     if (h->out_cap < 16) { set_error("ring of %zu too small for the C4FM loop", h->out_cap); return RCF_ECAP; }
     std::unique_ptr<Chan::Fsk4> k(new Chan::Fsk4);
@@ -249,6 +263,94 @@ int rcf_chan_fsk4_state(rcf_t *h, int chan_id, rcf_fsk4_state_t *out)
     if (rc != RCF_OK) return rc;
     out->n_symbols = st.n_out; out->n_slips = st.slips;
     out->clock = st.clock; out->spread = st.spread; out->fine = st.fine; out->coarse = st.coarse;
+    return RCF_OK;
+}
+
+// ---- hard decisions behind one of the three loops (slice.hip)
+int rcf_chan_slicer(rcf_t *h, int chan_id, const rcf_slicer_params_t *p)
+{
+    if (!h) return RCF_EINVAL;
+    int bps = 0, hit_cap = 256;
+    if (p) {
+        if (p->source != RCF_READ_CLOCK && p->source != RCF_READ_COSTAS && p->source != RCF_READ_FSK4) {
+            set_error("slicer: source %d is none of RCF_READ_CLOCK, RCF_READ_COSTAS, RCF_READ_FSK4", p->source);
+            return RCF_EINVAL;
+        }
+        if (p->mode != RCF_SLICE_BINARY && p->mode != RCF_SLICE_FSK4) { set_error("slicer: unknown mode %d", p->mode); return RCF_EINVAL; }
+        bps = p->mode == RCF_SLICE_BINARY ? 1 : 2;
+        if (bps == 2)
+            for (int i = 0; i < 4; ++i)
+                if (!std::isfinite(p->levels[i]) || (i && p->levels[i] < p->levels[i - 1])) {
+                    set_error("slicer: levels %g %g %g %g not finite or not non-decreasing", p->levels[0], p->levels[1], p->levels[2], p->levels[3]);
+                    return RCF_EINVAL;
+                }
+        if (p->sync_bits != 0 && (p->sync_bits < 8 || p->sync_bits > 64 || p->sync_bits % bps)) {
+            set_error("slicer: sync_bits %d is not 0 or 8 .. 64 and a multiple of %d", p->sync_bits, bps);
+            return RCF_EINVAL;
+        }
+        if (p->sync_max_errors < 0 || p->sync_max_errors > std::max(0, p->sync_bits - 1)) {
+            set_error("slicer: sync_max_errors %d outside 0 .. sync_bits - 1", p->sync_max_errors);
+            return RCF_EINVAL;
+        }
+        if (p->hit_capacity) hit_cap = p->hit_capacity;
+        if (hit_cap < 16 || hit_cap > (1 << 26) || (hit_cap & (hit_cap - 1))) {
+            set_error("slicer: hit_capacity %d is not a power of two 16 .. 2^26", p->hit_capacity);
+            return RCF_EINVAL;
+        }
+    }
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!p) return stage_off(h, c->slicer);
+    const float *soft = nullptr;
+    const void *counters = nullptr;
+    if (p->source == RCF_READ_CLOCK && c->clock) { soft = c->clock->ring(); counters = c->clock->counters(); }
+    if (p->source == RCF_READ_COSTAS && c->costas) { soft = c->costas->ring(); counters = c->costas->counters(); }
+    if (p->source == RCF_READ_FSK4 && c->fsk4) { soft = c->fsk4->ring(); counters = c->fsk4->counters(); }
+    if (!soft) { set_error("channel %d does not carry the loop (%d) the slicer is to read", chan_id, p->source); return RCF_ESTATE; }
+    if (h->out_cap < 64) { set_error("ring of %zu too small for the slicer", h->out_cap); return RCF_ECAP; }
+    std::unique_ptr<Chan::Slicer> k(new Chan::Slicer);
+    SliceLaunch &r = k->rec;
+    r.soft_ring = soft;
+    r.src_n_out = static_cast<const int64_t *>(counters);
+    // the stage's symbol 0: the loop's count as of everything queued (one round trip)
+    int rc = stage_state(h, r.src_n_out, &r.src0, sizeof(r.src0));
+    if (rc != RCF_OK) return rc;
+    r.bps = bps;
+    r.sync_word = p->sync_bits >= 64 ? p->sync_word : p->sync_word & ((1ull << p->sync_bits) - 1);
+    r.sync_bits = p->sync_bits; r.sync_max_errors = p->sync_max_errors;
+    for (int i = 0; i < 3; ++i) r.levels[i] = p->levels[i];
+    r.soft_mask = r.word_mask = (uint32_t)(h->out_cap - 1);
+    r.hit_mask = (uint32_t)hit_cap - 1;
+    k->source = p->source;
+    k->hit_cap = (uint32_t)hit_cap;
+    constexpr size_t kStateWords = 256 / sizeof(uint32_t);
+    static_assert(sizeof(SliceState) <= 256, "the state's slot");
+    const size_t state_at = h->out_cap, hits_at = state_at + kStateWords;          // in words (out_cap >= 64: the record's 64-bit fields are aligned)
+    Fresh<uint32_t> fresh;
+    RCF_HIP(fresh.alloc(hits_at + (size_t)hit_cap));
+    const SliceState st0{};
+    if (!hip_ok(hipMemcpy(fresh.p + state_at, &st0, sizeof(st0), hipMemcpyHostToDevice), "hipMemcpy(slicer state)")) return RCF_EHIP;
+    r.word_ring = fresh.take();
+    r.st = reinterpret_cast<SliceState *>(r.word_ring + state_at);
+    r.hit_ring = r.word_ring + hits_at;
+    drop_stage(h, c->slicer);
+    c->slicer = std::move(k);
+    ++h->chans_epoch;
+    return RCF_OK;
+}
+
+int rcf_chan_slicer_state(rcf_t *h, int chan_id, rcf_slicer_state_t *out)
+{
+    if (!h || !out) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!c->slicer) { set_error("channel %d has no slicer (rcf_chan_slicer)", chan_id); return RCF_ESTATE; }
+    SliceState st{};                    // (its three counters)
+    const int rc = stage_state(h, c->slicer->rec.st, &st, offsetof(SliceState, partial));
+    if (rc != RCF_OK) return rc;
+    out->n_symbols = st.n_symbols; out->n_words = st.n_words; out->n_hits = st.n_hits;
     return RCF_OK;
 }
 

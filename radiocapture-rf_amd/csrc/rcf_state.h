@@ -3,7 +3,7 @@
 //   rcf_handle.cpp   open / close / sync, pools, wideband ingest        rcf_plan.cpp    the per-block schedule (host)
 //   rcf_launch.cpp   the block's launches in dependency order           rcf_chan.cpp    channels: lifecycle, taps, queries
 //   rcf_stage.cpp    a channel's optional stages: symbol filter, AGC,   rcf_read.cpp    the stream table of a channel and the
-//                    symbol loops, voice chain (attach / off / counts)                  one read path of every host read
+//                    symbol loops, slicer, voice chain (attach / off)                    one read path of every host read
 //   rcf_bank.cpp     filterbank + scanner ABI                           rcf_timing.cpp  HIP-event timing
 //   rcf_comm.cpp     RCCL peak-list exchange                            rcf_group.cpp   grouped launches over front-ends
 #pragma once
@@ -138,13 +138,15 @@ struct Chan {
         }
         void release(rcf_t *h);
     };
+    // (kWhat: the loop's name in the ABI -- RCF_READ_CLOCK / COSTAS / FSK4 --, by which a slicer names its source)
     struct Clock : Loop<ClockState, ClockLaunch, &ClockLaunch::sym_ring> {   // clock_recovery_mm_ff over gain * fm (SmartNet / EDACS)
+        static constexpr int kWhat = RCF_READ_CLOCK;
         size_t reach() const { return (size_t)kClockTaps - 1; }         // a symbol's window starts up to 7 samples behind
     };
     // Gardner / Costas symbol recovery over the AGC ring (P25 CQPSK back half)
-    struct Costas : Loop<CostasState, CostasLaunch, &CostasLaunch::sym_ring> {};
+    struct Costas : Loop<CostasState, CostasLaunch, &CostasLaunch::sym_ring> { static constexpr int kWhat = RCF_READ_COSTAS; };
     // the C4FM symbol loop over the symbol-filter ring (P25 C4FM back half)
-    struct Fsk4 : Loop<Fsk4State, Fsk4Launch, &Fsk4Launch::out_ring> {};
+    struct Fsk4 : Loop<Fsk4State, Fsk4Launch, &Fsk4Launch::out_ring> { static constexpr int kWhat = RCF_READ_FSK4; };
     struct Audio {                      // the analog voice chain
         // owns st, the rings (one allocation from a_ring on: a | l | h | o | c (cf32), out_cap samples each) and the taps
         // (one allocation from lpf on: lpf | hpf | rs (padded))
@@ -159,13 +161,27 @@ struct Chan {
     std::unique_ptr<Clock> clock;
     std::unique_ptr<Costas> costas;
     std::unique_ptr<Fsk4> fsk4;
+    // Hard decisions behind ONE of the symbol loops (rcf_chan_slicer): packed words and sync hits.  One allocation, which
+    // starts at rec.word_ring: word ring of out_cap words | the state record, in a slot of 256 bytes | hit ring of hit_cap
+    // items.  A second call: new rings and state, cursors 0.  The stage has no `from`: it starts at a SYMBOL of its source
+    // (rec.src0), and goes when that loop goes or is attached again (rcf_stage.cpp)
+    struct Slicer {
+        SliceLaunch rec{};
+        int source = 0;                 // RCF_READ_CLOCK / COSTAS / FSK4
+        uint32_t hit_cap = 0;
+        int64_t rd_words = 0, rd_hits = 0;
+        size_t reach() const { return 0; }                               // it reads the loop's ring, never the channel's
+        void release(rcf_t *h);
+    };
     std::unique_ptr<Audio> audio;
+    std::unique_ptr<Slicer> slicer;
     // the one list of them: f(the stage's holder -- null when the channel has no such stage --, the bytes of its launch
     // record, whether its reach() is into rings of its own instead of the channel's)
     template <class F> void for_each_stage(F &&f)
     {
         f(sym, sizeof(FmFirLaunch), false); f(agc, sizeof(AgcLaunch), false); f(clock, sizeof(ClockLaunch), false);
         f(costas, sizeof(CostasLaunch), false); f(fsk4, sizeof(Fsk4Launch), false); f(audio, sizeof(AudioLaunch), true);
+        f(slicer, sizeof(SliceLaunch), false);
     }
     // ---- the rest
     float incr[2] = {1.f, 0.f};   // exact rotator: what GNU Radio iterates
@@ -178,7 +194,7 @@ struct Chan {
 #pragma GCC diagnostic push
 #pragma GCC diagnostic ignored "-Winvalid-offsetof"
 static_assert(offsetof(Chan, pos) + sizeof(Chan::Pos) <= 192, "what plan_channel advances: inside the first three cache lines");
-static_assert(offsetof(Chan, audio) + sizeof(std::unique_ptr<Chan::Audio>) <= 256, "what plan_channel reads: inside the four prefetched lines");
+static_assert(offsetof(Chan, slicer) + sizeof(std::unique_ptr<Chan::Slicer>) <= 256, "what plan_channel reads: inside the four prefetched lines");
 #pragma GCC diagnostic pop
 
 struct Pfb {
@@ -447,7 +463,7 @@ struct RingStream {
 // the stages' rows of the stream table.  These are table indices, not ABI values: the batched ABIs and the pump name the
 // same streams RCF_READ_SYM .. RCF_READ_AUDIO (16 .. 20), and stream_kind() maps `what` to the row (-1: no such stream;
 // 3 .. 15 stay refused)
-constexpr int kReadSym = 3, kReadClock = 4, kReadAudio = 5, kReadCostas = 6, kReadFsk4 = 7;
+constexpr int kReadSym = 3, kReadClock = 4, kReadAudio = 5, kReadCostas = 6, kReadFsk4 = 7, kHardBits = 8, kHardSync = 9;
 inline int stream_kind(int what)
 {
     switch (what) {
@@ -457,9 +473,13 @@ inline int stream_kind(int what)
         case RCF_READ_COSTAS: return kReadCostas;
         case RCF_READ_FSK4: return kReadFsk4;
         case RCF_READ_AUDIO: return kReadAudio;
+        case RCF_HARD_BITS: return kHardBits;
+        case RCF_HARD_SYNC: return kHardSync;
         default: return -1;
     }
 }
+// the slicer's two streams: uint32 items, never delivered by the pump, the hit ring with a capacity of its own
+inline bool kind_hard(int kind) { return kind == kHardBits || kind == kHardSync; }
 inline size_t stream_item_bytes(int kind) { return kind == RCF_READ_IQ || kind == RCF_READ_AGC ? sizeof(float2) : sizeof(float); }
 // A counted stream -- a symbol loop's or the voice chain's: its end is ceil(*counter * interp / decim) of a DEVICE counter.
 // chan_stream fetches it (a round trip); the batched readers and the pump hand the counter to the counted gather instead
@@ -470,15 +490,17 @@ struct CountedStream {
     uint32_t interp = 1, decim = 1;
     int64_t *cursor = nullptr;
     uint64_t serial = 0;
+    uint32_t cap = 0;                  // the ring's items when not the handle's out_cap (the slicer's hit ring); 0: out_cap
 };
-inline bool kind_counted(int kind) { return kind == kReadClock || kind == kReadCostas || kind == kReadFsk4 || kind == kReadAudio; }
+inline bool kind_counted(int kind) { return kind == kReadClock || kind == kReadCostas || kind == kReadFsk4 || kind == kReadAudio || kind_hard(kind); }
 int counted_stream(Chan *c, int kind, CountedStream *s);   // kind_counted(kind); RCF_ESTATE: the channel has no such stage
-// The stream table of a channel: c's stream `kind` (RCF_READ_IQ / FM / AGC, kReadSym / Clock / Audio / Costas / Fsk4), or RCF_ESTATE with
+// The stream table of a channel: c's stream `kind` (RCF_READ_IQ / FM / AGC, kReadSym / Clock / Audio / Costas / Fsk4, kHardBits / Sync), or RCF_ESTATE with
 // the refusal's message (IQ of a discriminator-only tap, a stage the channel does not carry).  The first four end at
 // c->produced.  The clock's, the voice chain's, the Gardner / Costas loop's and the C4FM loop's end at their stage's device counter: one
 // asynchronous copy and one synchronisation of the stream (RCF_EHIP); *aux, if given, takes the counter beside it (the
 // loops' slips, the samples that passed the voice chain's squelch).  That round trip is the single readers' and the
-// produced / state queries'; read_many and the pump use counted_stream instead.
+// produced / state queries'; read_many and the pump use counted_stream instead -- and so do the slicer's single readers: the
+// RingStream of kHardSync does not carry the hit ring's own capacity, a CountedStream does.
 int chan_stream(rcf_t *h, Chan *c, int kind, RingStream *s, int64_t *aux = nullptr);
 // the front `bytes` of a stage's device state record: one asynchronous copy behind everything queued, one synchronisation
 int stage_state(rcf_t *h, const void *d_state, void *st, size_t bytes);
@@ -512,6 +534,7 @@ struct ReadEntry {
     int64_t *count = nullptr;     // out: items read, or the entry's error code
     const int64_t *counter = nullptr;
     uint32_t interp = 1, decim = 1;
+    uint32_t cap = 0;             // counted: the ring's items, 0 = the handle's out_cap (CountedStream::cap)
 };
 // Every entry's new items in one gather launch (gather_rings; gather_counted for counted entries, which reserve
 // min(max, out_cap) items of staging each and learn their counts and cursors from the launch's result words) into `stage`

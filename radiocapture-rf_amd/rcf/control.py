@@ -5,26 +5,39 @@
                          -> binary_slicer_fb -> unpacked_to_packed_bb(1, MSB_FIRST)
 
 The discriminator and the Mueller and Mueller clock run per channel on the GPU (rcf_chan_clock_mm): a demod reads soft
-symbols at 3600 or 9600 per second (chan_read_clock), slices and packs them (pack_bits) and does the packet framing."""
+symbols at 3600 or 9600 per second (chan_read_clock), slices and packs them (pack_bits) and does the packet framing -- or,
+with hard=True, lets the GPU slice, pack and look for the frame sync (rcf_chan_slicer) and reads packed bits and the places
+frames begin (chan_read_hard, chan_read_sync)."""
 import numpy as np
+
+from . import native
 
 QUAD_GAIN = 5.0              # moto_control_demod.py:105, edacs_control_demod.py:84
 GAIN_OMEGA = 1.4395919       # moto_control_demod.py:113, edacs_control_demod.py:85 (the four constants below too)
 MU = 0.5
 GAIN_MU = 0.05
 OMEGA_RELATIVE_LIMIT = 0.005
+SMARTNET_SYNC, SMARTNET_SYNC_BITS = 0b10101100, 8      # moto_control_demod.py:216
+# edacs_control_demod.py:523; the inverted word stays the consumer's business
+EDACS_SYNC, EDACS_SYNC_BITS = 0b010101010101010101010111000100100101010101010101, 48
 
 
-def smartnet_clock(fe, cid, channel_rate=25000, symbol_rate=3600.0):
+def smartnet_clock(fe, cid, channel_rate=25000, symbol_rate=3600.0, hard=False):
     """clock_recovery_mm_ff(channel_rate / symbol_rate, ...) behind quadrature_demod_cf(5) on channel `cid` of Frontend
-    `fe` (moto_control_demod.py:103-113: channel_rate = 2 x 12500, symbol_rate = 3600.0 at :50)"""
+    `fe` (moto_control_demod.py:103-113: channel_rate = 2 x 12500, symbol_rate = 3600.0 at :50).  hard=True also attaches
+    the slicer behind the clock: binary, exact matches of the 8-bit frame sync."""
     fe.chan_clock_mm(cid, channel_rate / symbol_rate, GAIN_OMEGA, MU, GAIN_MU, OMEGA_RELATIVE_LIMIT, QUAD_GAIN)
+    if hard:
+        fe.chan_slicer(cid, native.READ_CLOCK, native.SLICE_BINARY, sync_word=SMARTNET_SYNC, sync_bits=SMARTNET_SYNC_BITS)
 
 
-def edacs_clock(fe, cid, receive_rate=25000, symbol_rate=9600.0):
+def edacs_clock(fe, cid, receive_rate=25000, symbol_rate=9600.0, hard=False):
     """the same behind an EDACS control channel (edacs_control_demod.py:76,85: receive_rate = 2 x 12500, symbol_rate
-    the system's, 9600 or 4800)"""
+    the system's, 9600 or 4800).  hard=True also attaches the slicer behind the clock: binary, exact matches of the
+    48-bit frame sync."""
     fe.chan_clock_mm(cid, receive_rate / symbol_rate, GAIN_OMEGA, MU, GAIN_MU, OMEGA_RELATIVE_LIMIT, QUAD_GAIN)
+    if hard:
+        fe.chan_slicer(cid, native.READ_CLOCK, native.SLICE_BINARY, sync_word=EDACS_SYNC, sync_bits=EDACS_SYNC_BITS)
 
 
 def pack_bits(soft, carry=None):

@@ -37,6 +37,7 @@ SYMBOLS = [
     "rcf_chan_clock_mm", "rcf_chan_clock_produced", "rcf_chan_read_clock", "rcf_chan_clock_ring", "rcf_design_mmse_interpolator",
     "rcf_chan_costas", "rcf_chan_costas_state", "rcf_chan_read_costas", "rcf_chan_costas_ring",
     "rcf_chan_fsk4", "rcf_chan_fsk4_state", "rcf_chan_read_fsk4", "rcf_chan_fsk4_ring",
+    "rcf_chan_slicer", "rcf_chan_slicer_state", "rcf_chan_read_hard", "rcf_chan_read_sync", "rcf_chan_slicer_rings",
     "rcf_design_firdes", "rcf_design_optfir_low_pass", "rcf_design_fm_deemph", "rcf_design_resampler", "rcf_chan_audio_open",
     "rcf_chan_audio_close", "rcf_chan_audio_produced", "rcf_chan_read_audio",
     "rcf_host_alloc", "rcf_host_free", "rcf_comm_unique_id", "rcf_comm_init", "rcf_comm_destroy", "rcf_comm_size",
@@ -50,7 +51,11 @@ READ_IQ, READ_FM, READ_AGC = 0, 1, 2
 # the streams of a channel's stages (RCF_READ_SYM .. RCF_READ_AUDIO): float32 rows of the batched readers and the pump
 READ_SYM, READ_CLOCK, READ_COSTAS, READ_FSK4, READ_AUDIO = 16, 17, 18, 19, 20
 _STAGE_WHAT = {"sym": READ_SYM, "clock": READ_CLOCK, "costas": READ_COSTAS, "fsk4": READ_FSK4, "audio": READ_AUDIO}
-T_FIR, T_PFB, T_FIR_DERIVED, T_DISC, T_SCAN_FFT, T_SCAN_MOVSUM, T_HISTORY, T_FIR_MFMA, T_AUDIO, T_TAPS, T_CLOCK, T_COSTAS, T_FSK4 = range(13)
+# the slicer's two streams (RCF_HARD_BITS, RCF_HARD_SYNC): uint32 rows of the batched readers; the pump does not deliver them
+HARD_BITS, HARD_SYNC = 32, 33
+_HARD_WHAT = {"hard": HARD_BITS, "sync": HARD_SYNC}
+SLICE_BINARY, SLICE_FSK4 = 1, 2
+T_FIR, T_PFB, T_FIR_DERIVED, T_DISC, T_SCAN_FFT, T_SCAN_MOVSUM, T_HISTORY, T_FIR_MFMA, T_AUDIO, T_TAPS, T_CLOCK, T_COSTAS, T_FSK4, T_SLICE = range(14)
 
 
 class AudioParams(C.Structure):
@@ -131,6 +136,27 @@ def fsk4_params_struct(sample_rate, symbol_rate, k_spread, k_timing, k_fine, k_c
     if taps is not None:
         p.interp_taps = taps.ctypes.data_as(C.POINTER(C.c_float))
     return p, taps
+
+
+class SlicerParams(C.Structure):
+    """rcf_slicer_params_t (include/rcf.h)"""
+    _fields_ = [("source", C.c_int), ("mode", C.c_int), ("levels", C.c_float * 4), ("sync_word", C.c_uint64),
+                ("sync_bits", C.c_int), ("sync_max_errors", C.c_int), ("hit_capacity", C.c_int), ("reserved_", C.c_int)]
+
+
+class SlicerState(C.Structure):
+    """rcf_slicer_state_t (include/rcf.h)"""
+    _fields_ = [("n_symbols", C.c_int64), ("n_words", C.c_int64), ("n_hits", C.c_int64)]
+
+
+def widen_hits(items, n_symbols):
+    """the hit ring's uint32 items -> (k as int64, dist as uint8): k is the largest value <= n_symbols - 1 with the item's low
+    26 bits (rcf.h at rcf_chan_slicer), n_symbols the stage's count when the items were read or later"""
+    items = np.asarray(items, dtype=np.uint32)
+    low = (items & np.uint32(0x3ffffff)).astype(np.int64)
+    last = int(n_symbols) - 1
+    k = low + ((last - low) >> 26 << 26)
+    return k, (items >> np.uint32(26)).astype(np.uint8)
 
 
 class PumpConfig(C.Structure):
@@ -215,6 +241,11 @@ def lib():
         "rcf_chan_fsk4_state": (C.c_int, [vp, C.c_int, C.POINTER(Fsk4State)]),
         "rcf_chan_read_fsk4": (i64, [vp, C.c_int, fp, sz]),
         "rcf_chan_fsk4_ring": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]),
+        "rcf_chan_slicer": (C.c_int, [vp, C.c_int, C.POINTER(SlicerParams)]),
+        "rcf_chan_slicer_state": (C.c_int, [vp, C.c_int, C.POINTER(SlicerState)]),
+        "rcf_chan_read_hard": (i64, [vp, C.c_int, C.POINTER(C.c_uint32), sz]),
+        "rcf_chan_read_sync": (i64, [vp, C.c_int, C.POINTER(C.c_uint32), sz]),
+        "rcf_chan_slicer_rings": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]),
         "rcf_design_mmse_interpolator": (C.c_int, [C.c_int, C.c_int, C.c_double, fp, C.c_int]),
         "rcf_chan_fm_level": (C.c_int, [vp, C.c_int, C.c_float, C.c_int, fp]),
         "rcf_design_firdes": (C.c_int, [C.c_int] + [C.c_double] * 4 + [C.c_int, C.c_double, fp, C.c_int]),
@@ -302,15 +333,20 @@ def lib():
 def _read_what(what, stages=False):
     """the batched readers' and the pump's `what`: "iq", "agc", anything else the discriminator (as it always was).
     stages=True -- how every reader of this module calls it -- also names the stages' streams: "sym", "clock", "costas",
-    "fsk4", "audio".  The one-argument form keeps its old answers ("sym" was never a stream there: the discriminator)."""
+    "fsk4", "audio", and the slicer's "hard" and "sync".  The one-argument form keeps its old answers ("sym" was never a
+    stream there: the discriminator)."""
     if stages and what in _STAGE_WHAT:
         return _STAGE_WHAT[what]
+    if stages and what in _HARD_WHAT:
+        return _HARD_WHAT[what]
     return READ_IQ if what == "iq" else READ_AGC if what == "agc" else READ_FM
 
 
 def _read_dtype(what):
-    """item type of stream `what` as the readers deliver it: cf32 for "iq" and "agc", float32 for everything else"""
-    return np.complex64 if _read_what(what, True) in (READ_IQ, READ_AGC) else np.float32
+    """item type of stream `what` as the readers deliver it: cf32 for "iq" and "agc", uint32 for the slicer's "hard" and
+    "sync", float32 for everything else"""
+    w = _read_what(what, True)
+    return np.complex64 if w in (READ_IQ, READ_AGC) else np.uint32 if w in (HARD_BITS, HARD_SYNC) else np.float32
 
 
 def _check(rc):
@@ -672,7 +708,8 @@ class Frontend:
         """new samples of many channels behind ONE device synchronisation (rcf_chan_read_many) -> list of arrays
         (views into `out`, a [len(cids), cap_each] complex64 / float32 array -- pass a PinnedArray's for overlapping
         copies), None where the channel no longer exists (or lacks the stream).  what: "iq", "fm" (x gain), "agc", or a
-        stage's stream -- "sym", "clock", "costas", "fsk4", "audio": float32, from where that stage's single reader stands"""
+        stage's stream -- "sym", "clock", "costas", "fsk4", "audio": float32, from where that stage's single reader stands --
+        or the slicer's "hard" (packed words) / "sync" (hit items, see widen_hits): uint32"""
         n = len(cids)
         dt = _read_dtype(what)
         if out is None:
@@ -808,6 +845,47 @@ class Frontend:
     def chan_read_fsk4(self, cid, max_symbols=1 << 20) -> np.ndarray:
         """unread soft symbols of the channel's C4FM loop (+-1, +-3 on a locked signal), oldest first"""
         return self._read_ring(lib().rcf_chan_read_fsk4, cid, max_symbols, np.float32)
+
+    def chan_slicer(self, cid, source, mode=None, levels=(-2.0, 0.0, 2.0, 4.0), sync_word=0, sync_bits=0, sync_max_errors=0,
+                    hit_capacity=0):
+        """hard decisions behind one of the channel's symbol loops (rcf_chan_slicer): source READ_CLOCK / READ_COSTAS /
+        READ_FSK4, mode SLICE_BINARY (binary_slicer_fb) or SLICE_FSK4 (op25 fsk4_slicer_fb(levels)); packed MSB first as
+        unpacked_to_packed_bb does, with a search for the low sync_bits bits of sync_word (hits: Hamming distance <=
+        sync_max_errors).  It starts at the loop's next symbol; source=None switches it off."""
+        if source is None:
+            _check(lib().rcf_chan_slicer(self._h, cid, None))
+            return
+        p = SlicerParams()
+        p.source, p.mode = int(source), int(mode)
+        p.levels = (C.c_float * 4)(*[float(v) for v in levels])
+        p.sync_word, p.sync_bits, p.sync_max_errors = int(sync_word), int(sync_bits), int(sync_max_errors)
+        p.hit_capacity = int(hit_capacity)
+        _check(lib().rcf_chan_slicer(self._h, cid, C.byref(p)))
+
+    def chan_slicer_state(self, cid) -> dict:
+        """n_symbols, n_words, n_hits of the slicer as of the last block (rcf_chan_slicer_state; syncs the stream)"""
+        st = SlicerState()
+        _check(lib().rcf_chan_slicer_state(self._h, cid, C.byref(st)))
+        return _state_dict(st)
+
+    def chan_read_hard(self, cid, max_words=1 << 18) -> np.ndarray:
+        """unread packed decisions as bytes, 4 per word: GNU Radio's unpacked_to_packed_bb(bps, MSB_FIRST) stream"""
+        out = np.empty(max_words, dtype=np.uint32)
+        n = _check(lib().rcf_chan_read_hard(self._h, cid, out.ctypes.data_as(C.POINTER(C.c_uint32)), max_words))
+        return out[:n].copy().view(np.uint8)
+
+    def chan_read_sync(self, cid, max_hits=1 << 16):
+        """unread sync hits -> (k as int64: the last symbol of the window, counted from the stage's start and widened
+        against the stage's symbol count; dist as uint8)"""
+        out = np.empty(max_hits, dtype=np.uint32)
+        n = _check(lib().rcf_chan_read_sync(self._h, cid, out.ctypes.data_as(C.POINTER(C.c_uint32)), max_hits))
+        return widen_hits(out[:n], self.chan_slicer_state(cid)["n_symbols"])
+
+    def chan_slicer_rings(self, cid):
+        """(word ring device pointer, its capacity, hit ring device pointer, its capacity) (rcf_chan_slicer_rings)"""
+        wp, wc, hp, hc = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t()
+        _check(lib().rcf_chan_slicer_rings(self._h, cid, C.byref(wp), C.byref(wc), C.byref(hp), C.byref(hc)))
+        return wp.value, wc.value, hp.value, hc.value
 
     def chan_fsk4_ring(self, cid):
         """(device pointer, capacity) of the stage's float32 soft-symbol ring (rcf_chan_fsk4_ring)"""

@@ -9,8 +9,10 @@ logging_receiver.py:231-332).  Both modulations start from the same pre-filter a
 Both chains run on the GPU up to the slicer (c4fm_demod, cqpsk_demod).  The two sequential op25 loops are the stages
 rcf_chan_fsk4 (fsk4_demod_ff) and rcf_chan_costas (gardner_costas_cc ... multiply_const_ff), which include/rcf.h defines
 from the published algorithms -- op25's source is not in the reference tree, so both stages are unpinned against op25 --,
-and a demod reads soft dibits at the symbol rate (chan_read_fsk4, chan_read_costas) and slices them (slice_dibits).  A
-consumer that runs op25's own loop reads the front half's output instead (chan_read_sym, chan_read_agc)."""
+and a demod reads soft dibits at the symbol rate (chan_read_fsk4, chan_read_costas) and slices them (slice_dibits) -- or,
+with hard=True, lets the GPU slice, pack and look for the frame sync (rcf_chan_slicer) and reads packed dibits and the
+places frames begin (chan_read_hard, chan_read_sync).  A consumer that runs op25's own loop reads the front half's output
+instead (chan_read_sym, chan_read_agc)."""
 import math
 
 import numpy as np
@@ -19,6 +21,16 @@ from . import native
 
 SYMBOL_RATE = 4800           # p25_control_demod.py:82 (phase 1; logging_receiver.py:286 runs phase 2 at 6000)
 SYMBOL_DEVIATION = 600.0     # p25_control_demod.py:116
+SLICER_LEVELS = (-2.0, 0.0, 2.0, 4.0)   # op25.fsk4_slicer_fb's argument (p25_control_demod.py:167)
+FRAME_SYNC = 0x5575F5FF77FF  # the 48-bit frame sync the consumer looks for (p25_control_demod.py:337)
+FRAME_SYNC_BITS = 48
+# Hamming distance up to which a window counts as a frame sync.  A default of this project: the reference itself compares
+# bytes exactly (buf.find), and op25's own threshold is not in the reference tree.
+FRAME_SYNC_MAX_ERRORS = 4
+
+
+def _hard(fe, cid, source):
+    fe.chan_slicer(cid, source, native.SLICE_FSK4, SLICER_LEVELS, FRAME_SYNC, FRAME_SYNC_BITS, FRAME_SYNC_MAX_ERRORS)
 
 
 def prefilter_taps(channel_rate):
@@ -61,12 +73,15 @@ def costas_params(channel_rate, symbol_rate=SYMBOL_RATE):
                 beta=0.125 * alpha * alpha, max_freq=2.0 * math.pi * 1200.0 / rate, omega_limit=0.005)
 
 
-def cqpsk_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE):
+def cqpsk_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False):
     """the whole CQPSK chain up to the slicer on channel `chan_id` of Frontend `fe`: the front half, then the Gardner /
     Costas stage (p25_control_demod.py:136-183).  Returns the pre-filter channel's id: chan_read_costas on it gives soft
-    dibits at symbol_rate (slice_dibits turns them into dibits), chan_costas_state its carrier estimate."""
+    dibits at symbol_rate (slice_dibits turns them into dibits), chan_costas_state its carrier estimate.  hard=True also
+    attaches the slicer behind the loop: chan_read_hard gives packed dibits, chan_read_sync where FRAME_SYNC ends."""
     cid = cqpsk_front_half(fe, chan_id, channel_rate)
     fe.chan_costas(cid, **costas_params(channel_rate, symbol_rate))
+    if hard:
+        _hard(fe, cid, native.READ_COSTAS)
     return cid
 
 
@@ -92,12 +107,15 @@ def fsk4_params(channel_rate, symbol_rate=SYMBOL_RATE):
                 k_coarse=0.00125, spread_min=1.6, spread_max=2.4)
 
 
-def c4fm_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE):
+def c4fm_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False):
     """the whole C4FM chain up to the slicer on channel `chan_id` of Frontend `fe`: the front half, then the symbol loop
     (p25_control_demod.py:118-135).  Returns the pre-filter channel's id: chan_read_fsk4 on it gives soft dibits at
-    symbol_rate (slice_dibits turns them into dibits), chan_fsk4_state its offset estimate (`coarse`)."""
+    symbol_rate (slice_dibits turns them into dibits), chan_fsk4_state its offset estimate (`coarse`).  hard=True also
+    attaches the slicer behind the loop: chan_read_hard gives packed dibits, chan_read_sync where FRAME_SYNC ends."""
     cid = c4fm_front_half(fe, chan_id, channel_rate, symbol_rate)
     fe.chan_fsk4(cid, **fsk4_params(channel_rate, symbol_rate))
+    if hard:
+        _hard(fe, cid, native.READ_FSK4)
     return cid
 
 
