@@ -45,6 +45,16 @@ int pfb_fm_upload_increments(rcf_t *h)
     return RCF_OK;
 }
 
+bool pfb_fm_stream(rcf_t *h, int bin, int64_t *cursor, bool pump, Stream *s)
+{
+    const Pfb &p = h->pfb;
+    if (!p.open || !p.d_fm || bin < 0 || bin >= p.NB) return false;
+    const int64_t end = p.fm_mode ? p.produced : p.fm_until;      // while the discriminator is off, readers stop where it was switched off
+    *s = Stream{h, p.d_fm + bin, 1u, (uint32_t)p.NB, (uint32_t)h->out_cap, cursor, end, pump ? end : p.produced};
+    if (pump && cursor) *cursor = std::max(*cursor, p.fm_from);   // (switched off and on again: the frames between were never demodulated)
+    return true;
+}
+
 }  // namespace rcfx
 
 using namespace rcfx;
@@ -158,7 +168,7 @@ int64_t rcf_pfb_read_bin(rcf_t *h, int bin, float *out, size_t max_samples)
     if (p.fm_mode == 2) { set_error("the bank writes its discriminator ring only (rcf_pfb_fm_enable mode 2): no bins to read"); return RCF_ESTATE; }
     // one bin out of the bank's ring (tiled or frame-major -- not a strided ring: gather_view_kernel, not host_read) into the
     // handle's pinned staging
-    const int64_t n = lag_clamp(h, &p.rd[bin], p.produced, p.produced, (int64_t)max_samples);
+    const int64_t n = lag_clamp((int64_t)h->out_cap, &p.rd[bin], p.produced, p.produced, (int64_t)max_samples);
     if (n == 0) return 0;
     SrcRange sr{};
     if (!source_range(h, RCF_SRC_PFB_BIN0 + bin, 0, 0, &sr)) return RCF_ESTATE;
@@ -260,11 +270,9 @@ int64_t rcf_pfb_read_fm(rcf_t *h, int bin, float gain, float *out, size_t max_sa
     if (set_dev(h)) return RCF_EHIP;
     Pfb &p = h->pfb;
     if (!p.open || !p.d_fm || bin < 0 || bin >= p.NB) { set_error("no discriminator ring / no such bin %d", bin); return RCF_EINVAL; }
-    // bin `bin` of the frame-major ring of floats: a stride of NB words.  While the discriminator is off, readers stop at the
-    // frame it was switched off at.
-    const int64_t end = p.fm_mode ? p.produced : p.fm_until;
-    return read_one(h, RingStream{h, p.d_fm + bin, 1u, (uint32_t)p.NB, end, p.produced, &p.rd_fm[(size_t)bin]}, gain, out,
-                    max_samples);
+    Stream s;
+    (void)pfb_fm_stream(h, bin, &p.rd_fm[(size_t)bin], false, &s);
+    return read_one(h, s, gain, out, max_samples);
 }
 
 int64_t rcf_pfb_fm_lost(rcf_t *h)

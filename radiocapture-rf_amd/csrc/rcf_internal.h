@@ -597,7 +597,7 @@ void launch_gather_rings(const GatherRec *d_recs, int n_recs, uint32_t *d_dst, u
 // ClockState / CostasState / Fsk4State) or the voice chain's audio (n_a of AudioState).  The kernel reads the stage's counter
 // itself (stable: the launch is queued behind the block's stage launches), applies the reader's lag clamp and copies
 //   end = ceil(*counter * interp / decim)            (interp == decim: the counter itself)
-//   cur = max(cursor, end - cap)                     (lag_clamp, rcf_state.h)
+//   cur = max(cursor, end - cap)                     (lag_clamp, rcf_streams.h)
 //   n   = min(end - cur, max_n), after the items a destination ring of dst_mask_w + 1 cannot hold were skipped
 //   dst[dst_w + ((pos + i) & dst_mask_w)] = ring[(cur + i) & (cap - 1)], i < n          (float32 items: words)
 // and one lane publishes result = {pos + n, cur + n}.  cursor and pos (the items the destination has taken so far) come

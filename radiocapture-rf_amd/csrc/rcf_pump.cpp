@@ -24,29 +24,30 @@ struct rcf_pump {
     std::vector<size_t> ring_blocks;
     std::vector<double> phase;
     std::vector<const volatile uint64_t *> written;
-    // subscription slots (guarded by g->mu): slot e delivers channel rd_chan[e] of member rd_member[e] (-1: free) as
-    // stream rd_kind[e] of the channel's stream table (stream_kind of the subscription's `what`; RCF_READ_FM x rd_gain[e]).
-    // Slots are fixed at start (cfg.n_read of them subscribed, room
-    // for max_read): rcf_pump_subscribe / rcf_pump_unsubscribe move channels in and out while the thread runs
-    std::vector<int> rd_member, rd_chan, rd_kind;
-    std::vector<float> rd_gain;
-    std::vector<std::vector<int>> entries_of;      // member -> indices into rd_*
-    std::vector<int64_t> bin_rd;                   // slots on a BIN of a member's fused discriminator ring (rd_chan >= RCF_SRC_PFB_BIN0): frames delivered
-    std::vector<int64_t> queued;                   // items ever queued for the host ring of each slot
-    // Counted slots (kind_counted: a symbol loop's soft symbols, the voice chain's audio).  How many items a gather takes
-    // only the device knows, and with two group blocks in flight the host cannot wait for it: the slot's cursor in the
-    // stage's stream and its item count live in d_cstate, {cursor, items} twice per slot -- a gather reads the copy
-    // c_par[e] and writes the other (CountedRec).  `queued` of such a slot is an UPPER bound: every gather adds the most
-    // it may take, and its completion puts the bound back on the true count its result words report.
+    // Subscription slots (guarded by g->mu), fixed at start (cfg.n_read of them subscribed, room for max_read):
+    // rcf_pump_subscribe / rcf_pump_unsubscribe move channels in and out while the thread runs.  A counted slot's cursor in
+    // the stage's stream and its item count live in d_cstate, {cursor, items} twice per slot -- a gather reads the copy
+    // `par` and writes the other (CountedRec; DESIGN.md, "Counted slots") --, and its `queued` is an UPPER bound: every
+    // gather adds the most it may take, and its completion puts the bound back on the true count its result words report.
+    struct Slot {
+        int member = -1;                           // -1: free
+        int chan = -1;                             // the member's channel, or RCF_SRC_PFB_BIN0 + a bin of its fused discriminator ring
+        int kind = kIq;                            // the stream delivered (row of kStreams; kFm x gain)
+        float gain = 1.0f;
+        Chan *c = nullptr;                         // the channel, resolved once per channel-set epoch (null: closed, or a bin)
+        int64_t bin_rd = 0;                        // a bin's slot: frames delivered
+        int64_t queued = 0;                        // items ever queued for the slot's host ring
+        bool par = false;                          // the copy of d_cstate the slot's next gather reads
+        bool fresh = true;                         // the next gather takes cursor and item count from the host: a new subscription
+        bool last_counted = false;                 // the slot's last tenant was counted (its count is the bound, not exact)
+        uint64_t serial = 0;                       // the attachment of the stage the device cursor belongs to (Stream::serial)
+        uint32_t gen = 0;                          // bumped by every subscription: gathers of an earlier tenant no longer count
+    };
+    std::vector<Slot> slots;
+    std::vector<std::vector<int>> entries_of;      // member -> its slots
+    std::vector<uint64_t> epoch_of;                // per member: the epoch Slot::c was resolved at (~0: resolve again)
     int64_t *d_cstate = nullptr;
-    std::vector<uint8_t> c_par;                    // the copy the slot's next gather reads
-    std::vector<uint8_t> c_fresh;                  // the next gather takes cursor and item count from the host: a new subscription
-    std::vector<uint8_t> c_last;                   // the slot's last tenant was counted (its count is the bound, not exact)
-    std::vector<uint64_t> c_serial;                // the attachment of the stage the device cursor belongs to (Chan::Loop::serial)
-    std::vector<uint32_t> c_gen;                   // bumped by every subscription: gathers of an earlier tenant no longer count
     unsigned char *h_crecs = nullptr, *h_crecs_dev = nullptr;   // pinned, per in-flight block: CountedRec[recs_cap] | result words[recs_cap][2]
-    std::vector<Chan *> chan_of;                   // subscribed channels, resolved once per channel-set epoch
-    std::vector<uint64_t> epoch_of;                // per member: the epoch chan_of was resolved at (~0: resolve again)
     size_t out_cap = 0;                            // host ring length per slot (items, power of two)
     static constexpr size_t kSlotItemBytes = 8;    // every slot is out_cap x 8 bytes (a discriminator slot uses half)
     unsigned char *h_out = nullptr, *h_out_dev = nullptr;   // the slots' rings
@@ -71,7 +72,30 @@ struct rcf_pump {
     int64_t nivcsw = 0;
     std::chrono::steady_clock::time_point t_start, t_end;
     char err_text[256] = "";
-    size_t item_bytes(int e) const { return stream_item_bytes(rd_kind[(size_t)e]); }
+    size_t item_bytes(int e) const { return kStreams[slots[(size_t)e].kind].item_w * 4u; }
+    // Slot e takes a new tenant.  Its counters go on from where the previous tenant left them: the new stream starts at
+    // `queued`.  Gathers still in flight for a COUNTED previous tenant no longer count (gen): the new stream starts at the
+    // bound they stay below, and the slot's item count jumps there
+    void occupy(int e, int member, int chan, int kind, float gain_, int64_t bin_rd_ = 0)
+    {
+        Slot &t = slots[(size_t)e];
+        t.member = member; t.chan = chan; t.kind = kind; t.gain = gain_; t.bin_rd = bin_rd_;
+        ++t.gen;
+        if (t.last_counted) out_written[(size_t)e].store(t.queued, std::memory_order_release);
+        t.last_counted = kStreams[kind].counted;
+        t.fresh = true;
+        t.c = nullptr;
+        entries_of[(size_t)member].push_back(e);
+        epoch_of[(size_t)member] = ~0ull;          // resolved at the member's next block
+    }
+    void vacate(int e)
+    {
+        Slot &t = slots[(size_t)e];
+        auto &v = entries_of[(size_t)t.member];
+        v.erase(std::remove(v.begin(), v.end(), e), v.end());
+        t.member = t.chan = -1;
+        t.c = nullptr;
+    }
     size_t crecs_bytes() const { return recs_cap * (sizeof(CountedRec) + 2 * sizeof(int64_t)); }   // of one in-flight block
     ~rcf_pump()
     {
@@ -117,10 +141,135 @@ long thread_nivcsw()
     return getrusage(RUSAGE_THREAD, &ru) == 0 ? ru.ru_nivcsw : 0;
 }
 
+// pinned host memory and the address the device sees it at; false, with the error text: none to be had
+bool pinned_alloc(size_t bytes, unsigned char **h, unsigned char **dev, const char *what)
+{
+    void *hp = nullptr, *dv = nullptr;
+    if (hipHostMalloc(&hp, bytes, hipHostMallocDefault) != hipSuccess || hipHostGetDevicePointer(&dv, hp, 0) != hipSuccess) {
+        if (hp) (void)hipHostFree(hp);
+        (void)hipGetLastError();
+        set_error("pinned %s of %zu bytes failed", what, bytes);
+        return false;
+    }
+    *h = static_cast<unsigned char *>(hp);
+    *dev = static_cast<unsigned char *>(dv);
+    return true;
+}
+
 void pump_fail(rcf_pump *p, int code)
 {
     p->error.store(code);
     std::snprintf(p->err_text, sizeof p->err_text, "%s", rcf_last_error());
+}
+
+// ---- the read of a group block: every subscribed channel of its members, straight into the host rings.  The caller
+// holds g->mu and the members' locks.
+constexpr uint32_t kSlotW = (uint32_t)(rcf_pump::kSlotItemBytes / 4);   // words per item a slot is laid out for
+
+struct Gather {
+    rcf_pump *p;
+    int block;                         // which of the two in flight
+    InFlight &s;
+    GatherRec *recs;                   // the block's records (pinned), and the counted ones as the host and the device see them
+    CountedRec *crecs;
+    unsigned char *crecs_dev;
+    int n_recs = 0, n_crecs = 0;
+    uint32_t max_w = 0, max_c = 0;
+    void plain(int e, const Stream &st);
+    void counted(int e, const Stream &st);
+    int launch();                      // both gathers, and the event the block's completion waits for
+};
+
+// channels were opened / closed on member m: look its slots' channels up again
+void resolve_member(rcf_pump *p, int m, rcf_t *h)
+{
+    for (int e : p->entries_of[(size_t)m]) {
+        rcf_pump::Slot &t = p->slots[(size_t)e];
+        if (t.chan >= RCF_SRC_PFB_BIN0) continue;
+        auto f = h->chans.find(t.chan);
+        t.c = f == h->chans.end() ? nullptr : f->second.get();
+    }
+    p->epoch_of[(size_t)m] = h->chans_epoch;
+}
+
+// what the slot delivers, or false: it starves (no such bin, a channel closed under the pump, a stream or stage it lacks)
+bool slot_stream(rcf_pump::Slot &t, rcf_t *h, Stream *st)
+{
+    if (t.chan >= RCF_SRC_PFB_BIN0) return pfb_fm_stream(h, t.chan - RCF_SRC_PFB_BIN0, &t.bin_rd, true, st);
+    return t.c && chan_stream(h, t.c, t.kind, st) == RCF_OK;
+}
+
+void Gather::plain(int e, const Stream &st)
+{
+    rcf_pump::Slot &t = p->slots[(size_t)e];
+    const int64_t n = ring_room(st.cursor, lag_clamp((int64_t)st.cap, st.cursor, st.newest, st.end, INT64_MAX), (int64_t)p->out_cap);
+    if (n == 0) return;
+    const uint32_t ew = st.item_w;                         // words per item of this slot's stream
+    const uint64_t dst_pos = (uint64_t)t.queued & (p->out_cap - 1);
+    t.queued += n;
+    // (published BEFORE the launch: a reader that copied positions this gather overwrites finds out)
+    p->out_queued[(size_t)e].store(t.queued, std::memory_order_release);
+    recs[n_recs++] = gather_rec(st, n, (uint32_t)((size_t)e * p->out_cap * kSlotW), (uint32_t)(dst_pos * ew),
+                                (uint32_t)(p->out_cap * ew - 1), t.kind == kFm ? t.gain : 1.0f);
+    max_w = std::max<uint32_t>(max_w, (uint32_t)n * ew);
+    *st.cursor += n;
+    s.delivered.push_back({e, n});
+}
+
+void Gather::counted(int e, const Stream &st)
+{
+    rcf_pump::Slot &t = p->slots[(size_t)e];
+    // a new subscription starts at the channel's own reader and at the slot's item count; a stage attached again (the host
+    // did it, under the member's lock) at symbol 0 of the new ring
+    const bool fresh = t.fresh, again = !fresh && t.serial != st.serial;
+    t.fresh = false;
+    t.serial = st.serial;
+    // the most this gather may take (the kernel holds it to that; a rest waits for the next block): steady state, what the
+    // block made; a first gather, whatever the ring holds
+    const int64_t n_k = std::max<int64_t>(0, t.c->pos.blk_after - t.c->pos.blk_before);
+    const int64_t bound = std::min<int64_t>(fresh || again ? (int64_t)st.cap : steady_bound(n_k, st.interp, st.decim), (int64_t)p->out_cap);
+    int64_t *cs = p->d_cstate + (size_t)e * 4;
+    const int par = t.par;
+    t.par = !t.par;
+    crecs[n_crecs] = CountedRec{static_cast<const uint32_t *>(st.ring), st.counter, cs + 2 * par, cs + 2 * (par ^ 1),
+                                reinterpret_cast<int64_t *>(crecs_dev + p->recs_cap * sizeof(CountedRec)) + 2 * n_crecs,
+                                fresh ? *st.cursor : 0, t.queued, st.interp, st.decim, st.cap,
+                                (uint32_t)bound, (uint32_t)((size_t)e * p->out_cap * kSlotW), (uint32_t)(p->out_cap - 1),
+                                fresh ? 3u : again ? 1u : 0u, 0u};
+    s.counted.push_back({e, t.gen, bound, n_crecs++});
+    max_c = std::max<uint32_t>(max_c, (uint32_t)bound);
+    t.queued += bound;
+    // (published BEFORE the launch, like a plain slot's: covers all this gather may write)
+    p->out_queued[(size_t)e].store(t.queued, std::memory_order_release);
+}
+
+int Gather::launch()
+{
+    uint32_t *out = reinterpret_cast<uint32_t *>(p->h_out_dev);
+    launch_gather_rings(reinterpret_cast<const GatherRec *>(p->h_recs_dev + (size_t)block * p->recs_cap * sizeof(GatherRec)), n_recs, out, max_w, p->g->stream);
+    launch_gather_counted(reinterpret_cast<const CountedRec *>(crecs_dev), n_crecs, out, max_c, p->g->stream);
+    if (hipEventRecord(p->slot_ev[block], p->g->stream) != hipSuccess) { set_error("pump: event record failed"); return RCF_EHIP; }
+    return RCF_OK;
+}
+
+// What the counted gathers of the finished block `s` took: each slot's true item count from its result words; the bound
+// goes back on it, plus what the other block in flight may still take (under g->mu).  Returns the items delivered
+int64_t rebase_counted(rcf_pump *p, const InFlight &s, const InFlight &other, const int64_t *res)
+{
+    int64_t items_out = 0;
+    for (const InFlight::Counted &c : s.counted) {
+        const size_t e = (size_t)c.entry;
+        rcf_pump::Slot &t = p->slots[e];
+        if (c.gen != t.gen) continue;                                 // the slot has a new tenant, whose stream began above this
+        const int64_t now_at = res[2 * c.rec];
+        int64_t ahead = 0;
+        if (other.busy) for (const InFlight::Counted &o : other.counted) if (o.entry == c.entry && o.gen == c.gen) ahead += o.bound;
+        items_out += now_at - p->out_written[e].load(std::memory_order_relaxed);
+        p->out_written[e].store(now_at, std::memory_order_release);
+        t.queued = now_at + ahead;
+        p->out_queued[e].store(t.queued, std::memory_order_release);
+    }
+    return items_out;
 }
 
 void pump_main(rcf_pump *p)
@@ -152,10 +301,6 @@ void pump_main(rcf_pump *p)
     InFlight slots[2];
     int head = 0, in_flight = 0;                   // slots[head] is the oldest busy one
     std::vector<GroupItem> items;
-    auto &queued = p->queued;
-    auto &chan_of = p->chan_of;
-    auto &epoch_of = p->epoch_of;
-    constexpr uint32_t slot_w = (uint32_t)(rcf_pump::kSlotItemBytes / 4);   // words per item a slot is laid out for
 
     auto complete_oldest = [&](bool block) -> bool {
         InFlight &s = slots[head];
@@ -170,22 +315,8 @@ void pump_main(rcf_pump *p)
         int64_t items_out = 0;
         for (auto &d : s.delivered) { p->out_written[(size_t)d.first].fetch_add(d.second, std::memory_order_release); items_out += d.second; }
         if (!s.counted.empty()) {
-            // what the counted gathers took: the slot's true item count from its result words; the bound goes back on it,
-            // plus what the other block in flight may still take (under the lock that guards `queued`)
             std::lock_guard<std::mutex> gl(g->mu);
-            const int64_t *res = reinterpret_cast<const int64_t *>(p->h_crecs + (size_t)head * p->crecs_bytes() + p->recs_cap * sizeof(CountedRec));
-            const InFlight &other = slots[head ^ 1];
-            for (const InFlight::Counted &c : s.counted) {
-                const size_t e = (size_t)c.entry;
-                if (c.gen != p->c_gen[e]) continue;                           // the slot has a new tenant, whose stream began above this
-                const int64_t now_at = res[2 * c.rec];
-                int64_t ahead = 0;
-                if (other.busy) for (const InFlight::Counted &o : other.counted) if (o.entry == c.entry && o.gen == c.gen) ahead += o.bound;
-                items_out += now_at - p->out_written[e].load(std::memory_order_relaxed);
-                p->out_written[e].store(now_at, std::memory_order_release);
-                queued[e] = now_at + ahead;
-                p->out_queued[e].store(queued[e], std::memory_order_release);
-            }
+            items_out += rebase_counted(p, s, slots[head ^ 1], reinterpret_cast<const int64_t *>(p->h_crecs + (size_t)head * p->crecs_bytes() + p->recs_cap * sizeof(CountedRec)));
         }
         {
             std::lock_guard<std::mutex> l(p->st_mu);
@@ -269,94 +400,18 @@ void pump_main(rcf_pump *p)
                 MemberLocks ml(g->members);
                 rc = group_process(g, items, cfg.fmt, cfg.scale, cfg.offset, false);
                 if (rc == RCF_OK) {
-                    // the read of this batch: every subscribed channel of its members, straight into the host rings
-                    GatherRec *recs = reinterpret_cast<GatherRec *>(p->h_recs + (size_t)slot * p->recs_cap * sizeof(GatherRec));
-                    CountedRec *crecs = reinterpret_cast<CountedRec *>(p->h_crecs + (size_t)slot * p->crecs_bytes());
-                    unsigned char *crecs_dev = p->h_crecs_dev + (size_t)slot * p->crecs_bytes();
-                    int n_recs = 0, n_crecs = 0;
-                    uint32_t max_w = 0, max_c = 0;
+                    Gather ga{p, slot, s, reinterpret_cast<GatherRec *>(p->h_recs + (size_t)slot * p->recs_cap * sizeof(GatherRec)),
+                              reinterpret_cast<CountedRec *>(p->h_crecs + (size_t)slot * p->crecs_bytes()), p->h_crecs_dev + (size_t)slot * p->crecs_bytes()};
                     for (const GroupItem &it : items) {
                         rcf_t *h = g->members[(size_t)it.m];
-                        if (epoch_of[(size_t)it.m] != h->chans_epoch) {            // channels were opened / closed: look them up again
-                            for (int e : p->entries_of[(size_t)it.m]) {
-                                if (p->rd_chan[(size_t)e] >= RCF_SRC_PFB_BIN0) continue;
-                                auto f = h->chans.find(p->rd_chan[(size_t)e]);
-                                chan_of[(size_t)e] = f == h->chans.end() ? nullptr : f->second.get();
-                            }
-                            epoch_of[(size_t)it.m] = h->chans_epoch;
-                        }
+                        if (p->epoch_of[(size_t)it.m] != h->chans_epoch) resolve_member(p, it.m, h);
                         for (int e : p->entries_of[(size_t)it.m]) {
-                            RingStream rs;
-                            if (p->rd_chan[(size_t)e] >= RCF_SRC_PFB_BIN0) {
-                                // one bin of the bank's fused discriminator ring (rcf_pfb_fm_enable): frame-major floats,
-                                // read with a stride of n_bins words
-                                Pfb &pf = h->pfb;
-                                const int bin = p->rd_chan[(size_t)e] - RCF_SRC_PFB_BIN0;
-                                if (!pf.open || !pf.d_fm || bin >= pf.NB) continue;
-                                const int64_t end = pf.fm_mode ? pf.produced : pf.fm_until;
-                                int64_t &cur = p->bin_rd[(size_t)e];
-                                cur = std::max(cur, pf.fm_from);          // (switched off and on again: the frames between were never demodulated)
-                                rs = RingStream{h, pf.d_fm + bin, 1u, (uint32_t)pf.NB, end, end, &cur};
-                            } else {
-                                Chan *c = chan_of[(size_t)e];
-                                if (!c) continue;                                  // closed under the pump: starves
-                                const int kind = p->rd_kind[(size_t)e];
-                                if (kind_counted(kind)) {
-                                    CountedStream cs;
-                                    if (counted_stream(c, kind, &cs) != RCF_OK) continue;      // the stage is off: starves
-                                    // a new subscription starts at the channel's own reader and at the slot's item count; a stage
-                                    // attached again (the host did it, under the member's lock) at symbol 0 of the new ring
-                                    const bool fresh = p->c_fresh[(size_t)e] != 0, again = !fresh && p->c_serial[(size_t)e] != cs.serial;
-                                    p->c_fresh[(size_t)e] = 0;
-                                    p->c_serial[(size_t)e] = cs.serial;
-                                    // the most this gather may take (the kernel holds it to that; a rest waits for the next
-                                    // block): steady state, what the block made -- at most one symbol per stage input,
-                                    // ceil(n_k interp / decim) + 1 audio samples; a first gather, whatever the ring holds
-                                    const int64_t n_k = std::max<int64_t>(0, c->pos.blk_after - c->pos.blk_before);
-                                    int64_t bound = kind == kReadAudio ? (n_k * cs.interp + cs.decim - 1) / cs.decim + 1 : n_k + 1;
-                                    if (fresh || again) bound = (int64_t)h->out_cap;
-                                    bound = std::min<int64_t>(bound, (int64_t)p->out_cap);
-                                    int64_t *st = p->d_cstate + (size_t)e * 4;
-                                    const int par = p->c_par[(size_t)e];
-                                    p->c_par[(size_t)e] ^= 1;
-                                    crecs[n_crecs] = CountedRec{static_cast<const uint32_t *>(cs.ring), cs.counter, st + 2 * par, st + 2 * (par ^ 1),
-                                                                reinterpret_cast<int64_t *>(crecs_dev + p->recs_cap * sizeof(CountedRec)) + 2 * n_crecs,
-                                                                fresh ? *cs.cursor : 0, queued[(size_t)e], cs.interp, cs.decim, (uint32_t)h->out_cap,
-                                                                (uint32_t)bound, (uint32_t)((size_t)e * p->out_cap * slot_w), (uint32_t)(p->out_cap - 1),
-                                                                fresh ? 3u : again ? 1u : 0u, 0u};
-                                    s.counted.push_back({e, p->c_gen[(size_t)e], bound, n_crecs});
-                                    ++n_crecs;
-                                    max_c = std::max<uint32_t>(max_c, (uint32_t)bound);
-                                    queued[(size_t)e] += bound;
-                                    // (published BEFORE the launch, like a plain slot's: covers all this gather may write)
-                                    p->out_queued[(size_t)e].store(queued[(size_t)e], std::memory_order_release);
-                                    continue;
-                                }
-                                if (chan_stream(h, c, kind, &rs) != RCF_OK) continue;   // (IQ of a discriminator-only tap, a channel without that stage)
-                            }
-                            int64_t n = lag_clamp(h, rs.cursor, rs.newest, rs.end, INT64_MAX);
-                            if (n == 0) continue;
-                            if ((size_t)n > p->out_cap) { *rs.cursor += n - (int64_t)p->out_cap; n = (int64_t)p->out_cap; }
-                            const uint32_t ew = rs.item_w;                         // words per item of this slot's stream
-                            const uint64_t dst_pos = (uint64_t)queued[(size_t)e] & (p->out_cap - 1);
-                            queued[(size_t)e] += n;
-                            // (published BEFORE the launch: a reader that copied positions this gather overwrites finds out)
-                            p->out_queued[(size_t)e].store(queued[(size_t)e], std::memory_order_release);
-                            recs[n_recs++] = gather_rec(rs, n, (uint32_t)((size_t)e * p->out_cap * slot_w), (uint32_t)(dst_pos * ew),
-                                                        (uint32_t)(p->out_cap * ew - 1),
-                                                        p->rd_kind[(size_t)e] == RCF_READ_FM ? p->rd_gain[(size_t)e] : 1.0f);
-                            max_w = std::max<uint32_t>(max_w, (uint32_t)n * ew);
-                            *rs.cursor += n;
-                            s.delivered.push_back({e, n});
+                            Stream st;
+                            if (!slot_stream(p->slots[(size_t)e], h, &st)) continue;
+                            if (st.counter) ga.counted(e, st); else ga.plain(e, st);
                         }
                     }
-                    if (n_recs)
-                        launch_gather_rings(reinterpret_cast<const GatherRec *>(p->h_recs_dev + (size_t)slot * p->recs_cap * sizeof(GatherRec)),
-                                            n_recs, reinterpret_cast<uint32_t *>(p->h_out_dev), max_w, g->stream);
-                    if (n_crecs)
-                        launch_gather_counted(reinterpret_cast<const CountedRec *>(crecs_dev), n_crecs, reinterpret_cast<uint32_t *>(p->h_out_dev),
-                                              max_c, g->stream);
-                    if (hipEventRecord(p->slot_ev[slot], g->stream) != hipSuccess) { set_error("pump: event record failed"); rc = RCF_EHIP; }
+                    rc = ga.launch();
                 }
             }
             if (rc != RCF_OK) { pump_fail(p, rc); break; }
@@ -431,7 +486,7 @@ int rcf_pump_start(rcf_group_t *g, const rcf_pump_config_t *cfg, rcf_pump_t **ou
 {
     if (!g || !cfg || !out || cfg->block_samples == 0 || !(cfg->samp_rate > 0) || !cfg->rings || !cfg->ring_blocks ||
         cfg->n_read < 0 || (cfg->n_read && (!cfg->read_members || !cfg->read_chans)) ||
-        stream_kind(cfg->what) < 0 || kind_hard(stream_kind(cfg->what)) || group_sample_bytes(cfg->fmt) == 0) {   // (the slicer's streams: not delivered)
+        stream_kind(cfg->what) < 0 || !kStreams[stream_kind(cfg->what)].pumped || group_sample_bytes(cfg->fmt) == 0) {
         set_error("bad pump configuration");
         return RCF_EINVAL;
     }
@@ -455,64 +510,23 @@ int rcf_pump_start(rcf_group_t *g, const rcf_pump_config_t *cfg, rcf_pump_t **ou
     }
     const int n_slots = std::max(std::max(cfg->n_read, cfg->max_read), 1);
     p->entries_of.resize(G);
-    p->rd_member.assign((size_t)n_slots, -1);
-    p->rd_chan.assign((size_t)n_slots, -1);
-    p->rd_kind.assign((size_t)n_slots, stream_kind(cfg->what));
-    p->c_par.assign((size_t)n_slots, 0);
-    p->c_fresh.assign((size_t)n_slots, 1);
-    p->c_last.assign((size_t)n_slots, 0);
-    p->c_serial.assign((size_t)n_slots, 0);
-    p->c_gen.assign((size_t)n_slots, 0);
-    p->rd_gain.assign((size_t)n_slots, cfg->gain);
-    p->queued.assign((size_t)n_slots, 0);
-    p->bin_rd.assign((size_t)n_slots, 0);
-    p->chan_of.assign((size_t)n_slots, nullptr);
+    p->slots.resize((size_t)n_slots);
     p->epoch_of.assign(G, ~0ull);
-    for (int e = 0; e < cfg->n_read; ++e) {
+    for (int e = 0; e < cfg->n_read; ++e)
         if (cfg->read_members[e] < 0 || cfg->read_members[e] >= (int)G) { set_error("subscribed channel %d: no such member", e); return RCF_EINVAL; }
-        p->rd_member[(size_t)e] = cfg->read_members[e];
-        p->rd_chan[(size_t)e] = cfg->read_chans[e];
-        p->entries_of[(size_t)cfg->read_members[e]].push_back(e);
-        p->c_last[(size_t)e] = cfg->read_chans[e] < RCF_SRC_PFB_BIN0 && kind_counted(p->rd_kind[(size_t)e]) ? 1 : 0;
-    }
     // the configuration's arrays belong to the caller: from here on the pump's own copies are used
     p->cfg.rings = nullptr; p->cfg.ring_blocks = nullptr; p->cfg.phase_s = nullptr; p->cfg.written = nullptr;
     p->cfg.read_members = nullptr; p->cfg.read_chans = nullptr;
     p->out_cap = pow2_at_least(cfg->out_ring_samples ? cfg->out_ring_samples : 4096);
     const size_t out_bytes = std::max<size_t>(64, (size_t)n_slots * p->out_cap * rcf_pump::kSlotItemBytes);
     if ((uint64_t)out_bytes / 4 > 0xffffffffull) { set_error("host rings of %zu bytes exceed the 32-bit word range", out_bytes); return RCF_ECAP; }
-    void *hp = nullptr, *dv = nullptr;
-    if (hipHostMalloc(&hp, out_bytes, hipHostMallocDefault) != hipSuccess || hipHostGetDevicePointer(&dv, hp, 0) != hipSuccess) {
-        if (hp) (void)hipHostFree(hp);
-        (void)hipGetLastError();
-        set_error("pinned host rings of %zu bytes failed", out_bytes);
-        return RCF_ENOMEM;
-    }
-    p->h_out = static_cast<unsigned char *>(hp);
-    p->h_out_dev = static_cast<unsigned char *>(dv);
+    if (!pinned_alloc(out_bytes, &p->h_out, &p->h_out_dev, "host rings")) return RCF_ENOMEM;
     p->out_written.reset(new std::atomic<int64_t>[(size_t)n_slots]);
     p->out_queued.reset(new std::atomic<int64_t>[(size_t)n_slots]);
     for (int e = 0; e < n_slots; ++e) { p->out_written[(size_t)e].store(0); p->out_queued[(size_t)e].store(0); }
     p->recs_cap = (size_t)n_slots;
-    hp = dv = nullptr;
-    if (hipHostMalloc(&hp, 2 * p->recs_cap * sizeof(GatherRec), hipHostMallocDefault) != hipSuccess ||
-        hipHostGetDevicePointer(&dv, hp, 0) != hipSuccess) {
-        if (hp) (void)hipHostFree(hp);
-        (void)hipGetLastError();
-        set_error("pinned gather records failed");
-        return RCF_ENOMEM;                            // (~rcf_pump releases the rings)
-    }
-    p->h_recs = static_cast<unsigned char *>(hp);
-    p->h_recs_dev = static_cast<unsigned char *>(dv);
-    hp = dv = nullptr;
-    if (hipHostMalloc(&hp, 2 * p->crecs_bytes(), hipHostMallocDefault) != hipSuccess || hipHostGetDevicePointer(&dv, hp, 0) != hipSuccess) {
-        if (hp) (void)hipHostFree(hp);
-        (void)hipGetLastError();
-        set_error("pinned counted-gather records failed");
-        return RCF_ENOMEM;
-    }
-    p->h_crecs = static_cast<unsigned char *>(hp);
-    p->h_crecs_dev = static_cast<unsigned char *>(dv);
+    if (!pinned_alloc(2 * p->recs_cap * sizeof(GatherRec), &p->h_recs, &p->h_recs_dev, "gather records") ||      // (~rcf_pump releases
+        !pinned_alloc(2 * p->crecs_bytes(), &p->h_crecs, &p->h_crecs_dev, "counted-gather records")) return RCF_ENOMEM;   // what there is)
     RCF_HIP(hipMalloc(&p->d_cstate, (size_t)n_slots * 4 * sizeof(int64_t)));
     RCF_HIP(hipMemset(p->d_cstate, 0, (size_t)n_slots * 4 * sizeof(int64_t)));
     for (int i = 0; i < 2; ++i) RCF_HIP(hipEventCreateWithFlags(&p->slot_ev[i], hipEventDisableTiming));
@@ -525,22 +539,23 @@ int rcf_pump_start(rcf_group_t *g, const rcf_pump_config_t *cfg, rcf_pump_t **ou
         if (!g->arenas.h[0] && g->arenas.cap < all) { size_t c_ = g->arenas.cap; while (c_ < all) c_ *= 2; g->arenas.cap = c_; }
         if (g->arenas.reserve(all, g->stream) != RCF_OK) return RCF_EHIP;
     }
-    // the subscribed channels' readers start at what has been produced so far
+    // the configured subscriptions; their readers start at what has been produced so far
     {
         MemberLocks ml(g->members);
         for (int e = 0; e < cfg->n_read; ++e) {
-            rcf_t *h = g->members[(size_t)p->rd_member[(size_t)e]];
-            if (p->rd_chan[(size_t)e] >= RCF_SRC_PFB_BIN0) {              // a bin of the fused discriminator ring
-                p->rd_kind[(size_t)e] = RCF_READ_FM;
-                p->bin_rd[(size_t)e] = h->pfb.produced;
-                continue;
-            }
-            auto f = h->chans.find(p->rd_chan[(size_t)e]);
+            const int m = cfg->read_members[e], chan = cfg->read_chans[e];
+            rcf_t *h = g->members[(size_t)m];
+            if (chan >= RCF_SRC_PFB_BIN0) { p->occupy(e, m, chan, kFm, cfg->gain, h->pfb.produced); continue; }   // a bin of the fused discriminator ring
+            p->occupy(e, m, chan, stream_kind(cfg->what), cfg->gain);
+            auto f = h->chans.find(chan);
             if (f == h->chans.end()) continue;
-            RingStream rs;
+            Stream st;
+            int64_t two[2];
+            if (chan_stream(h, f->second.get(), p->slots[(size_t)e].kind, &st) != RCF_OK) continue;
             // (a counted stream's end is fetched from the device here -- the one place the pump may wait for the stream; the
             // slot's first gather takes the cursor from there)
-            if (chan_stream(h, f->second.get(), p->rd_kind[(size_t)e], &rs) == RCF_OK) *rs.cursor = rs.end;
+            if (!st.counter) *st.cursor = st.end;
+            else if (stream_count(h, st, &st.end, two) == RCF_OK) *st.cursor = st.end;
         }
     }
     p->running.store(true);
@@ -599,7 +614,7 @@ int rcf_pump_stats(rcf_pump_t *p, rcf_pump_stats_t *st)
 
 int64_t rcf_pump_written(rcf_pump_t *p, int entry)
 {
-    if (!p || entry < 0 || entry >= (int)p->rd_member.size()) return RCF_EINVAL;
+    if (!p || entry < 0 || entry >= (int)p->slots.size()) return RCF_EINVAL;
     return p->out_written[(size_t)entry].load(std::memory_order_acquire);
 }
 
@@ -634,7 +649,7 @@ static int64_t pump_read_slot(rcf_pump *p, int entry, int64_t *cursor, unsigned 
 
 int64_t rcf_pump_read(rcf_pump_t *p, int entry, int64_t *cursor, void *out, size_t max_items)
 {
-    if (!p || !cursor || !out || entry < 0 || entry >= (int)p->rd_member.size()) { set_error("bad pump read arguments"); return RCF_EINVAL; }
+    if (!p || !cursor || !out || entry < 0 || entry >= (int)p->slots.size()) { set_error("bad pump read arguments"); return RCF_EINVAL; }
     return pump_read_slot(p, entry, cursor, static_cast<unsigned char *>(out), max_items);
 }
 
@@ -642,7 +657,7 @@ int rcf_pump_read_many(rcf_pump_t *p, const int *entries, int64_t *cursors, int 
 {
     if (!p || n < 0 || (n && (!entries || !cursors || !out || !counts))) { set_error("bad pump read arguments"); return RCF_EINVAL; }
     for (int i = 0; i < n; ++i) {
-        if (entries[i] < 0 || entries[i] >= (int)p->rd_member.size()) { counts[i] = -1; continue; }
+        if (entries[i] < 0 || entries[i] >= (int)p->slots.size()) { counts[i] = -1; continue; }
         counts[i] = pump_read_slot(p, entries[i], &cursors[i], static_cast<unsigned char *>(out) + (size_t)i * cap_each * rcf_pump::kSlotItemBytes, cap_each);
     }
     return RCF_OK;
@@ -650,14 +665,15 @@ int rcf_pump_read_many(rcf_pump_t *p, const int *entries, int64_t *cursors, int 
 
 int rcf_pump_subscribe(rcf_pump_t *p, int member, int chan_id, int what, float gain, int64_t *cursor)
 {
-    if (!p || stream_kind(what) < 0 || kind_hard(stream_kind(what))) { set_error("bad subscription"); return RCF_EINVAL; }
+    if (!p || stream_kind(what) < 0 || !kStreams[stream_kind(what)].pumped) { set_error("bad subscription"); return RCF_EINVAL; }
     rcf_group *g = p->g;
     std::lock_guard<std::mutex> gl(g->mu);
     if (member < 0 || member >= (int)g->members.size()) { set_error("no such member %d", member); return RCF_EINVAL; }
     int e = -1;
-    for (size_t i = 0; i < p->rd_member.size(); ++i) if (p->rd_member[i] < 0) { e = (int)i; break; }
-    if (e < 0) { set_error("all %zu subscription slots of the pump are taken (rcf_pump_config_t.max_read)", p->rd_member.size()); return RCF_ECAP; }
+    for (size_t i = 0; i < p->slots.size(); ++i) if (p->slots[i].member < 0) { e = (int)i; break; }
+    if (e < 0) { set_error("all %zu subscription slots of the pump are taken (rcf_pump_config_t.max_read)", p->slots.size()); return RCF_ECAP; }
     rcf_t *h = g->members[(size_t)member];
+    int64_t bin_start = 0;
     {
         // (the channel's own reader position is left where it is: a channel nobody has read yet is delivered from its
         // first output on -- what rcf_chan_read_iq would have handed out -- as far as its device ring still holds it)
@@ -665,32 +681,21 @@ int rcf_pump_subscribe(rcf_pump_t *p, int member, int chan_id, int what, float g
         if (chan_id >= RCF_SRC_PFB_BIN0) {
             // a bin of the member's fused discriminator ring (rcf_pfb_fm_enable): delivered from the bank's next frame on
             const int bin = chan_id - RCF_SRC_PFB_BIN0;
-            if (what != RCF_READ_FM || !h->pfb.open || !h->pfb.d_fm || bin >= h->pfb.NB) {
+            Stream st;
+            if (what != RCF_READ_FM || !pfb_fm_stream(h, bin, nullptr, true, &st)) {
                 set_error("member %d has no fused discriminator ring with a bin %d (rcf_pfb_fm_enable; what = RCF_READ_FM)", member, bin);
                 return RCF_EINVAL;
             }
-            p->bin_rd[(size_t)e] = h->pfb.fm_mode ? h->pfb.produced : h->pfb.fm_until;
+            bin_start = st.end;
         } else if (h->chans.find(chan_id) == h->chans.end()) {
             set_error("no such channel %d on member %d", chan_id, member);
             return RCF_EINVAL;
         }
     }
-    p->rd_member[(size_t)e] = member;
-    p->rd_chan[(size_t)e] = chan_id;
-    p->rd_kind[(size_t)e] = stream_kind(what);
-    p->rd_gain[(size_t)e] = gain;
-    // gathers still in flight for a COUNTED previous tenant no longer count (c_gen): the new stream starts at the bound they
-    // stay below, and the slot's item count jumps there
-    ++p->c_gen[(size_t)e];
-    if (p->c_last[(size_t)e]) p->out_written[(size_t)e].store(p->queued[(size_t)e], std::memory_order_release);
-    p->c_last[(size_t)e] = kind_counted(p->rd_kind[(size_t)e]) ? 1 : 0;
-    p->c_fresh[(size_t)e] = 1;
-    p->chan_of[(size_t)e] = nullptr;
-    p->entries_of[(size_t)member].push_back(e);
-    p->epoch_of[(size_t)member] = ~0ull;               // resolved at the member's next block
-    // the slot's counters go on from where its previous tenant left them: the new stream starts at `queued`, which the
-    // reader's cursor is set to (the gathers still in flight for the previous tenant end below it)
-    if (cursor) *cursor = p->queued[(size_t)e];
+    p->occupy(e, member, chan_id, stream_kind(what), gain, bin_start);
+    // the new stream starts at `queued`, which the reader's cursor is set to (the gathers still in flight for the previous
+    // tenant end below it)
+    if (cursor) *cursor = p->slots[(size_t)e].queued;
     return e;
 }
 
@@ -699,12 +704,8 @@ int rcf_pump_unsubscribe(rcf_pump_t *p, int entry)
     if (!p) return RCF_EINVAL;
     rcf_group *g = p->g;
     std::lock_guard<std::mutex> gl(g->mu);
-    if (entry < 0 || entry >= (int)p->rd_member.size() || p->rd_member[(size_t)entry] < 0) { set_error("no such subscription %d", entry); return RCF_EINVAL; }
-    auto &v = p->entries_of[(size_t)p->rd_member[(size_t)entry]];
-    v.erase(std::remove(v.begin(), v.end(), entry), v.end());
-    p->rd_member[(size_t)entry] = -1;
-    p->rd_chan[(size_t)entry] = -1;
-    p->chan_of[(size_t)entry] = nullptr;
+    if (entry < 0 || entry >= (int)p->slots.size() || p->slots[(size_t)entry].member < 0) { set_error("no such subscription %d", entry); return RCF_EINVAL; }
+    p->vacate(entry);
     return RCF_OK;
 }
 

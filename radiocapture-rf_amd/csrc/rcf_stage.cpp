@@ -417,20 +417,23 @@ int rcf_chan_audio_close(rcf_t *h, int chan_id)
     return RCF_OK;
 }
 
-// what a stage has produced so far: the end of its stream and the counter beside it (chan_stream)
-static int stage_produced(rcf_t *h, int chan_id, int kind, int64_t *n, int64_t *beside)
+// what a stage has produced so far: the end of its stream, and beside it word `word` of its counters (stream_count): the
+// clock's slips stand behind its symbol count; the samples that passed the voice chain's squelch ARE its counter
+static int stage_produced(rcf_t *h, int chan_id, int kind, int64_t *n, int64_t *beside, int word)
 {
     if (!h || !n) return RCF_EINVAL;
     std::lock_guard<std::mutex> g(h->mu);
     if (set_dev(h)) return RCF_EHIP;
     FIND_CHAN(h, chan_id, c);
-    RingStream s;
-    const int rc = chan_stream(h, c, kind, &s, beside);
-    if (rc == RCF_OK) *n = s.end;
-    return rc;
+    Stream s;
+    int64_t two[2];
+    int rc = chan_stream(h, c, kind, &s);
+    if (rc != RCF_OK || (rc = stream_count(h, s, n, two)) != RCF_OK) return rc;
+    if (beside) *beside = two[word];
+    return RCF_OK;
 }
 
-int rcf_chan_clock_produced(rcf_t *h, int chan_id, int64_t *n_symbols, int64_t *n_slips) { return stage_produced(h, chan_id, kReadClock, n_symbols, n_slips); }
-int rcf_chan_audio_produced(rcf_t *h, int chan_id, int64_t *n_audio, int64_t *n_ungated) { return stage_produced(h, chan_id, kReadAudio, n_audio, n_ungated); }
+int rcf_chan_clock_produced(rcf_t *h, int chan_id, int64_t *n_symbols, int64_t *n_slips) { return stage_produced(h, chan_id, kClock, n_symbols, n_slips, 1); }
+int rcf_chan_audio_produced(rcf_t *h, int chan_id, int64_t *n_audio, int64_t *n_ungated) { return stage_produced(h, chan_id, kAudio, n_audio, n_ungated, 0); }
 
 }  // extern "C"

@@ -2,8 +2,9 @@
 // filterbank, scanner, slab pools and launch arenas, and the helpers the host modules share.
 //   rcf_handle.cpp   open / close / sync, pools, wideband ingest        rcf_plan.cpp    the per-block schedule (host)
 //   rcf_launch.cpp   the block's launches in dependency order           rcf_chan.cpp    channels: lifecycle, taps, queries
-//   rcf_stage.cpp    a channel's optional stages: symbol filter, AGC,   rcf_read.cpp    the stream table of a channel and the
-//                    symbol loops, slicer, voice chain (attach / off)                    one read path of every host read
+//   rcf_stage.cpp    a channel's optional stages: symbol filter, AGC,   rcf_read.cpp    a channel's streams (one descriptor, Stream)
+//                    symbol loops, slicer, voice chain (attach / off)                    and the one read path of every host read
+//   rcf_streams.h    the stream table and the readers' integer rules (no HIP: g++ alone compiles it)
 //   rcf_bank.cpp     filterbank + scanner ABI                           rcf_timing.cpp  HIP-event timing
 //   rcf_comm.cpp     RCCL peak-list exchange                            rcf_group.cpp   grouped launches over front-ends
 #pragma once
@@ -22,6 +23,7 @@
 #include <vector>
 
 #include "rcf_internal.h"
+#include "rcf_streams.h"
 
 namespace rcfx {
 
@@ -450,108 +452,73 @@ template <class R> void drop_stage(rcf_t *h, std::unique_ptr<R> &r) { if (r) { r
 template <class S, class R, float *R::*Ring> void Chan::Loop<S, R, Ring>::release(rcf_t *h) { bury(h, ring()); ring() = nullptr; rec.st = nullptr; rec.taps = nullptr; }   // one allocation
 
 // ---------------------------------------------------------------- rcf_read.cpp
-// ---- the one read path.  A stream is a device ring of h->out_cap items (a power of two) of item_w 4-byte words:
-// item i at word (i & ring_mask) * stride_w of ring when stride_w > 1 (one bin of a frame-major ring of floats), else at
-// (i & ring_mask) * item_w.  The ring holds the out_cap items before `newest`; a reader at *cursor may take up to `end`.
-struct RingStream {
+// ---- the one read path.  A stream is a device ring of `cap` items (a power of two) of item_w 4-byte words: item i at word
+// (i & (cap - 1)) * stride_w of ring when stride_w > 1 (one bin of a frame-major ring of floats), else at
+// (i & (cap - 1)) * item_w.  A plain stream's end the host knows: the ring holds the cap items before `newest`, a reader at
+// *cursor may take up to `end`.  A counted stream -- counter != nullptr: a symbol loop's, the voice chain's, the slicer's --
+// ends at ceil(*counter * interp / decim) of a DEVICE counter, which the counted gather reads itself (CountedRec,
+// rcf_internal.h); serial: which attachment of the stage this is (a re-attached stage starts a new stream)
+struct Stream {
     rcf_t *h = nullptr;
     const void *ring = nullptr;
     uint32_t item_w = 1, stride_w = 0;
-    int64_t end = 0, newest = 0;
+    uint32_t cap = 0;                  // the handle's out_cap, or the ring's own (the slicer's hit ring)
     int64_t *cursor = nullptr;
-};
-// the stages' rows of the stream table.  These are table indices, not ABI values: the batched ABIs and the pump name the
-// same streams RCF_READ_SYM .. RCF_READ_AUDIO (16 .. 20), and stream_kind() maps `what` to the row (-1: no such stream;
-// 3 .. 15 stay refused)
-constexpr int kReadSym = 3, kReadClock = 4, kReadAudio = 5, kReadCostas = 6, kReadFsk4 = 7, kHardBits = 8, kHardSync = 9;
-inline int stream_kind(int what)
-{
-    switch (what) {
-        case RCF_READ_IQ: case RCF_READ_FM: case RCF_READ_AGC: return what;
-        case RCF_READ_SYM: return kReadSym;
-        case RCF_READ_CLOCK: return kReadClock;
-        case RCF_READ_COSTAS: return kReadCostas;
-        case RCF_READ_FSK4: return kReadFsk4;
-        case RCF_READ_AUDIO: return kReadAudio;
-        case RCF_HARD_BITS: return kHardBits;
-        case RCF_HARD_SYNC: return kHardSync;
-        default: return -1;
-    }
-}
-// the slicer's two streams: uint32 items, never delivered by the pump, the hit ring with a capacity of its own
-inline bool kind_hard(int kind) { return kind == kHardBits || kind == kHardSync; }
-inline size_t stream_item_bytes(int kind) { return kind == RCF_READ_IQ || kind == RCF_READ_AGC ? sizeof(float2) : sizeof(float); }
-// A counted stream -- a symbol loop's or the voice chain's: its end is ceil(*counter * interp / decim) of a DEVICE counter.
-// chan_stream fetches it (a round trip); the batched readers and the pump hand the counter to the counted gather instead
-// (CountedRec, rcf_internal.h).  serial: which attachment of the stage this is (a re-attached stage starts a new stream)
-struct CountedStream {
-    const void *ring = nullptr;
-    const int64_t *counter = nullptr;
+    int64_t end = 0, newest = 0;       // plain
+    const int64_t *counter = nullptr;  // counted
     uint32_t interp = 1, decim = 1;
-    int64_t *cursor = nullptr;
     uint64_t serial = 0;
-    uint32_t cap = 0;                  // the ring's items when not the handle's out_cap (the slicer's hit ring); 0: out_cap
 };
-inline bool kind_counted(int kind) { return kind == kReadClock || kind == kReadCostas || kind == kReadFsk4 || kind == kReadAudio || kind_hard(kind); }
-int counted_stream(Chan *c, int kind, CountedStream *s);   // kind_counted(kind); RCF_ESTATE: the channel has no such stage
-// The stream table of a channel: c's stream `kind` (RCF_READ_IQ / FM / AGC, kReadSym / Clock / Audio / Costas / Fsk4, kHardBits / Sync), or RCF_ESTATE with
-// the refusal's message (IQ of a discriminator-only tap, a stage the channel does not carry).  The first four end at
-// c->produced.  The clock's, the voice chain's, the Gardner / Costas loop's and the C4FM loop's end at their stage's device counter: one
-// asynchronous copy and one synchronisation of the stream (RCF_EHIP); *aux, if given, takes the counter beside it (the
-// loops' slips, the samples that passed the voice chain's squelch).  That round trip is the single readers' and the
-// produced / state queries'; read_many and the pump use counted_stream instead -- and so do the slicer's single readers: the
-// RingStream of kHardSync does not carry the hit ring's own capacity, a CountedStream does.
-int chan_stream(rcf_t *h, Chan *c, int kind, RingStream *s, int64_t *aux = nullptr);
+// The channel's side of the stream table (rcf_streams.h): c's stream `kind`, or RCF_ESTATE with the row's refusal (IQ of a
+// discriminator-only tap, a stage the channel does not carry).  Never touches the device.
+int chan_stream(rcf_t *h, Chan *c, int kind, Stream *s);
 // the front `bytes` of a stage's device state record: one asynchronous copy behind everything queued, one synchronisation
 int stage_state(rcf_t *h, const void *d_state, void *st, size_t bytes);
-
-// A reader that has fallen more than a ring behind lost what the ring overwrote: its cursor is raised to the oldest item
-// the ring still holds.  Returns how many items [*cursor, end) it may take, at most max.
-inline int64_t lag_clamp(const rcf_t *h, int64_t *cursor, int64_t produced, int64_t end, int64_t max)
-{
-    *cursor = std::max(*cursor, produced - (int64_t)h->out_cap);
-    return std::max<int64_t>(0, std::min(end - *cursor, max));
-}
+// The round trip of a counted stream: its end as of everything queued, and in two[] the counter and the word behind it
+// (the loops' {n_out, slips}, the voice chain's {n_a, n_prev}).  The produced / state queries' and rcf_pump_start's; no
+// read needs it
+int stream_count(rcf_t *h, const Stream &s, int64_t *end, int64_t two[2]);
 
 // the gather record of the n items of s from *s.cursor on into the destination described by dst_* (GatherRec); float items
 // leave multiplied by gain unless it is 1
-inline GatherRec gather_rec(const RingStream &s, int64_t n, uint32_t dst_w, uint32_t dst_pos_w, uint32_t dst_mask_w, float gain)
+inline GatherRec gather_rec(const Stream &s, int64_t n, uint32_t dst_w, uint32_t dst_pos_w, uint32_t dst_mask_w, float gain)
 {
-    return GatherRec{static_cast<const uint32_t *>(s.ring), (uint32_t)(((uint64_t)*s.cursor & s.h->ring_mask) * s.item_w),
-                     (uint32_t)n * s.item_w, (uint32_t)(s.h->out_cap * s.item_w - 1), dst_w, dst_pos_w, dst_mask_w, gain,
+    return GatherRec{static_cast<const uint32_t *>(s.ring), (uint32_t)(((uint64_t)*s.cursor & (s.cap - 1u)) * s.item_w),
+                     (uint32_t)n * s.item_w, s.cap * s.item_w - 1u, dst_w, dst_pos_w, dst_mask_w, gain,
                      gain != 1.0f ? 1u : 0u, s.stride_w};
 }
 
 // one entry of a host read: a stream, the row its items go to and at most how many.  s.ring == nullptr: nothing to read
-// (*count holds the entry's error code already).  counter != nullptr: a counted stream (CountedStream) -- s carries its ring
-// and cursor, the device finds its end
+// (*count holds the entry's error code already)
 struct ReadEntry {
-    RingStream s;
+    Stream s;
     Chan *c = nullptr;            // batched reads: a channel listed twice in one call is refused (RCF_EINVAL)
     float gain = 1.0f;
     void *out = nullptr;
     int64_t max = 0;
     int64_t *count = nullptr;     // out: items read, or the entry's error code
-    const int64_t *counter = nullptr;
-    uint32_t interp = 1, decim = 1;
-    uint32_t cap = 0;             // counted: the ring's items, 0 = the handle's out_cap (CountedStream::cap)
 };
 // Every entry's new items in one gather launch (gather_rings; gather_counted for counted entries, which reserve
-// min(max, out_cap) items of staging each and learn their counts and cursors from the launch's result words) into `stage`
-// and one synchronisation of `stream`; then the rows are
-// copied out, the cursors advanced and the graveyards of the idle handles (those on `stream`) released.  RCF_ECAP when the
-// words do not fit the records' 32 bits, RCF_ENOMEM when the staging cannot be had.
+// min(max, cap) items of staging each and learn their counts and cursors from the launch's result words) into `stage`
+// and one synchronisation of `stream`; then the rows are copied out, the cursors advanced and the graveyards of the idle
+// handles (those on `stream`) released.  RCF_ECAP: the words do not fit the records' 32 bits; RCF_ENOMEM: no staging.
 int host_read(PinnedStage &stage, hipStream_t stream, rcf_t *const *idle, size_t n_idle, ReadEntry *es, size_t n);
 // a single reader: host_read of one entry on h's own stream and staging; the items read, or an error code
-int64_t read_one(rcf_t *h, const RingStream &s, float gain, void *out, size_t max_items);
+int64_t read_one(rcf_t *h, const Stream &s, float gain, void *out, size_t max_items);
 // rcf_chan_read_many (hs = the handle, ms = nullptr) and rcf_group_read_many (hs = the members): entry i is channel
-// chan_ids[i] of hs[ms[i]] as `what` (RCF_READ_IQ / FM x gain / AGC / SYM .. AUDIO; the caller has checked it with
-// stream_kind) into row i of out; counts[i] its items or its error
+// chan_ids[i] of hs[ms[i]] as `what` (the caller has checked it with stream_kind; RCF_READ_FM x gain) into row i of out;
+// counts[i] its items or its error
 int read_many(PinnedStage &stage, hipStream_t stream, rcf_t *const *hs, size_t n_hs, const int *ms, const int *chan_ids, int n,
               int what, float gain, void *out, size_t cap_each, int64_t *counts);
 
 // ---------------------------------------------------------------- rcf_bank.cpp
 void pfb_release(rcf_t *h);          // the bank's device buffers go once the stream has passed them; the bank is closed
+// Bin `bin` of the bank's fused discriminator ring (rcf_pfb_fm_enable) as a stream for a reader at *cursor: frame-major
+// floats, read with a stride of NB words; it ends at `produced`, or at the frame the discriminator was switched off at.
+// false: no such ring or bin.  The two readers differ, and each keeps its way: rcf_pfb_read_fm (pump = false) measures a
+// reader's lag from `produced` and relies on rcf_pfb_fm_enable to move rd_fm past frames that were never demodulated; the
+// pump (pump = true) measures it from the stream's end and raises its own cursor to fm_from
+bool pfb_fm_stream(rcf_t *h, int bin, int64_t *cursor, bool pump, Stream *s);
 
 // ---------------------------------------------------------------- rcf_plan.cpp / rcf_launch.cpp
 int process_block(rcf_t *h, size_t n);

@@ -319,6 +319,45 @@ def test_word_ring_of_64_wraps_with_reads_between_pushes(gpu_required):
         assert _code(nat, _slicer, nat, fe, c, "clock", nat.SLICE_BINARY) == nat.RCF_ECAP
 
 
+def test_word_ring_of_256_readers_left_behind_get_its_last_words(gpu_required):
+    """out_capacity 256 and more than 256 words before anybody reads: the batched and the single reader of the word stream
+    both return exactly the ring's last 256 words -- of the whole stream, which a third twin gives whose single reader
+    comes after every block and never lags -- and go on block by block from there"""
+    nat = gpu_required
+    blk, K, cap = 16 * 150, 160, 256                          # 150 channel samples a block: ~29 dibits, under two words
+    x = _noise(256, blk * (K + 2))
+
+    def open_():
+        fe = nat.Frontend(FS, device=0, block_capacity=blk, out_capacity=cap)
+        c = fe.chan_open(CR, OFF)
+        _loop(fe, c, "fsk4")
+        _slicer(nat, fe, c, "fsk4", nat.SLICE_FSK4)
+        return fe, c
+
+    (fe, c), (tw, c_t), (al, c_a) = open_(), open_(), open_()
+    whole = []
+    try:
+        at = 0
+        for phase, n in enumerate((K, 1, 1)):
+            before = len(whole)
+            for _ in range(n):
+                for f in (fe, tw, al):
+                    f.push(x[at:at + blk])
+                at += blk
+                whole.extend(al.chan_read_hard(c_a).view("<u4").tolist())
+            row = fe.chan_read_many([c], "hard", cap_each=2 * cap)[0]
+            one = tw.chan_read_hard(c_t).view("<u4")
+            assert al.chan_slicer_state(c_a)["n_words"] == len(whole)
+            want = np.array(whole[-cap:] if phase == 0 else whole[before:], np.uint32)
+            assert phase or len(whole) > cap + 16                 # more than a ring behind
+            assert np.array_equal(row, want), (phase, len(row), len(want))
+            assert np.array_equal(one, want), (phase, len(one), len(want))
+        assert len(whole) > before                                # the last block brought words
+    finally:
+        for f in (fe, tw, al):
+            f.close()
+
+
 @pytest.mark.parametrize("max_errors", [2, 4])
 def test_hit_ring_of_16_wraps_between_reads_and_the_oldest_go(gpu_required, max_errors):
     """sync_bits 8 on the bits of noise: at 2 errors a seventh of the symbols hit, at 4 two thirds -- more than the ring

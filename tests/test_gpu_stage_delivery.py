@@ -153,17 +153,24 @@ def test_small_cap_each_and_single_reads_interleaved(gpu_required, what):
                                                      ("costas", 1 << 8, 150, 14), ("clock", 1 << 8, 150, 14),
                                                      ("fsk4", 1 << 8, 150, 14)])
 def test_a_reader_left_behind_gets_what_the_single_reader_gets(gpu_required, what, cap, block, n_blocks):
+    """the batched and the single reader take the same path: a third twin, read after every block so that it never lags,
+    gives the whole stream, and what the neglected readers get is its last out_capacity items"""
     nat = gpu_required
     x = _signal(D * block * (n_blocks + 2), 13)
     kw = dict(n_chans=2, out_capacity=cap, block=block, audio=cap > 256, agc_n=64 if cap > 256 else 16)
     fe, ids = _open(nat, **kw)
     tw, ids_t = _open(nat, **kw)
+    al, ids_a = _open(nat, **kw)
+    whole = [[], []]
     at = 0
     for phase, n in enumerate((n_blocks, 1, 1)):               # neglect, then block by block again
         for _ in range(n):
             fe.push(x[at:at + D * block])
             tw.push(x[at:at + D * block])
+            al.push(x[at:at + D * block])
             at += D * block
+            for k in range(2):
+                whole[k].append(getattr(al, SINGLE[what])(ids_a[k]))
         if phase == 0:
             assert _produced(tw, ids_t[0], what) > cap         # more than a ring behind
         rows = fe.chan_read_many(ids, what, cap_each=2 * cap)
@@ -171,8 +178,14 @@ def test_a_reader_left_behind_gets_what_the_single_reader_gets(gpu_required, wha
             w = getattr(tw, SINGLE[what])(ids_t[k])
             _same(rows[k], w, (what, phase, k))
             assert len(w) <= cap and (phase or len(w) > cap // 2)
+            if phase == 0:
+                so_far = np.concatenate(whole[k])
+                assert len(so_far) == _produced(al, ids_a[k], what) > cap
+                _same(rows[k], so_far[-cap:], (what, "batched, the ring's last items", k))
+                _same(w, so_far[-cap:], (what, "single, the ring's last items", k))
     fe.close()
     tw.close()
+    al.close()
 
 
 @pytest.mark.parametrize("what", WHATS)
