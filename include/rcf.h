@@ -161,7 +161,8 @@ int rcf_device(rcf_t *h);
 #define RCF_T_CLOCK        10  /* symbol clocks (rcf_chan_clock_mm): one launch per block for every clocked channel */
 #define RCF_T_COSTAS       11  /* Gardner / Costas loops (rcf_chan_costas): one launch per block for every channel with the stage */
 #define RCF_T_FSK4         12  /* C4FM symbol loops (rcf_chan_fsk4): one launch per block for every channel with the stage */
-#define RCF_T_SLICE        13  /* hard decisions (rcf_chan_slicer): one launch per block for every channel with the stage */
+#define RCF_T_SLICE        13  /* hard decisions (rcf_chan_slicer): one launch per block for every channel with the stage; and the
+                                * launch of the TSBK stages behind them (rcf_chan_tsbk), one more per block with such a stage */
 #define RCF_T_COUNT        14
 /* on = 0: off; 1: every class; otherwise a mask with bit (class + 1) set for each class to time -- every timed
  * launch costs two event records on the stream (~10 us of gap), so a throughput run times only what it reports.  The
@@ -542,6 +543,66 @@ int64_t rcf_chan_read_sync(rcf_t *h, int chan_id, uint32_t *out, size_t max_hits
  * at index i & (word_capacity - 1), hit i at i & (hit_capacity - 1); rcf_chan_slicer_state gives the counts.  Any of the
  * four may be NULL. */
 int rcf_chan_slicer_rings(rcf_t *h, int chan_id, void **word_ring, size_t *word_capacity, void **hit_ring, size_t *hit_capacity);
+/* P25 trunking blocks behind a slicer: what the reference's consumer does per frame of a control channel in Python
+ * (p25_control_demod.py:337-364, p25_general.procTSDU / subprocTSBK / procStatus / data_deinterleave / trellis_1_2_decode /
+ * crc16), as one more optional stage per channel on the GPU.  It reads the slicer's own two streams and writes a third, the
+ * counted stream RCF_HARD_TSBK of 32-byte records: a consumer of a control channel takes the 12-octet TSBKs instead of every
+ * word of the dibit stream.  All of it is integer work: the records are exactly what the rules below give for the words and
+ * hits the slicer's readers deliver.  (No BCH correction of the NID -- the reference reads NAC and DUID uncorrected --, no
+ * other data unit than the TSDU, no parsing of a TSBK's fields.)
+ * Frames.  A hit item gives k, the last dibit of the sync word (widened against n_symbols as above); the frame starts at
+ * dibit s = k - 23.  Hits are taken in order; a hit is ACCEPTED if k >= k_last_accepted + 24 (buf.find(sync, fsoffset + 6)),
+ * the first one the stage considers always.  An accepted hit is DECIDED in the first block after which the slicer's whole
+ * words hold the dibits up to s + 384, 16 n_words >= s + 384: the 360 dibits of the longest TSDU and the 24 of a sync word
+ * that may begin inside them -- so every hit that can shorten the frame is in the hit ring by then and the stream does not
+ * depend on how the input was cut into blocks.  frame_dibits = min(360, s_next - s), s_next the frame start of the next
+ * accepted hit if there is one by then.  Dibit r of the frame is stream dibit s + r; info dibit j sits at r = j + j / 35
+ * (every 36th dibit is a status symbol).
+ * NID: info bits 48 .. 111; nac = info bits 48 .. 59, duid = info bits 60 .. 63.
+ * Blocks are decoded only when duid == 7.  Block b (0, 1, 2) is the info dibits 56 + 98 b .. 153 + 98 b and is decoded if its
+ * last dibit lies inside the frame, r(153 + 98 b) < frame_dibits (for frames of 180, 288 and 360 dibits the reference's
+ * `while len(bitframe) >= 196`).
+ * Deinterleave: code word t = 0 .. 47 is the block's dibits i + j, i + j + 1 with i = 2 (t / 4), j = (0, 26, 50, 74)[t % 4];
+ * code word 48 is the dibits 24, 25.
+ * Trellis: state 0 at the start; per code word c (4 bits) the new state is the candidate d whose word W[state][d] has the
+ * most bits equal to c, the lowest d of equals; W = {2 C 1 F, E 0 D 3, 9 7 A 4, 5 B 6 8}.  The output is the first 48
+ * states = 96 bits; n_inexact counts the code words (0 .. 49) with no candidate equal to c.
+ * CRC: register 0, every one of the 96 bits shifted in, xor 0x1021 when bit 16 falls out; the block is good iff the register
+ * ends at 0xffff.
+ * Records, 8 uint32 each, in increasing k, then b:
+ *     word 0    bits 0-1 b (3: a frame record without a block), bit 2 CRC bad, bit 3 next_bit, bits 4-9 n_inexact,
+ *               bits 10-15 the hit's distance, bits 16-19 duid, bits 20-31 nac
+ *     word 1    the low 32 bits of the widened k
+ *     word 2-4  the 96 decoded bits, the first bit highest, bytes in memory order (the word ring's rule: a uint8 view is the
+ *               12 octets); 0 in a frame record
+ *     word 5-6  the NID's 64 bits, same rule
+ *     word 7    frame_dibits
+ * next_bit is the info bit that follows the block's last one if it lies inside the frame, else 0 (procTSDU stops behind a
+ * block that is followed by a 1).  A frame record goes out for an accepted frame with duid != 7 or with no whole block.
+ * Lost: hits that left the hit ring before they were examined, and frames whose first word the word ring had overwritten
+ * when they were decided, are skipped and counted (n_lost); a lost frame still counts as accepted.
+ * p == NULL switches the stage off.  It applies from the next block on and considers only hits appended after the call (hit
+ * index >= the slicer's n_hits at that moment: the call reads that counter and so synchronises the stream); calling again
+ * starts it afresh.  It goes when the slicer goes: slicer attached again or switched off, its source loop attached again or
+ * switched off, channel closed.
+ * RCF_ESTATE: the channel has no slicer in RCF_SLICE_FSK4 mode that searches a 48-bit sync word; RCF_EINVAL: capacity not
+ * 0 or a power of two >= 16 (at most 2^20); RCF_ENOCHAN: no such channel. */
+typedef struct rcf_tsbk_params {
+    int capacity;          /* records of the ring, a power of two >= 16; 0 = 256 */
+    int reserved_[3];
+} rcf_tsbk_params_t;
+int rcf_chan_tsbk(rcf_t *h, int chan_id, const rcf_tsbk_params_t *p);
+/* the stage's counters as of the last block; syncs the stream.  RCF_ESTATE without the stage (here and in the calls below) */
+typedef struct rcf_tsbk_state {
+    int64_t n_records, n_frames, n_blocks, n_crc_bad, n_lost;   /* records written, frames accepted (decided or lost), blocks decoded, of them with a bad CRC, hits and frames lost */
+} rcf_tsbk_state_t;
+int rcf_chan_tsbk_state(rcf_t *h, int chan_id, rcf_tsbk_state_t *out);
+/* unread records, oldest first: out = uint32[max_records][8] (one round trip); RCF_HARD_TSBK names the stream to
+ * rcf_chan_read_many and rcf_group_read_many (out = uint32[n_chans][cap_each][8]); the pump does not deliver it */
+#define RCF_HARD_TSBK    48
+int64_t rcf_chan_read_tsbk(rcf_t *h, int chan_id, uint32_t *out, size_t max_records);
+/* device pointer of the record ring and its capacity in records (zero-copy): record i lives at word 8 (i & (capacity - 1)) */
+int rcf_chan_tsbk_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity);
 /* drift probe of p25_control_demod.py:123-127: moving_average_ff(window, 1) * (1/window) of the
  * discriminator output (window = 10000 there) == mean of gain*fm over the last `window` samples; this is
  * the value demod_watcher hands to frontend_connector.report_offset */

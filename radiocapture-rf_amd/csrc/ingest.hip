@@ -155,9 +155,11 @@ static __global__ __launch_bounds__(256) void gather_counted_kernel(const Counte
         const int64_t room = (int64_t)r.dst_mask_w + 1;              // a destination ring keeps the newest `room` items
         if (avail > room) { cur += avail - room; avail = room; }
         const uint32_t n = (uint32_t)min(avail, (int64_t)r.max_n);
-        const uint32_t first = (uint32_t)((uint64_t)cur & (r.cap - 1u)), at = (uint32_t)(uint64_t)pos;
-        for (uint32_t w = (item % parts) * 256 + threadIdx.x; w < n; w += parts * 256)
-            dst[r.dst_w + ((at + w) & r.dst_mask_w)] = r.ring[(first + w) & (r.cap - 1u)];
+        // in words from here on: an item is item_w of them (a power of two; the TSBK records: 8)
+        const uint32_t iw = r.item_w ? r.item_w : 1u, ring_mask_w = r.cap * iw - 1u, n_w = n * iw;
+        const uint32_t first = (uint32_t)((uint64_t)cur & (r.cap - 1u)) * iw, at = (uint32_t)(uint64_t)pos * iw;
+        for (uint32_t w = (item % parts) * 256 + threadIdx.x; w < n_w; w += parts * 256)
+            dst[r.dst_w + ((at + w) & r.dst_mask_w)] = r.ring[(first + w) & ring_mask_w];
         if (item % parts == 0 && threadIdx.x == 0) {
             r.result[0] = pos + n;
             r.result[1] = cur + n;
@@ -166,7 +168,7 @@ static __global__ __launch_bounds__(256) void gather_counted_kernel(const Counte
     }
 }
 
-// max_items: the largest max_n among the records (the segments' true lengths are the device's to know)
+// max_items: the largest max_n x item_w among the records (the segments' true lengths are the device's to know)
 void launch_gather_counted(const CountedRec *d_recs, int n_recs, uint32_t *d_dst, uint32_t max_items, hipStream_t s)
 {
     if (n_recs <= 0) return;

@@ -351,6 +351,24 @@ struct SliceLaunch {
     float levels[3];         // bps 2: the decision levels (the fourth of rcf_slicer_params_t decides nothing)
 };
 void launch_slice(const SliceLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
+// P25 trunking blocks behind a slicer (tsbk.hip; procTSDU of the reference: status symbols, NID, deinterleave, rate-1/2
+// trellis, CRC; definition: include/rcf.h at rcf_chan_tsbk).
+// per-channel running state, device resident, owned by tsbk_kernel
+struct TsbkState {
+    int64_t n_records;       // records written so far (record i at rec_ring[(i & rec_mask) * 8])
+    int64_t n_frames, n_blocks, n_crc_bad, n_lost;
+    int64_t next_hit;        // the first hit of the slicer's stream that is neither rejected nor decided
+    int64_t k_last;          // the last accepted hit's k
+};
+struct TsbkLaunch {
+    const SliceState *src;   // the slicer's counters (device)
+    const uint32_t *word_ring, *hit_ring;    // the slicer's two rings
+    TsbkState *st;
+    uint32_t *rec_ring;
+    uint32_t word_mask, hit_mask, rec_mask;
+    int32_t n_k;             // the slicer's n_k of this block: at most that many new symbols, and so new hits
+};
+void launch_tsbk(const TsbkLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
 // mean of gain * fm over the last `window` samples ending at n_end (exclusive), one workgroup
 void launch_fm_level(const float *fm_ring, int64_t n_end, int window, float gain, uint64_t ring_mask, float *d_out,
                      hipStream_t s);
@@ -615,7 +633,8 @@ struct CountedRec {
     uint32_t cap;            // ring capacity in items, a power of two
     uint32_t max_n;          // most items to take
     uint32_t dst_w, dst_mask_w;   // as in GatherRec (dst_mask_w = ~0u: a linear row)
-    uint32_t flags, pad_;
+    uint32_t flags;
+    uint32_t item_w;         // 4-byte words per item (0: one); cap, max_n and the cursors count items, dst_w and dst_mask_w words
 };
 void launch_gather_counted(const CountedRec *d_recs, int n_recs, uint32_t *d_dst, uint32_t max_items, hipStream_t s);
 // one record of the grouped ingest launch (group_prep_kernel, ingest.hip): a block of one front-end, or a plain copy

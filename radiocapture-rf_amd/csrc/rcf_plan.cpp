@@ -354,6 +354,11 @@ int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c)
         SliceLaunch rec = c->slicer->rec;
         rec.n_k = (int32_t)(s.n_lo + s.cnt - std::max(s.n_lo, from));
         if (rec.n_k > 0) bp.tails.slf.add(rec);
+        if (rec.n_k > 0 && c->slicer->tsbk) {      // the stage behind it sees what this block's slicer launch wrote
+            TsbkLaunch tr = c->slicer->tsbk->rec;
+            tr.n_k = rec.n_k;
+            bp.tails.tsf.add(tr);
+        }
     }
     if (c->audio && s.a_n > 0) {
         AudioLaunch al = c->audio->rec;

@@ -29,6 +29,7 @@ void (*const kRows[kStreamKinds])(Chan *, Stream *) = {
     [](Chan *c, Stream *s) { loop_row(c->fsk4.get(), s); },
     [](Chan *c, Stream *s) { if (Chan::Slicer *l = c->slicer.get()) counted_row(s, l->rec.word_ring, &l->rd_words, &l->rec.st->n_words, 0); },
     [](Chan *c, Stream *s) { if (Chan::Slicer *l = c->slicer.get()) { counted_row(s, l->rec.hit_ring, &l->rd_hits, &l->rec.st->n_hits, 0); s->cap = l->hit_cap; } },
+    [](Chan *c, Stream *s) { if (Chan::Slicer::Tsbk *t = c->slicer ? c->slicer->tsbk.get() : nullptr) { counted_row(s, t->rec.rec_ring, &t->rd, &t->rec.st->n_records, 0); s->cap = t->cap; } },
 };
 
 }  // namespace
@@ -78,7 +79,7 @@ int PinnedStage::ensure(size_t need, hipStream_t stream)
 // One gather launch packs every entry's segment back to back into pinned host memory, one synchronisation, then the rows are
 // handed out.  (A device round trip per channel -- a single reader in a loop -- costs ~10 us each: 256 tapped bins of ten
 // front-ends are 25 ms per pass.)  Counted entries ride in a launch of their own kind behind the same synchronisation: the
-// host does not know their lengths, so each reserves the most it may take -- min(max, cap) -- and the launch's result
+// host does not know their lengths, so each reserves the most it may take -- min(max, cap) items -- and the launch's result
 // words {items, cursor after} say what came.
 // Staging: GatherRec[] | CountedRec[] | result words | the plain entries' rows | the counted entries' rows
 int host_read(PinnedStage &stage, hipStream_t stream, rcf_t *const *idle, size_t n_idle, ReadEntry *es, size_t n)
@@ -99,8 +100,8 @@ int host_read(PinnedStage &stage, hipStream_t stream, rcf_t *const *idle, size_t
             *e.count = 0;
             e.max = std::min<int64_t>(e.max, (int64_t)e.s.cap);
             if (e.max <= 0) continue;
-            counted_w += (uint64_t)e.max;
-            max_c = std::max<uint32_t>(max_c, (uint32_t)e.max);
+            counted_w += (uint64_t)e.max * e.s.item_w;
+            max_c = std::max<uint32_t>(max_c, (uint32_t)e.max * e.s.item_w);
             counted.push_back(&e);
         } else {
             *e.count = lag_clamp((int64_t)e.s.cap, e.s.cursor, e.s.newest, e.s.end, e.max);
@@ -130,8 +131,8 @@ int host_read(PinnedStage &stage, hipStream_t stream, rcf_t *const *idle, size_t
         const ReadEntry &e = *counted[k];                 // (the host owns the cursor and the row starts at 0: flags 3)
         crecs[k] = CountedRec{static_cast<const uint32_t *>(e.s.ring), e.s.counter, nullptr, nullptr,
                               reinterpret_cast<int64_t *>(stage.d + res_at) + 2 * k, *e.s.cursor, 0, e.s.interp, e.s.decim,
-                              e.s.cap, (uint32_t)e.max, at_w, ~0u, 3u, 0u};
-        at_w += (uint32_t)e.max;
+                              e.s.cap, (uint32_t)e.max, at_w, ~0u, 3u, e.s.item_w};
+        at_w += (uint32_t)e.max * e.s.item_w;
     }
     uint32_t *d_dst = reinterpret_cast<uint32_t *>(stage.d + data_at);
     launch_gather_rings(reinterpret_cast<const GatherRec *>(stage.d), (int)plain.size(), d_dst, max_w, stream);
@@ -149,8 +150,8 @@ int host_read(PinnedStage &stage, hipStream_t stream, rcf_t *const *idle, size_t
         const ReadEntry &e = *counted[k];
         *e.count = res[2 * k];                            // (pos0 = 0: the items copied)
         *e.s.cursor = res[2 * k + 1];
-        std::memcpy(e.out, src, (size_t)*e.count * 4);
-        src += (size_t)e.max * 4;
+        std::memcpy(e.out, src, (size_t)*e.count * e.s.item_w * 4);
+        src += (size_t)e.max * e.s.item_w * 4;
     }
     return RCF_OK;
 }
@@ -219,6 +220,7 @@ int64_t rcf_chan_read_fsk4(rcf_t *h, int chan_id, float *out, size_t n) { return
 int64_t rcf_chan_read_audio(rcf_t *h, int chan_id, float *out, size_t n) { return chan_read_one(h, chan_id, RCF_READ_AUDIO, 1.0f, out, n); }
 int64_t rcf_chan_read_hard(rcf_t *h, int chan_id, uint32_t *out, size_t n) { return chan_read_one(h, chan_id, RCF_HARD_BITS, 1.0f, out, n); }
 int64_t rcf_chan_read_sync(rcf_t *h, int chan_id, uint32_t *out, size_t n) { return chan_read_one(h, chan_id, RCF_HARD_SYNC, 1.0f, out, n); }
+int64_t rcf_chan_read_tsbk(rcf_t *h, int chan_id, uint32_t *out, size_t n) { return chan_read_one(h, chan_id, RCF_HARD_TSBK, 1.0f, out, n); }
 
 int rcf_chan_read_many(rcf_t *h, int what, const int *chan_ids, int n_chans, float gain, void *out, size_t cap_each,
                        int64_t *counts)
@@ -265,6 +267,16 @@ int rcf_chan_slicer_rings(rcf_t *h, int chan_id, void **word_ring, size_t *word_
     if (!c->slicer) { set_error("channel %d has no slicer (rcf_chan_slicer)", chan_id); return RCF_ESTATE; }   // (closed in between)
     if (hit_ring) *hit_ring = c->slicer->rec.hit_ring;
     if (hit_capacity) *hit_capacity = c->slicer->hit_cap;
+    return RCF_OK;
+}
+int rcf_chan_tsbk_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity)
+{
+    const int rc = chan_rings(h, chan_id, kTsbk, true, rec_ring, nullptr, nullptr);
+    if (rc != RCF_OK) return rc;
+    std::lock_guard<std::mutex> g(h->mu);
+    FIND_CHAN(h, chan_id, c);
+    if (!c->slicer || !c->slicer->tsbk) { set_error(kStreams[kTsbk].refusal, chan_id); return RCF_ESTATE; }   // (closed in between)
+    if (capacity) *capacity = c->slicer->tsbk->cap;
     return RCF_OK;
 }
 

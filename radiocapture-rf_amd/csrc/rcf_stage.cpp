@@ -1,18 +1,22 @@
 // rcf_stage.cpp -- the optional stages behind a channel's rings (the records of Chan, rcf_state.h): the P25 symbol filter,
 // the feed-forward AGC, the SmartNet / EDACS symbol clock, the P25 CQPSK Gardner / Costas loop, the P25 C4FM symbol loop and
-// the analog voice chain, and the slicer behind one of the loops.
+// the analog voice chain, the slicer behind one of the loops and the P25 trunking stage behind the slicer.
 // Attach, off, and what they produced.
 // An attach function allocates into Fresh<> holders and builds the new record completely; only then is it swapped into
 // the channel and the old one released.  A HIP call that fails before that leaves the channel as it was.
 // The three symbol loops share their record (Chan::Loop) and one attach path, attach_loop: an entry point validates its
 // parameters, checks what the loop reads and the ring's size, and fills in its own constants and initial state.
 #include "rcf_plan.h"
+#define RCF_DEVFN static inline
+#define RCF_DEVCONST static const
+#include "tsbk_core.hpp"       // (kTsbkNoFrame, kTsbkRecWords)
 
 namespace rcfx {
 
 void Chan::Sym::release(rcf_t *h) { bury(h, rec.sym_ring); bury(h, const_cast<float *>(rec.taps)); rec.sym_ring = nullptr; rec.taps = nullptr; }
 void Chan::Agc::release(rcf_t *h) { bury(h, rec.agc_ring); rec.agc_ring = nullptr; }
-void Chan::Slicer::release(rcf_t *h) { bury(h, rec.word_ring); rec = SliceLaunch{}; }     // one allocation
+void Chan::Slicer::release_tsbk(rcf_t *h) { if (tsbk) { bury(h, tsbk->rec.rec_ring); tsbk.reset(); } }     // one allocation
+void Chan::Slicer::release(rcf_t *h) { release_tsbk(h); bury(h, rec.word_ring); rec = SliceLaunch{}; }     // one allocation; the TSBK stage goes with its slicer
 void Chan::Audio::release(rcf_t *h) { bury(h, rec.st); bury(h, rec.a_ring); bury(h, const_cast<float *>(rec.lpf)); rec = AudioLaunch{}; }
 
 }  // namespace rcfx
@@ -351,6 +355,68 @@ int rcf_chan_slicer_state(rcf_t *h, int chan_id, rcf_slicer_state_t *out)
     const int rc = stage_state(h, c->slicer->rec.st, &st, offsetof(SliceState, partial));
     if (rc != RCF_OK) return rc;
     out->n_symbols = st.n_symbols; out->n_words = st.n_words; out->n_hits = st.n_hits;
+    return RCF_OK;
+}
+
+// ---- P25 trunking blocks behind the slicer (tsbk.hip)
+int rcf_chan_tsbk(rcf_t *h, int chan_id, const rcf_tsbk_params_t *p)
+{
+    if (!h) return RCF_EINVAL;
+    int cap = 256;
+    if (p) {
+        if (p->capacity) cap = p->capacity;
+        if (cap < 16 || cap > (1 << 20) || (cap & (cap - 1))) { set_error("TSBK stage: capacity %d is not a power of two 16 .. 2^20", p->capacity); return RCF_EINVAL; }
+    }
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!p) {
+        if (c->slicer && c->slicer->tsbk) { c->slicer->release_tsbk(h); ++h->chans_epoch; }
+        return RCF_OK;
+    }
+    if (!c->slicer || c->slicer->rec.bps != 2 || c->slicer->rec.sync_bits != 48) {
+        set_error("channel %d has no slicer in RCF_SLICE_FSK4 mode that searches a 48-bit sync word", chan_id);
+        return RCF_ESTATE;
+    }
+    const SliceLaunch &sl = c->slicer->rec;
+    std::unique_ptr<Chan::Slicer::Tsbk> k(new Chan::Slicer::Tsbk);
+    TsbkLaunch &r = k->rec;
+    r.src = sl.st;
+    r.word_ring = sl.word_ring; r.hit_ring = sl.hit_ring;
+    r.word_mask = sl.word_mask; r.hit_mask = sl.hit_mask; r.rec_mask = (uint32_t)cap - 1;
+    k->cap = (uint32_t)cap;
+    // the stage's first hit: the slicer's count as of everything queued (one round trip)
+    SliceState now{};
+    const int rc = stage_state(h, sl.st, &now, offsetof(SliceState, partial));
+    if (rc != RCF_OK) return rc;
+    TsbkState st0{};
+    st0.next_hit = now.n_hits;
+    st0.k_last = kTsbkNoFrame;
+    constexpr size_t kStateWords = 256 / sizeof(uint32_t);
+    static_assert(sizeof(TsbkState) <= 256, "the state's slot");
+    const size_t state_at = (size_t)cap * kTsbkRecWords;                   // in words (cap >= 16: the record's 64-bit fields are aligned)
+    Fresh<uint32_t> fresh;
+    RCF_HIP(fresh.alloc(state_at + kStateWords));
+    if (!hip_ok(hipMemcpy(fresh.p + state_at, &st0, sizeof(st0), hipMemcpyHostToDevice), "hipMemcpy(TSBK state)")) return RCF_EHIP;
+    r.rec_ring = fresh.take();
+    r.st = reinterpret_cast<TsbkState *>(r.rec_ring + state_at);
+    c->slicer->release_tsbk(h);
+    c->slicer->tsbk = std::move(k);
+    ++h->chans_epoch;
+    return RCF_OK;
+}
+
+int rcf_chan_tsbk_state(rcf_t *h, int chan_id, rcf_tsbk_state_t *out)
+{
+    if (!h || !out) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!c->slicer || !c->slicer->tsbk) { set_error("channel %d has no TSBK stage (rcf_chan_tsbk)", chan_id); return RCF_ESTATE; }
+    TsbkState st{};                     // (its five counters)
+    const int rc = stage_state(h, c->slicer->tsbk->rec.st, &st, offsetof(TsbkState, next_hit));
+    if (rc != RCF_OK) return rc;
+    out->n_records = st.n_records; out->n_frames = st.n_frames; out->n_blocks = st.n_blocks; out->n_crc_bad = st.n_crc_bad; out->n_lost = st.n_lost;
     return RCF_OK;
 }
 

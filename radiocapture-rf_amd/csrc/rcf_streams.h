@@ -16,7 +16,7 @@ struct StreamKind {
     bool pumped;            // the pump delivers it
     const char *refusal;    // RCF_ESTATE: what a channel without that ring says (%d: the channel)
 };
-enum : int { kIq, kFm, kAgc, kSym, kClock, kAudio, kCostas, kFsk4, kHardBits, kHardSync, kStreamKinds };
+enum : int { kIq, kFm, kAgc, kSym, kClock, kAudio, kCostas, kFsk4, kHardBits, kHardSync, kTsbk, kStreamKinds };
 constexpr StreamKind kStreams[kStreamKinds] = {
     {RCF_READ_IQ,     2, false, false, true,  "channel %d exposes its discriminator only (rcf_chan_set_fm_only)"},
     {RCF_READ_FM,     1, false, false, true,  "channel %d has no discriminator ring"},
@@ -28,6 +28,7 @@ constexpr StreamKind kStreams[kStreamKinds] = {
     {RCF_READ_FSK4,   1, false, true,  true,  "channel %d has no C4FM symbol loop (rcf_chan_fsk4)"},
     {RCF_HARD_BITS,   1, true,  true,  false, "channel %d has no slicer (rcf_chan_slicer)"},
     {RCF_HARD_SYNC,   1, true,  true,  false, "channel %d has no slicer (rcf_chan_slicer)"},
+    {RCF_HARD_TSBK,   8, true,  true,  false, "channel %d has no TSBK stage (rcf_chan_tsbk)"},
 };
 // the row of `what`; -1: no such stream (3 .. 15 stay refused)
 constexpr int stream_kind(int what)
@@ -36,7 +37,7 @@ constexpr int stream_kind(int what)
         if (kStreams[k].what == what) return k;
     return -1;
 }
-static_assert(stream_kind(RCF_READ_AUDIO) == kAudio && stream_kind(RCF_HARD_SYNC) == kHardSync, "the rows stand in the enum's order");
+static_assert(stream_kind(RCF_READ_AUDIO) == kAudio && stream_kind(RCF_HARD_SYNC) == kHardSync && stream_kind(RCF_HARD_TSBK) == kTsbk, "the rows stand in the enum's order");
 
 // A reader that has fallen more than a ring of `cap` items behind lost what the ring overwrote: its cursor is raised to the
 // oldest item the ring still holds (the ring holds the cap items before `newest`).  Returns how many items [*cursor, end) it

@@ -1,0 +1,117 @@
+// tsbk_core.hpp -- the arithmetic of the P25 trunking stage (tsbk.hip; definition: include/rcf.h at rcf_chan_tsbk): the
+// widening of a hit's k, the accept rule, where an info dibit sits in a frame, the deinterleaver's index map, the rate-1/2
+// trellis as transition maps with their composition (what the wave scans), the CRC's per-bit terms and the packing of a
+// record.  No HIP types in here, like slice_core.hpp, whose mask-to-word helpers it uses: RCF_DEVFN is the function
+// qualifier and RCF_DEVCONST the qualifier of the one table, so that the CPU suite compiles this very source with g++
+// (tests/native/tsbk_core_check.cpp).
+#pragma once
+#include "slice_core.hpp"
+#ifndef RCF_DEVCONST
+#define RCF_DEVCONST __constant__ const
+#endif
+
+namespace rcfx {
+
+namespace {
+
+constexpr int kTsbkSyncDibits = 24;      // the 48-bit frame sync
+constexpr int kTsbkFrameDibits = 360;    // the longest TSDU: three blocks
+// a frame is decided once the stream's whole words hold its 360 dibits and the 24 of a sync word that may follow them: every
+// hit that can shorten the frame is in the hit ring by then, however the input was cut
+constexpr int kTsbkDecideDibits = kTsbkFrameDibits + kTsbkSyncDibits;
+constexpr int kTsbkCodeWords = 49;       // code words of a block: 98 dibits
+constexpr int kTsbkRecWords = 8;         // uint32 words of a record
+constexpr int64_t kTsbkNoFrame = -((int64_t)1 << 60);   // k_last before the first accepted hit
+
+// a hit item's k: the largest value <= n_symbols - 1 with the item's low 26 bits (rcf.h at rcf_chan_slicer)
+RCF_DEVFN int64_t tsbk_widen_k(uint32_t item, int64_t n_symbols)
+{
+    const int64_t low = (int64_t)(item & 0x3ffffffu), last = n_symbols - 1;
+    return low + ((last - low) >> 26) * ((int64_t)1 << 26);
+}
+// buf.find(sync, fsoffset + 6): a sync word that begins inside the last accepted one is no frame
+RCF_DEVFN bool tsbk_accept(int64_t k, int64_t k_last) { return k >= k_last + kTsbkSyncDibits; }
+// frame dibit of info dibit j: every 36th dibit is a status symbol (procStatus)
+RCF_DEVFN int tsbk_frame_pos(int j) { return j + j / 35; }
+// block b's info dibits are 56 + 98 b .. 153 + 98 b; the blocks whose last dibit lies inside a frame of fd dibits
+RCF_DEVFN int tsbk_block_dibit(int b, int p) { return 56 + 98 * b + p; }
+RCF_DEVFN int tsbk_blocks_in(int fd)
+{
+    int n = 0;
+    for (int b = 0; b < 3; ++b) n += tsbk_frame_pos(tsbk_block_dibit(b, 97)) < fd ? 1 : 0;
+    return n;
+}
+// data_deinterleave: the first of the two block dibits (0 .. 96) of code word t (0 .. 48)
+RCF_DEVFN int tsbk_deinterleave(int t)
+{
+    const int m = t & 3;
+    return t >= 48 ? 24 : 2 * (t >> 2) + (m ? 2 + 24 * m : 0);
+}
+// dibit p (0 .. 15) of a word of the slicer's ring as it lies in memory
+RCF_DEVFN int tsbk_word_dibit(uint32_t mem, int p) { return (int)(slice_bswap32(mem) >> (30 - 2 * p)) & 3; }
+
+// ---- trellis_1_2_decode.  Row `state` of the standard's table, candidate d in the nibble 4 d
+RCF_DEVFN uint32_t tsbk_trellis_row(int state) { return state == 0 ? 0xF1C2u : state == 1 ? 0x3D0Eu : state == 2 ? 0x4A79u : 0x86B5u; }
+RCF_DEVFN int tsbk_pop4(uint32_t v) { return (int)(0x4332322132212110ull >> (4 * (v & 15u))) & 7; }
+// the state after code word c (4 bits) in `state`: the candidate with the most bits equal, the lowest of equals -- over all
+// 64 pairs what the reference's count(4) / count(3) / best-guess ladder gives; *exact: a candidate equals c
+RCF_DEVFN int tsbk_next_state(int state, uint32_t c, bool *exact)
+{
+    const uint32_t row = tsbk_trellis_row(state);
+    int best = 0, best_dist = 5;
+    for (int d = 0; d < 4; ++d) {
+        const int dist = tsbk_pop4(((row >> (4 * d)) & 15u) ^ c);
+        if (dist < best_dist) { best_dist = dist; best = d; }
+    }
+    *exact = best_dist == 0;
+    return best;
+}
+// a code word as a transition map: the state after it from state s in the bits 2 s, 2 s + 1
+RCF_DEVFN uint32_t tsbk_map(uint32_t c)
+{
+    uint32_t m = 0;
+    bool e;
+    for (int s = 0; s < 4; ++s) m |= (uint32_t)tsbk_next_state(s, c, &e) << (2 * s);
+    return m;
+}
+constexpr uint32_t kTsbkIdentity = 0xE4u;
+// first, then `then`: the map of two code words in a row (associative: what the inclusive scan combines)
+RCF_DEVFN uint32_t tsbk_compose(uint32_t first, uint32_t then)
+{
+    uint32_t m = 0;
+    for (int s = 0; s < 4; ++s) m |= ((then >> (2 * ((first >> (2 * s)) & 3u))) & 3u) << (2 * s);
+    return m;
+}
+
+// ---- crc16 of the reference: register 0, every bit shifted in, xor 0x1021 when bit 16 falls out; good: 0xffff.  From 0 the
+// register is linear in the bits: bit p (0 .. 95, the first one 0) adds x^(95 - p) mod the polynomial -- these terms
+struct TsbkCrcTerms { uint16_t t[96]; };
+constexpr TsbkCrcTerms tsbk_make_crc_terms()
+{
+    TsbkCrcTerms r{};
+    uint32_t v = 1;
+    for (int e = 0; e < 96; ++e) {
+        r.t[95 - e] = (uint16_t)v;
+        v <<= 1;
+        if (v & 0x10000u) v = (v & 0xffffu) ^ 0x1021u;
+    }
+    return r;
+}
+RCF_DEVCONST TsbkCrcTerms kTsbkCrcTerms = tsbk_make_crc_terms();
+// what decoded dibit t (0 .. 47) of a block adds to the register
+RCF_DEVFN uint32_t tsbk_crc_term(int t, int dibit)
+{
+    return ((dibit & 2) ? (uint32_t)kTsbkCrcTerms.t[2 * t] : 0u) ^ ((dibit & 1) ? (uint32_t)kTsbkCrcTerms.t[2 * t + 1] : 0u);
+}
+
+// ---- a record's word 0; nid0: the NID's first word in stream order, whose top 16 bits are nac and duid as the record holds them
+RCF_DEVFN uint32_t tsbk_word0(int b, bool crc_bad, int next_bit, int n_inexact, uint32_t dist, uint32_t nid0)
+{
+    return (uint32_t)(b & 3) | (crc_bad ? 4u : 0u) | ((uint32_t)(next_bit & 1) << 3) | ((uint32_t)(n_inexact & 63) << 4) |
+           ((dist & 63u) << 10) | (nid0 & 0xffff0000u);
+}
+RCF_DEVFN int tsbk_duid(uint32_t nid0) { return (int)(nid0 >> 16) & 15; }
+
+}  // namespace
+
+}  // namespace rcfx

@@ -38,6 +38,7 @@ SYMBOLS = [
     "rcf_chan_costas", "rcf_chan_costas_state", "rcf_chan_read_costas", "rcf_chan_costas_ring",
     "rcf_chan_fsk4", "rcf_chan_fsk4_state", "rcf_chan_read_fsk4", "rcf_chan_fsk4_ring",
     "rcf_chan_slicer", "rcf_chan_slicer_state", "rcf_chan_read_hard", "rcf_chan_read_sync", "rcf_chan_slicer_rings",
+    "rcf_chan_tsbk", "rcf_chan_tsbk_state", "rcf_chan_read_tsbk", "rcf_chan_tsbk_ring",
     "rcf_design_firdes", "rcf_design_optfir_low_pass", "rcf_design_fm_deemph", "rcf_design_resampler", "rcf_chan_audio_open",
     "rcf_chan_audio_close", "rcf_chan_audio_produced", "rcf_chan_read_audio",
     "rcf_host_alloc", "rcf_host_free", "rcf_comm_unique_id", "rcf_comm_init", "rcf_comm_destroy", "rcf_comm_size",
@@ -53,7 +54,12 @@ READ_SYM, READ_CLOCK, READ_COSTAS, READ_FSK4, READ_AUDIO = 16, 17, 18, 19, 20
 _STAGE_WHAT = {"sym": READ_SYM, "clock": READ_CLOCK, "costas": READ_COSTAS, "fsk4": READ_FSK4, "audio": READ_AUDIO}
 # the slicer's two streams (RCF_HARD_BITS, RCF_HARD_SYNC): uint32 rows of the batched readers; the pump does not deliver them
 HARD_BITS, HARD_SYNC = 32, 33
-_HARD_WHAT = {"hard": HARD_BITS, "sync": HARD_SYNC}
+# the stream of the TSBK stage behind a slicer (RCF_HARD_TSBK): records of 8 uint32, batched the same way
+HARD_TSBK = 48
+_HARD_WHAT = {"hard": HARD_BITS, "sync": HARD_SYNC, "tsbk": HARD_TSBK}
+# a record of RCF_HARD_TSBK (rcf.h at rcf_chan_tsbk): word 0 (see tsbk_fields), the low 32 bits of k, the 12 decoded octets,
+# the NID's 8 octets, frame_dibits
+TSBK_DTYPE = np.dtype([("flags", "<u4"), ("k", "<u4"), ("octets", "u1", (12,)), ("nid", "u1", (8,)), ("frame_dibits", "<u4")])
 SLICE_BINARY, SLICE_FSK4 = 1, 2
 T_FIR, T_PFB, T_FIR_DERIVED, T_DISC, T_SCAN_FFT, T_SCAN_MOVSUM, T_HISTORY, T_FIR_MFMA, T_AUDIO, T_TAPS, T_CLOCK, T_COSTAS, T_FSK4, T_SLICE = range(14)
 
@@ -147,6 +153,25 @@ class SlicerParams(C.Structure):
 class SlicerState(C.Structure):
     """rcf_slicer_state_t (include/rcf.h)"""
     _fields_ = [("n_symbols", C.c_int64), ("n_words", C.c_int64), ("n_hits", C.c_int64)]
+
+
+class TsbkParams(C.Structure):
+    """rcf_tsbk_params_t (include/rcf.h)"""
+    _fields_ = [("capacity", C.c_int), ("reserved_", C.c_int * 3)]
+
+
+class TsbkState(C.Structure):
+    """rcf_tsbk_state_t (include/rcf.h)"""
+    _fields_ = [("n_records", C.c_int64), ("n_frames", C.c_int64), ("n_blocks", C.c_int64), ("n_crc_bad", C.c_int64),
+                ("n_lost", C.c_int64)]
+
+
+def tsbk_fields(records):
+    """word 0 of TSBK records taken apart -> dict of arrays: b (3: a frame record), crc_bad, next_bit, n_inexact, dist, duid, nac"""
+    f = np.asarray(records["flags"], dtype=np.uint32)
+    return dict(b=(f & 3).astype(np.uint8), crc_bad=((f >> 2) & 1).astype(np.uint8), next_bit=((f >> 3) & 1).astype(np.uint8),
+                n_inexact=((f >> 4) & 63).astype(np.uint8), dist=((f >> 10) & 63).astype(np.uint8),
+                duid=((f >> 16) & 15).astype(np.uint8), nac=(f >> 20).astype(np.uint16))
 
 
 def widen_hits(items, n_symbols):
@@ -246,6 +271,10 @@ def lib():
         "rcf_chan_read_hard": (i64, [vp, C.c_int, C.POINTER(C.c_uint32), sz]),
         "rcf_chan_read_sync": (i64, [vp, C.c_int, C.POINTER(C.c_uint32), sz]),
         "rcf_chan_slicer_rings": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]),
+        "rcf_chan_tsbk": (C.c_int, [vp, C.c_int, C.POINTER(TsbkParams)]),
+        "rcf_chan_tsbk_state": (C.c_int, [vp, C.c_int, C.POINTER(TsbkState)]),
+        "rcf_chan_read_tsbk": (i64, [vp, C.c_int, C.POINTER(C.c_uint32), sz]),
+        "rcf_chan_tsbk_ring": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]),
         "rcf_design_mmse_interpolator": (C.c_int, [C.c_int, C.c_int, C.c_double, fp, C.c_int]),
         "rcf_chan_fm_level": (C.c_int, [vp, C.c_int, C.c_float, C.c_int, fp]),
         "rcf_design_firdes": (C.c_int, [C.c_int] + [C.c_double] * 4 + [C.c_int, C.c_double, fp, C.c_int]),
@@ -333,7 +362,7 @@ def lib():
 def _read_what(what, stages=False):
     """the batched readers' and the pump's `what`: "iq", "agc", anything else the discriminator (as it always was).
     stages=True -- how every reader of this module calls it -- also names the stages' streams: "sym", "clock", "costas",
-    "fsk4", "audio", and the slicer's "hard" and "sync".  The one-argument form keeps its old answers ("sym" was never a
+    "fsk4", "audio", the slicer's "hard" and "sync" and the TSBK stage's "tsbk".  The one-argument form keeps its old answers ("sym" was never a
     stream there: the discriminator)."""
     if stages and what in _STAGE_WHAT:
         return _STAGE_WHAT[what]
@@ -344,8 +373,10 @@ def _read_what(what, stages=False):
 
 def _read_dtype(what):
     """item type of stream `what` as the readers deliver it: cf32 for "iq" and "agc", uint32 for the slicer's "hard" and
-    "sync", float32 for everything else"""
+    "sync", TSBK_DTYPE for "tsbk", float32 for everything else"""
     w = _read_what(what, True)
+    if w == HARD_TSBK:
+        return TSBK_DTYPE
     return np.complex64 if w in (READ_IQ, READ_AGC) else np.uint32 if w in (HARD_BITS, HARD_SYNC) else np.float32
 
 
@@ -709,7 +740,8 @@ class Frontend:
         (views into `out`, a [len(cids), cap_each] complex64 / float32 array -- pass a PinnedArray's for overlapping
         copies), None where the channel no longer exists (or lacks the stream).  what: "iq", "fm" (x gain), "agc", or a
         stage's stream -- "sym", "clock", "costas", "fsk4", "audio": float32, from where that stage's single reader stands --
-        or the slicer's "hard" (packed words) / "sync" (hit items, see widen_hits): uint32"""
+        or the slicer's "hard" (packed words) / "sync" (hit items, see widen_hits): uint32 -- or the TSBK stage's "tsbk":
+        TSBK_DTYPE records"""
         n = len(cids)
         dt = _read_dtype(what)
         if out is None:
@@ -886,6 +918,34 @@ class Frontend:
         wp, wc, hp, hc = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t()
         _check(lib().rcf_chan_slicer_rings(self._h, cid, C.byref(wp), C.byref(wc), C.byref(hp), C.byref(hc)))
         return wp.value, wc.value, hp.value, hc.value
+
+    def chan_tsbk(self, cid, capacity=0, on=True):
+        """P25 trunking blocks behind the channel's slicer (rcf_chan_tsbk): frames from the sync hits, status symbols
+        stripped, NID read, every block deinterleaved, trellis-decoded and CRC-checked on the GPU; records of TSBK_DTYPE
+        in a ring of `capacity` (0: 256).  It considers the hits from now on; on=False switches it off."""
+        if not on:
+            _check(lib().rcf_chan_tsbk(self._h, cid, None))
+            return
+        p = TsbkParams()
+        p.capacity = int(capacity)
+        _check(lib().rcf_chan_tsbk(self._h, cid, C.byref(p)))
+
+    def chan_tsbk_state(self, cid) -> dict:
+        """n_records, n_frames, n_blocks, n_crc_bad, n_lost of the TSBK stage as of the last block (rcf_chan_tsbk_state;
+        syncs the stream)"""
+        st = TsbkState()
+        _check(lib().rcf_chan_tsbk_state(self._h, cid, C.byref(st)))
+        return _state_dict(st)
+
+    def chan_read_tsbk(self, cid, max_records=1 << 12) -> np.ndarray:
+        """unread records of the TSBK stage, oldest first: a structured array of TSBK_DTYPE (tsbk_fields takes `flags` apart)"""
+        out = np.empty(max_records, dtype=TSBK_DTYPE)
+        n = _check(lib().rcf_chan_read_tsbk(self._h, cid, out.ctypes.data_as(C.POINTER(C.c_uint32)), max_records))
+        return out[:n].copy()
+
+    def chan_tsbk_ring(self, cid):
+        """(device pointer, capacity in records) of the stage's record ring (rcf_chan_tsbk_ring)"""
+        return self._ring_of(lib().rcf_chan_tsbk_ring, cid)
 
     def chan_fsk4_ring(self, cid):
         """(device pointer, capacity) of the stage's float32 soft-symbol ring (rcf_chan_fsk4_ring)"""

@@ -29,8 +29,33 @@ FRAME_SYNC_BITS = 48
 FRAME_SYNC_MAX_ERRORS = 4
 
 
-def _hard(fe, cid, source):
+def _hard(fe, cid, source, tsbk=False):
     fe.chan_slicer(cid, source, native.SLICE_FSK4, SLICER_LEVELS, FRAME_SYNC, FRAME_SYNC_BITS, FRAME_SYNC_MAX_ERRORS)
+    if tsbk:
+        fe.chan_tsbk(cid)
+
+
+def tsdu_frames(records, reference_rule=False):
+    """records of the TSBK stage (Frontend.chan_read_tsbk, native.TSBK_DTYPE) grouped into frames, in the stream's order ->
+    list of dict(k, dist, nac, duid, frame_dibits, nid: 8 octets, tsbk: list of dict(b, octets: 12 octets, crc: 0 good /
+    1 bad as subprocTSBK's, next_bit, n_inexact)).  A frame record (no block) gives a frame with an empty list.
+    reference_rule=True stops a frame's list behind a block whose next_bit is 1, as procTSDU does: the list is then its
+    r['tsbk'].  A frame is told from the one before by the low 32 bits of k."""
+    records = np.asarray(records, dtype=native.TSBK_DTYPE)
+    f = native.tsbk_fields(records)
+    frames, stopped = [], False
+    for i in range(len(records)):
+        k = int(records["k"][i])
+        if not frames or frames[-1]["k"] != k:
+            frames.append(dict(k=k, dist=int(f["dist"][i]), nac=int(f["nac"][i]), duid=int(f["duid"][i]),
+                               frame_dibits=int(records["frame_dibits"][i]), nid=bytes(records["nid"][i]), tsbk=[]))
+            stopped = False
+        if f["b"][i] == 3 or stopped:
+            continue
+        frames[-1]["tsbk"].append(dict(b=int(f["b"][i]), octets=bytes(records["octets"][i]), crc=int(f["crc_bad"][i]),
+                                       next_bit=int(f["next_bit"][i]), n_inexact=int(f["n_inexact"][i])))
+        stopped = bool(reference_rule and f["next_bit"][i])
+    return frames
 
 
 def prefilter_taps(channel_rate):
@@ -73,15 +98,16 @@ def costas_params(channel_rate, symbol_rate=SYMBOL_RATE):
                 beta=0.125 * alpha * alpha, max_freq=2.0 * math.pi * 1200.0 / rate, omega_limit=0.005)
 
 
-def cqpsk_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False):
+def cqpsk_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False, tsbk=False):
     """the whole CQPSK chain up to the slicer on channel `chan_id` of Frontend `fe`: the front half, then the Gardner /
     Costas stage (p25_control_demod.py:136-183).  Returns the pre-filter channel's id: chan_read_costas on it gives soft
     dibits at symbol_rate (slice_dibits turns them into dibits), chan_costas_state its carrier estimate.  hard=True also
-    attaches the slicer behind the loop: chan_read_hard gives packed dibits, chan_read_sync where FRAME_SYNC ends."""
+    attaches the slicer behind the loop: chan_read_hard gives packed dibits, chan_read_sync where FRAME_SYNC ends; with
+    tsbk=True as well the TSBK stage behind the slicer (chan_read_tsbk, tsdu_frames)."""
     cid = cqpsk_front_half(fe, chan_id, channel_rate)
     fe.chan_costas(cid, **costas_params(channel_rate, symbol_rate))
     if hard:
-        _hard(fe, cid, native.READ_COSTAS)
+        _hard(fe, cid, native.READ_COSTAS, tsbk)
     return cid
 
 
@@ -107,15 +133,16 @@ def fsk4_params(channel_rate, symbol_rate=SYMBOL_RATE):
                 k_coarse=0.00125, spread_min=1.6, spread_max=2.4)
 
 
-def c4fm_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False):
+def c4fm_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False, tsbk=False):
     """the whole C4FM chain up to the slicer on channel `chan_id` of Frontend `fe`: the front half, then the symbol loop
     (p25_control_demod.py:118-135).  Returns the pre-filter channel's id: chan_read_fsk4 on it gives soft dibits at
     symbol_rate (slice_dibits turns them into dibits), chan_fsk4_state its offset estimate (`coarse`).  hard=True also
-    attaches the slicer behind the loop: chan_read_hard gives packed dibits, chan_read_sync where FRAME_SYNC ends."""
+    attaches the slicer behind the loop: chan_read_hard gives packed dibits, chan_read_sync where FRAME_SYNC ends; with
+    tsbk=True as well the TSBK stage behind the slicer (chan_read_tsbk, tsdu_frames)."""
     cid = c4fm_front_half(fe, chan_id, channel_rate, symbol_rate)
     fe.chan_fsk4(cid, **fsk4_params(channel_rate, symbol_rate))
     if hard:
-        _hard(fe, cid, native.READ_FSK4)
+        _hard(fe, cid, native.READ_FSK4, tsbk)
     return cid
 
 

@@ -1,0 +1,160 @@
+"""The P25 trunking stage (rcf_chan_tsbk, include/rcf.h) restated in plain numpy / Python over what the slicer's readers
+deliver: the packed words and the (widened) sync hits.  Frames from the hits by the accept rule, status symbols stripped, NID
+read, every block deinterleaved, trellis-decoded by the 49-step walk and CRC-checked bit by bit -> records of
+native.TSBK_DTYPE and the stage's counters.  `launches` walks the streams as the stage sees them grow, block by block, and
+models the two rings' losses."""
+import numpy as np
+
+from rcf import native
+
+W = ((0x2, 0xC, 0x1, 0xF), (0xE, 0x0, 0xD, 0x3), (0x9, 0x7, 0xA, 0x4), (0x5, 0xB, 0x6, 0x8))
+ORDER = [i + j + e for i in range(0, 23, 2) for j in (0, 26, 50, 74) for e in (0, 1)] + [24, 25]   # deinterleaved dibit n <- block dibit ORDER[n]
+DECIDE = 384                                       # dibits from the frame's start that must be in whole words
+
+
+def dibits_of(words):
+    """the dibit stream of packed words (uint32, or their uint8 view)"""
+    by = np.ascontiguousarray(words).view(np.uint8)
+    bits = np.unpackbits(by)
+    return (2 * bits[0::2] + bits[1::2]).astype(np.uint8)
+
+
+def pos(j):
+    """frame dibit of info dibit j"""
+    return j + j // 35
+
+
+def trellis(code_words):
+    """-> (states, code words with no exact candidate)"""
+    state, out, inexact = 0, [], 0
+    for c in code_words:
+        same = [4 - bin(W[state][d] ^ c).count("1") for d in range(4)]
+        inexact += 4 not in same
+        state = same.index(max(same))
+        out.append(state)
+    return out, inexact
+
+
+def crc_register(bits):
+    reg = 0
+    for b in bits:
+        reg = (reg << 1) | int(b)
+        if reg & 0x10000:
+            reg = (reg & 0xffff) ^ 0x1021
+    return reg
+
+
+def decode_block(block):
+    """a block's 98 dibits -> (the 96 bits, crc bad, n_inexact)"""
+    d = [int(block[at]) for at in ORDER]
+    states, inexact = trellis([4 * d[2 * t] + d[2 * t + 1] for t in range(49)])
+    bits = [v for s in states[:48] for v in (s >> 1, s & 1)]
+    return bits, int(crc_register(bits) != 0xffff), inexact
+
+
+def frame_records(d, s, fd, k, dist):
+    """the records of the frame that starts at stream dibit s and has fd dibits"""
+    info = lambda j: int(d[s + pos(j)])
+    nid_bits = [v for j in range(24, 56) for v in (info(j) >> 1, info(j) & 1)]
+    nid = np.packbits(np.array(nid_bits, np.uint8))
+    nac = int("".join(map(str, nid_bits[:12])), 2)
+    duid = int("".join(map(str, nid_bits[12:16])), 2)
+    recs = []
+    if duid == 7:
+        for b in range(3):
+            if pos(153 + 98 * b) >= fd:
+                break
+            bits, bad, inexact = decode_block([info(56 + 98 * b + p) for p in range(98)])
+            nxt = pos(154 + 98 * b)
+            next_bit = info(154 + 98 * b) >> 1 if nxt < fd else 0
+            recs.append((b, bad, next_bit, inexact, np.packbits(np.array(bits, np.uint8))))
+    if not recs:
+        recs.append((3, 0, 0, 0, np.zeros(12, np.uint8)))
+    out = np.zeros(len(recs), native.TSBK_DTYPE)
+    for r, (b, bad, next_bit, inexact, octets) in zip(out, recs):
+        r["flags"] = b | bad << 2 | next_bit << 3 | inexact << 4 | int(dist) << 10 | duid << 16 | nac << 20
+        r["k"] = k & 0xffffffff
+        r["octets"] = octets
+        r["nid"] = nid
+        r["frame_dibits"] = fd
+    return out
+
+
+# ---- the other direction, for the tests' signals: a TSBK's 12 octets -> a block -> a frame's dibits
+SYNC_DIBITS = [(0x5575F5FF77FF >> (46 - 2 * i)) & 3 for i in range(24)]
+
+
+def tsbk_octets(rng):
+    """10 random octets and the 2 that make the CRC good"""
+    payload = np.unpackbits(rng.integers(0, 256, 10).astype(np.uint8))
+    f = crc_register(list(payload) + [0] * 16) ^ 0xffff
+    return bytes(np.packbits(np.concatenate([payload, [(f >> (15 - i)) & 1 for i in range(16)]]).astype(np.uint8)))
+
+
+def encode_block(octets):
+    """12 octets -> the block's 98 dibits: the trellis forward from state 0 with a flushing dibit, then the interleaver"""
+    bits = np.unpackbits(np.frombuffer(octets, np.uint8))
+    coded, state = [], 0
+    for d in [2 * int(bits[2 * i]) + int(bits[2 * i + 1]) for i in range(48)] + [0]:
+        coded += [W[state][d] >> 2, W[state][d] & 3]
+        state = d
+    block = [0] * 98
+    for n, at in enumerate(ORDER):
+        block[at] = coded[n]
+    return block
+
+
+def frame(nac, duid, tsbks, rng, total=None):
+    """a data unit's dibits: sync, NID (nac, duid and 48 bits nobody checks), the TSBKs' blocks, null dibits up to `total`
+    (default: the TSDU's length for that many blocks), a status dibit behind every 35 info dibits"""
+    total = {0: 180, 1: 180, 2: 288, 3: 360}[len(tsbks)] if total is None else total
+    nid = (nac << 52) | (duid << 48) | int(rng.integers(0, 1 << 48))
+    info = SYNC_DIBITS + [(nid >> (62 - 2 * i)) & 3 for i in range(32)]
+    for t in tsbks:
+        info += encode_block(t)
+    info += [0] * (total - total // 36 - len(info))
+    out = []
+    for j, d in enumerate(info[:total - total // 36]):
+        out.append(d)
+        if j % 35 == 34:
+            out.append(int(rng.integers(0, 4)))
+    return np.array(out[:total], np.uint8)
+
+
+def run(words, k, dist, first_hit=0, launches=None, word_cap=None, hit_cap=None):
+    """-> (records, dict(n_records, n_frames, n_blocks, n_crc_bad, n_lost)).  words, k, dist: the slicer's streams from its
+    start; first_hit: the slicer's n_hits when the stage was attached; launches: [(n_words, n_hits)] after each block (default:
+    one, at the end); word_cap / hit_cap: the rings' capacities (default: nothing is ever overwritten)"""
+    d = dibits_of(words)
+    k = [int(v) for v in k]
+    launches = [(len(d) // 16, len(k))] if launches is None else launches
+    i, k_last = first_hit, None
+    out = []
+    st = dict(n_records=0, n_frames=0, n_blocks=0, n_crc_bad=0, n_lost=0)
+    for n_words, n_hits in launches:
+        if hit_cap and i < n_hits - hit_cap:
+            st["n_lost"] += n_hits - hit_cap - i
+            i = n_hits - hit_cap
+        while i < n_hits:
+            if k_last is not None and k[i] < k_last + 24:
+                i += 1
+                continue
+            s = k[i] - 23
+            if 16 * n_words < s + DECIDE:
+                break
+            later = [v for v in k[i + 1:n_hits] if v >= k[i] + 24]
+            fd = min(360, later[0] - k[i]) if later else 360
+            k_last = k[i]
+            st["n_frames"] += 1
+            i += 1
+            if word_cap and s // 16 < n_words - word_cap:
+                st["n_lost"] += 1
+                continue
+            recs = frame_records(d, s, fd, k_last, dist[i - 1])
+            out.append(recs)
+            blocks = recs[(recs["flags"] & 3) != 3]
+            st["n_blocks"] += len(blocks)
+            st["n_crc_bad"] += int(np.count_nonzero(blocks["flags"] & 4))
+    recs = np.concatenate(out) if out else np.zeros(0, native.TSBK_DTYPE)
+    st["n_records"] = len(recs)
+    return recs, st
