@@ -162,7 +162,8 @@ int rcf_device(rcf_t *h);
 #define RCF_T_COSTAS       11  /* Gardner / Costas loops (rcf_chan_costas): one launch per block for every channel with the stage */
 #define RCF_T_FSK4         12  /* C4FM symbol loops (rcf_chan_fsk4): one launch per block for every channel with the stage */
 #define RCF_T_SLICE        13  /* hard decisions (rcf_chan_slicer): one launch per block for every channel with the stage; and the
-                                * launch of the TSBK stages behind them (rcf_chan_tsbk), one more per block with such a stage */
+                                * launch of the TSBK stages behind them (rcf_chan_tsbk), one more per block with such a stage,
+                                * and likewise that of the EDACS stages (rcf_chan_edacs) */
 #define RCF_T_COUNT        14
 /* on = 0: off; 1: every class; otherwise a mask with bit (class + 1) set for each class to time -- every timed
  * launch costs two event records on the stream (~10 us of gap), so a throughput run times only what it reports.  The
@@ -510,13 +511,18 @@ int rcf_chan_fsk4_ring(rcf_t *h, int chan_id, void **sym_ring, size_t *capacity)
  * increasing k.  A reader widens k against n_symbols: the largest value <= n_symbols - 1 with those low 26 bits.  Neither
  * stream depends on how the input was cut into blocks.  The word ring has out_capacity words, the hit ring hit_capacity
  * items; a reader that falls more than a ring behind loses the oldest.
+ * Both polarities (sync_both = 1; edacs_control_demod.py:401-408 accepts its frame sync inverted): an item is appended as
+ * well when dist >= sync_bits - sync_max_errors, i.e. when the window is within sync_max_errors of the inverted word.  The
+ * item carries dist as it is: a reader takes dist > sync_bits / 2 as "inverted, at distance sync_bits - dist".  With
+ * sync_both = 0 nothing of this applies.
  * p == NULL switches the stage off.  It applies from the next block on, on every channel kind its source loop supports; a
  * retune keeps it, calling again starts it afresh (new rings and state, k = 0 at the loop's next symbol), closing the
  * channel releases it.  Switching the source loop off, or attaching it again (a fresh ring, symbol 0), DETACHES the slicer:
  * it must be attached again behind the new loop.  A channel has at most one slicer.
  * RCF_EINVAL: an unknown source or mode, levels that are not finite or not non-decreasing (RCF_SLICE_FSK4), sync_bits not 0
  * or 8 .. 64 and a multiple of the bits per symbol, sync_max_errors outside 0 .. sync_bits - 1 (0 without a search),
- * hit_capacity not 0 or a power of two >= 16 (at most 2^26); RCF_ENOCHAN: no such channel; RCF_ESTATE: the channel does not
+ * hit_capacity not 0 or a power of two >= 16 (at most 2^26), sync_both not 0 or 1, or 1 with 2 sync_max_errors >= sync_bits
+ * (the two polarities' ranges of dist would meet); RCF_ENOCHAN: no such channel; RCF_ESTATE: the channel does not
  * carry the named loop; RCF_ECAP: out_capacity < 64. */
 #define RCF_SLICE_BINARY 1
 #define RCF_SLICE_FSK4   2
@@ -528,7 +534,7 @@ typedef struct rcf_slicer_params {
     int sync_bits;         /* 0: no search; else 8 .. 64 and a multiple of the bits per symbol */
     int sync_max_errors;   /* a hit is a Hamming distance <= this, 0 .. sync_bits - 1 (63 at most) */
     int hit_capacity;      /* items of the hit ring, a power of two >= 16; 0 = 256 */
-    int reserved_;
+    int sync_both;         /* 0: the word as given; 1: its inverse is searched as well (see above) */
 } rcf_slicer_params_t;
 int rcf_chan_slicer(rcf_t *h, int chan_id, const rcf_slicer_params_t *p);
 /* the stage's counters as of the last block; syncs the stream.  RCF_ESTATE without the stage (here and in the calls below) */
@@ -585,8 +591,8 @@ int rcf_chan_slicer_rings(rcf_t *h, int chan_id, void **word_ring, size_t *word_
  * index >= the slicer's n_hits at that moment: the call reads that counter and so synchronises the stream); calling again
  * starts it afresh.  It goes when the slicer goes: slicer attached again or switched off, its source loop attached again or
  * switched off, channel closed.
- * RCF_ESTATE: the channel has no slicer in RCF_SLICE_FSK4 mode that searches a 48-bit sync word; RCF_EINVAL: capacity not
- * 0 or a power of two >= 16 (at most 2^20); RCF_ENOCHAN: no such channel. */
+ * RCF_ESTATE: the channel has no slicer in RCF_SLICE_FSK4 mode that searches a 48-bit sync word, or that slicer searches both
+ * polarities (sync_both = 1); RCF_EINVAL: capacity not 0 or a power of two >= 16 (at most 2^20); RCF_ENOCHAN: no such channel. */
 typedef struct rcf_tsbk_params {
     int capacity;          /* records of the ring, a power of two >= 16; 0 = 256 */
     int reserved_[3];
@@ -603,6 +609,71 @@ int rcf_chan_tsbk_state(rcf_t *h, int chan_id, rcf_tsbk_state_t *out);
 int64_t rcf_chan_read_tsbk(rcf_t *h, int chan_id, uint32_t *out, size_t max_records);
 /* device pointer of the record ring and its capacity in records (zero-copy): record i lives at word 8 (i & (capacity - 1)) */
 int rcf_chan_tsbk_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity);
+/* EDACS control frames behind a slicer: what the reference's consumer does per 288-bit frame of a control channel in Python
+ * strings (edacs_control_demod.py: get_next_frame 396-430, packet_framer 373-395, bch_decode 451-518, message_election
+ * 172-189), as one more optional stage per channel on the GPU.  It applies to a slicer in RCF_SLICE_BINARY mode that searches
+ * a 48-bit sync word, with sync_both 0 or 1.  It reads the slicer's own two streams and writes a third, the counted stream
+ * RCF_HARD_EDACS of 32-byte records, one per frame: a consumer takes the two elected 40-bit messages instead of every word
+ * of the bit stream.  All of it is integer work: the records are exactly what the rules below give for the words and hits the
+ * slicer's readers deliver.  (No parsing of a message's fields.)
+ * Frames.  A hit item gives k, the last bit of the sync word (widened against n_symbols as above); the frame starts at bit
+ * s = k - 47 and its 240 data bits are the stream bits s + 48 .. s + 287.  Hits are taken in order; a hit is ACCEPTED if
+ * k >= k_last_accepted + 288 (buf = buf[find + 288:]), the first one the stage considers always.  An accepted hit is DECIDED
+ * in the first block after which the slicer's whole words hold the frame, 32 n_words >= s + 288.  A frame is never shortened,
+ * so later hits cannot matter and the records do not depend on how the input was cut into blocks.  A hit is INVERTED if the
+ * slicer searches both polarities and the item's dist > 24; all 240 bits of an inverted frame are inverted first.
+ * Copies.  Copy c (0 .. 5) is the frame's data bits 40 c .. 40 c + 39; the copies 1 and 4 are inverted (packet_framer).
+ * BCH(48,36) over GF(64), alpha^6 = alpha + 1 (the reference's _GF_ALPHA / _GF_IDX).  Per copy the received polynomial has
+ * coefficient j = copy bit 39 - j for j = 0 .. 39 and 0 for j = 40 .. 62 (eight zero colour bits stand in front of the copy).
+ * S_i = xor over the set j of alpha^(i j mod 63), i = 1, 3 (S2 and S4 are S1^2 and S1^4 and decide nothing).
+ *     S1 = 0, S3 = 0      the copy stands
+ *     S1 = 0, S3 != 0     the copy stands as well, uncorrected and valid: the reference's fall-through (76 of 3000 words with
+ *                         three errors come back as received), reproduced here
+ *     S1 != 0, S3 = S1^3  one error at position p = log S1
+ *     otherwise           aux = S1^3 ^ S3, e1 = (log S1^2 - log aux) mod 63, e2 = (log S1 - log aux) mod 63; the positions are
+ *                         i % 63 for every i in 1 .. 63 with 1 ^ alpha^((e1 + i) % 63) ^ alpha^((e2 + 2 i) % 63) = 0; the copy
+ *                         FAILS unless exactly two positions result
+ * The copy FAILS if any position is > 47.  Positions 40 .. 47 (the colour bits) are accepted and change none of the 40 bits;
+ * a position p in 0 .. 39 flips copy bit 39 - p.
+ * Election (message_election), per message -- m1 of the copies 0 .. 2, m2 of the copies 3 .. 5 -- over the corrected copies:
+ * none decoded: no message; exactly one decoded: that one; otherwise the first value that two decoded copies share, else no
+ * message.  With esk != 0 the first four bits of an elected message are or-ed with 0xA.
+ * Records, 8 uint32 each, in increasing k:
+ *     word 0    bit 0 inverted, bit 1 m1 present, bit 2 m2 present, bits 4-9 the hit's distance from the polarity it matched,
+ *               bits 10-21 two bits per copy (copy c in the bits 10 + 2 c): 0 clean or stands, 1 one position, 2 two
+ *               positions, 3 failed
+ *     word 1    the low 32 bits of the widened k
+ *     word 2-3  the 40 bits of m1, the first bit highest, bytes in memory order (the word ring's rule: a uint8 view is the
+ *               5 octets), the rest 0; all 0 when absent
+ *     word 4-5  m2 likewise
+ *     word 6-7  0
+ * Lost: hits that left the hit ring before they were examined, and frames whose first word the word ring had overwritten
+ * when they were decided, are skipped and counted (n_lost); a lost frame still counts as accepted.
+ * Departure: get_next_frame searches its whole string buffer for the inverted word first and only then for the upright one;
+ * the stage takes the hits in stream order.  On a stream of one polarity the two agree.
+ * p == NULL switches the stage off.  It applies from the next block on and considers only hits appended after the call (hit
+ * index >= the slicer's n_hits at that moment: the call reads that counter and so synchronises the stream); calling again
+ * starts it afresh.  It goes when the slicer goes: slicer attached again or switched off, its source loop attached again or
+ * switched off, channel closed.  A slicer carries this stage or the TSBK stage, by its mode.
+ * RCF_ESTATE: the channel has no slicer in RCF_SLICE_BINARY mode that searches a 48-bit sync word; RCF_EINVAL: capacity not
+ * 0 or a power of two >= 16 (at most 2^20); RCF_ENOCHAN: no such channel. */
+typedef struct rcf_edacs_params {
+    int capacity;          /* records of the ring, a power of two >= 16; 0 = 256 */
+    int esk;               /* != 0: extended addressing, the first four bits of every elected message |= 0xA */
+    int reserved_[2];
+} rcf_edacs_params_t;
+int rcf_chan_edacs(rcf_t *h, int chan_id, const rcf_edacs_params_t *p);
+/* the stage's counters as of the last block; syncs the stream.  RCF_ESTATE without the stage (here and in the calls below) */
+typedef struct rcf_edacs_state {
+    int64_t n_records, n_frames, n_msgs, n_msgs_none, n_lost;   /* records written, frames accepted (decided or lost), messages elected, messages without a result, hits and frames lost */
+} rcf_edacs_state_t;
+int rcf_chan_edacs_state(rcf_t *h, int chan_id, rcf_edacs_state_t *out);
+/* unread records, oldest first: out = uint32[max_records][8] (one round trip); RCF_HARD_EDACS names the stream to
+ * rcf_chan_read_many and rcf_group_read_many (out = uint32[n_chans][cap_each][8]); the pump does not deliver it */
+#define RCF_HARD_EDACS   49
+int64_t rcf_chan_read_edacs(rcf_t *h, int chan_id, uint32_t *out, size_t max_records);
+/* device pointer of the record ring and its capacity in records (zero-copy): record i lives at word 8 (i & (capacity - 1)) */
+int rcf_chan_edacs_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity);
 /* drift probe of p25_control_demod.py:123-127: moving_average_ff(window, 1) * (1/window) of the
  * discriminator output (window = 10000 there) == mean of gain*fm over the last `window` samples; this is
  * the value demod_watcher hands to frontend_connector.report_offset */

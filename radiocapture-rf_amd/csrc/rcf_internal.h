@@ -349,6 +349,7 @@ struct SliceLaunch {
     int32_t sync_bits;       // 0: no search
     int32_t sync_max_errors;
     float levels[3];         // bps 2: the decision levels (the fourth of rcf_slicer_params_t decides nothing)
+    int32_t sync_both;       // 1: a window within sync_max_errors of the inverted word is a hit too
 };
 void launch_slice(const SliceLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
 // P25 trunking blocks behind a slicer (tsbk.hip; procTSDU of the reference: status symbols, NID, deinterleave, rate-1/2
@@ -369,6 +370,26 @@ struct TsbkLaunch {
     int32_t n_k;             // the slicer's n_k of this block: at most that many new symbols, and so new hits
 };
 void launch_tsbk(const TsbkLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
+// EDACS control frames behind a slicer (edacs.hip; get_next_frame, packet_framer, bch_decode, message_election of the
+// reference: six 40-bit copies per frame, BCH(48,36) over GF(64), two of three; definition: include/rcf.h at rcf_chan_edacs).
+// per-channel running state, device resident, owned by edacs_kernel
+struct EdacsState {
+    int64_t n_records;       // records written so far (record i at rec_ring[(i & rec_mask) * 8])
+    int64_t n_frames, n_msgs, n_msgs_none, n_lost;
+    int64_t next_hit;        // the first hit of the slicer's stream that is neither rejected nor decided
+    int64_t k_last;          // the last accepted hit's k
+};
+constexpr uint32_t kEdacsFlagBoth = 1u, kEdacsFlagEsk = 2u;   // EdacsLaunch::flags: the slicer's sync_both, the stage's esk
+struct EdacsLaunch {
+    const SliceState *src;   // the slicer's counters (device)
+    const uint32_t *word_ring, *hit_ring;    // the slicer's two rings
+    EdacsState *st;
+    uint32_t *rec_ring;
+    uint32_t word_mask, hit_mask, rec_mask;
+    int32_t n_k;             // the slicer's n_k of this block: at most that many new symbols, and so new hits
+    uint32_t flags;
+};
+void launch_edacs(const EdacsLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
 // mean of gain * fm over the last `window` samples ending at n_end (exclusive), one workgroup
 void launch_fm_level(const float *fm_ring, int64_t n_end, int window, float gain, uint64_t ring_mask, float *d_out,
                      hipStream_t s);

@@ -359,6 +359,11 @@ int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c)
             tr.n_k = rec.n_k;
             bp.tails.tsf.add(tr);
         }
+        if (rec.n_k > 0 && c->slicer->edacs) {
+            EdacsLaunch er = c->slicer->edacs->rec;
+            er.n_k = rec.n_k;
+            bp.tails.edf.add(er);
+        }
     }
     if (c->audio && s.a_n > 0) {
         AudioLaunch al = c->audio->rec;

@@ -17,8 +17,9 @@ void counted_row(Stream *s, const void *ring, int64_t *cursor, const int64_t *co
     s->interp = (uint32_t)interp; s->decim = (uint32_t)decim;
 }
 template <class L> void loop_row(L *l, Stream *s) { if (l) counted_row(s, l->ring(), &l->rd, static_cast<const int64_t *>(l->counters()), l->serial); }
-// ring, reader and counter of every row of kStreams, in its order; a row that leaves the ring null is refused
-void (*const kRows[kStreamKinds])(Chan *, Stream *) = {
+// ring, reader and counter of every row of kStreams and of the readers' rows behind it, in their order; a row that leaves the
+// ring null is refused
+void (*const kRows[kReadKinds])(Chan *, Stream *) = {
     [](Chan *c, Stream *s) { if (!c->fm_only) plain_row(c, s, c->d_iq, &c->rd_iq); },
     [](Chan *c, Stream *s) { plain_row(c, s, c->d_fm, &c->rd_fm); },
     [](Chan *c, Stream *s) { if (c->agc) plain_row(c, s, c->agc->rec.agc_ring, &c->agc->rd); },
@@ -30,15 +31,16 @@ void (*const kRows[kStreamKinds])(Chan *, Stream *) = {
     [](Chan *c, Stream *s) { if (Chan::Slicer *l = c->slicer.get()) counted_row(s, l->rec.word_ring, &l->rd_words, &l->rec.st->n_words, 0); },
     [](Chan *c, Stream *s) { if (Chan::Slicer *l = c->slicer.get()) { counted_row(s, l->rec.hit_ring, &l->rd_hits, &l->rec.st->n_hits, 0); s->cap = l->hit_cap; } },
     [](Chan *c, Stream *s) { if (Chan::Slicer::Tsbk *t = c->slicer ? c->slicer->tsbk.get() : nullptr) { counted_row(s, t->rec.rec_ring, &t->rd, &t->rec.st->n_records, 0); s->cap = t->cap; } },
+    [](Chan *c, Stream *s) { if (Chan::Slicer::Edacs *t = c->slicer ? c->slicer->edacs.get() : nullptr) { counted_row(s, t->rec.rec_ring, &t->rd, &t->rec.st->n_records, 0); s->cap = t->cap; } },
 };
 
 }  // namespace
 
 int chan_stream(rcf_t *h, Chan *c, int kind, Stream *s)
 {
-    *s = Stream{h, nullptr, kStreams[kind].item_w, 0u, (uint32_t)h->out_cap};
+    *s = Stream{h, nullptr, read_row(kind).item_w, 0u, (uint32_t)h->out_cap};
     kRows[kind](c, s);
-    if (!s->ring) { set_error(kStreams[kind].refusal, c->id); return RCF_ESTATE; }
+    if (!s->ring) { set_error(read_row(kind).refusal, c->id); return RCF_ESTATE; }
     return RCF_OK;
 }
 
@@ -181,8 +183,8 @@ static void chan_entry(rcf_t *h, int chan_id, int kind, float gain, void *out, s
 int read_many(PinnedStage &stage, hipStream_t stream, rcf_t *const *hs, size_t n_hs, const int *ms, const int *chan_ids, int n,
               int what, float gain, void *out, size_t cap_each, int64_t *counts)
 {
-    const int kind = stream_kind(what);
-    const size_t row = cap_each * kStreams[kind].item_w * 4;
+    const int kind = read_kind(what);
+    const size_t row = cap_each * read_row(kind).item_w * 4;
     std::vector<ReadEntry> es((size_t)n);
     for (int i = 0; i < n; ++i) {
         const int m = ms ? ms[i] : 0;
@@ -206,7 +208,7 @@ static int64_t chan_read_one(rcf_t *h, int chan_id, int what, float gain, void *
     if (set_dev(h)) return RCF_EHIP;
     int64_t n = 0;
     ReadEntry e;
-    chan_entry(h, chan_id, stream_kind(what), gain, out, max_items, &n, &e);
+    chan_entry(h, chan_id, read_kind(what), gain, out, max_items, &n, &e);
     return e.s.ring ? read_one(h, e.s, e.gain, out, max_items) : n;
 }
 
@@ -221,11 +223,12 @@ int64_t rcf_chan_read_audio(rcf_t *h, int chan_id, float *out, size_t n) { retur
 int64_t rcf_chan_read_hard(rcf_t *h, int chan_id, uint32_t *out, size_t n) { return chan_read_one(h, chan_id, RCF_HARD_BITS, 1.0f, out, n); }
 int64_t rcf_chan_read_sync(rcf_t *h, int chan_id, uint32_t *out, size_t n) { return chan_read_one(h, chan_id, RCF_HARD_SYNC, 1.0f, out, n); }
 int64_t rcf_chan_read_tsbk(rcf_t *h, int chan_id, uint32_t *out, size_t n) { return chan_read_one(h, chan_id, RCF_HARD_TSBK, 1.0f, out, n); }
+int64_t rcf_chan_read_edacs(rcf_t *h, int chan_id, uint32_t *out, size_t n) { return chan_read_one(h, chan_id, RCF_HARD_EDACS, 1.0f, out, n); }
 
 int rcf_chan_read_many(rcf_t *h, int what, const int *chan_ids, int n_chans, float gain, void *out, size_t cap_each,
                        int64_t *counts)
 {
-    if (!h || !chan_ids || !out || !counts || n_chans < 0 || stream_kind(what) < 0) {
+    if (!h || !chan_ids || !out || !counts || n_chans < 0 || read_kind(what) < 0) {
         set_error("bad batched read arguments");
         return RCF_EINVAL;
     }
@@ -277,6 +280,16 @@ int rcf_chan_tsbk_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity)
     FIND_CHAN(h, chan_id, c);
     if (!c->slicer || !c->slicer->tsbk) { set_error(kStreams[kTsbk].refusal, chan_id); return RCF_ESTATE; }   // (closed in between)
     if (capacity) *capacity = c->slicer->tsbk->cap;
+    return RCF_OK;
+}
+int rcf_chan_edacs_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity)
+{
+    const int rc = chan_rings(h, chan_id, kEdacs, true, rec_ring, nullptr, nullptr);
+    if (rc != RCF_OK) return rc;
+    std::lock_guard<std::mutex> g(h->mu);
+    FIND_CHAN(h, chan_id, c);
+    if (!c->slicer || !c->slicer->edacs) { set_error(read_row(kEdacs).refusal, chan_id); return RCF_ESTATE; }   // (closed in between)
+    if (capacity) *capacity = c->slicer->edacs->cap;
     return RCF_OK;
 }
 

@@ -1,6 +1,6 @@
 // rcf_stage.cpp -- the optional stages behind a channel's rings (the records of Chan, rcf_state.h): the P25 symbol filter,
 // the feed-forward AGC, the SmartNet / EDACS symbol clock, the P25 CQPSK Gardner / Costas loop, the P25 C4FM symbol loop and
-// the analog voice chain, the slicer behind one of the loops and the P25 trunking stage behind the slicer.
+// the analog voice chain, the slicer behind one of the loops and the P25 trunking stage or the EDACS control-frame stage behind the slicer.
 // Attach, off, and what they produced.
 // An attach function allocates into Fresh<> holders and builds the new record completely; only then is it swapped into
 // the channel and the old one released.  A HIP call that fails before that leaves the channel as it was.
@@ -10,13 +10,15 @@
 #define RCF_DEVFN static inline
 #define RCF_DEVCONST static const
 #include "tsbk_core.hpp"       // (kTsbkNoFrame, kTsbkRecWords)
+#include "edacs_core.hpp"      // (kEdacsNoFrame, kEdacsRecWords; slice_sync_both_ok of slice_core.hpp)
 
 namespace rcfx {
 
 void Chan::Sym::release(rcf_t *h) { bury(h, rec.sym_ring); bury(h, const_cast<float *>(rec.taps)); rec.sym_ring = nullptr; rec.taps = nullptr; }
 void Chan::Agc::release(rcf_t *h) { bury(h, rec.agc_ring); rec.agc_ring = nullptr; }
 void Chan::Slicer::release_tsbk(rcf_t *h) { if (tsbk) { bury(h, tsbk->rec.rec_ring); tsbk.reset(); } }     // one allocation
-void Chan::Slicer::release(rcf_t *h) { release_tsbk(h); bury(h, rec.word_ring); rec = SliceLaunch{}; }     // one allocation; the TSBK stage goes with its slicer
+void Chan::Slicer::release_edacs(rcf_t *h) { if (edacs) { bury(h, edacs->rec.rec_ring); edacs.reset(); } }   // one allocation
+void Chan::Slicer::release(rcf_t *h) { release_tsbk(h); release_edacs(h); bury(h, rec.word_ring); rec = SliceLaunch{}; }     // one allocation; the TSBK / EDACS stage goes with its slicer
 void Chan::Audio::release(rcf_t *h) { bury(h, rec.st); bury(h, rec.a_ring); bury(h, const_cast<float *>(rec.lpf)); rec = AudioLaunch{}; }
 
 }  // namespace rcfx
@@ -296,6 +298,10 @@ int rcf_chan_slicer(rcf_t *h, int chan_id, const rcf_slicer_params_t *p)
             set_error("slicer: sync_max_errors %d outside 0 .. sync_bits - 1", p->sync_max_errors);
             return RCF_EINVAL;
         }
+        if (!slice_sync_both_ok(p->sync_bits, p->sync_max_errors, p->sync_both)) {
+            set_error("slicer: sync_both %d is not 0 or 1, or 2 x sync_max_errors %d reaches sync_bits %d", p->sync_both, p->sync_max_errors, p->sync_bits);
+            return RCF_EINVAL;
+        }
         if (p->hit_capacity) hit_cap = p->hit_capacity;
         if (hit_cap < 16 || hit_cap > (1 << 26) || (hit_cap & (hit_cap - 1))) {
             set_error("slicer: hit_capacity %d is not a power of two 16 .. 2^26", p->hit_capacity);
@@ -322,7 +328,7 @@ int rcf_chan_slicer(rcf_t *h, int chan_id, const rcf_slicer_params_t *p)
     if (rc != RCF_OK) return rc;
     r.bps = bps;
     r.sync_word = p->sync_bits >= 64 ? p->sync_word : p->sync_word & ((1ull << p->sync_bits) - 1);
-    r.sync_bits = p->sync_bits; r.sync_max_errors = p->sync_max_errors;
+    r.sync_bits = p->sync_bits; r.sync_max_errors = p->sync_max_errors; r.sync_both = p->sync_both;
     for (int i = 0; i < 3; ++i) r.levels[i] = p->levels[i];
     r.soft_mask = r.word_mask = (uint32_t)(h->out_cap - 1);
     r.hit_mask = (uint32_t)hit_cap - 1;
@@ -374,8 +380,8 @@ int rcf_chan_tsbk(rcf_t *h, int chan_id, const rcf_tsbk_params_t *p)
         if (c->slicer && c->slicer->tsbk) { c->slicer->release_tsbk(h); ++h->chans_epoch; }
         return RCF_OK;
     }
-    if (!c->slicer || c->slicer->rec.bps != 2 || c->slicer->rec.sync_bits != 48) {
-        set_error("channel %d has no slicer in RCF_SLICE_FSK4 mode that searches a 48-bit sync word", chan_id);
+    if (!c->slicer || c->slicer->rec.bps != 2 || c->slicer->rec.sync_bits != 48 || c->slicer->rec.sync_both) {
+        set_error("channel %d has no slicer in RCF_SLICE_FSK4 mode that searches a 48-bit sync word in one polarity", chan_id);
         return RCF_ESTATE;
     }
     const SliceLaunch &sl = c->slicer->rec;
@@ -417,6 +423,69 @@ int rcf_chan_tsbk_state(rcf_t *h, int chan_id, rcf_tsbk_state_t *out)
     const int rc = stage_state(h, c->slicer->tsbk->rec.st, &st, offsetof(TsbkState, next_hit));
     if (rc != RCF_OK) return rc;
     out->n_records = st.n_records; out->n_frames = st.n_frames; out->n_blocks = st.n_blocks; out->n_crc_bad = st.n_crc_bad; out->n_lost = st.n_lost;
+    return RCF_OK;
+}
+
+// ---- EDACS control frames behind the slicer (edacs.hip)
+int rcf_chan_edacs(rcf_t *h, int chan_id, const rcf_edacs_params_t *p)
+{
+    if (!h) return RCF_EINVAL;
+    int cap = 256;
+    if (p) {
+        if (p->capacity) cap = p->capacity;
+        if (cap < 16 || cap > (1 << 20) || (cap & (cap - 1))) { set_error("EDACS stage: capacity %d is not a power of two 16 .. 2^20", p->capacity); return RCF_EINVAL; }
+    }
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!p) {
+        if (c->slicer && c->slicer->edacs) { c->slicer->release_edacs(h); ++h->chans_epoch; }
+        return RCF_OK;
+    }
+    if (!c->slicer || c->slicer->rec.bps != 1 || c->slicer->rec.sync_bits != kEdacsSyncBits) {
+        set_error("channel %d has no slicer in RCF_SLICE_BINARY mode that searches a 48-bit sync word", chan_id);
+        return RCF_ESTATE;
+    }
+    const SliceLaunch &sl = c->slicer->rec;
+    std::unique_ptr<Chan::Slicer::Edacs> k(new Chan::Slicer::Edacs);
+    EdacsLaunch &r = k->rec;
+    r.src = sl.st;
+    r.word_ring = sl.word_ring; r.hit_ring = sl.hit_ring;
+    r.word_mask = sl.word_mask; r.hit_mask = sl.hit_mask; r.rec_mask = (uint32_t)cap - 1;
+    r.flags = (sl.sync_both ? kEdacsFlagBoth : 0u) | (p->esk ? kEdacsFlagEsk : 0u);
+    k->cap = (uint32_t)cap;
+    // the stage's first hit: the slicer's count as of everything queued (one round trip)
+    SliceState now{};
+    const int rc = stage_state(h, sl.st, &now, offsetof(SliceState, partial));
+    if (rc != RCF_OK) return rc;
+    EdacsState st0{};
+    st0.next_hit = now.n_hits;
+    st0.k_last = kEdacsNoFrame;
+    constexpr size_t kStateWords = 256 / sizeof(uint32_t);
+    static_assert(sizeof(EdacsState) <= 256, "the state's slot");
+    const size_t state_at = (size_t)cap * kEdacsRecWords;                  // in words (cap >= 16: the record's 64-bit fields are aligned)
+    Fresh<uint32_t> fresh;
+    RCF_HIP(fresh.alloc(state_at + kStateWords));
+    if (!hip_ok(hipMemcpy(fresh.p + state_at, &st0, sizeof(st0), hipMemcpyHostToDevice), "hipMemcpy(EDACS state)")) return RCF_EHIP;
+    r.rec_ring = fresh.take();
+    r.st = reinterpret_cast<EdacsState *>(r.rec_ring + state_at);
+    c->slicer->release_edacs(h);
+    c->slicer->edacs = std::move(k);
+    ++h->chans_epoch;
+    return RCF_OK;
+}
+
+int rcf_chan_edacs_state(rcf_t *h, int chan_id, rcf_edacs_state_t *out)
+{
+    if (!h || !out) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!c->slicer || !c->slicer->edacs) { set_error("channel %d has no EDACS stage (rcf_chan_edacs)", chan_id); return RCF_ESTATE; }
+    EdacsState st{};                    // (its five counters)
+    const int rc = stage_state(h, c->slicer->edacs->rec.st, &st, offsetof(EdacsState, next_hit));
+    if (rc != RCF_OK) return rc;
+    out->n_records = st.n_records; out->n_frames = st.n_frames; out->n_msgs = st.n_msgs; out->n_msgs_none = st.n_msgs_none; out->n_lost = st.n_lost;
     return RCF_OK;
 }
 

@@ -38,6 +38,25 @@ constexpr int stream_kind(int what)
     return -1;
 }
 static_assert(stream_kind(RCF_READ_AUDIO) == kAudio && stream_kind(RCF_HARD_SYNC) == kHardSync && stream_kind(RCF_HARD_TSBK) == kTsbk, "the rows stand in the enum's order");
+// That table and stream_kind are also the pump's: its two entry points take a `what` through them and refuse what they do not
+// find or find unpumped, and its slots hold a row's index.  A stream that only the readers carry -- none of the pump's code
+// knows its items -- is added BEHIND the table, so that nothing the pump or a consumer of the table compiled against moves:
+// the readers' kinds go on where the table's end, read_kind / read_row are their stream_kind / kStreams.
+enum : int { kEdacs = kStreamKinds, kReadKinds };
+constexpr StreamKind kReadOnlyStreams[kReadKinds - kStreamKinds] = {
+    {RCF_HARD_EDACS,  8, true,  true,  false, "channel %d has no EDACS stage (rcf_chan_edacs)"},
+};
+constexpr const StreamKind &read_row(int kind) { return kind < kStreamKinds ? kStreams[kind] : kReadOnlyStreams[kind - kStreamKinds]; }
+// the readers' kind of `what`: a row of the table, or one behind it; -1: no such stream
+constexpr int read_kind(int what)
+{
+    if (stream_kind(what) >= 0) return stream_kind(what);
+    for (int k = kStreamKinds; k < kReadKinds; ++k)
+        if (read_row(k).what == what) return k;
+    return -1;
+}
+static_assert(read_kind(RCF_HARD_EDACS) == kEdacs && stream_kind(RCF_HARD_EDACS) == -1 && read_kind(RCF_HARD_TSBK) == kTsbk && !read_row(kEdacs).pumped,
+              "the readers' rows go on behind the table; the pump finds none of them");
 
 // A reader that has fallen more than a ring of `cap` items behind lost what the ring overwrote: its cursor is raised to the
 // oldest item the ring still holds (the ring holds the cap items before `newest`).  Returns how many items [*cursor, end) it

@@ -78,7 +78,7 @@ __global__ __launch_bounds__(64 * kSliceWaves) void slice_kernel(const SliceLaun
         // holds only the newest are stored (two lanes of one store never meet in a slot)
         if (L.sync_bits) {
             const int dist = slice_sync_dist(win, L.sync_word, L.sync_bits);
-            const bool hit = valid && k >= (int64_t)(sync_syms - 1) && dist <= L.sync_max_errors;
+            const bool hit = valid && k >= (int64_t)(sync_syms - 1) && slice_is_hit(dist, L.sync_bits, L.sync_max_errors, L.sync_both);
             const uint64_t hits = __ballot(hit);
             const int n_here = __popcll(hits), mine = __popcll(hits & below);
             if (hit && n_here - mine <= (int)L.hit_mask + 1)

@@ -93,6 +93,16 @@ RCF_DEVFN int slice_sync_dist(uint64_t window, uint64_t sync_word, int sync_bits
     const uint64_t m = sync_bits >= 64 ? ~0ull : (1ull << sync_bits) - 1;
     return slice_popcount64((window ^ sync_word) & m);
 }
+// The hit rule: within max_errors of the sync word, or -- sync_both -- of its inverse, whose distance is sync_bits - dist
+RCF_DEVFN bool slice_is_hit(int dist, int sync_bits, int max_errors, int sync_both)
+{
+    return dist <= max_errors || (sync_both && dist >= sync_bits - max_errors);
+}
+// ... and what makes the two polarities tell apart: the ranges 0 .. max_errors and sync_bits - max_errors .. sync_bits do not meet
+RCF_DEVFN bool slice_sync_both_ok(int sync_bits, int max_errors, int sync_both)
+{
+    return sync_both == 0 || (sync_both == 1 && sync_bits > 0 && 2 * max_errors < sync_bits);
+}
 // a hit's item in the hit ring
 RCF_DEVFN uint32_t slice_hit_item(int dist, int64_t k) { return ((uint32_t)dist << 26) | (uint32_t)((uint64_t)k & 0x3ffffffu); }
 

@@ -7,7 +7,8 @@
 The discriminator and the Mueller and Mueller clock run per channel on the GPU (rcf_chan_clock_mm): a demod reads soft
 symbols at 3600 or 9600 per second (chan_read_clock), slices and packs them (pack_bits) and does the packet framing -- or,
 with hard=True, lets the GPU slice, pack and look for the frame sync (rcf_chan_slicer) and reads packed bits and the places
-frames begin (chan_read_hard, chan_read_sync)."""
+frames begin (chan_read_hard, chan_read_sync).  For EDACS the GPU goes one step further with frames=True: framing, the BCH
+decode of the six copies and the election of the two messages (rcf_chan_edacs; chan_read_edacs, edacs_messages)."""
 import numpy as np
 
 from . import native
@@ -18,7 +19,7 @@ MU = 0.5
 GAIN_MU = 0.05
 OMEGA_RELATIVE_LIMIT = 0.005
 SMARTNET_SYNC, SMARTNET_SYNC_BITS = 0b10101100, 8      # moto_control_demod.py:216
-# edacs_control_demod.py:523; the inverted word stays the consumer's business
+# edacs_control_demod.py:523; the inverted word is searched as well with sync_both=1 (edacs_clock(frames=True))
 EDACS_SYNC, EDACS_SYNC_BITS = 0b010101010101010101010111000100100101010101010101, 48
 
 
@@ -31,13 +32,33 @@ def smartnet_clock(fe, cid, channel_rate=25000, symbol_rate=3600.0, hard=False):
         fe.chan_slicer(cid, native.READ_CLOCK, native.SLICE_BINARY, sync_word=SMARTNET_SYNC, sync_bits=SMARTNET_SYNC_BITS)
 
 
-def edacs_clock(fe, cid, receive_rate=25000, symbol_rate=9600.0, hard=False):
+def edacs_clock(fe, cid, receive_rate=25000, symbol_rate=9600.0, hard=False, frames=False, esk=False):
     """the same behind an EDACS control channel (edacs_control_demod.py:76,85: receive_rate = 2 x 12500, symbol_rate
     the system's, 9600 or 4800).  hard=True also attaches the slicer behind the clock: binary, exact matches of the
-    48-bit frame sync."""
+    48-bit frame sync.  With frames=True as well the slicer searches both polarities (get_next_frame accepts either) and the
+    EDACS stage sits behind it: chan_read_edacs gives a record per frame, edacs_messages the reference's strings; esk: the
+    system's extended-addressing flag."""
     fe.chan_clock_mm(cid, receive_rate / symbol_rate, GAIN_OMEGA, MU, GAIN_MU, OMEGA_RELATIVE_LIMIT, QUAD_GAIN)
     if hard:
-        fe.chan_slicer(cid, native.READ_CLOCK, native.SLICE_BINARY, sync_word=EDACS_SYNC, sync_bits=EDACS_SYNC_BITS)
+        fe.chan_slicer(cid, native.READ_CLOCK, native.SLICE_BINARY, sync_word=EDACS_SYNC, sync_bits=EDACS_SYNC_BITS,
+                       sync_both=1 if frames else 0)
+        if frames:
+            fe.chan_edacs(cid, esk=esk)
+
+
+def edacs_messages(records):
+    """records of the EDACS stage (Frontend.chan_read_edacs, native.EDACS_DTYPE) -> list of (k, inverted, m1, m2) in the
+    stream's order: k the low 32 bits of the sync word's last bit, m the 40-character bit string packet_framer returns for
+    the message, or -1 where the election gave none"""
+    records = np.asarray(records, dtype=native.EDACS_DTYPE)
+    f = native.edacs_fields(records)
+    out = []
+    for i in range(len(records)):
+        ms = []
+        for name, has in (("m1", f["has_m1"][i]), ("m2", f["has_m2"][i])):
+            ms.append("".join("{0:08b}".format(int(o)) for o in records[name][i][:5]) if has else -1)
+        out.append((int(records["k"][i]), bool(f["inverted"][i]), ms[0], ms[1]))
+    return out
 
 
 def pack_bits(soft, carry=None):

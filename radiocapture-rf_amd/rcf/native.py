@@ -39,6 +39,7 @@ SYMBOLS = [
     "rcf_chan_fsk4", "rcf_chan_fsk4_state", "rcf_chan_read_fsk4", "rcf_chan_fsk4_ring",
     "rcf_chan_slicer", "rcf_chan_slicer_state", "rcf_chan_read_hard", "rcf_chan_read_sync", "rcf_chan_slicer_rings",
     "rcf_chan_tsbk", "rcf_chan_tsbk_state", "rcf_chan_read_tsbk", "rcf_chan_tsbk_ring",
+    "rcf_chan_edacs", "rcf_chan_edacs_state", "rcf_chan_read_edacs", "rcf_chan_edacs_ring",
     "rcf_design_firdes", "rcf_design_optfir_low_pass", "rcf_design_fm_deemph", "rcf_design_resampler", "rcf_chan_audio_open",
     "rcf_chan_audio_close", "rcf_chan_audio_produced", "rcf_chan_read_audio",
     "rcf_host_alloc", "rcf_host_free", "rcf_comm_unique_id", "rcf_comm_init", "rcf_comm_destroy", "rcf_comm_size",
@@ -56,10 +57,15 @@ _STAGE_WHAT = {"sym": READ_SYM, "clock": READ_CLOCK, "costas": READ_COSTAS, "fsk
 HARD_BITS, HARD_SYNC = 32, 33
 # the stream of the TSBK stage behind a slicer (RCF_HARD_TSBK): records of 8 uint32, batched the same way
 HARD_TSBK = 48
-_HARD_WHAT = {"hard": HARD_BITS, "sync": HARD_SYNC, "tsbk": HARD_TSBK}
+# ... and of the EDACS stage (RCF_HARD_EDACS): records of 8 uint32 too, one per frame
+HARD_EDACS = 49
+_HARD_WHAT = {"hard": HARD_BITS, "sync": HARD_SYNC, "tsbk": HARD_TSBK, "edacs": HARD_EDACS}
 # a record of RCF_HARD_TSBK (rcf.h at rcf_chan_tsbk): word 0 (see tsbk_fields), the low 32 bits of k, the 12 decoded octets,
 # the NID's 8 octets, frame_dibits
 TSBK_DTYPE = np.dtype([("flags", "<u4"), ("k", "<u4"), ("octets", "u1", (12,)), ("nid", "u1", (8,)), ("frame_dibits", "<u4")])
+# a record of RCF_HARD_EDACS (rcf.h at rcf_chan_edacs): word 0 (see edacs_fields), the low 32 bits of k, the five octets of
+# m1 and of m2, each in a field of eight
+EDACS_DTYPE = np.dtype([("flags", "<u4"), ("k", "<u4"), ("m1", "u1", (8,)), ("m2", "u1", (8,)), ("zero", "<u4", (2,))])
 SLICE_BINARY, SLICE_FSK4 = 1, 2
 T_FIR, T_PFB, T_FIR_DERIVED, T_DISC, T_SCAN_FFT, T_SCAN_MOVSUM, T_HISTORY, T_FIR_MFMA, T_AUDIO, T_TAPS, T_CLOCK, T_COSTAS, T_FSK4, T_SLICE = range(14)
 
@@ -147,7 +153,7 @@ def fsk4_params_struct(sample_rate, symbol_rate, k_spread, k_timing, k_fine, k_c
 class SlicerParams(C.Structure):
     """rcf_slicer_params_t (include/rcf.h)"""
     _fields_ = [("source", C.c_int), ("mode", C.c_int), ("levels", C.c_float * 4), ("sync_word", C.c_uint64),
-                ("sync_bits", C.c_int), ("sync_max_errors", C.c_int), ("hit_capacity", C.c_int), ("reserved_", C.c_int)]
+                ("sync_bits", C.c_int), ("sync_max_errors", C.c_int), ("hit_capacity", C.c_int), ("sync_both", C.c_int)]
 
 
 class SlicerState(C.Structure):
@@ -172,6 +178,26 @@ def tsbk_fields(records):
     return dict(b=(f & 3).astype(np.uint8), crc_bad=((f >> 2) & 1).astype(np.uint8), next_bit=((f >> 3) & 1).astype(np.uint8),
                 n_inexact=((f >> 4) & 63).astype(np.uint8), dist=((f >> 10) & 63).astype(np.uint8),
                 duid=((f >> 16) & 15).astype(np.uint8), nac=(f >> 20).astype(np.uint16))
+
+
+class EdacsParams(C.Structure):
+    """rcf_edacs_params_t (include/rcf.h)"""
+    _fields_ = [("capacity", C.c_int), ("esk", C.c_int), ("reserved_", C.c_int * 2)]
+
+
+class EdacsState(C.Structure):
+    """rcf_edacs_state_t (include/rcf.h)"""
+    _fields_ = [("n_records", C.c_int64), ("n_frames", C.c_int64), ("n_msgs", C.c_int64), ("n_msgs_none", C.c_int64),
+                ("n_lost", C.c_int64)]
+
+
+def edacs_fields(records):
+    """word 0 of EDACS records taken apart -> dict of arrays: inverted, has_m1, has_m2, dist, status ([n, 6]: per copy 0 clean
+    or stands, 1 one position, 2 two positions, 3 failed)"""
+    f = np.asarray(records["flags"], dtype=np.uint32)
+    return dict(inverted=(f & 1).astype(np.uint8), has_m1=((f >> 1) & 1).astype(np.uint8), has_m2=((f >> 2) & 1).astype(np.uint8),
+                dist=((f >> 4) & 63).astype(np.uint8),
+                status=np.stack([((f >> (10 + 2 * c)) & 3).astype(np.uint8) for c in range(6)], axis=-1))
 
 
 def widen_hits(items, n_symbols):
@@ -275,6 +301,10 @@ def lib():
         "rcf_chan_tsbk_state": (C.c_int, [vp, C.c_int, C.POINTER(TsbkState)]),
         "rcf_chan_read_tsbk": (i64, [vp, C.c_int, C.POINTER(C.c_uint32), sz]),
         "rcf_chan_tsbk_ring": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]),
+        "rcf_chan_edacs": (C.c_int, [vp, C.c_int, C.POINTER(EdacsParams)]),
+        "rcf_chan_edacs_state": (C.c_int, [vp, C.c_int, C.POINTER(EdacsState)]),
+        "rcf_chan_read_edacs": (i64, [vp, C.c_int, C.POINTER(C.c_uint32), sz]),
+        "rcf_chan_edacs_ring": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]),
         "rcf_design_mmse_interpolator": (C.c_int, [C.c_int, C.c_int, C.c_double, fp, C.c_int]),
         "rcf_chan_fm_level": (C.c_int, [vp, C.c_int, C.c_float, C.c_int, fp]),
         "rcf_design_firdes": (C.c_int, [C.c_int] + [C.c_double] * 4 + [C.c_int, C.c_double, fp, C.c_int]),
@@ -362,7 +392,7 @@ def lib():
 def _read_what(what, stages=False):
     """the batched readers' and the pump's `what`: "iq", "agc", anything else the discriminator (as it always was).
     stages=True -- how every reader of this module calls it -- also names the stages' streams: "sym", "clock", "costas",
-    "fsk4", "audio", the slicer's "hard" and "sync" and the TSBK stage's "tsbk".  The one-argument form keeps its old answers ("sym" was never a
+    "fsk4", "audio", the slicer's "hard" and "sync", the TSBK stage's "tsbk" and the EDACS stage's "edacs".  The one-argument form keeps its old answers ("sym" was never a
     stream there: the discriminator)."""
     if stages and what in _STAGE_WHAT:
         return _STAGE_WHAT[what]
@@ -373,10 +403,12 @@ def _read_what(what, stages=False):
 
 def _read_dtype(what):
     """item type of stream `what` as the readers deliver it: cf32 for "iq" and "agc", uint32 for the slicer's "hard" and
-    "sync", TSBK_DTYPE for "tsbk", float32 for everything else"""
+    "sync", TSBK_DTYPE for "tsbk", EDACS_DTYPE for "edacs", float32 for everything else"""
     w = _read_what(what, True)
     if w == HARD_TSBK:
         return TSBK_DTYPE
+    if w == HARD_EDACS:
+        return EDACS_DTYPE
     return np.complex64 if w in (READ_IQ, READ_AGC) else np.uint32 if w in (HARD_BITS, HARD_SYNC) else np.float32
 
 
@@ -741,7 +773,7 @@ class Frontend:
         copies), None where the channel no longer exists (or lacks the stream).  what: "iq", "fm" (x gain), "agc", or a
         stage's stream -- "sym", "clock", "costas", "fsk4", "audio": float32, from where that stage's single reader stands --
         or the slicer's "hard" (packed words) / "sync" (hit items, see widen_hits): uint32 -- or the TSBK stage's "tsbk":
-        TSBK_DTYPE records"""
+        TSBK_DTYPE records -- or the EDACS stage's "edacs": EDACS_DTYPE records"""
         n = len(cids)
         dt = _read_dtype(what)
         if out is None:
@@ -879,11 +911,12 @@ class Frontend:
         return self._read_ring(lib().rcf_chan_read_fsk4, cid, max_symbols, np.float32)
 
     def chan_slicer(self, cid, source, mode=None, levels=(-2.0, 0.0, 2.0, 4.0), sync_word=0, sync_bits=0, sync_max_errors=0,
-                    hit_capacity=0):
+                    hit_capacity=0, sync_both=0):
         """hard decisions behind one of the channel's symbol loops (rcf_chan_slicer): source READ_CLOCK / READ_COSTAS /
         READ_FSK4, mode SLICE_BINARY (binary_slicer_fb) or SLICE_FSK4 (op25 fsk4_slicer_fb(levels)); packed MSB first as
         unpacked_to_packed_bb does, with a search for the low sync_bits bits of sync_word (hits: Hamming distance <=
-        sync_max_errors).  It starts at the loop's next symbol; source=None switches it off."""
+        sync_max_errors; with sync_both=1 also those within sync_max_errors of the inverted word, which carry dist >
+        sync_bits / 2).  It starts at the loop's next symbol; source=None switches it off."""
         if source is None:
             _check(lib().rcf_chan_slicer(self._h, cid, None))
             return
@@ -891,7 +924,7 @@ class Frontend:
         p.source, p.mode = int(source), int(mode)
         p.levels = (C.c_float * 4)(*[float(v) for v in levels])
         p.sync_word, p.sync_bits, p.sync_max_errors = int(sync_word), int(sync_bits), int(sync_max_errors)
-        p.hit_capacity = int(hit_capacity)
+        p.hit_capacity, p.sync_both = int(hit_capacity), int(sync_both)
         _check(lib().rcf_chan_slicer(self._h, cid, C.byref(p)))
 
     def chan_slicer_state(self, cid) -> dict:
@@ -946,6 +979,35 @@ class Frontend:
     def chan_tsbk_ring(self, cid):
         """(device pointer, capacity in records) of the stage's record ring (rcf_chan_tsbk_ring)"""
         return self._ring_of(lib().rcf_chan_tsbk_ring, cid)
+
+    def chan_edacs(self, cid, capacity=0, esk=False, on=True):
+        """EDACS control frames behind the channel's binary slicer (rcf_chan_edacs): frames from the sync hits of either
+        polarity, six copies per frame BCH-decoded and two messages elected on the GPU; records of EDACS_DTYPE in a ring of
+        `capacity` (0: 256); esk: extended addressing.  It considers the hits from now on; on=False switches it off."""
+        if not on:
+            _check(lib().rcf_chan_edacs(self._h, cid, None))
+            return
+        p = EdacsParams()
+        p.capacity, p.esk = int(capacity), int(bool(esk))
+        _check(lib().rcf_chan_edacs(self._h, cid, C.byref(p)))
+
+    def chan_edacs_state(self, cid) -> dict:
+        """n_records, n_frames, n_msgs, n_msgs_none, n_lost of the EDACS stage as of the last block (rcf_chan_edacs_state;
+        syncs the stream)"""
+        st = EdacsState()
+        _check(lib().rcf_chan_edacs_state(self._h, cid, C.byref(st)))
+        return _state_dict(st)
+
+    def chan_read_edacs(self, cid, max_records=1 << 12) -> np.ndarray:
+        """unread records of the EDACS stage, oldest first: a structured array of EDACS_DTYPE (edacs_fields takes `flags`
+        apart, rcf.control.edacs_messages gives the reference's strings)"""
+        out = np.empty(max_records, dtype=EDACS_DTYPE)
+        n = _check(lib().rcf_chan_read_edacs(self._h, cid, out.ctypes.data_as(C.POINTER(C.c_uint32)), max_records))
+        return out[:n].copy()
+
+    def chan_edacs_ring(self, cid):
+        """(device pointer, capacity in records) of the stage's record ring (rcf_chan_edacs_ring)"""
+        return self._ring_of(lib().rcf_chan_edacs_ring, cid)
 
     def chan_fsk4_ring(self, cid):
         """(device pointer, capacity) of the stage's float32 soft-symbol ring (rcf_chan_fsk4_ring)"""
