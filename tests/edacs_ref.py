@@ -108,11 +108,13 @@ def bits_of_words(words):
     return np.unpackbits(words if words.dtype == np.uint8 else words.astype("<u4").view(np.uint8))
 
 
-def run(words, k, dist, first_hit=0, launches=None, word_cap=None, hit_cap=None, sync_both=True, esk=False, base_words=0, base_hits=0):
+def run(words, k, dist, first_hit=0, launches=None, word_cap=None, hit_cap=None, sync_both=True, esk=False, base_words=0, base_hits=0,
+        frames=None):
     """-> (records, dict(n_records, n_frames, n_msgs, n_msgs_none, n_lost)).  words, k, dist: the slicer's streams from its
     start; first_hit: the slicer's n_hits when the stage was attached; launches: [(n_words, n_hits)] after each block (default:
     one, at the end); word_cap / hit_cap: the rings' capacities (default: nothing is ever overwritten); base_words / base_hits:
-    the index of the first word / hit given (k, first_hit and the launches count from the slicer's start)"""
+    the index of the first word / hit given (k, first_hit and the launches count from the slicer's start); frames: a list that
+    takes every decided frame's 240 data bits, polarity applied, in the records' order (for census)"""
     bits = bits_of_words(words)
     k = [None] * base_hits + [int(v) for v in k]
     dist = [None] * base_hits + list(dist)
@@ -140,6 +142,8 @@ def run(words, k, dist, first_hit=0, launches=None, word_cap=None, hit_cap=None,
             raw = int(dist[i - 1])
             inverted = bool(sync_both) and raw > 24
             data = bits[s + 48 - 32 * base_words:s + 288 - 32 * base_words] ^ (1 if inverted else 0)
+            if frames is not None:
+                frames.append(data)
             statuses, m1, m2 = decode_frame(data, esk)
             out.append(record(k_last, inverted, 48 - raw if inverted else raw, statuses, m1, m2))
             st["n_msgs"] += (m1 is not None) + (m2 is not None)
@@ -186,3 +190,109 @@ def frame(m1, m2, inverted=False):
 
 def bitstr(m):
     return -1 if m is None else "".join(str(int(b)) for b in m)
+
+
+# ---- designed input: copies with chosen error patterns, so that the decoder's correcting paths are walked on purpose
+def flip_patterns():
+    """-> (the 40 single flips, the 780 pairs of flips) of a 40-bit copy, each a tuple of copy bits (0: the first bit)"""
+    return [(a,) for a in range(40)], [(a, b) for a in range(40) for b in range(a + 1, 40)]
+
+
+def designed_bits(patterns, seed, inverted=False):
+    """600 bits for the clock to settle, then back-to-back frames of two random messages each, copy slot n % 6 of frame n // 6
+    carrying patterns[n] (a tuple of copy bits to flip; the slots past the last pattern stay clean), 420 bits behind ->
+    (bits, per frame (m1, m2) as sent, the frames' starts, per frame the six patterns)"""
+    rng = np.random.default_rng(seed)
+    patterns = list(patterns) + [()] * (-len(patterns) % 6)
+    parts, sent, starts, flips = [rng.integers(0, 2, 600).astype(np.uint8)], [], [], []
+    for n in range(0, len(patterns), 6):
+        m1, m2 = encode(rng.integers(0, 2, 28)), encode(rng.integers(0, 2, 28))
+        f = frame(m1, m2)
+        for c in range(6):
+            for b in patterns[n + c]:
+                f[48 + 40 * c + b] ^= 1
+        starts.append(600 + 288 * (n // 6)); sent.append((bitstr(m1), bitstr(m2))); flips.append(patterns[n:n + 6]); parts.append(f)
+    parts.append(rng.integers(0, 2, 420).astype(np.uint8))
+    bits = np.concatenate(parts)
+    return (bits ^ 1 if inverted else bits), sent, starts, flips
+
+
+CLASSES = ("fails", "miscorrects", "stands", "colour", "beyond")
+
+
+def pattern_classes(pattern):
+    """what the decoder makes of a valid copy with these copy bits flipped (the syndromes are the flips' alone) -> set of:
+    fails (status 3), miscorrects (status 2, and not back to what was sent), stands (S1 = 0, S3 != 0: status 0, uncorrected),
+    colour (a position in 40 .. 47: accepted, no bit changed), beyond (a position > 47: fails)"""
+    js = sorted(39 - b for b in pattern)
+    s1, s3 = syndromes(js)
+    status, pos = solve(s1, s3)
+    out = set()
+    if status == 3:
+        out.add("fails")
+        if any(p > 47 for p in pos):
+            out.add("beyond")
+    if status == 2 and sorted(pos) != js:
+        out.add("miscorrects")
+    if s1 == 0 and s3 != 0:
+        out.add("stands")
+    if status in (1, 2) and any(40 <= p <= 47 for p in pos):
+        out.add("colour")
+    return out
+
+
+def class_patterns(seed=3, each=10, limit=200000):
+    """random 3- and 4-flip patterns, searched until every class of CLASSES has `each` of them (at most `limit` candidates) ->
+    {class: [patterns]}"""
+    rng = np.random.default_rng(seed)
+    found = {c: [] for c in CLASSES}
+    for n in range(limit):
+        p = tuple(sorted(int(b) for b in rng.choice(40, 3 + n % 2, replace=False)))
+        for c in pattern_classes(p):
+            if len(found[c]) < each and p not in found[c]:
+                found[c].append(p)
+        if all(len(v) >= each for v in found.values()):
+            break
+    return found
+
+
+def designed_classes(seed=3):
+    """the patterns of the second designed carrier -> (patterns for designed_bits, {class: how many of them}).  Every class
+    pattern sits beside two clean copies of its message, its slot rotating through the six; then the election's cases, two
+    frames each (m1 and m2 alike): one of three copies decoded; two decoded that disagree; two that agree against a third"""
+    found = class_patterns(seed)
+    every = [p for c in CLASSES for p in found[c]]
+    out = []
+    for n, p in enumerate(every):
+        group = [(), (), ()]
+        group[n % 3] = p
+        out += group
+    out += [()] * (-len(out) % 6)
+    fails, wrong = found["fails"], found["miscorrects"]
+    for n in range(2):
+        out += [fails[0], fails[1], (), (), fails[2], fails[3]]                     # one decoded
+        out += [fails[4], wrong[0], (), wrong[1], (), fails[5]]                     # two decoded, different values
+        out += [wrong[2], (), (5, 17), (30,), wrong[3], ()]                         # three decoded, two agree
+    return out, {c: len(found[c]) for c in CLASSES}
+
+
+def census(frames, sent):
+    """frames: per decided frame its 240 data bits, polarity applied (run(frames=) collects them); sent: per frame the two
+    messages sent (bit strings) -> {class: copies of it met} and {"one", "differ", "outvoted": message groups of that kind}"""
+    seen = {c: 0 for c in CLASSES}
+    seen.update(one=0, differ=0, outvoted=0)
+    for data, ms in zip(frames, sent):
+        dec = []
+        for c in range(6):
+            copy = [int(b) ^ (1 if c in (1, 4) else 0) for b in data[40 * c:40 * c + 40]]
+            was = [int(ch) for ch in ms[c // 3]]
+            for cl in pattern_classes([b for b in range(40) if copy[b] != was[b]]):
+                seen[cl] += 1
+            st, bits, _ = bch(copy)
+            dec.append((st, tuple(bits)))
+        for g in (dec[:3], dec[3:]):
+            good = [b for st, b in g if st != 3]
+            seen["one"] += len(good) == 1
+            seen["differ"] += len(good) >= 2 and elect(g) is None
+            seen["outvoted"] += len(good) == 3 and len(set(good)) == 2
+    return seen

@@ -200,6 +200,42 @@ def test_back_to_back_frames_ragged_cuts_and_both_rings_losses_through_the_heade
     assert got.tobytes() == want_h.tobytes() and st == want_h_st and st["n_lost"] >= 1
 
 
+def test_designed_bits_guarantee_their_census_and_header_equals_restatement_on_them(check_programs, tmp_path):
+    """the inputs of the GPU suite's designed carriers (E.designed_bits) without a device: what they guarantee, and the header
+    on the same streams -- header, restatement and kernel stand on one input"""
+    singles, pairs = E.flip_patterns()
+    assert len(singles) == 40 and len(pairs) == 780 and len(set(pairs)) == 780
+    classes, found = E.designed_classes()
+    assert all(found[c] >= 10 for c in E.CLASSES), found       # the bounded search finds every class
+    n_frames = 0
+    for patterns, inverted, seed in ((singles, True, 61), (pairs, False, 62), (classes, False, 62)):
+        bits, sent, starts, planted = E.designed_bits(patterns, seed, inverted=inverted)
+        bits = np.concatenate([bits, np.zeros(-len(bits) % 32, np.uint8)])
+        r = E.slicer(soft_of(bits))
+        assert (np.asarray(r["k"]) - 47).tolist() == starts and np.all(r["dist"] == (48 if inverted else 0))
+        frames = []
+        want, want_st = E.run(r["words"], r["k"], r["dist"], frames=frames)
+        f = native.edacs_fields(want)
+        assert want_st["n_records"] == len(starts) and np.all(f["inverted"] == inverted)
+        n_frames += len(starts)
+        if patterns is not classes:                            # per copy status == number of flips; every message as sent
+            assert f["status"].tolist() == [[len(p) for p in six] for six in planted]
+            assert sorted(p for six in planted for p in six if p) == patterns
+            assert [(m[2], m[3]) for m in control.edacs_messages(want)] == sent
+            slots = {(len(p), c) for six in planted for c, p in enumerate(six) if p}
+            assert slots == {(len(patterns[0]), c) for c in range(6)}                        # every slot gets the kind
+        else:
+            seen = E.census(frames, sent)
+            assert all(seen[c] >= 10 for c in E.CLASSES) and min(seen["one"], seen["differ"], seen["outvoted"]) >= 2, seen
+            assert want_st["n_msgs_none"] == seen["differ"]
+            slots = {c for six in planted for c, p in enumerate(six) if len(p) > 2}
+            assert slots == set(range(6))
+        for cuts in ([], list(range(0, len(bits), 997))):
+            got, st, _ = through_header(check_programs, tmp_path, r["words"], r["k"], r["dist"], cuts, len(bits))
+            assert got.tobytes() == want.tobytes() and st == want_st, (seed, cuts[:4])
+    assert n_frames == 137 + len(classes) // 6
+
+
 def test_accept_rule_with_hits_280_to_296_bits_apart(check_programs, tmp_path):
     rng = np.random.default_rng(10)
     gaps = list(range(280, 297))

@@ -161,6 +161,68 @@ def test_attach_in_mid_frame_that_frame_does_not_appear_and_esk(gpu_required, ca
     assert any(esk(a) != a for a, _ in sent[2:])
 
 
+# ------------------------------------------------------------------------------------------------ designed errors
+def _run_designed(nat, bits):
+    """the bits as a noise-free 2-FSK carrier on a 400 kS/s front-end, strict search of both polarities -> (records, state,
+    the restatement's records, its state, the hits' k and dist, the decided frames' data bits)"""
+    x = M.fsk2_carrier(bits, BAUD, FS, OFF, DEV, np.random.default_rng(5), noise=0.0)
+    blk = 8 * BLK
+    with nat.Frontend(FS, device=0, block_capacity=blk) as fe:
+        c = fe.chan_open(CR, OFF)
+        control.edacs_clock(fe, c, hard=True, frames=True)
+        for a in range(0, len(x), blk):
+            fe.push(x[a:a + blk])
+        recs, st = fe.chan_read_edacs(c), fe.chan_edacs_state(c)
+        by = fe.chan_read_hard(c)
+        k, dist = fe.chan_read_sync(c)
+    frames = []
+    want, want_st = E.run(by, k, dist, frames=frames)
+    return recs, st, want, want_st, k, dist, frames
+
+
+@pytest.mark.parametrize("flips", [1, 2])
+def test_designed_carrier_every_single_flip_and_every_pair_of_flips_is_corrected(gpu_required, flips):
+    """All 40 single flips of a 40-bit copy on an inverted carrier (7 frames), all 780 pairs on an upright one (130 frames), the
+    patterns rotating through the six copy slots -- the inverted slots 1 and 4 and both halves of the kernel's packed
+    syndrome registers get every kind; every lane 0 .. 39 is a root of the Chien ballot, position 0 (lane 0's trial of 63)
+    among them.  Records and counters are the restatement's over the channel's own words and hits; per copy status == number
+    of flips; both messages elected and as sent.  tests/test_edacs_cpu.py holds the same on the planted bits."""
+    nat = gpu_required
+    patterns = E.flip_patterns()[flips - 1]
+    bits, sent, starts, planted = E.designed_bits(patterns, 60 + flips, inverted=flips == 1)
+    recs, st, want, want_st, k, dist, _ = _run_designed(nat, bits)
+    f = nat.edacs_fields(recs)
+    print("designed, %d flip(s): %d hits, %s" % (flips, len(k), st))
+    _same(recs, want, "designed")
+    assert st == want_st and st["n_lost"] == 0 and st["n_records"] == len(starts) == (len(patterns) + 5) // 6
+    # the planted frames, all of them, at distance 0 of their polarity and where they were put
+    assert len(k) == len(starts) and np.all(dist == (48 if flips == 1 else 0)) and np.diff(k).tolist() == np.diff(starts).tolist()
+    assert not np.any(f["dist"]) and np.all(f["inverted"] == (flips == 1))
+    assert f["status"].tolist() == [[len(p) for p in six] for six in planted]
+    assert sorted(p for six in planted for p in six if p) == patterns and len(patterns) == (40, 780)[flips - 1]
+    assert [(m[2], m[3]) for m in control.edacs_messages(recs)] == sent and st["n_msgs"] == 2 * len(starts)
+
+
+def test_designed_carrier_of_the_classes_that_do_not_correct_and_the_election(gpu_required):
+    """Copies chosen on the CPU from random 3- and 4-flip patterns (E.class_patterns: a bounded search that finds ten of each):
+    status 3, status 2 that miscorrects, "stands" with S1 = 0 and S3 != 0, a position in 40 .. 47 (accepted, no bit changed),
+    a position > 47 (fails); and frames for the election: one of three copies decoded, two that disagree, two that agree
+    against a third.  The census is taken from the restatement over the delivered streams."""
+    nat = gpu_required
+    patterns, found = E.designed_classes()
+    assert all(found[c] >= 10 for c in E.CLASSES), found
+    bits, sent, starts, _ = E.designed_bits(patterns, 62)
+    recs, st, want, want_st, k, dist, frames = _run_designed(nat, bits)
+    seen = E.census(frames, sent)
+    print("designed classes: %d hits, %s, census %s" % (len(k), st, seen))
+    _same(recs, want, "designed classes")
+    assert st == want_st and st["n_lost"] == 0 and st["n_records"] == len(starts) == len(frames)
+    assert len(k) == len(starts) and not np.any(dist) and np.diff(k).tolist() == np.diff(starts).tolist()
+    assert all(seen[c] >= 10 for c in E.CLASSES) and min(seen["one"], seen["differ"], seen["outvoted"]) >= 2, seen
+    f = nat.edacs_fields(recs)
+    assert set(f["status"].reshape(-1).tolist()) == {0, 1, 2, 3} and st["n_msgs_none"] == seen["differ"] > 0
+
+
 # ------------------------------------------------------------------------------------------------ many channels, groups
 def _kind_of(j):
     return "clock" if j in (0, 63, 64, 129) or j % 3 == 2 else ("fsk4", "costas")[j % 3]

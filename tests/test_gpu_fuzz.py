@@ -1716,3 +1716,386 @@ def test_random_stage_streams_batched_reads_equal_single_reads(gpu_required, see
     if os.environ.get("RCF_FUZZ_DEBUG"):
         print("DBG", seed, "ring", cap, "blocks", n_blocks, "items", items, "refused", refused[0])
     assert sum(items.values()) > 1000 and counted[1] > 100, (seed, cap, n_blocks, items, refused[0])
+
+
+# ---- the hard-decision chain: symbol loop -> slicer -> TSBK / EDACS stage
+_HARD_KINDS = ("clock", "fsk4", "costas")
+_HARD_SAMPLES = 600000                           # input samples of a run at 400 kS/s: twice the longer planted fixture
+_P25_SYNC, _EDACS_SYNC = 0x5575F5FF77FF, 0b010101010101010101010111000100100101010101010101
+EINVAL, ESTATE = -1, -6
+
+
+def _hard_plan(seed):
+    """Everything test_random_hard_decision_lifecycles draws, and the model of the lifetime rules (include/rcf.h at
+    rcf_chan_slicer, rcf_chan_tsbk, rcf_chan_edacs) that says what each call must answer: no device is needed to make it, so the
+    floors on what a seed exercises are facts about the draws.  -> dict(cap, group, slots, sizes, ops, reads, counts): ops[b] the
+    calls in front of block b, each (name, slot, arguments, expected code); reads[b] per stream (reader, cap_each, order seed)"""
+    rng = np.random.default_rng(51000 + seed)
+    cap = 1 << int(rng.integers(8, 12))
+    most = min(400, (cap - 64) // 2)             # channel samples a block: what the smallest ring takes beside the loops' windows
+    group = seed % 2 == 1
+    slots = [dict(kind=_HARD_KINDS[i % 3], fe=i % 2 if group else 0, f=-140e3 + 40e3 * i) for i in range(8)]
+    sizes = []
+    while sum(sizes) < _HARD_SAMPLES:
+        sizes.append(int(rng.integers(1, 40)) if rng.random() < 0.15 else int(rng.integers(8 * most, 16 * most + 1)))
+    model = {}                                   # slot -> dict(loop, slicer: None / dict(mode, bits, both), stage: None / kind)
+    counts = dict(loop_again_under_stage=0, slicer_again=0, stage_again=0, close=0, refusals=0, retune=0, off=0)
+    ops, reads = [], []
+
+    def slicer_op(i, ops_b, proper=False):
+        kind, m = slots[i]["kind"], model[i]
+        binary = kind == "clock"
+        u = 1.0 if proper else rng.random()
+        p = dict(source=kind, mode=1 if binary else 2, sync_word=_EDACS_SYNC if binary else _P25_SYNC, sync_bits=48,
+                 sync_max_errors=13 if kind == "fsk4" else 17, hit_capacity=int(rng.choice([16, 64, 4096], p=[0.5, 0.25, 0.25])),
+                 sync_both=int(rng.random() < (0.7 if binary else 0.1)))
+        code = 0
+        if u < 0.05:
+            p.update(dict(sync_both=1, sync_max_errors=24) if rng.random() < 0.5 else dict(hit_capacity=24))
+            code = EINVAL
+        elif u < 0.10:
+            p["source"] = _HARD_KINDS[(_HARD_KINDS.index(kind) + 1 + int(rng.integers(0, 2))) % 3]
+            code = ESTATE
+        elif u < 0.20:
+            p.update(sync_word=0x2D6, sync_bits=10, sync_max_errors=1)
+        elif u < 0.28:                           # the other system's slicer behind this loop
+            p.update(mode=2 if binary else 1, sync_word=_P25_SYNC if binary else _EDACS_SYNC, sync_max_errors=17)
+        if code == 0 and not m["loop"]:
+            code = ESTATE
+        ops_b.append(("slicer", i, p, code))
+        if code:
+            counts["refusals"] += 1
+            return
+        counts["slicer_again"] += m["slicer"] is not None
+        m["slicer"], m["stage"] = dict(mode=p["mode"], bits=p["sync_bits"], both=p["sync_both"]), None
+
+    def stage_op(i, ops_b, proper=False):
+        m = model[i]
+        own = "edacs" if slots[i]["kind"] == "clock" else "tsbk"
+        kind = own if proper or rng.random() < 0.85 else ("tsbk" if own == "edacs" else "edacs")
+        capacity, esk = int(rng.choice([16, 256])), bool(rng.random() < 0.5)
+        s = m["slicer"]
+        fits = s is not None and s["bits"] == 48 and ((s["mode"] == 2 and not s["both"]) if kind == "tsbk" else s["mode"] == 1)
+        code = 0 if fits else ESTATE
+        if fits and not proper and rng.random() < 0.07:
+            capacity, code = 24, EINVAL
+        ops_b.append(("stage", i, dict(kind=kind, capacity=capacity, esk=esk), code))
+        if code:
+            counts["refusals"] += 1
+            return
+        counts["stage_again"] += m["stage"] == kind
+        m["stage"] = kind                        # (a slicer carries one of the two, by its mode)
+
+    def loop_op(i, ops_b):
+        m = model[i]
+        counts["loop_again_under_stage"] += bool(m["loop"] and m["stage"])
+        ops_b.append(("loop", i, True, 0))
+        m.update(loop=True, slicer=None, stage=None)
+
+    def open_op(i, ops_b):
+        model[i] = dict(loop=False, slicer=None, stage=None)
+        ops_b.append(("open", i, slots[i]["f"], 0))
+        loop_op(i, ops_b); slicer_op(i, ops_b, proper=True); stage_op(i, ops_b, proper=True)
+
+    for b, n in enumerate(sizes):
+        ops_b = []
+        if b == 0:
+            for i in range(6):
+                open_op(i, ops_b)
+        for _ in range(int(rng.poisson(100.0 * n / _HARD_SAMPLES))):
+            u = rng.random()
+            free = [i for i in range(len(slots)) if i not in model]
+            if free and (u < 0.12 or not model):
+                open_op(free[int(rng.integers(0, len(free)))], ops_b)
+                continue
+            if not model:
+                continue
+            live = sorted(model)
+            i = live[int(rng.integers(0, len(live)))]
+            m = model[i]
+            again = rng.random() < 0.7           # what went with the old one is attached again behind the new one
+            if u < 0.18:
+                counts["close"] += 1
+                ops_b.append(("close", i, None, 0))
+                del model[i]
+            elif u < 0.28:
+                counts["retune"] += 1
+                ops_b.append(("retune", i, slots[i]["f"] + 1250.0 * float(rng.integers(-3, 4)), 0))
+            elif u < 0.42:
+                loop_op(i, ops_b)
+                if again:
+                    slicer_op(i, ops_b, proper=True); stage_op(i, ops_b, proper=True)
+            elif u < 0.47:
+                counts["off"] += 1
+                ops_b.append(("loop", i, False, 0))
+                m.update(loop=False, slicer=None, stage=None)
+            elif u < 0.65:
+                slicer_op(i, ops_b)
+                if again:
+                    stage_op(i, ops_b)
+            elif u < 0.70:
+                counts["off"] += 1
+                ops_b.append(("slicer", i, None, 0))
+                m.update(slicer=None, stage=None)
+            elif u < 0.93:
+                stage_op(i, ops_b)
+            else:
+                counts["off"] += 1
+                ops_b.append(("stage", i, None, 0))
+                m["stage"] = None
+        ops.append(ops_b)
+        reads.append({w: (str(rng.choice(["single", "many", "group"] if group else ["single", "many"])), int(rng.choice([3, 17, 64, 1024])),
+                          int(rng.integers(0, 1 << 30))) for w in ("clock", "fsk4", "costas", "hard", "sync", "tsbk", "edacs")})
+    return dict(cap=cap, group=group, slots=slots, sizes=sizes, ops=ops, reads=reads, counts=counts)
+
+
+@pytest.mark.parametrize("seed", _seeds())
+def test_random_hard_decision_lifecycles(gpu_required, seed):
+    """The hard-decision chain under a random lifecycle: eight slots of 25 kS/s channels on a 400 kS/s front end (odd seeds: on
+    two front ends in a Group) -- clock loop -> binary slicer with the EDACS word (sync_both drawn) -> EDACS stage; C4FM loop or
+    Gardner / Costas loop -> FSK4 slicer with the P25 word -> TSBK stage -- over noise and the two planted fixtures of the stage
+    tests, under searches so loose that noise hits.  At random block boundaries channels are opened, closed and retuned; the loop
+    is attached again or switched off with slicer and stage behind it; the slicer is attached again (other rings, sometimes
+    the other system's mode or a short word) or switched off; the stage is attached, attached again (esk and capacity
+    redrawn), or switched off; calls that must be refused are made, and every answer is compared with a model of the rules of
+    include/rcf.h (_hard_plan).  Rings: out_capacity 2^8 .. 2^11, hit rings of 16 / 64 / 4096, record rings of 16 / 256; ragged
+    pushes, some of under one symbol.  After every block the loops' soft symbols, the words, the hits and the records are
+    drained by the single readers, chan_read_many or the group's reader with a drawn cap_each until nothing comes; every row
+    continues its life's log.  Yardsticks, bit for bit: slicer_ref.run over a slicer life's soft symbols gives its words and
+    hits; tsbk_ref.run / edacs_ref.run over those, from the life's first hit, launch by launch with the hit ring's capacity,
+    gives a stage life's records and final counters.  Every draw is made before the device is touched: a failing seed replays.
+    Floors, so that the test cannot pass empty.  The draws alone give, over seeds 0 .. 39, at least 3 loop re-attaches under a
+    live stage, 5 slicer re-attaches, 4 stage re-calls, 5 closes and 14 refused calls: at least 2 of each are asserted.  Measured
+    on an MI355X over seeds 0 .. 39 (all 40 pass, about 1 s each), the minimum and maximum per seed: records of TSBK stages behind
+    the C4FM loop 3 .. 45, behind the Gardner / Costas loop 0 .. 100 (seed 19 has none), of both together 16 .. 134, of EDACS
+    stages 18 .. 86, stage lives with n_lost > 0 1 .. 14; slicer words 1588 .. 2799, hits 1054 .. 5330.  The floors are half the
+    minima: 1, none for the Costas loop alone, 8, 9, and one life with n_lost > 0 (half of one, in whole lives)."""
+    import edacs_ref as E
+    import slicer_ref as S
+    import tsbk_ref as T
+    import fsk4_ref as F
+    import mm_ref as M
+    from rcf import control, p25
+    from test_gpu_edacs import edacs_bits
+    from test_gpu_tsbk import tsdu_dibits
+    nat = gpu_required
+    plan = _hard_plan(seed)
+    cap, slots, sizes, counts = plan["cap"], plan["slots"], plan["sizes"], plan["counts"]
+    assert min(counts[c] for c in ("loop_again_under_stage", "slicer_again", "stage_again", "close")) >= 2 and counts["refusals"] >= 2, counts
+    fs, cr, total = 400e3, 12500, int(np.sum(sizes))
+    n_fe = 2 if plan["group"] else 1
+    xs = [(0.05 * synth.awgn(np.random.default_rng(52000 + 2 * seed + m), total)).astype(np.complex64) for m in range(n_fe)]
+    planted = [M.fsk2_carrier(edacs_bits()[0], 9600.0, fs, slots[0]["f"], 1200.0, np.random.default_rng(5)),
+               F.c4fm_carrier(tsdu_dibits()[0], 4800, fs, slots[1]["f"] + 150.0, 0.5, 600.0)]
+    for i, c in enumerate(planted):
+        n = min(len(c), total)
+        xs[slots[i]["fe"]][:n] += (0.2 if i == 0 else 0.4) * c[:n]
+    single = dict(clock="chan_read_clock", fsk4="chan_read_fsk4", costas="chan_read_costas", hard="chan_read_hard", sync="chan_read_sync",
+                  tsbk="chan_read_tsbk", edacs="chan_read_edacs")
+    slicer_lives, stage_lives = [], []
+    fes = [nat.Frontend(fs, device=0, block_capacity=max(sizes) + 16, out_capacity=cap) for _ in range(n_fe)]
+    grp = nat.Group(fes) if plan["group"] else None
+    try:
+        dev = {}                                 # slot -> dict(fe, m, cid, loop: life / None, slicer: life / None, stage: life / None)
+
+        def call(code, fn, *a, **kw):
+            try:
+                fn(*a, **kw)
+                got = 0
+            except nat.RcfError as e:
+                got = e.code
+            assert got == code, (seed, fn.__name__, a, kw, got, code)
+
+        def has(d, w):
+            if w in _HARD_KINDS:
+                return d["loop"] is not None and slots[d["slot"]]["kind"] == w
+            return d["slicer"] is not None if w in ("hard", "sync") else d["stage"] is not None and d["stage"]["kind"] == w
+
+        def do(op):
+            name, i, arg, code = op
+            kind = slots[i]["kind"]
+            if name == "open":
+                fe = fes[slots[i]["fe"]]
+                cid = fe.chan_open(cr, arg)
+                if kind == "fsk4":
+                    fe.chan_fm_filter(cid, p25.fm_gain(cr), p25.symbol_taps(cr, 4800))
+                elif kind == "costas":
+                    fe.chan_agc(cid, 16, 1.0)
+                dev[i] = dict(slot=i, fe=fe, m=slots[i]["fe"], cid=cid, loop=None, slicer=None, stage=None)
+                return
+            d = dev[i]
+            fe, cid = d["fe"], d["cid"]
+            if name == "close":
+                fe.chan_close(cid)
+                del dev[i]
+            elif name == "retune":
+                fe.chan_set_offset(cid, arg)
+            elif name == "loop":
+                if kind == "clock":
+                    control.edacs_clock(fe, cid) if arg else fe.chan_clock_mm(cid, None)
+                elif kind == "fsk4":
+                    fe.chan_fsk4(cid, **p25.fsk4_params(cr, 4800)) if arg else fe.chan_fsk4(cid, None)
+                else:
+                    fe.chan_costas(cid, **p25.costas_params(cr, 4800)) if arg else fe.chan_costas(cid, None)
+                d.update(loop=dict(soft=[], n=0) if arg else None, slicer=None, stage=None)
+                for w in ("chan_slicer_state", "chan_tsbk_state", "chan_edacs_state"):          # slicer and stage went with the old loop
+                    call(ESTATE, getattr(fe, w), cid)
+            elif name == "slicer":
+                if arg is None:
+                    fe.chan_slicer(cid, None)
+                    d.update(slicer=None, stage=None)
+                else:
+                    p = dict(arg)
+                    source = dict(clock=nat.READ_CLOCK, fsk4=nat.READ_FSK4, costas=nat.READ_COSTAS)[p.pop("source")]
+                    call(code, fe.chan_slicer, cid, source, p.pop("mode"), **p)
+                    if code == 0:
+                        d["slicer"] = dict(p=arg, kind=kind, loop=d["loop"], soft_from=d["loop"]["n"], words=[], hits=[], launches=[], n_symbols=0)
+                        d["stage"] = None
+                        slicer_lives.append(d["slicer"])
+                        assert fe.chan_slicer_state(cid) == dict(n_symbols=0, n_words=0, n_hits=0)
+                if code == 0:
+                    for w in ("chan_tsbk_state", "chan_edacs_state"):                           # the stage went with the old slicer
+                        call(ESTATE, getattr(fe, w), cid)
+            else:
+                if arg is None:
+                    fe.chan_tsbk(cid, on=False); fe.chan_edacs(cid, on=False)
+                    d["stage"] = None
+                    return
+                if arg["kind"] == "tsbk":
+                    call(code, fe.chan_tsbk, cid, arg["capacity"])
+                else:
+                    call(code, fe.chan_edacs, cid, arg["capacity"], esk=arg["esk"])
+                if code == 0:
+                    s = d["slicer"]
+                    d["stage"] = dict(arg, slicer=s, first_hit=s["launches"][-1][1] if s["launches"] else 0, launch_from=len(s["launches"]),
+                                      recs=[], n=0, state=None)
+                    stage_lives.append(d["stage"])
+                    state = fe.chan_tsbk_state(cid) if arg["kind"] == "tsbk" else fe.chan_edacs_state(cid)
+                    assert not any(state.values()), (seed, state)                               # afresh
+                    ring = fe.chan_tsbk_ring(cid) if arg["kind"] == "tsbk" else fe.chan_edacs_ring(cid)
+                    assert ring[1] == arg["capacity"]
+
+        def drain(w, how, cap_each, order_seed):
+            """-> {slot: rows of stream w new since the last drain}, by the drawn reader, repeated until nothing comes"""
+            live = [dev[i] for i in np.random.default_rng(order_seed).permutation(sorted(dev))]
+            got = {d["slot"]: [] for d in live if has(d, w)}
+            if how == "single":
+                for d in live:
+                    reader = getattr(d["fe"], single[w])
+                    if not has(d, w):
+                        call(ESTATE, reader, d["cid"], cap_each)
+                        continue
+                    while True:
+                        rows = reader(d["cid"], cap_each)
+                        rows = np.stack(rows) if w == "sync" else rows.view("<u4") if w == "hard" else rows
+                        if rows.shape[-1] == 0:
+                            break
+                        got[d["slot"]].append(rows)
+                return got
+            lists = [live] if how == "group" else [[d for d in live if d["m"] == m] for m in range(n_fe)]
+            for lst in lists:
+                while lst:
+                    if how == "group":
+                        rows = grp.read_many([(d["m"], d["cid"]) for d in lst], w, cap_each=cap_each)
+                    else:
+                        rows = lst[0]["fe"].chan_read_many([d["cid"] for d in lst], w, cap_each=cap_each)
+                    more = False
+                    for d, r in zip(lst, rows):
+                        assert (r is not None) == has(d, w), (seed, w, how, d["slot"])
+                        if r is not None and len(r):
+                            more = True
+                            if w == "sync":
+                                r = np.stack(nat.widen_hits(r, d["slicer"]["n_symbols"]))
+                            got[d["slot"]].append(r.copy())
+                    if not more:
+                        break
+            return got
+
+        at = 0
+        for b, n in enumerate(sizes):
+            for op in plan["ops"][b]:
+                do(op)
+            if grp is not None:
+                grp.push([x[at:at + n] for x in xs])
+            else:
+                fes[0].push(xs[0][at:at + n])
+            at += n
+            for d in dev.values():
+                s, t = d["slicer"], d["stage"]
+                if s is not None:
+                    st = d["fe"].chan_slicer_state(d["cid"])
+                    s["before"] = s["launches"][-1] if s["launches"] else (0, 0)
+                    s["launches"].append((st["n_words"], st["n_hits"]))
+                    s["n_symbols"] = st["n_symbols"]
+                if t is not None:
+                    t["state"] = d["fe"].chan_tsbk_state(d["cid"]) if t["kind"] == "tsbk" else d["fe"].chan_edacs_state(d["cid"])
+                    t["launches"] = s["launches"][t["launch_from"]:]           # (a copy: the slicer may outlive the stage)
+            for w, (how, cap_each, order_seed) in plan["reads"][b].items():
+                for i, rows in drain(w, how, cap_each, order_seed).items():
+                    d = dev[i]
+                    if w in _HARD_KINDS:
+                        d["loop"]["soft"] += rows
+                        d["loop"]["n"] += sum(len(r) for r in rows)
+                    elif w == "hard":
+                        d["slicer"]["words"] += rows
+                    elif w == "sync":
+                        s = d["slicer"]
+                        s["hits"].append((s["before"][1], s["launches"][-1][1], np.concatenate(rows, axis=1) if rows else np.zeros((2, 0), np.int64)))
+                    else:
+                        t = d["stage"]
+                        t["recs"].append((t["n"], t["state"]["n_records"], np.concatenate(rows) if rows else np.zeros(0, nat._read_dtype(w))))
+                        t["n"] = t["state"]["n_records"]
+            for d in dev.values():               # the slicer has sliced every symbol its loop has delivered
+                if d["slicer"] is not None:
+                    assert d["slicer"]["n_symbols"] == d["loop"]["n"] - d["slicer"]["soft_from"], (seed, b, d["slot"])
+    finally:
+        if grp is not None:
+            grp.close()
+        for fe in fes:
+            fe.close()
+
+    def tail(want, before, after, ring, got, what):
+        """a reader that was `ring` or less behind gets everything; one further behind the newest `ring`"""
+        first = max(before, after - ring)
+        assert len(got) == after - first and after <= len(want), (seed, what, before, after, ring, len(got), len(want))
+        return first
+
+    n_items = dict(words=0, hits=0)
+    for s in slicer_lives:
+        p = s["p"]
+        soft = np.concatenate(s["loop"]["soft"] + [np.zeros(0, np.float32)])[s["soft_from"]:s["soft_from"] + s["n_symbols"]]
+        assert len(soft) == s["n_symbols"]
+        ref = S.run(soft, p["mode"], sync_word=p["sync_word"], sync_bits=p["sync_bits"],
+                    max_errors=p["sync_bits"] if p["sync_both"] else p["sync_max_errors"])
+        keep = np.array([E.is_hit(int(v), p["sync_max_errors"], p["sync_both"], p["sync_bits"]) for v in ref["dist"]], bool)
+        s["ref"] = ref["words"], np.asarray(ref["k"])[keep], np.asarray(ref["dist"])[keep]
+        words = np.concatenate(s["words"] + [np.zeros(0, "<u4")])
+        n_words, n_hits = s["launches"][-1] if s["launches"] else (0, 0)
+        assert n_words == len(ref["words"]) and np.array_equal(words, ref["words"]), (seed, s["kind"], p, n_words, len(ref["words"]))
+        assert n_hits == len(s["ref"][1]), (seed, s["kind"], p, n_hits, len(s["ref"][1]))
+        for before, after, rows in s["hits"]:
+            first = tail(s["ref"][1], before, after, p["hit_capacity"], rows[0], "hits")
+            assert np.array_equal(rows[0], s["ref"][1][first:after]) and np.array_equal(rows[1], s["ref"][2][first:after]), (seed, p, before, after)
+        n_items["words"] += n_words; n_items["hits"] += n_hits
+    n_recs, n_lost = dict(tsbk_fsk4=0, tsbk_costas=0, edacs=0), 0
+    for t in stage_lives:
+        s = t["slicer"]
+        if t["state"] is None:                   # gone before a block came
+            continue
+        words, k, dist = s["ref"]
+        kw = dict(first_hit=t["first_hit"], launches=t["launches"], hit_cap=s["p"]["hit_capacity"])
+        if t["kind"] == "tsbk":
+            want, want_st = T.run(words, k, dist, **kw)
+        else:
+            want, want_st = E.run(words, k, dist, sync_both=bool(s["p"]["sync_both"]), esk=t["esk"], **kw)
+        assert t["state"] == want_st, (seed, t["kind"], s["kind"], s["p"], t["first_hit"], t["state"], want_st)
+        for before, after, rows in t["recs"]:
+            first = tail(want, before, after, t["capacity"], rows, "records")
+            assert rows.tobytes() == want[first:after].tobytes(), (seed, t["kind"], s["kind"], before, after)
+        key = "edacs" if t["kind"] == "edacs" else "tsbk_" + s["kind"]
+        n_recs[key] = n_recs.get(key, 0) + want_st["n_records"]
+        n_lost += want_st["n_lost"] > 0
+    tsbk_both = n_recs.get("tsbk_fsk4", 0) + n_recs.get("tsbk_costas", 0)
+    assert n_recs.get("tsbk_fsk4", 0) >= 1 and tsbk_both >= 8 and n_recs["edacs"] >= 9 and n_lost >= 1, (seed, n_recs, n_lost)
+    print("hard-decision lifecycles, seed %d: ring %d blocks %d group %d: %s slicer lives %d stage lives %d items %s records %s lives with n_lost %d" % (
+        seed, cap, len(sizes), plan["group"], counts, len(slicer_lives), len(stage_lives), n_items, n_recs, n_lost))

@@ -177,6 +177,43 @@ def test_a_second_sync_10_dibits_behind_a_first_is_not_accepted(gpu_required):
     assert int(exact[0]) in ks and int(exact[0]) + 10 not in ks
 
 
+# ------------------------------------------------------------------------------------------------ designed errors
+def test_designed_carrier_of_wrong_blocks_walks_every_correcting_path(gpu_required):
+    """T.designed_dibits as a noise-free C4FM carrier under the strict search: 50 TSDUs with DUID 7 whose 147 blocks are random
+    dibits (30 frames) or valid TSBKs with 1 .. 4 wrong dibits, every code word 0 .. 48 damaged in some block, a 180- and a
+    288-dibit frame among them.  Records and counters are the restatement's over the channel's own words and hits; and the
+    census over those delivered streams says that the kernel's scan, its n_inexact ballot and its CRC reduction met what the
+    input was built for: all 64 (state, code word) pairs, an inexact word at every lane, every lane entered from all four
+    states, n_inexact >= 32, bad and good CRCs.  tests/test_tsbk_cpu.py holds the same census on the planted dibits."""
+    nat = gpu_required
+    d, starts = T.designed_dibits(NAC)
+    x = F.c4fm_carrier(d, 4800, FS, OFF + 150.0, 0.5, 600.0)
+    blk = 4 * BLK
+    with nat.Frontend(FS, device=0, block_capacity=blk) as fe:
+        c = p25.c4fm_demod(fe, fe.chan_open(CR, OFF), CR, 4800, hard=True, tsbk=True)
+        for a in range(0, len(x), blk):
+            fe.push(x[a:a + blk])
+        recs, st = fe.chan_read_tsbk(c), fe.chan_tsbk_state(c)
+        by = fe.chan_read_hard(c)
+        k, dist = fe.chan_read_sync(c)
+    blocks = []
+    want, want_st = T.run(by, k, dist, blocks=blocks)
+    census = T.census(blocks, want_st)
+    f = nat.tsbk_fields(recs)
+    print("designed: %d hits, %s; census: %d pairs, %d lanes inexact, n_inexact up to %d (device: %d), %d good CRCs" % (
+        len(k), st, len(census["pairs"]), len(census["inexact_lanes"]), census["max_inexact"], int(f["n_inexact"].max()), census["n_crc_good"]))
+    _same(recs, want, "designed")
+    assert st == want_st and st["n_lost"] == 0
+    # the planted frames, all of them, at distance 0 and where they were put (the loop's delay moves them all alike)
+    assert len(k) == len(starts) and not np.any(dist) and np.diff(k).tolist() == np.diff(starts).tolist()
+    frames = p25.tsdu_frames(recs)
+    assert [fr["frame_dibits"] for fr in frames] == T.DESIGNED_FRAME_DIBITS and all(fr["duid"] == 7 and fr["nac"] == NAC for fr in frames)
+    assert st["n_frames"] == 50 and st["n_blocks"] == len(blocks) == 147
+    T.check_census(census)
+    assert int(f["n_inexact"].max()) == census["max_inexact"] and st["n_crc_bad"] == census["n_crc_bad"] == int(np.sum(f["crc_bad"]))
+    assert not any(t["crc"] or t["n_inexact"] for t in frames[-1]["tsbk"])       # the last frame is clean
+
+
 # ------------------------------------------------------------------------------------------------ many channels, groups
 def _kind_of(j):
     return "costas" if j % 3 == 1 else "fsk4"

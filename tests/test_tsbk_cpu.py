@@ -155,6 +155,35 @@ def test_back_to_back_frames_and_ragged_cuts_through_the_header(check_programs, 
     assert got.tobytes() == want_h.tobytes() and st == want_h_st and st["n_lost"] >= 1
 
 
+def test_designed_dibits_guarantee_their_census_and_header_equals_restatement_on_them(check_programs, tmp_path):
+    """the input of the GPU suite's designed carrier (T.designed_dibits) without a device: what it guarantees, and the header
+    on the same stream -- header, restatement and kernel stand on one input"""
+    d, starts = T.designed_dibits()
+    assert len(starts) == 50 and 16000 < len(d) < 20000
+    words, k, dist = slicer_streams(d)
+    assert (np.asarray(k) - 23).tolist() == starts and not np.any(dist)           # every planted frame, and nothing else
+    blocks = []
+    want, want_st = T.run(words, k, dist, blocks=blocks)
+    T.check_census(T.census(blocks, want_st))
+    frames = p25.tsdu_frames(want)
+    assert [f["frame_dibits"] for f in frames] == T.DESIGNED_FRAME_DIBITS and want_st["n_blocks"] == len(blocks) == 147
+    # what set 2 is made of: a valid TSBK with 1 .. 4 wrong dibits, one of them in the code word asked for (48: dibits 24, 25)
+    rng = np.random.default_rng(5)
+    for t in range(49):
+        octets = T.tsbk_octets(rng)
+        block = T.damaged_block(octets, t, 1 + t % 4, rng)
+        wrong = {p for p, (a, b) in enumerate(zip(T.encode_block(octets), block)) if a != b}
+        assert len(wrong) == 1 + t % 4 and len(wrong & {T.ORDER[2 * t], T.ORDER[2 * t + 1]}) == 1, (t, wrong)
+    assert (T.ORDER[96], T.ORDER[97]) == (24, 25)
+    # the blocks of sets 2 and 3 as delivered: 54 blocks that are no code words' images, of which the walk repairs some
+    damaged = [T.decode_block(b) for b in blocks[90:144]]
+    assert any(inexact > 0 and not bad for _, bad, inexact in damaged) and 0 < sum(bad for _, bad, _ in damaged) < 54
+    assert [T.decode_block(b)[1:] for b in blocks[144:]] == [(0, 0)] * 3        # the last frame is clean
+    for cuts in ([], list(range(0, len(d), 997))):
+        got, st, _ = through_header(check_programs, tmp_path, words, k, dist, cuts, len(d))
+        assert got.tobytes() == want.tobytes() and st == want_st, cuts[:4]
+
+
 def test_accept_rule_with_hits_1_to_30_dibits_apart(check_programs, tmp_path):
     rng = np.random.default_rng(10)
     d = rng.integers(0, 4, 30 * 500 + 600).astype(np.uint8)
