@@ -163,7 +163,7 @@ int rcf_device(rcf_t *h);
 #define RCF_T_FSK4         12  /* C4FM symbol loops (rcf_chan_fsk4): one launch per block for every channel with the stage */
 #define RCF_T_SLICE        13  /* hard decisions (rcf_chan_slicer): one launch per block for every channel with the stage; and the
                                 * launch of the TSBK stages behind them (rcf_chan_tsbk), one more per block with such a stage,
-                                * and likewise that of the EDACS stages (rcf_chan_edacs) */
+                                * and likewise that of the EDACS stages (rcf_chan_edacs) and of the OSW stages (rcf_chan_osw) */
 #define RCF_T_COUNT        14
 /* on = 0: off; 1: every class; otherwise a mask with bit (class + 1) set for each class to time -- every timed
  * launch costs two event records on the stream (~10 us of gap), so a throughput run times only what it reports.  The
@@ -674,6 +674,74 @@ int rcf_chan_edacs_state(rcf_t *h, int chan_id, rcf_edacs_state_t *out);
 int64_t rcf_chan_read_edacs(rcf_t *h, int chan_id, uint32_t *out, size_t max_records);
 /* device pointer of the record ring and its capacity in records (zero-copy): record i lives at word 8 (i & (capacity - 1)) */
 int rcf_chan_edacs_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity);
+/* SmartNet outbound signalling words (OSWs) behind a slicer: what the reference's consumer does per 84-bit frame of a control
+ * channel in Python strings (moto_control_demod.py: receive_engine 212-331 -- the framing with its lock counter 252-281 and
+ * 521-525, deinterleave 198-203, the parity syndrome and its correction 284-320, the two xor masks 325-330), as one more
+ * optional stage per channel on the GPU.  It applies to a slicer in RCF_SLICE_BINARY mode that searches an 8-bit sync word
+ * (10101100 there) with sync_max_errors = 0 and sync_both = 0.  It reads the slicer's own two streams and writes a third, the
+ * counted stream RCF_HARD_OSW of 32-byte records, one per frame.  All of it is integer work: the records are exactly what
+ * the rules below give for the words and hits the slicer's readers deliver, however the input was cut into blocks.
+ * Notation.  Bits are the slicer's bit stream; a hit item gives k, the last bit of the sync word (widened against n_symbols
+ * as above), and the hit STARTS at h = k - 7.  W = 32 n_words.  State: the cursor pos, a bit index, initially the slicer's
+ * n_symbols at the call; locked, an int32, initially 0, which can go negative (it stops at the least int32); is_locked.
+ * Only hits appended after the call and with h >= pos are considered.
+ * One step at pos:
+ *   A. locked >= 4, or locked == 3 and a hit starts at pos: the frame is at pos.  Decided in the first block with
+ *      W >= pos + 84.  rel = 0 with a hit at pos; without one only rel != 0 matters (260-263) and the record carries 65535.
+ *   B. anything else: h0 = the first hit with h >= pos (the stage waits for one), h1 = the first hit with h >= h0 + 8.
+ *      Decided in the first block with W >= h0 + 92: by then every hit that starts in h0 + 8 .. h0 + 84 is there.  With
+ *      locked <= 2 the candidate is accepted iff h1 - h0 == 84 (260); otherwise pos = h0 + 8 (525) and n_rejects += 1.  With
+ *      locked == 3 it is accepted regardless.  rel = h0 - pos.
+ *   Accepted: (1) rel != 0: locked -= 1, else locked += 1 if locked < 5;  (2) is_locked = locked >= 5;  (3) n_frames += 1;
+ *      (4) with locked > 2 now, the packet is the bits pos + 8 .. pos + 83 and pos += 84;  (5) otherwise the packet is the bits
+ *      h0 + 8 .. h0 + 83 and pos = h0 + 84.
+ * Packet b[0 .. 75]: out[4 x + j] = b[x + 19 j], x = 0 .. 18, j = 0 .. 3 (deinterleave); data[i] = out[2 i], parity[i] =
+ * out[2 i + 1], i = 0 .. 37; psyn[i] = parity[i] ^ data[i] ^ data[i - 1] with data[-1] = 0.  If any psyn bit is set:
+ * n_bad += 1 and data[x] ^= psyn[x] & psyn[x + 1] for x = 0 .. 36 (psyn itself is not modified, bit 37 is never corrected);
+ * else, if rel != 0, locked += 1 (320).  lid = data[0 .. 15] ^ 0xcc38, individual = data[16], cmd = data[17 .. 26] ^ 0xd5,
+ * the first bit highest; the bits 27 .. 37 are delivered and not interpreted (the reference does not check them).
+ * Records, 8 uint32 each, in increasing position:
+ *     word 0    bit 0 sync at the cursor (rel == 0), bit 1 syndrome nonzero, bit 2 is_locked, bit 3 individual, bits 4-9 the
+ *               number of data bits flipped, bits 10-15 the number of set psyn bits, bits 16-31 min(rel, 65535)
+ *     word 1    the low 32 bits of the packet's sync position (the packet's first bit - 8)
+ *     word 2    lid | cmd << 16
+ *     word 3-4  the 38 corrected data bits, the first bit highest, bytes in memory order (the word ring's rule), the rest 0
+ *     word 5-6  the 38 psyn bits likewise
+ *     word 7    locked after the step, as int32
+ * n_frames and n_bad are the reference's packets and packets_bad, which its quality_check reads.
+ * Lost: hits that left the hit ring before they were examined are counted (n_lost); an accepted frame whose sync position's
+ * word the word ring had overwritten when it was decided is counted (n_lost) and nothing else of its step applies.  After a
+ * loss pos moves to the first retained hit at or behind it -- behind a lost frame: at or behind the oldest retained word --
+ * if the block knows one, else (a lost frame) to the oldest retained word.
+ * Departures.  The reference decides against whatever its string buffer holds -- more than 228 bits, one message more per
+ * loop, all of it dropped when no sync word is in it -- so its output depends on how the stream arrives.  The stage equals
+ * the reference with the whole stream in view, waits where the reference would see find() == -1, and has no 229-bit
+ * minimum.  sync_loops, the retune (tune_next_control, which also zeroes locked) and the no-flow rule are control-plane policy
+ * and stay with the consumer: one that retunes calls rcf_chan_osw again.  (No naming of cmd: dual, last_cmd, the type
+ * table, the channel grants.)
+ * p == NULL switches the stage off.  It applies from the next block on and considers only hits appended after the call (the
+ * call reads the slicer's counters and so synchronises the stream); calling again starts it afresh, locked = 0 and a new
+ * ring.  It goes when the slicer goes: slicer attached again or switched off, its source loop attached again or switched
+ * off, channel closed.  A slicer carries at most one of the TSBK, EDACS and OSW stages: what it searches decides which.
+ * RCF_ESTATE: the channel has no slicer in RCF_SLICE_BINARY mode that searches an 8-bit sync word with sync_max_errors = 0
+ * and sync_both = 0; RCF_EINVAL: capacity not 0 or a power of two >= 16 (at most 2^20); RCF_ENOCHAN: no such channel. */
+typedef struct rcf_osw_params {
+    int capacity;          /* records of the ring, a power of two >= 16; 0 = 256 */
+    int reserved_[3];
+} rcf_osw_params_t;
+int rcf_chan_osw(rcf_t *h, int chan_id, const rcf_osw_params_t *p);
+/* the stage's counters as of the last block; syncs the stream.  RCF_ESTATE without the stage (here and in the calls below) */
+typedef struct rcf_osw_state {
+    int64_t n_records, n_frames, n_bad, n_rejects, n_lost;   /* records written, frames accepted (packets), of them with a nonzero syndrome (packets_bad), candidates rejected, hits and frames lost */
+    int32_t locked, is_locked;                               /* the lock counter; is_locked as of the last accepted frame */
+} rcf_osw_state_t;
+int rcf_chan_osw_state(rcf_t *h, int chan_id, rcf_osw_state_t *out);
+/* unread records, oldest first: out = uint32[max_records][8] (one round trip); RCF_HARD_OSW names the stream to
+ * rcf_chan_read_many and rcf_group_read_many (out = uint32[n_chans][cap_each][8]); the pump does not deliver it */
+#define RCF_HARD_OSW     51   /* (50 stays unassigned: the readers refuse it as an unknown stream) */
+int64_t rcf_chan_read_osw(rcf_t *h, int chan_id, uint32_t *out, size_t max_records);
+/* device pointer of the record ring and its capacity in records (zero-copy): record i lives at word 8 (i & (capacity - 1)) */
+int rcf_chan_osw_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity);
 /* drift probe of p25_control_demod.py:123-127: moving_average_ff(window, 1) * (1/window) of the
  * discriminator output (window = 10000 there) == mean of gain*fm over the last `window` samples; this is
  * the value demod_watcher hands to frontend_connector.report_offset */

@@ -390,6 +390,25 @@ struct EdacsLaunch {
     uint32_t flags;
 };
 void launch_edacs(const EdacsLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
+// SmartNet OSWs behind a slicer (osw.hip; receive_engine of the reference: 84-bit framing with its lock counter, deinterleave,
+// parity syndrome and correction, the two xor masks; definition: include/rcf.h at rcf_chan_osw).
+// per-channel running state, device resident, owned by osw_kernel
+struct OswState {
+    int64_t n_records;       // records written so far (record i at rec_ring[(i & rec_mask) * 8])
+    int64_t n_frames, n_bad, n_rejects, n_lost;
+    int32_t locked, is_locked;
+    int64_t next_hit;        // the first hit of the slicer's stream that may still start at or behind pos
+    int64_t pos;             // the cursor: the first bit no step has passed
+};
+struct OswLaunch {
+    const SliceState *src;   // the slicer's counters (device)
+    const uint32_t *word_ring, *hit_ring;    // the slicer's two rings
+    OswState *st;
+    uint32_t *rec_ring;
+    uint32_t word_mask, hit_mask, rec_mask;
+    int32_t n_k;             // the slicer's n_k of this block: at most that many new symbols, and so new hits
+};
+void launch_osw(const OswLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
 // mean of gain * fm over the last `window` samples ending at n_end (exclusive), one workgroup
 void launch_fm_level(const float *fm_ring, int64_t n_end, int window, float gain, uint64_t ring_mask, float *d_out,
                      hipStream_t s);

@@ -364,6 +364,11 @@ int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c)
             er.n_k = rec.n_k;
             bp.tails.edf.add(er);
         }
+        if (rec.n_k > 0 && c->slicer->osw) {
+            OswLaunch orc = c->slicer->osw->rec;
+            orc.n_k = rec.n_k;
+            bp.tails.osf.add(orc);
+        }
     }
     if (c->audio && s.a_n > 0) {
         AudioLaunch al = c->audio->rec;

@@ -1,5 +1,5 @@
 // rcf_plan.h -- the per-block schedule: what one commit of one front-end launches, built on the host first.  The stages
-// behind the FIRs (symbol filters, AGCs, the three symbol loops, the slicers behind the loops, the TSBK and EDACS stages behind the slicers) are one table, TailStages: a block's plan and a group's
+// behind the FIRs (symbol filters, AGCs, the three symbol loops, the slicers behind the loops, the TSBK, EDACS and OSW stages behind the slicers) are one table, TailStages: a block's plan and a group's
 // block each hold one, and the planner, the group's merge and the launcher visit it through TailStages::each.
 #pragma once
 #include <chrono>
@@ -89,6 +89,7 @@ struct TailStages {
     StageRecs<SliceLaunch> slf;        // slicers, behind the three loops: they read the loops' soft-symbol rings and counters
     StageRecs<TsbkLaunch> tsf;         // P25 trunking blocks, behind the slicers: they read the slicers' rings and counters
     StageRecs<EdacsLaunch> edf;        // EDACS control frames, behind the slicers likewise
+    StageRecs<OswLaunch> osf;          // SmartNet OSWs, behind the slicers likewise
     template <class F, class... T> static void each(F &&f, T &...t)
     {
         f(RCF_T_DISC, launch_fm_fir, t.symf...);
@@ -99,6 +100,7 @@ struct TailStages {
         f(RCF_T_SLICE, launch_slice, t.slf...);
         f(RCF_T_SLICE, launch_tsbk, t.tsf...);
         f(RCF_T_SLICE, launch_edacs, t.edf...);
+        f(RCF_T_SLICE, launch_osw, t.osf...);
     }
     void append(const TailStages &o) { each([](int, auto, auto &mine, const auto &theirs) { mine.append(theirs); }, *this, o); }
     bool upload(Arena &ar)

@@ -19,7 +19,7 @@ void counted_row(Stream *s, const void *ring, int64_t *cursor, const int64_t *co
 template <class L> void loop_row(L *l, Stream *s) { if (l) counted_row(s, l->ring(), &l->rd, static_cast<const int64_t *>(l->counters()), l->serial); }
 // ring, reader and counter of every row of kStreams and of the readers' rows behind it, in their order; a row that leaves the
 // ring null is refused
-void (*const kRows[kReadKinds])(Chan *, Stream *) = {
+void (*const kRows[kAllReadKinds])(Chan *, Stream *) = {
     [](Chan *c, Stream *s) { if (!c->fm_only) plain_row(c, s, c->d_iq, &c->rd_iq); },
     [](Chan *c, Stream *s) { plain_row(c, s, c->d_fm, &c->rd_fm); },
     [](Chan *c, Stream *s) { if (c->agc) plain_row(c, s, c->agc->rec.agc_ring, &c->agc->rd); },
@@ -32,6 +32,7 @@ void (*const kRows[kReadKinds])(Chan *, Stream *) = {
     [](Chan *c, Stream *s) { if (Chan::Slicer *l = c->slicer.get()) { counted_row(s, l->rec.hit_ring, &l->rd_hits, &l->rec.st->n_hits, 0); s->cap = l->hit_cap; } },
     [](Chan *c, Stream *s) { if (Chan::Slicer::Tsbk *t = c->slicer ? c->slicer->tsbk.get() : nullptr) { counted_row(s, t->rec.rec_ring, &t->rd, &t->rec.st->n_records, 0); s->cap = t->cap; } },
     [](Chan *c, Stream *s) { if (Chan::Slicer::Edacs *t = c->slicer ? c->slicer->edacs.get() : nullptr) { counted_row(s, t->rec.rec_ring, &t->rd, &t->rec.st->n_records, 0); s->cap = t->cap; } },
+    [](Chan *c, Stream *s) { if (Chan::Slicer::Osw *t = c->slicer ? c->slicer->osw.get() : nullptr) { counted_row(s, t->rec.rec_ring, &t->rd, &t->rec.st->n_records, 0); s->cap = t->cap; } },
 };
 
 }  // namespace
@@ -224,6 +225,7 @@ int64_t rcf_chan_read_hard(rcf_t *h, int chan_id, uint32_t *out, size_t n) { ret
 int64_t rcf_chan_read_sync(rcf_t *h, int chan_id, uint32_t *out, size_t n) { return chan_read_one(h, chan_id, RCF_HARD_SYNC, 1.0f, out, n); }
 int64_t rcf_chan_read_tsbk(rcf_t *h, int chan_id, uint32_t *out, size_t n) { return chan_read_one(h, chan_id, RCF_HARD_TSBK, 1.0f, out, n); }
 int64_t rcf_chan_read_edacs(rcf_t *h, int chan_id, uint32_t *out, size_t n) { return chan_read_one(h, chan_id, RCF_HARD_EDACS, 1.0f, out, n); }
+int64_t rcf_chan_read_osw(rcf_t *h, int chan_id, uint32_t *out, size_t n) { return chan_read_one(h, chan_id, RCF_HARD_OSW, 1.0f, out, n); }
 
 int rcf_chan_read_many(rcf_t *h, int what, const int *chan_ids, int n_chans, float gain, void *out, size_t cap_each,
                        int64_t *counts)
@@ -290,6 +292,16 @@ int rcf_chan_edacs_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity
     FIND_CHAN(h, chan_id, c);
     if (!c->slicer || !c->slicer->edacs) { set_error(read_row(kEdacs).refusal, chan_id); return RCF_ESTATE; }   // (closed in between)
     if (capacity) *capacity = c->slicer->edacs->cap;
+    return RCF_OK;
+}
+int rcf_chan_osw_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity)
+{
+    const int rc = chan_rings(h, chan_id, kOsw, true, rec_ring, nullptr, nullptr);
+    if (rc != RCF_OK) return rc;
+    std::lock_guard<std::mutex> g(h->mu);
+    FIND_CHAN(h, chan_id, c);
+    if (!c->slicer || !c->slicer->osw) { set_error(read_row(kOsw).refusal, chan_id); return RCF_ESTATE; }   // (closed in between)
+    if (capacity) *capacity = c->slicer->osw->cap;
     return RCF_OK;
 }
 

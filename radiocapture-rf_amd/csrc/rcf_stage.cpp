@@ -1,6 +1,6 @@
 // rcf_stage.cpp -- the optional stages behind a channel's rings (the records of Chan, rcf_state.h): the P25 symbol filter,
 // the feed-forward AGC, the SmartNet / EDACS symbol clock, the P25 CQPSK Gardner / Costas loop, the P25 C4FM symbol loop and
-// the analog voice chain, the slicer behind one of the loops and the P25 trunking stage or the EDACS control-frame stage behind the slicer.
+// the analog voice chain, the slicer behind one of the loops and the P25 trunking stage, the EDACS control-frame stage or the SmartNet OSW stage behind the slicer.
 // Attach, off, and what they produced.
 // An attach function allocates into Fresh<> holders and builds the new record completely; only then is it swapped into
 // the channel and the old one released.  A HIP call that fails before that leaves the channel as it was.
@@ -11,6 +11,7 @@
 #define RCF_DEVCONST static const
 #include "tsbk_core.hpp"       // (kTsbkNoFrame, kTsbkRecWords)
 #include "edacs_core.hpp"      // (kEdacsNoFrame, kEdacsRecWords; slice_sync_both_ok of slice_core.hpp)
+#include "osw_core.hpp"        // (kOswSyncBits, kOswRecWords)
 
 namespace rcfx {
 
@@ -18,7 +19,8 @@ void Chan::Sym::release(rcf_t *h) { bury(h, rec.sym_ring); bury(h, const_cast<fl
 void Chan::Agc::release(rcf_t *h) { bury(h, rec.agc_ring); rec.agc_ring = nullptr; }
 void Chan::Slicer::release_tsbk(rcf_t *h) { if (tsbk) { bury(h, tsbk->rec.rec_ring); tsbk.reset(); } }     // one allocation
 void Chan::Slicer::release_edacs(rcf_t *h) { if (edacs) { bury(h, edacs->rec.rec_ring); edacs.reset(); } }   // one allocation
-void Chan::Slicer::release(rcf_t *h) { release_tsbk(h); release_edacs(h); bury(h, rec.word_ring); rec = SliceLaunch{}; }     // one allocation; the TSBK / EDACS stage goes with its slicer
+void Chan::Slicer::release_osw(rcf_t *h) { if (osw) { bury(h, osw->rec.rec_ring); osw.reset(); } }           // one allocation
+void Chan::Slicer::release(rcf_t *h) { release_tsbk(h); release_edacs(h); release_osw(h); bury(h, rec.word_ring); rec = SliceLaunch{}; }     // one allocation; the TSBK / EDACS / OSW stage goes with its slicer
 void Chan::Audio::release(rcf_t *h) { bury(h, rec.st); bury(h, rec.a_ring); bury(h, const_cast<float *>(rec.lpf)); rec = AudioLaunch{}; }
 
 }  // namespace rcfx
@@ -486,6 +488,69 @@ int rcf_chan_edacs_state(rcf_t *h, int chan_id, rcf_edacs_state_t *out)
     const int rc = stage_state(h, c->slicer->edacs->rec.st, &st, offsetof(EdacsState, next_hit));
     if (rc != RCF_OK) return rc;
     out->n_records = st.n_records; out->n_frames = st.n_frames; out->n_msgs = st.n_msgs; out->n_msgs_none = st.n_msgs_none; out->n_lost = st.n_lost;
+    return RCF_OK;
+}
+
+// ---- SmartNet OSWs behind the slicer (osw.hip)
+int rcf_chan_osw(rcf_t *h, int chan_id, const rcf_osw_params_t *p)
+{
+    if (!h) return RCF_EINVAL;
+    int cap = 256;
+    if (p) {
+        if (p->capacity) cap = p->capacity;
+        if (cap < 16 || cap > (1 << 20) || (cap & (cap - 1))) { set_error("OSW stage: capacity %d is not a power of two 16 .. 2^20", p->capacity); return RCF_EINVAL; }
+    }
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!p) {
+        if (c->slicer && c->slicer->osw) { c->slicer->release_osw(h); ++h->chans_epoch; }
+        return RCF_OK;
+    }
+    if (!c->slicer || c->slicer->rec.bps != 1 || c->slicer->rec.sync_bits != kOswSyncBits || c->slicer->rec.sync_max_errors != 0 || c->slicer->rec.sync_both) {
+        set_error("channel %d has no slicer in RCF_SLICE_BINARY mode that searches an 8-bit sync word exactly, in one polarity", chan_id);
+        return RCF_ESTATE;
+    }
+    const SliceLaunch &sl = c->slicer->rec;
+    std::unique_ptr<Chan::Slicer::Osw> k(new Chan::Slicer::Osw);
+    OswLaunch &r = k->rec;
+    r.src = sl.st;
+    r.word_ring = sl.word_ring; r.hit_ring = sl.hit_ring;
+    r.word_mask = sl.word_mask; r.hit_mask = sl.hit_mask; r.rec_mask = (uint32_t)cap - 1;
+    k->cap = (uint32_t)cap;
+    // the stage's first hit and its cursor: the slicer's counts as of everything queued (one round trip)
+    SliceState now{};
+    const int rc = stage_state(h, sl.st, &now, offsetof(SliceState, partial));
+    if (rc != RCF_OK) return rc;
+    OswState st0{};
+    st0.next_hit = now.n_hits;
+    st0.pos = now.n_symbols;
+    constexpr size_t kStateWords = 256 / sizeof(uint32_t);
+    static_assert(sizeof(OswState) <= 256, "the state's slot");
+    const size_t state_at = (size_t)cap * kOswRecWords;                    // in words (cap >= 16: the state's 64-bit fields are aligned)
+    Fresh<uint32_t> fresh;
+    RCF_HIP(fresh.alloc(state_at + kStateWords));
+    if (!hip_ok(hipMemcpy(fresh.p + state_at, &st0, sizeof(st0), hipMemcpyHostToDevice), "hipMemcpy(OSW state)")) return RCF_EHIP;
+    r.rec_ring = fresh.take();
+    r.st = reinterpret_cast<OswState *>(r.rec_ring + state_at);
+    c->slicer->release_osw(h);
+    c->slicer->osw = std::move(k);
+    ++h->chans_epoch;
+    return RCF_OK;
+}
+
+int rcf_chan_osw_state(rcf_t *h, int chan_id, rcf_osw_state_t *out)
+{
+    if (!h || !out) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!c->slicer || !c->slicer->osw) { set_error("channel %d has no OSW stage (rcf_chan_osw)", chan_id); return RCF_ESTATE; }
+    OswState st{};                      // (its five counters and the lock)
+    const int rc = stage_state(h, c->slicer->osw->rec.st, &st, offsetof(OswState, next_hit));
+    if (rc != RCF_OK) return rc;
+    out->n_records = st.n_records; out->n_frames = st.n_frames; out->n_bad = st.n_bad; out->n_rejects = st.n_rejects; out->n_lost = st.n_lost;
+    out->locked = st.locked; out->is_locked = st.is_locked;
     return RCF_OK;
 }
 

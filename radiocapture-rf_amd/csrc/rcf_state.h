@@ -3,7 +3,7 @@
 //   rcf_handle.cpp   open / close / sync, pools, wideband ingest        rcf_plan.cpp    the per-block schedule (host)
 //   rcf_launch.cpp   the block's launches in dependency order           rcf_chan.cpp    channels: lifecycle, taps, queries
 //   rcf_stage.cpp    a channel's optional stages: symbol filter, AGC,   rcf_read.cpp    a channel's streams (one descriptor, Stream)
-//                    symbol loops, slicer, TSBK / EDACS stages, voice chain (attach / off)                    and the one read path of every host read
+//                    symbol loops, slicer, TSBK / EDACS / OSW stages, voice chain (attach / off)                    and the one read path of every host read
 //   rcf_streams.h    the stream table and the readers' integer rules (no HIP: g++ alone compiles it)
 //   rcf_bank.cpp     filterbank + scanner ABI                           rcf_timing.cpp  HIP-event timing
 //   rcf_comm.cpp     RCCL peak-list exchange                            rcf_group.cpp   grouped launches over front-ends
@@ -188,10 +188,18 @@ struct Chan {
             int64_t rd = 0;
         };
         std::unique_ptr<Edacs> edacs;
+        // SmartNet OSWs (rcf_chan_osw), behind a binary slicer that searches the 8-bit word: the same arrangement
+        struct Osw {
+            OswLaunch rec{};
+            uint32_t cap = 0;
+            int64_t rd = 0;
+        };
+        std::unique_ptr<Osw> osw;
         size_t reach() const { return 0; }                               // it reads the loop's ring, never the channel's
         void release(rcf_t *h);
         void release_tsbk(rcf_t *h);
         void release_edacs(rcf_t *h);
+        void release_osw(rcf_t *h);
     };
     std::unique_ptr<Audio> audio;
     std::unique_ptr<Slicer> slicer;
@@ -201,7 +209,7 @@ struct Chan {
     {
         f(sym, sizeof(FmFirLaunch), false); f(agc, sizeof(AgcLaunch), false); f(clock, sizeof(ClockLaunch), false);
         f(costas, sizeof(CostasLaunch), false); f(fsk4, sizeof(Fsk4Launch), false); f(audio, sizeof(AudioLaunch), true);
-        f(slicer, sizeof(SliceLaunch) + std::max(sizeof(TsbkLaunch), sizeof(EdacsLaunch)) + 64, false);    // (with the TSBK or EDACS stage it may carry)
+        f(slicer, sizeof(SliceLaunch) + std::max({sizeof(TsbkLaunch), sizeof(EdacsLaunch), sizeof(OswLaunch)}) + 64, false);    // (with the TSBK, EDACS or OSW stage it may carry)
     }
     // ---- the rest
     float incr[2] = {1.f, 0.f};   // exact rotator: what GNU Radio iterates
@@ -473,14 +481,14 @@ template <class S, class R, float *R::*Ring> void Chan::Loop<S, R, Ring>::releas
 // ---- the one read path.  A stream is a device ring of `cap` items (a power of two) of item_w 4-byte words: item i at word
 // (i & (cap - 1)) * stride_w of ring when stride_w > 1 (one bin of a frame-major ring of floats), else at
 // (i & (cap - 1)) * item_w.  A plain stream's end the host knows: the ring holds the cap items before `newest`, a reader at
-// *cursor may take up to `end`.  A counted stream -- counter != nullptr: a symbol loop's, the voice chain's, the slicer's, the TSBK and EDACS stages' --
+// *cursor may take up to `end`.  A counted stream -- counter != nullptr: a symbol loop's, the voice chain's, the slicer's, the TSBK, EDACS and OSW stages' --
 // ends at ceil(*counter * interp / decim) of a DEVICE counter, which the counted gather reads itself (CountedRec,
 // rcf_internal.h); serial: which attachment of the stage this is (a re-attached stage starts a new stream)
 struct Stream {
     rcf_t *h = nullptr;
     const void *ring = nullptr;
     uint32_t item_w = 1, stride_w = 0;
-    uint32_t cap = 0;                  // the handle's out_cap, or the ring's own (the slicer's hit ring, the TSBK and EDACS records')
+    uint32_t cap = 0;                  // the handle's out_cap, or the ring's own (the slicer's hit ring, the TSBK, EDACS and OSW records')
     int64_t *cursor = nullptr;
     int64_t end = 0, newest = 0;       // plain
     const int64_t *counter = nullptr;  // counted

@@ -8,7 +8,9 @@ The discriminator and the Mueller and Mueller clock run per channel on the GPU (
 symbols at 3600 or 9600 per second (chan_read_clock), slices and packs them (pack_bits) and does the packet framing -- or,
 with hard=True, lets the GPU slice, pack and look for the frame sync (rcf_chan_slicer) and reads packed bits and the places
 frames begin (chan_read_hard, chan_read_sync).  For EDACS the GPU goes one step further with frames=True: framing, the BCH
-decode of the six copies and the election of the two messages (rcf_chan_edacs; chan_read_edacs, edacs_messages)."""
+decode of the six copies and the election of the two messages (rcf_chan_edacs; chan_read_edacs, edacs_messages).  For
+SmartNet likewise with osw=True: the 84-bit framing with its lock counter, deinterleave, the parity syndrome and its
+correction (rcf_chan_osw; chan_read_osw, smartnet_osws)."""
 import numpy as np
 
 from . import native
@@ -23,13 +25,27 @@ SMARTNET_SYNC, SMARTNET_SYNC_BITS = 0b10101100, 8      # moto_control_demod.py:2
 EDACS_SYNC, EDACS_SYNC_BITS = 0b010101010101010101010111000100100101010101010101, 48
 
 
-def smartnet_clock(fe, cid, channel_rate=25000, symbol_rate=3600.0, hard=False):
+def smartnet_clock(fe, cid, channel_rate=25000, symbol_rate=3600.0, hard=False, osw=False):
     """clock_recovery_mm_ff(channel_rate / symbol_rate, ...) behind quadrature_demod_cf(5) on channel `cid` of Frontend
     `fe` (moto_control_demod.py:103-113: channel_rate = 2 x 12500, symbol_rate = 3600.0 at :50).  hard=True also attaches
-    the slicer behind the clock: binary, exact matches of the 8-bit frame sync."""
+    the slicer behind the clock: binary, exact matches of the 8-bit frame sync.  With osw=True as well the OSW stage sits
+    behind it: chan_read_osw gives a record per frame, smartnet_osws the fields the reference publishes."""
     fe.chan_clock_mm(cid, channel_rate / symbol_rate, GAIN_OMEGA, MU, GAIN_MU, OMEGA_RELATIVE_LIMIT, QUAD_GAIN)
     if hard:
         fe.chan_slicer(cid, native.READ_CLOCK, native.SLICE_BINARY, sync_word=SMARTNET_SYNC, sync_bits=SMARTNET_SYNC_BITS)
+        if osw:
+            fe.chan_osw(cid)
+
+
+def smartnet_osws(records):
+    """records of the OSW stage (Frontend.chan_read_osw, native.OSW_DTYPE) -> list of (k, cmd, ind, lid, tg, status, bad,
+    is_locked) in the stream's order: k the low 32 bits of the packet's sync position; cmd, ind ('G' / 'I'), lid, tg =
+    lid & 0xfff0 and status = lid & 0xf as receive_engine publishes them (moto_control_demod.py:325-339); bad: the packet
+    counted into packets_bad; is_locked as the frame left it"""
+    records = np.asarray(records, dtype=native.OSW_DTYPE)
+    f = native.osw_fields(records)
+    return [(int(r["k"]), int(r["cmd"]), "G" if ind else "I", int(r["lid"]), int(r["lid"]) & 0xfff0, int(r["lid"]) & 0xf,
+             bool(bad), bool(lk)) for r, ind, bad, lk in zip(records, f["individual"], f["bad"], f["is_locked"])]
 
 
 def edacs_clock(fe, cid, receive_rate=25000, symbol_rate=9600.0, hard=False, frames=False, esk=False):

@@ -40,6 +40,7 @@ SYMBOLS = [
     "rcf_chan_slicer", "rcf_chan_slicer_state", "rcf_chan_read_hard", "rcf_chan_read_sync", "rcf_chan_slicer_rings",
     "rcf_chan_tsbk", "rcf_chan_tsbk_state", "rcf_chan_read_tsbk", "rcf_chan_tsbk_ring",
     "rcf_chan_edacs", "rcf_chan_edacs_state", "rcf_chan_read_edacs", "rcf_chan_edacs_ring",
+    "rcf_chan_osw", "rcf_chan_osw_state", "rcf_chan_read_osw", "rcf_chan_osw_ring",
     "rcf_design_firdes", "rcf_design_optfir_low_pass", "rcf_design_fm_deemph", "rcf_design_resampler", "rcf_chan_audio_open",
     "rcf_chan_audio_close", "rcf_chan_audio_produced", "rcf_chan_read_audio",
     "rcf_host_alloc", "rcf_host_free", "rcf_comm_unique_id", "rcf_comm_init", "rcf_comm_destroy", "rcf_comm_size",
@@ -59,13 +60,19 @@ HARD_BITS, HARD_SYNC = 32, 33
 HARD_TSBK = 48
 # ... and of the EDACS stage (RCF_HARD_EDACS): records of 8 uint32 too, one per frame
 HARD_EDACS = 49
-_HARD_WHAT = {"hard": HARD_BITS, "sync": HARD_SYNC, "tsbk": HARD_TSBK, "edacs": HARD_EDACS}
+# ... and of the SmartNet OSW stage (RCF_HARD_OSW): records of 8 uint32 as well, one per frame
+HARD_OSW = 51
+_HARD_WHAT = {"hard": HARD_BITS, "sync": HARD_SYNC, "tsbk": HARD_TSBK, "edacs": HARD_EDACS, "osw": HARD_OSW}
 # a record of RCF_HARD_TSBK (rcf.h at rcf_chan_tsbk): word 0 (see tsbk_fields), the low 32 bits of k, the 12 decoded octets,
 # the NID's 8 octets, frame_dibits
 TSBK_DTYPE = np.dtype([("flags", "<u4"), ("k", "<u4"), ("octets", "u1", (12,)), ("nid", "u1", (8,)), ("frame_dibits", "<u4")])
 # a record of RCF_HARD_EDACS (rcf.h at rcf_chan_edacs): word 0 (see edacs_fields), the low 32 bits of k, the five octets of
 # m1 and of m2, each in a field of eight
 EDACS_DTYPE = np.dtype([("flags", "<u4"), ("k", "<u4"), ("m1", "u1", (8,)), ("m2", "u1", (8,)), ("zero", "<u4", (2,))])
+# a record of RCF_HARD_OSW (rcf.h at rcf_chan_osw): word 0 (see osw_fields), the low 32 bits of the packet's sync position,
+# lid and cmd, the 38 corrected data bits and the 38 syndrome bits as octets (five each, in a field of eight), locked
+OSW_DTYPE = np.dtype([("flags", "<u4"), ("k", "<u4"), ("lid", "<u2"), ("cmd", "<u2"), ("data", "u1", (8,)), ("psyn", "u1", (8,)),
+                      ("locked", "<i4")])
 SLICE_BINARY, SLICE_FSK4 = 1, 2
 T_FIR, T_PFB, T_FIR_DERIVED, T_DISC, T_SCAN_FFT, T_SCAN_MOVSUM, T_HISTORY, T_FIR_MFMA, T_AUDIO, T_TAPS, T_CLOCK, T_COSTAS, T_FSK4, T_SLICE = range(14)
 
@@ -200,6 +207,27 @@ def edacs_fields(records):
                 status=np.stack([((f >> (10 + 2 * c)) & 3).astype(np.uint8) for c in range(6)], axis=-1))
 
 
+class OswParams(C.Structure):
+    """rcf_osw_params_t (include/rcf.h)"""
+    _fields_ = [("capacity", C.c_int), ("reserved_", C.c_int * 3)]
+
+
+class OswState(C.Structure):
+    """rcf_osw_state_t (include/rcf.h)"""
+    _fields_ = [("n_records", C.c_int64), ("n_frames", C.c_int64), ("n_bad", C.c_int64), ("n_rejects", C.c_int64),
+                ("n_lost", C.c_int64), ("locked", C.c_int32), ("is_locked", C.c_int32)]
+
+
+def osw_fields(records):
+    """word 0 of OSW records taken apart -> dict of arrays: at_cursor (the sync word stood at the cursor), bad (syndrome
+    nonzero), is_locked, individual, flipped (data bits corrected), syn_bits (set syndrome bits), rel (bits between the cursor
+    and the sync word; 65535: that many or more, or not determined)"""
+    f = np.asarray(records["flags"], dtype=np.uint32)
+    return dict(at_cursor=(f & 1).astype(np.uint8), bad=((f >> 1) & 1).astype(np.uint8), is_locked=((f >> 2) & 1).astype(np.uint8),
+                individual=((f >> 3) & 1).astype(np.uint8), flipped=((f >> 4) & 63).astype(np.uint8),
+                syn_bits=((f >> 10) & 63).astype(np.uint8), rel=(f >> 16).astype(np.uint16))
+
+
 def widen_hits(items, n_symbols):
     """the hit ring's uint32 items -> (k as int64, dist as uint8): k is the largest value <= n_symbols - 1 with the item's low
     26 bits (rcf.h at rcf_chan_slicer), n_symbols the stage's count when the items were read or later"""
@@ -305,6 +333,10 @@ def lib():
         "rcf_chan_edacs_state": (C.c_int, [vp, C.c_int, C.POINTER(EdacsState)]),
         "rcf_chan_read_edacs": (i64, [vp, C.c_int, C.POINTER(C.c_uint32), sz]),
         "rcf_chan_edacs_ring": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]),
+        "rcf_chan_osw": (C.c_int, [vp, C.c_int, C.POINTER(OswParams)]),
+        "rcf_chan_osw_state": (C.c_int, [vp, C.c_int, C.POINTER(OswState)]),
+        "rcf_chan_read_osw": (i64, [vp, C.c_int, C.POINTER(C.c_uint32), sz]),
+        "rcf_chan_osw_ring": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]),
         "rcf_design_mmse_interpolator": (C.c_int, [C.c_int, C.c_int, C.c_double, fp, C.c_int]),
         "rcf_chan_fm_level": (C.c_int, [vp, C.c_int, C.c_float, C.c_int, fp]),
         "rcf_design_firdes": (C.c_int, [C.c_int] + [C.c_double] * 4 + [C.c_int, C.c_double, fp, C.c_int]),
@@ -392,7 +424,7 @@ def lib():
 def _read_what(what, stages=False):
     """the batched readers' and the pump's `what`: "iq", "agc", anything else the discriminator (as it always was).
     stages=True -- how every reader of this module calls it -- also names the stages' streams: "sym", "clock", "costas",
-    "fsk4", "audio", the slicer's "hard" and "sync", the TSBK stage's "tsbk" and the EDACS stage's "edacs".  The one-argument form keeps its old answers ("sym" was never a
+    "fsk4", "audio", the slicer's "hard" and "sync", the TSBK stage's "tsbk", the EDACS stage's "edacs" and the OSW stage's "osw".  The one-argument form keeps its old answers ("sym" was never a
     stream there: the discriminator)."""
     if stages and what in _STAGE_WHAT:
         return _STAGE_WHAT[what]
@@ -403,12 +435,14 @@ def _read_what(what, stages=False):
 
 def _read_dtype(what):
     """item type of stream `what` as the readers deliver it: cf32 for "iq" and "agc", uint32 for the slicer's "hard" and
-    "sync", TSBK_DTYPE for "tsbk", EDACS_DTYPE for "edacs", float32 for everything else"""
+    "sync", TSBK_DTYPE for "tsbk", EDACS_DTYPE for "edacs", OSW_DTYPE for "osw", float32 for everything else"""
     w = _read_what(what, True)
     if w == HARD_TSBK:
         return TSBK_DTYPE
     if w == HARD_EDACS:
         return EDACS_DTYPE
+    if w == HARD_OSW:
+        return OSW_DTYPE
     return np.complex64 if w in (READ_IQ, READ_AGC) else np.uint32 if w in (HARD_BITS, HARD_SYNC) else np.float32
 
 
@@ -773,7 +807,7 @@ class Frontend:
         copies), None where the channel no longer exists (or lacks the stream).  what: "iq", "fm" (x gain), "agc", or a
         stage's stream -- "sym", "clock", "costas", "fsk4", "audio": float32, from where that stage's single reader stands --
         or the slicer's "hard" (packed words) / "sync" (hit items, see widen_hits): uint32 -- or the TSBK stage's "tsbk":
-        TSBK_DTYPE records -- or the EDACS stage's "edacs": EDACS_DTYPE records"""
+        TSBK_DTYPE records -- or the EDACS stage's "edacs": EDACS_DTYPE records -- or the OSW stage's "osw": OSW_DTYPE records"""
         n = len(cids)
         dt = _read_dtype(what)
         if out is None:
@@ -1008,6 +1042,35 @@ class Frontend:
     def chan_edacs_ring(self, cid):
         """(device pointer, capacity in records) of the stage's record ring (rcf_chan_edacs_ring)"""
         return self._ring_of(lib().rcf_chan_edacs_ring, cid)
+
+    def chan_osw(self, cid, capacity=0, on=True):
+        """SmartNet OSWs behind the channel's binary slicer (rcf_chan_osw): the 84-bit framing with its lock counter,
+        deinterleave, parity syndrome and correction on the GPU; records of OSW_DTYPE in a ring of `capacity` (0: 256).  It
+        starts at the slicer's next symbol with locked = 0; on=False switches it off."""
+        if not on:
+            _check(lib().rcf_chan_osw(self._h, cid, None))
+            return
+        p = OswParams()
+        p.capacity = int(capacity)
+        _check(lib().rcf_chan_osw(self._h, cid, C.byref(p)))
+
+    def chan_osw_state(self, cid) -> dict:
+        """n_records, n_frames (the reference's packets), n_bad (packets_bad), n_rejects, n_lost, locked, is_locked of the OSW
+        stage as of the last block (rcf_chan_osw_state; syncs the stream)"""
+        st = OswState()
+        _check(lib().rcf_chan_osw_state(self._h, cid, C.byref(st)))
+        return _state_dict(st)
+
+    def chan_read_osw(self, cid, max_records=1 << 12) -> np.ndarray:
+        """unread records of the OSW stage, oldest first: a structured array of OSW_DTYPE (osw_fields takes `flags` apart,
+        rcf.control.smartnet_osws gives the fields the reference publishes)"""
+        out = np.empty(max_records, dtype=OSW_DTYPE)
+        n = _check(lib().rcf_chan_read_osw(self._h, cid, out.ctypes.data_as(C.POINTER(C.c_uint32)), max_records))
+        return out[:n].copy()
+
+    def chan_osw_ring(self, cid):
+        """(device pointer, capacity in records) of the stage's record ring (rcf_chan_osw_ring)"""
+        return self._ring_of(lib().rcf_chan_osw_ring, cid)
 
     def chan_fsk4_ring(self, cid):
         """(device pointer, capacity) of the stage's float32 soft-symbol ring (rcf_chan_fsk4_ring)"""
