@@ -16,21 +16,14 @@
 // the lanes 0 .. 7 store the record's eight words.
 // All trip counts come from the host's n_k; the counters read from the device only clamp.  Every ring index is masked.  Plain
 // vector stores only; nothing is shared between waves; no LDS.
-#include "rcf_internal.h"
+#include "item_wave.hpp"
 #include "edacs_core.hpp"
 
 namespace rcfx {
 
 namespace {
 
-constexpr int kEdacsWaves = 4;
-
-__device__ __forceinline__ int64_t rl_i64(int64_t v, int src)
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)v, src);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), src);
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
+constexpr int kEdacsWaves = kItemWaves;
 
 __global__ __launch_bounds__(64 * kEdacsWaves) void edacs_kernel(const EdacsLaunch *__restrict__ items, int n_items)
 {
@@ -121,8 +114,7 @@ __global__ __launch_bounds__(64 * kEdacsWaves) void edacs_kernel(const EdacsLaun
 // ring_mask: unused -- every record carries the masks of its three rings
 void launch_edacs(const EdacsLaunch *d_items, int n_items, int max_n_k, uint64_t, hipStream_t s)
 {
-    if (n_items <= 0 || max_n_k <= 0) return;
-    hipLaunchKernelGGL(edacs_kernel, dim3((n_items + kEdacsWaves - 1) / kEdacsWaves), dim3(64 * kEdacsWaves), 0, s, d_items, n_items);
+    launch_item_waves(edacs_kernel, d_items, n_items, max_n_k, s);
 }
 
 }  // namespace rcfx

@@ -20,21 +20,14 @@
 // ends the launch undecided, one skips a frame the word ring has lost (after it pos is inside the ring: once a launch).
 // All trip counts come from the host's n_k; the counters read from the device only clamp.  Every ring index is masked.  Plain
 // vector stores only; nothing is shared between waves; no LDS.
-#include "rcf_internal.h"
+#include "item_wave.hpp"
 #include "osw_core.hpp"
 
 namespace rcfx {
 
 namespace {
 
-constexpr int kOswWaves = 4;
-
-__device__ __forceinline__ int64_t osw_rl_i64(int64_t v, int src)
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)v, src);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), src);
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
+constexpr int kOswWaves = kItemWaves;
 
 __global__ __launch_bounds__(64 * kOswWaves) void osw_kernel(const OswLaunch *__restrict__ items, int n_items)
 {
@@ -66,13 +59,13 @@ __global__ __launch_bounds__(64 * kOswWaves) void osw_kernel(const OswLaunch *__
             const int a = __builtin_ctzll(ge);
             i += a;
             if (a > 64 - kOswSyncBits - 1) continue;                                         // h1 may lie past these 64: again, from h0
-            h0 = osw_rl_i64(h, a);
+            h0 = rl_i64(h, a);
         }
         if (resync) { resync = false; if (have0) pos = h0; }
         if (!osw_ready(locked, have0, h0, pos, W)) break;                                    // not all there yet: the next launch
         const uint64_t ge1 = have0 ? __ballot(valid && h >= h0 + kOswSyncBits) : 0;
         const bool have1 = ge1 != 0;
-        const int64_t h1 = have1 ? osw_rl_i64(h, __builtin_ctzll(ge1)) : 0;
+        const int64_t h1 = have1 ? rl_i64(h, __builtin_ctzll(ge1)) : 0;
         bool rel_nz;
         uint32_t rel;
         if (osw_decide(locked, have0, h0, have1, h1, pos, &rel_nz, &rel) == kOswReject) { pos = h0 + kOswSyncBits; ++n_rejects; continue; }
@@ -108,8 +101,7 @@ __global__ __launch_bounds__(64 * kOswWaves) void osw_kernel(const OswLaunch *__
 // ring_mask: unused -- every record carries the masks of its three rings
 void launch_osw(const OswLaunch *d_items, int n_items, int max_n_k, uint64_t, hipStream_t s)
 {
-    if (n_items <= 0 || max_n_k <= 0) return;
-    hipLaunchKernelGGL(osw_kernel, dim3((n_items + kOswWaves - 1) / kOswWaves), dim3(64 * kOswWaves), 0, s, d_items, n_items);
+    launch_item_waves(osw_kernel, d_items, n_items, max_n_k, s);
 }
 
 }  // namespace rcfx

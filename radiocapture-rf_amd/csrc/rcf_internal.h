@@ -352,6 +352,17 @@ struct SliceLaunch {
     int32_t sync_both;       // 1: a window within sync_max_errors of the inverted word is a hit too
 };
 void launch_slice(const SliceLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
+// What the launch records of the frame decoders behind a slicer (TSBK, EDACS, OSW) begin with, State being the decoder's
+// own state record: n_records first, next_hit somewhere behind its counters.  (The records derive from it rather than
+// being it: the kernels keep their names.)
+template <class State> struct FramesLaunch {
+    const SliceState *src;   // the slicer's counters (device)
+    const uint32_t *word_ring, *hit_ring;    // the slicer's two rings
+    State *st;
+    uint32_t *rec_ring;
+    uint32_t word_mask, hit_mask, rec_mask;
+    int32_t n_k;             // the slicer's n_k of this block: at most that many new symbols, and so new hits
+};
 // P25 trunking blocks behind a slicer (tsbk.hip; procTSDU of the reference: status symbols, NID, deinterleave, rate-1/2
 // trellis, CRC; definition: include/rcf.h at rcf_chan_tsbk).
 // per-channel running state, device resident, owned by tsbk_kernel
@@ -361,14 +372,7 @@ struct TsbkState {
     int64_t next_hit;        // the first hit of the slicer's stream that is neither rejected nor decided
     int64_t k_last;          // the last accepted hit's k
 };
-struct TsbkLaunch {
-    const SliceState *src;   // the slicer's counters (device)
-    const uint32_t *word_ring, *hit_ring;    // the slicer's two rings
-    TsbkState *st;
-    uint32_t *rec_ring;
-    uint32_t word_mask, hit_mask, rec_mask;
-    int32_t n_k;             // the slicer's n_k of this block: at most that many new symbols, and so new hits
-};
+struct TsbkLaunch : FramesLaunch<TsbkState> {};
 void launch_tsbk(const TsbkLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
 // EDACS control frames behind a slicer (edacs.hip; get_next_frame, packet_framer, bch_decode, message_election of the
 // reference: six 40-bit copies per frame, BCH(48,36) over GF(64), two of three; definition: include/rcf.h at rcf_chan_edacs).
@@ -380,13 +384,7 @@ struct EdacsState {
     int64_t k_last;          // the last accepted hit's k
 };
 constexpr uint32_t kEdacsFlagBoth = 1u, kEdacsFlagEsk = 2u;   // EdacsLaunch::flags: the slicer's sync_both, the stage's esk
-struct EdacsLaunch {
-    const SliceState *src;   // the slicer's counters (device)
-    const uint32_t *word_ring, *hit_ring;    // the slicer's two rings
-    EdacsState *st;
-    uint32_t *rec_ring;
-    uint32_t word_mask, hit_mask, rec_mask;
-    int32_t n_k;             // the slicer's n_k of this block: at most that many new symbols, and so new hits
+struct EdacsLaunch : FramesLaunch<EdacsState> {
     uint32_t flags;
 };
 void launch_edacs(const EdacsLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
@@ -400,15 +398,21 @@ struct OswState {
     int64_t next_hit;        // the first hit of the slicer's stream that may still start at or behind pos
     int64_t pos;             // the cursor: the first bit no step has passed
 };
-struct OswLaunch {
-    const SliceState *src;   // the slicer's counters (device)
-    const uint32_t *word_ring, *hit_ring;    // the slicer's two rings
-    OswState *st;
-    uint32_t *rec_ring;
-    uint32_t word_mask, hit_mask, rec_mask;
-    int32_t n_k;             // the slicer's n_k of this block: at most that many new symbols, and so new hits
-};
+struct OswLaunch : FramesLaunch<OswState> {};
 void launch_osw(const OswLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
+// the records' layouts as the kernels were compiled for them
+#pragma GCC diagnostic push
+#pragma GCC diagnostic ignored "-Winvalid-offsetof"
+template <class L> constexpr bool frames_launch_layout()
+{
+    return offsetof(L, src) == 0 && offsetof(L, word_ring) == 8 && offsetof(L, hit_ring) == 16 && offsetof(L, st) == 24 &&
+           offsetof(L, rec_ring) == 32 && offsetof(L, word_mask) == 40 && offsetof(L, hit_mask) == 44 && offsetof(L, rec_mask) == 48 &&
+           offsetof(L, n_k) == 52;
+}
+static_assert(frames_launch_layout<TsbkLaunch>() && sizeof(TsbkLaunch) == 56, "TsbkLaunch");
+static_assert(frames_launch_layout<OswLaunch>() && sizeof(OswLaunch) == 56, "OswLaunch");
+static_assert(frames_launch_layout<EdacsLaunch>() && sizeof(EdacsLaunch) == 64 && offsetof(EdacsLaunch, flags) == 56, "EdacsLaunch");
+#pragma GCC diagnostic pop
 // mean of gain * fm over the last `window` samples ending at n_end (exclusive), one workgroup
 void launch_fm_level(const float *fm_ring, int64_t n_end, int window, float gain, uint64_t ring_mask, float *d_out,
                      hipStream_t s);

@@ -354,21 +354,13 @@ int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c)
         SliceLaunch rec = c->slicer->rec;
         rec.n_k = (int32_t)(s.n_lo + s.cnt - std::max(s.n_lo, from));
         if (rec.n_k > 0) bp.tails.slf.add(rec);
-        if (rec.n_k > 0 && c->slicer->tsbk) {      // the stage behind it sees what this block's slicer launch wrote
-            TsbkLaunch tr = c->slicer->tsbk->rec;
-            tr.n_k = rec.n_k;
-            bp.tails.tsf.add(tr);
-        }
-        if (rec.n_k > 0 && c->slicer->edacs) {
-            EdacsLaunch er = c->slicer->edacs->rec;
-            er.n_k = rec.n_k;
-            bp.tails.edf.add(er);
-        }
-        if (rec.n_k > 0 && c->slicer->osw) {
-            OswLaunch orc = c->slicer->osw->rec;
-            orc.n_k = rec.n_k;
-            bp.tails.osf.add(orc);
-        }
+        if (rec.n_k > 0)                   // the frame decoder behind it sees what this block's slicer launch wrote
+            c->slicer->for_each_frames([&](const auto &f) {
+                if (!f) return;
+                auto fr = f->rec;
+                fr.n_k = rec.n_k;
+                bp.tails.of<decltype(fr)>().add(fr);
+            });
     }
     if (c->audio && s.a_n > 0) {
         AudioLaunch al = c->audio->rec;

@@ -102,6 +102,12 @@ struct TailStages {
         f(RCF_T_SLICE, launch_edacs, t.edf...);
         f(RCF_T_SLICE, launch_osw, t.osf...);
     }
+    template <class Rec> StageRecs<Rec> &of()      // the stage whose records are plain StageRecs<Rec>: found at compile time
+    {
+        StageRecs<Rec> *r = nullptr;
+        each([&r](int, auto, auto &s) { if constexpr (std::is_same<StageRecs<Rec> &, decltype(s)>::value) r = &s; }, *this);
+        return *r;
+    }
     void append(const TailStages &o) { each([](int, auto, auto &mine, const auto &theirs) { mine.append(theirs); }, *this, o); }
     bool upload(Arena &ar)
     {

@@ -17,6 +17,11 @@ void counted_row(Stream *s, const void *ring, int64_t *cursor, const int64_t *co
     s->interp = (uint32_t)interp; s->decim = (uint32_t)decim;
 }
 template <class L> void loop_row(L *l, Stream *s) { if (l) counted_row(s, l->ring(), &l->rd, static_cast<const int64_t *>(l->counters()), l->serial); }
+// a frame decoder's records: a ring of the decoder's own capacity
+template <class R> void frames_row(Chan *c, Stream *s)
+{
+    if (R *t = c->slicer ? c->slicer->frames<R>().get() : nullptr) { counted_row(s, t->rec.rec_ring, &t->rd, &t->rec.st->n_records, 0); s->cap = t->cap; }
+}
 // ring, reader and counter of every row of kStreams and of the readers' rows behind it, in their order; a row that leaves the
 // ring null is refused
 void (*const kRows[kAllReadKinds])(Chan *, Stream *) = {
@@ -30,9 +35,9 @@ void (*const kRows[kAllReadKinds])(Chan *, Stream *) = {
     [](Chan *c, Stream *s) { loop_row(c->fsk4.get(), s); },
     [](Chan *c, Stream *s) { if (Chan::Slicer *l = c->slicer.get()) counted_row(s, l->rec.word_ring, &l->rd_words, &l->rec.st->n_words, 0); },
     [](Chan *c, Stream *s) { if (Chan::Slicer *l = c->slicer.get()) { counted_row(s, l->rec.hit_ring, &l->rd_hits, &l->rec.st->n_hits, 0); s->cap = l->hit_cap; } },
-    [](Chan *c, Stream *s) { if (Chan::Slicer::Tsbk *t = c->slicer ? c->slicer->tsbk.get() : nullptr) { counted_row(s, t->rec.rec_ring, &t->rd, &t->rec.st->n_records, 0); s->cap = t->cap; } },
-    [](Chan *c, Stream *s) { if (Chan::Slicer::Edacs *t = c->slicer ? c->slicer->edacs.get() : nullptr) { counted_row(s, t->rec.rec_ring, &t->rd, &t->rec.st->n_records, 0); s->cap = t->cap; } },
-    [](Chan *c, Stream *s) { if (Chan::Slicer::Osw *t = c->slicer ? c->slicer->osw.get() : nullptr) { counted_row(s, t->rec.rec_ring, &t->rd, &t->rec.st->n_records, 0); s->cap = t->cap; } },
+    frames_row<Chan::Slicer::Tsbk>,
+    frames_row<Chan::Slicer::Edacs>,
+    frames_row<Chan::Slicer::Osw>,
 };
 
 }  // namespace
@@ -239,8 +244,20 @@ int rcf_chan_read_many(rcf_t *h, int what, const int *chan_ids, int n_chans, flo
     return read_many(h->host_stage, h->stream, &h, 1, nullptr, chan_ids, n_chans, what, gain, out, cap_each, counts);
 }
 
-// a zero-copy reader's view of a channel: the device ring of stream `kind` if the channel has it (`always`: or else
-// RCF_ESTATE even when nobody asked for the pointer), the discriminator ring, the rings' capacity
+// a zero-copy reader's view of c's stream `kind`: its device ring and that ring's capacity, the handle's out_cap or the
+// ring's own; RCF_ESTATE when the channel does not carry it.  (The caller holds the lock.)
+static int stream_ring(rcf_t *h, Chan *c, int kind, void **ring, size_t *capacity)
+{
+    Stream s;
+    const int rc = chan_stream(h, c, kind, &s);
+    if (rc != RCF_OK) return rc;
+    if (ring) *ring = const_cast<void *>(s.ring);
+    if (capacity) *capacity = s.cap;
+    return RCF_OK;
+}
+
+// ... of a channel: the ring of stream `kind` if the channel has it (`always`: or else RCF_ESTATE even when nobody asked
+// for the pointer), the discriminator ring, the rings' capacity
 static int chan_rings(rcf_t *h, int chan_id, int kind, bool always, void **ring, void **fm_ring, size_t *capacity)
 {
     if (!h) return RCF_EINVAL;
@@ -248,13 +265,10 @@ static int chan_rings(rcf_t *h, int chan_id, int kind, bool always, void **ring,
     if (set_dev(h)) return RCF_EHIP;                  // (zero-copy readers order themselves on rcf_stream: nothing stays deferred)
     FIND_CHAN(h, chan_id, c);
     if (ring || always) {
-        Stream s;
-        const int rc = chan_stream(h, c, kind, &s);
+        const int rc = stream_ring(h, c, kind, ring, capacity);
         if (rc != RCF_OK) return rc;
-        if (ring) *ring = const_cast<void *>(s.ring);
-    }
+    } else if (capacity) *capacity = h->out_cap;
     if (fm_ring) *fm_ring = c->d_fm;
-    if (capacity) *capacity = h->out_cap;
     return RCF_OK;
 }
 
@@ -265,44 +279,15 @@ int rcf_chan_costas_ring(rcf_t *h, int chan_id, void **sym_ring, size_t *capacit
 int rcf_chan_fsk4_ring(rcf_t *h, int chan_id, void **sym_ring, size_t *capacity) { return chan_rings(h, chan_id, kFsk4, true, sym_ring, nullptr, capacity); }
 int rcf_chan_slicer_rings(rcf_t *h, int chan_id, void **word_ring, size_t *word_capacity, void **hit_ring, size_t *hit_capacity)
 {
-    const int rc = chan_rings(h, chan_id, kHardBits, true, word_ring, nullptr, word_capacity);
-    if (rc != RCF_OK) return rc;
+    if (!h) return RCF_EINVAL;
     std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
     FIND_CHAN(h, chan_id, c);
-    if (!c->slicer) { set_error("channel %d has no slicer (rcf_chan_slicer)", chan_id); return RCF_ESTATE; }   // (closed in between)
-    if (hit_ring) *hit_ring = c->slicer->rec.hit_ring;
-    if (hit_capacity) *hit_capacity = c->slicer->hit_cap;
-    return RCF_OK;
+    const int rc = stream_ring(h, c, kHardBits, word_ring, word_capacity);
+    return rc != RCF_OK ? rc : stream_ring(h, c, kHardSync, hit_ring, hit_capacity);
 }
-int rcf_chan_tsbk_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity)
-{
-    const int rc = chan_rings(h, chan_id, kTsbk, true, rec_ring, nullptr, nullptr);
-    if (rc != RCF_OK) return rc;
-    std::lock_guard<std::mutex> g(h->mu);
-    FIND_CHAN(h, chan_id, c);
-    if (!c->slicer || !c->slicer->tsbk) { set_error(kStreams[kTsbk].refusal, chan_id); return RCF_ESTATE; }   // (closed in between)
-    if (capacity) *capacity = c->slicer->tsbk->cap;
-    return RCF_OK;
-}
-int rcf_chan_edacs_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity)
-{
-    const int rc = chan_rings(h, chan_id, kEdacs, true, rec_ring, nullptr, nullptr);
-    if (rc != RCF_OK) return rc;
-    std::lock_guard<std::mutex> g(h->mu);
-    FIND_CHAN(h, chan_id, c);
-    if (!c->slicer || !c->slicer->edacs) { set_error(read_row(kEdacs).refusal, chan_id); return RCF_ESTATE; }   // (closed in between)
-    if (capacity) *capacity = c->slicer->edacs->cap;
-    return RCF_OK;
-}
-int rcf_chan_osw_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity)
-{
-    const int rc = chan_rings(h, chan_id, kOsw, true, rec_ring, nullptr, nullptr);
-    if (rc != RCF_OK) return rc;
-    std::lock_guard<std::mutex> g(h->mu);
-    FIND_CHAN(h, chan_id, c);
-    if (!c->slicer || !c->slicer->osw) { set_error(read_row(kOsw).refusal, chan_id); return RCF_ESTATE; }   // (closed in between)
-    if (capacity) *capacity = c->slicer->osw->cap;
-    return RCF_OK;
-}
+int rcf_chan_tsbk_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity) { return chan_rings(h, chan_id, kTsbk, true, rec_ring, nullptr, capacity); }
+int rcf_chan_edacs_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity) { return chan_rings(h, chan_id, kEdacs, true, rec_ring, nullptr, capacity); }
+int rcf_chan_osw_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity) { return chan_rings(h, chan_id, kOsw, true, rec_ring, nullptr, capacity); }
 
 }  // extern "C"

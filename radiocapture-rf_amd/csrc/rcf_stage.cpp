@@ -1,11 +1,14 @@
 // rcf_stage.cpp -- the optional stages behind a channel's rings (the records of Chan, rcf_state.h): the P25 symbol filter,
 // the feed-forward AGC, the SmartNet / EDACS symbol clock, the P25 CQPSK Gardner / Costas loop, the P25 C4FM symbol loop and
-// the analog voice chain, the slicer behind one of the loops and the P25 trunking stage, the EDACS control-frame stage or the SmartNet OSW stage behind the slicer.
+// the analog voice chain, the slicer behind one of the loops and the frame decoder behind the slicer (P25 trunking blocks,
+// EDACS control frames or SmartNet OSWs).
 // Attach, off, and what they produced.
 // An attach function allocates into Fresh<> holders and builds the new record completely; only then is it swapped into
 // the channel and the old one released.  A HIP call that fails before that leaves the channel as it was.
 // The three symbol loops share their record (Chan::Loop) and one attach path, attach_loop: an entry point validates its
 // parameters, checks what the loop reads and the ring's size, and fills in its own constants and initial state.
+// The three frame decoders likewise: one record (Slicer::Frames), one attach path, attach_frames, and one state path,
+// frames_state; an entry point brings what it asks of the slicer and its own lines of the initial state.
 #include "rcf_plan.h"
 #define RCF_DEVFN static inline
 #define RCF_DEVCONST static const
@@ -17,10 +20,13 @@ namespace rcfx {
 
 void Chan::Sym::release(rcf_t *h) { bury(h, rec.sym_ring); bury(h, const_cast<float *>(rec.taps)); rec.sym_ring = nullptr; rec.taps = nullptr; }
 void Chan::Agc::release(rcf_t *h) { bury(h, rec.agc_ring); rec.agc_ring = nullptr; }
-void Chan::Slicer::release_tsbk(rcf_t *h) { if (tsbk) { bury(h, tsbk->rec.rec_ring); tsbk.reset(); } }     // one allocation
-void Chan::Slicer::release_edacs(rcf_t *h) { if (edacs) { bury(h, edacs->rec.rec_ring); edacs.reset(); } }   // one allocation
-void Chan::Slicer::release_osw(rcf_t *h) { if (osw) { bury(h, osw->rec.rec_ring); osw.reset(); } }           // one allocation
-void Chan::Slicer::release(rcf_t *h) { release_tsbk(h); release_edacs(h); release_osw(h); bury(h, rec.word_ring); rec = SliceLaunch{}; }     // one allocation; the TSBK / EDACS / OSW stage goes with its slicer
+template <class R> static void release_frames(rcf_t *h, std::unique_ptr<R> &f) { if (f) { bury(h, f->rec.rec_ring); f.reset(); } }     // one allocation
+void Chan::Slicer::release(rcf_t *h)                 // one allocation; the frame decoder goes with its slicer
+{
+    for_each_frames([h](auto &f) { release_frames(h, f); });
+    bury(h, rec.word_ring);
+    rec = SliceLaunch{};
+}
 void Chan::Audio::release(rcf_t *h) { bury(h, rec.st); bury(h, rec.a_ring); bury(h, const_cast<float *>(rec.lpf)); rec = AudioLaunch{}; }
 
 }  // namespace rcfx
@@ -85,6 +91,71 @@ static int attach_loop(rcf_t *h, Chan *c, std::unique_ptr<R> &stage, std::unique
     stage = std::move(k);
     ++h->chans_epoch;
     return RCF_OK;
+}
+
+// What attaching a frame decoder R behind the slicer comes to; its entry point brings slicer_ok, what it asks of the slicer
+// (else RCF_ESTATE with `refusal`), and init, its own lines of the launch record and of the initial state.  p == nullptr: off.
+// One allocation -- record ring of cap records | the state record, in a slot of 256 bytes (cap >= 16: the state's 64-bit
+// fields are aligned) --, one copy, and the swap.  Every call is a new stream: a fresh ring and state, cursor 0; the first
+// hit is the slicer's count as of everything queued (one round trip), which `now` hands to init as well.
+template <class R, class P, class Ok, class Init>
+static int attach_frames(rcf_t *h, int chan_id, const P *p, Ok &&slicer_ok, const char *refusal, Init &&init)
+{
+    if (!h) return RCF_EINVAL;
+    int cap = 256;
+    if (p) {
+        if (p->capacity) cap = p->capacity;
+        if (cap < 16 || cap > (1 << 20) || (cap & (cap - 1))) { set_error("%s stage: capacity %d is not a power of two 16 .. 2^20", R::kName, p->capacity); return RCF_EINVAL; }
+    }
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!p) {
+        if (c->slicer && c->slicer->frames<R>()) { release_frames(h, c->slicer->frames<R>()); ++h->chans_epoch; }
+        return RCF_OK;
+    }
+    if (!c->slicer || !slicer_ok(c->slicer->rec)) { set_error(refusal, chan_id); return RCF_ESTATE; }
+    const SliceLaunch &sl = c->slicer->rec;
+    std::unique_ptr<R> k(new R);
+    typename R::Launch &r = k->rec;
+    r.src = sl.st;
+    r.word_ring = sl.word_ring; r.hit_ring = sl.hit_ring;
+    r.word_mask = sl.word_mask; r.hit_mask = sl.hit_mask; r.rec_mask = (uint32_t)cap - 1;
+    k->cap = (uint32_t)cap;
+    SliceState now{};
+    const int rc = stage_state(h, sl.st, &now, offsetof(SliceState, partial));
+    if (rc != RCF_OK) return rc;
+    typename R::State st0{};
+    st0.next_hit = now.n_hits;
+    init(r, st0, sl, now);
+    constexpr size_t kStateWords = 256 / sizeof(uint32_t);
+    static_assert(sizeof(typename R::State) <= 256, "the state's slot");
+    const size_t state_at = (size_t)cap * read_row(R::kKind).item_w;       // in words
+    Fresh<uint32_t> fresh;
+    RCF_HIP(fresh.alloc(state_at + kStateWords));
+    char state_copy[32];
+    snprintf(state_copy, sizeof(state_copy), "hipMemcpy(%s state)", R::kName);
+    if (!hip_ok(hipMemcpy(fresh.p + state_at, &st0, sizeof(st0), hipMemcpyHostToDevice), state_copy)) return RCF_EHIP;
+    r.rec_ring = fresh.take();
+    r.st = reinterpret_cast<typename R::State *>(r.rec_ring + state_at);
+    release_frames(h, c->slicer->frames<R>());
+    c->slicer->frames<R>() = std::move(k);
+    ++h->chans_epoch;
+    return RCF_OK;
+}
+static_assert(read_row(kTsbk).item_w == kTsbkRecWords && read_row(kEdacs).item_w == kEdacsRecWords && read_row(kOsw).item_w == kOswRecWords,
+              "the stream table's words per record are the kernels'");
+
+// the decoder's counters -- its state record up to next_hit -- as of everything queued; refused as its stream is
+template <class R, class Out>
+static int frames_state(rcf_t *h, int chan_id, const Out *out, typename R::State *st)
+{
+    if (!h || !out) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!c->slicer || !c->slicer->frames<R>()) { set_error(read_row(R::kKind).refusal, chan_id); return RCF_ESTATE; }
+    return stage_state(h, c->slicer->frames<R>()->rec.st, st, offsetof(typename R::State, next_hit));
 }
 
 extern "C" {
@@ -366,188 +437,56 @@ int rcf_chan_slicer_state(rcf_t *h, int chan_id, rcf_slicer_state_t *out)
     return RCF_OK;
 }
 
-// ---- P25 trunking blocks behind the slicer (tsbk.hip)
+// ---- the frame decoders behind the slicer (tsbk.hip, edacs.hip, osw.hip)
 int rcf_chan_tsbk(rcf_t *h, int chan_id, const rcf_tsbk_params_t *p)
 {
-    if (!h) return RCF_EINVAL;
-    int cap = 256;
-    if (p) {
-        if (p->capacity) cap = p->capacity;
-        if (cap < 16 || cap > (1 << 20) || (cap & (cap - 1))) { set_error("TSBK stage: capacity %d is not a power of two 16 .. 2^20", p->capacity); return RCF_EINVAL; }
-    }
-    std::lock_guard<std::mutex> g(h->mu);
-    if (set_dev(h)) return RCF_EHIP;
-    FIND_CHAN(h, chan_id, c);
-    if (!p) {
-        if (c->slicer && c->slicer->tsbk) { c->slicer->release_tsbk(h); ++h->chans_epoch; }
-        return RCF_OK;
-    }
-    if (!c->slicer || c->slicer->rec.bps != 2 || c->slicer->rec.sync_bits != 48 || c->slicer->rec.sync_both) {
-        set_error("channel %d has no slicer in RCF_SLICE_FSK4 mode that searches a 48-bit sync word in one polarity", chan_id);
-        return RCF_ESTATE;
-    }
-    const SliceLaunch &sl = c->slicer->rec;
-    std::unique_ptr<Chan::Slicer::Tsbk> k(new Chan::Slicer::Tsbk);
-    TsbkLaunch &r = k->rec;
-    r.src = sl.st;
-    r.word_ring = sl.word_ring; r.hit_ring = sl.hit_ring;
-    r.word_mask = sl.word_mask; r.hit_mask = sl.hit_mask; r.rec_mask = (uint32_t)cap - 1;
-    k->cap = (uint32_t)cap;
-    // the stage's first hit: the slicer's count as of everything queued (one round trip)
-    SliceState now{};
-    const int rc = stage_state(h, sl.st, &now, offsetof(SliceState, partial));
-    if (rc != RCF_OK) return rc;
-    TsbkState st0{};
-    st0.next_hit = now.n_hits;
-    st0.k_last = kTsbkNoFrame;
-    constexpr size_t kStateWords = 256 / sizeof(uint32_t);
-    static_assert(sizeof(TsbkState) <= 256, "the state's slot");
-    const size_t state_at = (size_t)cap * kTsbkRecWords;                   // in words (cap >= 16: the record's 64-bit fields are aligned)
-    Fresh<uint32_t> fresh;
-    RCF_HIP(fresh.alloc(state_at + kStateWords));
-    if (!hip_ok(hipMemcpy(fresh.p + state_at, &st0, sizeof(st0), hipMemcpyHostToDevice), "hipMemcpy(TSBK state)")) return RCF_EHIP;
-    r.rec_ring = fresh.take();
-    r.st = reinterpret_cast<TsbkState *>(r.rec_ring + state_at);
-    c->slicer->release_tsbk(h);
-    c->slicer->tsbk = std::move(k);
-    ++h->chans_epoch;
-    return RCF_OK;
+    return attach_frames<Chan::Slicer::Tsbk>(h, chan_id, p,
+        [](const SliceLaunch &sl) { return sl.bps == 2 && sl.sync_bits == 48 && !sl.sync_both; },
+        "channel %d has no slicer in RCF_SLICE_FSK4 mode that searches a 48-bit sync word in one polarity",
+        [](TsbkLaunch &, TsbkState &st0, const SliceLaunch &, const SliceState &) { st0.k_last = kTsbkNoFrame; });
 }
 
 int rcf_chan_tsbk_state(rcf_t *h, int chan_id, rcf_tsbk_state_t *out)
 {
-    if (!h || !out) return RCF_EINVAL;
-    std::lock_guard<std::mutex> g(h->mu);
-    if (set_dev(h)) return RCF_EHIP;
-    FIND_CHAN(h, chan_id, c);
-    if (!c->slicer || !c->slicer->tsbk) { set_error("channel %d has no TSBK stage (rcf_chan_tsbk)", chan_id); return RCF_ESTATE; }
     TsbkState st{};                     // (its five counters)
-    const int rc = stage_state(h, c->slicer->tsbk->rec.st, &st, offsetof(TsbkState, next_hit));
+    const int rc = frames_state<Chan::Slicer::Tsbk>(h, chan_id, out, &st);
     if (rc != RCF_OK) return rc;
     out->n_records = st.n_records; out->n_frames = st.n_frames; out->n_blocks = st.n_blocks; out->n_crc_bad = st.n_crc_bad; out->n_lost = st.n_lost;
     return RCF_OK;
 }
 
-// ---- EDACS control frames behind the slicer (edacs.hip)
 int rcf_chan_edacs(rcf_t *h, int chan_id, const rcf_edacs_params_t *p)
 {
-    if (!h) return RCF_EINVAL;
-    int cap = 256;
-    if (p) {
-        if (p->capacity) cap = p->capacity;
-        if (cap < 16 || cap > (1 << 20) || (cap & (cap - 1))) { set_error("EDACS stage: capacity %d is not a power of two 16 .. 2^20", p->capacity); return RCF_EINVAL; }
-    }
-    std::lock_guard<std::mutex> g(h->mu);
-    if (set_dev(h)) return RCF_EHIP;
-    FIND_CHAN(h, chan_id, c);
-    if (!p) {
-        if (c->slicer && c->slicer->edacs) { c->slicer->release_edacs(h); ++h->chans_epoch; }
-        return RCF_OK;
-    }
-    if (!c->slicer || c->slicer->rec.bps != 1 || c->slicer->rec.sync_bits != kEdacsSyncBits) {
-        set_error("channel %d has no slicer in RCF_SLICE_BINARY mode that searches a 48-bit sync word", chan_id);
-        return RCF_ESTATE;
-    }
-    const SliceLaunch &sl = c->slicer->rec;
-    std::unique_ptr<Chan::Slicer::Edacs> k(new Chan::Slicer::Edacs);
-    EdacsLaunch &r = k->rec;
-    r.src = sl.st;
-    r.word_ring = sl.word_ring; r.hit_ring = sl.hit_ring;
-    r.word_mask = sl.word_mask; r.hit_mask = sl.hit_mask; r.rec_mask = (uint32_t)cap - 1;
-    r.flags = (sl.sync_both ? kEdacsFlagBoth : 0u) | (p->esk ? kEdacsFlagEsk : 0u);
-    k->cap = (uint32_t)cap;
-    // the stage's first hit: the slicer's count as of everything queued (one round trip)
-    SliceState now{};
-    const int rc = stage_state(h, sl.st, &now, offsetof(SliceState, partial));
-    if (rc != RCF_OK) return rc;
-    EdacsState st0{};
-    st0.next_hit = now.n_hits;
-    st0.k_last = kEdacsNoFrame;
-    constexpr size_t kStateWords = 256 / sizeof(uint32_t);
-    static_assert(sizeof(EdacsState) <= 256, "the state's slot");
-    const size_t state_at = (size_t)cap * kEdacsRecWords;                  // in words (cap >= 16: the record's 64-bit fields are aligned)
-    Fresh<uint32_t> fresh;
-    RCF_HIP(fresh.alloc(state_at + kStateWords));
-    if (!hip_ok(hipMemcpy(fresh.p + state_at, &st0, sizeof(st0), hipMemcpyHostToDevice), "hipMemcpy(EDACS state)")) return RCF_EHIP;
-    r.rec_ring = fresh.take();
-    r.st = reinterpret_cast<EdacsState *>(r.rec_ring + state_at);
-    c->slicer->release_edacs(h);
-    c->slicer->edacs = std::move(k);
-    ++h->chans_epoch;
-    return RCF_OK;
+    return attach_frames<Chan::Slicer::Edacs>(h, chan_id, p,
+        [](const SliceLaunch &sl) { return sl.bps == 1 && sl.sync_bits == kEdacsSyncBits; },
+        "channel %d has no slicer in RCF_SLICE_BINARY mode that searches a 48-bit sync word",
+        [p](EdacsLaunch &r, EdacsState &st0, const SliceLaunch &sl, const SliceState &) {
+            r.flags = (sl.sync_both ? kEdacsFlagBoth : 0u) | (p->esk ? kEdacsFlagEsk : 0u);
+            st0.k_last = kEdacsNoFrame;
+        });
 }
 
 int rcf_chan_edacs_state(rcf_t *h, int chan_id, rcf_edacs_state_t *out)
 {
-    if (!h || !out) return RCF_EINVAL;
-    std::lock_guard<std::mutex> g(h->mu);
-    if (set_dev(h)) return RCF_EHIP;
-    FIND_CHAN(h, chan_id, c);
-    if (!c->slicer || !c->slicer->edacs) { set_error("channel %d has no EDACS stage (rcf_chan_edacs)", chan_id); return RCF_ESTATE; }
     EdacsState st{};                    // (its five counters)
-    const int rc = stage_state(h, c->slicer->edacs->rec.st, &st, offsetof(EdacsState, next_hit));
+    const int rc = frames_state<Chan::Slicer::Edacs>(h, chan_id, out, &st);
     if (rc != RCF_OK) return rc;
     out->n_records = st.n_records; out->n_frames = st.n_frames; out->n_msgs = st.n_msgs; out->n_msgs_none = st.n_msgs_none; out->n_lost = st.n_lost;
     return RCF_OK;
 }
 
-// ---- SmartNet OSWs behind the slicer (osw.hip)
 int rcf_chan_osw(rcf_t *h, int chan_id, const rcf_osw_params_t *p)
 {
-    if (!h) return RCF_EINVAL;
-    int cap = 256;
-    if (p) {
-        if (p->capacity) cap = p->capacity;
-        if (cap < 16 || cap > (1 << 20) || (cap & (cap - 1))) { set_error("OSW stage: capacity %d is not a power of two 16 .. 2^20", p->capacity); return RCF_EINVAL; }
-    }
-    std::lock_guard<std::mutex> g(h->mu);
-    if (set_dev(h)) return RCF_EHIP;
-    FIND_CHAN(h, chan_id, c);
-    if (!p) {
-        if (c->slicer && c->slicer->osw) { c->slicer->release_osw(h); ++h->chans_epoch; }
-        return RCF_OK;
-    }
-    if (!c->slicer || c->slicer->rec.bps != 1 || c->slicer->rec.sync_bits != kOswSyncBits || c->slicer->rec.sync_max_errors != 0 || c->slicer->rec.sync_both) {
-        set_error("channel %d has no slicer in RCF_SLICE_BINARY mode that searches an 8-bit sync word exactly, in one polarity", chan_id);
-        return RCF_ESTATE;
-    }
-    const SliceLaunch &sl = c->slicer->rec;
-    std::unique_ptr<Chan::Slicer::Osw> k(new Chan::Slicer::Osw);
-    OswLaunch &r = k->rec;
-    r.src = sl.st;
-    r.word_ring = sl.word_ring; r.hit_ring = sl.hit_ring;
-    r.word_mask = sl.word_mask; r.hit_mask = sl.hit_mask; r.rec_mask = (uint32_t)cap - 1;
-    k->cap = (uint32_t)cap;
-    // the stage's first hit and its cursor: the slicer's counts as of everything queued (one round trip)
-    SliceState now{};
-    const int rc = stage_state(h, sl.st, &now, offsetof(SliceState, partial));
-    if (rc != RCF_OK) return rc;
-    OswState st0{};
-    st0.next_hit = now.n_hits;
-    st0.pos = now.n_symbols;
-    constexpr size_t kStateWords = 256 / sizeof(uint32_t);
-    static_assert(sizeof(OswState) <= 256, "the state's slot");
-    const size_t state_at = (size_t)cap * kOswRecWords;                    // in words (cap >= 16: the state's 64-bit fields are aligned)
-    Fresh<uint32_t> fresh;
-    RCF_HIP(fresh.alloc(state_at + kStateWords));
-    if (!hip_ok(hipMemcpy(fresh.p + state_at, &st0, sizeof(st0), hipMemcpyHostToDevice), "hipMemcpy(OSW state)")) return RCF_EHIP;
-    r.rec_ring = fresh.take();
-    r.st = reinterpret_cast<OswState *>(r.rec_ring + state_at);
-    c->slicer->release_osw(h);
-    c->slicer->osw = std::move(k);
-    ++h->chans_epoch;
-    return RCF_OK;
+    return attach_frames<Chan::Slicer::Osw>(h, chan_id, p,
+        [](const SliceLaunch &sl) { return sl.bps == 1 && sl.sync_bits == kOswSyncBits && sl.sync_max_errors == 0 && !sl.sync_both; },
+        "channel %d has no slicer in RCF_SLICE_BINARY mode that searches an 8-bit sync word exactly, in one polarity",
+        [](OswLaunch &, OswState &st0, const SliceLaunch &, const SliceState &now) { st0.pos = now.n_symbols; });     // its cursor
 }
 
 int rcf_chan_osw_state(rcf_t *h, int chan_id, rcf_osw_state_t *out)
 {
-    if (!h || !out) return RCF_EINVAL;
-    std::lock_guard<std::mutex> g(h->mu);
-    if (set_dev(h)) return RCF_EHIP;
-    FIND_CHAN(h, chan_id, c);
-    if (!c->slicer || !c->slicer->osw) { set_error("channel %d has no OSW stage (rcf_chan_osw)", chan_id); return RCF_ESTATE; }
     OswState st{};                      // (its five counters and the lock)
-    const int rc = stage_state(h, c->slicer->osw->rec.st, &st, offsetof(OswState, next_hit));
+    const int rc = frames_state<Chan::Slicer::Osw>(h, chan_id, out, &st);
     if (rc != RCF_OK) return rc;
     out->n_records = st.n_records; out->n_frames = st.n_frames; out->n_bad = st.n_bad; out->n_rejects = st.n_rejects; out->n_lost = st.n_lost;
     out->locked = st.locked; out->is_locked = st.is_locked;

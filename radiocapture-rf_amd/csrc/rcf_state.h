@@ -3,7 +3,8 @@
 //   rcf_handle.cpp   open / close / sync, pools, wideband ingest        rcf_plan.cpp    the per-block schedule (host)
 //   rcf_launch.cpp   the block's launches in dependency order           rcf_chan.cpp    channels: lifecycle, taps, queries
 //   rcf_stage.cpp    a channel's optional stages: symbol filter, AGC,   rcf_read.cpp    a channel's streams (one descriptor, Stream)
-//                    symbol loops, slicer, TSBK / EDACS / OSW stages, voice chain (attach / off)                    and the one read path of every host read
+//                    symbol loops, slicer, the frame decoders behind it                 and the one read path of every host read
+//                    (one record, Slicer::Frames), voice chain (attach / off)
 //   rcf_streams.h    the stream table and the readers' integer rules (no HIP: g++ alone compiles it)
 //   rcf_bank.cpp     filterbank + scanner ABI                           rcf_timing.cpp  HIP-event timing
 //   rcf_comm.cpp     RCCL peak-list exchange                            rcf_group.cpp   grouped launches over front-ends
@@ -172,34 +173,42 @@ struct Chan {
         int source = 0;                 // RCF_READ_CLOCK / COSTAS / FSK4
         uint32_t hit_cap = 0;
         int64_t rd_words = 0, rd_hits = 0;
-        // P25 trunking blocks out of the slicer's two streams (rcf_chan_tsbk): it hangs off the slicer -- Chan stays inside
-        // its prefetched lines -- and goes whenever the slicer goes.  One allocation, which starts at rec.rec_ring: record
-        // ring of cap records of 8 words | the state record, in a slot of 256 bytes.  A second call: new ring and state
-        struct Tsbk {
-            TsbkLaunch rec{};
+        // The frame decoders out of the slicer's two streams: P25 trunking blocks (rcf_chan_tsbk), EDACS control frames
+        // (rcf_chan_edacs), SmartNet OSWs (rcf_chan_osw).  One record shape.  A decoder hangs off the slicer -- Chan stays
+        // inside its prefetched lines -- and goes whenever the slicer goes.  One allocation, which starts at rec.rec_ring:
+        // record ring of cap records of the stream's item_w words | the state record, in a slot of 256 bytes.  A second
+        // call: new ring and state, cursor 0 (attach_frames, rcf_stage.cpp).  kKind: the decoder's stream (rcf_streams.h:
+        // its words per record, and its refusal); kName: how the messages spell it
+        template <class State_, class Launch_> struct Frames {
+            typedef State_ State;
+            typedef Launch_ Launch;
+            Launch rec{};
             uint32_t cap = 0;
             int64_t rd = 0;
         };
+        struct Tsbk : Frames<TsbkState, TsbkLaunch> { static constexpr int kKind = kTsbk; static constexpr const char *kName = "TSBK"; };
+        struct Edacs : Frames<EdacsState, EdacsLaunch> { static constexpr int kKind = kEdacs; static constexpr const char *kName = "EDACS"; };
+        struct Osw : Frames<OswState, OswLaunch> { static constexpr int kKind = kOsw; static constexpr const char *kName = "OSW"; };
         std::unique_ptr<Tsbk> tsbk;
-        // EDACS control frames out of the same two streams (rcf_chan_edacs), behind a binary slicer: the same arrangement
-        struct Edacs {
-            EdacsLaunch rec{};
-            uint32_t cap = 0;
-            int64_t rd = 0;
-        };
         std::unique_ptr<Edacs> edacs;
-        // SmartNet OSWs (rcf_chan_osw), behind a binary slicer that searches the 8-bit word: the same arrangement
-        struct Osw {
-            OswLaunch rec{};
-            uint32_t cap = 0;
-            int64_t rd = 0;
-        };
         std::unique_ptr<Osw> osw;
+        // The one list of them.  At most one is ever attached: what they ask of the slicer excludes each other (TSBK: 2
+        // bits per symbol; EDACS: binary, a 48-bit sync word; OSW: binary, an 8-bit sync word matched exactly)
+        template <class F> void for_each_frames(F &&f) { f(tsbk); f(edacs); f(osw); }
+        template <class R> std::unique_ptr<R> &frames()                  // the list's holder of an R
+        {
+            std::unique_ptr<R> *r = nullptr;
+            for_each_frames([&r](auto &f) { if constexpr (std::is_same<std::unique_ptr<R> &, decltype(f)>::value) r = &f; });
+            return *r;
+        }
+        static size_t max_frames_launch()                                // the largest launch record of the list
+        {
+            size_t n = 0;
+            Slicer{}.for_each_frames([&n](auto &f) { n = std::max(n, sizeof(f->rec)); });
+            return n;
+        }
         size_t reach() const { return 0; }                               // it reads the loop's ring, never the channel's
         void release(rcf_t *h);
-        void release_tsbk(rcf_t *h);
-        void release_edacs(rcf_t *h);
-        void release_osw(rcf_t *h);
     };
     std::unique_ptr<Audio> audio;
     std::unique_ptr<Slicer> slicer;
@@ -209,7 +218,7 @@ struct Chan {
     {
         f(sym, sizeof(FmFirLaunch), false); f(agc, sizeof(AgcLaunch), false); f(clock, sizeof(ClockLaunch), false);
         f(costas, sizeof(CostasLaunch), false); f(fsk4, sizeof(Fsk4Launch), false); f(audio, sizeof(AudioLaunch), true);
-        f(slicer, sizeof(SliceLaunch) + std::max({sizeof(TsbkLaunch), sizeof(EdacsLaunch), sizeof(OswLaunch)}) + 64, false);    // (with the TSBK, EDACS or OSW stage it may carry)
+        f(slicer, sizeof(SliceLaunch) + Slicer::max_frames_launch() + 64, false);    // (with the frame decoder it may carry)
     }
     // ---- the rest
     float incr[2] = {1.f, 0.f};   // exact rotator: what GNU Radio iterates

@@ -14,21 +14,14 @@
 // 64-bit window as a funnel shift over (the 64 bits before : the chunk's bits), and the hits' places in the ring from a
 // ballot of the hit lanes and a prefix popcount.  The trip count comes from the host's n_k, never from the device counter.
 // Plain vector stores only; nothing is shared between waves.
-#include "rcf_internal.h"
+#include "item_wave.hpp"
 #include "slice_core.hpp"
 
 namespace rcfx {
 
 namespace {
 
-constexpr int kSliceWaves = 4;
-
-__device__ __forceinline__ uint64_t rl_u64(uint64_t v, int src)
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), src);
-    return ((uint64_t)hi << 32) | lo;
-}
+constexpr int kSliceWaves = kItemWaves;
 
 __global__ __launch_bounds__(64 * kSliceWaves) void slice_kernel(const SliceLaunch *__restrict__ items, int n_items)
 {
@@ -99,8 +92,7 @@ __global__ __launch_bounds__(64 * kSliceWaves) void slice_kernel(const SliceLaun
 // ring_mask: unused -- every record carries the masks of its three rings (the hit ring has a capacity of its own)
 void launch_slice(const SliceLaunch *d_items, int n_items, int max_n_k, uint64_t, hipStream_t s)
 {
-    if (n_items <= 0 || max_n_k <= 0) return;
-    hipLaunchKernelGGL(slice_kernel, dim3((n_items + kSliceWaves - 1) / kSliceWaves), dim3(64 * kSliceWaves), 0, s, d_items, n_items);
+    launch_item_waves(slice_kernel, d_items, n_items, max_n_k, s);
 }
 
 }  // namespace rcfx

@@ -17,21 +17,14 @@
 // idle.  The lanes 0 .. 7 store a record's eight words.
 // All trip counts come from the host's n_k; the counters read from the device only clamp.  Every ring index is masked.  Plain
 // vector stores only; nothing is shared between waves; no LDS.
-#include "rcf_internal.h"
+#include "item_wave.hpp"
 #include "tsbk_core.hpp"
 
 namespace rcfx {
 
 namespace {
 
-constexpr int kTsbkWaves = 4;
-
-__device__ __forceinline__ int64_t rl_i64(int64_t v, int src)
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)v, src);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), src);
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
+constexpr int kTsbkWaves = kItemWaves;
 
 // stream dibit p of the slicer's word ring (p inside the whole words: the caller's condition)
 __device__ __forceinline__ int ring_dibit(const TsbkLaunch &L, int64_t p)
@@ -132,8 +125,7 @@ __global__ __launch_bounds__(64 * kTsbkWaves) void tsbk_kernel(const TsbkLaunch 
 // ring_mask: unused -- every record carries the masks of its three rings
 void launch_tsbk(const TsbkLaunch *d_items, int n_items, int max_n_k, uint64_t, hipStream_t s)
 {
-    if (n_items <= 0 || max_n_k <= 0) return;
-    hipLaunchKernelGGL(tsbk_kernel, dim3((n_items + kTsbkWaves - 1) / kTsbkWaves), dim3(64 * kTsbkWaves), 0, s, d_items, n_items);
+    launch_item_waves(tsbk_kernel, d_items, n_items, max_n_k, s);
 }
 
 }  // namespace rcfx

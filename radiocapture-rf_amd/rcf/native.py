@@ -228,6 +228,9 @@ def osw_fields(records):
                 syn_bits=((f >> 10) & 63).astype(np.uint8), rel=(f >> 16).astype(np.uint16))
 
 
+_RECORD_DTYPE = {HARD_TSBK: TSBK_DTYPE, HARD_EDACS: EDACS_DTYPE, HARD_OSW: OSW_DTYPE}
+
+
 def widen_hits(items, n_symbols):
     """the hit ring's uint32 items -> (k as int64, dist as uint8): k is the largest value <= n_symbols - 1 with the item's low
     26 bits (rcf.h at rcf_chan_slicer), n_symbols the stage's count when the items were read or later"""
@@ -325,18 +328,6 @@ def lib():
         "rcf_chan_read_hard": (i64, [vp, C.c_int, C.POINTER(C.c_uint32), sz]),
         "rcf_chan_read_sync": (i64, [vp, C.c_int, C.POINTER(C.c_uint32), sz]),
         "rcf_chan_slicer_rings": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]),
-        "rcf_chan_tsbk": (C.c_int, [vp, C.c_int, C.POINTER(TsbkParams)]),
-        "rcf_chan_tsbk_state": (C.c_int, [vp, C.c_int, C.POINTER(TsbkState)]),
-        "rcf_chan_read_tsbk": (i64, [vp, C.c_int, C.POINTER(C.c_uint32), sz]),
-        "rcf_chan_tsbk_ring": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]),
-        "rcf_chan_edacs": (C.c_int, [vp, C.c_int, C.POINTER(EdacsParams)]),
-        "rcf_chan_edacs_state": (C.c_int, [vp, C.c_int, C.POINTER(EdacsState)]),
-        "rcf_chan_read_edacs": (i64, [vp, C.c_int, C.POINTER(C.c_uint32), sz]),
-        "rcf_chan_edacs_ring": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]),
-        "rcf_chan_osw": (C.c_int, [vp, C.c_int, C.POINTER(OswParams)]),
-        "rcf_chan_osw_state": (C.c_int, [vp, C.c_int, C.POINTER(OswState)]),
-        "rcf_chan_read_osw": (i64, [vp, C.c_int, C.POINTER(C.c_uint32), sz]),
-        "rcf_chan_osw_ring": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)]),
         "rcf_design_mmse_interpolator": (C.c_int, [C.c_int, C.c_int, C.c_double, fp, C.c_int]),
         "rcf_chan_fm_level": (C.c_int, [vp, C.c_int, C.c_float, C.c_int, fp]),
         "rcf_design_firdes": (C.c_int, [C.c_int] + [C.c_double] * 4 + [C.c_int, C.c_double, fp, C.c_int]),
@@ -413,6 +404,11 @@ def lib():
         "rcf_pump_unsubscribe": (C.c_int, [vp, C.c_int]),
         "rcf_pump_stop": (C.c_int, [vp]),
     }
+    for name, params, state in (("tsbk", TsbkParams, TsbkState), ("edacs", EdacsParams, EdacsState), ("osw", OswParams, OswState)):
+        sig["rcf_chan_" + name] = (C.c_int, [vp, C.c_int, C.POINTER(params)])     # the frame decoders behind the slicer
+        sig["rcf_chan_%s_state" % name] = (C.c_int, [vp, C.c_int, C.POINTER(state)])
+        sig["rcf_chan_read_" + name] = (i64, [vp, C.c_int, C.POINTER(C.c_uint32), sz])
+        sig["rcf_chan_%s_ring" % name] = (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)])
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
         fn.restype = res
@@ -437,12 +433,8 @@ def _read_dtype(what):
     """item type of stream `what` as the readers deliver it: cf32 for "iq" and "agc", uint32 for the slicer's "hard" and
     "sync", TSBK_DTYPE for "tsbk", EDACS_DTYPE for "edacs", OSW_DTYPE for "osw", float32 for everything else"""
     w = _read_what(what, True)
-    if w == HARD_TSBK:
-        return TSBK_DTYPE
-    if w == HARD_EDACS:
-        return EDACS_DTYPE
-    if w == HARD_OSW:
-        return OSW_DTYPE
+    if w in _RECORD_DTYPE:
+        return _RECORD_DTYPE[w]
     return np.complex64 if w in (READ_IQ, READ_AGC) else np.uint32 if w in (HARD_BITS, HARD_SYNC) else np.float32
 
 
@@ -793,6 +785,29 @@ class Frontend:
         _check(fn(self._h, cid, C.byref(p), C.byref(cap)))
         return p.value, cap.value
 
+    def _attach(self, fn, cid, params, on=True, **fields):
+        """a stage of channel cid through fn(h, cid, &params): a params() with the integer `fields` set; on=False: off (NULL)"""
+        if not on:
+            _check(fn(self._h, cid, None))
+            return
+        p = params()
+        for k, v in fields.items():
+            setattr(p, k, int(v))
+        _check(fn(self._h, cid, C.byref(p)))
+
+    def _state_of(self, fn, cid, state) -> dict:
+        """a stage's state through fn(h, cid, &state) as a dict of the struct's fields"""
+        st = state()
+        _check(fn(self._h, cid, C.byref(st)))
+        return _state_dict(st)
+
+    def _read_records(self, fn, cid, n, dtype):
+        """the unread items of one of channel cid's uint32 rings through its single reader fn(h, cid, out, max): at most n
+        items of dtype (whole words)"""
+        out = np.empty(n, dtype=dtype)
+        n = _check(fn(self._h, cid, out.ctypes.data_as(C.POINTER(C.c_uint32)), n))
+        return out[:n].copy()
+
     def chan_read_iq(self, cid, max_samples=1 << 20) -> np.ndarray:
         return self._read_ring(lib().rcf_chan_read_iq, cid, max_samples, np.complex64)
 
@@ -907,9 +922,7 @@ class Frontend:
     def chan_costas_state(self, cid) -> dict:
         """the loop's state as of the last block: n_symbols, n_slips, mu, omega, freq (radians per channel sample, of the
         sign opposite to the carrier's offset), phase (rcf_chan_costas_state; syncs the stream)"""
-        st = CostasState()
-        _check(lib().rcf_chan_costas_state(self._h, cid, C.byref(st)))
-        return _state_dict(st)
+        return self._state_of(lib().rcf_chan_costas_state, cid, CostasState)
 
     def chan_read_costas(self, cid, max_symbols=1 << 20) -> np.ndarray:
         """unread soft symbols of the channel's Gardner / Costas stage (+-1, +-3 on a locked signal), oldest first"""
@@ -936,9 +949,7 @@ class Frontend:
         """the loop's state as of the last block: n_symbols, n_slips, clock, spread, fine, coarse (the slow average of the
         level offset, of the carrier offset's sign: what op25 posts to its autotune queue) (rcf_chan_fsk4_state; syncs
         the stream)"""
-        st = Fsk4State()
-        _check(lib().rcf_chan_fsk4_state(self._h, cid, C.byref(st)))
-        return _state_dict(st)
+        return self._state_of(lib().rcf_chan_fsk4_state, cid, Fsk4State)
 
     def chan_read_fsk4(self, cid, max_symbols=1 << 20) -> np.ndarray:
         """unread soft symbols of the channel's C4FM loop (+-1, +-3 on a locked signal), oldest first"""
@@ -963,9 +974,7 @@ class Frontend:
 
     def chan_slicer_state(self, cid) -> dict:
         """n_symbols, n_words, n_hits of the slicer as of the last block (rcf_chan_slicer_state; syncs the stream)"""
-        st = SlicerState()
-        _check(lib().rcf_chan_slicer_state(self._h, cid, C.byref(st)))
-        return _state_dict(st)
+        return self._state_of(lib().rcf_chan_slicer_state, cid, SlicerState)
 
     def chan_read_hard(self, cid, max_words=1 << 18) -> np.ndarray:
         """unread packed decisions as bytes, 4 per word: GNU Radio's unpacked_to_packed_bb(bps, MSB_FIRST) stream"""
@@ -990,25 +999,16 @@ class Frontend:
         """P25 trunking blocks behind the channel's slicer (rcf_chan_tsbk): frames from the sync hits, status symbols
         stripped, NID read, every block deinterleaved, trellis-decoded and CRC-checked on the GPU; records of TSBK_DTYPE
         in a ring of `capacity` (0: 256).  It considers the hits from now on; on=False switches it off."""
-        if not on:
-            _check(lib().rcf_chan_tsbk(self._h, cid, None))
-            return
-        p = TsbkParams()
-        p.capacity = int(capacity)
-        _check(lib().rcf_chan_tsbk(self._h, cid, C.byref(p)))
+        self._attach(lib().rcf_chan_tsbk, cid, TsbkParams, on, capacity=capacity)
 
     def chan_tsbk_state(self, cid) -> dict:
         """n_records, n_frames, n_blocks, n_crc_bad, n_lost of the TSBK stage as of the last block (rcf_chan_tsbk_state;
         syncs the stream)"""
-        st = TsbkState()
-        _check(lib().rcf_chan_tsbk_state(self._h, cid, C.byref(st)))
-        return _state_dict(st)
+        return self._state_of(lib().rcf_chan_tsbk_state, cid, TsbkState)
 
     def chan_read_tsbk(self, cid, max_records=1 << 12) -> np.ndarray:
         """unread records of the TSBK stage, oldest first: a structured array of TSBK_DTYPE (tsbk_fields takes `flags` apart)"""
-        out = np.empty(max_records, dtype=TSBK_DTYPE)
-        n = _check(lib().rcf_chan_read_tsbk(self._h, cid, out.ctypes.data_as(C.POINTER(C.c_uint32)), max_records))
-        return out[:n].copy()
+        return self._read_records(lib().rcf_chan_read_tsbk, cid, max_records, TSBK_DTYPE)
 
     def chan_tsbk_ring(self, cid):
         """(device pointer, capacity in records) of the stage's record ring (rcf_chan_tsbk_ring)"""
@@ -1018,26 +1018,17 @@ class Frontend:
         """EDACS control frames behind the channel's binary slicer (rcf_chan_edacs): frames from the sync hits of either
         polarity, six copies per frame BCH-decoded and two messages elected on the GPU; records of EDACS_DTYPE in a ring of
         `capacity` (0: 256); esk: extended addressing.  It considers the hits from now on; on=False switches it off."""
-        if not on:
-            _check(lib().rcf_chan_edacs(self._h, cid, None))
-            return
-        p = EdacsParams()
-        p.capacity, p.esk = int(capacity), int(bool(esk))
-        _check(lib().rcf_chan_edacs(self._h, cid, C.byref(p)))
+        self._attach(lib().rcf_chan_edacs, cid, EdacsParams, on, capacity=capacity, esk=bool(esk))
 
     def chan_edacs_state(self, cid) -> dict:
         """n_records, n_frames, n_msgs, n_msgs_none, n_lost of the EDACS stage as of the last block (rcf_chan_edacs_state;
         syncs the stream)"""
-        st = EdacsState()
-        _check(lib().rcf_chan_edacs_state(self._h, cid, C.byref(st)))
-        return _state_dict(st)
+        return self._state_of(lib().rcf_chan_edacs_state, cid, EdacsState)
 
     def chan_read_edacs(self, cid, max_records=1 << 12) -> np.ndarray:
         """unread records of the EDACS stage, oldest first: a structured array of EDACS_DTYPE (edacs_fields takes `flags`
         apart, rcf.control.edacs_messages gives the reference's strings)"""
-        out = np.empty(max_records, dtype=EDACS_DTYPE)
-        n = _check(lib().rcf_chan_read_edacs(self._h, cid, out.ctypes.data_as(C.POINTER(C.c_uint32)), max_records))
-        return out[:n].copy()
+        return self._read_records(lib().rcf_chan_read_edacs, cid, max_records, EDACS_DTYPE)
 
     def chan_edacs_ring(self, cid):
         """(device pointer, capacity in records) of the stage's record ring (rcf_chan_edacs_ring)"""
@@ -1047,26 +1038,17 @@ class Frontend:
         """SmartNet OSWs behind the channel's binary slicer (rcf_chan_osw): the 84-bit framing with its lock counter,
         deinterleave, parity syndrome and correction on the GPU; records of OSW_DTYPE in a ring of `capacity` (0: 256).  It
         starts at the slicer's next symbol with locked = 0; on=False switches it off."""
-        if not on:
-            _check(lib().rcf_chan_osw(self._h, cid, None))
-            return
-        p = OswParams()
-        p.capacity = int(capacity)
-        _check(lib().rcf_chan_osw(self._h, cid, C.byref(p)))
+        self._attach(lib().rcf_chan_osw, cid, OswParams, on, capacity=capacity)
 
     def chan_osw_state(self, cid) -> dict:
         """n_records, n_frames (the reference's packets), n_bad (packets_bad), n_rejects, n_lost, locked, is_locked of the OSW
         stage as of the last block (rcf_chan_osw_state; syncs the stream)"""
-        st = OswState()
-        _check(lib().rcf_chan_osw_state(self._h, cid, C.byref(st)))
-        return _state_dict(st)
+        return self._state_of(lib().rcf_chan_osw_state, cid, OswState)
 
     def chan_read_osw(self, cid, max_records=1 << 12) -> np.ndarray:
         """unread records of the OSW stage, oldest first: a structured array of OSW_DTYPE (osw_fields takes `flags` apart,
         rcf.control.smartnet_osws gives the fields the reference publishes)"""
-        out = np.empty(max_records, dtype=OSW_DTYPE)
-        n = _check(lib().rcf_chan_read_osw(self._h, cid, out.ctypes.data_as(C.POINTER(C.c_uint32)), max_records))
-        return out[:n].copy()
+        return self._read_records(lib().rcf_chan_read_osw, cid, max_records, OSW_DTYPE)
 
     def chan_osw_ring(self, cid):
         """(device pointer, capacity in records) of the stage's record ring (rcf_chan_osw_ring)"""
