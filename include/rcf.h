@@ -592,7 +592,8 @@ int rcf_chan_slicer_rings(rcf_t *h, int chan_id, void **word_ring, size_t *word_
  * starts it afresh.  It goes when the slicer goes: slicer attached again or switched off, its source loop attached again or
  * switched off, channel closed.
  * RCF_ESTATE: the channel has no slicer in RCF_SLICE_FSK4 mode that searches a 48-bit sync word, or that slicer searches both
- * polarities (sync_both = 1); RCF_EINVAL: capacity not 0 or a power of two >= 16 (at most 2^20); RCF_ENOCHAN: no such channel. */
+ * polarities (sync_both = 1), or it carries the P25 voice stage (rcf_chan_p25lc); RCF_EINVAL: capacity not 0 or a power of
+ * two >= 16 (at most 2^20); RCF_ENOCHAN: no such channel. */
 typedef struct rcf_tsbk_params {
     int capacity;          /* records of the ring, a power of two >= 16; 0 = 256 */
     int reserved_[3];
@@ -742,6 +743,81 @@ int rcf_chan_osw_state(rcf_t *h, int chan_id, rcf_osw_state_t *out);
 int64_t rcf_chan_read_osw(rcf_t *h, int chan_id, uint32_t *out, size_t max_records);
 /* device pointer of the record ring and its capacity in records (zero-copy): record i lives at word 8 (i & (capacity - 1)) */
 int rcf_chan_osw_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity);
+/* P25 voice data units behind a slicer: what the reference's consumer does per frame of a voice channel in Python
+ * (logging_receiver.py p25_sensor 381-473 and p25_control_demod.py 365-385: p25_general.procHDU / procLDU1 / procTLC /
+ * subprocLC / procStatus, with the codecs of hamming.py, golay.py and rs64.py that stand beside p25_general's stubs), as one
+ * more optional stage per channel on the GPU: the voice-channel counterpart of rcf_chan_tsbk.  It reads the slicer's own two
+ * streams and writes a third, the counted stream RCF_HARD_P25LC of 32-byte records, one per frame: a consumer of a voice
+ * channel takes NAC, DUID and the decoded link control instead of every word of the dibit stream.  All of it is integer
+ * work: the records are exactly what the rules below give for the words and hits the slicer's readers deliver.  (No BCH
+ * correction of the NID, no decoding of LDU2's encryption sync or of the LSD's (16,8,5) code, no erasures from bad inner
+ * words into the Reed-Solomon decoder, no IMBE.)
+ * Frames.  Hits, the widening of k, the accept rule (k >= k_last_accepted + 24), the start at hit index >= the slicer's
+ * n_hits at the call, the lost rule and "info dibit j sits at frame dibit r = j + j / 35" are rcf_chan_tsbk's.  The frame
+ * starts at dibit s = k - 23; frame_dibits = min(864, s_next - s), s_next the frame start of the next accepted hit if there
+ * is one by then.  An accepted hit is DECIDED in the first block with 16 n_words >= s + 888: the 864 dibits of an LDU and
+ * the 24 of a sync word that may begin inside them -- so the records do not depend on how the input was cut into blocks.
+ * NID: nac = info bits 48 .. 59, duid = info bits 60 .. 63, uncorrected (info bit 0 is the sync word's first bit).
+ * Units.  A unit is decoded only if its last needed frame dibit lies inside the frame (r < frame_dibits):
+ *     duid 0x0  HDU   36 words of 18 bits, word w = info bits 112 + 18 w .. + 17; last dibit 389; inner code shortened Golay
+ *                     (18,6,8), outer code RS(36,20,17); payload 20 hexbits = 15 octets (MI 72, MFID 8, ALGID 8, KID 16, TGID 16)
+ *     duid 0x5  LDU1  24 words of 10 bits, word w = info bits 112 + B[w / 4] + 10 (w % 4) .. + 9, B = (288, 472, 656, 840,
+ *                     1024, 1208) (procLDU1's slices); inner code Hamming (10,6,3), outer code RS(24,12,13); payload the
+ *                     hexbits 0 .. 11 = 9 octets; the 32 raw LSD bits are info bits 1504 .. 1535; last dibit 788
+ *     duid 0xF  TLC   12 words of 24 bits, word w = info bits 112 + 24 w .. + 23; last dibit 204; inner code extended Golay
+ *                     (24,12,8), two hexbits per word, outer code RS(24,12,13); payload 9 octets
+ * Every other duid (3, 7, 0xA -- LDU2, whose duid the consumer's activity rule needs --, 0xC, unknown) and a decodable duid
+ * whose frame is too short gives a frame record without payload.
+ * Modes.  correct = 0: p25_general's own reading, bit for bit: the payload is the first 6 (12 for the (24,12) words) bits of
+ * every inner word, then the first 72 (HDU: 120) of those bits; nothing is corrected and all counts are 0.  correct = 1: the
+ * decoders below.
+ * Hamming (10,6,3), the first bit highest: the syndrome's four bits are the parities of the word under 0b1110011000,
+ * 0b1101010100, 0b1011100010, 0b0111100001.  Syndrome 0: the word is good.  Syndrome equal to entry i of (1110, 1101, 1011,
+ * 0111, 0011, 1100, 1000, 0100, 0010, 0001): bit i counted from the first is flipped and the word counts as FIXED.
+ * Anything else: the word counts as BAD and its data bits are taken as read.
+ * Golay, generator 0xC75: the result is the 12 data bits (the first 12) of the (23,12,7) code word nearest to the word's
+ * first 23 bits -- unique and at most 3 bits away, the code being perfect; the 24th bit takes no part (golay.py searches on
+ * msg >> 1).  The word counts as FIXED if any of the 23 bits changed.  An (18,6) word is extended by six leading zero data
+ * bits; if the nearest code word's six leading data bits are not all zero the word counts as BAD and its data are taken as
+ * read.  This decoder is complete; the reference's error-trapping search returns None on about half a percent of the
+ * patterns of up to three errors.
+ * RS(n, k, d) over GF(64), primitive polynomial x^6 + x + 1, alpha = 2, generator roots alpha^1 .. alpha^(d - 1), symbols
+ * in the order of rs64.py's msg (data first, parity behind: symbol i is the coefficient of x^(n - 1 - i)), t = (d - 1) / 2.
+ * The result is the code word of the shortened code within t symbols of the inner-decoded word if there is one -- it is
+ * unique --, n_rs the number of symbols it changes; otherwise rs_bad is set, n_rs is 0 and the payload is the inner-decoded
+ * data symbols as they stand.  No erasures.
+ * Records, 8 uint32 each, in increasing k:
+ *     word 0    bits 0-1 kind (0 HDU, 1 LDU1, 2 TLC, 3 a frame record), bit 2 rs_bad, bit 3 zero, bits 4-7 n_rs, bits 8-9
+ *               zero, bits 10-15 the hit's distance, bits 16-19 duid, bits 20-31 nac (the last three where TSBK has them)
+ *     word 1    the low 32 bits of the widened k
+ *     word 2-5  the payload's octets, the first bit highest, bytes in memory order (the word ring's rule), zero padded; 0
+ *               in a frame record
+ *     word 6    the 32 raw LSD bits, same rule (LDU1), else 0
+ *     word 7    bits 0-15 frame_dibits, bits 16-21 inner words fixed, bits 22-27 inner words bad, bits 28-31 zero
+ * p == NULL switches the stage off.  It applies from the next block on and considers only hits appended after the call;
+ * calling again starts it afresh.  It goes when the slicer goes: slicer attached again or switched off, its source loop
+ * attached again or switched off, channel closed.  A slicer carries this stage or the TSBK stage, never both: each of the two
+ * calls is refused while the other stage is attached.
+ * RCF_ESTATE: the channel has no slicer in RCF_SLICE_FSK4 mode that searches a 48-bit sync word, that slicer searches both
+ * polarities (sync_both = 1), or it carries the TSBK stage; RCF_EINVAL: capacity not 0 or a power of two >= 16 (at most
+ * 2^20), correct not 0 or 1; RCF_ENOCHAN: no such channel. */
+typedef struct rcf_p25lc_params {
+    int capacity;          /* records of the ring, a power of two >= 16; 0 = 256 */
+    int correct;           /* 0: the reference's p25_general reading (systematic bits, nothing corrected); 1: the decoders above */
+    int reserved_[2];
+} rcf_p25lc_params_t;
+int rcf_chan_p25lc(rcf_t *h, int chan_id, const rcf_p25lc_params_t *p);
+/* the stage's counters as of the last block; syncs the stream.  RCF_ESTATE without the stage (here and in the calls below) */
+typedef struct rcf_p25lc_state {
+    int64_t n_records, n_frames, n_decoded, n_rs_bad, n_lost;   /* records written, frames accepted (decided or lost), units decoded (HDU, LDU1, TLC), of them with rs_bad, hits and frames lost */
+} rcf_p25lc_state_t;
+int rcf_chan_p25lc_state(rcf_t *h, int chan_id, rcf_p25lc_state_t *out);
+/* unread records, oldest first: out = uint32[max_records][8] (one round trip); RCF_HARD_P25LC names the stream to
+ * rcf_chan_read_many and rcf_group_read_many (out = uint32[n_chans][cap_each][8]); the pump does not deliver it */
+#define RCF_HARD_P25LC   53   /* (52 stays unassigned like 50: the readers refuse both as unknown streams) */
+int64_t rcf_chan_read_p25lc(rcf_t *h, int chan_id, uint32_t *out, size_t max_records);
+/* device pointer of the record ring and its capacity in records (zero-copy): record i lives at word 8 (i & (capacity - 1)) */
+int rcf_chan_p25lc_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity);
 /* drift probe of p25_control_demod.py:123-127: moving_average_ff(window, 1) * (1/window) of the
  * discriminator output (window = 10000 there) == mean of gain*fm over the last `window` samples; this is
  * the value demod_watcher hands to frontend_connector.report_offset */

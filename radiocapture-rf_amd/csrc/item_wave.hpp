@@ -1,4 +1,4 @@
-// item_wave.hpp -- what the kernels in the slicer's layout share (slice.hip, tsbk.hip, edacs.hip, osw.hip): a WAVE is an
+// item_wave.hpp -- what the kernels in the slicer's layout share (slice.hip, tsbk.hip, edacs.hip, osw.hip, p25lc.hip): a WAVE is an
 // item (a channel's stage), four items per workgroup, nothing shared between the waves.  Here are the 64-bit lane reads and
 // the launcher; the walks are each kernel's own.
 #pragma once

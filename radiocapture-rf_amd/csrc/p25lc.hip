@@ -1,0 +1,187 @@
+// p25lc.hip -- P25 voice data units behind a channel's slicer (gfx950): what the reference's voice-channel consumer does per
+// frame in Python (logging_receiver.p25_sensor: p25_general.procHDU / procLDU1 / procTLC with the codecs of hamming.py,
+// golay.py and rs64.py) -- strip the status symbols, read the NID, and for a header, an LDU1 or a terminator with link
+// control decode the inner Golay / Hamming words and the outer Reed-Solomon word --, every such stage of a block (or of a
+// group's block) in one launch behind slice_kernel's.  include/rcf.h at rcf_chan_p25lc DEFINES the stage, tests/p25lc_ref.py
+// restates it; the arithmetic is p25lc_core.hpp, which the CPU suite compiles for the host as it stands.
+//
+// The slicer's layout: a WAVE is a channel, four channels per workgroup.  The walk over the hit ring, the accept rule and
+// the frame's length are tsbk.hip's (tsbk_core.hpp's helpers), with 864 + 24 dibits to wait for.  Per decided frame the
+// lanes 0 .. 31 gather the NID.  Then lane w is inner word w (36, 24 or 12 lanes): it gathers its 9, 5 or 12 dibits through
+// the status-symbol map, takes the syndrome with masks and popcount parity (Hamming) or twelve shift / xor rounds and the
+// syndrome table (Golay; see p25lc_core.hpp for why a table) and corrects.  The Reed-Solomon word has a symbol per lane:
+//   syndromes       lane m runs Horner over the symbols, read uniformly, for S[m] = r(alpha^(m + 1))
+//   Berlekamp-      a fixed 2 t rounds, coefficient i of the locator and of the shadow polynomial in lane i; a round is
+//   Massey          one lane-reversed read of S, a product, an xor-reduction over the wave (the discrepancy, then in every
+//                   lane) and one shifted read of the shadow polynomial
+//   Chien           lane i evaluates the locator at 1 / X_i; the ballot of the zeros is the error set, which must have as
+//                   many members as the locator's degree (a root outside the n positions is missing there)
+//   Forney          lane m forms coefficient m of S(x) Lambda(x), the error lanes evaluate it and the derivative
+//   re-check        the syndromes of the corrected word, again one per lane
+// instead of lane 0 walking dependent chains over 36 symbols with 63 lanes idle.  The lanes 0 .. 3 cut the payload words out
+// of the data symbols, the lanes 0 .. 7 store a record's eight words.
+// All trip counts come from the host's n_k or are compile-time constants; the counters read from the device only clamp.
+// Every ring index is masked.  Plain vector stores only; nothing is shared between waves; no LDS.  Every cross-lane read
+// stands in wave-uniform control flow.
+#include "item_wave.hpp"
+#include "p25lc_core.hpp"
+
+namespace rcfx {
+
+namespace {
+
+constexpr int kP25lcWaves = kItemWaves;
+
+__device__ __forceinline__ int ring_dibit(const P25lcLaunch &L, int64_t p)
+{
+    return tsbk_word_dibit(L.word_ring[(uint64_t)(p >> 4) & L.word_mask], (int)(p & 15));
+}
+__device__ __forceinline__ uint32_t lane_read(uint32_t v, int src) { return (uint32_t)__shfl((int)v, src & 63); }
+__device__ __forceinline__ uint32_t wave_xor(uint32_t v)
+{
+    for (int m = 32; m; m >>= 1) v ^= (uint32_t)__shfl_xor((int)v, m);
+    return v;
+}
+// lane m < 2 t: S[m] = the word's value at alpha^(m + 1); the other lanes 0
+__device__ __forceinline__ uint32_t rs_syndrome(uint32_t sym, int n, int t, int lane)
+{
+    const uint32_t am = p25lc_gf_alpha(lane + 1);
+    uint32_t S = 0;
+    for (int i = 0; i < kP25lcMaxSyms; ++i) {
+        const uint32_t r = lane_read(sym, i);
+        if (i < n) S = p25lc_gf_mul(S, am) ^ r;
+    }
+    return lane < 2 * t ? S : 0u;
+}
+// the symbols of RS(n, n - 2 t) (lane i: symbol i; the lanes >= n hold 0) -> the corrected symbols, or the symbols as they
+// are with *rs_bad; *n_rs: the symbols changed
+__device__ __forceinline__ uint32_t rs_decode(uint32_t sym, int n, int t, int lane, bool *rs_bad, int *n_rs)
+{
+    const uint32_t S = rs_syndrome(sym, n, t, lane);
+    uint32_t C = lane == 0 ? 1u : 0u, B = C, b = 1;
+    int Ln = 0, m = 1;
+    for (int r = 0; r < 2 * kP25lcMaxT; ++r) {
+        const uint32_t Sr = lane_read(S, r - lane);
+        const uint32_t d = wave_xor(lane <= r ? p25lc_gf_mul(C, Sr) : 0u);
+        const uint32_t Bs = lane_read(B, lane - m);
+        if (r >= 2 * t) continue;                    // (uniform)
+        if (d == 0) { ++m; continue; }
+        const uint32_t Cn = C ^ p25lc_gf_mul(p25lc_gf_mul(d, p25lc_gf_inv(b)), lane >= m ? Bs : 0u);
+        if (2 * Ln <= r) { B = C; Ln = r + 1 - Ln; b = d; m = 1; } else ++m;
+        C = Cn;
+    }
+    const uint32_t xi = lane < n ? p25lc_rs_xinv(n, lane) : 0u, xi2 = p25lc_gf_mul(xi, xi);
+    uint32_t v = 0, om = 0;
+    for (int j = kP25lcMaxT; j >= 0; --j) v = p25lc_gf_mul(v, xi) ^ lane_read(C, j);
+    const bool root = lane < n && v == 0;
+    const bool ok = Ln <= t && __popcll(__ballot(root)) == Ln;
+    for (int i = 0; i <= kP25lcMaxT; ++i) {          // coefficient `lane` of S(x) Lambda(x)
+        const uint32_t ci = lane_read(C, i), si = lane_read(S, lane - i);
+        if (i <= lane) om ^= p25lc_gf_mul(ci, si);
+    }
+    uint32_t num = 0, den = 0;
+    for (int j = kP25lcMaxT - 1; j >= 0; --j) num = p25lc_gf_mul(num, xi) ^ lane_read(om, j);
+    for (int j = kP25lcMaxT - 1; j >= 1; j -= 2) den = p25lc_gf_mul(den, xi2) ^ lane_read(C, j);
+    const uint32_t e = root && den ? p25lc_gf_mul(num, p25lc_gf_inv(den)) : 0u;
+    const uint32_t fixed = sym ^ e;
+    const bool left = __ballot(rs_syndrome(fixed, n, t, lane) != 0) != 0;
+    *rs_bad = !ok || left;
+    *n_rs = *rs_bad ? 0 : __popcll(__ballot(e != 0));
+    return *rs_bad ? sym : fixed;
+}
+
+__global__ __launch_bounds__(64 * kP25lcWaves) void p25lc_kernel(const P25lcLaunch *__restrict__ items, int n_items)
+{
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(blockIdx.x * kP25lcWaves + (threadIdx.x >> 6));
+    if (w >= n_items) return;                        // (no workgroup barrier below: a wave leaves on its own)
+    const P25lcLaunch L = items[w];
+    P25lcState *st = L.st;
+    const bool correct = L.flags & kP25lcFlagCorrect;
+    const int64_t n_sym = L.src->n_symbols, n_words = L.src->n_words, n_hits = L.src->n_hits;
+    int64_t n_records = st->n_records, n_frames = st->n_frames, n_decoded = st->n_decoded, n_rs_bad = st->n_rs_bad, n_lost = st->n_lost;
+    int64_t i = st->next_hit, k_last = st->k_last;
+    const int64_t hit_cap = (int64_t)L.hit_mask + 1, word_cap = (int64_t)L.word_mask + 1;
+    if (i < n_hits - hit_cap) { n_lost += n_hits - hit_cap - i; i = n_hits - hit_cap; }      // hits that left the ring unexamined
+    // the host's bounds, whatever the counters say (tsbk.hip): this block's hits and those of an undecided frame's 888 dibits
+    // and the unfinished word; a decided frame costs at most two trips, 64 rejected hits one
+    const int bound = L.n_k + kP25lcDecideDibits + 32;
+    const int trips = 2 * (bound / kTsbkSyncDibits + 1) + bound / 64 + 2;
+    for (int t = 0; t < trips && i < n_hits; ++t) {
+        const bool valid = i + lane < n_hits;
+        const uint32_t item = valid ? L.hit_ring[(uint64_t)(i + lane) & L.hit_mask] : 0u;
+        const int64_t k = tsbk_widen_k(item, n_sym);
+        const uint64_t acc = __ballot(valid && tsbk_accept(k, k_last));
+        if (!acc) { i += n_hits - i < 64 ? n_hits - i : 64; continue; }                      // all rejected
+        const int a = __builtin_ctzll(acc);
+        if (a > 32) { i += a; continue; }            // take the chunk again from the accepted hit on: the next frame's hit is among the 24 behind it
+        const int64_t k0 = rl_i64(k, a), s = k0 - (kTsbkSyncDibits - 1);
+        const uint32_t dist = (uint32_t)__builtin_amdgcn_readlane((int)item, a) >> 26;
+        i += a;
+        if (16 * n_words < s + kP25lcDecideDibits) break;                                     // not all there yet: the next launch
+        const uint64_t nxt = __ballot(valid && lane > a && tsbk_accept(k, k0));
+        int fd = kP25lcFrameDibits;
+        if (nxt) {
+            const int64_t gap = rl_i64(k, __builtin_ctzll(nxt)) - k0;
+            if (gap < fd) fd = (int)gap;
+        }
+        ++i; k_last = k0; ++n_frames;
+        if ((s >> 4) < n_words - word_cap) { ++n_lost; continue; }                            // its first word is overwritten
+        const auto dibit = [&L, s](int r) { return ring_dibit(L, s + r); };
+        // ---- the NID: info dibits 24 .. 55
+        const int dn = lane < 32 ? dibit(tsbk_frame_pos(24 + lane)) : 0;
+        const uint64_t nhi = __ballot(dn & 2), nlo = __ballot(dn & 1);
+        const uint32_t nid0 = slice_word_be(nhi, nlo, 2, 0);
+        const int kind = __builtin_amdgcn_readfirstlane(p25lc_kind(tsbk_duid(nid0), fd));
+        uint32_t *rec = L.rec_ring + ((uint64_t)n_records & L.rec_mask) * kP25lcRecWords;
+        ++n_records;
+        if (kind == kP25lcFrame) {
+            const uint32_t v = lane == 0 ? p25lc_word0(kind, false, 0, dist, nid0) : lane == 1 ? (uint32_t)(uint64_t)k0 : lane == 7 ? p25lc_word7(fd, 0, 0) : 0u;
+            if (lane < kP25lcRecWords) rec[lane] = v;
+            continue;
+        }
+        // ---- inner word `lane`
+        const bool mine = lane < p25lc_inner_words(kind);
+        const uint32_t word = mine ? p25lc_gather(dibit, kind, lane) : 0u;
+        int status = 0;
+        uint32_t data = mine ? (correct ? p25lc_inner(kind, word, &status) : p25lc_systematic(kind, word)) : 0u;
+        const int n_fixed = __popcll(__ballot(mine && status == 1)), n_bad = __popcll(__ballot(mine && status == 2));
+        const int n = p25lc_rs_n(kind), kk = p25lc_rs_k(kind);
+        if (kind == kP25lcTlc) {                     // a Golay word is two symbols
+            const uint32_t two = lane_read(data, lane >> 1);
+            data = lane < n ? (lane & 1 ? two & 63u : two >> 6) : 0u;
+        }
+        bool rs_bad = false;
+        int n_rs = 0;
+        if (correct) data = rs_decode(data, n, p25lc_rs_t(kind), lane, &rs_bad, &n_rs);      // (uniform)
+        // ---- the payload: the data symbols' bits, the lanes 0 .. 3 a word each
+        uint64_t pay = 0;
+        for (int j = 0; j < 7; ++j) {
+            const int at = p25lc_pay_first(lane & 3) + j;
+            const uint32_t v = lane_read(data, at);
+            pay = pay << 6 | (at < kk ? v : 0u);
+        }
+        const uint32_t pw = lane_read(slice_word_mem(p25lc_pay_word(pay, lane & 3)), lane - 2);
+        const int dl = kind == kP25lcLdu1 && lane < 16 ? dibit(tsbk_frame_pos(kP25lcLsdDibit + lane)) : 0;
+        const uint64_t lhi = __ballot(dl & 2), llo = __ballot(dl & 1);
+        const uint32_t v = lane == 0 ? p25lc_word0(kind, rs_bad, n_rs, dist, nid0) : lane == 1 ? (uint32_t)(uint64_t)k0 : lane < 6 ? pw :
+                           lane == 6 ? slice_word_mem(slice_word_be(lhi, llo, 2, 0)) : p25lc_word7(fd, n_fixed, n_bad);
+        if (lane < kP25lcRecWords) rec[lane] = v;
+        ++n_decoded;
+        n_rs_bad += rs_bad ? 1 : 0;
+    }
+    if (lane == 0) {
+        st->n_records = n_records; st->n_frames = n_frames; st->n_decoded = n_decoded; st->n_rs_bad = n_rs_bad; st->n_lost = n_lost;
+        st->next_hit = i; st->k_last = k_last;
+    }
+}
+
+}  // namespace
+
+// ring_mask: unused -- every record carries the masks of its three rings
+void launch_p25lc(const P25lcLaunch *d_items, int n_items, int max_n_k, uint64_t, hipStream_t s)
+{
+    launch_item_waves(p25lc_kernel, d_items, n_items, max_n_k, s);
+}
+
+}  // namespace rcfx

@@ -352,7 +352,7 @@ struct SliceLaunch {
     int32_t sync_both;       // 1: a window within sync_max_errors of the inverted word is a hit too
 };
 void launch_slice(const SliceLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
-// What the launch records of the frame decoders behind a slicer (TSBK, EDACS, OSW) begin with, State being the decoder's
+// What the launch records of the frame decoders behind a slicer (TSBK, EDACS, OSW, P25 voice) begin with, State being the decoder's
 // own state record: n_records first, next_hit somewhere behind its counters.  (The records derive from it rather than
 // being it: the kernels keep their names.)
 template <class State> struct FramesLaunch {
@@ -400,6 +400,19 @@ struct OswState {
 };
 struct OswLaunch : FramesLaunch<OswState> {};
 void launch_osw(const OswLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
+// P25 voice data units behind a slicer (p25lc.hip; p25_sensor of the reference: procHDU / procLDU1 / procTLC with the Golay,
+// Hamming and Reed-Solomon codecs beside them; definition: include/rcf.h at rcf_chan_p25lc).
+// per-channel running state, device resident, owned by p25lc_kernel
+struct P25lcState {
+    int64_t n_records;       // records written so far (record i at rec_ring[(i & rec_mask) * 8])
+    int64_t n_frames, n_decoded, n_rs_bad, n_lost;
+    int64_t next_hit;        // the first hit of the slicer's stream that is neither rejected nor decided
+    int64_t k_last;          // the last accepted hit's k
+};
+struct P25lcLaunch : FramesLaunch<P25lcState> {
+    uint32_t flags;          // bit 0: the stage's `correct`
+};
+void launch_p25lc(const P25lcLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
 // the records' layouts as the kernels were compiled for them
 #pragma GCC diagnostic push
 #pragma GCC diagnostic ignored "-Winvalid-offsetof"
@@ -412,6 +425,7 @@ template <class L> constexpr bool frames_launch_layout()
 static_assert(frames_launch_layout<TsbkLaunch>() && sizeof(TsbkLaunch) == 56, "TsbkLaunch");
 static_assert(frames_launch_layout<OswLaunch>() && sizeof(OswLaunch) == 56, "OswLaunch");
 static_assert(frames_launch_layout<EdacsLaunch>() && sizeof(EdacsLaunch) == 64 && offsetof(EdacsLaunch, flags) == 56, "EdacsLaunch");
+static_assert(frames_launch_layout<P25lcLaunch>() && sizeof(P25lcLaunch) == 64 && offsetof(P25lcLaunch, flags) == 56, "P25lcLaunch");
 #pragma GCC diagnostic pop
 // mean of gain * fm over the last `window` samples ending at n_end (exclusive), one workgroup
 void launch_fm_level(const float *fm_ring, int64_t n_end, int window, float gain, uint64_t ring_mask, float *d_out,

@@ -1,5 +1,5 @@
 // rcf_plan.h -- the per-block schedule: what one commit of one front-end launches, built on the host first.  The stages
-// behind the FIRs (symbol filters, AGCs, the three symbol loops, the slicers behind the loops, the TSBK, EDACS and OSW stages behind the slicers) are one table, TailStages: a block's plan and a group's
+// behind the FIRs (symbol filters, AGCs, the three symbol loops, the slicers behind the loops, the TSBK, EDACS, OSW and P25 voice stages behind the slicers) are one table, TailStages: a block's plan and a group's
 // block each hold one, and the planner, the group's merge and the launcher visit it through TailStages::each.
 #pragma once
 #include <chrono>
@@ -90,6 +90,7 @@ struct TailStages {
     StageRecs<TsbkLaunch> tsf;         // P25 trunking blocks, behind the slicers: they read the slicers' rings and counters
     StageRecs<EdacsLaunch> edf;        // EDACS control frames, behind the slicers likewise
     StageRecs<OswLaunch> osf;          // SmartNet OSWs, behind the slicers likewise
+    StageRecs<P25lcLaunch> lcf;        // P25 voice data units, behind the slicers likewise
     template <class F, class... T> static void each(F &&f, T &...t)
     {
         f(RCF_T_DISC, launch_fm_fir, t.symf...);
@@ -101,6 +102,7 @@ struct TailStages {
         f(RCF_T_SLICE, launch_tsbk, t.tsf...);
         f(RCF_T_SLICE, launch_edacs, t.edf...);
         f(RCF_T_SLICE, launch_osw, t.osf...);
+        f(RCF_T_SLICE, launch_p25lc, t.lcf...);
     }
     template <class Rec> StageRecs<Rec> &of()      // the stage whose records are plain StageRecs<Rec>: found at compile time
     {

@@ -24,7 +24,7 @@ template <class R> void frames_row(Chan *c, Stream *s)
 }
 // ring, reader and counter of every row of kStreams and of the readers' rows behind it, in their order; a row that leaves the
 // ring null is refused
-void (*const kRows[kAllReadKinds])(Chan *, Stream *) = {
+void (*const kRows[kReadKindsEnd])(Chan *, Stream *) = {
     [](Chan *c, Stream *s) { if (!c->fm_only) plain_row(c, s, c->d_iq, &c->rd_iq); },
     [](Chan *c, Stream *s) { plain_row(c, s, c->d_fm, &c->rd_fm); },
     [](Chan *c, Stream *s) { if (c->agc) plain_row(c, s, c->agc->rec.agc_ring, &c->agc->rd); },
@@ -38,6 +38,7 @@ void (*const kRows[kAllReadKinds])(Chan *, Stream *) = {
     frames_row<Chan::Slicer::Tsbk>,
     frames_row<Chan::Slicer::Edacs>,
     frames_row<Chan::Slicer::Osw>,
+    frames_row<Chan::Slicer::P25lc>,
 };
 
 }  // namespace
@@ -231,6 +232,7 @@ int64_t rcf_chan_read_sync(rcf_t *h, int chan_id, uint32_t *out, size_t n) { ret
 int64_t rcf_chan_read_tsbk(rcf_t *h, int chan_id, uint32_t *out, size_t n) { return chan_read_one(h, chan_id, RCF_HARD_TSBK, 1.0f, out, n); }
 int64_t rcf_chan_read_edacs(rcf_t *h, int chan_id, uint32_t *out, size_t n) { return chan_read_one(h, chan_id, RCF_HARD_EDACS, 1.0f, out, n); }
 int64_t rcf_chan_read_osw(rcf_t *h, int chan_id, uint32_t *out, size_t n) { return chan_read_one(h, chan_id, RCF_HARD_OSW, 1.0f, out, n); }
+int64_t rcf_chan_read_p25lc(rcf_t *h, int chan_id, uint32_t *out, size_t n) { return chan_read_one(h, chan_id, RCF_HARD_P25LC, 1.0f, out, n); }
 
 int rcf_chan_read_many(rcf_t *h, int what, const int *chan_ids, int n_chans, float gain, void *out, size_t cap_each,
                        int64_t *counts)
@@ -289,5 +291,6 @@ int rcf_chan_slicer_rings(rcf_t *h, int chan_id, void **word_ring, size_t *word_
 int rcf_chan_tsbk_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity) { return chan_rings(h, chan_id, kTsbk, true, rec_ring, nullptr, capacity); }
 int rcf_chan_edacs_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity) { return chan_rings(h, chan_id, kEdacs, true, rec_ring, nullptr, capacity); }
 int rcf_chan_osw_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity) { return chan_rings(h, chan_id, kOsw, true, rec_ring, nullptr, capacity); }
+int rcf_chan_p25lc_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity) { return chan_rings(h, chan_id, kP25lc, true, rec_ring, nullptr, capacity); }
 
 }  // extern "C"

@@ -1,13 +1,13 @@
 // rcf_stage.cpp -- the optional stages behind a channel's rings (the records of Chan, rcf_state.h): the P25 symbol filter,
 // the feed-forward AGC, the SmartNet / EDACS symbol clock, the P25 CQPSK Gardner / Costas loop, the P25 C4FM symbol loop and
 // the analog voice chain, the slicer behind one of the loops and the frame decoder behind the slicer (P25 trunking blocks,
-// EDACS control frames or SmartNet OSWs).
+// EDACS control frames, SmartNet OSWs or P25 voice data units).
 // Attach, off, and what they produced.
 // An attach function allocates into Fresh<> holders and builds the new record completely; only then is it swapped into
 // the channel and the old one released.  A HIP call that fails before that leaves the channel as it was.
 // The three symbol loops share their record (Chan::Loop) and one attach path, attach_loop: an entry point validates its
 // parameters, checks what the loop reads and the ring's size, and fills in its own constants and initial state.
-// The three frame decoders likewise: one record (Slicer::Frames), one attach path, attach_frames, and one state path,
+// The four frame decoders likewise: one record (Slicer::Frames), one attach path, attach_frames, and one state path,
 // frames_state; an entry point brings what it asks of the slicer and its own lines of the initial state.
 #include "rcf_plan.h"
 #define RCF_DEVFN static inline
@@ -15,6 +15,7 @@
 #include "tsbk_core.hpp"       // (kTsbkNoFrame, kTsbkRecWords)
 #include "edacs_core.hpp"      // (kEdacsNoFrame, kEdacsRecWords; slice_sync_both_ok of slice_core.hpp)
 #include "osw_core.hpp"        // (kOswSyncBits, kOswRecWords)
+#include "p25lc_core.hpp"      // (kP25lcRecWords, kP25lcFlagCorrect)
 
 namespace rcfx {
 
@@ -94,7 +95,7 @@ static int attach_loop(rcf_t *h, Chan *c, std::unique_ptr<R> &stage, std::unique
 }
 
 // What attaching a frame decoder R behind the slicer comes to; its entry point brings slicer_ok, what it asks of the slicer
-// (else RCF_ESTATE with `refusal`), and init, its own lines of the launch record and of the initial state.  p == nullptr: off.
+// and of what else it carries (else RCF_ESTATE with `refusal`), and init, its own lines of the launch record and of the initial state.  p == nullptr: off.
 // One allocation -- record ring of cap records | the state record, in a slot of 256 bytes (cap >= 16: the state's 64-bit
 // fields are aligned) --, one copy, and the swap.  Every call is a new stream: a fresh ring and state, cursor 0; the first
 // hit is the slicer's count as of everything queued (one round trip), which `now` hands to init as well.
@@ -114,7 +115,7 @@ static int attach_frames(rcf_t *h, int chan_id, const P *p, Ok &&slicer_ok, cons
         if (c->slicer && c->slicer->frames<R>()) { release_frames(h, c->slicer->frames<R>()); ++h->chans_epoch; }
         return RCF_OK;
     }
-    if (!c->slicer || !slicer_ok(c->slicer->rec)) { set_error(refusal, chan_id); return RCF_ESTATE; }
+    if (!c->slicer || !slicer_ok(*c->slicer)) { set_error(refusal, chan_id); return RCF_ESTATE; }
     const SliceLaunch &sl = c->slicer->rec;
     std::unique_ptr<R> k(new R);
     typename R::Launch &r = k->rec;
@@ -143,7 +144,8 @@ static int attach_frames(rcf_t *h, int chan_id, const P *p, Ok &&slicer_ok, cons
     ++h->chans_epoch;
     return RCF_OK;
 }
-static_assert(read_row(kTsbk).item_w == kTsbkRecWords && read_row(kEdacs).item_w == kEdacsRecWords && read_row(kOsw).item_w == kOswRecWords,
+static_assert(read_row(kTsbk).item_w == kTsbkRecWords && read_row(kEdacs).item_w == kEdacsRecWords && read_row(kOsw).item_w == kOswRecWords &&
+              read_row(kP25lc).item_w == kP25lcRecWords,
               "the stream table's words per record are the kernels'");
 
 // the decoder's counters -- its state record up to next_hit -- as of everything queued; refused as its stream is
@@ -437,12 +439,12 @@ int rcf_chan_slicer_state(rcf_t *h, int chan_id, rcf_slicer_state_t *out)
     return RCF_OK;
 }
 
-// ---- the frame decoders behind the slicer (tsbk.hip, edacs.hip, osw.hip)
+// ---- the frame decoders behind the slicer (tsbk.hip, edacs.hip, osw.hip, p25lc.hip)
 int rcf_chan_tsbk(rcf_t *h, int chan_id, const rcf_tsbk_params_t *p)
 {
     return attach_frames<Chan::Slicer::Tsbk>(h, chan_id, p,
-        [](const SliceLaunch &sl) { return sl.bps == 2 && sl.sync_bits == 48 && !sl.sync_both; },
-        "channel %d has no slicer in RCF_SLICE_FSK4 mode that searches a 48-bit sync word in one polarity",
+        [](const Chan::Slicer &l) { return l.rec.bps == 2 && l.rec.sync_bits == 48 && !l.rec.sync_both && !l.p25lc; },
+        "channel %d has no slicer in RCF_SLICE_FSK4 mode that searches a 48-bit sync word in one polarity, or that slicer carries the P25 voice stage",
         [](TsbkLaunch &, TsbkState &st0, const SliceLaunch &, const SliceState &) { st0.k_last = kTsbkNoFrame; });
 }
 
@@ -458,7 +460,7 @@ int rcf_chan_tsbk_state(rcf_t *h, int chan_id, rcf_tsbk_state_t *out)
 int rcf_chan_edacs(rcf_t *h, int chan_id, const rcf_edacs_params_t *p)
 {
     return attach_frames<Chan::Slicer::Edacs>(h, chan_id, p,
-        [](const SliceLaunch &sl) { return sl.bps == 1 && sl.sync_bits == kEdacsSyncBits; },
+        [](const Chan::Slicer &l) { return l.rec.bps == 1 && l.rec.sync_bits == kEdacsSyncBits; },
         "channel %d has no slicer in RCF_SLICE_BINARY mode that searches a 48-bit sync word",
         [p](EdacsLaunch &r, EdacsState &st0, const SliceLaunch &sl, const SliceState &) {
             r.flags = (sl.sync_both ? kEdacsFlagBoth : 0u) | (p->esk ? kEdacsFlagEsk : 0u);
@@ -478,7 +480,7 @@ int rcf_chan_edacs_state(rcf_t *h, int chan_id, rcf_edacs_state_t *out)
 int rcf_chan_osw(rcf_t *h, int chan_id, const rcf_osw_params_t *p)
 {
     return attach_frames<Chan::Slicer::Osw>(h, chan_id, p,
-        [](const SliceLaunch &sl) { return sl.bps == 1 && sl.sync_bits == kOswSyncBits && sl.sync_max_errors == 0 && !sl.sync_both; },
+        [](const Chan::Slicer &l) { return l.rec.bps == 1 && l.rec.sync_bits == kOswSyncBits && l.rec.sync_max_errors == 0 && !l.rec.sync_both; },
         "channel %d has no slicer in RCF_SLICE_BINARY mode that searches an 8-bit sync word exactly, in one polarity",
         [](OswLaunch &, OswState &st0, const SliceLaunch &, const SliceState &now) { st0.pos = now.n_symbols; });     // its cursor
 }
@@ -490,6 +492,27 @@ int rcf_chan_osw_state(rcf_t *h, int chan_id, rcf_osw_state_t *out)
     if (rc != RCF_OK) return rc;
     out->n_records = st.n_records; out->n_frames = st.n_frames; out->n_bad = st.n_bad; out->n_rejects = st.n_rejects; out->n_lost = st.n_lost;
     out->locked = st.locked; out->is_locked = st.is_locked;
+    return RCF_OK;
+}
+
+int rcf_chan_p25lc(rcf_t *h, int chan_id, const rcf_p25lc_params_t *p)
+{
+    if (p && p->correct != 0 && p->correct != 1) { set_error("P25 voice stage: correct %d is not 0 or 1", p->correct); return RCF_EINVAL; }
+    return attach_frames<Chan::Slicer::P25lc>(h, chan_id, p,
+        [](const Chan::Slicer &l) { return l.rec.bps == 2 && l.rec.sync_bits == 48 && !l.rec.sync_both && !l.tsbk; },
+        "channel %d has no slicer in RCF_SLICE_FSK4 mode that searches a 48-bit sync word in one polarity, or that slicer carries the TSBK stage",
+        [p](P25lcLaunch &r, P25lcState &st0, const SliceLaunch &, const SliceState &) {
+            r.flags = p->correct ? kP25lcFlagCorrect : 0u;
+            st0.k_last = kTsbkNoFrame;
+        });
+}
+
+int rcf_chan_p25lc_state(rcf_t *h, int chan_id, rcf_p25lc_state_t *out)
+{
+    P25lcState st{};                    // (its five counters)
+    const int rc = frames_state<Chan::Slicer::P25lc>(h, chan_id, out, &st);
+    if (rc != RCF_OK) return rc;
+    out->n_records = st.n_records; out->n_frames = st.n_frames; out->n_decoded = st.n_decoded; out->n_rs_bad = st.n_rs_bad; out->n_lost = st.n_lost;
     return RCF_OK;
 }
 

@@ -174,7 +174,7 @@ struct Chan {
         uint32_t hit_cap = 0;
         int64_t rd_words = 0, rd_hits = 0;
         // The frame decoders out of the slicer's two streams: P25 trunking blocks (rcf_chan_tsbk), EDACS control frames
-        // (rcf_chan_edacs), SmartNet OSWs (rcf_chan_osw).  One record shape.  A decoder hangs off the slicer -- Chan stays
+        // (rcf_chan_edacs), SmartNet OSWs (rcf_chan_osw), P25 voice data units (rcf_chan_p25lc).  One record shape.  A decoder hangs off the slicer -- Chan stays
         // inside its prefetched lines -- and goes whenever the slicer goes.  One allocation, which starts at rec.rec_ring:
         // record ring of cap records of the stream's item_w words | the state record, in a slot of 256 bytes.  A second
         // call: new ring and state, cursor 0 (attach_frames, rcf_stage.cpp).  kKind: the decoder's stream (rcf_streams.h:
@@ -191,10 +191,13 @@ struct Chan {
         struct Osw : Frames<OswState, OswLaunch> { static constexpr int kKind = kOsw; static constexpr const char *kName = "OSW"; };
         std::unique_ptr<Tsbk> tsbk;
         std::unique_ptr<Edacs> edacs;
+        struct P25lc : Frames<P25lcState, P25lcLaunch> { static constexpr int kKind = kP25lc; static constexpr const char *kName = "P25 voice"; };
         std::unique_ptr<Osw> osw;
+        std::unique_ptr<P25lc> p25lc;
         // The one list of them.  At most one is ever attached: what they ask of the slicer excludes each other (TSBK: 2
-        // bits per symbol; EDACS: binary, a 48-bit sync word; OSW: binary, an 8-bit sync word matched exactly)
-        template <class F> void for_each_frames(F &&f) { f(tsbk); f(edacs); f(osw); }
+        // bits per symbol; EDACS: binary, a 48-bit sync word; OSW: binary, an 8-bit sync word matched exactly), and the two
+        // that ask the same, TSBK and the P25 voice stage (rcf_chan_p25lc), refuse each other by name
+        template <class F> void for_each_frames(F &&f) { f(tsbk); f(edacs); f(osw); f(p25lc); }
         template <class R> std::unique_ptr<R> &frames()                  // the list's holder of an R
         {
             std::unique_ptr<R> *r = nullptr;
@@ -490,14 +493,14 @@ template <class S, class R, float *R::*Ring> void Chan::Loop<S, R, Ring>::releas
 // ---- the one read path.  A stream is a device ring of `cap` items (a power of two) of item_w 4-byte words: item i at word
 // (i & (cap - 1)) * stride_w of ring when stride_w > 1 (one bin of a frame-major ring of floats), else at
 // (i & (cap - 1)) * item_w.  A plain stream's end the host knows: the ring holds the cap items before `newest`, a reader at
-// *cursor may take up to `end`.  A counted stream -- counter != nullptr: a symbol loop's, the voice chain's, the slicer's, the TSBK, EDACS and OSW stages' --
+// *cursor may take up to `end`.  A counted stream -- counter != nullptr: a symbol loop's, the voice chain's, the slicer's, the TSBK, EDACS, OSW and P25 voice stages' --
 // ends at ceil(*counter * interp / decim) of a DEVICE counter, which the counted gather reads itself (CountedRec,
 // rcf_internal.h); serial: which attachment of the stage this is (a re-attached stage starts a new stream)
 struct Stream {
     rcf_t *h = nullptr;
     const void *ring = nullptr;
     uint32_t item_w = 1, stride_w = 0;
-    uint32_t cap = 0;                  // the handle's out_cap, or the ring's own (the slicer's hit ring, the TSBK, EDACS and OSW records')
+    uint32_t cap = 0;                  // the handle's out_cap, or the ring's own (the slicer's hit ring, the frame decoders' records')
     int64_t *cursor = nullptr;
     int64_t end = 0, newest = 0;       // plain
     const int64_t *counter = nullptr;  // counted

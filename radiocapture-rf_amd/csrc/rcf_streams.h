@@ -45,23 +45,27 @@ static_assert(stream_kind(RCF_READ_AUDIO) == kAudio && stream_kind(RCF_HARD_SYNC
 // kReadKinds is where the rows ended when the first of them (49) came, and stays there -- a consumer compiled against it sees
 // what it saw; rows added since go on behind it, and kAllReadKinds ends them all.  A new stream takes a number that was never
 // refused by name: 50 stands in the suite as the readers' example of "no such stream", so the OSW stage's is 51.
-enum : int { kEdacs = kStreamKinds, kReadKinds, kOsw = kReadKinds, kAllReadKinds };
-constexpr StreamKind kReadOnlyStreams[kAllReadKinds - kStreamKinds] = {
+// kAllReadKinds in turn is where they ended when the P25 voice stage's row came (the suite pins it as it pins kReadKinds, and
+// 52 beside 50 as no stream: the row's number is 53); kReadKindsEnd ends them all now, and the readers' loops run to it.
+enum : int { kEdacs = kStreamKinds, kReadKinds, kOsw = kReadKinds, kAllReadKinds, kP25lc = kAllReadKinds, kReadKindsEnd };
+constexpr StreamKind kReadOnlyStreams[kReadKindsEnd - kStreamKinds] = {
     {RCF_HARD_EDACS,  8, true,  true,  false, "channel %d has no EDACS stage (rcf_chan_edacs)"},
     {RCF_HARD_OSW,    8, true,  true,  false, "channel %d has no OSW stage (rcf_chan_osw)"},
+    {RCF_HARD_P25LC,  8, true,  true,  false, "channel %d has no P25 voice stage (rcf_chan_p25lc)"},
 };
 constexpr const StreamKind &read_row(int kind) { return kind < kStreamKinds ? kStreams[kind] : kReadOnlyStreams[kind - kStreamKinds]; }
 // the readers' kind of `what`: a row of the table, or one behind it; -1: no such stream
 constexpr int read_kind(int what)
 {
     if (stream_kind(what) >= 0) return stream_kind(what);
-    for (int k = kStreamKinds; k < kAllReadKinds; ++k)
+    for (int k = kStreamKinds; k < kReadKindsEnd; ++k)
         if (read_row(k).what == what) return k;
     return -1;
 }
 static_assert(read_kind(RCF_HARD_EDACS) == kEdacs && stream_kind(RCF_HARD_EDACS) == -1 && read_kind(RCF_HARD_TSBK) == kTsbk && !read_row(kEdacs).pumped,
               "the readers' rows go on behind the table; the pump finds none of them");
 static_assert(read_kind(RCF_HARD_OSW) == kOsw && stream_kind(RCF_HARD_OSW) == -1 && !read_row(kOsw).pumped && read_kind(50) == -1, "likewise");
+static_assert(read_kind(RCF_HARD_P25LC) == kP25lc && stream_kind(RCF_HARD_P25LC) == -1 && !read_row(kP25lc).pumped && read_kind(52) == -1, "likewise");
 
 // A reader that has fallen more than a ring of `cap` items behind lost what the ring overwrote: its cursor is raised to the
 // oldest item the ring still holds (the ring holds the cap items before `newest`).  Returns how many items [*cursor, end) it

@@ -41,6 +41,7 @@ SYMBOLS = [
     "rcf_chan_tsbk", "rcf_chan_tsbk_state", "rcf_chan_read_tsbk", "rcf_chan_tsbk_ring",
     "rcf_chan_edacs", "rcf_chan_edacs_state", "rcf_chan_read_edacs", "rcf_chan_edacs_ring",
     "rcf_chan_osw", "rcf_chan_osw_state", "rcf_chan_read_osw", "rcf_chan_osw_ring",
+    "rcf_chan_p25lc", "rcf_chan_p25lc_state", "rcf_chan_read_p25lc", "rcf_chan_p25lc_ring",
     "rcf_design_firdes", "rcf_design_optfir_low_pass", "rcf_design_fm_deemph", "rcf_design_resampler", "rcf_chan_audio_open",
     "rcf_chan_audio_close", "rcf_chan_audio_produced", "rcf_chan_read_audio",
     "rcf_host_alloc", "rcf_host_free", "rcf_comm_unique_id", "rcf_comm_init", "rcf_comm_destroy", "rcf_comm_size",
@@ -62,7 +63,9 @@ HARD_TSBK = 48
 HARD_EDACS = 49
 # ... and of the SmartNet OSW stage (RCF_HARD_OSW): records of 8 uint32 as well, one per frame
 HARD_OSW = 51
-_HARD_WHAT = {"hard": HARD_BITS, "sync": HARD_SYNC, "tsbk": HARD_TSBK, "edacs": HARD_EDACS, "osw": HARD_OSW}
+# ... and of the P25 voice stage (RCF_HARD_P25LC): records of 8 uint32, one per frame
+HARD_P25LC = 53
+_HARD_WHAT = {"hard": HARD_BITS, "sync": HARD_SYNC, "tsbk": HARD_TSBK, "edacs": HARD_EDACS, "osw": HARD_OSW, "p25lc": HARD_P25LC}
 # a record of RCF_HARD_TSBK (rcf.h at rcf_chan_tsbk): word 0 (see tsbk_fields), the low 32 bits of k, the 12 decoded octets,
 # the NID's 8 octets, frame_dibits
 TSBK_DTYPE = np.dtype([("flags", "<u4"), ("k", "<u4"), ("octets", "u1", (12,)), ("nid", "u1", (8,)), ("frame_dibits", "<u4")])
@@ -73,6 +76,9 @@ EDACS_DTYPE = np.dtype([("flags", "<u4"), ("k", "<u4"), ("m1", "u1", (8,)), ("m2
 # lid and cmd, the 38 corrected data bits and the 38 syndrome bits as octets (five each, in a field of eight), locked
 OSW_DTYPE = np.dtype([("flags", "<u4"), ("k", "<u4"), ("lid", "<u2"), ("cmd", "<u2"), ("data", "u1", (8,)), ("psyn", "u1", (8,)),
                       ("locked", "<i4")])
+# a record of RCF_HARD_P25LC (rcf.h at rcf_chan_p25lc): word 0 (see p25lc_fields), the low 32 bits of k, the payload's octets
+# (15 of an HDU, 9 of an LDU1 or a TLC, zero padded), the LDU1's four LSD octets, frame_dibits and the inner words' counts
+P25LC_DTYPE = np.dtype([("flags", "<u4"), ("k", "<u4"), ("payload", "u1", (16,)), ("lsd", "u1", (4,)), ("tail", "<u4")])
 SLICE_BINARY, SLICE_FSK4 = 1, 2
 T_FIR, T_PFB, T_FIR_DERIVED, T_DISC, T_SCAN_FFT, T_SCAN_MOVSUM, T_HISTORY, T_FIR_MFMA, T_AUDIO, T_TAPS, T_CLOCK, T_COSTAS, T_FSK4, T_SLICE = range(14)
 
@@ -228,7 +234,29 @@ def osw_fields(records):
                 syn_bits=((f >> 10) & 63).astype(np.uint8), rel=(f >> 16).astype(np.uint16))
 
 
-_RECORD_DTYPE = {HARD_TSBK: TSBK_DTYPE, HARD_EDACS: EDACS_DTYPE, HARD_OSW: OSW_DTYPE}
+class P25lcParams(C.Structure):
+    """rcf_p25lc_params_t (include/rcf.h)"""
+    _fields_ = [("capacity", C.c_int), ("correct", C.c_int), ("reserved_", C.c_int * 2)]
+
+
+class P25lcState(C.Structure):
+    """rcf_p25lc_state_t (include/rcf.h)"""
+    _fields_ = [("n_records", C.c_int64), ("n_frames", C.c_int64), ("n_decoded", C.c_int64), ("n_rs_bad", C.c_int64),
+                ("n_lost", C.c_int64)]
+
+
+def p25lc_fields(records):
+    """words 0 and 7 of P25 voice records taken apart -> dict of arrays: kind (0 HDU, 1 LDU1, 2 TLC, 3: a frame record),
+    rs_bad, n_rs, dist, duid, nac, frame_dibits, n_fixed, n_bad (inner words corrected / given up)"""
+    f = np.asarray(records["flags"], dtype=np.uint32)
+    t = np.asarray(records["tail"], dtype=np.uint32)
+    return dict(kind=(f & 3).astype(np.uint8), rs_bad=((f >> 2) & 1).astype(np.uint8), n_rs=((f >> 4) & 15).astype(np.uint8),
+                dist=((f >> 10) & 63).astype(np.uint8), duid=((f >> 16) & 15).astype(np.uint8), nac=(f >> 20).astype(np.uint16),
+                frame_dibits=(t & 0xffff).astype(np.uint16), n_fixed=((t >> 16) & 63).astype(np.uint8),
+                n_bad=((t >> 22) & 63).astype(np.uint8))
+
+
+_RECORD_DTYPE = {HARD_TSBK: TSBK_DTYPE, HARD_EDACS: EDACS_DTYPE, HARD_OSW: OSW_DTYPE, HARD_P25LC: P25LC_DTYPE}
 
 
 def widen_hits(items, n_symbols):
@@ -404,7 +432,8 @@ def lib():
         "rcf_pump_unsubscribe": (C.c_int, [vp, C.c_int]),
         "rcf_pump_stop": (C.c_int, [vp]),
     }
-    for name, params, state in (("tsbk", TsbkParams, TsbkState), ("edacs", EdacsParams, EdacsState), ("osw", OswParams, OswState)):
+    for name, params, state in (("tsbk", TsbkParams, TsbkState), ("edacs", EdacsParams, EdacsState), ("osw", OswParams, OswState),
+                                ("p25lc", P25lcParams, P25lcState)):
         sig["rcf_chan_" + name] = (C.c_int, [vp, C.c_int, C.POINTER(params)])     # the frame decoders behind the slicer
         sig["rcf_chan_%s_state" % name] = (C.c_int, [vp, C.c_int, C.POINTER(state)])
         sig["rcf_chan_read_" + name] = (i64, [vp, C.c_int, C.POINTER(C.c_uint32), sz])
@@ -420,7 +449,7 @@ def lib():
 def _read_what(what, stages=False):
     """the batched readers' and the pump's `what`: "iq", "agc", anything else the discriminator (as it always was).
     stages=True -- how every reader of this module calls it -- also names the stages' streams: "sym", "clock", "costas",
-    "fsk4", "audio", the slicer's "hard" and "sync", the TSBK stage's "tsbk", the EDACS stage's "edacs" and the OSW stage's "osw".  The one-argument form keeps its old answers ("sym" was never a
+    "fsk4", "audio", the slicer's "hard" and "sync", the TSBK stage's "tsbk", the EDACS stage's "edacs", the OSW stage's "osw" and the P25 voice stage's "p25lc".  The one-argument form keeps its old answers ("sym" was never a
     stream there: the discriminator)."""
     if stages and what in _STAGE_WHAT:
         return _STAGE_WHAT[what]
@@ -431,7 +460,7 @@ def _read_what(what, stages=False):
 
 def _read_dtype(what):
     """item type of stream `what` as the readers deliver it: cf32 for "iq" and "agc", uint32 for the slicer's "hard" and
-    "sync", TSBK_DTYPE for "tsbk", EDACS_DTYPE for "edacs", OSW_DTYPE for "osw", float32 for everything else"""
+    "sync", TSBK_DTYPE for "tsbk", EDACS_DTYPE for "edacs", OSW_DTYPE for "osw", P25LC_DTYPE for "p25lc", float32 for everything else"""
     w = _read_what(what, True)
     if w in _RECORD_DTYPE:
         return _RECORD_DTYPE[w]
@@ -822,7 +851,7 @@ class Frontend:
         copies), None where the channel no longer exists (or lacks the stream).  what: "iq", "fm" (x gain), "agc", or a
         stage's stream -- "sym", "clock", "costas", "fsk4", "audio": float32, from where that stage's single reader stands --
         or the slicer's "hard" (packed words) / "sync" (hit items, see widen_hits): uint32 -- or the TSBK stage's "tsbk":
-        TSBK_DTYPE records -- or the EDACS stage's "edacs": EDACS_DTYPE records -- or the OSW stage's "osw": OSW_DTYPE records"""
+        TSBK_DTYPE records -- or the EDACS stage's "edacs": EDACS_DTYPE records -- or the OSW stage's "osw": OSW_DTYPE records -- or the P25 voice stage's "p25lc": P25LC_DTYPE records"""
         n = len(cids)
         dt = _read_dtype(what)
         if out is None:
@@ -1053,6 +1082,27 @@ class Frontend:
     def chan_osw_ring(self, cid):
         """(device pointer, capacity in records) of the stage's record ring (rcf_chan_osw_ring)"""
         return self._ring_of(lib().rcf_chan_osw_ring, cid)
+
+    def chan_p25lc(self, cid, capacity=0, correct=True, on=True):
+        """P25 voice data units behind the channel's slicer (rcf_chan_p25lc): frames from the sync hits, status symbols
+        stripped, NID read, and for an HDU, an LDU1 or a TLC the inner Golay / Hamming words and the outer Reed-Solomon
+        word decoded on the GPU (correct=False: p25_general's uncorrected reading); records of P25LC_DTYPE in a ring of
+        `capacity` (0: 256).  It considers the hits from now on and excludes the TSBK stage; on=False switches it off."""
+        self._attach(lib().rcf_chan_p25lc, cid, P25lcParams, on, capacity=capacity, correct=int(correct))
+
+    def chan_p25lc_state(self, cid) -> dict:
+        """n_records, n_frames, n_decoded, n_rs_bad, n_lost of the P25 voice stage as of the last block
+        (rcf_chan_p25lc_state; syncs the stream)"""
+        return self._state_of(lib().rcf_chan_p25lc_state, cid, P25lcState)
+
+    def chan_read_p25lc(self, cid, max_records=1 << 12) -> np.ndarray:
+        """unread records of the P25 voice stage, oldest first: a structured array of P25LC_DTYPE (p25lc_fields takes
+        `flags` and `tail` apart, rcf.p25.voice_units gives the fields the reference publishes)"""
+        return self._read_records(lib().rcf_chan_read_p25lc, cid, max_records, P25LC_DTYPE)
+
+    def chan_p25lc_ring(self, cid):
+        """(device pointer, capacity in records) of the stage's record ring (rcf_chan_p25lc_ring)"""
+        return self._ring_of(lib().rcf_chan_p25lc_ring, cid)
 
     def chan_fsk4_ring(self, cid):
         """(device pointer, capacity) of the stage's float32 soft-symbol ring (rcf_chan_fsk4_ring)"""

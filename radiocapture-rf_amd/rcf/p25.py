@@ -29,10 +29,17 @@ FRAME_SYNC_BITS = 48
 FRAME_SYNC_MAX_ERRORS = 4
 
 
-def _hard(fe, cid, source, tsbk=False):
+def _one_decoder(tsbk, lc):
+    if tsbk and lc:
+        raise ValueError("tsbk and lc exclude each other: a slicer carries one frame decoder")
+
+
+def _hard(fe, cid, source, tsbk=False, lc=False):
     fe.chan_slicer(cid, source, native.SLICE_FSK4, SLICER_LEVELS, FRAME_SYNC, FRAME_SYNC_BITS, FRAME_SYNC_MAX_ERRORS)
     if tsbk:
         fe.chan_tsbk(cid)
+    if lc:
+        fe.chan_p25lc(cid)
 
 
 def tsdu_frames(records, reference_rule=False):
@@ -56,6 +63,51 @@ def tsdu_frames(records, reference_rule=False):
                                        next_bit=int(f["next_bit"][i]), n_inexact=int(f["n_inexact"][i])))
         stopped = bool(reference_rule and f["next_bit"][i])
     return frames
+
+
+# the data units by DUID, as p25_general's proc* name them in r['short']
+DUID_SHORT = {0x0: "HDU", 0x3: "TnoLC", 0x5: "LDU1", 0x7: "TSDU", 0xA: "LDU2", 0xC: "PDU", 0xF: "TLC"}
+
+
+def _bits(octets, lo, hi):
+    return (int.from_bytes(octets, "big") >> (8 * len(octets) - hi)) & ((1 << (hi - lo)) - 1)
+
+
+def link_control(octets):
+    """the 9 octets of a link control word as p25_general.subprocLC reads them -> dict(lcf, mfid; for lcf 0x0 lcf_long,
+    emergency, tgid, source_id; for lcf 0x15 lcf_long)"""
+    lc = dict(lcf=_bits(octets, 2, 8), mfid=_bits(octets, 8, 16))
+    if lc["lcf"] == 0x0:
+        lc.update(lcf_long="Group Voice Channel User", emergency=_bits(octets, 16, 17), tgid=_bits(octets, 32, 48),
+                  source_id=_bits(octets, 48, 72))
+    elif lc["lcf"] == 0x15:
+        lc["lcf_long"] = "Call Termination / Cancellation"
+    return lc
+
+
+def voice_units(records):
+    """records of the P25 voice stage (Frontend.chan_read_p25lc, native.P25LC_DTYPE), in the stream's order -> list of dict
+    shaped like the results of p25_general's proc*: short ('HDU' / 'LDU1' / 'TLC' / 'LDU2' / 'TnoLC' / 'TSDU' / 'PDU'; None
+    for a DUID the reference does not know), nac, duid, k, dist, frame_dibits, decoded (False: a frame record -- the unit has
+    no link control, or the frame was too short for it), rs_bad, n_rs, n_fixed, n_bad; for a decoded LDU1 or TLC `lc`
+    (link_control of the 9 octets) and for the LDU1 `lsd` (4 octets); for a decoded HDU mi (9 octets), mfid, algid, kid, tgid"""
+    records = np.asarray(records, dtype=native.P25LC_DTYPE)
+    f = native.p25lc_fields(records)
+    units = []
+    for i in range(len(records)):
+        kind, duid = int(f["kind"][i]), int(f["duid"][i])
+        u = dict(short=DUID_SHORT.get(duid), nac=int(f["nac"][i]), duid=duid, k=int(records["k"][i]), dist=int(f["dist"][i]),
+                 frame_dibits=int(f["frame_dibits"][i]), decoded=kind != 3, rs_bad=int(f["rs_bad"][i]), n_rs=int(f["n_rs"][i]),
+                 n_fixed=int(f["n_fixed"][i]), n_bad=int(f["n_bad"][i]))
+        pay = bytes(records["payload"][i])
+        if kind == 0:
+            u.update(mi=pay[:9], mfid=pay[9], algid=pay[10], kid=_bits(pay, 88, 104), tgid=_bits(pay, 104, 120))
+        elif kind in (1, 2):
+            u["lc"] = link_control(pay[:9])
+            if kind == 1:
+                u["lsd"] = bytes(records["lsd"][i])
+        units.append(u)
+    return units
 
 
 def prefilter_taps(channel_rate):
@@ -98,16 +150,18 @@ def costas_params(channel_rate, symbol_rate=SYMBOL_RATE):
                 beta=0.125 * alpha * alpha, max_freq=2.0 * math.pi * 1200.0 / rate, omega_limit=0.005)
 
 
-def cqpsk_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False, tsbk=False):
+def cqpsk_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False, tsbk=False, lc=False):
     """the whole CQPSK chain up to the slicer on channel `chan_id` of Frontend `fe`: the front half, then the Gardner /
     Costas stage (p25_control_demod.py:136-183).  Returns the pre-filter channel's id: chan_read_costas on it gives soft
     dibits at symbol_rate (slice_dibits turns them into dibits), chan_costas_state its carrier estimate.  hard=True also
     attaches the slicer behind the loop: chan_read_hard gives packed dibits, chan_read_sync where FRAME_SYNC ends; with
-    tsbk=True as well the TSBK stage behind the slicer (chan_read_tsbk, tsdu_frames)."""
+    tsbk=True as well the TSBK stage behind the slicer (chan_read_tsbk, tsdu_frames), or with lc=True the voice-channel
+    stage (chan_read_p25lc, voice_units); the two exclude each other (ValueError)."""
+    _one_decoder(tsbk, lc)
     cid = cqpsk_front_half(fe, chan_id, channel_rate)
     fe.chan_costas(cid, **costas_params(channel_rate, symbol_rate))
     if hard:
-        _hard(fe, cid, native.READ_COSTAS, tsbk)
+        _hard(fe, cid, native.READ_COSTAS, tsbk, lc)
     return cid
 
 
@@ -133,16 +187,18 @@ def fsk4_params(channel_rate, symbol_rate=SYMBOL_RATE):
                 k_coarse=0.00125, spread_min=1.6, spread_max=2.4)
 
 
-def c4fm_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False, tsbk=False):
+def c4fm_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False, tsbk=False, lc=False):
     """the whole C4FM chain up to the slicer on channel `chan_id` of Frontend `fe`: the front half, then the symbol loop
     (p25_control_demod.py:118-135).  Returns the pre-filter channel's id: chan_read_fsk4 on it gives soft dibits at
     symbol_rate (slice_dibits turns them into dibits), chan_fsk4_state its offset estimate (`coarse`).  hard=True also
     attaches the slicer behind the loop: chan_read_hard gives packed dibits, chan_read_sync where FRAME_SYNC ends; with
-    tsbk=True as well the TSBK stage behind the slicer (chan_read_tsbk, tsdu_frames)."""
+    tsbk=True as well the TSBK stage behind the slicer (chan_read_tsbk, tsdu_frames), or with lc=True the voice-channel
+    stage (chan_read_p25lc, voice_units); the two exclude each other (ValueError)."""
+    _one_decoder(tsbk, lc)
     cid = c4fm_front_half(fe, chan_id, channel_rate, symbol_rate)
     fe.chan_fsk4(cid, **fsk4_params(channel_rate, symbol_rate))
     if hard:
-        _hard(fe, cid, native.READ_FSK4, tsbk)
+        _hard(fe, cid, native.READ_FSK4, tsbk, lc)
     return cid
 
 
