@@ -749,9 +749,10 @@ int rcf_chan_osw_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity);
  * more optional stage per channel on the GPU: the voice-channel counterpart of rcf_chan_tsbk.  It reads the slicer's own two
  * streams and writes a third, the counted stream RCF_HARD_P25LC of 32-byte records, one per frame: a consumer of a voice
  * channel takes NAC, DUID and the decoded link control instead of every word of the dibit stream.  All of it is integer
- * work: the records are exactly what the rules below give for the words and hits the slicer's readers deliver.  (No BCH
- * correction of the NID, no decoding of LDU2's encryption sync or of the LSD's (16,8,5) code, no erasures from bad inner
- * words into the Reed-Solomon decoder, no IMBE.)
+ * work: the records are exactly what the rules below give for the words and hits the slicer's readers deliver.  Optional,
+ * through rcf_chan_p25lc_opt: LDU2's encryption sync (RCF_P25LC_ES) and inner words given up as erasures of the Reed-Solomon
+ * decoder (RCF_P25LC_ERASURES); without an option every record is what the rules give without the paragraphs "LDU2" and
+ * "Erasures".  (No BCH correction of the NID, no decoding of the LSD's (16,8,5) code, no IMBE.)
  * Frames.  Hits, the widening of k, the accept rule (k >= k_last_accepted + 24), the start at hit index >= the slicer's
  * n_hits at the call, the lost rule and "info dibit j sits at frame dibit r = j + j / 35" are rcf_chan_tsbk's.  The frame
  * starts at dibit s = k - 23; frame_dibits = min(864, s_next - s), s_next the frame start of the next accepted hit if there
@@ -785,14 +786,29 @@ int rcf_chan_osw_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity);
  * in the order of rs64.py's msg (data first, parity behind: symbol i is the coefficient of x^(n - 1 - i)), t = (d - 1) / 2.
  * The result is the code word of the shortened code within t symbols of the inner-decoded word if there is one -- it is
  * unique --, n_rs the number of symbols it changes; otherwise rs_bad is set, n_rs is 0 and the payload is the inner-decoded
- * data symbols as they stand.  No erasures.
+ * data symbols as they stand.  No erasures without RCF_P25LC_ERASURES.
+ * LDU2 (RCF_P25LC_ES).  Duid 0xA with frame_dibits > 788 is a unit of kind 4: 24 words of 10 bits at the LDU1's positions,
+ * inner code Hamming (10,6,3) as above, outer code RS(24,16,9), t = 4, in the field, root order and symbol order of the other
+ * two; payload the hexbits 0 .. 15 = 12 octets (MI 72, ALGID 8, KID 16); the 32 raw LSD bits where the LDU1 has them.  It
+ * counts in n_decoded and n_rs_bad.  correct = 0: the first 6 bits of every word, then the first 96 of those --
+ * rs_24_16_9_decode(hamming_10_6_3_decode(lc)) of p25_general over procLDU1's slices (its procLDU2 is empty).
+ * Erasures (RCF_P25LC_ERASURES, correct = 1; all four units).  The erased set E is the symbols of the inner words that count
+ * as BAD: one symbol per Hamming or (18,6) word, both symbols of a (24,12) word.  So that a (24,12) word can be BAD, its 24th
+ * bit takes part under this option only: if the nearest (23,12) code word is 3 bits away and the received 24th bit is not the
+ * overall parity of that code word (golay.py's encode appends it), four errors are detected, the word counts as BAD and its
+ * data are taken as read.  The result is the code word of the shortened code that agrees with the inner-decoded word outside E
+ * in all but v symbols with 2 v + |E| <= d - 1 if there is one -- it is unique --, n_rs the number of symbols it changes,
+ * erased ones included (up to 16); otherwise, or if |E| > d - 1, rs_bad is set, n_rs is 0 and the data stand.  |E| is n_bad,
+ * 2 n_bad for a TLC.  rs64.py's decode with its `erasures` list answers None on many patterns inside this bound and is right
+ * wherever it answers; this decoder is complete.
  * Records, 8 uint32 each, in increasing k:
- *     word 0    bits 0-1 kind (0 HDU, 1 LDU1, 2 TLC, 3 a frame record), bit 2 rs_bad, bit 3 zero, bits 4-7 n_rs, bits 8-9
+ *     word 0    bits 0-1 and bit 3 kind (0 HDU, 1 LDU1, 2 TLC, 3 a frame record; bit 3: 4 LDU2, with RCF_P25LC_ES only),
+ *               bit 2 rs_bad, bits 4-7 n_rs's low four bits and bit 8 its fifth (set with RCF_P25LC_ERASURES only), bit 9
  *               zero, bits 10-15 the hit's distance, bits 16-19 duid, bits 20-31 nac (the last three where TSBK has them)
  *     word 1    the low 32 bits of the widened k
  *     word 2-5  the payload's octets, the first bit highest, bytes in memory order (the word ring's rule), zero padded; 0
  *               in a frame record
- *     word 6    the 32 raw LSD bits, same rule (LDU1), else 0
+ *     word 6    the 32 raw LSD bits, same rule (LDU1, LDU2), else 0
  *     word 7    bits 0-15 frame_dibits, bits 16-21 inner words fixed, bits 22-27 inner words bad, bits 28-31 zero
  * p == NULL switches the stage off.  It applies from the next block on and considers only hits appended after the call;
  * calling again starts it afresh.  It goes when the slicer goes: slicer attached again or switched off, its source loop
@@ -800,13 +816,18 @@ int rcf_chan_osw_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity);
  * calls is refused while the other stage is attached.
  * RCF_ESTATE: the channel has no slicer in RCF_SLICE_FSK4 mode that searches a 48-bit sync word, that slicer searches both
  * polarities (sync_both = 1), or it carries the TSBK stage; RCF_EINVAL: capacity not 0 or a power of two >= 16 (at most
- * 2^20), correct not 0 or 1; RCF_ENOCHAN: no such channel. */
+ * 2^20), correct not 0 or 1, an unknown option bit, RCF_P25LC_ERASURES with correct = 0; RCF_ENOCHAN: no such channel.
+ * rcf_chan_p25lc(h, c, p) is rcf_chan_p25lc_opt(h, c, p, 0): one attach path, and calling either again starts the stage
+ * afresh with the options of that call. */
 typedef struct rcf_p25lc_params {
     int capacity;          /* records of the ring, a power of two >= 16; 0 = 256 */
     int correct;           /* 0: the reference's p25_general reading (systematic bits, nothing corrected); 1: the decoders above */
     int reserved_[2];
 } rcf_p25lc_params_t;
 int rcf_chan_p25lc(rcf_t *h, int chan_id, const rcf_p25lc_params_t *p);
+#define RCF_P25LC_ES        1u   /* decode LDU2's encryption sync */
+#define RCF_P25LC_ERASURES  2u   /* inner words given up become Reed-Solomon erasures (needs correct = 1) */
+int rcf_chan_p25lc_opt(rcf_t *h, int chan_id, const rcf_p25lc_params_t *p, uint32_t options);
 /* the stage's counters as of the last block; syncs the stream.  RCF_ESTATE without the stage (here and in the calls below) */
 typedef struct rcf_p25lc_state {
     int64_t n_records, n_frames, n_decoded, n_rs_bad, n_lost;   /* records written, frames accepted (decided or lost), units decoded (HDU, LDU1, TLC), of them with rs_bad, hits and frames lost */

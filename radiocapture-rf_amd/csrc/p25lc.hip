@@ -18,7 +18,9 @@
 //                   many members as the locator's degree (a root outside the n positions is missing there)
 //   Forney          lane m forms coefficient m of S(x) Lambda(x), the error lanes evaluate it and the derivative
 //   re-check        the syndromes of the corrected word, again one per lane
-// instead of lane 0 walking dependent chains over 36 symbols with 63 lanes idle.  The lanes 0 .. 3 cut the payload words out
+// instead of lane 0 walking dependent chains over 36 symbols with 63 lanes idle.  The options of rcf_chan_p25lc_opt: an LDU2 is
+// a fourth unit on the LDU1's lanes with RS(24,16,9); with erasures the ballot of the BAD lanes is the erased set and rs_decode
+// runs as rs_decode<true>, chosen by a wave-uniform branch on the flag, so a stage without the option walks the loops of t.  The lanes 0 .. 3 cut the payload words out
 // of the data symbols, the lanes 0 .. 7 store a record's eight words.
 // All trip counts come from the host's n_k or are compile-time constants; the counters read from the device only clamp.
 // Every ring index is masked.  Plain vector stores only; nothing is shared between waves; no LDS.  Every cross-lane read
@@ -54,34 +56,52 @@ __device__ __forceinline__ uint32_t rs_syndrome(uint32_t sym, int n, int t, int 
     return lane < 2 * t ? S : 0u;
 }
 // the symbols of RS(n, n - 2 t) (lane i: symbol i; the lanes >= n hold 0) -> the corrected symbols, or the symbols as they
-// are with *rs_bad; *n_rs: the symbols changed
-__device__ __forceinline__ uint32_t rs_decode(uint32_t sym, int n, int t, int lane, bool *rs_bad, int *n_rs)
+// are with *rs_bad; *n_rs: the symbols changed.  kErasures: E, the ballot of the erased symbols, enters -- the locator starts
+// as the erasure locator prod (1 + X_j x) over E (coefficient i in lane i, a member of E per uniform round), Berlekamp-Massey
+// from round |E| on, and Chien, Forney and the products run to degree d - 1 and no longer t: the joint locator of |E|
+// erasures and v errors with 2 v + |E| <= d - 1.  Without it E is 0 and every bound the errors-only decoder's
+template <bool kErasures>
+__device__ __forceinline__ uint32_t rs_decode(uint32_t sym, uint64_t E, int n, int t, int lane, bool *rs_bad, int *n_rs)
 {
+    constexpr int kDeg = kErasures ? kP25lcMaxD1 : kP25lcMaxT;       // the locator's highest degree
+    const int ne = kErasures ? __popcll(E) : 0;
     const uint32_t S = rs_syndrome(sym, n, t, lane);
-    uint32_t C = lane == 0 ? 1u : 0u, B = C, b = 1;
-    int Ln = 0, m = 1;
+    uint32_t C = lane == 0 ? 1u : 0u;
+    if (kErasures) {
+        uint64_t rest = ne <= 2 * t ? E : 0ull;      // (more than d - 1: given up below)
+        for (int r = 0; r < kP25lcMaxD1; ++r) {
+            const uint32_t up = lane_read(C, lane - 1);
+            if (!rest) continue;                     // (uniform)
+            C ^= p25lc_gf_mul(p25lc_rs_x(n, __builtin_ctzll(rest)), lane ? up : 0u);
+            rest &= rest - 1;
+        }
+    }
+    uint32_t B = C, b = 1;
+    int Ln = ne, m = 1;
     for (int r = 0; r < 2 * kP25lcMaxT; ++r) {
         const uint32_t Sr = lane_read(S, r - lane);
         const uint32_t d = wave_xor(lane <= r ? p25lc_gf_mul(C, Sr) : 0u);
         const uint32_t Bs = lane_read(B, lane - m);
-        if (r >= 2 * t) continue;                    // (uniform)
+        if (r < ne || r >= 2 * t) continue;          // (uniform)
         if (d == 0) { ++m; continue; }
         const uint32_t Cn = C ^ p25lc_gf_mul(p25lc_gf_mul(d, p25lc_gf_inv(b)), lane >= m ? Bs : 0u);
-        if (2 * Ln <= r) { B = C; Ln = r + 1 - Ln; b = d; m = 1; } else ++m;
+        if (2 * Ln <= r + ne) { B = C; Ln = r + 1 - Ln + ne; b = d; m = 1; } else ++m;
         C = Cn;
     }
     const uint32_t xi = lane < n ? p25lc_rs_xinv(n, lane) : 0u, xi2 = p25lc_gf_mul(xi, xi);
     uint32_t v = 0, om = 0;
-    for (int j = kP25lcMaxT; j >= 0; --j) v = p25lc_gf_mul(v, xi) ^ lane_read(C, j);
+    for (int j = kDeg; j >= 0; --j) v = p25lc_gf_mul(v, xi) ^ lane_read(C, j);
     const bool root = lane < n && v == 0;
-    const bool ok = Ln <= t && __popcll(__ballot(root)) == Ln;
-    for (int i = 0; i <= kP25lcMaxT; ++i) {          // coefficient `lane` of S(x) Lambda(x)
+    const uint64_t roots = __ballot(root);
+    const bool ok = 2 * Ln - ne <= 2 * t && __popcll(roots) == Ln && (roots & E) == E;
+    for (int i = 0; i <= kDeg; ++i) {                // coefficient `lane` of S(x) Lambda(x)
         const uint32_t ci = lane_read(C, i), si = lane_read(S, lane - i);
         if (i <= lane) om ^= p25lc_gf_mul(ci, si);
     }
+    if (kErasures && lane >= 2 * t) om = 0;          // ... modulo x^(2 t): its degree is below the locator's, which t no longer bounds
     uint32_t num = 0, den = 0;
-    for (int j = kP25lcMaxT - 1; j >= 0; --j) num = p25lc_gf_mul(num, xi) ^ lane_read(om, j);
-    for (int j = kP25lcMaxT - 1; j >= 1; j -= 2) den = p25lc_gf_mul(den, xi2) ^ lane_read(C, j);
+    for (int j = kDeg - 1; j >= 0; --j) num = p25lc_gf_mul(num, xi) ^ lane_read(om, j);
+    for (int j = kDeg - 1; j >= 1; j -= 2) den = p25lc_gf_mul(den, xi2) ^ lane_read(C, j);
     const uint32_t e = root && den ? p25lc_gf_mul(num, p25lc_gf_inv(den)) : 0u;
     const uint32_t fixed = sym ^ e;
     const bool left = __ballot(rs_syndrome(fixed, n, t, lane) != 0) != 0;
@@ -97,7 +117,7 @@ __global__ __launch_bounds__(64 * kP25lcWaves) void p25lc_kernel(const P25lcLaun
     if (w >= n_items) return;                        // (no workgroup barrier below: a wave leaves on its own)
     const P25lcLaunch L = items[w];
     P25lcState *st = L.st;
-    const bool correct = L.flags & kP25lcFlagCorrect;
+    const bool correct = L.flags & kP25lcFlagCorrect, erasures = L.flags & kP25lcFlagErasures;
     const int64_t n_sym = L.src->n_symbols, n_words = L.src->n_words, n_hits = L.src->n_hits;
     int64_t n_records = st->n_records, n_frames = st->n_frames, n_decoded = st->n_decoded, n_rs_bad = st->n_rs_bad, n_lost = st->n_lost;
     int64_t i = st->next_hit, k_last = st->k_last;
@@ -132,7 +152,7 @@ __global__ __launch_bounds__(64 * kP25lcWaves) void p25lc_kernel(const P25lcLaun
         const int dn = lane < 32 ? dibit(tsbk_frame_pos(24 + lane)) : 0;
         const uint64_t nhi = __ballot(dn & 2), nlo = __ballot(dn & 1);
         const uint32_t nid0 = slice_word_be(nhi, nlo, 2, 0);
-        const int kind = __builtin_amdgcn_readfirstlane(p25lc_kind(tsbk_duid(nid0), fd));
+        const int kind = __builtin_amdgcn_readfirstlane(p25lc_kind(tsbk_duid(nid0), fd, L.flags));
         uint32_t *rec = L.rec_ring + ((uint64_t)n_records & L.rec_mask) * kP25lcRecWords;
         ++n_records;
         if (kind == kP25lcFrame) {
@@ -141,19 +161,23 @@ __global__ __launch_bounds__(64 * kP25lcWaves) void p25lc_kernel(const P25lcLaun
             continue;
         }
         // ---- inner word `lane`
-        const bool mine = lane < p25lc_inner_words(kind);
-        const uint32_t word = mine ? p25lc_gather(dibit, kind, lane) : 0u;
+        const int wk = p25lc_words_kind(kind);       // (an LDU2's words are an LDU1's)
+        const bool mine = lane < p25lc_inner_words(wk);
+        const uint32_t word = mine ? p25lc_gather(dibit, wk, lane) : 0u;
         int status = 0;
-        uint32_t data = mine ? (correct ? p25lc_inner(kind, word, &status) : p25lc_systematic(kind, word)) : 0u;
-        const int n_fixed = __popcll(__ballot(mine && status == 1)), n_bad = __popcll(__ballot(mine && status == 2));
-        const int n = p25lc_rs_n(kind), kk = p25lc_rs_k(kind);
+        uint32_t data = mine ? (correct ? p25lc_inner(kind, word, &status, erasures) : p25lc_systematic(wk, word)) : 0u;
+        uint64_t bad = __ballot(mine && status == 2);
+        const int n_fixed = __popcll(__ballot(mine && status == 1)), n_bad = __popcll(bad);
+        const int n = p25lc_rs_n(wk), kk = p25lc_rs_k_es(kind);
         if (kind == kP25lcTlc) {                     // a Golay word is two symbols
             const uint32_t two = lane_read(data, lane >> 1);
             data = lane < n ? (lane & 1 ? two & 63u : two >> 6) : 0u;
+            bad = __ballot(lane < n && (bad >> (lane >> 1) & 1));
         }
         bool rs_bad = false;
         int n_rs = 0;
-        if (correct) data = rs_decode(data, n, p25lc_rs_t(kind), lane, &rs_bad, &n_rs);      // (uniform)
+        if (correct && erasures) data = rs_decode<true>(data, bad, n, p25lc_rs_t_es(kind), lane, &rs_bad, &n_rs);          // (uniform, both)
+        else if (correct) data = rs_decode<false>(data, 0, n, p25lc_rs_t_es(kind), lane, &rs_bad, &n_rs);
         // ---- the payload: the data symbols' bits, the lanes 0 .. 3 a word each
         uint64_t pay = 0;
         for (int j = 0; j < 7; ++j) {
@@ -162,9 +186,9 @@ __global__ __launch_bounds__(64 * kP25lcWaves) void p25lc_kernel(const P25lcLaun
             pay = pay << 6 | (at < kk ? v : 0u);
         }
         const uint32_t pw = lane_read(slice_word_mem(p25lc_pay_word(pay, lane & 3)), lane - 2);
-        const int dl = kind == kP25lcLdu1 && lane < 16 ? dibit(tsbk_frame_pos(kP25lcLsdDibit + lane)) : 0;
+        const int dl = p25lc_has_lsd(kind) && lane < 16 ? dibit(tsbk_frame_pos(kP25lcLsdDibit + lane)) : 0;
         const uint64_t lhi = __ballot(dl & 2), llo = __ballot(dl & 1);
-        const uint32_t v = lane == 0 ? p25lc_word0(kind, rs_bad, n_rs, dist, nid0) : lane == 1 ? (uint32_t)(uint64_t)k0 : lane < 6 ? pw :
+        const uint32_t v = lane == 0 ? p25lc_word0_wide(kind, rs_bad, n_rs, dist, nid0) : lane == 1 ? (uint32_t)(uint64_t)k0 : lane < 6 ? pw :
                            lane == 6 ? slice_word_mem(slice_word_be(lhi, llo, 2, 0)) : p25lc_word7(fd, n_fixed, n_bad);
         if (lane < kP25lcRecWords) rec[lane] = v;
         ++n_decoded;

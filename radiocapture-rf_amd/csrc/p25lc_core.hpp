@@ -3,7 +3,7 @@
 // word, GF(64) with the pieces of the Reed-Solomon decoder that one lane computes, and the packing of a record.  Frames,
 // hits and the status-symbol map are tsbk_core.hpp's, used as they stand.  No HIP types in here, like tsbk_core.hpp:
 // RCF_DEVFN is the function qualifier and RCF_DEVCONST the qualifier of the tables, so that the CPU suite compiles this very
-// source with g++ (tests/native/p25lc_core_check.cpp).
+// source with g++ (tests/native/p25lc_core_check.cpp; tests/native/p25es_core_check.cpp for the options at the file's end).
 //
 // Golay: a 2048-entry table from the 11-bit syndrome to the error pattern of weight <= 3, built at compile time.  The code is
 // perfect, so the table IS the complete decoder -- one syndrome (twelve shift / xor rounds) and one load per word -- where an
@@ -148,6 +148,38 @@ RCF_DEVFN uint32_t p25lc_word7(int fd, int n_fixed, int n_bad) { return (uint32_
 // from the seven symbols first .. first + 6 (acc: those, symbols >= k as 0)
 RCF_DEVFN int p25lc_pay_first(int q) { return (32 * q) / 6; }
 RCF_DEVFN uint32_t p25lc_pay_word(uint64_t acc, int q) { return (uint32_t)(acc >> (10 - (32 * q - 6 * p25lc_pay_first(q)))); }
+
+// ---- the options of rcf_chan_p25lc_opt (include/rcf.h): LDU2's encryption sync, and inner words given up as erasures.
+// Everything above stands as it is; what an option changes is a function of its own down here.
+constexpr uint32_t kP25lcFlagEs = 2u, kP25lcFlagErasures = 4u;                  // P25lcLaunch::flags: the call's options << 1
+constexpr int kP25lcLdu2 = 4;                                                   // a record's kind: bit 2 of it is word 0 bit 3
+constexpr int kP25lcMaxD1 = 2 * kP25lcMaxT;                                     // d - 1 of RS(36,20,17): the most erasures, the joint locator's highest degree
+RCF_DEVFN int p25lc_kind(int duid, int fd, uint32_t flags) { return (flags & kP25lcFlagEs) && duid == 0xA && fd > 788 ? kP25lcLdu2 : p25lc_kind(duid, fd); }
+// an LDU2's 24 Hamming words sit where the LDU1's do: the kind to gather and to decode inner words by
+RCF_DEVFN int p25lc_words_kind(int kind) { return kind == kP25lcLdu2 ? kP25lcLdu1 : kind; }
+RCF_DEVFN int p25lc_rs_k_es(int kind) { return kind == kP25lcLdu2 ? 16 : p25lc_rs_k(kind); }      // RS(24,16,9)
+RCF_DEVFN int p25lc_rs_t_es(int kind) { return kind == kP25lcLdu2 ? 4 : p25lc_rs_t(kind); }
+RCF_DEVFN bool p25lc_has_lsd(int kind) { return kind == kP25lcLdu1 || kind == kP25lcLdu2; }
+// extended (24,12,8) with the 24th bit taking part: three bits changed and the received overall parity is not the corrected
+// word's -> four errors detected: BAD, data as read.  Otherwise p25lc_golay24's answer
+RCF_DEVFN uint32_t p25lc_golay24_detect(uint32_t w, int *status)
+{
+    const uint32_t r = (w >> 1) & 0x7fffffu, c = p25lc_golay23(r);
+    if (slice_popcount64(c ^ r) == 3 && p25lc_parity(c) != (w & 1u)) { *status = 2; return (w >> 12) & 0xfffu; }
+    *status = c != r ? 1 : 0;
+    return c >> 11;
+}
+RCF_DEVFN uint32_t p25lc_inner(int kind, uint32_t w, int *status, bool erasures)
+{
+    return erasures && kind == kP25lcTlc ? p25lc_golay24_detect(w, status) : p25lc_inner(p25lc_words_kind(kind), w, status);
+}
+// X of symbol i, the factor (1 + X x) it contributes to the erasure locator
+RCF_DEVFN uint32_t p25lc_rs_x(int n, int i) { return p25lc_gf_alpha(n - 1 - i); }
+// word 0 with the kind's third bit in bit 3 and n_rs's fifth in bit 8: p25lc_word0's value for kind < 4 and n_rs < 16
+RCF_DEVFN uint32_t p25lc_word0_wide(int kind, bool rs_bad, int n_rs, uint32_t dist, uint32_t nid0)
+{
+    return p25lc_word0(kind, rs_bad, n_rs, dist, nid0) | ((uint32_t)(kind & 4) << 1) | ((uint32_t)(n_rs & 16) << 4);
+}
 
 }  // namespace
 

@@ -410,7 +410,7 @@ struct P25lcState {
     int64_t k_last;          // the last accepted hit's k
 };
 struct P25lcLaunch : FramesLaunch<P25lcState> {
-    uint32_t flags;          // bit 0: the stage's `correct`
+    uint32_t flags;          // bit 0: the stage's `correct`; from bit 1 on the options of rcf_chan_p25lc_opt (kP25lcFlagEs, kP25lcFlagErasures)
 };
 void launch_p25lc(const P25lcLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
 // the records' layouts as the kernels were compiled for them

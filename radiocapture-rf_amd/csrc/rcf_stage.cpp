@@ -16,6 +16,7 @@
 #include "edacs_core.hpp"      // (kEdacsNoFrame, kEdacsRecWords; slice_sync_both_ok of slice_core.hpp)
 #include "osw_core.hpp"        // (kOswSyncBits, kOswRecWords)
 #include "p25lc_core.hpp"      // (kP25lcRecWords, kP25lcFlagCorrect)
+static_assert(rcfx::kP25lcFlagEs == RCF_P25LC_ES << 1 && rcfx::kP25lcFlagErasures == RCF_P25LC_ERASURES << 1, "the options travel in P25lcLaunch::flags behind kP25lcFlagCorrect");
 
 namespace rcfx {
 
@@ -495,14 +496,18 @@ int rcf_chan_osw_state(rcf_t *h, int chan_id, rcf_osw_state_t *out)
     return RCF_OK;
 }
 
-int rcf_chan_p25lc(rcf_t *h, int chan_id, const rcf_p25lc_params_t *p)
+int rcf_chan_p25lc(rcf_t *h, int chan_id, const rcf_p25lc_params_t *p) { return rcf_chan_p25lc_opt(h, chan_id, p, 0u); }
+
+int rcf_chan_p25lc_opt(rcf_t *h, int chan_id, const rcf_p25lc_params_t *p, uint32_t options)
 {
     if (p && p->correct != 0 && p->correct != 1) { set_error("P25 voice stage: correct %d is not 0 or 1", p->correct); return RCF_EINVAL; }
+    if (p && (options & ~(RCF_P25LC_ES | RCF_P25LC_ERASURES))) { set_error("P25 voice stage: unknown option bits 0x%x", options); return RCF_EINVAL; }
+    if (p && (options & RCF_P25LC_ERASURES) && !p->correct) { set_error("P25 voice stage: RCF_P25LC_ERASURES needs correct = 1"); return RCF_EINVAL; }
     return attach_frames<Chan::Slicer::P25lc>(h, chan_id, p,
         [](const Chan::Slicer &l) { return l.rec.bps == 2 && l.rec.sync_bits == 48 && !l.rec.sync_both && !l.tsbk; },
         "channel %d has no slicer in RCF_SLICE_FSK4 mode that searches a 48-bit sync word in one polarity, or that slicer carries the TSBK stage",
-        [p](P25lcLaunch &r, P25lcState &st0, const SliceLaunch &, const SliceState &) {
-            r.flags = p->correct ? kP25lcFlagCorrect : 0u;
+        [p, options](P25lcLaunch &r, P25lcState &st0, const SliceLaunch &, const SliceState &) {
+            r.flags = (p->correct ? kP25lcFlagCorrect : 0u) | options << 1;
             st0.k_last = kTsbkNoFrame;
         });
 }

@@ -41,7 +41,7 @@ SYMBOLS = [
     "rcf_chan_tsbk", "rcf_chan_tsbk_state", "rcf_chan_read_tsbk", "rcf_chan_tsbk_ring",
     "rcf_chan_edacs", "rcf_chan_edacs_state", "rcf_chan_read_edacs", "rcf_chan_edacs_ring",
     "rcf_chan_osw", "rcf_chan_osw_state", "rcf_chan_read_osw", "rcf_chan_osw_ring",
-    "rcf_chan_p25lc", "rcf_chan_p25lc_state", "rcf_chan_read_p25lc", "rcf_chan_p25lc_ring",
+    "rcf_chan_p25lc", "rcf_chan_p25lc_opt", "rcf_chan_p25lc_state", "rcf_chan_read_p25lc", "rcf_chan_p25lc_ring",
     "rcf_design_firdes", "rcf_design_optfir_low_pass", "rcf_design_fm_deemph", "rcf_design_resampler", "rcf_chan_audio_open",
     "rcf_chan_audio_close", "rcf_chan_audio_produced", "rcf_chan_read_audio",
     "rcf_host_alloc", "rcf_host_free", "rcf_comm_unique_id", "rcf_comm_init", "rcf_comm_destroy", "rcf_comm_size",
@@ -65,6 +65,7 @@ HARD_EDACS = 49
 HARD_OSW = 51
 # ... and of the P25 voice stage (RCF_HARD_P25LC): records of 8 uint32, one per frame
 HARD_P25LC = 53
+P25LC_ES, P25LC_ERASURES = 1, 2   # rcf_chan_p25lc_opt's options (RCF_P25LC_*)
 _HARD_WHAT = {"hard": HARD_BITS, "sync": HARD_SYNC, "tsbk": HARD_TSBK, "edacs": HARD_EDACS, "osw": HARD_OSW, "p25lc": HARD_P25LC}
 # a record of RCF_HARD_TSBK (rcf.h at rcf_chan_tsbk): word 0 (see tsbk_fields), the low 32 bits of k, the 12 decoded octets,
 # the NID's 8 octets, frame_dibits
@@ -77,7 +78,7 @@ EDACS_DTYPE = np.dtype([("flags", "<u4"), ("k", "<u4"), ("m1", "u1", (8,)), ("m2
 OSW_DTYPE = np.dtype([("flags", "<u4"), ("k", "<u4"), ("lid", "<u2"), ("cmd", "<u2"), ("data", "u1", (8,)), ("psyn", "u1", (8,)),
                       ("locked", "<i4")])
 # a record of RCF_HARD_P25LC (rcf.h at rcf_chan_p25lc): word 0 (see p25lc_fields), the low 32 bits of k, the payload's octets
-# (15 of an HDU, 9 of an LDU1 or a TLC, zero padded), the LDU1's four LSD octets, frame_dibits and the inner words' counts
+# (15 of an HDU, 9 of an LDU1 or a TLC, 12 of an LDU2, zero padded), the LDU's four LSD octets, frame_dibits and the inner words' counts
 P25LC_DTYPE = np.dtype([("flags", "<u4"), ("k", "<u4"), ("payload", "u1", (16,)), ("lsd", "u1", (4,)), ("tail", "<u4")])
 SLICE_BINARY, SLICE_FSK4 = 1, 2
 T_FIR, T_PFB, T_FIR_DERIVED, T_DISC, T_SCAN_FFT, T_SCAN_MOVSUM, T_HISTORY, T_FIR_MFMA, T_AUDIO, T_TAPS, T_CLOCK, T_COSTAS, T_FSK4, T_SLICE = range(14)
@@ -246,11 +247,13 @@ class P25lcState(C.Structure):
 
 
 def p25lc_fields(records):
-    """words 0 and 7 of P25 voice records taken apart -> dict of arrays: kind (0 HDU, 1 LDU1, 2 TLC, 3: a frame record),
-    rs_bad, n_rs, dist, duid, nac, frame_dibits, n_fixed, n_bad (inner words corrected / given up)"""
+    """words 0 and 7 of P25 voice records taken apart -> dict of arrays: kind (0 HDU, 1 LDU1, 2 TLC, 3: a frame record, 4 LDU2:
+    its third bit is word 0 bit 3), rs_bad, n_rs (five bits, the fifth is word 0 bit 8), dist, duid, nac, frame_dibits, n_fixed,
+    n_bad (inner words corrected / given up)"""
     f = np.asarray(records["flags"], dtype=np.uint32)
     t = np.asarray(records["tail"], dtype=np.uint32)
-    return dict(kind=(f & 3).astype(np.uint8), rs_bad=((f >> 2) & 1).astype(np.uint8), n_rs=((f >> 4) & 15).astype(np.uint8),
+    return dict(kind=((f & 3) | ((f >> 1) & 4)).astype(np.uint8), rs_bad=((f >> 2) & 1).astype(np.uint8),
+                n_rs=(((f >> 4) & 15) | ((f >> 4) & 16)).astype(np.uint8),
                 dist=((f >> 10) & 63).astype(np.uint8), duid=((f >> 16) & 15).astype(np.uint8), nac=(f >> 20).astype(np.uint16),
                 frame_dibits=(t & 0xffff).astype(np.uint16), n_fixed=((t >> 16) & 63).astype(np.uint8),
                 n_bad=((t >> 22) & 63).astype(np.uint8))
@@ -438,6 +441,7 @@ def lib():
         sig["rcf_chan_%s_state" % name] = (C.c_int, [vp, C.c_int, C.POINTER(state)])
         sig["rcf_chan_read_" + name] = (i64, [vp, C.c_int, C.POINTER(C.c_uint32), sz])
         sig["rcf_chan_%s_ring" % name] = (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)])
+    sig["rcf_chan_p25lc_opt"] = (C.c_int, [vp, C.c_int, C.POINTER(P25lcParams), C.c_uint32])
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
         fn.restype = res
@@ -1083,12 +1087,15 @@ class Frontend:
         """(device pointer, capacity in records) of the stage's record ring (rcf_chan_osw_ring)"""
         return self._ring_of(lib().rcf_chan_osw_ring, cid)
 
-    def chan_p25lc(self, cid, capacity=0, correct=True, on=True):
-        """P25 voice data units behind the channel's slicer (rcf_chan_p25lc): frames from the sync hits, status symbols
+    def chan_p25lc(self, cid, capacity=0, correct=True, on=True, es=False, erasures=False):
+        """P25 voice data units behind the channel's slicer (rcf_chan_p25lc_opt): frames from the sync hits, status symbols
         stripped, NID read, and for an HDU, an LDU1 or a TLC the inner Golay / Hamming words and the outer Reed-Solomon
         word decoded on the GPU (correct=False: p25_general's uncorrected reading); records of P25LC_DTYPE in a ring of
-        `capacity` (0: 256).  It considers the hits from now on and excludes the TSBK stage; on=False switches it off."""
-        self._attach(lib().rcf_chan_p25lc, cid, P25lcParams, on, capacity=capacity, correct=int(correct))
+        `capacity` (0: 256).  es=True decodes LDU2's encryption sync as well (kind 4); erasures=True (needs correct) hands
+        the inner words given up to the Reed-Solomon decoder as erasures.  It considers the hits from now on and excludes
+        the TSBK stage; on=False switches it off."""
+        options = (P25LC_ES if es else 0) | (P25LC_ERASURES if erasures else 0)
+        self._attach(lambda h, c, p: lib().rcf_chan_p25lc_opt(h, c, p, options), cid, P25lcParams, on, capacity=capacity, correct=int(correct))
 
     def chan_p25lc_state(self, cid) -> dict:
         """n_records, n_frames, n_decoded, n_rs_bad, n_lost of the P25 voice stage as of the last block

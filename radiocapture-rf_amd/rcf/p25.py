@@ -34,12 +34,12 @@ def _one_decoder(tsbk, lc):
         raise ValueError("tsbk and lc exclude each other: a slicer carries one frame decoder")
 
 
-def _hard(fe, cid, source, tsbk=False, lc=False):
+def _hard(fe, cid, source, tsbk=False, lc=False, es=False, erasures=False):
     fe.chan_slicer(cid, source, native.SLICE_FSK4, SLICER_LEVELS, FRAME_SYNC, FRAME_SYNC_BITS, FRAME_SYNC_MAX_ERRORS)
     if tsbk:
         fe.chan_tsbk(cid)
     if lc:
-        fe.chan_p25lc(cid)
+        fe.chan_p25lc(cid, es=es, erasures=erasures)
 
 
 def tsdu_frames(records, reference_rule=False):
@@ -90,7 +90,8 @@ def voice_units(records):
     shaped like the results of p25_general's proc*: short ('HDU' / 'LDU1' / 'TLC' / 'LDU2' / 'TnoLC' / 'TSDU' / 'PDU'; None
     for a DUID the reference does not know), nac, duid, k, dist, frame_dibits, decoded (False: a frame record -- the unit has
     no link control, or the frame was too short for it), rs_bad, n_rs, n_fixed, n_bad; for a decoded LDU1 or TLC `lc`
-    (link_control of the 9 octets) and for the LDU1 `lsd` (4 octets); for a decoded HDU mi (9 octets), mfid, algid, kid, tgid"""
+    (link_control of the 9 octets) and for the LDU1 `lsd` (4 octets); for a decoded HDU mi (9 octets), mfid, algid, kid, tgid;
+    for a decoded LDU2 (a stage attached with es=True) its encryption sync mi (9 octets), algid, kid, and `lsd`"""
     records = np.asarray(records, dtype=native.P25LC_DTYPE)
     f = native.p25lc_fields(records)
     units = []
@@ -106,6 +107,8 @@ def voice_units(records):
             u["lc"] = link_control(pay[:9])
             if kind == 1:
                 u["lsd"] = bytes(records["lsd"][i])
+        elif kind == 4:
+            u.update(mi=pay[:9], algid=pay[9], kid=_bits(pay, 80, 96), lsd=bytes(records["lsd"][i]))
         units.append(u)
     return units
 
@@ -150,18 +153,18 @@ def costas_params(channel_rate, symbol_rate=SYMBOL_RATE):
                 beta=0.125 * alpha * alpha, max_freq=2.0 * math.pi * 1200.0 / rate, omega_limit=0.005)
 
 
-def cqpsk_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False, tsbk=False, lc=False):
+def cqpsk_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False, tsbk=False, lc=False, es=False, erasures=False):
     """the whole CQPSK chain up to the slicer on channel `chan_id` of Frontend `fe`: the front half, then the Gardner /
     Costas stage (p25_control_demod.py:136-183).  Returns the pre-filter channel's id: chan_read_costas on it gives soft
     dibits at symbol_rate (slice_dibits turns them into dibits), chan_costas_state its carrier estimate.  hard=True also
     attaches the slicer behind the loop: chan_read_hard gives packed dibits, chan_read_sync where FRAME_SYNC ends; with
     tsbk=True as well the TSBK stage behind the slicer (chan_read_tsbk, tsdu_frames), or with lc=True the voice-channel
-    stage (chan_read_p25lc, voice_units); the two exclude each other (ValueError)."""
+    stage (chan_read_p25lc, voice_units; es / erasures: its options, Frontend.chan_p25lc); the two exclude each other (ValueError)."""
     _one_decoder(tsbk, lc)
     cid = cqpsk_front_half(fe, chan_id, channel_rate)
     fe.chan_costas(cid, **costas_params(channel_rate, symbol_rate))
     if hard:
-        _hard(fe, cid, native.READ_COSTAS, tsbk, lc)
+        _hard(fe, cid, native.READ_COSTAS, tsbk, lc, es, erasures)
     return cid
 
 
@@ -187,18 +190,18 @@ def fsk4_params(channel_rate, symbol_rate=SYMBOL_RATE):
                 k_coarse=0.00125, spread_min=1.6, spread_max=2.4)
 
 
-def c4fm_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False, tsbk=False, lc=False):
+def c4fm_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False, tsbk=False, lc=False, es=False, erasures=False):
     """the whole C4FM chain up to the slicer on channel `chan_id` of Frontend `fe`: the front half, then the symbol loop
     (p25_control_demod.py:118-135).  Returns the pre-filter channel's id: chan_read_fsk4 on it gives soft dibits at
     symbol_rate (slice_dibits turns them into dibits), chan_fsk4_state its offset estimate (`coarse`).  hard=True also
     attaches the slicer behind the loop: chan_read_hard gives packed dibits, chan_read_sync where FRAME_SYNC ends; with
     tsbk=True as well the TSBK stage behind the slicer (chan_read_tsbk, tsdu_frames), or with lc=True the voice-channel
-    stage (chan_read_p25lc, voice_units); the two exclude each other (ValueError)."""
+    stage (chan_read_p25lc, voice_units; es / erasures: its options, Frontend.chan_p25lc); the two exclude each other (ValueError)."""
     _one_decoder(tsbk, lc)
     cid = c4fm_front_half(fe, chan_id, channel_rate, symbol_rate)
     fe.chan_fsk4(cid, **fsk4_params(channel_rate, symbol_rate))
     if hard:
-        _hard(fe, cid, native.READ_FSK4, tsbk, lc)
+        _hard(fe, cid, native.READ_FSK4, tsbk, lc, es, erasures)
     return cid
 
 

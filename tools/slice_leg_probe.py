@@ -1,8 +1,9 @@
 """The RCF_T_SLICE leg per block with 256 channels behind one 4800-baud C4FM carrier (400 kS/s front-end, 25 kS/s channels, blocks
 of 16000 samples = 192 symbols a channel): slicers alone, with the TSBK stage on TSDUs sent back to back, with the P25 voice stage
-on LDU1 / LDU2 sent back to back.  The package directory names the tree whose rcf package (and librcf.so) is measured, so that a
+on LDU1 / LDU2 sent back to back -- as it always was (p25lc), with LDU2's encryption sync decoded (p25lc+es) and with erasures as
+well (p25lc+es+er).  The package directory names the tree whose rcf package (and librcf.so) is measured, so that a
 parent commit's build can stand next to this one's in one session; prints one JSON line (profiles/p25lc_slice_leg.json holds them).
-    python tools/slice_leg_probe.py <package dir> <none|tsbk|p25lc>"""
+    python tools/slice_leg_probe.py <package dir> <none|tsbk|p25lc|p25lc+es|p25lc+es+er>"""
 import json
 import os
 import sys
@@ -11,6 +12,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG, STAGE = os.path.abspath(sys.argv[1]), sys.argv[2]
+STAGE, OPTIONS = STAGE.split("+")[0], STAGE.split("+")[1:]
 for p in (os.path.join(ROOT, "tests"), PKG):
     sys.path.insert(0, p)
 import fsk4_ref as F  # noqa: E402
@@ -42,7 +44,7 @@ with nat.Frontend(FS, device=0, block_capacity=BLK) as fe:
         if STAGE == "tsbk":
             fe.chan_tsbk(c)
         elif STAGE == "p25lc":
-            fe.chan_p25lc(c)
+            fe.chan_p25lc(c, **({"es": "es" in OPTIONS, "erasures": "er" in OPTIONS} if OPTIONS else {}))     # (no option: a parent's binding too)
         cids.append(c)
     fe.timing_enable(True, classes=[nat.T_SLICE])
     for b in range(WARM):
@@ -55,6 +57,6 @@ with nat.Frontend(FS, device=0, block_capacity=BLK) as fe:
         per.append(ms)
     st = {} if STAGE == "none" else (fe.chan_tsbk_state(cids[-1]) if STAGE == "tsbk" else fe.chan_p25lc_state(cids[-1]))
 per = np.array(per)
-print(json.dumps(dict(pkg=os.path.relpath(PKG, ROOT), stage=STAGE, channels=N_CH, blocks=len(per), launches_per_block=int(n),
+print(json.dumps(dict(pkg=os.path.relpath(PKG, ROOT), stage="+".join([STAGE] + OPTIONS), channels=N_CH, blocks=len(per), launches_per_block=int(n),
                       slice_leg_ms_per_block_median=round(float(np.median(per)), 4), min=round(float(per.min()), 4),
                       max=round(float(per.max()), 4), last_channel_state=st)))
