@@ -554,8 +554,9 @@ int rcf_chan_slicer_rings(rcf_t *h, int chan_id, void **word_ring, size_t *word_
  * crc16), as one more optional stage per channel on the GPU.  It reads the slicer's own two streams and writes a third, the
  * counted stream RCF_HARD_TSBK of 32-byte records: a consumer of a control channel takes the 12-octet TSBKs instead of every
  * word of the dibit stream.  All of it is integer work: the records are exactly what the rules below give for the words and
- * hits the slicer's readers deliver.  (No BCH correction of the NID -- the reference reads NAC and DUID uncorrected --, no
- * other data unit than the TSDU, no parsing of a TSBK's fields.)
+ * hits the slicer's readers deliver.  (The reference reads NAC and DUID uncorrected and so does rcf_chan_tsbk; BCH
+ * correction of the NID is the option of rcf_chan_tsbk_ex below.  No other data unit than the TSDU, no parsing of a TSBK's
+ * fields.)
  * Frames.  A hit item gives k, the last dibit of the sync word (widened against n_symbols as above); the frame starts at
  * dibit s = k - 23.  Hits are taken in order; a hit is ACCEPTED if k >= k_last_accepted + 24 (buf.find(sync, fsoffset + 6)),
  * the first one the stage considers always.  An accepted hit is DECIDED in the first block after which the slicer's whole
@@ -593,12 +594,36 @@ int rcf_chan_slicer_rings(rcf_t *h, int chan_id, void **word_ring, size_t *word_
  * switched off, channel closed.
  * RCF_ESTATE: the channel has no slicer in RCF_SLICE_FSK4 mode that searches a 48-bit sync word, or that slicer searches both
  * polarities (sync_both = 1), or it carries the P25 voice stage (rcf_chan_p25lc); RCF_EINVAL: capacity not 0 or a power of
- * two >= 16 (at most 2^20); RCF_ENOCHAN: no such channel. */
+ * two >= 16 (at most 2^20); RCF_ENOCHAN: no such channel.
+ * The NID (RCF_NID_BCH; rcf_chan_tsbk_ex here, rcf_chan_p25lc_ex for the voice stage).  The NID's first 63 bits are a word
+ * of the binary BCH(63,16,23) code, t = 11: code bit i (0 .. 62) is info bit 48 + i of the frame -- bits 0 .. 11 the nac,
+ * bits 12 .. 15 the duid -- and the coefficient of x^(62 - i), data first, in rs64.py's msg order.  The code is the binary
+ * subfield subcode of RS(63,41,23) over GF(64) with x^6 + x + 1, alpha = 2 and the roots alpha^1 .. alpha^22 -- rs64.Codec(23)
+ * on 63 symbols that are all 0 or 1 --; its generator, the lcm of those roots' minimal polynomials, is octal
+ * 6331141367235453.  Info bit 111, the NID's 64th bit, takes no part (as the (24,12) Golay word's 24th bit without the
+ * erasure option).  With the option the result is the code word within 11 bits of the received 63 if there is one -- it is
+ * unique, d being 23 --: nac and duid are its first 16 bits and nid_fix is the number of bits it changes, 0 .. 11.  If there
+ * is none, nac and duid stand as received and nid_fix = 15.  The decoder is complete inside the bound.  The decoded duid is
+ * the one the stage acts on: "blocks are decoded only when duid == 7" here, the unit's kind in the voice stage.  The record's
+ * nac and duid carry the decoded values; a TSBK record's words 5-6 keep the 64 bits as received, so a consumer sees both.
+ * TSBK record: word 7 bits 16-19 nid_fix, bit 20 set (the NID went through the decoder).  Voice record: word 7 bits 28-31
+ * nid_fix, word 0 bit 9 set.  Without the option (RCF_NID_RAW) all of these bits are 0.  The option is fixed for a stage's
+ * life; calling an attach again starts the stage afresh with that call's value, so the records stay independent of how the
+ * input is cut.  rcf_chan_tsbk(h, c, p) is rcf_chan_tsbk_ex(h, c, p, RCF_NID_RAW): one attach path.  RCF_EINVAL as well: nid
+ * neither RCF_NID_RAW nor RCF_NID_BCH. */
 typedef struct rcf_tsbk_params {
     int capacity;          /* records of the ring, a power of two >= 16; 0 = 256 */
     int reserved_[3];
 } rcf_tsbk_params_t;
 int rcf_chan_tsbk(rcf_t *h, int chan_id, const rcf_tsbk_params_t *p);
+#define RCF_NID_RAW 0u   /* nac and duid as received (the reference's reading) */
+#define RCF_NID_BCH 1u   /* the NID's BCH(63,16,23) word decoded first: the rule above */
+int rcf_chan_tsbk_ex(rcf_t *h, int chan_id, const rcf_tsbk_params_t *p, uint32_t nid);
+/* the NID decoder's counters of the channel's TSBK or voice stage as of the last block; syncs the stream: frames whose NID
+ * went through the decoder, of them with nid_fix 1 .. 11, the sum of those nid_fix values, frames with nid_fix = 15.  All 0
+ * for a stage attached with RCF_NID_RAW.  RCF_ESTATE: the channel has neither stage */
+typedef struct rcf_nid_state { int64_t n_decoded, n_fixed, n_bits, n_bad; } rcf_nid_state_t;
+int rcf_chan_nid_state(rcf_t *h, int chan_id, rcf_nid_state_t *out);
 /* the stage's counters as of the last block; syncs the stream.  RCF_ESTATE without the stage (here and in the calls below) */
 typedef struct rcf_tsbk_state {
     int64_t n_records, n_frames, n_blocks, n_crc_bad, n_lost;   /* records written, frames accepted (decided or lost), blocks decoded, of them with a bad CRC, hits and frames lost */
@@ -752,13 +777,15 @@ int rcf_chan_osw_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity);
  * work: the records are exactly what the rules below give for the words and hits the slicer's readers deliver.  Optional,
  * through rcf_chan_p25lc_opt: LDU2's encryption sync (RCF_P25LC_ES) and inner words given up as erasures of the Reed-Solomon
  * decoder (RCF_P25LC_ERASURES); without an option every record is what the rules give without the paragraphs "LDU2" and
- * "Erasures".  (No BCH correction of the NID, no decoding of the LSD's (16,8,5) code, no IMBE.)
+ * "Erasures".  BCH correction of the NID is rcf_chan_p25lc_ex's option RCF_NID_BCH, by the rule "The NID" at rcf_chan_tsbk_ex.
+ * (No decoding of the LSD's (16,8,5) code, no IMBE.)
  * Frames.  Hits, the widening of k, the accept rule (k >= k_last_accepted + 24), the start at hit index >= the slicer's
  * n_hits at the call, the lost rule and "info dibit j sits at frame dibit r = j + j / 35" are rcf_chan_tsbk's.  The frame
  * starts at dibit s = k - 23; frame_dibits = min(864, s_next - s), s_next the frame start of the next accepted hit if there
  * is one by then.  An accepted hit is DECIDED in the first block with 16 n_words >= s + 888: the 864 dibits of an LDU and
  * the 24 of a sync word that may begin inside them -- so the records do not depend on how the input was cut into blocks.
- * NID: nac = info bits 48 .. 59, duid = info bits 60 .. 63, uncorrected (info bit 0 is the sync word's first bit).
+ * NID: nac = info bits 48 .. 59, duid = info bits 60 .. 63 (info bit 0 is the sync word's first bit), uncorrected unless the
+ * stage was attached with RCF_NID_BCH: then they are the decoded ones, and the decoded duid names the unit.
  * Units.  A unit is decoded only if its last needed frame dibit lies inside the frame (r < frame_dibits):
  *     duid 0x0  HDU   36 words of 18 bits, word w = info bits 112 + 18 w .. + 17; last dibit 389; inner code shortened Golay
  *                     (18,6,8), outer code RS(36,20,17); payload 20 hexbits = 15 octets (MI 72, MFID 8, ALGID 8, KID 16, TGID 16)
@@ -804,12 +831,12 @@ int rcf_chan_osw_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity);
  * Records, 8 uint32 each, in increasing k:
  *     word 0    bits 0-1 and bit 3 kind (0 HDU, 1 LDU1, 2 TLC, 3 a frame record; bit 3: 4 LDU2, with RCF_P25LC_ES only),
  *               bit 2 rs_bad, bits 4-7 n_rs's low four bits and bit 8 its fifth (set with RCF_P25LC_ERASURES only), bit 9
- *               zero, bits 10-15 the hit's distance, bits 16-19 duid, bits 20-31 nac (the last three where TSBK has them)
+ *               set with RCF_NID_BCH only, bits 10-15 the hit's distance, bits 16-19 duid, bits 20-31 nac (the last three where TSBK has them)
  *     word 1    the low 32 bits of the widened k
  *     word 2-5  the payload's octets, the first bit highest, bytes in memory order (the word ring's rule), zero padded; 0
  *               in a frame record
  *     word 6    the 32 raw LSD bits, same rule (LDU1, LDU2), else 0
- *     word 7    bits 0-15 frame_dibits, bits 16-21 inner words fixed, bits 22-27 inner words bad, bits 28-31 zero
+ *     word 7    bits 0-15 frame_dibits, bits 16-21 inner words fixed, bits 22-27 inner words bad, bits 28-31 nid_fix (RCF_NID_BCH; else zero)
  * p == NULL switches the stage off.  It applies from the next block on and considers only hits appended after the call;
  * calling again starts it afresh.  It goes when the slicer goes: slicer attached again or switched off, its source loop
  * attached again or switched off, channel closed.  A slicer carries this stage or the TSBK stage, never both: each of the two
@@ -818,7 +845,8 @@ int rcf_chan_osw_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity);
  * polarities (sync_both = 1), or it carries the TSBK stage; RCF_EINVAL: capacity not 0 or a power of two >= 16 (at most
  * 2^20), correct not 0 or 1, an unknown option bit, RCF_P25LC_ERASURES with correct = 0; RCF_ENOCHAN: no such channel.
  * rcf_chan_p25lc(h, c, p) is rcf_chan_p25lc_opt(h, c, p, 0): one attach path, and calling either again starts the stage
- * afresh with the options of that call. */
+ * afresh with the options of that call.  rcf_chan_p25lc_opt(h, c, p, o) in turn is rcf_chan_p25lc_ex(h, c, p, o, RCF_NID_RAW);
+ * RCF_EINVAL as well: nid neither RCF_NID_RAW nor RCF_NID_BCH. */
 typedef struct rcf_p25lc_params {
     int capacity;          /* records of the ring, a power of two >= 16; 0 = 256 */
     int correct;           /* 0: the reference's p25_general reading (systematic bits, nothing corrected); 1: the decoders above */
@@ -828,6 +856,7 @@ int rcf_chan_p25lc(rcf_t *h, int chan_id, const rcf_p25lc_params_t *p);
 #define RCF_P25LC_ES        1u   /* decode LDU2's encryption sync */
 #define RCF_P25LC_ERASURES  2u   /* inner words given up become Reed-Solomon erasures (needs correct = 1) */
 int rcf_chan_p25lc_opt(rcf_t *h, int chan_id, const rcf_p25lc_params_t *p, uint32_t options);
+int rcf_chan_p25lc_ex(rcf_t *h, int chan_id, const rcf_p25lc_params_t *p, uint32_t options, uint32_t nid);
 /* the stage's counters as of the last block; syncs the stream.  RCF_ESTATE without the stage (here and in the calls below) */
 typedef struct rcf_p25lc_state {
     int64_t n_records, n_frames, n_decoded, n_rs_bad, n_lost;   /* records written, frames accepted (decided or lost), units decoded (HDU, LDU1, TLC), of them with rs_bad, hits and frames lost */

@@ -25,8 +25,11 @@
 // All trip counts come from the host's n_k or are compile-time constants; the counters read from the device only clamp.
 // Every ring index is masked.  Plain vector stores only; nothing is shared between waves; no LDS.  Every cross-lane read
 // stands in wave-uniform control flow.
+// The option RCF_NID_BCH (kNidFlagBch): the NID's 63 bits go through nid_wave.hpp's decoder before the DUID names the unit's
+// kind, behind a wave-uniform branch like the other options.
 #include "item_wave.hpp"
 #include "p25lc_core.hpp"
+#include "nid_wave.hpp"
 
 namespace rcfx {
 
@@ -117,7 +120,8 @@ __global__ __launch_bounds__(64 * kP25lcWaves) void p25lc_kernel(const P25lcLaun
     if (w >= n_items) return;                        // (no workgroup barrier below: a wave leaves on its own)
     const P25lcLaunch L = items[w];
     P25lcState *st = L.st;
-    const bool correct = L.flags & kP25lcFlagCorrect, erasures = L.flags & kP25lcFlagErasures;
+    const bool correct = L.flags & kP25lcFlagCorrect, erasures = L.flags & kP25lcFlagErasures, nid = L.flags & kNidFlagBch;
+    NidCount nc;
     const int64_t n_sym = L.src->n_symbols, n_words = L.src->n_words, n_hits = L.src->n_hits;
     int64_t n_records = st->n_records, n_frames = st->n_frames, n_decoded = st->n_decoded, n_rs_bad = st->n_rs_bad, n_lost = st->n_lost;
     int64_t i = st->next_hit, k_last = st->k_last;
@@ -151,12 +155,18 @@ __global__ __launch_bounds__(64 * kP25lcWaves) void p25lc_kernel(const P25lcLaun
         // ---- the NID: info dibits 24 .. 55
         const int dn = lane < 32 ? dibit(tsbk_frame_pos(24 + lane)) : 0;
         const uint64_t nhi = __ballot(dn & 2), nlo = __ballot(dn & 1);
-        const uint32_t nid0 = slice_word_be(nhi, nlo, 2, 0);
+        uint32_t nid0 = slice_word_be(nhi, nlo, 2, 0), w0 = 0, w7 = 0;     // (what the option adds to the words 0 and 7)
+        if (nid) {                                   // (uniform)
+            int fix;
+            nid0 = nid_word0_of(nid_decode_wave(nid_poly(nid0, slice_word_be(nhi, nlo, 2, 1)), lane, &fix));
+            w0 = kNidP25lcWord0; w7 = nid_p25lc_word7(fix);
+            nc.add(fix);
+        }
         const int kind = __builtin_amdgcn_readfirstlane(p25lc_kind(tsbk_duid(nid0), fd, L.flags));
         uint32_t *rec = L.rec_ring + ((uint64_t)n_records & L.rec_mask) * kP25lcRecWords;
         ++n_records;
         if (kind == kP25lcFrame) {
-            const uint32_t v = lane == 0 ? p25lc_word0(kind, false, 0, dist, nid0) : lane == 1 ? (uint32_t)(uint64_t)k0 : lane == 7 ? p25lc_word7(fd, 0, 0) : 0u;
+            const uint32_t v = lane == 0 ? p25lc_word0(kind, false, 0, dist, nid0) | w0 : lane == 1 ? (uint32_t)(uint64_t)k0 : lane == 7 ? p25lc_word7(fd, 0, 0) | w7 : 0u;
             if (lane < kP25lcRecWords) rec[lane] = v;
             continue;
         }
@@ -188,8 +198,8 @@ __global__ __launch_bounds__(64 * kP25lcWaves) void p25lc_kernel(const P25lcLaun
         const uint32_t pw = lane_read(slice_word_mem(p25lc_pay_word(pay, lane & 3)), lane - 2);
         const int dl = p25lc_has_lsd(kind) && lane < 16 ? dibit(tsbk_frame_pos(kP25lcLsdDibit + lane)) : 0;
         const uint64_t lhi = __ballot(dl & 2), llo = __ballot(dl & 1);
-        const uint32_t v = lane == 0 ? p25lc_word0_wide(kind, rs_bad, n_rs, dist, nid0) : lane == 1 ? (uint32_t)(uint64_t)k0 : lane < 6 ? pw :
-                           lane == 6 ? slice_word_mem(slice_word_be(lhi, llo, 2, 0)) : p25lc_word7(fd, n_fixed, n_bad);
+        const uint32_t v = lane == 0 ? p25lc_word0_wide(kind, rs_bad, n_rs, dist, nid0) | w0 : lane == 1 ? (uint32_t)(uint64_t)k0 : lane < 6 ? pw :
+                           lane == 6 ? slice_word_mem(slice_word_be(lhi, llo, 2, 0)) : p25lc_word7(fd, n_fixed, n_bad) | w7;
         if (lane < kP25lcRecWords) rec[lane] = v;
         ++n_decoded;
         n_rs_bad += rs_bad ? 1 : 0;
@@ -197,6 +207,7 @@ __global__ __launch_bounds__(64 * kP25lcWaves) void p25lc_kernel(const P25lcLaun
     if (lane == 0) {
         st->n_records = n_records; st->n_frames = n_frames; st->n_decoded = n_decoded; st->n_rs_bad = n_rs_bad; st->n_lost = n_lost;
         st->next_hit = i; st->k_last = k_last;
+        if (nid) { st->nid_decoded += nc.decoded; st->nid_fixed += nc.fixed; st->nid_bits += nc.bits; st->nid_bad += nc.bad; }
     }
 }
 

@@ -371,8 +371,11 @@ struct TsbkState {
     int64_t n_frames, n_blocks, n_crc_bad, n_lost;
     int64_t next_hit;        // the first hit of the slicer's stream that is neither rejected nor decided
     int64_t k_last;          // the last accepted hit's k
+    int64_t nid_decoded, nid_fixed, nid_bits, nid_bad;   // rcf_nid_state_t's counters (RCF_NID_BCH; else 0)
 };
-struct TsbkLaunch : FramesLaunch<TsbkState> {};
+struct TsbkLaunch : FramesLaunch<TsbkState> {
+    uint32_t flags;          // kNidFlagBch (nid_core.hpp): the stage decodes the NID
+};
 void launch_tsbk(const TsbkLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
 // EDACS control frames behind a slicer (edacs.hip; get_next_frame, packet_framer, bch_decode, message_election of the
 // reference: six 40-bit copies per frame, BCH(48,36) over GF(64), two of three; definition: include/rcf.h at rcf_chan_edacs).
@@ -408,9 +411,10 @@ struct P25lcState {
     int64_t n_frames, n_decoded, n_rs_bad, n_lost;
     int64_t next_hit;        // the first hit of the slicer's stream that is neither rejected nor decided
     int64_t k_last;          // the last accepted hit's k
+    int64_t nid_decoded, nid_fixed, nid_bits, nid_bad;   // rcf_nid_state_t's counters (RCF_NID_BCH; else 0)
 };
 struct P25lcLaunch : FramesLaunch<P25lcState> {
-    uint32_t flags;          // bit 0: the stage's `correct`; from bit 1 on the options of rcf_chan_p25lc_opt (kP25lcFlagEs, kP25lcFlagErasures)
+    uint32_t flags;          // bit 0: the stage's `correct`; from bit 1 on the options of rcf_chan_p25lc_opt (kP25lcFlagEs, kP25lcFlagErasures); kNidFlagBch
 };
 void launch_p25lc(const P25lcLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
 // the records' layouts as the kernels were compiled for them
@@ -422,7 +426,7 @@ template <class L> constexpr bool frames_launch_layout()
            offsetof(L, rec_ring) == 32 && offsetof(L, word_mask) == 40 && offsetof(L, hit_mask) == 44 && offsetof(L, rec_mask) == 48 &&
            offsetof(L, n_k) == 52;
 }
-static_assert(frames_launch_layout<TsbkLaunch>() && sizeof(TsbkLaunch) == 56, "TsbkLaunch");
+static_assert(frames_launch_layout<TsbkLaunch>() && sizeof(TsbkLaunch) == 64 && offsetof(TsbkLaunch, flags) == 56, "TsbkLaunch");
 static_assert(frames_launch_layout<OswLaunch>() && sizeof(OswLaunch) == 56, "OswLaunch");
 static_assert(frames_launch_layout<EdacsLaunch>() && sizeof(EdacsLaunch) == 64 && offsetof(EdacsLaunch, flags) == 56, "EdacsLaunch");
 static_assert(frames_launch_layout<P25lcLaunch>() && sizeof(P25lcLaunch) == 64 && offsetof(P25lcLaunch, flags) == 56, "P25lcLaunch");

@@ -16,6 +16,7 @@
 #include "edacs_core.hpp"      // (kEdacsNoFrame, kEdacsRecWords; slice_sync_both_ok of slice_core.hpp)
 #include "osw_core.hpp"        // (kOswSyncBits, kOswRecWords)
 #include "p25lc_core.hpp"      // (kP25lcRecWords, kP25lcFlagCorrect)
+#include "nid_core.hpp"        // (kNidFlagBch)
 static_assert(rcfx::kP25lcFlagEs == RCF_P25LC_ES << 1 && rcfx::kP25lcFlagErasures == RCF_P25LC_ERASURES << 1, "the options travel in P25lcLaunch::flags behind kP25lcFlagCorrect");
 
 namespace rcfx {
@@ -441,12 +442,43 @@ int rcf_chan_slicer_state(rcf_t *h, int chan_id, rcf_slicer_state_t *out)
 }
 
 // ---- the frame decoders behind the slicer (tsbk.hip, edacs.hip, osw.hip, p25lc.hip)
-int rcf_chan_tsbk(rcf_t *h, int chan_id, const rcf_tsbk_params_t *p)
+// the NID option of the two P25 stages: RCF_NID_RAW or RCF_NID_BCH, as the launch record's flag
+static bool nid_ok(const void *p, uint32_t nid, const char *name)
 {
+    if (p && nid != RCF_NID_RAW && nid != RCF_NID_BCH) { set_error("%s stage: nid %u is neither RCF_NID_RAW nor RCF_NID_BCH", name, nid); return false; }
+    return true;
+}
+
+int rcf_chan_tsbk(rcf_t *h, int chan_id, const rcf_tsbk_params_t *p) { return rcf_chan_tsbk_ex(h, chan_id, p, RCF_NID_RAW); }
+
+int rcf_chan_tsbk_ex(rcf_t *h, int chan_id, const rcf_tsbk_params_t *p, uint32_t nid)
+{
+    if (!nid_ok(p, nid, "TSBK")) return RCF_EINVAL;
     return attach_frames<Chan::Slicer::Tsbk>(h, chan_id, p,
         [](const Chan::Slicer &l) { return l.rec.bps == 2 && l.rec.sync_bits == 48 && !l.rec.sync_both && !l.p25lc; },
         "channel %d has no slicer in RCF_SLICE_FSK4 mode that searches a 48-bit sync word in one polarity, or that slicer carries the P25 voice stage",
-        [](TsbkLaunch &, TsbkState &st0, const SliceLaunch &, const SliceState &) { st0.k_last = kTsbkNoFrame; });
+        [nid](TsbkLaunch &r, TsbkState &st0, const SliceLaunch &, const SliceState &) {
+            r.flags = nid == RCF_NID_BCH ? kNidFlagBch : 0u;
+            st0.k_last = kTsbkNoFrame;
+        });
+}
+
+// the NID decoder's counters: the end of the state record of whichever of the two stages the slicer carries
+int rcf_chan_nid_state(rcf_t *h, int chan_id, rcf_nid_state_t *out)
+{
+    if (!h || !out) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    static_assert(offsetof(TsbkState, nid_decoded) == offsetof(P25lcState, nid_decoded) && sizeof(TsbkState) == sizeof(P25lcState), "one place for both stages");
+    const char *st = c->slicer && c->slicer->tsbk ? reinterpret_cast<const char *>(c->slicer->tsbk->rec.st) :
+                     c->slicer && c->slicer->p25lc ? reinterpret_cast<const char *>(c->slicer->p25lc->rec.st) : nullptr;
+    if (!st) { set_error("channel %d has neither the TSBK stage nor the P25 voice stage", chan_id); return RCF_ESTATE; }
+    int64_t four[4];
+    const int rc = stage_state(h, st + offsetof(TsbkState, nid_decoded), four, sizeof(four));
+    if (rc != RCF_OK) return rc;
+    out->n_decoded = four[0]; out->n_fixed = four[1]; out->n_bits = four[2]; out->n_bad = four[3];
+    return RCF_OK;
 }
 
 int rcf_chan_tsbk_state(rcf_t *h, int chan_id, rcf_tsbk_state_t *out)
@@ -498,16 +530,19 @@ int rcf_chan_osw_state(rcf_t *h, int chan_id, rcf_osw_state_t *out)
 
 int rcf_chan_p25lc(rcf_t *h, int chan_id, const rcf_p25lc_params_t *p) { return rcf_chan_p25lc_opt(h, chan_id, p, 0u); }
 
-int rcf_chan_p25lc_opt(rcf_t *h, int chan_id, const rcf_p25lc_params_t *p, uint32_t options)
+int rcf_chan_p25lc_opt(rcf_t *h, int chan_id, const rcf_p25lc_params_t *p, uint32_t options) { return rcf_chan_p25lc_ex(h, chan_id, p, options, RCF_NID_RAW); }
+
+int rcf_chan_p25lc_ex(rcf_t *h, int chan_id, const rcf_p25lc_params_t *p, uint32_t options, uint32_t nid)
 {
+    if (!nid_ok(p, nid, "P25 voice")) return RCF_EINVAL;
     if (p && p->correct != 0 && p->correct != 1) { set_error("P25 voice stage: correct %d is not 0 or 1", p->correct); return RCF_EINVAL; }
     if (p && (options & ~(RCF_P25LC_ES | RCF_P25LC_ERASURES))) { set_error("P25 voice stage: unknown option bits 0x%x", options); return RCF_EINVAL; }
     if (p && (options & RCF_P25LC_ERASURES) && !p->correct) { set_error("P25 voice stage: RCF_P25LC_ERASURES needs correct = 1"); return RCF_EINVAL; }
     return attach_frames<Chan::Slicer::P25lc>(h, chan_id, p,
         [](const Chan::Slicer &l) { return l.rec.bps == 2 && l.rec.sync_bits == 48 && !l.rec.sync_both && !l.tsbk; },
         "channel %d has no slicer in RCF_SLICE_FSK4 mode that searches a 48-bit sync word in one polarity, or that slicer carries the TSBK stage",
-        [p, options](P25lcLaunch &r, P25lcState &st0, const SliceLaunch &, const SliceState &) {
-            r.flags = (p->correct ? kP25lcFlagCorrect : 0u) | options << 1;
+        [p, options, nid](P25lcLaunch &r, P25lcState &st0, const SliceLaunch &, const SliceState &) {
+            r.flags = (p->correct ? kP25lcFlagCorrect : 0u) | options << 1 | (nid == RCF_NID_BCH ? kNidFlagBch : 0u);
             st0.k_last = kTsbkNoFrame;
         });
 }

@@ -17,8 +17,11 @@
 // idle.  The lanes 0 .. 7 store a record's eight words.
 // All trip counts come from the host's n_k; the counters read from the device only clamp.  Every ring index is masked.  Plain
 // vector stores only; nothing is shared between waves; no LDS.
+// The option RCF_NID_BCH (kNidFlagBch in the launch record's flags): the NID's 63 bits go through nid_wave.hpp's decoder
+// before the DUID is looked at, behind a wave-uniform branch that a stage without the option never enters.
 #include "item_wave.hpp"
 #include "tsbk_core.hpp"
+#include "nid_wave.hpp"
 
 namespace rcfx {
 
@@ -39,6 +42,8 @@ __global__ __launch_bounds__(64 * kTsbkWaves) void tsbk_kernel(const TsbkLaunch 
     if (w >= n_items) return;                        // (no workgroup barrier below: a wave leaves on its own)
     const TsbkLaunch L = items[w];
     TsbkState *st = L.st;
+    const bool nid = L.flags & kNidFlagBch;
+    NidCount nc;
     const int64_t n_sym = L.src->n_symbols, n_words = L.src->n_words, n_hits = L.src->n_hits;
     int64_t n_records = st->n_records, n_frames = st->n_frames, n_blocks = st->n_blocks, n_crc_bad = st->n_crc_bad, n_lost = st->n_lost;
     int64_t i = st->next_hit, k_last = st->k_last;
@@ -72,11 +77,18 @@ __global__ __launch_bounds__(64 * kTsbkWaves) void tsbk_kernel(const TsbkLaunch 
         const int dn = lane < 32 ? ring_dibit(L, s + tsbk_frame_pos(24 + lane)) : 0;
         const uint64_t nhi = __ballot(dn & 2), nlo = __ballot(dn & 1);
         const uint32_t nid0 = slice_word_be(nhi, nlo, 2, 0), nid1 = slice_word_be(nhi, nlo, 2, 1);
-        const int nb = tsbk_duid(nid0) == 7 ? tsbk_blocks_in(fd) : 0;
+        uint32_t nidc = nid0, w7 = (uint32_t)fd;     // nac and duid as the record holds them; word 7
+        if (nid) {                                   // (uniform)
+            int fix;
+            nidc = nid_word0_of(nid_decode_wave(nid_poly(nid0, nid1), lane, &fix));
+            w7 |= nid_tsbk_word7(fix);
+            nc.add(fix);
+        }
+        const int nb = tsbk_duid(nidc) == 7 ? tsbk_blocks_in(fd) : 0;
         uint32_t *rec = L.rec_ring + ((uint64_t)n_records & L.rec_mask) * kTsbkRecWords;
         if (nb == 0) {                               // a frame record
-            const uint32_t v = lane == 0 ? tsbk_word0(3, false, 0, 0, dist, nid0) : lane == 1 ? (uint32_t)(uint64_t)k0 :
-                               lane == 5 ? slice_word_mem(nid0) : lane == 6 ? slice_word_mem(nid1) : lane == 7 ? (uint32_t)fd : 0u;
+            const uint32_t v = lane == 0 ? tsbk_word0(3, false, 0, 0, dist, nidc) : lane == 1 ? (uint32_t)(uint64_t)k0 :
+                               lane == 5 ? slice_word_mem(nid0) : lane == 6 ? slice_word_mem(nid1) : lane == 7 ? w7 : 0u;
             if (lane < kTsbkRecWords) rec[lane] = v;
             ++n_records;
             continue;
@@ -106,9 +118,9 @@ __global__ __launch_bounds__(64 * kTsbkWaves) void tsbk_kernel(const TsbkLaunch 
             const int jn = tsbk_frame_pos(tsbk_block_dibit(b, 98));                           // the info bit behind the block
             const int next_bit = jn < fd ? ring_dibit(L, s + jn) >> 1 : 0;
             rec = L.rec_ring + ((uint64_t)n_records & L.rec_mask) * kTsbkRecWords;
-            const uint32_t v = lane == 0 ? tsbk_word0(b, crc_bad, next_bit, n_inexact, dist, nid0) : lane == 1 ? (uint32_t)(uint64_t)k0 :
+            const uint32_t v = lane == 0 ? tsbk_word0(b, crc_bad, next_bit, n_inexact, dist, nidc) : lane == 1 ? (uint32_t)(uint64_t)k0 :
                                lane < 5 ? slice_word_mem(slice_word_be(hi, lo, 2, lane - 2)) :
-                               lane == 5 ? slice_word_mem(nid0) : lane == 6 ? slice_word_mem(nid1) : (uint32_t)fd;
+                               lane == 5 ? slice_word_mem(nid0) : lane == 6 ? slice_word_mem(nid1) : w7;
             if (lane < kTsbkRecWords) rec[lane] = v;
             ++n_records; ++n_blocks;
             n_crc_bad += crc_bad ? 1 : 0;
@@ -117,6 +129,7 @@ __global__ __launch_bounds__(64 * kTsbkWaves) void tsbk_kernel(const TsbkLaunch 
     if (lane == 0) {
         st->n_records = n_records; st->n_frames = n_frames; st->n_blocks = n_blocks; st->n_crc_bad = n_crc_bad; st->n_lost = n_lost;
         st->next_hit = i; st->k_last = k_last;
+        if (nid) { st->nid_decoded += nc.decoded; st->nid_fixed += nc.fixed; st->nid_bits += nc.bits; st->nid_bad += nc.bad; }
     }
 }
 

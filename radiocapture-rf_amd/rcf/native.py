@@ -41,6 +41,7 @@ SYMBOLS = [
     "rcf_chan_tsbk", "rcf_chan_tsbk_state", "rcf_chan_read_tsbk", "rcf_chan_tsbk_ring",
     "rcf_chan_edacs", "rcf_chan_edacs_state", "rcf_chan_read_edacs", "rcf_chan_edacs_ring",
     "rcf_chan_osw", "rcf_chan_osw_state", "rcf_chan_read_osw", "rcf_chan_osw_ring",
+    "rcf_chan_tsbk_ex", "rcf_chan_p25lc_ex", "rcf_chan_nid_state",
     "rcf_chan_p25lc", "rcf_chan_p25lc_opt", "rcf_chan_p25lc_state", "rcf_chan_read_p25lc", "rcf_chan_p25lc_ring",
     "rcf_design_firdes", "rcf_design_optfir_low_pass", "rcf_design_fm_deemph", "rcf_design_resampler", "rcf_chan_audio_open",
     "rcf_chan_audio_close", "rcf_chan_audio_produced", "rcf_chan_read_audio",
@@ -186,12 +187,31 @@ class TsbkState(C.Structure):
                 ("n_lost", C.c_int64)]
 
 
+class NidState(C.Structure):
+    """rcf_nid_state_t (include/rcf.h)"""
+    _fields_ = [("n_decoded", C.c_int64), ("n_fixed", C.c_int64), ("n_bits", C.c_int64), ("n_bad", C.c_int64)]
+
+
 def tsbk_fields(records):
     """word 0 of TSBK records taken apart -> dict of arrays: b (3: a frame record), crc_bad, next_bit, n_inexact, dist, duid, nac"""
     f = np.asarray(records["flags"], dtype=np.uint32)
     return dict(b=(f & 3).astype(np.uint8), crc_bad=((f >> 2) & 1).astype(np.uint8), next_bit=((f >> 3) & 1).astype(np.uint8),
                 n_inexact=((f >> 4) & 63).astype(np.uint8), dist=((f >> 10) & 63).astype(np.uint8),
                 duid=((f >> 16) & 15).astype(np.uint8), nac=(f >> 20).astype(np.uint16))
+
+
+def nid_fields(records):
+    """what RCF_NID_BCH adds to TSBK records (TSBK_DTYPE) or P25 voice records (P25LC_DTYPE) -> dict of arrays: nid_fix (bits
+    the NID's BCH decoder changed, 15: no code word within its bound), nid_decoded (the NID went through that decoder; both
+    are 0 for a stage attached without the option) and frame_dibits (word 7's low 16 bits: in a TSBK record the option's
+    bits stand above them)"""
+    if "frame_dibits" in records.dtype.names:
+        t = np.asarray(records["frame_dibits"], dtype=np.uint32)
+        fix, decoded = (t >> 16) & 15, (t >> 20) & 1
+    else:
+        t = np.asarray(records["tail"], dtype=np.uint32)
+        fix, decoded = t >> 28, (np.asarray(records["flags"], dtype=np.uint32) >> 9) & 1
+    return dict(nid_fix=fix.astype(np.uint8), nid_decoded=decoded.astype(np.uint8), frame_dibits=(t & 0xffff).astype(np.uint16))
 
 
 class EdacsParams(C.Structure):
@@ -249,7 +269,7 @@ class P25lcState(C.Structure):
 def p25lc_fields(records):
     """words 0 and 7 of P25 voice records taken apart -> dict of arrays: kind (0 HDU, 1 LDU1, 2 TLC, 3: a frame record, 4 LDU2:
     its third bit is word 0 bit 3), rs_bad, n_rs (five bits, the fifth is word 0 bit 8), dist, duid, nac, frame_dibits, n_fixed,
-    n_bad (inner words corrected / given up)"""
+    n_bad (inner words corrected / given up).  What RCF_NID_BCH adds: nid_fields"""
     f = np.asarray(records["flags"], dtype=np.uint32)
     t = np.asarray(records["tail"], dtype=np.uint32)
     return dict(kind=((f & 3) | ((f >> 1) & 4)).astype(np.uint8), rs_bad=((f >> 2) & 1).astype(np.uint8),
@@ -442,6 +462,9 @@ def lib():
         sig["rcf_chan_read_" + name] = (i64, [vp, C.c_int, C.POINTER(C.c_uint32), sz])
         sig["rcf_chan_%s_ring" % name] = (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz)])
     sig["rcf_chan_p25lc_opt"] = (C.c_int, [vp, C.c_int, C.POINTER(P25lcParams), C.c_uint32])
+    sig["rcf_chan_tsbk_ex"] = (C.c_int, [vp, C.c_int, C.POINTER(TsbkParams), C.c_uint32])
+    sig["rcf_chan_p25lc_ex"] = (C.c_int, [vp, C.c_int, C.POINTER(P25lcParams), C.c_uint32, C.c_uint32])
+    sig["rcf_chan_nid_state"] = (C.c_int, [vp, C.c_int, C.POINTER(NidState)])
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
         fn.restype = res
@@ -1028,11 +1051,18 @@ class Frontend:
         _check(lib().rcf_chan_slicer_rings(self._h, cid, C.byref(wp), C.byref(wc), C.byref(hp), C.byref(hc)))
         return wp.value, wc.value, hp.value, hc.value
 
-    def chan_tsbk(self, cid, capacity=0, on=True):
-        """P25 trunking blocks behind the channel's slicer (rcf_chan_tsbk): frames from the sync hits, status symbols
+    def chan_tsbk(self, cid, capacity=0, on=True, nid=False):
+        """P25 trunking blocks behind the channel's slicer (rcf_chan_tsbk_ex): frames from the sync hits, status symbols
         stripped, NID read, every block deinterleaved, trellis-decoded and CRC-checked on the GPU; records of TSBK_DTYPE
-        in a ring of `capacity` (0: 256).  It considers the hits from now on; on=False switches it off."""
-        self._attach(lib().rcf_chan_tsbk, cid, TsbkParams, on, capacity=capacity)
+        in a ring of `capacity` (0: 256).  nid=True (RCF_NID_BCH): the NID's BCH(63,16,23) word is decoded first and the
+        decoded DUID decides whether blocks are decoded (nid_fields: nid_fix, nid_decoded; chan_nid_state).  It considers the
+        hits from now on; on=False switches it off."""
+        self._attach(lambda h, c, p: lib().rcf_chan_tsbk_ex(h, c, p, int(nid)), cid, TsbkParams, on, capacity=capacity)
+
+    def chan_nid_state(self, cid) -> dict:
+        """n_decoded, n_fixed, n_bits, n_bad of the NID decoder of the channel's TSBK or P25 voice stage as of the last block
+        (rcf_chan_nid_state; syncs the stream): all 0 for a stage attached without nid"""
+        return self._state_of(lib().rcf_chan_nid_state, cid, NidState)
 
     def chan_tsbk_state(self, cid) -> dict:
         """n_records, n_frames, n_blocks, n_crc_bad, n_lost of the TSBK stage as of the last block (rcf_chan_tsbk_state;
@@ -1093,9 +1123,15 @@ class Frontend:
         word decoded on the GPU (correct=False: p25_general's uncorrected reading); records of P25LC_DTYPE in a ring of
         `capacity` (0: 256).  es=True decodes LDU2's encryption sync as well (kind 4); erasures=True (needs correct) hands
         the inner words given up to the Reed-Solomon decoder as erasures.  It considers the hits from now on and excludes
-        the TSBK stage; on=False switches it off."""
+        the TSBK stage; on=False switches it off.  chan_p25lc_ex is this with the NID option."""
+        self.chan_p25lc_ex(cid, capacity, correct, on, es, erasures)
+
+    def chan_p25lc_ex(self, cid, capacity=0, correct=True, on=True, es=False, erasures=False, nid=False):
+        """chan_p25lc with rcf_chan_p25lc_ex's last argument: nid=True (RCF_NID_BCH) decodes the NID's BCH(63,16,23) word
+        first, and the decoded DUID names the unit (nid_fields takes nid_fix and nid_decoded out of the records;
+        chan_nid_state has the counters)"""
         options = (P25LC_ES if es else 0) | (P25LC_ERASURES if erasures else 0)
-        self._attach(lambda h, c, p: lib().rcf_chan_p25lc_opt(h, c, p, options), cid, P25lcParams, on, capacity=capacity, correct=int(correct))
+        self._attach(lambda h, c, p: lib().rcf_chan_p25lc_ex(h, c, p, options, int(nid)), cid, P25lcParams, on, capacity=capacity, correct=int(correct))
 
     def chan_p25lc_state(self, cid) -> dict:
         """n_records, n_frames, n_decoded, n_rs_bad, n_lost of the P25 voice stage as of the last block

@@ -34,28 +34,70 @@ def _one_decoder(tsbk, lc):
         raise ValueError("tsbk and lc exclude each other: a slicer carries one frame decoder")
 
 
-def _hard(fe, cid, source, tsbk=False, lc=False, es=False, erasures=False):
+def _hard(fe, cid, source, tsbk=False, lc=False, es=False, erasures=False, nid=False):
     fe.chan_slicer(cid, source, native.SLICE_FSK4, SLICER_LEVELS, FRAME_SYNC, FRAME_SYNC_BITS, FRAME_SYNC_MAX_ERRORS)
     if tsbk:
-        fe.chan_tsbk(cid)
+        fe.chan_tsbk(cid, nid=nid)
     if lc:
-        fe.chan_p25lc(cid, es=es, erasures=erasures)
+        fe.chan_p25lc_ex(cid, es=es, erasures=erasures, nid=nid)
+
+
+# ---- the NID's BCH(63,16,23) word on the host (the stages' option nid=True decodes it on the GPU: rcf.h at rcf_chan_tsbk_ex)
+NID_GENERATOR = 0o6331141367235453   # degree 47: the lcm of the minimal polynomials of alpha^1 .. alpha^22 in GF(64), x^6 + x + 1
+_NID_WORDS = None
+
+
+def nid_encode(nac, duid):
+    """the 63-bit code word of (nac, duid), the first bit highest: the 16 data bits, then the 47 check bits"""
+    data = ((nac & 0xfff) << 4 | (duid & 15)) << 47
+    rem = data
+    for e in range(62, 46, -1):
+        if rem >> e & 1:
+            rem ^= NID_GENERATOR << (e - 47)
+    return data | rem
+
+
+def nid_decode(bits):
+    """the host form of the stages' NID rule.  bits: the NID's first 63 bits (a sequence of 0 / 1, info bits 48 .. 110 of a
+    frame; a 64th is ignored) or the same as an int, the first bit highest -> dict(nac, duid, nid_fix): the code word within
+    11 bits if there is one, nid_fix the bits it changes; else nac and duid as received and nid_fix 15.  By search over all
+    65536 code words, so complete by construction"""
+    global _NID_WORDS
+    if _NID_WORDS is None:
+        rows = [nid_encode(0, 0)] + [nid_encode((1 << b) >> 4, (1 << b) & 15) for b in range(16)]
+        words = np.zeros(1, np.uint64)
+        for r in rows[1:]:
+            words = np.concatenate([words, words ^ np.uint64(r)])
+        _NID_WORDS = words
+    if not isinstance(bits, (int, np.integer)):
+        v = 0
+        for b in list(bits)[:63]:
+            v = v << 1 | (int(b) & 1)
+        bits = v
+    r = int(bits) & ((1 << 63) - 1)
+    x = _NID_WORDS ^ np.uint64(r)
+    dist = np.unpackbits(x.view(np.uint8)).reshape(-1, 64).sum(axis=1)
+    at = int(np.argmin(dist))
+    fix = int(dist[at])
+    word = int(_NID_WORDS[at]) if fix <= 11 else r
+    return dict(nac=word >> 51, duid=word >> 47 & 15, nid_fix=fix if fix <= 11 else 15)
 
 
 def tsdu_frames(records, reference_rule=False):
     """records of the TSBK stage (Frontend.chan_read_tsbk, native.TSBK_DTYPE) grouped into frames, in the stream's order ->
-    list of dict(k, dist, nac, duid, frame_dibits, nid: 8 octets, tsbk: list of dict(b, octets: 12 octets, crc: 0 good /
+    list of dict(k, dist, nac, duid, frame_dibits, nid: 8 octets as received, nid_fix, nid_decoded, tsbk: list of dict(b, octets: 12 octets, crc: 0 good /
     1 bad as subprocTSBK's, next_bit, n_inexact)).  A frame record (no block) gives a frame with an empty list.
     reference_rule=True stops a frame's list behind a block whose next_bit is 1, as procTSDU does: the list is then its
     r['tsbk'].  A frame is told from the one before by the low 32 bits of k."""
     records = np.asarray(records, dtype=native.TSBK_DTYPE)
-    f = native.tsbk_fields(records)
+    f = dict(native.tsbk_fields(records), **native.nid_fields(records))
     frames, stopped = [], False
     for i in range(len(records)):
         k = int(records["k"][i])
         if not frames or frames[-1]["k"] != k:
             frames.append(dict(k=k, dist=int(f["dist"][i]), nac=int(f["nac"][i]), duid=int(f["duid"][i]),
-                               frame_dibits=int(records["frame_dibits"][i]), nid=bytes(records["nid"][i]), tsbk=[]))
+                               frame_dibits=int(f["frame_dibits"][i]), nid=bytes(records["nid"][i]), nid_fix=int(f["nid_fix"][i]),
+                               nid_decoded=int(f["nid_decoded"][i]), tsbk=[]))
             stopped = False
         if f["b"][i] == 3 or stopped:
             continue
@@ -89,17 +131,17 @@ def voice_units(records):
     """records of the P25 voice stage (Frontend.chan_read_p25lc, native.P25LC_DTYPE), in the stream's order -> list of dict
     shaped like the results of p25_general's proc*: short ('HDU' / 'LDU1' / 'TLC' / 'LDU2' / 'TnoLC' / 'TSDU' / 'PDU'; None
     for a DUID the reference does not know), nac, duid, k, dist, frame_dibits, decoded (False: a frame record -- the unit has
-    no link control, or the frame was too short for it), rs_bad, n_rs, n_fixed, n_bad; for a decoded LDU1 or TLC `lc`
+    no link control, or the frame was too short for it), rs_bad, n_rs, n_fixed, n_bad, nid_fix, nid_decoded; for a decoded LDU1 or TLC `lc`
     (link_control of the 9 octets) and for the LDU1 `lsd` (4 octets); for a decoded HDU mi (9 octets), mfid, algid, kid, tgid;
     for a decoded LDU2 (a stage attached with es=True) its encryption sync mi (9 octets), algid, kid, and `lsd`"""
     records = np.asarray(records, dtype=native.P25LC_DTYPE)
-    f = native.p25lc_fields(records)
+    f = dict(native.p25lc_fields(records), **native.nid_fields(records))
     units = []
     for i in range(len(records)):
         kind, duid = int(f["kind"][i]), int(f["duid"][i])
         u = dict(short=DUID_SHORT.get(duid), nac=int(f["nac"][i]), duid=duid, k=int(records["k"][i]), dist=int(f["dist"][i]),
                  frame_dibits=int(f["frame_dibits"][i]), decoded=kind != 3, rs_bad=int(f["rs_bad"][i]), n_rs=int(f["n_rs"][i]),
-                 n_fixed=int(f["n_fixed"][i]), n_bad=int(f["n_bad"][i]))
+                 n_fixed=int(f["n_fixed"][i]), n_bad=int(f["n_bad"][i]), nid_fix=int(f["nid_fix"][i]), nid_decoded=int(f["nid_decoded"][i]))
         pay = bytes(records["payload"][i])
         if kind == 0:
             u.update(mi=pay[:9], mfid=pay[9], algid=pay[10], kid=_bits(pay, 88, 104), tgid=_bits(pay, 104, 120))
@@ -153,18 +195,18 @@ def costas_params(channel_rate, symbol_rate=SYMBOL_RATE):
                 beta=0.125 * alpha * alpha, max_freq=2.0 * math.pi * 1200.0 / rate, omega_limit=0.005)
 
 
-def cqpsk_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False, tsbk=False, lc=False, es=False, erasures=False):
+def cqpsk_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False, tsbk=False, lc=False, es=False, erasures=False, nid=False):
     """the whole CQPSK chain up to the slicer on channel `chan_id` of Frontend `fe`: the front half, then the Gardner /
     Costas stage (p25_control_demod.py:136-183).  Returns the pre-filter channel's id: chan_read_costas on it gives soft
     dibits at symbol_rate (slice_dibits turns them into dibits), chan_costas_state its carrier estimate.  hard=True also
     attaches the slicer behind the loop: chan_read_hard gives packed dibits, chan_read_sync where FRAME_SYNC ends; with
     tsbk=True as well the TSBK stage behind the slicer (chan_read_tsbk, tsdu_frames), or with lc=True the voice-channel
-    stage (chan_read_p25lc, voice_units; es / erasures: its options, Frontend.chan_p25lc); the two exclude each other (ValueError)."""
+    stage (chan_read_p25lc, voice_units; es / erasures: its options, Frontend.chan_p25lc); the two exclude each other (ValueError).  nid=True: either stage decodes the NID's BCH word first (nid_decode is the host form)."""
     _one_decoder(tsbk, lc)
     cid = cqpsk_front_half(fe, chan_id, channel_rate)
     fe.chan_costas(cid, **costas_params(channel_rate, symbol_rate))
     if hard:
-        _hard(fe, cid, native.READ_COSTAS, tsbk, lc, es, erasures)
+        _hard(fe, cid, native.READ_COSTAS, tsbk, lc, es, erasures, nid)
     return cid
 
 
@@ -190,18 +232,18 @@ def fsk4_params(channel_rate, symbol_rate=SYMBOL_RATE):
                 k_coarse=0.00125, spread_min=1.6, spread_max=2.4)
 
 
-def c4fm_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False, tsbk=False, lc=False, es=False, erasures=False):
+def c4fm_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False, tsbk=False, lc=False, es=False, erasures=False, nid=False):
     """the whole C4FM chain up to the slicer on channel `chan_id` of Frontend `fe`: the front half, then the symbol loop
     (p25_control_demod.py:118-135).  Returns the pre-filter channel's id: chan_read_fsk4 on it gives soft dibits at
     symbol_rate (slice_dibits turns them into dibits), chan_fsk4_state its offset estimate (`coarse`).  hard=True also
     attaches the slicer behind the loop: chan_read_hard gives packed dibits, chan_read_sync where FRAME_SYNC ends; with
     tsbk=True as well the TSBK stage behind the slicer (chan_read_tsbk, tsdu_frames), or with lc=True the voice-channel
-    stage (chan_read_p25lc, voice_units; es / erasures: its options, Frontend.chan_p25lc); the two exclude each other (ValueError)."""
+    stage (chan_read_p25lc, voice_units; es / erasures: its options, Frontend.chan_p25lc); the two exclude each other (ValueError).  nid=True: either stage decodes the NID's BCH word first (nid_decode is the host form)."""
     _one_decoder(tsbk, lc)
     cid = c4fm_front_half(fe, chan_id, channel_rate, symbol_rate)
     fe.chan_fsk4(cid, **fsk4_params(channel_rate, symbol_rate))
     if hard:
-        _hard(fe, cid, native.READ_FSK4, tsbk, lc, es, erasures)
+        _hard(fe, cid, native.READ_FSK4, tsbk, lc, es, erasures, nid)
     return cid
 
 

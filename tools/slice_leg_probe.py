@@ -1,9 +1,9 @@
 """The RCF_T_SLICE leg per block with 256 channels behind one 4800-baud C4FM carrier (400 kS/s front-end, 25 kS/s channels, blocks
 of 16000 samples = 192 symbols a channel): slicers alone, with the TSBK stage on TSDUs sent back to back, with the P25 voice stage
 on LDU1 / LDU2 sent back to back -- as it always was (p25lc), with LDU2's encryption sync decoded (p25lc+es) and with erasures as
-well (p25lc+es+er).  The package directory names the tree whose rcf package (and librcf.so) is measured, so that a
+well (p25lc+es+er); +nid on tsbk or p25lc decodes the NID's BCH word first (RCF_NID_BCH).  The package directory names the tree whose rcf package (and librcf.so) is measured, so that a
 parent commit's build can stand next to this one's in one session; prints one JSON line (profiles/p25lc_slice_leg.json holds them).
-    python tools/slice_leg_probe.py <package dir> <none|tsbk|p25lc|p25lc+es|p25lc+es+er>"""
+    python tools/slice_leg_probe.py <package dir> <none|tsbk|tsbk+nid|p25lc|p25lc+es|p25lc+es+er|p25lc+nid|p25lc+es+er+nid>"""
 import json
 import os
 import sys
@@ -42,7 +42,9 @@ with nat.Frontend(FS, device=0, block_capacity=BLK) as fe:
         fe.chan_fsk4(c, **p25.fsk4_params(CR, 4800))
         fe.chan_slicer(c, nat.READ_FSK4, nat.SLICE_FSK4, p25.SLICER_LEVELS, p25.FRAME_SYNC, 48, 4)
         if STAGE == "tsbk":
-            fe.chan_tsbk(c)
+            fe.chan_tsbk(c, **({"nid": True} if "nid" in OPTIONS else {}))                                    # (no option: a parent's binding too)
+        elif STAGE == "p25lc" and "nid" in OPTIONS:
+            fe.chan_p25lc_ex(c, es="es" in OPTIONS, erasures="er" in OPTIONS, nid=True)
         elif STAGE == "p25lc":
             fe.chan_p25lc(c, **({"es": "es" in OPTIONS, "erasures": "er" in OPTIONS} if OPTIONS else {}))     # (no option: a parent's binding too)
         cids.append(c)
