@@ -260,6 +260,30 @@ def with_erasures_and_errors(kind, words, e, v, rng, wrong=True):
     return words
 
 
+def symbol_error_word(kind, word, value, half=0):
+    """the valid inner word whose hexbit is `word`'s xor `value` (1 .. 63); half: which of a (24,12) word's two hexbits"""
+    assert 1 <= value <= 63
+    wk = WORDS_KIND[kind]
+    if wk == TLC:
+        return R.golay24_encode((word >> 12) ^ value << (0 if half else 6))
+    d = (word >> (R.WORD_BITS[wk] - 6)) ^ value
+    return R.golay18_encode(d) if wk == HDU else R.hamming_encode(d)
+
+
+def with_erasures_and_errors_at(kind, words, erased, errors, rng, wrong=True):
+    """with_erasures_and_errors with the places given: `erased`, the symbol positions whose inner words are given up (both
+    symbols of a (24,12) word or neither), and `errors`, {symbol position: the value added to it}, outside the erased words"""
+    words = list(words)
+    per = 2 if kind == TLC else 1
+    erased_words = sorted({i // per for i in erased})
+    assert len(erased_words) * per == len(set(erased)) and not {i // per for i in errors} & set(erased_words)
+    for w in erased_words:
+        words[w] = bad_word(kind, words[w], rng, wrong)
+    for i, value in errors.items():
+        words[i // per] = symbol_error_word(kind, words[i // per], value, i % per)
+    return words
+
+
 # the designed stream's units: kind -> (|E|, v) pairs that decode, and pairs beyond the bound
 DESIGN_OK = {LDU2: [(0, 4), (2, 3), (4, 2), (6, 1), (8, 0)], LDU1: [(0, 6), (6, 3), (12, 0)], HDU: [(0, 8), (8, 4), (16, 0)],
              TLC: [(2, 5), (8, 2), (12, 0)]}
