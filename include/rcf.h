@@ -935,6 +935,68 @@ int64_t rcf_pfb_fm_lost(rcf_t *h);
  * relative frame i sits at fm_ring[(i & (capacity - 1)) n_bins + k].  Order reads on rcf_stream(h) after rcf_sync / an event. */
 int rcf_pfb_fm_ring(rcf_t *h, void **fm_ring, size_t *capacity_frames, int64_t *first_frame);
 
+/* ------------------------------------------------------------------ carrier detect (scanning_receiver.py) */
+/*
+ * The reference's conventional-channel ("scanner") system type hangs analog.simple_squelch_cc(system['threshold'], 0.1)
+ * behind a 12.5 kHz channel, polls squelch.unmuted() every 10 ms and calls call_progress(freq), which opens or keeps
+ * alive a logging_receiver (scanning_receiver.py:53,108-113).  Here that block is one more optional stage behind a
+ * channel, and -- what a flowgraph per frequency cannot do -- a stage on EVERY bin of an open filterbank at once: a
+ * band-wide activity map at block latency.  It reports and gates nothing: the IQ stream passes unchanged.
+ * The definition restates GNU Radio 3.8's simple_squelch_cc_impl (unpinned against GNU Radio's own build, like the symbol
+ * loops):
+ *      thr   = pow(10.0, threshold_db / 10)
+ *      p     = (float)(re * re + im * im)          float products, float sum, not contracted; then widened to double
+ *      level = alpha * p + (1 - alpha) * level     filter::single_pole_iir<double,double,double>: double, level 0 at the start
+ *      open  = level >= thr                        per sample; `unmuted` is that comparison for the last sample seen
+ * A NaN level reads as muted and stays NaN; an Inf level stays open (with alpha == 1 the next sample turns it into a
+ * NaN: 0 x Inf, as in GNU Radio).  The call that attached the stage resets it.
+ * Limits: no ramp (simple_squelch_cc has none), no gating of the IQ stream (the reference connects the
+ * block to a null sink and reads unmuted() only).
+ *
+ * Behind a channel: exact, bit for bit the sequential evaluation above, however the stream is cut into blocks.  p == NULL
+ * detaches the stage; calling it again resets the state (level 0, counters 0) from the channel's next output on.  It
+ * reads the channel's IQ ring over each block's new samples, so it serves every channel kind (direct, chained, stage 2 on
+ * a bin, filterbank tap) on one front-end and in a group; a retune keeps it, closing the channel releases it.
+ * RCF_EINVAL: alpha outside (0, 1] or a threshold that is not finite; RCF_ENOCHAN: no such channel; RCF_ESTATE: the
+ * channel exposes its discriminator only (rcf_chan_set_fm_only: no IQ ring) -- and rcf_chan_set_fm_only(on) is refused
+ * (RCF_ESTATE) while the channel carries the stage. */
+typedef struct rcf_squelch_params {
+    double threshold_db;        /* simple_squelch_cc's threshold, dB */
+    double alpha;               /* its filter's alpha, (0, 1]; the reference uses 0.1 */
+} rcf_squelch_params_t;
+int rcf_chan_squelch(rcf_t *h, int chan_id, const rcf_squelch_params_t *p);
+/* the stage's state as of everything queued; syncs the stream.  Indices count the channel's outputs (sample k is the k-th
+ * sample rcf_chan_read_iq ever delivers to a reader that keeps up); -1: none.  RCF_ESTATE without the stage. */
+typedef struct rcf_squelch_state {
+    double level;               /* the filter's output after the last sample seen */
+    int64_t n_seen, n_open;     /* samples seen / of them open, since the stage was (last) attached */
+    int64_t first_open, last_open;      /* index of the first / the last open sample since then */
+    int32_t unmuted;            /* the last sample seen was open */
+    int32_t reserved_;
+} rcf_squelch_state_t;
+int rcf_chan_squelch_state(rcf_t *h, int chan_id, rcf_squelch_state_t *out);
+/* The same stage on every bin of the open filterbank, over each block's new frames of the bins ring (either layout: every
+ * shape rcf_pfb_open accepts).  n == n_bins: one threshold per bin; n == 1: one for all; threshold_db == NULL: off (the
+ * last state stays readable).  Takes effect with the next block; calling it again resets every bin.
+ * The recurrence is cut in time -- segments of rcf_pfb_squelch_segment() frames, each first walked from level 0, then
+ * entered at the level the segments before it leave, carried across a segment by pow(1 - alpha, segment) -- which is exact
+ * up to rounding: a bin's level differs from the sequential evaluation by at most 64 x 2^-53 / alpha, relative (both add
+ * positive terms, commit two roundings of 2^-53 per step and forget them at rate alpha; the factor covers both and the one
+ * pow and one product per segment).  n_open, last_open and the mask are those of the sequential evaluation wherever no
+ * sample's level lies within that distance of its threshold.
+ * RCF_ESTATE: no filterbank open, or the bank writes its discriminator ring only (rcf_pfb_fm_enable mode 2: no bins to
+ * read) -- and mode 2 is refused (RCF_ESTATE) while the stage is on, as it is while a channel reads a bin; mode 1 is
+ * fine.  RCF_EINVAL: n neither 1 nor n_bins, alpha outside (0, 1], a threshold that is not finite. */
+int rcf_pfb_squelch(rcf_t *h, const double *threshold_db, int n, double alpha);
+/* per bin: the level after the last frame, the open frames and the last open frame (index since rcf_pfb_open, as
+ * rcf_pfb_read_bin counts; -1: none) since the stage was (last) switched on, and whether the last frame was open (bin k:
+ * word k / 32, bit k % 32 of unmuted_mask, (n_bins + 31) / 32 words); *frames_seen: frames walked since then.  Any array
+ * may be NULL; n_bins must be the bank's (RCF_EINVAL).  Syncs the stream.  RCF_ESTATE: no bank, or the stage never on. */
+int rcf_pfb_squelch_read(rcf_t *h, double *level, int64_t *n_open, int64_t *last_open, uint32_t *unmuted_mask, int n_bins,
+                         int64_t *frames_seen);
+/* frames per segment of the bank's stage (no device needed) */
+int rcf_pfb_squelch_segment(void);
+
 
 /* ------------------------------------------------------------------ polyphase filterbank */
 /*

@@ -1,5 +1,7 @@
 // rcf_bank.cpp -- C ABI of the polyphase filterbank and the scanner (fft_vector.py + fft_peak_detection.py).
 #include "rcf_plan.h"
+#define RCF_DEVFN static inline
+#include "squelch_core.hpp"    // (squelch_threshold, squelch_a_pow_s)
 
 namespace rcfx {
 
@@ -7,7 +9,7 @@ void pfb_release(rcf_t *h)
 {
     Pfb &p = h->pfb;
     for (void *q : {(void *)p.d_ptaps, (void *)p.d_tw, (void *)p.d_bins, (void *)p.d_fm, (void *)p.d_fm_inc, (void *)p.d_fm_edge,
-                    (void *)p.d_fm_flag, (void *)p.d_fm_err})
+                    (void *)p.d_fm_flag, (void *)p.d_fm_err, (void *)p.sq.d_state, (void *)p.sq.d_z})
         bury(h, q);
     p = Pfb();
 }
@@ -197,6 +199,7 @@ int rcf_pfb_fm_enable(rcf_t *h, int mode, int gr_phase)
                           kv.second->src - RCF_SRC_PFB_BIN0);
                 return RCF_ESTATE;
             }
+        if (p.sq.on) { set_error("the carrier detector (rcf_pfb_squelch) reads the bins ring, which mode 2 stops writing: switch it off first"); return RCF_ESTATE; }
     }
     if (p.fm_mode == 2 && mode != 2)                      // the frames of mode 2 never reached the bins ring: its readers skip them
         for (auto &r : p.rd) r = std::max(r, p.produced);
@@ -298,6 +301,81 @@ int rcf_pfb_fm_ring(rcf_t *h, void **fm_ring, size_t *capacity_frames, int64_t *
     if (fm_ring) *fm_ring = h->pfb.d_fm;
     if (capacity_frames) *capacity_frames = h->out_cap;
     if (first_frame) *first_frame = h->pfb.fm_from;
+    return RCF_OK;
+}
+
+// ---- carrier detect on every bin (squelch.hip)
+int rcf_pfb_squelch_segment(void) { return pfb_squelch_segment(); }
+
+int rcf_pfb_squelch(rcf_t *h, const double *threshold_db, int n, double alpha)
+{
+    if (!h) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    Pfb &p = h->pfb;
+    if (!p.open) { set_error("no filterbank open"); return RCF_ESTATE; }
+    Pfb::Squelch &q = p.sq;
+    if (!threshold_db) {                                       // off: the state stays readable as the last block left it
+        if (q.on) q.until = p.produced;
+        q.on = false;
+        return RCF_OK;
+    }
+    if ((n != 1 && n != p.NB) || !(alpha > 0.0 && alpha <= 1.0)) {
+        set_error("carrier detect: %d thresholds for %d bins (1 or all of them), or alpha %g outside (0, 1]", n, p.NB, alpha);
+        return RCF_EINVAL;
+    }
+    for (int k = 0; k < n; ++k)
+        if (!std::isfinite(threshold_db[k])) { set_error("carrier detect: threshold %d is not finite", k); return RCF_EINVAL; }
+    if (p.fm_mode == 2) { set_error("the bank writes its discriminator ring only (rcf_pfb_fm_enable mode 2): no bins for the carrier detector to read"); return RCF_ESTATE; }
+    // a fresh state on every call: level 0, no bin open, counters 0.  The old one goes once the stream has passed it
+    Pfb::Squelch nq;
+    nq.bins_pad = ((size_t)p.NB + 63) & ~size_t(63);
+    std::vector<double> st0(nq.state_doubles(), 0.0);
+    int64_t *last = reinterpret_cast<int64_t *>(st0.data() + 3 * nq.bins_pad);
+    for (size_t k = 0; k < nq.bins_pad; ++k) {
+        last[k] = -1;
+        st0[4 * nq.bins_pad + k] = squelch_threshold(threshold_db[n == 1 ? 0 : std::min<size_t>(k, (size_t)p.NB - 1)]);
+    }
+    // the z scratch of the largest launch the handle accepts: a block is at most ceil(block_cap / D) frames, and at most out_cap
+    const int64_t max_frames = std::min<int64_t>((int64_t)h->out_cap, ceil_div((int64_t)h->block_cap, p.D));
+    const size_t z_rows = (size_t)ceil_div(max_frames, pfb_squelch_segment());
+    Fresh<double> d_state, d_z;
+    RCF_HIP(d_state.alloc(st0.size()));
+    if (!q.d_z) RCF_HIP(d_z.alloc(z_rows * (size_t)p.NB));
+    if (!hip_ok(hipMemcpy(d_state.p, st0.data(), sizeof(double) * st0.size(), hipMemcpyHostToDevice), "hipMemcpy(carrier detect state)")) return RCF_EHIP;
+    nq.on = true;
+    nq.alpha = alpha;
+    nq.a_pow_s = squelch_a_pow_s(alpha, pfb_squelch_segment());
+    nq.d_z = q.d_z ? q.d_z : d_z.take();
+    nq.d_state = d_state.take();
+    nq.from = p.produced;
+    bury(h, q.d_state);
+    q = nq;
+    return RCF_OK;
+}
+
+int rcf_pfb_squelch_read(rcf_t *h, double *level, int64_t *n_open, int64_t *last_open, uint32_t *unmuted_mask, int n_bins,
+                         int64_t *frames_seen)
+{
+    if (!h) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    Pfb &p = h->pfb;
+    if (!p.open) { set_error("no filterbank open"); return RCF_ESTATE; }
+    const Pfb::Squelch &q = p.sq;
+    if (!q.d_state) { set_error("the bank carries no carrier detector (rcf_pfb_squelch)"); return RCF_ESTATE; }
+    if (n_bins != p.NB) { set_error("carrier detect: %d bins asked for, the bank has %d", n_bins, p.NB); return RCF_EINVAL; }
+    std::vector<double> st(q.state_doubles());
+    RCF_HIP(hipMemcpyAsync(st.data(), q.d_state, sizeof(double) * st.size(), hipMemcpyDeviceToHost, h->stream));
+    RCF_HIP(hipStreamSynchronize(h->stream));
+    free_graveyard_idle(h);
+    const size_t nb = (size_t)p.NB;
+    if (level) std::memcpy(level, st.data() + (size_t)q.cur * q.bins_pad, sizeof(double) * nb);
+    if (n_open) std::memcpy(n_open, st.data() + 2 * q.bins_pad, sizeof(int64_t) * nb);
+    if (last_open) std::memcpy(last_open, st.data() + 3 * q.bins_pad, sizeof(int64_t) * nb);
+    if (unmuted_mask) std::memcpy(unmuted_mask, st.data() + 5 * q.bins_pad, sizeof(uint32_t) * ((nb + 31) / 32));
+    // (off: the count stands where the detector was switched off)
+    if (frames_seen) *frames_seen = (q.on ? p.produced : q.until) - q.from;
     return RCF_OK;
 }
 

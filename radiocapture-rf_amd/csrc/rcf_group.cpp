@@ -11,7 +11,7 @@
 //   pfb_group_kernel_* / pfb5_group_kernel / pfbm_group_kernel   the chunks of every member of one bank shape   (pfb.hip, pfb5.hip, pfbm.hip)
 //   fir_small_kernel / fir_bank_kernel       stage-2 channels of all members of one (D, T) class (records concatenated)
 //   tap_finalize_group_kernel  the tapped bins of every member                               (tapfin.hip)
-//   disc / rot_fill, and the tail stages (TailStages, rcf_plan.h: fm_fir / agc / clock_mm / costas / fsk4 / slice / tsbk / edacs / osw / p25lc)   records
+//   disc / rot_fill, and the tail stages (TailStages, rcf_plan.h: fm_fir / agc / clock_mm / costas / fsk4 / slice / tsbk / edacs / osw / p25lc / squelch)   records
 //                              concatenated: the group's table is the members' tables appended
 //   gather_rings_kernel        the read: new output of any channels of any members -> pinned host memory, one launch
 // What is not concatenable (matrix-core banks with their per-handle tap slabs, voice chains, scans, banks that still see
@@ -329,6 +329,7 @@ int launch_block(GroupBlock &b, bool wait)
         else launch_banks_alone(b, bg.idx);
     }
     launch_banks_alone(b, b.bank_singles);
+    for (size_t i = 0; i < b.size(); ++i) launch_member_pfb_squelch(b.member(i), *b.plans[i], st);
     if (b.d_tap_args) {
         Timed t(h0, RCF_T_TAPS);
         launch_tap_finalize_group(b.d_tap_args, (int)b.tap_args.size(), b.tap_max_taps, b.tap_max_rows, h0->ring_mask, h0->d_atan, st);

@@ -417,6 +417,43 @@ struct P25lcLaunch : FramesLaunch<P25lcState> {
     uint32_t flags;          // bit 0: the stage's `correct`; from bit 1 on the options of rcf_chan_p25lc_opt (kP25lcFlagEs, kP25lcFlagErasures); kNidFlagBch
 };
 void launch_p25lc(const P25lcLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
+// Carrier detect behind a channel (squelch.hip; GNU Radio's simple_squelch_cc as the reference's scanning_receiver.py:53 hangs
+// it behind a 12.5 kHz channel; definition: include/rcf.h at rcf_chan_squelch).
+// per-channel running state, device resident, owned by squelch_kernel
+struct SquelchState {
+    double level;            // single_pole_iir<double>'s output after the last sample seen
+    int64_t n_seen, n_open;  // samples walked / of them open, since the stage was (last) attached
+    int64_t first_open, last_open;   // relative channel output index of the first / the last open sample, -1: none
+    int32_t unmuted;         // the last sample seen was open
+    int32_t pad_;
+};
+struct SquelchLaunch {
+    const float2 *iq_ring;
+    SquelchState *st;
+    int64_t n_lo;            // first relative channel output index that is new in this launch
+    int32_t n_k;
+    int32_t pad_;
+    double thr, alpha;       // pow(10, threshold_db / 10), the filter's alpha
+};
+void launch_squelch(const SquelchLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
+// ... and on every bin of a filterbank (rcf_pfb_squelch): one record per block, a kernel argument.  The state is one
+// allocation of bins_pad = bins rounded up to 64 items per array: level x 2 | n_open | last_open | thr | the unmuted mask
+struct PfbSquelchLaunch {
+    const float2 *bins_ring; // PfbLaunch's, in its layout
+    const double *level_in;  // [bins_pad] the levels before this launch ...
+    double *level_out;       // ... and behind it: the state's two level arrays take turns (a launch's segments all read level_in)
+    int64_t *n_open, *last_open;     // [bins_pad]; last_open: relative frame index, -1: none
+    const double *thr;       // [bins_pad]
+    uint32_t *mask;          // [bins_pad / 32] bin k: word k / 32, bit k % 32
+    double *z;               // [segments - 1][n_bins] zero-state responses of the launch's whole segments
+    uint64_t ring_mask;
+    int64_t tile_pitch;
+    int64_t i_lo;            // first relative frame index (frame - n_abs0) of this launch
+    double alpha, a_pow_s;   // a_pow_s = pow(1 - alpha, kSquelchSegment)
+    int32_t n_frames, n_bins, frame_major, pad_;
+};
+void launch_pfb_squelch(const PfbSquelchLaunch &p, hipStream_t s);
+int pfb_squelch_segment();
 // the records' layouts as the kernels were compiled for them
 #pragma GCC diagnostic push
 #pragma GCC diagnostic ignored "-Winvalid-offsetof"

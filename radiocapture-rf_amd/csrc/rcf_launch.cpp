@@ -47,6 +47,7 @@ void launch_tail(rcf_t *h, const DiscJob *disc, size_t n_disc, const TailStages 
     }
     TailStages::each([&](int timing_class, auto launch, const auto &s) {
         if (!s.dev) return;
+        if (timing_class == kNoTimingClass) { launch_stage(s, launch, h->ring_mask, st); return; }
         Timed tm(h, timing_class);
         launch_stage(s, launch, h->ring_mask, st);
     }, t);
@@ -57,6 +58,29 @@ void launch_member_audio(rcf_t *h, const BlockPlan &bp, hipStream_t st)
     if (!bp.d_audf) return;
     Timed t(h, RCF_T_AUDIO);
     launch_audio(bp.d_audf, (int)bp.audf.size(), bp.audf_max_n, bp.audf_num, bp.audf_den, h->ring_mask, h->d_atan, st);
+}
+
+// The carrier detector of every bin (rcf_pfb_squelch) over the frames the bank's launch of this block wrote.  The record is a
+// kernel argument, built here: which of the state's two level arrays holds the levels is a fact of the LAUNCH order (a
+// planned block that is taken back never gets here).
+void launch_member_pfb_squelch(rcf_t *h, const BlockPlan &bp, hipStream_t st)
+{
+    if (!bp.run_pfb_squelch) return;
+    Pfb::Squelch &q = h->pfb.sq;
+    const PfbLaunch &pl = bp.pl;
+    PfbSquelchLaunch p{};
+    p.bins_ring = pl.bins_ring;
+    p.level_in = q.level(q.cur);
+    p.level_out = q.level(q.cur ^ 1);
+    p.n_open = q.n_open(); p.last_open = q.last_open(); p.thr = q.thr(); p.mask = q.mask();
+    p.z = q.d_z;
+    p.ring_mask = pl.ring_mask;
+    p.tile_pitch = pl.tile_pitch;
+    p.i_lo = pl.n_lo - pl.n_abs0;
+    p.alpha = q.alpha; p.a_pow_s = q.a_pow_s;
+    p.n_frames = pl.n_frames; p.n_bins = pl.NB; p.frame_major = pl.frame_major;
+    launch_pfb_squelch(p, st);
+    q.cur ^= 1;
 }
 
 // upload all launch parameters in one copy, then launch in dependency order
@@ -120,6 +144,7 @@ int launch_plan(rcf_t *h, BlockPlan &bp)
     if (!bp.fir_by_depth.empty())
         for (auto &j : bp.fir_by_depth[0]) launch_fir_job(h, j, j.dims.mfma ? RCF_T_FIR_MFMA : RCF_T_FIR, st);
     if (bp.run_pfb) { TimedAttached t(h, RCF_T_PFB, pl); launch_pfb(bp.shape, pl, bp.pfb_zero_history, st, sr.n_wgs ? &sr : nullptr); }
+    launch_member_pfb_squelch(h, bp, st);
     if (bp.run_pfb && pl.n_taps > 0) {
         Timed t(h, RCF_T_TAPS);
         launch_tap_finalize(bp.d_tap_list, pl.n_taps, pl.tap_mat, pl.tap_pitch, pl.n_frames, pl.n_lo - pl.n_abs0,

@@ -203,6 +203,7 @@ int plan_pfb(rcf_t *h, BlockPlan &bp)
             bp.shape = p.shape;
             bp.pfb_zero_history = pfb_zero_history(p.shape, n_lo, p.start_sample, p.fm_mode ? p.shape.chunk_frames : 0);
             run_pfb = true;
+            bp.run_pfb_squelch = p.sq.on;
             p.produced = n_hi - p.n_abs0 + 1;
         }
     }
@@ -362,6 +363,7 @@ int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c)
                 bp.tails.of<decltype(fr)>().add(fr);
             });
     }
+    if (c->squelch) stage(c->squelch->rec, c->squelch->from, bp.tails.sqf);
     if (c->audio && s.a_n > 0) {
         AudioLaunch al = c->audio->rec;
         al.n_lo = s.a_lo;

@@ -1,5 +1,5 @@
 // rcf_plan.h -- the per-block schedule: what one commit of one front-end launches, built on the host first.  The stages
-// behind the FIRs (symbol filters, AGCs, the three symbol loops, the slicers behind the loops, the TSBK, EDACS, OSW and P25 voice stages behind the slicers) are one table, TailStages: a block's plan and a group's
+// behind the FIRs (symbol filters, AGCs, the three symbol loops, the slicers behind the loops, the TSBK, EDACS, OSW and P25 voice stages behind the slicers, the carrier detectors) are one table, TailStages: a block's plan and a group's
 // block each hold one, and the planner, the group's merge and the launcher visit it through TailStages::each.
 #pragma once
 #include <chrono>
@@ -79,7 +79,9 @@ struct AgcRecs : StageRecs<AgcLaunch> {
 };
 
 // The stages that follow the derived FIRs and the discriminators, in launch order.  each() is the one list of them: it
-// calls f(timing class, launcher, the stage of every table given).
+// calls f(timing class, launcher, the stage of every table given).  kNoTimingClass: the stage's launch is not timed
+// (RCF_T_COUNT is the ABI's).
+constexpr int kNoTimingClass = -1;
 struct TailStages {
     StageRecs<FmFirLaunch> symf;       // symbol filters: they read the rings the discriminators wrote
     AgcRecs agcf;                      // feedforward AGCs
@@ -91,6 +93,7 @@ struct TailStages {
     StageRecs<EdacsLaunch> edf;        // EDACS control frames, behind the slicers likewise
     StageRecs<OswLaunch> osf;          // SmartNet OSWs, behind the slicers likewise
     StageRecs<P25lcLaunch> lcf;        // P25 voice data units, behind the slicers likewise
+    StageRecs<SquelchLaunch> sqf;      // carrier detect: it reads the IQ rings the FIRs and the tap finalize wrote
     template <class F, class... T> static void each(F &&f, T &...t)
     {
         f(RCF_T_DISC, launch_fm_fir, t.symf...);
@@ -103,6 +106,7 @@ struct TailStages {
         f(RCF_T_SLICE, launch_edacs, t.edf...);
         f(RCF_T_SLICE, launch_osw, t.osf...);
         f(RCF_T_SLICE, launch_p25lc, t.lcf...);
+        f(kNoTimingClass, launch_squelch, t.sqf...);
     }
     template <class Rec> StageRecs<Rec> &of()      // the stage whose records are plain StageRecs<Rec>: found at compile time
     {
@@ -158,6 +162,7 @@ struct BlockPlan {
     int audf_num = 1, audf_den = 1;
     PfbLaunch pl{};
     bool run_pfb = false;
+    bool run_pfb_squelch = false;      // the bank carries the carrier detector (rcf_pfb_squelch): two launches behind the bank's
     PfbShape shape;                    // run_pfb: the bank's shape, and whether this launch still reaches before its start
     bool pfb_zero_history = false;     // (plan_pfb; with the fused discriminator: of the launch and its halo chunk)
     const TapLaunch *d_tap_list = nullptr;
@@ -225,6 +230,7 @@ void launch_fir_job(rcf_t *h, FirJob &j, int timing_class, hipStream_t st);   //
 // what follows the derived FIRs: one discriminator launch per job, then the uploaded stages of t
 void launch_tail(rcf_t *h, const DiscJob *disc, size_t n_disc, const TailStages &t, hipStream_t st);
 void launch_member_audio(rcf_t *h, const BlockPlan &bp, hipStream_t st);
+void launch_member_pfb_squelch(rcf_t *h, const BlockPlan &bp, hipStream_t st);   // behind the bank's launch, single or grouped
 int run_scan(rcf_t *h, const BlockPlan &bp);
 int finish_block(rcf_t *h, const BlockPlan &bp);
 

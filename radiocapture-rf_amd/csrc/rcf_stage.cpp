@@ -17,6 +17,7 @@
 #include "osw_core.hpp"        // (kOswSyncBits, kOswRecWords)
 #include "p25lc_core.hpp"      // (kP25lcRecWords, kP25lcFlagCorrect)
 #include "nid_core.hpp"        // (kNidFlagBch)
+#include "squelch_core.hpp"    // (squelch_threshold)
 static_assert(rcfx::kP25lcFlagEs == RCF_P25LC_ES << 1 && rcfx::kP25lcFlagErasures == RCF_P25LC_ERASURES << 1, "the options travel in P25lcLaunch::flags behind kP25lcFlagCorrect");
 
 namespace rcfx {
@@ -30,6 +31,7 @@ void Chan::Slicer::release(rcf_t *h)                 // one allocation; the fram
     bury(h, rec.word_ring);
     rec = SliceLaunch{};
 }
+void Chan::Squelch::release(rcf_t *h) { bury(h, rec.st); rec = SquelchLaunch{}; }
 void Chan::Audio::release(rcf_t *h) { bury(h, rec.st); bury(h, rec.a_ring); bury(h, const_cast<float *>(rec.lpf)); rec = AudioLaunch{}; }
 
 }  // namespace rcfx
@@ -553,6 +555,53 @@ int rcf_chan_p25lc_state(rcf_t *h, int chan_id, rcf_p25lc_state_t *out)
     const int rc = frames_state<Chan::Slicer::P25lc>(h, chan_id, out, &st);
     if (rc != RCF_OK) return rc;
     out->n_records = st.n_records; out->n_frames = st.n_frames; out->n_decoded = st.n_decoded; out->n_rs_bad = st.n_rs_bad; out->n_lost = st.n_lost;
+    return RCF_OK;
+}
+
+// ---- carrier detect over the IQ stream (squelch.hip)
+int rcf_chan_squelch(rcf_t *h, int chan_id, const rcf_squelch_params_t *p)
+{
+    if (!h) return RCF_EINVAL;
+    if (p && (!std::isfinite(p->threshold_db) || !(p->alpha > 0.0 && p->alpha <= 1.0))) {
+        set_error("carrier detect: threshold %g dB is not finite, or alpha %g outside (0, 1]", p->threshold_db, p->alpha);
+        return RCF_EINVAL;
+    }
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!p) return stage_off(h, c->squelch);
+    if (c->fm_only) { set_error("channel %d exposes its discriminator only: the carrier detector reads IQ", chan_id); return RCF_ESTATE; }
+    std::unique_ptr<Chan::Squelch> k(new Chan::Squelch);
+    SquelchLaunch &r = k->rec;
+    r.iq_ring = c->d_iq;
+    r.thr = squelch_threshold(p->threshold_db);
+    r.alpha = p->alpha;
+    SquelchState st0{};
+    st0.first_open = st0.last_open = -1;
+    Fresh<SquelchState> d_state;
+    RCF_HIP(d_state.alloc(1));
+    if (!hip_ok(hipMemcpy(d_state.p, &st0, sizeof(st0), hipMemcpyHostToDevice), "hipMemcpy(carrier detect state)")) return RCF_EHIP;
+    r.st = d_state.take();
+    k->from = c->pos.produced;                                   // a new GR block: level 0 from the channel's next output on
+    drop_stage(h, c->squelch);
+    c->squelch = std::move(k);
+    ++h->chans_epoch;
+    return RCF_OK;
+}
+
+int rcf_chan_squelch_state(rcf_t *h, int chan_id, rcf_squelch_state_t *out)
+{
+    if (!h || !out) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!c->squelch) { set_error("channel %d has no carrier detector (rcf_chan_squelch)", chan_id); return RCF_ESTATE; }
+    SquelchState st{};
+    const int rc = stage_state(h, c->squelch->rec.st, &st, sizeof(st));
+    if (rc != RCF_OK) return rc;
+    out->level = st.level;
+    out->n_seen = st.n_seen; out->n_open = st.n_open; out->first_open = st.first_open; out->last_open = st.last_open;
+    out->unmuted = st.unmuted;
     return RCF_OK;
 }
 

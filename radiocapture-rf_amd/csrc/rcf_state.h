@@ -213,8 +213,17 @@ struct Chan {
         size_t reach() const { return 0; }                               // it reads the loop's ring, never the channel's
         void release(rcf_t *h);
     };
+    // Carrier detect over the IQ stream (rcf_chan_squelch): simple_squelch_cc's level and what it opened.  It writes no ring
+    // and has no reader: its state record (one allocation, rec.st) is the result.  A second call: a new state, `from` = `produced`
+    struct Squelch {
+        SquelchLaunch rec{};            // owns st
+        int64_t from = 0;
+        size_t reach() const { return 0; }                               // the level is in the state record: no look-back
+        void release(rcf_t *h);
+    };
     std::unique_ptr<Audio> audio;
     std::unique_ptr<Slicer> slicer;
+    std::unique_ptr<Squelch> squelch;
     // the one list of them: f(the stage's holder -- null when the channel has no such stage --, the bytes of its launch
     // record, whether its reach() is into rings of its own instead of the channel's)
     template <class F> void for_each_stage(F &&f)
@@ -222,6 +231,7 @@ struct Chan {
         f(sym, sizeof(FmFirLaunch), false); f(agc, sizeof(AgcLaunch), false); f(clock, sizeof(ClockLaunch), false);
         f(costas, sizeof(CostasLaunch), false); f(fsk4, sizeof(Fsk4Launch), false); f(audio, sizeof(AudioLaunch), true);
         f(slicer, sizeof(SliceLaunch) + Slicer::max_frames_launch() + 64, false);    // (with the frame decoder it may carry)
+        f(squelch, sizeof(SquelchLaunch), false);
     }
     // ---- the rest
     float incr[2] = {1.f, 0.f};   // exact rotator: what GNU Radio iterates
@@ -234,7 +244,7 @@ struct Chan {
 #pragma GCC diagnostic push
 #pragma GCC diagnostic ignored "-Winvalid-offsetof"
 static_assert(offsetof(Chan, pos) + sizeof(Chan::Pos) <= 192, "what plan_channel advances: inside the first three cache lines");
-static_assert(offsetof(Chan, slicer) + sizeof(std::unique_ptr<Chan::Slicer>) <= 256, "what plan_channel reads: inside the four prefetched lines");
+static_assert(offsetof(Chan, squelch) + sizeof(std::unique_ptr<Chan::Squelch>) <= 256, "what plan_channel reads: inside the four prefetched lines");
 #pragma GCC diagnostic pop
 
 struct Pfb {
@@ -262,6 +272,23 @@ struct Pfb {
     int fm_local = 0;              // the hand-over stays in one XCD's L2 (pfb5_xcd_map_ok said so)
     uint64_t fm_serial = 0;        // launches so far (the flags' tags)
     std::vector<int64_t> rd_fm;    // per-bin read cursors
+    // carrier detect on every bin (rcf_pfb_squelch): one state allocation of bins_pad = NB rounded up to 64 items per array,
+    // level x 2 | n_open | last_open | thr | mask (PfbSquelchLaunch), and the z scratch of the largest launch the handle accepts
+    struct Squelch {
+        bool on = false;
+        double alpha = 0, a_pow_s = 0;
+        double *d_state = nullptr, *d_z = nullptr;
+        size_t bins_pad = 0;
+        int cur = 0;               // which level array holds the levels as of everything queued (a launch flips it)
+        int64_t from = 0;          // first relative frame it saw, or will see
+        int64_t until = 0;         // (off) the frame it was switched off at
+        double *level(int which) const { return d_state + (size_t)which * bins_pad; }
+        int64_t *n_open() const { return reinterpret_cast<int64_t *>(d_state + 2 * bins_pad); }
+        int64_t *last_open() const { return reinterpret_cast<int64_t *>(d_state + 3 * bins_pad); }
+        double *thr() const { return d_state + 4 * bins_pad; }
+        uint32_t *mask() const { return reinterpret_cast<uint32_t *>(d_state + 5 * bins_pad); }
+        size_t state_doubles() const { return 5 * bins_pad + bins_pad / 64; }
+    } sq;
 };
 
 struct Scan {

@@ -49,6 +49,7 @@ SYMBOLS = [
     "rcf_allgather_peaks", "rcf_allreduce_max", "rcf_pfb_tap_open", "rcf_chan_set_fm_only", "rcf_pfb_shape_supported", "rcf_pfb_shape_family",
     "rcf_pfb_tap_leakage", "rcf_set_rotator", "rcf_timing_stride", "rcf_set_stage2_lag",
     "rcf_group_open", "rcf_group_close", "rcf_group_size", "rcf_group_push", "rcf_group_commit", "rcf_group_read_many",
+    "rcf_chan_squelch", "rcf_chan_squelch_state", "rcf_pfb_squelch", "rcf_pfb_squelch_read", "rcf_pfb_squelch_segment",
     "rcf_group_sync", "rcf_pump_start", "rcf_pump_stats", "rcf_pump_written", "rcf_pump_read", "rcf_pump_read_many", "rcf_pump_subscribe", "rcf_pump_unsubscribe", "rcf_pump_stop",
 ]
 FMT_CF32, FMT_U8, FMT_S8, FMT_S16 = 0, 1, 2, 3
@@ -163,6 +164,17 @@ def fsk4_params_struct(sample_rate, symbol_rate, k_spread, k_timing, k_fine, k_c
     if taps is not None:
         p.interp_taps = taps.ctypes.data_as(C.POINTER(C.c_float))
     return p, taps
+
+
+class SquelchParams(C.Structure):
+    """rcf_squelch_params_t (include/rcf.h)"""
+    _fields_ = [("threshold_db", C.c_double), ("alpha", C.c_double)]
+
+
+class SquelchState(C.Structure):
+    """rcf_squelch_state_t (include/rcf.h)"""
+    _fields_ = [("level", C.c_double), ("n_seen", C.c_int64), ("n_open", C.c_int64), ("first_open", C.c_int64),
+                ("last_open", C.c_int64), ("unmuted", C.c_int32), ("reserved_", C.c_int32)]
 
 
 class SlicerParams(C.Structure):
@@ -409,6 +421,12 @@ def lib():
         "rcf_pfb_read_bin": (i64, [vp, C.c_int, fp, sz]),
         "rcf_pfb_fm_enable": (C.c_int, [vp, C.c_int, C.c_int]),
         "rcf_pfb_read_fm": (i64, [vp, C.c_int, C.c_float, fp, sz]),
+        "rcf_chan_squelch": (C.c_int, [vp, C.c_int, C.POINTER(SquelchParams)]),
+        "rcf_chan_squelch_state": (C.c_int, [vp, C.c_int, C.POINTER(SquelchState)]),
+        "rcf_pfb_squelch": (C.c_int, [vp, C.POINTER(C.c_double), C.c_int, C.c_double]),
+        "rcf_pfb_squelch_read": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_uint32), C.c_int,
+                                           C.POINTER(i64)]),
+        "rcf_pfb_squelch_segment": (C.c_int, []),
         "rcf_pfb_fm_ring": (C.c_int, [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(i64)]),
         "rcf_pfb_fm_lost": (i64, [vp]),
         "rcf_pfb_rings": (C.c_int, [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz)]),
@@ -502,6 +520,11 @@ def _check(rc):
 
 def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def pfb_squelch_segment() -> int:
+    """frames per segment of the bank's carrier detector (rcf_pfb_squelch_segment; no device needed)"""
+    return lib().rcf_pfb_squelch_segment()
 
 
 def device_count() -> int:
@@ -1011,6 +1034,23 @@ class Frontend:
         """unread soft symbols of the channel's C4FM loop (+-1, +-3 on a locked signal), oldest first"""
         return self._read_ring(lib().rcf_chan_read_fsk4, cid, max_symbols, np.float32)
 
+    def chan_squelch(self, cid, threshold_db, alpha=0.1):
+        """analog.simple_squelch_cc(threshold_db, alpha) as a carrier detector on the channel's IQ stream (rcf_chan_squelch,
+        which defines the stage; scanning_receiver.py:53): it reports and gates nothing.  Level 0 from the channel's next
+        output on, again on every call; threshold_db=None detaches it"""
+        if threshold_db is None:
+            _check(lib().rcf_chan_squelch(self._h, cid, None))
+            return
+        p = SquelchParams(float(threshold_db), float(alpha))
+        _check(lib().rcf_chan_squelch(self._h, cid, C.byref(p)))
+
+    def chan_squelch_state(self, cid) -> dict:
+        """the detector's state as of the last block: level, n_seen, n_open, first_open, last_open (channel-sample indices,
+        -1: none), unmuted (rcf_chan_squelch_state; syncs the stream)"""
+        st = self._state_of(lib().rcf_chan_squelch_state, cid, SquelchState)
+        st.pop("reserved_", None)
+        return st
+
     def chan_slicer(self, cid, source, mode=None, levels=(-2.0, 0.0, 2.0, 4.0), sync_word=0, sync_bits=0, sync_max_errors=0,
                     hit_capacity=0, sync_both=0):
         """hard decisions behind one of the channel's symbol loops (rcf_chan_slicer): source READ_CLOCK / READ_COSTAS /
@@ -1207,6 +1247,31 @@ class Frontend:
         """the discriminator of EVERY bin in the bank's own kernel (rcf_pfb_fm_enable): mode 1 beside the bins ring, 2
         instead of it, 0 off"""
         _check(lib().rcf_pfb_fm_enable(self._h, int(mode), 1 if gr_phase else 0))
+
+    def pfb_squelch(self, threshold_db, alpha=0.1):
+        """the carrier detector on EVERY bin of the open bank (rcf_pfb_squelch): one threshold in dB for all bins or one per
+        bin; None switches it off.  Takes effect with the next block; every call resets every bin"""
+        if threshold_db is None:
+            _check(lib().rcf_pfb_squelch(self._h, None, 0, float(alpha)))
+            return
+        thr = np.ascontiguousarray(np.atleast_1d(threshold_db), dtype=np.float64)
+        _check(lib().rcf_pfb_squelch(self._h, thr.ctypes.data_as(C.POINTER(C.c_double)), len(thr), float(alpha)))
+
+    def pfb_squelch_read(self, n_bins) -> dict:
+        """per bin of the bank's carrier detector: level (float64), n_open and last_open (int64; frame index since pfb_open,
+        -1: none), unmuted (bool, the mask unpacked), and frames_seen (rcf_pfb_squelch_read; syncs the stream)"""
+        n_bins = int(n_bins)
+        level = np.empty(n_bins, np.float64)
+        n_open, last_open = np.empty(n_bins, np.int64), np.empty(n_bins, np.int64)
+        mask = np.zeros((n_bins + 31) // 32, np.uint32)
+        seen = C.c_int64()
+        p64 = C.POINTER(C.c_int64)
+        _check(lib().rcf_pfb_squelch_read(self._h, level.ctypes.data_as(C.POINTER(C.c_double)), n_open.ctypes.data_as(p64),
+                                          last_open.ctypes.data_as(p64), mask.ctypes.data_as(C.POINTER(C.c_uint32)), n_bins,
+                                          C.byref(seen)))
+        unmuted = (mask[np.arange(n_bins) // 32] >> (np.arange(n_bins) % 32).astype(np.uint32)) & 1
+        return dict(level=level, n_open=n_open, last_open=last_open, unmuted=unmuted.astype(bool), mask=mask,
+                    frames_seen=seen.value)
 
     def pfb_fm_lost(self):
         return _check(lib().rcf_pfb_fm_lost(self._h))
