@@ -273,7 +273,8 @@ int64_t rcf_chan_read_fm(rcf_t *h, int chan_id, float gain, float *out, size_t m
 #define RCF_READ_AUDIO   20   /* float32 audio of the voice chain */
 /* The two streams of rcf_chan_slicer, batched the same way: out = uint32[n_chans][cap_each], gain ignored, RCF_ESTATE for a
  * channel without the stage; the reader positions are those of rcf_chan_read_hard / rcf_chan_read_sync.  They are not float
- * streams and the real-time pump does not deliver them (rcf_pump_start / rcf_pump_subscribe: RCF_EINVAL). */
+ * streams: rcf_pump_start and rcf_pump_subscribe refuse them (RCF_EINVAL), the real-time pump delivers them through
+ * rcf_pump_subscribe_hard. */
 #define RCF_HARD_BITS    32   /* uint32 words of packed decisions */
 #define RCF_HARD_SYNC    33   /* uint32 sync hits, (distance << 26) | (k & 0x3ffffff) */
 int rcf_chan_read_many(rcf_t *h, int what, const int *chan_ids, int n_chans, float gain, void *out, size_t cap_each,
@@ -630,7 +631,8 @@ typedef struct rcf_tsbk_state {
 } rcf_tsbk_state_t;
 int rcf_chan_tsbk_state(rcf_t *h, int chan_id, rcf_tsbk_state_t *out);
 /* unread records, oldest first: out = uint32[max_records][8] (one round trip); RCF_HARD_TSBK names the stream to
- * rcf_chan_read_many and rcf_group_read_many (out = uint32[n_chans][cap_each][8]); the pump does not deliver it */
+ * rcf_chan_read_many and rcf_group_read_many (out = uint32[n_chans][cap_each][8]); the pump delivers it
+ * through rcf_pump_subscribe_hard */
 #define RCF_HARD_TSBK    48
 int64_t rcf_chan_read_tsbk(rcf_t *h, int chan_id, uint32_t *out, size_t max_records);
 /* device pointer of the record ring and its capacity in records (zero-copy): record i lives at word 8 (i & (capacity - 1)) */
@@ -695,7 +697,8 @@ typedef struct rcf_edacs_state {
 } rcf_edacs_state_t;
 int rcf_chan_edacs_state(rcf_t *h, int chan_id, rcf_edacs_state_t *out);
 /* unread records, oldest first: out = uint32[max_records][8] (one round trip); RCF_HARD_EDACS names the stream to
- * rcf_chan_read_many and rcf_group_read_many (out = uint32[n_chans][cap_each][8]); the pump does not deliver it */
+ * rcf_chan_read_many and rcf_group_read_many (out = uint32[n_chans][cap_each][8]); the pump delivers it
+ * through rcf_pump_subscribe_hard */
 #define RCF_HARD_EDACS   49
 int64_t rcf_chan_read_edacs(rcf_t *h, int chan_id, uint32_t *out, size_t max_records);
 /* device pointer of the record ring and its capacity in records (zero-copy): record i lives at word 8 (i & (capacity - 1)) */
@@ -763,7 +766,8 @@ typedef struct rcf_osw_state {
 } rcf_osw_state_t;
 int rcf_chan_osw_state(rcf_t *h, int chan_id, rcf_osw_state_t *out);
 /* unread records, oldest first: out = uint32[max_records][8] (one round trip); RCF_HARD_OSW names the stream to
- * rcf_chan_read_many and rcf_group_read_many (out = uint32[n_chans][cap_each][8]); the pump does not deliver it */
+ * rcf_chan_read_many and rcf_group_read_many (out = uint32[n_chans][cap_each][8]); the pump delivers it
+ * through rcf_pump_subscribe_hard */
 #define RCF_HARD_OSW     51   /* (50 stays unassigned: the readers refuse it as an unknown stream) */
 int64_t rcf_chan_read_osw(rcf_t *h, int chan_id, uint32_t *out, size_t max_records);
 /* device pointer of the record ring and its capacity in records (zero-copy): record i lives at word 8 (i & (capacity - 1)) */
@@ -863,7 +867,8 @@ typedef struct rcf_p25lc_state {
 } rcf_p25lc_state_t;
 int rcf_chan_p25lc_state(rcf_t *h, int chan_id, rcf_p25lc_state_t *out);
 /* unread records, oldest first: out = uint32[max_records][8] (one round trip); RCF_HARD_P25LC names the stream to
- * rcf_chan_read_many and rcf_group_read_many (out = uint32[n_chans][cap_each][8]); the pump does not deliver it */
+ * rcf_chan_read_many and rcf_group_read_many (out = uint32[n_chans][cap_each][8]); the pump delivers it
+ * through rcf_pump_subscribe_hard */
 #define RCF_HARD_P25LC   53   /* (52 stays unassigned like 50: the readers refuse both as unknown streams) */
 int64_t rcf_chan_read_p25lc(rcf_t *h, int chan_id, uint32_t *out, size_t max_records);
 /* device pointer of the record ring and its capacity in records (zero-copy): record i lives at word 8 (i & (capacity - 1)) */
@@ -1236,7 +1241,9 @@ int64_t rcf_pump_written(rcf_pump_t *p, int entry);
  * loses the oldest (as a PUB socket at its HWM does) */
 int64_t rcf_pump_read(rcf_pump_t *p, int entry, int64_t *cursor, void *out, size_t max_items);
 /* rcf_pump_read for n slots at once: slot entries[i] from cursors[i] on into out + i * cap_each * 8 bytes (cf32 pairs, or
- * floats in the first half of the row), counts[i] items (-1: no such slot) */
+ * floats in the first half of the row), counts[i] items (-1: no such slot).  Row i stays at out + i * cap_each * 8 bytes
+ * whatever its slot delivers and holds at most cap_each * 8 / item_bytes items: cap_each of up to 8 bytes (a 4-byte stream
+ * fills the first half of its row), cap_each / 4 of the 32-byte records of rcf_pump_subscribe_hard */
 int rcf_pump_read_many(rcf_pump_t *p, const int *entries, int64_t *cursors, int n, void *out, size_t cap_each, int64_t *counts);
 /* Channels come and go while a channelizer runs (rc_frontend/receiver.py:296-342 connect_channel builds and starts a
  * channel flowgraph under the running top block, :424-435 / :635-648 release and destroy it): a running pump takes a new
@@ -1256,6 +1263,27 @@ int rcf_pump_subscribe(rcf_pump_t *p, int member, int chan_id, int what, float g
  * member's fused discriminator ring (rcf_pfb_fm_enable: every bin of the bank demodulated inside its launch) instead of a
  * channel: delivered from the bank's next frame on, x gain -- quadrature_demod_cf behind the reference's channel at that
  * bin's frequency (p25_control_demod.py:120-121) without a tap, a tap matrix or a tap_finalize pass. */
+/* Everything behind the slicer through the pump: `what` = RCF_HARD_BITS, RCF_HARD_SYNC (uint32 items), RCF_HARD_TSBK,
+ * RCF_HARD_EDACS, RCF_HARD_OSW or RCF_HARD_P25LC (32-byte records); anything else is RCF_EINVAL, the plain and soft streams
+ * stay with rcf_pump_subscribe (which, like rcf_pump_start, goes on refusing these six).  The slot comes out of the same
+ * max_read slots and is used as any other entry: rcf_pump_unsubscribe, rcf_pump_written, rcf_pump_read and
+ * rcf_pump_read_many count in items -- a word, a hit, a record.
+ *   Ring geometry.  A slot is out_ring_samples (rounded up to a power of two) x 8 bytes whatever it delivers.  The host ring of
+ * a hard slot holds R items: R = out_ring_samples for the 4-byte streams (half the slot, as a discriminator slot),
+ * R = out_ring_samples / 4 for the records.  R < 16: RCF_ECAP.
+ *   Rules.  These streams are counted on the device, so the slot owns a cursor there as a soft-symbol slot does: the stream
+ * begins where the channel's single reader of that stream stands (rcf_chan_read_hard .. rcf_chan_read_p25lc; left alone
+ * afterwards), or at the oldest item the stage's ring still holds if that has wrapped past it; a stage attached again -- and
+ * a slicer attached again takes its decoder with it -- starts a new stream at its item 0, appended to the slot's item count
+ * without a gap; a slot handed from one tenant to the next keeps counting, whatever the two tenants' item sizes.  A channel
+ * that lacks the stage is no error: the slot starves until the stage is attached.
+ *   Lag.  The pump reserves for every gather in flight (two at most) the most it may take: after a block of n_k channel
+ * outputs ceil(n_k bps / 32) + 1 words, n_k + 1 hits, (n_k + 15) / 24 + 3 TSBK records, (n_k + 15) / 24 + 1 voice records,
+ * (n_k + 31) / 288 + 1 EDACS records, (n_k + 31) / 76 + 1 OSWs -- each the framing rule's densest case; what a stage has
+ * ready beyond it leaves with the next block -- and min(the stage's ring, R) for the first gather of a stream.  With
+ * `bound` the larger of the two blocks' figures a reader loses nothing while it lags fewer than R - 2 bound items.
+ * RCF_EINVAL as well: no such member or channel; RCF_ECAP as well: no free slot. */
+int rcf_pump_subscribe_hard(rcf_pump_t *p, int member, int chan_id, int what, int64_t *cursor);
 /* frees the slot (its channel may already be closed) */
 int rcf_pump_unsubscribe(rcf_pump_t *p, int entry);
 /* stops the thread (if still running), waits for it, releases the pump */

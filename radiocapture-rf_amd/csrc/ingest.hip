@@ -152,11 +152,13 @@ static __global__ __launch_bounds__(256) void gather_counted_kernel(const Counte
         const int64_t pos = (r.flags & 2u) ? r.pos0 : r.state_in[1];
         cur = max(cur, end - (int64_t)r.cap);                        // a reader more than a ring behind lost what was overwritten
         int64_t avail = max((int64_t)0, end - cur);
-        const int64_t room = (int64_t)r.dst_mask_w + 1;              // a destination ring keeps the newest `room` items
+        // an item is item_w words (a power of two; the frame decoders' records: 8); dst_mask_w counts words, room items
+        const uint32_t iw = r.item_w ? r.item_w : 1u;
+        const int64_t room = ((int64_t)r.dst_mask_w + 1) >> (__ffs((int)iw) - 1);   // a destination ring keeps the newest `room` items
         if (avail > room) { cur += avail - room; avail = room; }
         const uint32_t n = (uint32_t)min(avail, (int64_t)r.max_n);
-        // in words from here on: an item is item_w of them (a power of two; the TSBK records: 8)
-        const uint32_t iw = r.item_w ? r.item_w : 1u, ring_mask_w = r.cap * iw - 1u, n_w = n * iw;
+        // in words from here on
+        const uint32_t ring_mask_w = r.cap * iw - 1u, n_w = n * iw;
         const uint32_t first = (uint32_t)((uint64_t)cur & (r.cap - 1u)) * iw, at = (uint32_t)(uint64_t)pos * iw;
         for (uint32_t w = (item % parts) * 256 + threadIdx.x; w < n_w; w += parts * 256)
             dst[r.dst_w + ((at + w) & r.dst_mask_w)] = r.ring[(first + w) & ring_mask_w];

@@ -32,7 +32,7 @@ struct rcf_pump {
     struct Slot {
         int member = -1;                           // -1: free
         int chan = -1;                             // the member's channel, or RCF_SRC_PFB_BIN0 + a bin of its fused discriminator ring
-        int kind = kIq;                            // the stream delivered (row of kStreams; kFm x gain)
+        int kind = kIq;                            // the stream delivered: a reader's kind (read_kind / read_row; kFm x gain)
         float gain = 1.0f;
         Chan *c = nullptr;                         // the channel, resolved once per channel-set epoch (null: closed, or a bin)
         int64_t bin_rd = 0;                        // a bin's slot: frames delivered
@@ -48,8 +48,9 @@ struct rcf_pump {
     std::vector<uint64_t> epoch_of;                // per member: the epoch Slot::c was resolved at (~0: resolve again)
     int64_t *d_cstate = nullptr;
     unsigned char *h_crecs = nullptr, *h_crecs_dev = nullptr;   // pinned, per in-flight block: CountedRec[recs_cap] | result words[recs_cap][2]
-    size_t out_cap = 0;                            // host ring length per slot (items, power of two)
-    static constexpr size_t kSlotItemBytes = 8;    // every slot is out_cap x 8 bytes (a discriminator slot uses half)
+    size_t out_cap = 0;                            // host ring length per slot (items of up to 8 bytes, power of two)
+    static constexpr size_t kSlotItemBytes = 8;    // every slot is out_cap x 8 bytes (a discriminator slot uses half; 32-byte
+                                                   // records: out_cap / 4 of them -- ring_items)
     unsigned char *h_out = nullptr, *h_out_dev = nullptr;   // the slots' rings
     std::unique_ptr<std::atomic<int64_t>[]> out_written;    // items delivered per slot
     std::unique_ptr<std::atomic<int64_t>[]> out_queued;     // items whose gather has been (or is about to be) launched
@@ -72,7 +73,8 @@ struct rcf_pump {
     int64_t nivcsw = 0;
     std::chrono::steady_clock::time_point t_start, t_end;
     char err_text[256] = "";
-    size_t item_bytes(int e) const { return kStreams[slots[(size_t)e].kind].item_w * 4u; }
+    size_t item_bytes(int e) const { return read_row(slots[(size_t)e].kind).item_w * 4u; }
+    size_t ring_items(int e) const { return (size_t)slot_items(slots[(size_t)e].kind, (int64_t)out_cap); }   // the slot's host ring, in ITS items
     // Slot e takes a new tenant.  Its counters go on from where the previous tenant left them: the new stream starts at
     // `queued`.  Gathers still in flight for a COUNTED previous tenant no longer count (gen): the new stream starts at the
     // bound they stay below, and the slot's item count jumps there
@@ -82,7 +84,7 @@ struct rcf_pump {
         t.member = member; t.chan = chan; t.kind = kind; t.gain = gain_; t.bin_rd = bin_rd_;
         ++t.gen;
         if (t.last_counted) out_written[(size_t)e].store(t.queued, std::memory_order_release);
-        t.last_counted = kStreams[kind].counted;
+        t.last_counted = read_row(kind).counted;
         t.fresh = true;
         t.c = nullptr;
         entries_of[(size_t)member].push_back(e);
@@ -227,17 +229,23 @@ void Gather::counted(int e, const Stream &st)
     // the most this gather may take (the kernel holds it to that; a rest waits for the next block): steady state, what the
     // block made; a first gather, whatever the ring holds
     const int64_t n_k = std::max<int64_t>(0, t.c->pos.blk_after - t.c->pos.blk_before);
-    const int64_t bound = std::min<int64_t>(fresh || again ? (int64_t)st.cap : steady_bound(n_k, st.interp, st.decim), (int64_t)p->out_cap);
+    // (a hard stream: what its framing rule allows with the slicer's bits per symbol; 2, the larger figure, should a hard row
+    // ever come without a slicer)
+    const Chan::Slicer *sl = t.c->slicer.get();
+    const int64_t hard = hard_bound(t.kind, n_k, sl ? sl->rec.bps : 2);
+    const int64_t steady = hard < 0 ? steady_bound(n_k, st.interp, st.decim) : hard;
+    const int64_t R = (int64_t)p->ring_items(e);
+    const int64_t bound = std::min<int64_t>(fresh || again ? (int64_t)st.cap : steady, R);
     int64_t *cs = p->d_cstate + (size_t)e * 4;
     const int par = t.par;
     t.par = !t.par;
     crecs[n_crecs] = CountedRec{static_cast<const uint32_t *>(st.ring), st.counter, cs + 2 * par, cs + 2 * (par ^ 1),
                                 reinterpret_cast<int64_t *>(crecs_dev + p->recs_cap * sizeof(CountedRec)) + 2 * n_crecs,
                                 fresh ? *st.cursor : 0, t.queued, st.interp, st.decim, st.cap,
-                                (uint32_t)bound, (uint32_t)((size_t)e * p->out_cap * kSlotW), (uint32_t)(p->out_cap - 1),
-                                fresh ? 3u : again ? 1u : 0u, 0u};
+                                (uint32_t)bound, (uint32_t)((size_t)e * p->out_cap * kSlotW), (uint32_t)((size_t)R * st.item_w - 1),
+                                fresh ? 3u : again ? 1u : 0u, st.item_w};
     s.counted.push_back({e, t.gen, bound, n_crecs++});
-    max_c = std::max<uint32_t>(max_c, (uint32_t)bound);
+    max_c = std::max<uint32_t>(max_c, (uint32_t)bound * st.item_w);
     t.queued += bound;
     // (published BEFORE the launch, like a plain slot's: covers all this gather may write)
     p->out_queued[(size_t)e].store(t.queued, std::memory_order_release);
@@ -619,24 +627,24 @@ int64_t rcf_pump_written(rcf_pump_t *p, int entry)
 }
 
 // one slot's new items from *cursor on -> out; the items the pump has meanwhile queued over (up to two gathers are in flight and
-// write [written, queued) of the ring -- the oldest out_cap region a lagging reader may be copying) are dropped from the
-// front AFTER the copy, so that what is returned was whole when it was read
+// write [written, queued) of the ring -- the oldest region a lagging reader may be copying) are dropped from the
+// front AFTER the copy, so that what is returned was whole when it was read.  The ring is the slot's own: R of its items
 static int64_t pump_read_slot(rcf_pump *p, int entry, int64_t *cursor, unsigned char *out, size_t max_items)
 {
-    const size_t elem = p->item_bytes(entry);
+    const size_t elem = p->item_bytes(entry), R = p->ring_items(entry);
     const int64_t w = p->out_written[(size_t)entry].load(std::memory_order_acquire);
     int64_t avail = w - *cursor;
     if (avail <= 0 || max_items == 0) return 0;
     const int64_t q0 = p->out_queued[(size_t)entry].load(std::memory_order_acquire);
-    if (*cursor < q0 - (int64_t)p->out_cap) { *cursor = q0 - (int64_t)p->out_cap; avail = w - *cursor; if (avail <= 0) return 0; }
+    if (*cursor < q0 - (int64_t)R) { *cursor = q0 - (int64_t)R; avail = w - *cursor; if (avail <= 0) return 0; }
     int64_t n = std::min<int64_t>(avail, (int64_t)max_items);
     const unsigned char *ring = p->h_out + (size_t)entry * p->out_cap * rcf_pump::kSlotItemBytes;
-    const size_t pos = (size_t)((uint64_t)*cursor & (p->out_cap - 1));
-    const size_t first = std::min<size_t>((size_t)n, p->out_cap - pos);
+    const size_t pos = (size_t)((uint64_t)*cursor & (R - 1));
+    const size_t first = std::min<size_t>((size_t)n, R - pos);
     std::memcpy(out, ring + pos * elem, first * elem);
     if ((size_t)n > first) std::memcpy(out + first * elem, ring, ((size_t)n - first) * elem);
     std::atomic_thread_fence(std::memory_order_acquire);
-    const int64_t lo = p->out_queued[(size_t)entry].load(std::memory_order_acquire) - (int64_t)p->out_cap;
+    const int64_t lo = p->out_queued[(size_t)entry].load(std::memory_order_acquire) - (int64_t)R;
     if (lo > *cursor) {                               // overwritten while it was copied: what is left starts at lo
         const int64_t drop = std::min<int64_t>(n, lo - *cursor);
         if (drop < n) std::memmove(out, out + (size_t)drop * elem, (size_t)(n - drop) * elem);
@@ -658,14 +666,16 @@ int rcf_pump_read_many(rcf_pump_t *p, const int *entries, int64_t *cursors, int 
     if (!p || n < 0 || (n && (!entries || !cursors || !out || !counts))) { set_error("bad pump read arguments"); return RCF_EINVAL; }
     for (int i = 0; i < n; ++i) {
         if (entries[i] < 0 || entries[i] >= (int)p->slots.size()) { counts[i] = -1; continue; }
-        counts[i] = pump_read_slot(p, entries[i], &cursors[i], static_cast<unsigned char *>(out) + (size_t)i * cap_each * rcf_pump::kSlotItemBytes, cap_each);
+        // (row i is cap_each x 8 bytes whatever the slot delivers: cap_each items of up to 8 bytes, cap_each / 4 records)
+        counts[i] = pump_read_slot(p, entries[i], &cursors[i], static_cast<unsigned char *>(out) + (size_t)i * cap_each * rcf_pump::kSlotItemBytes,
+                                   (size_t)slot_items(p->slots[(size_t)entries[i]].kind, (int64_t)cap_each));
     }
     return RCF_OK;
 }
 
-int rcf_pump_subscribe(rcf_pump_t *p, int member, int chan_id, int what, float gain, int64_t *cursor)
+// a subscription of either entry point: `kind` is the reader's kind of `what`, which the entry point has admitted
+static int pump_subscribe(rcf_pump *p, int member, int chan_id, int what, int kind, float gain, int64_t *cursor)
 {
-    if (!p || stream_kind(what) < 0 || !kStreams[stream_kind(what)].pumped) { set_error("bad subscription"); return RCF_EINVAL; }
     rcf_group *g = p->g;
     std::lock_guard<std::mutex> gl(g->mu);
     if (member < 0 || member >= (int)g->members.size()) { set_error("no such member %d", member); return RCF_EINVAL; }
@@ -692,11 +702,30 @@ int rcf_pump_subscribe(rcf_pump_t *p, int member, int chan_id, int what, float g
             return RCF_EINVAL;
         }
     }
-    p->occupy(e, member, chan_id, stream_kind(what), gain, bin_start);
+    p->occupy(e, member, chan_id, kind, gain, bin_start);
     // the new stream starts at `queued`, which the reader's cursor is set to (the gathers still in flight for the previous
     // tenant end below it)
     if (cursor) *cursor = p->slots[(size_t)e].queued;
     return e;
+}
+
+int rcf_pump_subscribe(rcf_pump_t *p, int member, int chan_id, int what, float gain, int64_t *cursor)
+{
+    if (!p || stream_kind(what) < 0 || !kStreams[stream_kind(what)].pumped) { set_error("bad subscription"); return RCF_EINVAL; }
+    return pump_subscribe(p, member, chan_id, what, stream_kind(what), gain, cursor);
+}
+
+// The streams behind the slicer.  The table's `pumped` column and stream_kind stay what the two entry points above refuse
+// by; this one admits exactly the counted uint32 rows, of the table and behind it
+int rcf_pump_subscribe_hard(rcf_pump_t *p, int member, int chan_id, int what, int64_t *cursor)
+{
+    const int kind = read_kind(what);
+    if (!p || kind < 0 || hard_bound(kind, 0, 1) < 0 || chan_id >= RCF_SRC_PFB_BIN0) { set_error("bad subscription: %d is no stream behind a slicer", what); return RCF_EINVAL; }
+    if (slot_items(kind, (int64_t)p->out_cap) < 16) {
+        set_error("host rings of %zu x 8 bytes hold fewer than 16 items of stream %d (rcf_pump_config_t.out_ring_samples)", p->out_cap, what);
+        return RCF_ECAP;
+    }
+    return pump_subscribe(p, member, chan_id, what, kind, 1.0f, cursor);
 }
 
 int rcf_pump_unsubscribe(rcf_pump_t *p, int entry)

@@ -20,7 +20,7 @@ template <class L> void loop_row(L *l, Stream *s) { if (l) counted_row(s, l->rin
 // a frame decoder's records: a ring of the decoder's own capacity
 template <class R> void frames_row(Chan *c, Stream *s)
 {
-    if (R *t = c->slicer ? c->slicer->frames<R>().get() : nullptr) { counted_row(s, t->rec.rec_ring, &t->rd, &t->rec.st->n_records, 0); s->cap = t->cap; }
+    if (R *t = c->slicer ? c->slicer->frames<R>().get() : nullptr) { counted_row(s, t->rec.rec_ring, &t->rd, &t->rec.st->n_records, t->serial); s->cap = t->cap; }
 }
 // ring, reader and counter of every row of kStreams and of the readers' rows behind it, in their order; a row that leaves the
 // ring null is refused
@@ -33,8 +33,8 @@ void (*const kRows[kReadKindsEnd])(Chan *, Stream *) = {
     [](Chan *c, Stream *s) { if (Chan::Audio *a = c->audio.get()) counted_row(s, a->rec.o_ring, &a->rd, &a->rec.st->n_a, a->serial, a->rec.interp, a->rec.decim); },
     [](Chan *c, Stream *s) { loop_row(c->costas.get(), s); },
     [](Chan *c, Stream *s) { loop_row(c->fsk4.get(), s); },
-    [](Chan *c, Stream *s) { if (Chan::Slicer *l = c->slicer.get()) counted_row(s, l->rec.word_ring, &l->rd_words, &l->rec.st->n_words, 0); },
-    [](Chan *c, Stream *s) { if (Chan::Slicer *l = c->slicer.get()) { counted_row(s, l->rec.hit_ring, &l->rd_hits, &l->rec.st->n_hits, 0); s->cap = l->hit_cap; } },
+    [](Chan *c, Stream *s) { if (Chan::Slicer *l = c->slicer.get()) counted_row(s, l->rec.word_ring, &l->rd_words, &l->rec.st->n_words, l->serial); },
+    [](Chan *c, Stream *s) { if (Chan::Slicer *l = c->slicer.get()) { counted_row(s, l->rec.hit_ring, &l->rd_hits, &l->rec.st->n_hits, l->serial); s->cap = l->hit_cap; } },
     frames_row<Chan::Slicer::Tsbk>,
     frames_row<Chan::Slicer::Edacs>,
     frames_row<Chan::Slicer::Osw>,

@@ -127,6 +127,7 @@ static int attach_frames(rcf_t *h, int chan_id, const P *p, Ok &&slicer_ok, cons
     r.word_ring = sl.word_ring; r.hit_ring = sl.hit_ring;
     r.word_mask = sl.word_mask; r.hit_mask = sl.hit_mask; r.rec_mask = (uint32_t)cap - 1;
     k->cap = (uint32_t)cap;
+    k->serial = next_stage_serial();
     SliceState now{};
     const int rc = stage_state(h, sl.st, &now, offsetof(SliceState, partial));
     if (rc != RCF_OK) return rc;
@@ -413,6 +414,7 @@ int rcf_chan_slicer(rcf_t *h, int chan_id, const rcf_slicer_params_t *p)
     r.hit_mask = (uint32_t)hit_cap - 1;
     k->source = p->source;
     k->hit_cap = (uint32_t)hit_cap;
+    k->serial = next_stage_serial();
     constexpr size_t kStateWords = 256 / sizeof(uint32_t);
     static_assert(sizeof(SliceState) <= 256, "the state's slot");
     const size_t state_at = h->out_cap, hits_at = state_at + kStateWords;          // in words (out_cap >= 64: the record's 64-bit fields are aligned)

@@ -173,6 +173,8 @@ struct Chan {
         int source = 0;                 // RCF_READ_CLOCK / COSTAS / FSK4
         uint32_t hit_cap = 0;
         int64_t rd_words = 0, rd_hits = 0;
+        uint64_t serial = 0;            // which attachment its two streams belong to (next_stage_serial, set where the stage is
+                                        // attached: max_frames_launch below builds a Slicer per call); a frame decoder has its own
         // The frame decoders out of the slicer's two streams: P25 trunking blocks (rcf_chan_tsbk), EDACS control frames
         // (rcf_chan_edacs), SmartNet OSWs (rcf_chan_osw), P25 voice data units (rcf_chan_p25lc).  One record shape.  A decoder hangs off the slicer -- Chan stays
         // inside its prefetched lines -- and goes whenever the slicer goes.  One allocation, which starts at rec.rec_ring:
@@ -185,6 +187,7 @@ struct Chan {
             Launch rec{};
             uint32_t cap = 0;
             int64_t rd = 0;
+            uint64_t serial = 0;        // set by attach_frames
         };
         struct Tsbk : Frames<TsbkState, TsbkLaunch> { static constexpr int kKind = kTsbk; static constexpr const char *kName = "TSBK"; };
         struct Edacs : Frames<EdacsState, EdacsLaunch> { static constexpr int kKind = kEdacs; static constexpr const char *kName = "EDACS"; };

@@ -39,8 +39,9 @@ constexpr int stream_kind(int what)
 }
 static_assert(stream_kind(RCF_READ_AUDIO) == kAudio && stream_kind(RCF_HARD_SYNC) == kHardSync && stream_kind(RCF_HARD_TSBK) == kTsbk, "the rows stand in the enum's order");
 // That table and stream_kind are also the pump's: its two entry points take a `what` through them and refuse what they do not
-// find or find unpumped, and its slots hold a row's index.  A stream that only the readers carry -- none of the pump's code
-// knows its items -- is added BEHIND the table, so that nothing the pump or a consumer of the table compiled against moves:
+// find or find unpumped.  (rcf_pump_subscribe_hard, the pump's third, takes the counted uint32 streams -- rows 32, 33 and 48 and
+// the rows behind the table -- through read_kind, and a slot holds a reader's kind.)  A stream that only the readers carry -- none
+// of the code compiled against the table knows its items -- is added BEHIND the table, so that nothing the pump or a consumer of the table compiled against moves:
 // the readers' kinds go on where the table's end, read_kind / read_row are their stream_kind / kStreams.
 // kReadKinds is where the rows ended when the first of them (49) came, and stays there -- a consumer compiled against it sees
 // what it saw; rows added since go on behind it, and kAllReadKinds ends them all.  A new stream takes a number that was never
@@ -84,6 +85,39 @@ inline int64_t count_end(int64_t counter, uint32_t interp, uint32_t decim)
 // the most a steady-state gather of the pump takes after a block of n_k stage inputs: n_k + 1 symbols of a loop (interp =
 // decim = 1), ceil(n_k interp / decim) + 1 audio samples
 inline int64_t steady_bound(int64_t n_k, uint32_t interp, uint32_t decim) { return count_end(n_k, interp, decim) + 1; }
+// A slot of the pump is out_cap x 8 bytes whatever it delivers; its host ring holds slot_items() of the stream's items: out_cap
+// of up to 8 bytes (a 4-byte stream uses half the slot), out_cap / 4 of the 32-byte records.  Both are powers of two
+inline int64_t slot_items(int kind, int64_t out_cap) { return read_row(kind).item_w <= 2 ? out_cap : out_cap * 2 / (int64_t)read_row(kind).item_w; }
+// The most a steady-state gather of a slot of rcf_pump_subscribe_hard takes after a block of n_k channel outputs; bps = the
+// slicer's bits per symbol (1, 2).  A symbol loop makes at most n_k + 1 symbols of them (steady_bound), so the slicer's whole
+// words cover at most dW = n_k + 1 + (32 / bps - 1) more symbols than before the block: the unfinished word may have lacked
+// one symbol.  Every frame decoder DECIDES a frame in the first block whose whole words reach a threshold that lies a fixed
+// distance behind the frame's start (rcf.h: s + 384, s + 888, s + 288, pos + 84 or h0 + 92), so the frames of a block are those
+// with a threshold among dW consecutive symbols, and the framing rule says how close two thresholds can lie:
+//   words   ceil(n_k bps / 32) + 1       (n_k + 1 symbols behind an unfinished word of at most 32 - bps bits)
+//   hits    n_k + 1                      (one item per symbol at most: the two polarities' ranges of dist do not meet)
+//   TSBK    (n_k + 15) / 24 + 3          accepted hits lie >= 24 dibits apart, dW = n_k + 16.  A frame cut d dibits behind its start
+//                                        gives 1 record for d < 259, 2 for d < 359, else 3 -- never more than d / 24 --, so all
+//                                        frames but the block's last give at most (dW - 1) / 24 together, and the last at most 3
+//   P25LC   (n_k + 15) / 24 + 1          the same accept rule, one record per frame
+//   EDACS   (n_k + 31) / 288 + 1         accepted hits lie >= 288 bits apart, dW = n_k + 32, one record per frame
+//   OSW     (n_k + 31) / 76 + 1          a packet's threshold is its sync position + 84 (step A) or + 92 (step B), the next
+//                                        packet's sync position lies >= 84 bits on: thresholds >= 76 bits apart, dW = n_k + 32
+// A stage that has more than this ready (a backlog behind a loss, say) is held to the bound by the gather kernel; the rest
+// leaves with the next block.  -1: not a hard stream
+inline int64_t hard_bound(int kind, int64_t n_k, int bps)
+{
+    if (n_k < 0) n_k = 0;
+    switch (kind) {
+    case kHardBits: return (n_k * bps + 31) / 32 + 1;
+    case kHardSync: return n_k + 1;
+    case kTsbk:     return (n_k + 15) / 24 + 3;
+    case kP25lc:    return (n_k + 15) / 24 + 1;
+    case kEdacs:    return (n_k + 31) / 288 + 1;
+    case kOsw:      return (n_k + 31) / 76 + 1;
+    default:        return -1;
+    }
+}
 // a plain slot of the pump: of the n items from *cursor on, those a host ring of `room` items cannot hold are skipped
 inline int64_t ring_room(int64_t *cursor, int64_t n, int64_t room)
 {

@@ -101,6 +101,7 @@ class NativeDataPlane(egress.EgressPump):
         self.classes = {}
         self.member_of = {}            # id(front-end) -> (class, member index)
         self.subs = {}                 # block_id -> [class, chan_id, iq slot, fm slot or None]
+        self.rec_subs = {}             # (block_id, what) -> [class, chan_id, slot]: what lies behind the channel's slicer
         self._plans = {}
         self._pins = []
         self._build()
@@ -279,7 +280,78 @@ class NativeDataPlane(egress.EgressPump):
 
     def _drop(self, block_id):
         self._unsubscribe(block_id)
+        for key in [k for k in self.rec_subs if k[0] == block_id]:
+            self._unsubscribe_records(key)
         super()._drop(block_id)
+
+    # ------------------------------------------------------------------ what lies behind a channel's slicer
+    # The packed decisions, the sync hits and the frame decoders' records of a channel of the running front-end reach a
+    # consumer in this process through the channel's class pump (rcf_pump_subscribe_hard): no read synchronises the stream.
+    # They are not published on a socket.  WHICH native channel carries the stage is the caller's to say: rcf.control's
+    # edacs_clock / smartnet_clock attach to the channel they are given, the block's own; rcf.p25's c4fm_demod / cqpsk_demod
+    # put loop, slicer and decoder on a chained pre-filter channel and RETURN its id -- that id is `chan_id` below.  Nothing
+    # in the pump follows a chain: subscribed on the block's own channel, a P25 stream starves.
+    def subscribe_records(self, block_id, what, chan_id=None):
+        """channel `block_id`'s stream `what` ("hard", "sync", "tsbk", "edacs", "osw", "p25lc") -> its slot on the class pump.
+        chan_id: the native channel the stage sits on where that is not the block's own -- what rcf.p25.c4fm_demod /
+        cqpsk_demod returned for it; remembered per (block_id, what), so later calls and read_records need not repeat it.
+        Subscribed on the first call.  After a retune gave the block a new native channel: an own-channel subscription is
+        made again on the new one; a NAMED channel went with the old one (its stages too), so the slot is released and
+        RuntimeError raised until the caller has built the chain again and names its channel.  Naming another channel moves
+        the subscription there.  A channel without the stage is no error: the slot starves until the stage is attached.
+        The slot comes out of the pump's max_channels slots, which the IQ and discriminator subscriptions share: when none
+        is free the call raises RcfError with RCF_ECAP (so does a host ring of fewer than 16 items: out_ring_samples < 64
+        for records)"""
+        if what not in self.native._HARD_WHAT:
+            raise ValueError("no stream behind a slicer: %r" % (what,))
+        with self.tb.access_lock:
+            ch = self.tb.channels.get(block_id)
+            if ch is None or ch.chan_id is None:
+                raise KeyError("no such channel %s" % (block_id,))
+            where = self.member_of.get(id(getattr(ch, "frontend", None)))
+            if where is None or where[0].pump is None:
+                raise RuntimeError("channel %s is not on a running native pump" % (block_id,))
+            cl, member = where
+            key = (block_id, what)
+            sub = self.rec_subs.get(key)                          # [class, the block's native channel then, slot, stage channel, named]
+            retuned = sub is not None and sub[1] != ch.chan_id    # (the NAMED channel is never compared with ch.chan_id)
+            if chan_id is not None:
+                stage, named = int(chan_id), True
+            elif sub is not None and sub[4] and not retuned:
+                stage, named = sub[3], True
+            else:
+                stage, named = ch.chan_id, False
+                if sub is not None and sub[4]:                    # retuned under a named chain, and no new name
+                    self._unsubscribe_records(key)
+                    raise RuntimeError("channel %s was retuned: the chain that carried %r went with its native channel %d; build it "
+                                       "again and name its channel (chan_id=)" % (block_id, what, sub[3]))
+            if sub is not None and (retuned or sub[3] != stage):
+                self._unsubscribe_records(key)
+                sub = None
+            if sub is None:
+                sub = self.rec_subs[key] = [cl, ch.chan_id, cl.pump.subscribe(member, stage, what), stage, named]
+            return sub[2]
+
+    def read_records(self, block_id, what, max_items=None, chan_id=None):
+        """the new items of channel `block_id`'s stream `what` since the last call: a uint32 array ("hard", "sync") or the
+        stage's structured records (native.TSBK_DTYPE, EDACS_DTYPE, OSW_DTYPE, P25LC_DTYPE).  It subscribes as
+        subscribe_records does (chan_id: see there) and raises what that raises.  max_items: the most one call returns --
+        the call allocates and copies that many items' room, so the default is 4096 words or hits and 256 records (8 KiB);
+        what is left comes with the next call"""
+        if max_items is None:
+            max_items = 1 << 12 if what in ("hard", "sync") else 256
+        with self.tb.access_lock:
+            slot = self.subscribe_records(block_id, what, chan_id)
+            return self.rec_subs[(block_id, what)][0].pump.read(slot, int(max_items))
+
+    def _unsubscribe_records(self, key):
+        sub = self.rec_subs.pop(key, None)
+        if sub is None or sub[0].pump is None:
+            return
+        try:
+            sub[0].pump.unsubscribe(sub[2])
+        except Exception as e:
+            log.error("unsubscribe of channel %s's %s records failed: %s" % (key[0], key[1], e))
 
     # ------------------------------------------------------------------ what the status line carries
     def stats(self):

@@ -51,13 +51,15 @@ SYMBOLS = [
     "rcf_group_open", "rcf_group_close", "rcf_group_size", "rcf_group_push", "rcf_group_commit", "rcf_group_read_many",
     "rcf_chan_squelch", "rcf_chan_squelch_state", "rcf_pfb_squelch", "rcf_pfb_squelch_read", "rcf_pfb_squelch_segment",
     "rcf_group_sync", "rcf_pump_start", "rcf_pump_stats", "rcf_pump_written", "rcf_pump_read", "rcf_pump_read_many", "rcf_pump_subscribe", "rcf_pump_unsubscribe", "rcf_pump_stop",
+    "rcf_pump_subscribe_hard",
 ]
 FMT_CF32, FMT_U8, FMT_S8, FMT_S16 = 0, 1, 2, 3
 READ_IQ, READ_FM, READ_AGC = 0, 1, 2
 # the streams of a channel's stages (RCF_READ_SYM .. RCF_READ_AUDIO): float32 rows of the batched readers and the pump
 READ_SYM, READ_CLOCK, READ_COSTAS, READ_FSK4, READ_AUDIO = 16, 17, 18, 19, 20
 _STAGE_WHAT = {"sym": READ_SYM, "clock": READ_CLOCK, "costas": READ_COSTAS, "fsk4": READ_FSK4, "audio": READ_AUDIO}
-# the slicer's two streams (RCF_HARD_BITS, RCF_HARD_SYNC): uint32 rows of the batched readers; the pump does not deliver them
+# the slicer's two streams (RCF_HARD_BITS, RCF_HARD_SYNC): uint32 rows of the batched readers; the pump delivers them, and the
+# records below, through Pump.subscribe (rcf_pump_subscribe_hard), never as the `what` it is started with
 HARD_BITS, HARD_SYNC = 32, 33
 # the stream of the TSBK stage behind a slicer (RCF_HARD_TSBK): records of 8 uint32, batched the same way
 HARD_TSBK = 48
@@ -470,6 +472,7 @@ def lib():
         "rcf_pump_read": (i64, [vp, C.c_int, C.POINTER(i64), vp, sz]),
         "rcf_pump_read_many": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(i64), C.c_int, vp, sz, C.POINTER(i64)]),
         "rcf_pump_subscribe": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(i64)]),
+        "rcf_pump_subscribe_hard": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(i64)]),
         "rcf_pump_unsubscribe": (C.c_int, [vp, C.c_int]),
         "rcf_pump_stop": (C.c_int, [vp]),
     }
@@ -1390,7 +1393,9 @@ class Pump:
     cyclically at `samp_rate` of wall-clock time, block boundaries shifted by phase_s[i], or, where `written[i]` is a
     one-element uint64 array, taken block by block as its producer counts them complete.  Subscriptions may be given at
     start ((member, channel id) pairs delivered as `what` x `gain`) and change while it runs (subscribe / unsubscribe, up to
-    `max_read` at a time).  what: "iq", "fm", "agc" or a stage's stream ("sym", "clock", "costas", "fsk4", "audio")."""
+    `max_read` at a time).  what: "iq", "fm", "agc" or a stage's stream ("sym", "clock", "costas", "fsk4", "audio").
+    subscribe() also takes what lies behind a slicer -- "hard", "sync" (uint32 items), "tsbk", "edacs", "osw", "p25lc"
+    (records, their structured dtypes) --; the pump cannot be STARTED with one of those (RCF_EINVAL)."""
 
     def __init__(self, group, rings, block_samples, samp_rate, subscriptions=(), fmt=FMT_U8, scale=1.0, offset=0.0,
                  what="fm", gain=1.0, phase_s=None, out_ring_samples=4096, n_blocks=0, warm_blocks=0, max_batch=0,
@@ -1470,10 +1475,14 @@ class Pump:
         return self.stats()
 
     def subscribe(self, member, chan_id, what="iq", gain=1.0):
-        """channel `chan_id` of member `member` from its next output on -> the slot (rcf_pump_subscribe)"""
+        """channel `chan_id` of member `member` from its next output on -> the slot (rcf_pump_subscribe; a stream behind the
+        slicer: rcf_pump_subscribe_hard, counted in words, hits or records)"""
         cur = C.c_int64(0)
-        e = _check(lib().rcf_pump_subscribe(self._p, int(member), int(chan_id), _read_what(what, True),
-                                            float(gain), C.byref(cur)))
+        if what in _HARD_WHAT:
+            e = _check(lib().rcf_pump_subscribe_hard(self._p, int(member), int(chan_id), _HARD_WHAT[what], C.byref(cur)))
+        else:
+            e = _check(lib().rcf_pump_subscribe(self._p, int(member), int(chan_id), _read_what(what, True),
+                                                float(gain), C.byref(cur)))
         self._cursors[e] = cur
         self._what[e] = what
         return e
@@ -1497,14 +1506,19 @@ class Pump:
 
     def read_many_plan(self, entries, cap_each=1 << 13):
         """-> call() -> list of arrays (views into one buffer that the next call overwrites; None: no such slot): the new
-        items of every listed slot with ONE native call (rcf_pump_read_many).  The call's arguments are built once."""
+        items of every listed slot with ONE native call (rcf_pump_read_many).  The call's arguments are built once.  Every
+        row is cap_each x 8 bytes: cap_each items of up to 8 bytes, cap_each // 4 records of a frame decoder's slot (any
+        cap_each: a record row is viewed over its whole records' bytes, the rest of the row stays unused)."""
         n = len(entries)
         ents = (C.c_int * max(n, 1))(*[int(e) for e in entries])
         curs = (C.c_int64 * max(n, 1))(*[self._cursors[e].value for e in entries])
         counts = (C.c_int64 * max(n, 1))()
         out = np.empty((max(n, 1), cap_each), dtype=np.complex64)
-        outf = out.view(np.float32)
-        is_iq = [_read_dtype(self._what[e]) == np.complex64 for e in entries]   # cf32 rows ("iq", "agc")
+        rows = []                                                # each row as its slot's items
+        for i, e in enumerate(entries):
+            dt = np.dtype(_read_dtype(self._what[e]))
+            per = max(1, dt.itemsize // 8)                        # 8-byte units of the row per item (records: 4)
+            rows.append(out[i, :cap_each // per * per].view(dt))
         fn, pp, op = lib().rcf_pump_read_many, self._p, out.ctypes.data_as(C.c_void_p)
 
         def call():
@@ -1513,7 +1527,7 @@ class Pump:
             for i in range(n):
                 c = counts[i]
                 self._cursors[entries[i]].value = curs[i]
-                res.append(None if c < 0 else (out[i, :c] if is_iq[i] else outf[i, :c]))
+                res.append(None if c < 0 else rows[i][:c])
             return res
         return call
 
