@@ -955,8 +955,8 @@ int rcf_pfb_fm_ring(rcf_t *h, void **fm_ring, size_t *capacity_frames, int64_t *
  *      open  = level >= thr                        per sample; `unmuted` is that comparison for the last sample seen
  * A NaN level reads as muted and stays NaN; an Inf level stays open (with alpha == 1 the next sample turns it into a
  * NaN: 0 x Inf, as in GNU Radio).  The call that attached the stage resets it.
- * Limits: no ramp (simple_squelch_cc has none), no gating of the IQ stream (the reference connects the
- * block to a null sink and reads unmuted() only).
+ * Limits: no ramp (simple_squelch_cc has none), and this stage reports only (the reference connects the
+ * block to a null sink and reads unmuted() only): gating the IQ stream is rcf_chan_capture's, below.
  *
  * Behind a channel: exact, bit for bit the sequential evaluation above, however the stream is cut into blocks.  p == NULL
  * detaches the stage; calling it again resets the state (level 0, counters 0) from the channel's next output on.  It
@@ -1001,6 +1001,96 @@ int rcf_pfb_squelch_read(rcf_t *h, double *level, int64_t *n_open, int64_t *last
                          int64_t *frames_seen);
 /* frames per segment of the bank's stage (no device needed) */
 int rcf_pfb_squelch_segment(void);
+
+/* ------------------------------------------------------------------ carrier-operated capture */
+/*
+ * The reference does not stop at the report: scanning_receiver.py:108-113 polls unmuted() every 10 ms, call_progress
+ * (:62-97) opens a logging_receiver on that frequency, and the receiver stays alive hang_time = 0.5 s behind the last
+ * activity.  What it records has lost the head of the transmission (the poll period plus the connect at least).  Here the
+ * gate itself is one more optional stage behind a channel, independent of rcf_chan_squelch (a channel may carry either or
+ * both): it turns the channel's IQ stream into the samples of its transmissions only, with a lead-in the reference cannot
+ * have, a hang time counted in samples, and a record per transmission.
+ *
+ * Definition.  Let a be the channel-output index of the first sample after the attaching call (indices as
+ * rcf_squelch_state_t counts them).
+ *   Detector: exactly rcf_chan_squelch's -- thr = pow(10, threshold_db / 10), p = (float)(re re + im im),
+ *     level = alpha p + (1 - alpha) level in double from level 0 at a, open(i) <=> level_i >= thr; a NaN level is muted for
+ *     good, an Inf level stays open.
+ *   Gate: with integers pre >= 0 and hang >= 0 in channel samples, sample j >= a is KEPT <=> some i >= a has open(i) and
+ *     j - hang <= i <= j + pre.  With L(n) the greatest open index <= n (or none): keep(j) <=> L(j + pre) >= j - hang.  So the
+ *     writer runs pre samples behind the detector and needs only L at the detector's position: O(1) per sample and exact,
+ *     however the stream is cut into blocks.  After n_seen samples the stage has DECIDED samples a .. a + n_seen - pre - 1;
+ *     the last pre samples wait for the next block.  Nothing before a is ever kept: the lead-in is clipped at the attach
+ *     point.
+ *   Captured stream (RCF_READ_CAPTURE: cf32, counted on the device): the kept samples in order, bits unchanged, compacted
+ *     into a ring of `capacity` samples the stage owns.
+ *   Records (RCF_HARD_CAPTURE: rcf_capture_rec_t, 32 bytes, counted on the device, a ring of rec_capacity records): an OPEN
+ *     record at every j with keep(j) && !(j > a && keep(j - 1)), a CLOSE record at every j with !keep(j) && keep(j - 1).
+ *     OPEN: sample = the first kept sample, pos = its index in the captured stream, n_open = 0, peak = 0.  CLOSE: sample =
+ *     the first sample not kept, pos = one past the window's last captured sample, n_open = the open samples of the
+ *     window (saturating), peak = (float) of the largest level at one of them.  The two CLOSE accumulators count from the
+ *     last CLOSE on, which is exact: keep(j) is false at a CLOSE, so no index in [j - hang, j + pre] is open -- every open
+ *     sample the detector has seen by then lies inside the window that just ended (or one before it, whose CLOSE took it
+ *     out).  Records alternate OPEN, CLOSE, OPEN, ... and start with OPEN; close.pos - open.pos == close.sample -
+ *     open.sample; every open sample lies in exactly one window.
+ * p == NULL detaches the stage.  Calling it again resets everything and restarts both streams at item 0, from the channel's
+ * next output on.  It reads the channel's IQ ring, so it serves every channel kind on one front-end and in a group; a retune
+ * keeps it, closing the channel releases it.
+ * capacity and rec_capacity are rounded up to powers of two; 0: the handle's ring capacity / 256 records; capacity is at
+ * least 64, rec_capacity at least 16 (smaller values are raised).
+ * RCF_EINVAL: alpha outside (0, 1], a threshold that is not finite, pre or hang negative, a capacity beyond 2^26 samples or
+ * 2^20 records.  RCF_ECAP: the writer re-reads the channel's IQ ring pre samples behind the detector, so pre plus the most
+ * outputs one block can give the channel must fit that ring: with N the handle's block capacity and the channel's chain of
+ * decimations D_1 .. D_m (the filterbank's first for a channel on a bin), M_0 = N, M_i = M_(i-1) / D_i + 1 (integer
+ * division), the call is refused when pre + M_m exceeds the ring capacity.  (A block that would still overrun the ring is
+ * refused when it is pushed, as for every stage that looks back.)  RCF_ESTATE: the channel exposes its discriminator only
+ * (rcf_chan_set_fm_only) -- and rcf_chan_set_fm_only(on) is refused (RCF_ESTATE) while the channel carries the stage.
+ * RCF_ENOCHAN: no such channel.
+ * A reader of either stream that lags more than its ring loses the oldest items, like every counted stream. */
+/* (enumerators, not macros: the RCF_READ_* macros are the rows of the stream table proper -- what rcf_pump_start takes, and a list
+ * the suite pins --, and these two streams stand behind that table, with the readers' rows) */
+enum {
+    RCF_READ_CAPTURE = 24,    /* cf32 samples of rcf_chan_capture's captured stream */
+    RCF_HARD_CAPTURE = 56     /* its 32-byte records */
+};
+#define RCF_CAPTURE_OPEN  1
+#define RCF_CAPTURE_CLOSE 2
+typedef struct rcf_capture_params {
+    double threshold_db;        /* the detector's threshold, dB */
+    double alpha;               /* its filter's alpha, (0, 1]; the reference uses 0.1 */
+    int64_t pre;                /* lead-in, channel samples */
+    int64_t hang;               /* hang time, channel samples */
+    uint32_t capacity;          /* captured-stream ring, samples; 0: the handle's ring capacity */
+    uint32_t rec_capacity;      /* record ring, records; 0: 256 */
+} rcf_capture_params_t;
+typedef struct rcf_capture_rec {
+    uint32_t kind;              /* RCF_CAPTURE_OPEN / RCF_CAPTURE_CLOSE */
+    uint32_t n_open;
+    int64_t sample;
+    int64_t pos;
+    float peak;
+    uint32_t reserved_;         /* 0 */
+} rcf_capture_rec_t;
+int rcf_chan_capture(rcf_t *h, int chan_id, const rcf_capture_params_t *p);
+/* the stage's state as of everything queued; syncs the stream.  RCF_ESTATE without the stage. */
+typedef struct rcf_capture_state {
+    double level;               /* the detector's level after the last sample seen */
+    int64_t n_seen;             /* samples the detector has seen since the stage was (last) attached */
+    int64_t n_decided;          /* samples decided: max(0, n_seen - pre) */
+    int64_t n_kept;             /* items of the captured stream so far */
+    int64_t n_records;          /* items of the record stream so far */
+    int64_t n_windows;          /* OPEN records among them */
+    int64_t last_open;          /* index of the last open sample, -1: none */
+    int32_t in_window;          /* the last decided sample was kept: an OPEN without its CLOSE */
+    int32_t unmuted;            /* the last sample seen was open */
+} rcf_capture_state_t;
+int rcf_chan_capture_state(rcf_t *h, int chan_id, rcf_capture_state_t *out);
+/* unread captured samples, oldest first: out = cf32[max_samples] (one round trip) */
+int64_t rcf_chan_read_capture(rcf_t *h, int chan_id, float *out, size_t max_samples);
+/* unread records, oldest first: out = rcf_capture_rec_t[max_records] as uint32[max_records][8] */
+int64_t rcf_chan_read_capture_rec(rcf_t *h, int chan_id, uint32_t *out, size_t max_records);
+/* zero-copy: the two device rings and their capacities in items (order reads on rcf_stream(h)) */
+int rcf_chan_capture_rings(rcf_t *h, int chan_id, void **cap_ring, size_t *capacity, void **rec_ring, size_t *rec_capacity);
 
 
 /* ------------------------------------------------------------------ polyphase filterbank */
@@ -1257,7 +1347,11 @@ int rcf_pump_read_many(rcf_pump_t *p, const int *entries, int64_t *cursors, int 
  * where the channel's own reader stood; the channel's host-side reader position is left alone (an rcf_chan_read_costas
  * beside the subscription reads the same symbols again).  A stage switched off under its subscription starves the slot, as
  * a closed channel does; attached again (a fresh ring, symbol 0) the slot goes on with symbol 0 of the new attachment,
- * appended to its item count without a gap. */
+ * appended to its item count without a gap.
+ *   what = RCF_READ_CAPTURE (cf32) delivers the captured stream of rcf_chan_capture by the same rules: counted on the device,
+ * the slot owns its cursor there; a channel without the stage starves the slot.  A gather takes at most n_k samples after a
+ * block of n_k channel outputs: the writer decides as many samples as the detector saw, once it runs pre behind.
+ * (rcf_pump_start does not take it: subscribe it.) */
 int rcf_pump_subscribe(rcf_pump_t *p, int member, int chan_id, int what, float gain, int64_t *cursor);
 /* chan_id = RCF_SRC_PFB_BIN0 + bin (here and in rcf_pump_config_t.read_chans) with what = RCF_READ_FM subscribes ONE BIN of the
  * member's fused discriminator ring (rcf_pfb_fm_enable: every bin of the bank demodulated inside its launch) instead of a
@@ -1282,7 +1376,11 @@ int rcf_pump_subscribe(rcf_pump_t *p, int member, int chan_id, int what, float g
  * (n_k + 31) / 288 + 1 EDACS records, (n_k + 31) / 76 + 1 OSWs -- each the framing rule's densest case; what a stage has
  * ready beyond it leaves with the next block -- and min(the stage's ring, R) for the first gather of a stream.  With
  * `bound` the larger of the two blocks' figures a reader loses nothing while it lags fewer than R - 2 bound items.
- * RCF_EINVAL as well: no such member or channel; RCF_ECAP as well: no free slot. */
+ * RCF_EINVAL as well: no such member or channel; RCF_ECAP as well: no free slot.
+ *   what = RCF_HARD_CAPTURE delivers the records of rcf_chan_capture (32 bytes, R = out_ring_samples / 4) by the same rules;
+ * its per-block bound is 2 (n_k / (pre + hang + 2)) + 4 records: an OPEN and its CLOSE lie at least pre + hang + 1 samples
+ * apart, a CLOSE and the next OPEN at least 1, so two records cost pre + hang + 2 samples; the + 4 covers the span's two ends
+ * and the one window per attachment whose lead-in is clipped. */
 int rcf_pump_subscribe_hard(rcf_pump_t *p, int member, int chan_id, int what, int64_t *cursor);
 /* frees the slot (its channel may already be closed) */
 int rcf_pump_unsubscribe(rcf_pump_t *p, int entry);

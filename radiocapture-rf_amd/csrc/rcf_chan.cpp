@@ -332,6 +332,7 @@ int rcf_chan_set_fm_only(rcf_t *h, int chan_id, int on)
         if (c->audio) { set_error("channel %d carries a voice chain, which reads its IQ stream", chan_id); return RCF_ESTATE; }
         if (c->agc) { set_error("channel %d carries an AGC, which reads its IQ stream", chan_id); return RCF_ESTATE; }
         if (c->squelch) { set_error("channel %d carries the carrier detector, which reads its IQ stream", chan_id); return RCF_ESTATE; }
+        if (c->capture) { set_error("channel %d carries the capture stage, which reads its IQ stream", chan_id); return RCF_ESTATE; }
         for (auto &kv : h->chans)
             if (kv.second->src == chan_id) { set_error("channel %d reads channel %d's IQ stream", kv.first, chan_id); return RCF_ESTATE; }
     } else if (c->fm_only) {

@@ -11,7 +11,7 @@
 //   pfb_group_kernel_* / pfb5_group_kernel / pfbm_group_kernel   the chunks of every member of one bank shape   (pfb.hip, pfb5.hip, pfbm.hip)
 //   fir_small_kernel / fir_bank_kernel       stage-2 channels of all members of one (D, T) class (records concatenated)
 //   tap_finalize_group_kernel  the tapped bins of every member                               (tapfin.hip)
-//   disc / rot_fill, and the tail stages (TailStages, rcf_plan.h: fm_fir / agc / clock_mm / costas / fsk4 / slice / tsbk / edacs / osw / p25lc / squelch)   records
+//   disc / rot_fill, and the tail stages (TailStages, rcf_plan.h: fm_fir / agc / clock_mm / costas / fsk4 / slice / tsbk / edacs / osw / p25lc / squelch / capture)   records
 //                              concatenated: the group's table is the members' tables appended
 //   gather_rings_kernel        the read: new output of any channels of any members -> pinned host memory, one launch
 // What is not concatenable (matrix-core banks with their per-handle tap slabs, voice chains, scans, banks that still see
@@ -528,7 +528,7 @@ int rcf_group_sync(rcf_group_t *g)
 int rcf_group_read_many(rcf_group_t *g, int what, const int *members, const int *chan_ids, int n, float gain, void *out,
                         size_t cap_each, int64_t *counts)
 {
-    if (!g || !members || !chan_ids || !out || !counts || n < 0 || read_kind(what) < 0) {
+    if (!g || !members || !chan_ids || !out || !counts || n < 0 || row_kind(what) < 0) {
         set_error("bad batched read arguments");
         return RCF_EINVAL;
     }

@@ -454,6 +454,36 @@ struct PfbSquelchLaunch {
 };
 void launch_pfb_squelch(const PfbSquelchLaunch &p, hipStream_t s);
 int pfb_squelch_segment();
+// Carrier-operated capture behind a channel (capture.hip; definition: include/rcf.h at rcf_chan_capture): the detector above
+// as a gate with a lead-in and a hang time.  Per-channel running state, device resident, owned by capture_kernel; n_kept and
+// n_records are the counters of the stage's two streams (a counted reader fetches a counter and the word behind it)
+struct CaptureState {
+    double level;            // the detector's filter output after the last sample seen
+    int64_t n_seen;          // samples the detector walked, since the stage was (last) attached
+    int64_t n_decided;       // samples the writer decided: max(0, n_seen - pre)
+    int64_t n_kept;          // items of the captured stream
+    int64_t n_records;       // items of the record stream
+    int64_t n_windows;       // OPEN records among them
+    int64_t last_open;       // relative channel output index of the last open sample, -1: none
+    int64_t acc_open;        // open samples since the last CLOSE, and the largest level at one of them: what the next CLOSE reports
+    double acc_peak;
+    int32_t in_window;       // the last decided sample was kept
+    int32_t unmuted;         // the last sample seen was open
+};
+struct CaptureLaunch {
+    const float2 *iq_ring;
+    CaptureState *st;
+    float2 *cap_ring;        // the captured stream: cap_mask + 1 samples (>= 64: a chunk's survivors never meet themselves)
+    uint32_t *rec_ring;      // the records: rec_mask + 1 records of 8 words
+    int64_t n_lo;            // first relative channel output index that is new in this launch (the detector's)
+    int64_t a;               // the attach point: nothing before it is decided
+    int64_t hang;
+    int32_t n_k;
+    int32_t pre;             // the writer re-reads the IQ ring this far behind the detector
+    uint32_t cap_mask, rec_mask;
+    double thr, alpha;       // pow(10, threshold_db / 10), the filter's alpha
+};
+void launch_capture(const CaptureLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
 // the records' layouts as the kernels were compiled for them
 #pragma GCC diagnostic push
 #pragma GCC diagnostic ignored "-Winvalid-offsetof"

@@ -364,6 +364,7 @@ int plan_channel(rcf_t *h, BlockPlan &bp, ClassPlan &cp, Chan *c)
             });
     }
     if (c->squelch) stage(c->squelch->rec, c->squelch->from, bp.tails.sqf);
+    if (c->capture) stage(c->capture->rec, c->capture->from, bp.tails.capf);
     if (c->audio && s.a_n > 0) {
         AudioLaunch al = c->audio->rec;
         al.n_lo = s.a_lo;

@@ -1,5 +1,5 @@
 // rcf_plan.h -- the per-block schedule: what one commit of one front-end launches, built on the host first.  The stages
-// behind the FIRs (symbol filters, AGCs, the three symbol loops, the slicers behind the loops, the TSBK, EDACS, OSW and P25 voice stages behind the slicers, the carrier detectors) are one table, TailStages: a block's plan and a group's
+// behind the FIRs (symbol filters, AGCs, the three symbol loops, the slicers behind the loops, the TSBK, EDACS, OSW and P25 voice stages behind the slicers, the carrier detectors, the capture stages) are one table, TailStages: a block's plan and a group's
 // block each hold one, and the planner, the group's merge and the launcher visit it through TailStages::each.
 #pragma once
 #include <chrono>
@@ -94,6 +94,7 @@ struct TailStages {
     StageRecs<OswLaunch> osf;          // SmartNet OSWs, behind the slicers likewise
     StageRecs<P25lcLaunch> lcf;        // P25 voice data units, behind the slicers likewise
     StageRecs<SquelchLaunch> sqf;      // carrier detect: it reads the IQ rings the FIRs and the tap finalize wrote
+    StageRecs<CaptureLaunch> capf;     // carrier-operated capture: it reads the same rings, this block's samples and `pre` before them
     template <class F, class... T> static void each(F &&f, T &...t)
     {
         f(RCF_T_DISC, launch_fm_fir, t.symf...);
@@ -107,6 +108,7 @@ struct TailStages {
         f(RCF_T_SLICE, launch_osw, t.osf...);
         f(RCF_T_SLICE, launch_p25lc, t.lcf...);
         f(kNoTimingClass, launch_squelch, t.sqf...);
+        f(kNoTimingClass, launch_capture, t.capf...);
     }
     template <class Rec> StageRecs<Rec> &of()      // the stage whose records are plain StageRecs<Rec>: found at compile time
     {

@@ -233,7 +233,11 @@ void Gather::counted(int e, const Stream &st)
     // ever come without a slicer)
     const Chan::Slicer *sl = t.c->slicer.get();
     const int64_t hard = hard_bound(t.kind, n_k, sl ? sl->rec.bps : 2);
-    const int64_t steady = hard < 0 ? steady_bound(n_k, st.interp, st.decim) : hard;
+    // (the capture stage's two streams: what the gate's rule allows, capture_bound / capture_rec_bound of rcf_streams.h)
+    const Chan::Capture *cp = t.c->capture.get();
+    const int64_t steady = t.kind == kCapture ? capture_bound(n_k)
+                         : t.kind == kCaptureRec ? capture_rec_bound(n_k, cp ? cp->rec.pre : 0, cp ? cp->rec.hang : 0)
+                         : hard < 0 ? steady_bound(n_k, st.interp, st.decim) : hard;
     const int64_t R = (int64_t)p->ring_items(e);
     const int64_t bound = std::min<int64_t>(fresh || again ? (int64_t)st.cap : steady, R);
     int64_t *cs = p->d_cstate + (size_t)e * 4;
@@ -711,6 +715,8 @@ static int pump_subscribe(rcf_pump *p, int member, int chan_id, int what, int ki
 
 int rcf_pump_subscribe(rcf_pump_t *p, int member, int chan_id, int what, float gain, int64_t *cursor)
 {
+    // (the captured stream of rcf_chan_capture stands behind the table: the one row there this entry point delivers)
+    if (p && what == RCF_READ_CAPTURE && chan_id < RCF_SRC_PFB_BIN0) return pump_subscribe(p, member, chan_id, what, kCapture, 1.0f, cursor);
     if (!p || stream_kind(what) < 0 || !kStreams[stream_kind(what)].pumped) { set_error("bad subscription"); return RCF_EINVAL; }
     return pump_subscribe(p, member, chan_id, what, stream_kind(what), gain, cursor);
 }
@@ -719,8 +725,8 @@ int rcf_pump_subscribe(rcf_pump_t *p, int member, int chan_id, int what, float g
 // by; this one admits exactly the counted uint32 rows, of the table and behind it
 int rcf_pump_subscribe_hard(rcf_pump_t *p, int member, int chan_id, int what, int64_t *cursor)
 {
-    const int kind = read_kind(what);
-    if (!p || kind < 0 || hard_bound(kind, 0, 1) < 0 || chan_id >= RCF_SRC_PFB_BIN0) { set_error("bad subscription: %d is no stream behind a slicer", what); return RCF_EINVAL; }
+    const int kind = row_kind(what);
+    if (!p || kind < 0 || (hard_bound(kind, 0, 1) < 0 && kind != kCaptureRec) || chan_id >= RCF_SRC_PFB_BIN0) { set_error("bad subscription: %d is no stream behind a slicer", what); return RCF_EINVAL; }
     if (slot_items(kind, (int64_t)p->out_cap) < 16) {
         set_error("host rings of %zu x 8 bytes hold fewer than 16 items of stream %d (rcf_pump_config_t.out_ring_samples)", p->out_cap, what);
         return RCF_ECAP;

@@ -24,7 +24,7 @@ template <class R> void frames_row(Chan *c, Stream *s)
 }
 // ring, reader and counter of every row of kStreams and of the readers' rows behind it, in their order; a row that leaves the
 // ring null is refused
-void (*const kRows[kReadKindsEnd])(Chan *, Stream *) = {
+void (*const kRows[kReadRowsEnd])(Chan *, Stream *) = {
     [](Chan *c, Stream *s) { if (!c->fm_only) plain_row(c, s, c->d_iq, &c->rd_iq); },
     [](Chan *c, Stream *s) { plain_row(c, s, c->d_fm, &c->rd_fm); },
     [](Chan *c, Stream *s) { if (c->agc) plain_row(c, s, c->agc->rec.agc_ring, &c->agc->rd); },
@@ -39,6 +39,8 @@ void (*const kRows[kReadKindsEnd])(Chan *, Stream *) = {
     frames_row<Chan::Slicer::Edacs>,
     frames_row<Chan::Slicer::Osw>,
     frames_row<Chan::Slicer::P25lc>,
+    [](Chan *c, Stream *s) { if (Chan::Capture *k = c->capture.get()) { counted_row(s, k->rec.cap_ring, &k->rd, &k->rec.st->n_kept, k->serial); s->cap = k->cap; } },
+    [](Chan *c, Stream *s) { if (Chan::Capture *k = c->capture.get()) { counted_row(s, k->rec.rec_ring, &k->rd_rec, &k->rec.st->n_records, k->serial); s->cap = k->rec_cap; } },
 };
 
 }  // namespace
@@ -190,7 +192,7 @@ static void chan_entry(rcf_t *h, int chan_id, int kind, float gain, void *out, s
 int read_many(PinnedStage &stage, hipStream_t stream, rcf_t *const *hs, size_t n_hs, const int *ms, const int *chan_ids, int n,
               int what, float gain, void *out, size_t cap_each, int64_t *counts)
 {
-    const int kind = read_kind(what);
+    const int kind = row_kind(what);
     const size_t row = cap_each * read_row(kind).item_w * 4;
     std::vector<ReadEntry> es((size_t)n);
     for (int i = 0; i < n; ++i) {
@@ -215,7 +217,7 @@ static int64_t chan_read_one(rcf_t *h, int chan_id, int what, float gain, void *
     if (set_dev(h)) return RCF_EHIP;
     int64_t n = 0;
     ReadEntry e;
-    chan_entry(h, chan_id, read_kind(what), gain, out, max_items, &n, &e);
+    chan_entry(h, chan_id, row_kind(what), gain, out, max_items, &n, &e);
     return e.s.ring ? read_one(h, e.s, e.gain, out, max_items) : n;
 }
 
@@ -233,11 +235,13 @@ int64_t rcf_chan_read_tsbk(rcf_t *h, int chan_id, uint32_t *out, size_t n) { ret
 int64_t rcf_chan_read_edacs(rcf_t *h, int chan_id, uint32_t *out, size_t n) { return chan_read_one(h, chan_id, RCF_HARD_EDACS, 1.0f, out, n); }
 int64_t rcf_chan_read_osw(rcf_t *h, int chan_id, uint32_t *out, size_t n) { return chan_read_one(h, chan_id, RCF_HARD_OSW, 1.0f, out, n); }
 int64_t rcf_chan_read_p25lc(rcf_t *h, int chan_id, uint32_t *out, size_t n) { return chan_read_one(h, chan_id, RCF_HARD_P25LC, 1.0f, out, n); }
+int64_t rcf_chan_read_capture(rcf_t *h, int chan_id, float *out, size_t n) { return chan_read_one(h, chan_id, RCF_READ_CAPTURE, 1.0f, out, n); }
+int64_t rcf_chan_read_capture_rec(rcf_t *h, int chan_id, uint32_t *out, size_t n) { return chan_read_one(h, chan_id, RCF_HARD_CAPTURE, 1.0f, out, n); }
 
 int rcf_chan_read_many(rcf_t *h, int what, const int *chan_ids, int n_chans, float gain, void *out, size_t cap_each,
                        int64_t *counts)
 {
-    if (!h || !chan_ids || !out || !counts || n_chans < 0 || read_kind(what) < 0) {
+    if (!h || !chan_ids || !out || !counts || n_chans < 0 || row_kind(what) < 0) {
         set_error("bad batched read arguments");
         return RCF_EINVAL;
     }
@@ -287,6 +291,15 @@ int rcf_chan_slicer_rings(rcf_t *h, int chan_id, void **word_ring, size_t *word_
     FIND_CHAN(h, chan_id, c);
     const int rc = stream_ring(h, c, kHardBits, word_ring, word_capacity);
     return rc != RCF_OK ? rc : stream_ring(h, c, kHardSync, hit_ring, hit_capacity);
+}
+int rcf_chan_capture_rings(rcf_t *h, int chan_id, void **cap_ring, size_t *capacity, void **rec_ring, size_t *rec_capacity)
+{
+    if (!h) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    const int rc = stream_ring(h, c, kCapture, cap_ring, capacity);
+    return rc != RCF_OK ? rc : stream_ring(h, c, kCaptureRec, rec_ring, rec_capacity);
 }
 int rcf_chan_tsbk_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity) { return chan_rings(h, chan_id, kTsbk, true, rec_ring, nullptr, capacity); }
 int rcf_chan_edacs_ring(rcf_t *h, int chan_id, void **rec_ring, size_t *capacity) { return chan_rings(h, chan_id, kEdacs, true, rec_ring, nullptr, capacity); }

@@ -1,7 +1,8 @@
 // rcf_stage.cpp -- the optional stages behind a channel's rings (the records of Chan, rcf_state.h): the P25 symbol filter,
 // the feed-forward AGC, the SmartNet / EDACS symbol clock, the P25 CQPSK Gardner / Costas loop, the P25 C4FM symbol loop and
 // the analog voice chain, the slicer behind one of the loops and the frame decoder behind the slicer (P25 trunking blocks,
-// EDACS control frames, SmartNet OSWs or P25 voice data units).
+// EDACS control frames, SmartNet OSWs or P25 voice data units), the carrier detector and the carrier-operated capture over the IQ
+// stream.
 // Attach, off, and what they produced.
 // An attach function allocates into Fresh<> holders and builds the new record completely; only then is it swapped into
 // the channel and the old one released.  A HIP call that fails before that leaves the channel as it was.
@@ -18,6 +19,7 @@
 #include "p25lc_core.hpp"      // (kP25lcRecWords, kP25lcFlagCorrect)
 #include "nid_core.hpp"        // (kNidFlagBch)
 #include "squelch_core.hpp"    // (squelch_threshold)
+#include "capture_core.hpp"    // (kCaptureRecWords, CaptureRec)
 static_assert(rcfx::kP25lcFlagEs == RCF_P25LC_ES << 1 && rcfx::kP25lcFlagErasures == RCF_P25LC_ERASURES << 1, "the options travel in P25lcLaunch::flags behind kP25lcFlagCorrect");
 
 namespace rcfx {
@@ -32,6 +34,7 @@ void Chan::Slicer::release(rcf_t *h)                 // one allocation; the fram
     rec = SliceLaunch{};
 }
 void Chan::Squelch::release(rcf_t *h) { bury(h, rec.st); rec = SquelchLaunch{}; }
+void Chan::Capture::release(rcf_t *h) { bury(h, rec.cap_ring); rec = CaptureLaunch{}; }       // one allocation
 void Chan::Audio::release(rcf_t *h) { bury(h, rec.st); bury(h, rec.a_ring); bury(h, const_cast<float *>(rec.lpf)); rec = AudioLaunch{}; }
 
 }  // namespace rcfx
@@ -604,6 +607,105 @@ int rcf_chan_squelch_state(rcf_t *h, int chan_id, rcf_squelch_state_t *out)
     out->level = st.level;
     out->n_seen = st.n_seen; out->n_open = st.n_open; out->first_open = st.first_open; out->last_open = st.last_open;
     out->unmuted = st.unmuted;
+    return RCF_OK;
+}
+
+// ---- carrier-operated capture over the IQ stream (capture.hip)
+static_assert(read_row(kCaptureRec).item_w == kCaptureRecWords && sizeof(rcf_capture_rec_t) == 4 * kCaptureRecWords && sizeof(CaptureRec) == sizeof(rcf_capture_rec_t) &&
+              offsetof(rcf_capture_rec_t, sample) == 8 && offsetof(rcf_capture_rec_t, pos) == 16 && offsetof(rcf_capture_rec_t, peak) == 24,
+              "the stream table's words per record and the ABI's record are the kernel's");
+static_assert(RCF_CAPTURE_OPEN == kCaptureOpen && RCF_CAPTURE_CLOSE == kCaptureClose, "the record kinds");
+
+// the most outputs one block of the handle can give c (rcf.h at rcf_chan_capture: M_0 = block capacity, M_i = M_(i-1) / D_i + 1
+// down the channel's chain of decimations, the filterbank's first for a channel on a bin)
+static int64_t max_block_outputs(rcf_t *h, const Chan *c)
+{
+    int64_t m = (int64_t)h->block_cap;
+    if (c->src >= RCF_SRC_PFB_BIN0) m = m / std::max(1, h->pfb.D) + 1;
+    else if (c->src >= 0) {
+        auto it = h->chans.find(c->src);
+        if (it != h->chans.end()) m = max_block_outputs(h, it->second.get());
+    }
+    return m / std::max(1, c->D) + 1;
+}
+
+int rcf_chan_capture(rcf_t *h, int chan_id, const rcf_capture_params_t *p)
+{
+    if (!h) return RCF_EINVAL;
+    size_t cap = 0, rec_cap = 256;
+    if (p) {
+        if (!std::isfinite(p->threshold_db) || !(p->alpha > 0.0 && p->alpha <= 1.0)) {
+            set_error("capture: threshold %g dB is not finite, or alpha %g outside (0, 1]", p->threshold_db, p->alpha);
+            return RCF_EINVAL;
+        }
+        if (p->pre < 0 || p->hang < 0 || p->hang > (int64_t(1) << 60)) {
+            set_error("capture: pre %lld or hang %lld is negative (or hang beyond 2^60)", (long long)p->pre, (long long)p->hang);
+            return RCF_EINVAL;
+        }
+        if (p->capacity > (1u << 26) || p->rec_capacity > (1u << 20)) {
+            set_error("capture: capacity %u beyond 2^26 samples, or rec_capacity %u beyond 2^20 records", p->capacity, p->rec_capacity);
+            return RCF_EINVAL;
+        }
+        cap = p->capacity;
+        if (p->rec_capacity) rec_cap = p->rec_capacity;
+    }
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!p) return stage_off(h, c->capture);
+    if (c->fm_only) { set_error("channel %d exposes its discriminator only: the capture stage reads IQ", chan_id); return RCF_ESTATE; }
+    const int64_t most = max_block_outputs(h, c);
+    if (p->pre + most > (int64_t)h->out_cap) {
+        set_error("capture: pre %lld + the %lld outputs a block can give channel %d > ring capacity %zu", (long long)p->pre, (long long)most, chan_id, h->out_cap);
+        return RCF_ECAP;
+    }
+    cap = pow2_at_least(std::max<size_t>(cap ? cap : h->out_cap, 64));
+    rec_cap = pow2_at_least(std::max<size_t>(rec_cap, 16));
+    std::unique_ptr<Chan::Capture> k(new Chan::Capture);
+    CaptureLaunch &r = k->rec;
+    r.iq_ring = c->d_iq;
+    r.thr = squelch_threshold(p->threshold_db);
+    r.alpha = p->alpha;
+    r.pre = (int32_t)p->pre;
+    r.hang = p->hang;
+    r.cap_mask = (uint32_t)cap - 1;
+    r.rec_mask = (uint32_t)rec_cap - 1;
+    k->cap = (uint32_t)cap;
+    k->rec_cap = (uint32_t)rec_cap;
+    CaptureState st0{};
+    st0.last_open = -1;
+    // one allocation, in words: captured ring | record ring | the state record's slot (cap >= 64: its 64-bit fields are aligned)
+    constexpr size_t kStateWords = 256 / sizeof(uint32_t);
+    static_assert(sizeof(CaptureState) <= 256, "the state's slot");
+    const size_t recs_at = cap * 2, state_at = recs_at + rec_cap * kCaptureRecWords;
+    Fresh<uint32_t> fresh;
+    RCF_HIP(fresh.alloc(state_at + kStateWords));
+    if (!hip_ok(hipMemcpy(fresh.p + state_at, &st0, sizeof(st0), hipMemcpyHostToDevice), "hipMemcpy(capture state)")) return RCF_EHIP;
+    uint32_t *base = fresh.take();
+    r.cap_ring = reinterpret_cast<float2 *>(base);
+    r.rec_ring = base + recs_at;
+    r.st = reinterpret_cast<CaptureState *>(base + state_at);
+    r.a = k->from = c->pos.produced;                             // the attach point: level 0 from the channel's next output on
+    drop_stage(h, c->capture);
+    c->capture = std::move(k);
+    ++h->chans_epoch;
+    return RCF_OK;
+}
+
+int rcf_chan_capture_state(rcf_t *h, int chan_id, rcf_capture_state_t *out)
+{
+    if (!h || !out) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!c->capture) { set_error(read_row(kCapture).refusal, chan_id); return RCF_ESTATE; }
+    CaptureState st{};
+    const int rc = stage_state(h, c->capture->rec.st, &st, sizeof(st));
+    if (rc != RCF_OK) return rc;
+    out->level = st.level;
+    out->n_seen = st.n_seen; out->n_decided = st.n_decided; out->n_kept = st.n_kept; out->n_records = st.n_records;
+    out->n_windows = st.n_windows; out->last_open = st.last_open;
+    out->in_window = st.in_window; out->unmuted = st.unmuted;
     return RCF_OK;
 }
 

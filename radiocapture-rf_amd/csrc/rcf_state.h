@@ -95,7 +95,6 @@ struct Chan {
         int64_t blk_before = 0, blk_after = 0;
         uint64_t blk_serial = 0;
     } pos;
-    int64_t rd_iq = 0, rd_fm = 0;
     // ---- the optional stages behind the rings, one record each; null = the channel has no such stage.  What a second
     // call of the attaching function means:
     //   stage                                  ring on re-call       from         read cursor
@@ -224,9 +223,25 @@ struct Chan {
         size_t reach() const { return 0; }                               // the level is in the state record: no look-back
         void release(rcf_t *h);
     };
+    // Carrier-operated capture over the IQ stream (rcf_chan_capture): the detector as a gate.  One allocation, which starts at
+    // rec.cap_ring: captured ring of cap samples | record ring of rec_cap records | the state record, in a slot of 256 bytes.
+    // A second call: new rings and state, cursors 0, `from` = `produced`
+    struct Capture {
+        CaptureLaunch rec{};            // owns cap_ring (rec_ring and st lie behind it)
+        int64_t from = 0;
+        uint32_t cap = 0, rec_cap = 0;
+        int64_t rd = 0, rd_rec = 0;     // items handed to the two streams' readers
+        const uint64_t serial = next_stage_serial();
+        size_t reach() const { return (size_t)std::max(1, rec.pre); }    // the writer re-reads the IQ ring `pre` samples back
+        void release(rcf_t *h);
+    };
     std::unique_ptr<Audio> audio;
     std::unique_ptr<Slicer> slicer;
     std::unique_ptr<Squelch> squelch;
+    std::unique_ptr<Capture> capture;
+    // (the two plain readers' cursors: planning a block never looks at them, so they stand behind the stage holders it does
+    // look at, which fill the fourth prefetched line to its end)
+    int64_t rd_iq = 0, rd_fm = 0;
     // the one list of them: f(the stage's holder -- null when the channel has no such stage --, the bytes of its launch
     // record, whether its reach() is into rings of its own instead of the channel's)
     template <class F> void for_each_stage(F &&f)
@@ -235,6 +250,7 @@ struct Chan {
         f(costas, sizeof(CostasLaunch), false); f(fsk4, sizeof(Fsk4Launch), false); f(audio, sizeof(AudioLaunch), true);
         f(slicer, sizeof(SliceLaunch) + Slicer::max_frames_launch() + 64, false);    // (with the frame decoder it may carry)
         f(squelch, sizeof(SquelchLaunch), false);
+        f(capture, sizeof(CaptureLaunch), false);
     }
     // ---- the rest
     float incr[2] = {1.f, 0.f};   // exact rotator: what GNU Radio iterates
@@ -247,7 +263,7 @@ struct Chan {
 #pragma GCC diagnostic push
 #pragma GCC diagnostic ignored "-Winvalid-offsetof"
 static_assert(offsetof(Chan, pos) + sizeof(Chan::Pos) <= 192, "what plan_channel advances: inside the first three cache lines");
-static_assert(offsetof(Chan, squelch) + sizeof(std::unique_ptr<Chan::Squelch>) <= 256, "what plan_channel reads: inside the four prefetched lines");
+static_assert(offsetof(Chan, capture) + sizeof(std::unique_ptr<Chan::Capture>) <= 256, "what plan_channel reads: inside the four prefetched lines");
 #pragma GCC diagnostic pop
 
 struct Pfb {

@@ -48,11 +48,20 @@ static_assert(stream_kind(RCF_READ_AUDIO) == kAudio && stream_kind(RCF_HARD_SYNC
 // refused by name: 50 stands in the suite as the readers' example of "no such stream", so the OSW stage's is 51.
 // kAllReadKinds in turn is where they ended when the P25 voice stage's row came (the suite pins it as it pins kReadKinds, and
 // 52 beside 50 as no stream: the row's number is 53); kReadKindsEnd ends them all now, and the readers' loops run to it.
-enum : int { kEdacs = kStreamKinds, kReadKinds, kOsw = kReadKinds, kAllReadKinds, kP25lc = kAllReadKinds, kReadKindsEnd };
-constexpr StreamKind kReadOnlyStreams[kReadKindsEnd - kStreamKinds] = {
+// kReadKindsEnd in turn is where they ended when the capture stage's two rows came (rcf_chan_capture; the suite pins it too):
+// 24, the first row behind the table that is not uint32 -- counted cf32, which rcf_pump_subscribe admits by name, as
+// stream_kind and the table do not move --, and 56, its records, which rcf_pump_subscribe_hard delivers.  kReadRowsEnd ends
+// them all now.  read_kind, too, stays what its consumers compiled against -- the suite walks it over 0 .. 60 and pins the
+// streams it finds --: it goes on ending at kReadKindsEnd, and the readers and the pump look a `what` up with row_kind, which
+// is read_kind and the rows behind kReadKindsEnd.
+enum : int { kEdacs = kStreamKinds, kReadKinds, kOsw = kReadKinds, kAllReadKinds, kP25lc = kAllReadKinds, kReadKindsEnd,
+             kCapture = kReadKindsEnd, kCaptureRec, kReadRowsEnd };
+constexpr StreamKind kReadOnlyStreams[kReadRowsEnd - kStreamKinds] = {
     {RCF_HARD_EDACS,  8, true,  true,  false, "channel %d has no EDACS stage (rcf_chan_edacs)"},
     {RCF_HARD_OSW,    8, true,  true,  false, "channel %d has no OSW stage (rcf_chan_osw)"},
     {RCF_HARD_P25LC,  8, true,  true,  false, "channel %d has no P25 voice stage (rcf_chan_p25lc)"},
+    {RCF_READ_CAPTURE, 2, false, true, true,  "channel %d has no capture stage (rcf_chan_capture)"},
+    {RCF_HARD_CAPTURE, 8, true,  true,  false, "channel %d has no capture stage (rcf_chan_capture)"},
 };
 constexpr const StreamKind &read_row(int kind) { return kind < kStreamKinds ? kStreams[kind] : kReadOnlyStreams[kind - kStreamKinds]; }
 // the readers' kind of `what`: a row of the table, or one behind it; -1: no such stream
@@ -63,10 +72,22 @@ constexpr int read_kind(int what)
         if (read_row(k).what == what) return k;
     return -1;
 }
+// the row of `what` among ALL rows: what the readers and the pump's subscriptions take; -1: no such stream
+constexpr int row_kind(int what)
+{
+    if (read_kind(what) >= 0) return read_kind(what);
+    for (int k = kReadKindsEnd; k < kReadRowsEnd; ++k)
+        if (read_row(k).what == what) return k;
+    return -1;
+}
 static_assert(read_kind(RCF_HARD_EDACS) == kEdacs && stream_kind(RCF_HARD_EDACS) == -1 && read_kind(RCF_HARD_TSBK) == kTsbk && !read_row(kEdacs).pumped,
               "the readers' rows go on behind the table; the pump finds none of them");
 static_assert(read_kind(RCF_HARD_OSW) == kOsw && stream_kind(RCF_HARD_OSW) == -1 && !read_row(kOsw).pumped && read_kind(50) == -1, "likewise");
 static_assert(read_kind(RCF_HARD_P25LC) == kP25lc && stream_kind(RCF_HARD_P25LC) == -1 && !read_row(kP25lc).pumped && read_kind(52) == -1, "likewise");
+static_assert(row_kind(RCF_READ_CAPTURE) == kCapture && row_kind(RCF_HARD_CAPTURE) == kCaptureRec && read_kind(RCF_READ_CAPTURE) == -1 &&
+              read_kind(RCF_HARD_CAPTURE) == -1 && read_row(kCapture).pumped && !read_row(kCaptureRec).pumped && row_kind(21) == -1 &&
+              row_kind(50) == -1 && row_kind(52) == -1 && row_kind(RCF_HARD_P25LC) == kP25lc,
+              "likewise; the captured stream is the one row behind the table that rcf_pump_subscribe delivers");
 
 // A reader that has fallen more than a ring of `cap` items behind lost what the ring overwrote: its cursor is raised to the
 // oldest item the ring still holds (the ring holds the cap items before `newest`).  Returns how many items [*cursor, end) it
@@ -117,6 +138,19 @@ inline int64_t hard_bound(int kind, int64_t n_k, int bps)
     case kOsw:      return (n_k + 31) / 76 + 1;
     default:        return -1;
     }
+}
+// The capture stage's two streams (rcf_chan_capture) after a block of n_k channel outputs.  The writer decides at most as
+// many samples as the detector saw -- exactly as many once it runs pre behind --, so a block adds at most n_k captured
+// samples.  Records: a block's events lie among n_k consecutive decided samples.  An OPEN and its CLOSE lie at least
+// pre + hang + 1 apart (one open sample keeps that many), a CLOSE and the next OPEN at least 1 (two keyings pre + hang + 1
+// apart leave one sample out), so two records cost pre + hang + 2 samples: E records span at least
+// floor((E - 1) / 2) (pre + hang + 2) <= n_k - 1, E <= 2 floor((n_k - 1) / (pre + hang + 2)) + 2.  One window per attachment may be
+// shorter -- the one whose lead-in is clipped at the attach point, hang + 1 at the least --, which the + 4 below covers
+inline int64_t capture_bound(int64_t n_k) { return n_k < 0 ? 0 : n_k; }
+inline int64_t capture_rec_bound(int64_t n_k, int64_t pre, int64_t hang)
+{
+    if (n_k < 0) n_k = 0;
+    return 2 * (n_k / (pre + hang + 2)) + 4;
 }
 // a plain slot of the pump: of the n items from *cursor on, those a host ring of `room` items cannot hold are skipped
 inline int64_t ring_room(int64_t *cursor, int64_t n, int64_t room)

@@ -50,6 +50,7 @@ SYMBOLS = [
     "rcf_pfb_tap_leakage", "rcf_set_rotator", "rcf_timing_stride", "rcf_set_stage2_lag",
     "rcf_group_open", "rcf_group_close", "rcf_group_size", "rcf_group_push", "rcf_group_commit", "rcf_group_read_many",
     "rcf_chan_squelch", "rcf_chan_squelch_state", "rcf_pfb_squelch", "rcf_pfb_squelch_read", "rcf_pfb_squelch_segment",
+    "rcf_chan_capture", "rcf_chan_capture_state", "rcf_chan_read_capture", "rcf_chan_read_capture_rec", "rcf_chan_capture_rings",
     "rcf_group_sync", "rcf_pump_start", "rcf_pump_stats", "rcf_pump_written", "rcf_pump_read", "rcf_pump_read_many", "rcf_pump_subscribe", "rcf_pump_unsubscribe", "rcf_pump_stop",
     "rcf_pump_subscribe_hard",
 ]
@@ -70,6 +71,11 @@ HARD_OSW = 51
 # ... and of the P25 voice stage (RCF_HARD_P25LC): records of 8 uint32, one per frame
 HARD_P25LC = 53
 P25LC_ES, P25LC_ERASURES = 1, 2   # rcf_chan_p25lc_opt's options (RCF_P25LC_*)
+# the two streams of the capture stage (rcf_chan_capture): RCF_READ_CAPTURE, cf32 samples, and RCF_HARD_CAPTURE, records of
+# CAPTURE_REC_DTYPE; the pump delivers the first through rcf_pump_subscribe and the second through rcf_pump_subscribe_hard
+READ_CAPTURE, HARD_CAPTURE = 24, 56
+CAPTURE_OPEN, CAPTURE_CLOSE = 1, 2
+_CAPTURE_WHAT = {"capture": READ_CAPTURE, "capture_rec": HARD_CAPTURE}
 _HARD_WHAT = {"hard": HARD_BITS, "sync": HARD_SYNC, "tsbk": HARD_TSBK, "edacs": HARD_EDACS, "osw": HARD_OSW, "p25lc": HARD_P25LC}
 # a record of RCF_HARD_TSBK (rcf.h at rcf_chan_tsbk): word 0 (see tsbk_fields), the low 32 bits of k, the 12 decoded octets,
 # the NID's 8 octets, frame_dibits
@@ -177,6 +183,19 @@ class SquelchState(C.Structure):
     """rcf_squelch_state_t (include/rcf.h)"""
     _fields_ = [("level", C.c_double), ("n_seen", C.c_int64), ("n_open", C.c_int64), ("first_open", C.c_int64),
                 ("last_open", C.c_int64), ("unmuted", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class CaptureParams(C.Structure):
+    """rcf_capture_params_t (include/rcf.h)"""
+    _fields_ = [("threshold_db", C.c_double), ("alpha", C.c_double), ("pre", C.c_int64), ("hang", C.c_int64),
+                ("capacity", C.c_uint32), ("rec_capacity", C.c_uint32)]
+
+
+class CaptureState(C.Structure):
+    """rcf_capture_state_t (include/rcf.h)"""
+    _fields_ = [("level", C.c_double), ("n_seen", C.c_int64), ("n_decided", C.c_int64), ("n_kept", C.c_int64),
+                ("n_records", C.c_int64), ("n_windows", C.c_int64), ("last_open", C.c_int64), ("in_window", C.c_int32),
+                ("unmuted", C.c_int32)]
 
 
 class SlicerParams(C.Structure):
@@ -293,7 +312,9 @@ def p25lc_fields(records):
                 n_bad=((t >> 22) & 63).astype(np.uint8))
 
 
-_RECORD_DTYPE = {HARD_TSBK: TSBK_DTYPE, HARD_EDACS: EDACS_DTYPE, HARD_OSW: OSW_DTYPE, HARD_P25LC: P25LC_DTYPE}
+# a record of RCF_HARD_CAPTURE (rcf_capture_rec_t, rcf.h at rcf_chan_capture)
+CAPTURE_REC_DTYPE = np.dtype([("kind", "<u4"), ("n_open", "<u4"), ("sample", "<i8"), ("pos", "<i8"), ("peak", "<f4"), ("reserved_", "<u4")])
+_RECORD_DTYPE = {HARD_TSBK: TSBK_DTYPE, HARD_EDACS: EDACS_DTYPE, HARD_OSW: OSW_DTYPE, HARD_P25LC: P25LC_DTYPE, HARD_CAPTURE: CAPTURE_REC_DTYPE}
 
 
 def widen_hits(items, n_symbols):
@@ -429,6 +450,11 @@ def lib():
         "rcf_pfb_squelch_read": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_uint32), C.c_int,
                                            C.POINTER(i64)]),
         "rcf_pfb_squelch_segment": (C.c_int, []),
+        "rcf_chan_capture": (C.c_int, [vp, C.c_int, C.POINTER(CaptureParams)]),
+        "rcf_chan_capture_state": (C.c_int, [vp, C.c_int, C.POINTER(CaptureState)]),
+        "rcf_chan_read_capture": (i64, [vp, C.c_int, fp, sz]),
+        "rcf_chan_read_capture_rec": (i64, [vp, C.c_int, C.POINTER(C.c_uint32), sz]),
+        "rcf_chan_capture_rings": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]),
         "rcf_pfb_fm_ring": (C.c_int, [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(i64)]),
         "rcf_pfb_fm_lost": (i64, [vp]),
         "rcf_pfb_rings": (C.c_int, [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz)]),
@@ -503,6 +529,8 @@ def _read_what(what, stages=False):
         return _STAGE_WHAT[what]
     if stages and what in _HARD_WHAT:
         return _HARD_WHAT[what]
+    if stages and what in _CAPTURE_WHAT:           # the capture stage's "capture" (cf32) and "capture_rec" (CAPTURE_REC_DTYPE)
+        return _CAPTURE_WHAT[what]
     return READ_IQ if what == "iq" else READ_AGC if what == "agc" else READ_FM
 
 
@@ -512,7 +540,7 @@ def _read_dtype(what):
     w = _read_what(what, True)
     if w in _RECORD_DTYPE:
         return _RECORD_DTYPE[w]
-    return np.complex64 if w in (READ_IQ, READ_AGC) else np.uint32 if w in (HARD_BITS, HARD_SYNC) else np.float32
+    return np.complex64 if w in (READ_IQ, READ_AGC, READ_CAPTURE) else np.uint32 if w in (HARD_BITS, HARD_SYNC) else np.float32
 
 
 def _check(rc):
@@ -1054,6 +1082,37 @@ class Frontend:
         st.pop("reserved_", None)
         return st
 
+    def chan_capture(self, cid, threshold_db, alpha=0.1, pre=0, hang=0, capacity=0, rec_capacity=0):
+        """the carrier detector as a gate on the channel's IQ stream (rcf_chan_capture, which defines the stage): the
+        samples of the channel's transmissions only, `pre` samples of lead-in and `hang` samples of hang time included, and
+        an OPEN and a CLOSE record per transmission.  Every call starts both streams again at item 0, from the channel's
+        next output on; threshold_db=None detaches the stage"""
+        if threshold_db is None:
+            _check(lib().rcf_chan_capture(self._h, cid, None))
+            return
+        p = CaptureParams(float(threshold_db), float(alpha), int(pre), int(hang), int(capacity), int(rec_capacity))
+        _check(lib().rcf_chan_capture(self._h, cid, C.byref(p)))
+
+    def chan_capture_state(self, cid) -> dict:
+        """the stage's state as of the last block: level, n_seen, n_decided, n_kept, n_records, n_windows, last_open (-1:
+        none), in_window, unmuted (rcf_chan_capture_state; syncs the stream)"""
+        return self._state_of(lib().rcf_chan_capture_state, cid, CaptureState)
+
+    def chan_read_capture(self, cid, max_samples=1 << 20) -> np.ndarray:
+        """unread samples of the captured stream, oldest first (complex64)"""
+        return self._read_ring(lib().rcf_chan_read_capture, cid, max_samples, np.complex64)
+
+    def chan_read_capture_rec(self, cid, max_records=1 << 12) -> np.ndarray:
+        """unread records of the capture stage, oldest first: a structured array of CAPTURE_REC_DTYPE"""
+        return self._read_records(lib().rcf_chan_read_capture_rec, cid, max_records, CAPTURE_REC_DTYPE)
+
+    def chan_capture_rings(self, cid):
+        """(captured ring's device pointer, its capacity in samples, record ring's device pointer, its capacity in records)
+        (rcf_chan_capture_rings)"""
+        p, cap, r, rcap = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t()
+        _check(lib().rcf_chan_capture_rings(self._h, cid, C.byref(p), C.byref(cap), C.byref(r), C.byref(rcap)))
+        return p.value, cap.value, r.value, rcap.value
+
     def chan_slicer(self, cid, source, mode=None, levels=(-2.0, 0.0, 2.0, 4.0), sync_word=0, sync_bits=0, sync_max_errors=0,
                     hit_capacity=0, sync_both=0):
         """hard decisions behind one of the channel's symbol loops (rcf_chan_slicer): source READ_CLOCK / READ_COSTAS /
@@ -1395,7 +1454,8 @@ class Pump:
     start ((member, channel id) pairs delivered as `what` x `gain`) and change while it runs (subscribe / unsubscribe, up to
     `max_read` at a time).  what: "iq", "fm", "agc" or a stage's stream ("sym", "clock", "costas", "fsk4", "audio").
     subscribe() also takes what lies behind a slicer -- "hard", "sync" (uint32 items), "tsbk", "edacs", "osw", "p25lc"
-    (records, their structured dtypes) --; the pump cannot be STARTED with one of those (RCF_EINVAL)."""
+    (records, their structured dtypes) --, and the capture stage's "capture" (cf32) and "capture_rec" (CAPTURE_REC_DTYPE
+    records); the pump cannot be STARTED with one of those (RCF_EINVAL)."""
 
     def __init__(self, group, rings, block_samples, samp_rate, subscriptions=(), fmt=FMT_U8, scale=1.0, offset=0.0,
                  what="fm", gain=1.0, phase_s=None, out_ring_samples=4096, n_blocks=0, warm_blocks=0, max_batch=0,
@@ -1478,8 +1538,8 @@ class Pump:
         """channel `chan_id` of member `member` from its next output on -> the slot (rcf_pump_subscribe; a stream behind the
         slicer: rcf_pump_subscribe_hard, counted in words, hits or records)"""
         cur = C.c_int64(0)
-        if what in _HARD_WHAT:
-            e = _check(lib().rcf_pump_subscribe_hard(self._p, int(member), int(chan_id), _HARD_WHAT[what], C.byref(cur)))
+        if what in _HARD_WHAT or what == "capture_rec":
+            e = _check(lib().rcf_pump_subscribe_hard(self._p, int(member), int(chan_id), _read_what(what, True), C.byref(cur)))
         else:
             e = _check(lib().rcf_pump_subscribe(self._p, int(member), int(chan_id), _read_what(what, True),
                                                 float(gain), C.byref(cur)))
