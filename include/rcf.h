@@ -584,7 +584,7 @@ int rcf_chan_slicer_rings(rcf_t *h, int chan_id, void **word_ring, size_t *word_
  *     word 2-4  the 96 decoded bits, the first bit highest, bytes in memory order (the word ring's rule: a uint8 view is the
  *               12 octets); 0 in a frame record
  *     word 5-6  the NID's 64 bits, same rule
- *     word 7    frame_dibits
+ *     word 7    bits 0-15 frame_dibits; bits 16-20 RCF_NID_BCH's, bits 21-29 RCF_TRELLIS_VITERBI's (below); else zero
  * next_bit is the info bit that follows the block's last one if it lies inside the frame, else 0 (procTSDU stops behind a
  * block that is followed by a 1).  A frame record goes out for an accepted frame with duid != 7 or with no whole block.
  * Lost: hits that left the hit ring before they were examined, and frames whose first word the word ring had overwritten
@@ -611,7 +611,30 @@ int rcf_chan_slicer_rings(rcf_t *h, int chan_id, void **word_ring, size_t *word_
  * nid_fix, word 0 bit 9 set.  Without the option (RCF_NID_RAW) all of these bits are 0.  The option is fixed for a stage's
  * life; calling an attach again starts the stage afresh with that call's value, so the records stay independent of how the
  * input is cut.  rcf_chan_tsbk(h, c, p) is rcf_chan_tsbk_ex(h, c, p, RCF_NID_RAW): one attach path.  RCF_EINVAL as well: nid
- * neither RCF_NID_RAW nor RCF_NID_BCH. */
+ * neither RCF_NID_RAW nor RCF_NID_BCH.
+ * The trellis (RCF_TRELLIS_VITERBI; rcf_chan_tsbk_opt).  The paragraph "Trellis" above is the reference's walk: it decides
+ * code word by code word and never looks back, so one wrong bit that leaves two candidates of a row tied at three equal
+ * bits (0x2 / 0x1 and 0xC / 0xF of row 0 are 2 bits apart) can take the wrong one, and every later state follows from it.
+ * With the option a block is decoded as a whole, by maximum likelihood for hard decisions.  A block is the same 49 code
+ * words c_0 .. c_48.  A path is a state sequence s_0 .. s_48 with s_-1 = 0 and s_48 = 0: the encoder's flushing dibit
+ * (the reference ignores the 49th code word; this rule uses it).  A path's cost is the sum over t of
+ * popcount(W[s_(t-1)][s_t] xor c_t), with the W above.  The result is the path of least cost, among equal costs the
+ * lexicographically smallest (s_0, s_1, ...); the output is s_0 .. s_47 = 96 bits as above.  Sequentially:
+ * beta_48[s] = popcount(W[s][0] xor c_48); for t = 47 .. 0, beta_t[s] = min over d of popcount(W[s][d] xor c_t) +
+ * beta_(t+1)[d]; then forward from state 0, at step t the lowest d that minimises popcount(W[s][d] xor c_t) + beta_(t+1)[d]
+ * (at t = 48: d = 0).  Costs stay <= 4 x 49 = 196: small-integer work, no rounding.  The free distance of W's trellis is
+ * 5, so every pattern of at most 2 wrong bits in a block's 196 is corrected.  If the reference's walk finds a candidate
+ * equal to c at all 49 code words, both rules give the same 96 bits: that path costs 0, and a path of cost 0 is unique
+ * because the four words of a row of W differ.
+ * Records with the option: n_inexact (word 0 bits 4-9) counts the code words (0 .. 49) that differ from the chosen path's
+ * word -- the meaning above, on the new path --; word 7 bits 21-28 hold the path's cost (0 .. 196) and bit 29 is set (the
+ * block went through this decoder); in a frame record (b = 3) bits 21-29 are 0.  CRC bad, next_bit, the octets and all else
+ * follow from the decoded bits by the rules above.  With RCF_TRELLIS_GREEDY all of these bits are 0 and the records are
+ * those of rcf_chan_tsbk_ex bit for bit.  Like nid the option is fixed for a stage's life; attaching again starts the stage
+ * afresh with that call's value.  It applies to the TSBK stage only (the voice stage has no trellis).
+ * rcf_chan_tsbk_ex(h, c, p, nid) is rcf_chan_tsbk_opt(h, c, p, nid, RCF_TRELLIS_GREEDY): one attach path.  RCF_EINVAL as
+ * well: trellis neither RCF_TRELLIS_GREEDY nor RCF_TRELLIS_VITERBI.  With p == NULL (the stage switched off) neither nid nor
+ * trellis is looked at: the call returns what rcf_chan_tsbk(h, c, NULL) returns. */
 typedef struct rcf_tsbk_params {
     int capacity;          /* records of the ring, a power of two >= 16; 0 = 256 */
     int reserved_[3];
@@ -625,6 +648,14 @@ int rcf_chan_tsbk_ex(rcf_t *h, int chan_id, const rcf_tsbk_params_t *p, uint32_t
  * for a stage attached with RCF_NID_RAW.  RCF_ESTATE: the channel has neither stage */
 typedef struct rcf_nid_state { int64_t n_decoded, n_fixed, n_bits, n_bad; } rcf_nid_state_t;
 int rcf_chan_nid_state(rcf_t *h, int chan_id, rcf_nid_state_t *out);
+#define RCF_TRELLIS_GREEDY  0u   /* the reference's walk: the paragraph "Trellis" */
+#define RCF_TRELLIS_VITERBI 1u   /* the least-cost path that ends in state 0: the paragraph "The trellis" */
+int rcf_chan_tsbk_opt(rcf_t *h, int chan_id, const rcf_tsbk_params_t *p, uint32_t nid, uint32_t trellis);
+/* the trellis decoder's counters of the channel's TSBK stage as of the last block; syncs the stream: blocks that went through
+ * the decoder, of them with cost 0, the sum of the costs, the sum of the n_inexact values.  All 0 for a stage attached with
+ * RCF_TRELLIS_GREEDY.  RCF_ESTATE: the channel has no TSBK stage */
+typedef struct rcf_trellis_state { int64_t n_decoded, n_clean, n_bits, n_words; } rcf_trellis_state_t;
+int rcf_chan_trellis_state(rcf_t *h, int chan_id, rcf_trellis_state_t *out);
 /* the stage's counters as of the last block; syncs the stream.  RCF_ESTATE without the stage (here and in the calls below) */
 typedef struct rcf_tsbk_state {
     int64_t n_records, n_frames, n_blocks, n_crc_bad, n_lost;   /* records written, frames accepted (decided or lost), blocks decoded, of them with a bad CRC, hits and frames lost */

@@ -372,9 +372,10 @@ struct TsbkState {
     int64_t next_hit;        // the first hit of the slicer's stream that is neither rejected nor decided
     int64_t k_last;          // the last accepted hit's k
     int64_t nid_decoded, nid_fixed, nid_bits, nid_bad;   // rcf_nid_state_t's counters (RCF_NID_BCH; else 0)
+    int64_t vit_decoded, vit_clean, vit_bits, vit_words; // rcf_trellis_state_t's counters (RCF_TRELLIS_VITERBI; else 0)
 };
 struct TsbkLaunch : FramesLaunch<TsbkState> {
-    uint32_t flags;          // kNidFlagBch (nid_core.hpp): the stage decodes the NID
+    uint32_t flags;          // kNidFlagBch (nid_core.hpp): the stage decodes the NID; kTsbkFlagViterbi (tsbk_core.hpp): the least-cost path
 };
 void launch_tsbk(const TsbkLaunch *d_items, int n_items, int max_n_k, uint64_t ring_mask, hipStream_t s);
 // EDACS control frames behind a slicer (edacs.hip; get_next_frame, packet_framer, bch_decode, message_election of the

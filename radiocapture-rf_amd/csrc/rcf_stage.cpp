@@ -458,16 +458,37 @@ static bool nid_ok(const void *p, uint32_t nid, const char *name)
 
 int rcf_chan_tsbk(rcf_t *h, int chan_id, const rcf_tsbk_params_t *p) { return rcf_chan_tsbk_ex(h, chan_id, p, RCF_NID_RAW); }
 
-int rcf_chan_tsbk_ex(rcf_t *h, int chan_id, const rcf_tsbk_params_t *p, uint32_t nid)
+int rcf_chan_tsbk_ex(rcf_t *h, int chan_id, const rcf_tsbk_params_t *p, uint32_t nid) { return rcf_chan_tsbk_opt(h, chan_id, p, nid, RCF_TRELLIS_GREEDY); }
+
+int rcf_chan_tsbk_opt(rcf_t *h, int chan_id, const rcf_tsbk_params_t *p, uint32_t nid, uint32_t trellis)
 {
     if (!nid_ok(p, nid, "TSBK")) return RCF_EINVAL;
+    if (p && trellis != RCF_TRELLIS_GREEDY && trellis != RCF_TRELLIS_VITERBI) {
+        set_error("TSBK stage: trellis %u is neither RCF_TRELLIS_GREEDY nor RCF_TRELLIS_VITERBI", trellis);
+        return RCF_EINVAL;
+    }
     return attach_frames<Chan::Slicer::Tsbk>(h, chan_id, p,
         [](const Chan::Slicer &l) { return l.rec.bps == 2 && l.rec.sync_bits == 48 && !l.rec.sync_both && !l.p25lc; },
         "channel %d has no slicer in RCF_SLICE_FSK4 mode that searches a 48-bit sync word in one polarity, or that slicer carries the P25 voice stage",
-        [nid](TsbkLaunch &r, TsbkState &st0, const SliceLaunch &, const SliceState &) {
-            r.flags = nid == RCF_NID_BCH ? kNidFlagBch : 0u;
+        [nid, trellis](TsbkLaunch &r, TsbkState &st0, const SliceLaunch &, const SliceState &) {
+            r.flags = (nid == RCF_NID_BCH ? kNidFlagBch : 0u) | (trellis == RCF_TRELLIS_VITERBI ? kTsbkFlagViterbi : 0u);
             st0.k_last = kTsbkNoFrame;
         });
+}
+
+// the trellis decoder's counters: the end of the TSBK stage's state record
+int rcf_chan_trellis_state(rcf_t *h, int chan_id, rcf_trellis_state_t *out)
+{
+    if (!h || !out) return RCF_EINVAL;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (set_dev(h)) return RCF_EHIP;
+    FIND_CHAN(h, chan_id, c);
+    if (!c->slicer || !c->slicer->tsbk) { set_error(read_row(Chan::Slicer::Tsbk::kKind).refusal, chan_id); return RCF_ESTATE; }
+    int64_t four[4];
+    const int rc = stage_state(h, &c->slicer->tsbk->rec.st->vit_decoded, four, sizeof(four));
+    if (rc != RCF_OK) return rc;
+    out->n_decoded = four[0]; out->n_clean = four[1]; out->n_bits = four[2]; out->n_words = four[3];
+    return RCF_OK;
 }
 
 // the NID decoder's counters: the end of the state record of whichever of the two stages the slicer carries
@@ -477,7 +498,7 @@ int rcf_chan_nid_state(rcf_t *h, int chan_id, rcf_nid_state_t *out)
     std::lock_guard<std::mutex> g(h->mu);
     if (set_dev(h)) return RCF_EHIP;
     FIND_CHAN(h, chan_id, c);
-    static_assert(offsetof(TsbkState, nid_decoded) == offsetof(P25lcState, nid_decoded) && sizeof(TsbkState) == sizeof(P25lcState), "one place for both stages");
+    static_assert(offsetof(TsbkState, nid_decoded) == offsetof(P25lcState, nid_decoded), "one place for both stages");
     const char *st = c->slicer && c->slicer->tsbk ? reinterpret_cast<const char *>(c->slicer->tsbk->rec.st) :
                      c->slicer && c->slicer->p25lc ? reinterpret_cast<const char *>(c->slicer->p25lc->rec.st) : nullptr;
     if (!st) { set_error("channel %d has neither the TSBK stage nor the P25 voice stage", chan_id); return RCF_ESTATE; }

@@ -19,6 +19,10 @@
 // vector stores only; nothing is shared between waves; no LDS.
 // The option RCF_NID_BCH (kNidFlagBch in the launch record's flags): the NID's 63 bits go through nid_wave.hpp's decoder
 // before the DUID is looked at, behind a wave-uniform branch that a stage without the option never enters.
+// The option RCF_TRELLIS_VITERBI (kTsbkFlagViterbi, likewise): a lane's transition map comes from the least-cost path instead
+// of the nearest candidate.  A suffix scan of the code words' min-plus matrices -- six cross-lane steps, four packed registers
+// a lane -- leaves beta_t in lane t; with its right neighbour's beta the lane forms the map of the forward step, and the same
+// inclusive scan as without the option gives the states.  A ballot counts the words off the path, an add-reduction sums the cost.
 #include "item_wave.hpp"
 #include "tsbk_core.hpp"
 #include "nid_wave.hpp"
@@ -35,6 +39,23 @@ __device__ __forceinline__ int ring_dibit(const TsbkLaunch &L, int64_t p)
     return tsbk_word_dibit(L.word_ring[(uint64_t)(p >> 4) & L.word_mask], (int)(p & 15));
 }
 
+// lane t's transition map on the least-cost path through the code words c of the lanes 0 .. 48 (tsbk_core.hpp).  Out of
+// line: inlined, its unrolled compositions raise the kernel's registers past 128 and cost a stage without the option a wave
+// of occupancy
+__device__ __noinline__ uint32_t viterbi_map_wave(uint32_t c, int lane)
+{
+    const TsbkMat own = lane < kTsbkCodeWords ? tsbk_mat(c, lane == kTsbkCodeWords - 1) : tsbk_mat_identity();
+    TsbkMat suffix = own;                            // the product of the lanes lane .. 63
+    for (int d = 1; d < 64; d <<= 1) {
+        TsbkMat after;
+        for (int s = 0; s < 4; ++s) after.row[s] = (uint32_t)__shfl_down((int)suffix.row[s], d);
+        if (lane + d < 64) suffix = tsbk_mat_compose(suffix, after);
+    }
+    const uint32_t beta_next = (uint32_t)__shfl_down((int)tsbk_mat_beta(suffix), 1);
+    if (lane >= kTsbkCodeWords) return kTsbkIdentity;
+    return tsbk_viterbi_map(own, lane == kTsbkCodeWords - 1 ? 0u : beta_next);
+}
+
 __global__ __launch_bounds__(64 * kTsbkWaves) void tsbk_kernel(const TsbkLaunch *__restrict__ items, int n_items)
 {
     const int lane = threadIdx.x & 63;
@@ -42,8 +63,9 @@ __global__ __launch_bounds__(64 * kTsbkWaves) void tsbk_kernel(const TsbkLaunch 
     if (w >= n_items) return;                        // (no workgroup barrier below: a wave leaves on its own)
     const TsbkLaunch L = items[w];
     TsbkState *st = L.st;
-    const bool nid = L.flags & kNidFlagBch;
+    const bool nid = L.flags & kNidFlagBch, viterbi = L.flags & kTsbkFlagViterbi;
     NidCount nc;
+    int64_t vit_decoded = 0, vit_clean = 0, vit_bits = 0, vit_words = 0;
     const int64_t n_sym = L.src->n_symbols, n_words = L.src->n_words, n_hits = L.src->n_hits;
     int64_t n_records = st->n_records, n_frames = st->n_frames, n_blocks = st->n_blocks, n_crc_bad = st->n_crc_bad, n_lost = st->n_lost;
     int64_t i = st->next_hit, k_last = st->k_last;
@@ -101,6 +123,7 @@ __global__ __launch_bounds__(64 * kTsbkWaves) void tsbk_kernel(const TsbkLaunch 
                 c = (uint32_t)(ring_dibit(L, s + tsbk_frame_pos(j)) << 2 | ring_dibit(L, s + tsbk_frame_pos(j + 1)));
                 map = tsbk_map(c);
             }
+            if (viterbi) map = viterbi_map_wave(c, lane);                                     // (uniform)
             for (int d = 1; d < 64; d <<= 1) {       // the inclusive scan: the map of the code words 0 .. lane
                 const uint32_t before = (uint32_t)__shfl_up((int)map, d);
                 if (lane >= d) map = tsbk_compose(before, map);
@@ -109,7 +132,15 @@ __global__ __launch_bounds__(64 * kTsbkWaves) void tsbk_kernel(const TsbkLaunch 
             const int prev = __shfl_up(state, 1);
             bool exact;
             (void)tsbk_next_state(lane ? prev : 0, c, &exact);
-            const int n_inexact = __popcll(__ballot(lane < kTsbkCodeWords && !exact));
+            int n_inexact = __popcll(__ballot(lane < kTsbkCodeWords && !exact));
+            uint32_t w7b = w7;
+            if (viterbi) {                           // (uniform) the words off the chosen path and the path's cost
+                int cost = lane < kTsbkCodeWords ? tsbk_branch_dist(lane ? prev : 0, state, c) : 0;
+                n_inexact = __popcll(__ballot(cost != 0));
+                for (int m = 32; m; m >>= 1) cost += __shfl_xor(cost, m);
+                w7b |= tsbk_viterbi_word7(cost);
+                ++vit_decoded; vit_clean += cost == 0 ? 1 : 0; vit_bits += cost; vit_words += n_inexact;
+            }
             const bool out = lane < 48;              // the first 48 states are the 96 bits
             const uint64_t hi = __ballot(out && (state & 2)), lo = __ballot(out && (state & 1));
             uint32_t crc = out ? tsbk_crc_term(lane, state) : 0u;
@@ -120,7 +151,7 @@ __global__ __launch_bounds__(64 * kTsbkWaves) void tsbk_kernel(const TsbkLaunch 
             rec = L.rec_ring + ((uint64_t)n_records & L.rec_mask) * kTsbkRecWords;
             const uint32_t v = lane == 0 ? tsbk_word0(b, crc_bad, next_bit, n_inexact, dist, nidc) : lane == 1 ? (uint32_t)(uint64_t)k0 :
                                lane < 5 ? slice_word_mem(slice_word_be(hi, lo, 2, lane - 2)) :
-                               lane == 5 ? slice_word_mem(nid0) : lane == 6 ? slice_word_mem(nid1) : w7;
+                               lane == 5 ? slice_word_mem(nid0) : lane == 6 ? slice_word_mem(nid1) : w7b;
             if (lane < kTsbkRecWords) rec[lane] = v;
             ++n_records; ++n_blocks;
             n_crc_bad += crc_bad ? 1 : 0;
@@ -130,6 +161,7 @@ __global__ __launch_bounds__(64 * kTsbkWaves) void tsbk_kernel(const TsbkLaunch 
         st->n_records = n_records; st->n_frames = n_frames; st->n_blocks = n_blocks; st->n_crc_bad = n_crc_bad; st->n_lost = n_lost;
         st->next_hit = i; st->k_last = k_last;
         if (nid) { st->nid_decoded += nc.decoded; st->nid_fixed += nc.fixed; st->nid_bits += nc.bits; st->nid_bad += nc.bad; }
+        if (viterbi) { st->vit_decoded += vit_decoded; st->vit_clean += vit_clean; st->vit_bits += vit_bits; st->vit_words += vit_words; }
     }
 }
 

@@ -1,9 +1,10 @@
 // tsbk_core.hpp -- the arithmetic of the P25 trunking stage (tsbk.hip; definition: include/rcf.h at rcf_chan_tsbk): the
 // widening of a hit's k, the accept rule, where an info dibit sits in a frame, the deinterleaver's index map, the rate-1/2
-// trellis as transition maps with their composition (what the wave scans), the CRC's per-bit terms and the packing of a
-// record.  No HIP types in here, like slice_core.hpp, whose mask-to-word helpers it uses: RCF_DEVFN is the function
-// qualifier and RCF_DEVCONST the qualifier of the one table, so that the CPU suite compiles this very source with g++
-// (tests/native/tsbk_core_check.cpp).
+// trellis as transition maps with their composition (what the wave scans), for the option RCF_TRELLIS_VITERBI the code
+// words as min-plus matrices with theirs, the CRC's per-bit terms and the packing of a record.  No HIP types in here, like
+// slice_core.hpp, whose mask-to-word helpers it uses: RCF_DEVFN is the function qualifier and RCF_DEVCONST the qualifier of
+// the one table, so that the CPU suite compiles this very source with g++ (tests/native/tsbk_core_check.cpp,
+// trellis_core_check.cpp).
 #pragma once
 #include "slice_core.hpp"
 #ifndef RCF_DEVCONST
@@ -82,6 +83,76 @@ RCF_DEVFN uint32_t tsbk_compose(uint32_t first, uint32_t then)
     for (int s = 0; s < 4; ++s) m |= ((then >> (2 * ((first >> (2 * s)) & 3u))) & 3u) << (2 * s);
     return m;
 }
+
+// ---- the option RCF_TRELLIS_VITERBI (rcf.h at rcf_chan_tsbk_opt): the path of least cost that ends in state 0, the
+// lexicographically smallest of equals.  All of it is min-plus algebra over 4 x 4 matrices of small integers: a code word
+// is the matrix M[s][d] = popcount(W[s][d] xor c), a run of code words their product, and column 0 of the product of the
+// words t .. 48 is beta_t, the least cost from each state before word t to the end.  The wave scans the products.
+constexpr uint32_t kTsbkFlagViterbi = 0x200u;    // TsbkLaunch::flags, next to kNidFlagBch
+constexpr uint32_t kTsbkNoPath = 255u;           // an entry no path reaches; a path's cost is at most 4 x 49 = 196
+// row s in row[s], entry d in its byte d
+struct TsbkMat { uint32_t row[4]; };
+RCF_DEVFN uint32_t tsbk_mat_at(const TsbkMat &m, int s, int d) { return (m.row[s] >> (8 * d)) & 255u; }
+// the matrix of code word c; flush: the 49th word, whose dibit is 0, so only d = 0 is a path
+RCF_DEVFN TsbkMat tsbk_mat(uint32_t c, bool flush)
+{
+    TsbkMat m;
+    for (int s = 0; s < 4; ++s) {
+        const uint32_t row = tsbk_trellis_row(s);
+        uint32_t v = 0;
+        for (int d = 0; d < 4; ++d) v |= (flush && d ? kTsbkNoPath : (uint32_t)tsbk_pop4(((row >> (4 * d)) & 15u) ^ c)) << (8 * d);
+        m.row[s] = v;
+    }
+    return m;
+}
+RCF_DEVFN TsbkMat tsbk_mat_identity()
+{
+    TsbkMat m;
+    for (int s = 0; s < 4; ++s) m.row[s] = 0xffffffffu ^ (255u << (8 * s));
+    return m;
+}
+// first, then `then`: (A x B)[s][d] = min over m of A[s][m] + B[m][d], kTsbkNoPath absorbing (associative: the sums of real
+// paths stay below it)
+RCF_DEVFN TsbkMat tsbk_mat_compose(const TsbkMat &first, const TsbkMat &then)
+{
+    TsbkMat r;
+    for (int s = 0; s < 4; ++s) {
+        uint32_t v = 0;
+        for (int d = 0; d < 4; ++d) {
+            uint32_t best = kTsbkNoPath;
+            for (int m = 0; m < 4; ++m) {
+                const uint32_t sum = tsbk_mat_at(first, s, m) + tsbk_mat_at(then, m, d);
+                if (sum < best) best = sum;
+            }
+            v |= best << (8 * d);
+        }
+        r.row[s] = v;
+    }
+    return r;
+}
+// column 0 of a suffix product: beta[s] in byte s
+RCF_DEVFN uint32_t tsbk_mat_beta(const TsbkMat &suffix)
+{
+    return (suffix.row[0] & 255u) | (suffix.row[1] & 255u) << 8 | (suffix.row[2] & 255u) << 16 | (suffix.row[3] & 255u) << 24;
+}
+// the forward step as a transition map (tsbk_map's encoding): from state s the lowest d with the least M[s][d] + beta_next[d]
+RCF_DEVFN uint32_t tsbk_viterbi_map(const TsbkMat &m, uint32_t beta_next)
+{
+    uint32_t map = 0;
+    for (int s = 0; s < 4; ++s) {
+        uint32_t best = 0, least = 2 * kTsbkNoPath + 1;
+        for (int d = 0; d < 4; ++d) {
+            const uint32_t sum = tsbk_mat_at(m, s, d) + ((beta_next >> (8 * d)) & 255u);
+            if (sum < least) { least = sum; best = (uint32_t)d; }
+        }
+        map |= best << (2 * s);
+    }
+    return map;
+}
+// bits in which code word c differs from the path's word W[prev][state]
+RCF_DEVFN int tsbk_branch_dist(int prev, int state, uint32_t c) { return tsbk_pop4(((tsbk_trellis_row(prev) >> (4 * state)) & 15u) ^ c); }
+// what the option adds to a record's word 7 (without it these bits are 0): the path's cost, and that the block went this way
+RCF_DEVFN uint32_t tsbk_viterbi_word7(int cost) { return ((uint32_t)(cost & 255) << 21) | (1u << 29); }
 
 // ---- crc16 of the reference: register 0, every bit shifted in, xor 0x1021 when bit 16 falls out; good: 0xffff.  From 0 the
 // register is linear in the bits: bit p (0 .. 95, the first one 0) adds x^(95 - p) mod the polynomial -- these terms

@@ -42,6 +42,7 @@ SYMBOLS = [
     "rcf_chan_edacs", "rcf_chan_edacs_state", "rcf_chan_read_edacs", "rcf_chan_edacs_ring",
     "rcf_chan_osw", "rcf_chan_osw_state", "rcf_chan_read_osw", "rcf_chan_osw_ring",
     "rcf_chan_tsbk_ex", "rcf_chan_p25lc_ex", "rcf_chan_nid_state",
+    "rcf_chan_tsbk_opt", "rcf_chan_trellis_state",
     "rcf_chan_p25lc", "rcf_chan_p25lc_opt", "rcf_chan_p25lc_state", "rcf_chan_read_p25lc", "rcf_chan_p25lc_ring",
     "rcf_design_firdes", "rcf_design_optfir_low_pass", "rcf_design_fm_deemph", "rcf_design_resampler", "rcf_chan_audio_open",
     "rcf_chan_audio_close", "rcf_chan_audio_produced", "rcf_chan_read_audio",
@@ -223,6 +224,19 @@ class TsbkState(C.Structure):
 class NidState(C.Structure):
     """rcf_nid_state_t (include/rcf.h)"""
     _fields_ = [("n_decoded", C.c_int64), ("n_fixed", C.c_int64), ("n_bits", C.c_int64), ("n_bad", C.c_int64)]
+
+
+class TrellisState(C.Structure):
+    """rcf_trellis_state_t (include/rcf.h)"""
+    _fields_ = [("n_decoded", C.c_int64), ("n_clean", C.c_int64), ("n_bits", C.c_int64), ("n_words", C.c_int64)]
+
+
+def trellis_fields(records):
+    """what RCF_TRELLIS_VITERBI adds to word 7 of TSBK records (TSBK_DTYPE) -> dict of arrays: cost (the bits in which the
+    block's 196 differ from the decoded path's, 0 .. 196) and viterbi (the block went through that decoder); both are 0 in a
+    frame record and for a stage attached without the option"""
+    t = np.asarray(records["frame_dibits"], dtype=np.uint32)
+    return dict(cost=((t >> 21) & 255).astype(np.uint8), viterbi=((t >> 29) & 1).astype(np.uint8))
 
 
 def tsbk_fields(records):
@@ -512,6 +526,8 @@ def lib():
     sig["rcf_chan_tsbk_ex"] = (C.c_int, [vp, C.c_int, C.POINTER(TsbkParams), C.c_uint32])
     sig["rcf_chan_p25lc_ex"] = (C.c_int, [vp, C.c_int, C.POINTER(P25lcParams), C.c_uint32, C.c_uint32])
     sig["rcf_chan_nid_state"] = (C.c_int, [vp, C.c_int, C.POINTER(NidState)])
+    sig["rcf_chan_tsbk_opt"] = (C.c_int, [vp, C.c_int, C.POINTER(TsbkParams), C.c_uint32, C.c_uint32])
+    sig["rcf_chan_trellis_state"] = (C.c_int, [vp, C.c_int, C.POINTER(TrellisState)])
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
         fn.restype = res
@@ -1153,13 +1169,20 @@ class Frontend:
         _check(lib().rcf_chan_slicer_rings(self._h, cid, C.byref(wp), C.byref(wc), C.byref(hp), C.byref(hc)))
         return wp.value, wc.value, hp.value, hc.value
 
-    def chan_tsbk(self, cid, capacity=0, on=True, nid=False):
-        """P25 trunking blocks behind the channel's slicer (rcf_chan_tsbk_ex): frames from the sync hits, status symbols
+    def chan_tsbk(self, cid, capacity=0, on=True, nid=False, viterbi=False):
+        """P25 trunking blocks behind the channel's slicer (rcf_chan_tsbk_opt): frames from the sync hits, status symbols
         stripped, NID read, every block deinterleaved, trellis-decoded and CRC-checked on the GPU; records of TSBK_DTYPE
         in a ring of `capacity` (0: 256).  nid=True (RCF_NID_BCH): the NID's BCH(63,16,23) word is decoded first and the
-        decoded DUID decides whether blocks are decoded (nid_fields: nid_fix, nid_decoded; chan_nid_state).  It considers the
-        hits from now on; on=False switches it off."""
-        self._attach(lambda h, c, p: lib().rcf_chan_tsbk_ex(h, c, p, int(nid)), cid, TsbkParams, on, capacity=capacity)
+        decoded DUID decides whether blocks are decoded (nid_fields: nid_fix, nid_decoded; chan_nid_state).  viterbi=True
+        (RCF_TRELLIS_VITERBI): a block's trellis is decoded as a whole, by the least-cost path that ends in state 0, instead of
+        the reference's word-by-word walk (trellis_fields: cost, viterbi; chan_trellis_state).  It considers the hits from now
+        on; on=False switches it off."""
+        self._attach(lambda h, c, p: lib().rcf_chan_tsbk_opt(h, c, p, int(nid), int(viterbi)), cid, TsbkParams, on, capacity=capacity)
+
+    def chan_trellis_state(self, cid) -> dict:
+        """n_decoded, n_clean, n_bits, n_words of the trellis decoder of the channel's TSBK stage as of the last block
+        (rcf_chan_trellis_state; syncs the stream): all 0 for a stage attached without viterbi"""
+        return self._state_of(lib().rcf_chan_trellis_state, cid, TrellisState)
 
     def chan_nid_state(self, cid) -> dict:
         """n_decoded, n_fixed, n_bits, n_bad of the NID decoder of the channel's TSBK or P25 voice stage as of the last block

@@ -34,10 +34,10 @@ def _one_decoder(tsbk, lc):
         raise ValueError("tsbk and lc exclude each other: a slicer carries one frame decoder")
 
 
-def _hard(fe, cid, source, tsbk=False, lc=False, es=False, erasures=False, nid=False):
+def _hard(fe, cid, source, tsbk=False, lc=False, es=False, erasures=False, nid=False, viterbi=False):
     fe.chan_slicer(cid, source, native.SLICE_FSK4, SLICER_LEVELS, FRAME_SYNC, FRAME_SYNC_BITS, FRAME_SYNC_MAX_ERRORS)
     if tsbk:
-        fe.chan_tsbk(cid, nid=nid)
+        fe.chan_tsbk(cid, nid=nid, viterbi=viterbi)
     if lc:
         fe.chan_p25lc_ex(cid, es=es, erasures=erasures, nid=nid)
 
@@ -81,6 +81,47 @@ def nid_decode(bits):
     fix = int(dist[at])
     word = int(_NID_WORDS[at]) if fix <= 11 else r
     return dict(nac=word >> 51, duid=word >> 47 & 15, nid_fix=fix if fix <= 11 else 15)
+
+
+# ---- a TSBK block's rate-1/2 trellis on the host (the TSBK stage's option viterbi=True decodes it on the GPU: rcf.h at
+# rcf_chan_tsbk_opt).  TRELLIS[s][d]: the 4-bit code word sent for dibit d in state s
+TRELLIS = ((0x2, 0xC, 0x1, 0xF), (0xE, 0x0, 0xD, 0x3), (0x9, 0x7, 0xA, 0x4), (0x5, 0xB, 0x6, 0x8))
+
+
+def trellis_decode(code_words, viterbi=True):
+    """the host form of the TSBK stage's trellis rule.  code_words: a block's 49 deinterleaved code words of 4 bits each ->
+    (the 48 decoded dibits, cost, n_inexact).  viterbi=True: the path of least cost that ends in state 0, the
+    lexicographically smallest of equals, by the backward costs beta and a forward walk; cost is the number of bits in which
+    the 196 differ from the path's, n_inexact the code words that differ.  viterbi=False: the reference's walk -- per code
+    word the nearest candidate, the lowest of equals --; n_inexact counts the words with no equal candidate and cost is the
+    sum of the distances to the candidates taken"""
+    c = [int(v) & 15 for v in code_words]
+    if len(c) != 49:
+        raise ValueError("a block has 49 code words, not %d" % len(c))
+    dist = lambda s, d, t: bin(TRELLIS[s][d] ^ c[t]).count("1")
+    states, cost, inexact, s = [], 0, 0, 0
+    if not viterbi:
+        for t in range(49):
+            away = [dist(s, d, t) for d in range(4)]
+            d = away.index(min(away))
+            cost += away[d]
+            inexact += away[d] != 0
+            states.append(d)
+            s = d
+        return states[:48], cost, inexact
+    beta = [[0] * 4 for _ in range(50)]
+    beta[48] = [dist(r, 0, 48) for r in range(4)]
+    for t in range(47, -1, -1):
+        beta[t] = [min(dist(r, d, t) + beta[t + 1][d] for d in range(4)) for r in range(4)]
+    for t in range(49):
+        sums = [dist(s, d, t) + beta[t + 1][d] for d in (range(4) if t < 48 else range(1))]
+        d = sums.index(min(sums))
+        away = dist(s, d, t)
+        cost += away
+        inexact += away != 0
+        states.append(d)
+        s = d
+    return states[:48], cost, inexact
 
 
 def tsdu_frames(records, reference_rule=False):
@@ -195,18 +236,19 @@ def costas_params(channel_rate, symbol_rate=SYMBOL_RATE):
                 beta=0.125 * alpha * alpha, max_freq=2.0 * math.pi * 1200.0 / rate, omega_limit=0.005)
 
 
-def cqpsk_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False, tsbk=False, lc=False, es=False, erasures=False, nid=False):
+def cqpsk_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False, tsbk=False, lc=False, es=False, erasures=False, nid=False, viterbi=False):
     """the whole CQPSK chain up to the slicer on channel `chan_id` of Frontend `fe`: the front half, then the Gardner /
     Costas stage (p25_control_demod.py:136-183).  Returns the pre-filter channel's id: chan_read_costas on it gives soft
     dibits at symbol_rate (slice_dibits turns them into dibits), chan_costas_state its carrier estimate.  hard=True also
     attaches the slicer behind the loop: chan_read_hard gives packed dibits, chan_read_sync where FRAME_SYNC ends; with
     tsbk=True as well the TSBK stage behind the slicer (chan_read_tsbk, tsdu_frames), or with lc=True the voice-channel
-    stage (chan_read_p25lc, voice_units; es / erasures: its options, Frontend.chan_p25lc); the two exclude each other (ValueError).  nid=True: either stage decodes the NID's BCH word first (nid_decode is the host form)."""
+    stage (chan_read_p25lc, voice_units; es / erasures: its options, Frontend.chan_p25lc); the two exclude each other (ValueError).  nid=True: either stage decodes the NID's BCH word first (nid_decode is the host form).
+    viterbi=True: the TSBK stage decodes a block's trellis by the least-cost path (trellis_decode is the host form)."""
     _one_decoder(tsbk, lc)
     cid = cqpsk_front_half(fe, chan_id, channel_rate)
     fe.chan_costas(cid, **costas_params(channel_rate, symbol_rate))
     if hard:
-        _hard(fe, cid, native.READ_COSTAS, tsbk, lc, es, erasures, nid)
+        _hard(fe, cid, native.READ_COSTAS, tsbk, lc, es, erasures, nid, viterbi)
     return cid
 
 
@@ -232,18 +274,19 @@ def fsk4_params(channel_rate, symbol_rate=SYMBOL_RATE):
                 k_coarse=0.00125, spread_min=1.6, spread_max=2.4)
 
 
-def c4fm_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False, tsbk=False, lc=False, es=False, erasures=False, nid=False):
+def c4fm_demod(fe, chan_id, channel_rate, symbol_rate=SYMBOL_RATE, hard=False, tsbk=False, lc=False, es=False, erasures=False, nid=False, viterbi=False):
     """the whole C4FM chain up to the slicer on channel `chan_id` of Frontend `fe`: the front half, then the symbol loop
     (p25_control_demod.py:118-135).  Returns the pre-filter channel's id: chan_read_fsk4 on it gives soft dibits at
     symbol_rate (slice_dibits turns them into dibits), chan_fsk4_state its offset estimate (`coarse`).  hard=True also
     attaches the slicer behind the loop: chan_read_hard gives packed dibits, chan_read_sync where FRAME_SYNC ends; with
     tsbk=True as well the TSBK stage behind the slicer (chan_read_tsbk, tsdu_frames), or with lc=True the voice-channel
-    stage (chan_read_p25lc, voice_units; es / erasures: its options, Frontend.chan_p25lc); the two exclude each other (ValueError).  nid=True: either stage decodes the NID's BCH word first (nid_decode is the host form)."""
+    stage (chan_read_p25lc, voice_units; es / erasures: its options, Frontend.chan_p25lc); the two exclude each other (ValueError).  nid=True: either stage decodes the NID's BCH word first (nid_decode is the host form).
+    viterbi=True: the TSBK stage decodes a block's trellis by the least-cost path (trellis_decode is the host form)."""
     _one_decoder(tsbk, lc)
     cid = c4fm_front_half(fe, chan_id, channel_rate, symbol_rate)
     fe.chan_fsk4(cid, **fsk4_params(channel_rate, symbol_rate))
     if hard:
-        _hard(fe, cid, native.READ_FSK4, tsbk, lc, es, erasures, nid)
+        _hard(fe, cid, native.READ_FSK4, tsbk, lc, es, erasures, nid, viterbi)
     return cid
 
 
