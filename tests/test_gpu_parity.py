@@ -120,8 +120,9 @@ def test_multichannel_bank_gr_faithful(gpu_required, fs, cr, offsets):
 def test_matrix_core_bank_equals_oracle(gpu_required, fs, cr, nch, D_override):
     """>= 8 channels on one source run on the FP32 matrix cores once their history is real (fir.hip
     fir_mfma_kernel): same GR-faithful result as the oracle, including a channel count that leaves dead MFMA
-    rows (37, 12, 9), the reference's 2909-tap / 800 shape, an odd decimation (no LDS skew), and the largest
-    shape of the SURVEY 8(a) a3 table that fits the matrix-core tile (25 Msps: D = 1000, T = 3637, 149 KB of LDS)."""
+    rows (37, 12, 9), the reference's 2909-tap / 800 shape, an odd decimation, and the 25 Msps shape of the SURVEY 8(a)
+    a3 table (D = 1000, T = 3637).  The kernel keeps no sample tile in LDS (the samples come straight from the wideband
+    buffer, the taps stream through 64 KB of LDS in chunks of 64), so no shape is bounded by D or T any more."""
     nat = gpu_required
     rng = np.random.default_rng(nch)
     D, taps = G.channel_params(fs, cr)
@@ -151,8 +152,8 @@ def test_matrix_core_bank_equals_oracle(gpu_required, fs, cr, nch, D_override):
 
 
 def test_largest_channel_shape_20msps_6k25(gpu_required):
-    """SURVEY 8(a) a3's biggest filter: 6.25 kHz channels at 20 Msps, D = 1600, T = 5819.  Sixteen outputs' worth of
-    samples no longer fit the LDS: the matrix-core kernel runs 8-output tiles (136 KB)."""
+    """SURVEY 8(a) a3's biggest filter: 6.25 kHz channels at 20 Msps, D = 1600, T = 5819.  The matrix-core kernel has no
+    sample tile in LDS, so this shape too runs full 16-output tiles (fir.hip, "There is no sample tile in LDS")."""
     nat = gpu_required
     fs, cr = 20e6, 6250
     rng = np.random.default_rng(3)
