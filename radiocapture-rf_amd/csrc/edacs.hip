@@ -4,18 +4,16 @@
 // there.  include/rcf.h at rcf_chan_edacs DEFINES the stage, tests/edacs_ref.py restates it; the arithmetic is
 // edacs_core.hpp, which the CPU suite compiles for the host as it stands.
 //
-// The slicer's layout: a WAVE is a channel, four channels per workgroup.  The wave walks the slicer's hit ring from the
-// state's next_hit on, 64 hits a trip with a lane each; the accept rule picks the first hit a whole frame behind the last
-// accepted one.  A frame whose 288 bits are not all in whole words yet stays where it is -- next_hit does not pass it -- and
-// is looked at again in the next launch.  Per decided frame the lanes 0 .. 39 are the coefficients of the six copies'
+// The slicer's layout: a WAVE is a channel, four channels per workgroup.  The walk over the slicer's hit ring is
+// item_wave.hpp's frame_walk with edacs_core.hpp's EdacsWalk: the accept rule picks the first hit a whole frame behind the last
+// accepted one, and a frame waits for its 288 bits.  Per decided frame the lanes 0 .. 39 are the coefficients of the six copies'
 // received polynomials: each gathers its six bits (polarity and the middle copies' inversion applied), a ballot per copy is
 // the copy's 40-bit value, and the twelve 6-bit syndromes S1, S3 -- packed two copies to a register -- are three
 // xor-reductions over the wave of six steps each, where the reference walks 48 coefficients four times per copy.  What
 // follows is wave-uniform: the class of each syndrome pair, and for a pair that needs the Chien search its 63 trials are 63
 // lanes and the error positions a ballot; corrections are xor masks on the copies' values, the election compares them, and
 // the lanes 0 .. 7 store the record's eight words.
-// All trip counts come from the host's n_k; the counters read from the device only clamp.  Every ring index is masked.  Plain
-// vector stores only; nothing is shared between waves; no LDS.
+// Every ring index is masked.  Plain vector stores only; nothing is shared between waves; no LDS.
 #include "item_wave.hpp"
 #include "edacs_core.hpp"
 
@@ -27,35 +25,16 @@ constexpr int kEdacsWaves = kItemWaves;
 
 __global__ __launch_bounds__(64 * kEdacsWaves) void edacs_kernel(const EdacsLaunch *__restrict__ items, int n_items)
 {
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(blockIdx.x * kEdacsWaves + (threadIdx.x >> 6));
-    if (w >= n_items) return;                        // (no workgroup barrier below: a wave leaves on its own)
+    int lane;
+    const int w = item_of_wave(n_items, &lane);
+    if (w < 0) return;
     const EdacsLaunch L = items[w];
     EdacsState *st = L.st;
-    const int64_t n_sym = L.src->n_symbols, n_words = L.src->n_words, n_hits = L.src->n_hits;
-    int64_t n_records = st->n_records, n_frames = st->n_frames, n_msgs = st->n_msgs, n_msgs_none = st->n_msgs_none, n_lost = st->n_lost;
-    int64_t i = st->next_hit, k_last = st->k_last;
-    const int64_t hit_cap = (int64_t)L.hit_mask + 1, word_cap = (int64_t)L.word_mask + 1;
-    if (i < n_hits - hit_cap) { n_lost += n_hits - hit_cap - i; i = n_hits - hit_cap; }      // hits that left the ring unexamined
+    int64_t n_records = st->n_records, n_msgs = st->n_msgs, n_msgs_none = st->n_msgs_none;
     const bool sync_both = L.flags & kEdacsFlagBoth, esk = L.flags & kEdacsFlagEsk;
     const uint32_t term = lane < kEdacsCopyBits ? edacs_syn_term(lane) : 0u;                // what this lane's coefficient adds to (S1, S3)
-    // the host's bounds, whatever the counters say: the hits to look at are this block's (at most one per new symbol) and those
-    // behind an undecided frame's sync word up to the unfinished word; a decided frame costs one trip, 64 rejected hits one
-    const int bound = L.n_k + kEdacsFrameBits + 32;
-    const int trips = bound / kEdacsFrameBits + 1 + bound / 64 + 2;
-    for (int t = 0; t < trips && i < n_hits; ++t) {
-        const bool valid = i + lane < n_hits;
-        const uint32_t item = valid ? L.hit_ring[(uint64_t)(i + lane) & L.hit_mask] : 0u;
-        const int64_t k = edacs_widen_k(item, n_sym);
-        const uint64_t acc = __ballot(valid && edacs_accept(k, k_last));
-        if (!acc) { i += n_hits - i < 64 ? n_hits - i : 64; continue; }                      // all rejected
-        const int a = __builtin_ctzll(acc);
-        const int64_t k0 = rl_i64(k, a), s = k0 - (kEdacsSyncBits - 1);
-        const uint32_t raw = (uint32_t)__builtin_amdgcn_readlane((int)item, a) >> 26;
-        i += a;
-        if (32 * n_words < s + kEdacsFrameBits) break;                                        // not all there yet: the next launch
-        ++i; k_last = k0; ++n_frames;
-        if ((s >> 5) < n_words - word_cap) { ++n_lost; continue; }                            // its first word is overwritten
+    FrameWalk walk(st);
+    frame_walk<EdacsWalk>(L, lane, walk, [&](int64_t s, int, int64_t k0, uint32_t raw) __attribute__((always_inline)) {
         const bool inverted = edacs_inverted(raw, sync_both);
         // ---- coefficient `lane` of the six copies; the copies' values; the syndromes, two copies to a register
         uint64_t val[kEdacsCopies];
@@ -71,10 +50,7 @@ __global__ __launch_bounds__(64 * kEdacsWaves) void edacs_kernel(const EdacsLaun
             if (bit) syn[c >> 1] ^= term << (12 * (c & 1));
         }
 #pragma unroll
-        for (int q = 0; q < kEdacsCopies / 2; ++q) {
-            for (int m = 32; m; m >>= 1) syn[q] ^= (uint32_t)__shfl_xor((int)syn[q], m);
-            syn[q] = (uint32_t)__builtin_amdgcn_readfirstlane((int)syn[q]);
-        }
+        for (int q = 0; q < kEdacsCopies / 2; ++q) syn[q] = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_xor(syn[q]));
         // ---- per copy, wave-uniform: class, positions, correction
         int status[kEdacsCopies];
         uint32_t statuses = 0;
@@ -102,10 +78,10 @@ __global__ __launch_bounds__(64 * kEdacsWaves) void edacs_kernel(const EdacsLaun
         ++n_records;
         n_msgs += (has1 ? 1 : 0) + (has2 ? 1 : 0);
         n_msgs_none += (has1 ? 0 : 1) + (has2 ? 0 : 1);
-    }
+    });
     if (lane == 0) {
-        st->n_records = n_records; st->n_frames = n_frames; st->n_msgs = n_msgs; st->n_msgs_none = n_msgs_none; st->n_lost = n_lost;
-        st->next_hit = i; st->k_last = k_last;
+        st->n_records = n_records; st->n_msgs = n_msgs; st->n_msgs_none = n_msgs_none;
+        walk.store(st);
     }
 }
 

@@ -1,5 +1,5 @@
 // edacs_core.hpp -- the arithmetic of the EDACS control-frame stage (edacs.hip; definition: include/rcf.h at rcf_chan_edacs):
-// the widening of a hit's k and its polarity, the accept rule, where a copy's bit sits in a frame, GF(64) as its two
+// the frame walk's constants, a hit's polarity, where a copy's bit sits in a frame, GF(64) as its two
 // tables, a coefficient's syndrome term, the classification of a syndrome pair, one trial of the Chien search, what the
 // found positions do to a copy, the election and the packing of a record.  No HIP types in here, like slice_core.hpp:
 // RCF_DEVFN is the function qualifier and RCF_DEVCONST the qualifier of the one table, so that the CPU suite compiles this
@@ -22,14 +22,15 @@ constexpr int kEdacsCodeBits = 48;       // BCH(48,36): eight colour bits (0 her
 constexpr int kEdacsRecWords = 8;        // uint32 words of a record
 constexpr int64_t kEdacsNoFrame = -((int64_t)1 << 60);   // k_last before the first accepted hit
 
-// a hit item's k: the largest value <= n_symbols - 1 with the item's low 26 bits (rcf.h at rcf_chan_slicer)
-RCF_DEVFN int64_t edacs_widen_k(uint32_t item, int64_t n_symbols)
-{
-    const int64_t low = (int64_t)(item & 0x3ffffffu), last = n_symbols - 1;
-    return low + ((last - low) >> 26) * ((int64_t)1 << 26);
-}
-// buf = buf[find + 288:]: the next frame's sync word ends a whole frame behind the last accepted one, or later
-RCF_DEVFN bool edacs_accept(int64_t k, int64_t k_last) { return k >= k_last + kEdacsFrameBits; }
+// the frame walk's constants (slice_core.hpp at slice_walk_trips).  kAccept is buf = buf[find + 288:]: the next frame's sync word
+// ends a whole frame behind the last accepted one, or later -- so every frame has its 288 bits and no hit cuts one short
+struct EdacsWalk {
+    static constexpr int kSync = kEdacsSyncBits, kAccept = kEdacsFrameBits, kDecide = kEdacsFrameBits, kLongest = kEdacsFrameBits, kPerWord = 32;
+    static constexpr bool kCut = false;
+};
+// the stage's own names for the widening and the accept rule, for sources that walk the hits themselves
+RCF_DEVFN int64_t edacs_widen_k(uint32_t item, int64_t n_symbols) { return slice_widen_k(item, n_symbols); }
+RCF_DEVFN bool edacs_accept(int64_t k, int64_t k_last) { return k >= k_last + EdacsWalk::kAccept; }
 // a hit of a slicer that searches both polarities matched the inverted word when its distance is past the half
 RCF_DEVFN bool edacs_inverted(uint32_t dist, bool sync_both) { return sync_both && dist > (uint32_t)(kEdacsSyncBits / 2); }
 RCF_DEVFN uint32_t edacs_hit_dist(uint32_t dist, bool inverted) { return inverted ? (uint32_t)kEdacsSyncBits - dist : dist; }

@@ -31,18 +31,18 @@ constexpr int kOswWaves = kItemWaves;
 
 __global__ __launch_bounds__(64 * kOswWaves) void osw_kernel(const OswLaunch *__restrict__ items, int n_items)
 {
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(blockIdx.x * kOswWaves + (threadIdx.x >> 6));
-    if (w >= n_items) return;                        // (no workgroup barrier below: a wave leaves on its own)
+    int lane;
+    const int w = item_of_wave(n_items, &lane);
+    if (w < 0) return;
     const OswLaunch L = items[w];
     OswState *st = L.st;
     const int64_t n_sym = L.src->n_symbols, n_words = L.src->n_words, n_hits = L.src->n_hits, W = 32 * n_words;
     int64_t n_records = st->n_records, n_frames = st->n_frames, n_bad = st->n_bad, n_rejects = st->n_rejects, n_lost = st->n_lost;
     int64_t i = st->next_hit, pos = st->pos;
     int32_t locked = st->locked, is_locked = st->is_locked;
-    const int64_t hit_cap = (int64_t)L.hit_mask + 1, word_cap = (int64_t)L.word_mask + 1;
-    bool resync = false;                             // after a loss: pos moves to the first retained hit at or behind it
-    if (i < n_hits - hit_cap) { n_lost += n_hits - hit_cap - i; i = n_hits - hit_cap; resync = true; }   // hits that left the ring unexamined
+    const int64_t word_cap = (int64_t)L.word_mask + 1, lost = hits_lost(i, n_hits, L.hit_mask);
+    n_lost += lost;
+    bool resync = lost != 0;                         // after a loss: pos moves to the first retained hit at or behind it
     const int trips = osw_trips(L.n_k);
     for (int t = 0; t < trips; ++t) {
         const bool valid = i + lane < n_hits;

@@ -30,12 +30,10 @@ RCF_DEVFN int osw_trips(int n_k)
     return b / kOswSyncBits + 1 + b / 56 + 1 + 2;
 }
 
-// where a hit item's sync word starts: k - 7, k the largest value <= n_symbols - 1 with the item's low 26 bits (rcf.h at
-// rcf_chan_slicer)
+// where a hit item's sync word starts: k - 7
 RCF_DEVFN int64_t osw_hit_start(uint32_t item, int64_t n_symbols)
 {
-    const int64_t low = (int64_t)(item & 0x3ffffffu), last = n_symbols - 1;
-    return low + ((last - low) >> 26) * ((int64_t)1 << 26) - (kOswSyncBits - 1);
+    return slice_widen_k(item, n_symbols) - (kOswSyncBits - 1);
 }
 
 // ---- one step of the framing (receive_engine 252-281, 521-525).  What is known: have0 / h0, the first hit with h >= pos;

@@ -6,10 +6,10 @@
 // restates it; the arithmetic is p25lc_core.hpp, which the CPU suite compiles for the host as it stands.
 //
 // The slicer's layout: a WAVE is a channel, four channels per workgroup.  The walk over the hit ring, the accept rule and
-// the frame's length are tsbk.hip's (tsbk_core.hpp's helpers), with 864 + 24 dibits to wait for.  Per decided frame the
-// lanes 0 .. 31 gather the NID.  Then lane w is inner word w (36, 24 or 12 lanes): it gathers its 9, 5 or 12 dibits through
-// the status-symbol map, takes the syndrome with masks and popcount parity (Hamming) or twelve shift / xor rounds and the
-// syndrome table (Golay; see p25lc_core.hpp for why a table) and corrects.  The Reed-Solomon word has a symbol per lane:
+// the frame's length are item_wave.hpp's frame_walk with P25lcWalk: tsbk.hip's, with 864 + 24 dibits to wait for.  Per decided
+// frame the lanes 0 .. 31 gather the NID (nid_wave.hpp).  Then lane w is inner word w (36, 24 or 12 lanes): it gathers its
+// 9, 5 or 12 dibits through the status-symbol map, takes the syndrome with masks and popcount parity (Hamming) or twelve
+// shift / xor rounds and the syndrome table (Golay; see p25lc_core.hpp for why a table) and corrects.  The Reed-Solomon word has a symbol per lane:
 //   syndromes       lane m runs Horner over the symbols, read uniformly, for S[m] = r(alpha^(m + 1))
 //   Berlekamp-      a fixed 2 t rounds, coefficient i of the locator and of the shadow polynomial in lane i; a round is
 //   Massey          one lane-reversed read of S, a product, an xor-reduction over the wave (the discrepancy, then in every
@@ -22,9 +22,8 @@
 // a fourth unit on the LDU1's lanes with RS(24,16,9); with erasures the ballot of the BAD lanes is the erased set and rs_decode
 // runs as rs_decode<true>, chosen by a wave-uniform branch on the flag, so a stage without the option walks the loops of t.  The lanes 0 .. 3 cut the payload words out
 // of the data symbols, the lanes 0 .. 7 store a record's eight words.
-// All trip counts come from the host's n_k or are compile-time constants; the counters read from the device only clamp.
-// Every ring index is masked.  Plain vector stores only; nothing is shared between waves; no LDS.  Every cross-lane read
-// stands in wave-uniform control flow.
+// The decoders' trip counts are compile-time constants.  Every ring index is masked.  Plain vector stores only; nothing is
+// shared between waves; no LDS.  Every cross-lane read stands in wave-uniform control flow.
 // The option RCF_NID_BCH (kNidFlagBch): the NID's 63 bits go through nid_wave.hpp's decoder before the DUID names the unit's
 // kind, behind a wave-uniform branch like the other options.
 #include "item_wave.hpp"
@@ -37,16 +36,6 @@ namespace {
 
 constexpr int kP25lcWaves = kItemWaves;
 
-__device__ __forceinline__ int ring_dibit(const P25lcLaunch &L, int64_t p)
-{
-    return tsbk_word_dibit(L.word_ring[(uint64_t)(p >> 4) & L.word_mask], (int)(p & 15));
-}
-__device__ __forceinline__ uint32_t lane_read(uint32_t v, int src) { return (uint32_t)__shfl((int)v, src & 63); }
-__device__ __forceinline__ uint32_t wave_xor(uint32_t v)
-{
-    for (int m = 32; m; m >>= 1) v ^= (uint32_t)__shfl_xor((int)v, m);
-    return v;
-}
 // lane m < 2 t: S[m] = the word's value at alpha^(m + 1); the other lanes 0
 __device__ __forceinline__ uint32_t rs_syndrome(uint32_t sym, int n, int t, int lane)
 {
@@ -115,60 +104,27 @@ __device__ __forceinline__ uint32_t rs_decode(uint32_t sym, uint64_t E, int n, i
 
 __global__ __launch_bounds__(64 * kP25lcWaves) void p25lc_kernel(const P25lcLaunch *__restrict__ items, int n_items)
 {
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(blockIdx.x * kP25lcWaves + (threadIdx.x >> 6));
-    if (w >= n_items) return;                        // (no workgroup barrier below: a wave leaves on its own)
+    int lane;
+    const int w = item_of_wave(n_items, &lane);
+    if (w < 0) return;
     const P25lcLaunch L = items[w];
     P25lcState *st = L.st;
     const bool correct = L.flags & kP25lcFlagCorrect, erasures = L.flags & kP25lcFlagErasures, nid = L.flags & kNidFlagBch;
     NidCount nc;
-    const int64_t n_sym = L.src->n_symbols, n_words = L.src->n_words, n_hits = L.src->n_hits;
-    int64_t n_records = st->n_records, n_frames = st->n_frames, n_decoded = st->n_decoded, n_rs_bad = st->n_rs_bad, n_lost = st->n_lost;
-    int64_t i = st->next_hit, k_last = st->k_last;
-    const int64_t hit_cap = (int64_t)L.hit_mask + 1, word_cap = (int64_t)L.word_mask + 1;
-    if (i < n_hits - hit_cap) { n_lost += n_hits - hit_cap - i; i = n_hits - hit_cap; }      // hits that left the ring unexamined
-    // the host's bounds, whatever the counters say (tsbk.hip): this block's hits and those of an undecided frame's 888 dibits
-    // and the unfinished word; a decided frame costs at most two trips, 64 rejected hits one
-    const int bound = L.n_k + kP25lcDecideDibits + 32;
-    const int trips = 2 * (bound / kTsbkSyncDibits + 1) + bound / 64 + 2;
-    for (int t = 0; t < trips && i < n_hits; ++t) {
-        const bool valid = i + lane < n_hits;
-        const uint32_t item = valid ? L.hit_ring[(uint64_t)(i + lane) & L.hit_mask] : 0u;
-        const int64_t k = tsbk_widen_k(item, n_sym);
-        const uint64_t acc = __ballot(valid && tsbk_accept(k, k_last));
-        if (!acc) { i += n_hits - i < 64 ? n_hits - i : 64; continue; }                      // all rejected
-        const int a = __builtin_ctzll(acc);
-        if (a > 32) { i += a; continue; }            // take the chunk again from the accepted hit on: the next frame's hit is among the 24 behind it
-        const int64_t k0 = rl_i64(k, a), s = k0 - (kTsbkSyncDibits - 1);
-        const uint32_t dist = (uint32_t)__builtin_amdgcn_readlane((int)item, a) >> 26;
-        i += a;
-        if (16 * n_words < s + kP25lcDecideDibits) break;                                     // not all there yet: the next launch
-        const uint64_t nxt = __ballot(valid && lane > a && tsbk_accept(k, k0));
-        int fd = kP25lcFrameDibits;
-        if (nxt) {
-            const int64_t gap = rl_i64(k, __builtin_ctzll(nxt)) - k0;
-            if (gap < fd) fd = (int)gap;
-        }
-        ++i; k_last = k0; ++n_frames;
-        if ((s >> 4) < n_words - word_cap) { ++n_lost; continue; }                            // its first word is overwritten
+    int64_t n_records = st->n_records, n_decoded = st->n_decoded, n_rs_bad = st->n_rs_bad;
+    FrameWalk walk(st);
+    frame_walk<P25lcWalk>(L, lane, walk, [&](int64_t s, int fd, int64_t k0, uint32_t dist) __attribute__((always_inline)) {
         const auto dibit = [&L, s](int r) { return ring_dibit(L, s + r); };
-        // ---- the NID: info dibits 24 .. 55
-        const int dn = lane < 32 ? dibit(tsbk_frame_pos(24 + lane)) : 0;
-        const uint64_t nhi = __ballot(dn & 2), nlo = __ballot(dn & 1);
-        uint32_t nid0 = slice_word_be(nhi, nlo, 2, 0), w0 = 0, w7 = 0;     // (what the option adds to the words 0 and 7)
-        if (nid) {                                   // (uniform)
-            int fix;
-            nid0 = nid_word0_of(nid_decode_wave(nid_poly(nid0, slice_word_be(nhi, nlo, 2, 1)), lane, &fix));
-            w0 = kNidP25lcWord0; w7 = nid_p25lc_word7(fix);
-            nc.add(fix);
-        }
+        const Nid id = read_nid(L, s, lane, nid, nc);
+        const uint32_t nid0 = id.word0;              // (decoded with the option)
+        const uint32_t w0 = nid ? kNidP25lcWord0 : 0u, w7 = nid ? nid_p25lc_word7(id.fix) : 0u;      // what the option adds to the words 0 and 7
         const int kind = __builtin_amdgcn_readfirstlane(p25lc_kind(tsbk_duid(nid0), fd, L.flags));
         uint32_t *rec = L.rec_ring + ((uint64_t)n_records & L.rec_mask) * kP25lcRecWords;
         ++n_records;
         if (kind == kP25lcFrame) {
             const uint32_t v = lane == 0 ? p25lc_word0(kind, false, 0, dist, nid0) | w0 : lane == 1 ? (uint32_t)(uint64_t)k0 : lane == 7 ? p25lc_word7(fd, 0, 0) | w7 : 0u;
             if (lane < kP25lcRecWords) rec[lane] = v;
-            continue;
+            return;
         }
         // ---- inner word `lane`
         const int wk = p25lc_words_kind(kind);       // (an LDU2's words are an LDU1's)
@@ -203,11 +159,11 @@ __global__ __launch_bounds__(64 * kP25lcWaves) void p25lc_kernel(const P25lcLaun
         if (lane < kP25lcRecWords) rec[lane] = v;
         ++n_decoded;
         n_rs_bad += rs_bad ? 1 : 0;
-    }
+    });
     if (lane == 0) {
-        st->n_records = n_records; st->n_frames = n_frames; st->n_decoded = n_decoded; st->n_rs_bad = n_rs_bad; st->n_lost = n_lost;
-        st->next_hit = i; st->k_last = k_last;
-        if (nid) { st->nid_decoded += nc.decoded; st->nid_fixed += nc.fixed; st->nid_bits += nc.bits; st->nid_bad += nc.bad; }
+        st->n_records = n_records; st->n_decoded = n_decoded; st->n_rs_bad = n_rs_bad;
+        walk.store(st);
+        if (nid) nc.store(st);
     }
 }
 

@@ -19,6 +19,10 @@ namespace {
 constexpr int kP25lcFrameDibits = 864;   // the longest voice data unit: an LDU
 // a frame is decided once the stream's whole words hold the 864 dibits and the 24 of a sync word that may begin inside them
 constexpr int kP25lcDecideDibits = kP25lcFrameDibits + kTsbkSyncDibits;
+// the frame walk's constants: the trunking stage's with the longer frame
+struct P25lcWalk : TsbkWalk {
+    static constexpr int kDecide = kP25lcDecideDibits, kLongest = kP25lcFrameDibits;
+};
 constexpr int kP25lcRecWords = 8;        // uint32 words of a record
 constexpr int kP25lcHdu = 0, kP25lcLdu1 = 1, kP25lcTlc = 2, kP25lcFrame = 3;   // a record's kind
 constexpr int kP25lcMaxSyms = 36, kP25lcMaxT = 8;                               // RS(36,20,17): the longest word, the most errors

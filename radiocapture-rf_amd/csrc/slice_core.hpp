@@ -105,6 +105,29 @@ RCF_DEVFN bool slice_sync_both_ok(int sync_bits, int max_errors, int sync_both)
 }
 // a hit's item in the hit ring
 RCF_DEVFN uint32_t slice_hit_item(int dist, int64_t k) { return ((uint32_t)dist << 26) | (uint32_t)((uint64_t)k & 0x3ffffffu); }
+// ... and its k again: the largest value <= n_symbols - 1 with the item's low 26 bits (rcf.h at rcf_chan_slicer)
+RCF_DEVFN int64_t slice_widen_k(uint32_t item, int64_t n_symbols)
+{
+    const int64_t low = (int64_t)(item & 0x3ffffffu), last = n_symbols - 1;
+    return low + ((last - low) >> 26) * ((int64_t)1 << 26);
+}
+
+// ---- The frame walk of the decoders behind a slicer (TSBK, P25 voice, EDACS): item_wave.hpp's frame_walk on the device,
+// tests/native/wave_host.hpp's walk on the host.  A stage names its constants in a struct W:
+//   kSync      symbols of the sync word: a hit's k is its last symbol, the frame starts at s = k - (kSync - 1)
+//   kAccept    a hit is accepted when its k is at least this far behind the last accepted one's
+//   kDecide    a frame is decided once the symbols s .. s + kDecide - 1 are in whole words
+//   kLongest   symbols of the longest frame
+//   kPerWord   symbols per word of the slicer's ring: 16 (dibits) or 32 (bits)
+//   kCut       the next accepted hit cuts the frame short (the walk looks ahead for it in the same 64 hits)
+// The trips of one launch from the host's n_k (the block's new symbols at most), whatever the device's counters say: the hits
+// to look at are this block's (at most one per new symbol) and those of an undecided frame's kDecide symbols and the unfinished
+// word; a decided frame costs one trip, with kCut at most two, and 64 rejected hits one
+template <class W> RCF_DEVFN int slice_walk_trips(int n_k)
+{
+    const int bound = n_k + W::kDecide + 32;
+    return (W::kCut ? 2 : 1) * (bound / W::kAccept + 1) + bound / 64 + 2;
+}
 
 // What a chunk does to the packed stream, for the lanes [a, b) of it that are new (0 <= a < b <= 64; the masks carry those
 // lanes only).  `partial` is the unfinished word so far, in stream order with its missing bits 0 -- it belongs to the word

@@ -1,5 +1,5 @@
 // tsbk_core.hpp -- the arithmetic of the P25 trunking stage (tsbk.hip; definition: include/rcf.h at rcf_chan_tsbk): the
-// widening of a hit's k, the accept rule, where an info dibit sits in a frame, the deinterleaver's index map, the rate-1/2
+// frame walk's constants, where an info dibit sits in a frame, the deinterleaver's index map, the rate-1/2
 // trellis as transition maps with their composition (what the wave scans), for the option RCF_TRELLIS_VITERBI the code
 // words as min-plus matrices with theirs, the CRC's per-bit terms and the packing of a record.  No HIP types in here, like
 // slice_core.hpp, whose mask-to-word helpers it uses: RCF_DEVFN is the function qualifier and RCF_DEVCONST the qualifier of
@@ -24,14 +24,15 @@ constexpr int kTsbkCodeWords = 49;       // code words of a block: 98 dibits
 constexpr int kTsbkRecWords = 8;         // uint32 words of a record
 constexpr int64_t kTsbkNoFrame = -((int64_t)1 << 60);   // k_last before the first accepted hit
 
-// a hit item's k: the largest value <= n_symbols - 1 with the item's low 26 bits (rcf.h at rcf_chan_slicer)
-RCF_DEVFN int64_t tsbk_widen_k(uint32_t item, int64_t n_symbols)
-{
-    const int64_t low = (int64_t)(item & 0x3ffffffu), last = n_symbols - 1;
-    return low + ((last - low) >> 26) * ((int64_t)1 << 26);
-}
-// buf.find(sync, fsoffset + 6): a sync word that begins inside the last accepted one is no frame
-RCF_DEVFN bool tsbk_accept(int64_t k, int64_t k_last) { return k >= k_last + kTsbkSyncDibits; }
+// the frame walk's constants (slice_core.hpp at slice_walk_trips).  kAccept is buf.find(sync, fsoffset + 6): a sync word that
+// begins inside the last accepted one is no frame
+struct TsbkWalk {
+    static constexpr int kSync = kTsbkSyncDibits, kAccept = kTsbkSyncDibits, kDecide = kTsbkDecideDibits, kLongest = kTsbkFrameDibits, kPerWord = 16;
+    static constexpr bool kCut = true;
+};
+// the stage's own names for the widening and the accept rule, for sources that walk the hits themselves
+RCF_DEVFN int64_t tsbk_widen_k(uint32_t item, int64_t n_symbols) { return slice_widen_k(item, n_symbols); }
+RCF_DEVFN bool tsbk_accept(int64_t k, int64_t k_last) { return k >= k_last + TsbkWalk::kAccept; }
 // frame dibit of info dibit j: every 36th dibit is a status symbol (procStatus)
 RCF_DEVFN int tsbk_frame_pos(int j) { return j + j / 35; }
 // block b's info dibits are 56 + 98 b .. 153 + 98 b; the blocks whose last dibit lies inside a frame of fd dibits

@@ -5,6 +5,7 @@ slicer's hit rule with sync_both."""
 import numpy as np
 
 import slicer_ref as S
+from frames_ref import frame_walk
 from rcf import native
 
 SYNC, SYNC_BITS, FRAME_BITS = 0b010101010101010101010111000100100101010101010101, 48, 288
@@ -119,35 +120,19 @@ def run(words, k, dist, first_hit=0, launches=None, word_cap=None, hit_cap=None,
     k = [None] * base_hits + [int(v) for v in k]
     dist = [None] * base_hits + list(dist)
     launches = [(base_words + len(bits) // 32, len(k))] if launches is None else launches
-    i, k_last = first_hit, None
     out = []
     st = dict(n_records=0, n_frames=0, n_msgs=0, n_msgs_none=0, n_lost=0)
-    for n_words, n_hits in launches:
-        if hit_cap and i < n_hits - hit_cap:
-            st["n_lost"] += n_hits - hit_cap - i
-            i = n_hits - hit_cap
-        while i < n_hits:
-            if k_last is not None and k[i] < k_last + FRAME_BITS:
-                i += 1
-                continue
-            s = k[i] - 47
-            if 32 * n_words < s + FRAME_BITS:
-                break
-            k_last = k[i]
-            st["n_frames"] += 1
-            i += 1
-            if word_cap and s // 32 < n_words - word_cap:
-                st["n_lost"] += 1
-                continue
-            raw = int(dist[i - 1])
-            inverted = bool(sync_both) and raw > 24
-            data = bits[s + 48 - 32 * base_words:s + 288 - 32 * base_words] ^ (1 if inverted else 0)
-            if frames is not None:
-                frames.append(data)
-            statuses, m1, m2 = decode_frame(data, esk)
-            out.append(record(k_last, inverted, 48 - raw if inverted else raw, statuses, m1, m2))
-            st["n_msgs"] += (m1 is not None) + (m2 is not None)
-            st["n_msgs_none"] += (m1 is None) + (m2 is None)
+    for i, s, _ in frame_walk(k, launches, st, first_hit, word_cap, hit_cap, sync=48, accept=FRAME_BITS, decide=FRAME_BITS, longest=FRAME_BITS,
+                              per_word=32, cut=False):
+        raw = int(dist[i])
+        inverted = bool(sync_both) and raw > 24
+        data = bits[s + 48 - 32 * base_words:s + 288 - 32 * base_words] ^ (1 if inverted else 0)
+        if frames is not None:
+            frames.append(data)
+        statuses, m1, m2 = decode_frame(data, esk)
+        out.append(record(k[i], inverted, 48 - raw if inverted else raw, statuses, m1, m2))
+        st["n_msgs"] += (m1 is not None) + (m2 is not None)
+        st["n_msgs_none"] += (m1 is None) + (m2 is None)
     recs = np.array(out, native.EDACS_DTYPE) if out else np.zeros(0, native.EDACS_DTYPE)
     st["n_records"] = len(recs)
     return recs, st

@@ -9,50 +9,33 @@
 //   osw_core_check masks <n_random>       psyn patterns -- all single bits, all pairs, n_random random ones -- with their flip mask
 //   osw_core_check start <item hex> <n_symbols>
 // tests/test_osw_cpu.py holds the output to the numpy restatement's (tests/osw_ref.py).
-#include <cinttypes>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
 #define RCF_DEVFN static inline
 #include "../../radiocapture-rf_amd/csrc/osw_core.hpp"
-
-using namespace rcfx;
+#include "wave_host.hpp"
 
 namespace {
 
-struct State {
+struct OswState {
     int64_t n_records = 0, n_frames = 0, n_bad = 0, n_rejects = 0, n_lost = 0;
     int32_t locked = 0, is_locked = 0;
     int64_t next_hit = 0, pos = 0;
 };
-struct Rings {
-    std::vector<uint32_t> words, hits;          // the streams from base_words / base_hits on
-    uint32_t word_mask, hit_mask;
-    int64_t base_words, base_hits;
+struct OswRings : Rings {                       // ... with a launch's bounds: a read of an item the ring does not hold aborts
     int64_t n_words = 0, n_hits = 0;            // of the launch under way
     uint32_t word(int64_t i) const
     {
         if (i >= n_words || i < n_words - ((int64_t)word_mask + 1)) { fprintf(stderr, "word %" PRId64 " is not in the ring\n", i); abort(); }
-        return words.at((size_t)(i - base_words));
+        return Rings::word(i);
     }
     uint32_t hit(int64_t i) const
     {
         if (i >= n_hits || i < n_hits - ((int64_t)hit_mask + 1)) { fprintf(stderr, "hit %" PRId64 " is not in the ring\n", i); abort(); }
-        return hits.at((size_t)(i - base_hits));
+        return Rings::hit(i);
     }
 };
 
-uint64_t ballot(const bool (&b)[64])
-{
-    uint64_t m = 0;
-    for (int l = 0; l < 64; ++l) m |= (uint64_t)b[l] << l;
-    return m;
-}
-
 // one launch (osw_kernel, one wave)
-void launch(Rings &R, State &st, int64_t n_words, int64_t n_hits, int64_t n_sym, int n_k, std::vector<uint32_t> &out)
+void launch(OswRings &R, OswState &st, int64_t n_words, int64_t n_hits, int64_t n_sym, int n_k, std::vector<uint32_t> &out)
 {
     R.n_words = n_words; R.n_hits = n_hits;
     const int64_t W = 32 * n_words;
@@ -121,34 +104,18 @@ void launch(Rings &R, State &st, int64_t n_words, int64_t n_hits, int64_t n_sym,
     st.locked = locked; st.is_locked = is_locked; st.next_hit = i; st.pos = pos;
 }
 
-std::vector<uint32_t> read_u32(const char *path)
-{
-    std::vector<uint32_t> v;
-    FILE *f = fopen(path, "rb");
-    if (!f) { perror(path); exit(2); }
-    uint32_t buf[4096];
-    for (size_t n; (n = fread(buf, sizeof(uint32_t), 4096, f)) > 0;) v.insert(v.end(), buf, buf + n);
-    fclose(f);
-    return v;
-}
-
 int mode_stream(int argc, char **argv)
 {
     if (argc < 10 || (argc - 10) % 4) return 2;
-    Rings R{read_u32(argv[2]), read_u32(argv[3]), (uint32_t)atoll(argv[6]) - 1u, (uint32_t)atoll(argv[7]) - 1u, atoll(argv[8]), atoll(argv[9])};
-    State st;
+    OswRings R{{read_file<uint32_t>(argv[2]), read_file<uint32_t>(argv[3]), (uint32_t)atoll(argv[6]) - 1u, (uint32_t)atoll(argv[7]) - 1u, atoll(argv[8]), atoll(argv[9])}};
+    OswState st;
     st.next_hit = atoll(argv[4]);
     st.pos = atoll(argv[5]);
     std::vector<uint32_t> out;
-    for (int i = 10; i + 3 < argc; i += 4) {
-        const int64_t n_words = atoll(argv[i]), n_hits = atoll(argv[i + 1]), n_sym = atoll(argv[i + 2]);
-        if (n_words - R.base_words > (int64_t)R.words.size() || n_hits - R.base_hits > (int64_t)R.hits.size()) return 2;
-        launch(R, st, n_words, n_hits, n_sym, atoi(argv[i + 3]), out);
-    }
+    if (!for_launches(R, argc, argv, 10, [&](int64_t n_words, int64_t n_hits, int64_t n_sym, int n_k) { launch(R, st, n_words, n_hits, n_sym, n_k, out); })) return 2;
     printf("records %" PRId64 " frames %" PRId64 " bad %" PRId64 " rejects %" PRId64 " lost %" PRId64 " locked %d is_locked %d\n", st.n_records,
            st.n_frames, st.n_bad, st.n_rejects, st.n_lost, st.locked, st.is_locked);
-    for (size_t r = 0; r + 8 <= out.size(); r += 8)
-        for (int q = 0; q < 8; ++q) printf("%08x%s", out[r + q], q == 7 ? "\n" : " ");
+    print_records(out);
     return 0;
 }
 

@@ -1,9 +1,8 @@
 // trellis_core_check.cpp -- the trellis option of the P25 trunking stage (RCF_TRELLIS_VITERBI; radiocapture-rf_amd/csrc/
-// tsbk_core.hpp) compiled for the host: the wave form of tsbk.hip walked stand-alone -- the 64 lanes of a wave as a loop, a
-// shuffle as an index into the lanes' array, a ballot as the mask that loop builds -- with the min-plus matrices, their
-// composition, the forward map, the branch distance and the record bits coming from the header's own functions, held to a
-// sequential form written out here (backward costs, forward walk).  The frame walk and the NID are nid_core_check.cpp's,
-// included in a namespace of its own.
+// tsbk_core.hpp) compiled for the host: the wave form of tsbk.hip walked stand-alone (tsbk_decode_host.hpp) -- with the
+// min-plus matrices, their composition, the forward map, the branch distance and the record bits coming from the header's
+// own functions -- held to a sequential form written out here (backward costs, forward walk).  The frame walk is
+// wave_host.hpp's.
 //   trellis_core_check assoc <seed> <n>          n random triples of matrices: (A x B) x C == A x (B x C)
 //   trellis_core_check blocks <n_words> <c.u8>   rows of n_words + 1 code words (a byte each; n_words 48 is a TSBK block,
 //                                               the last word the flushing one): per row the wave form's states as digits,
@@ -15,69 +14,12 @@
 //       every record as 8 hex words
 // tests/test_trellis_cpu.py holds the output to the restatement's (tests/trellis_ref.py).
 #include <algorithm>
-#include <cinttypes>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
 #define RCF_DEVFN static inline
 #define RCF_DEVCONST static const
-#include "../../radiocapture-rf_amd/csrc/nid_core.hpp"
-#include "../../radiocapture-rf_amd/csrc/tsbk_core.hpp"
-
-namespace nidc {                 // (its main becomes nidc::main, a function like any other)
-#include "nid_core_check.cpp"
-}
-
-using namespace rcfx;
+#include "tsbk_decode_host.hpp"
 
 namespace {
-
-typedef nidc::Rings Rings;
-
-// viterbi_map_wave of tsbk.hip over the 64 lanes; last: the lane of the flushing word (48 for a TSBK block)
-void viterbi_maps(const uint32_t (&c)[64], int last, uint32_t (&map)[64], uint32_t *beta0)
-{
-    TsbkMat own[64], suffix[64];
-    for (int l = 0; l < 64; ++l) suffix[l] = own[l] = l <= last ? tsbk_mat(c[l], l == last) : tsbk_mat_identity();
-    for (int d = 1; d < 64; d <<= 1) {
-        TsbkMat after[64];
-        for (int l = 0; l < 64; ++l) after[l] = suffix[l + d < 64 ? l + d : l];
-        for (int l = 0; l < 64; ++l)
-            if (l + d < 64) suffix[l] = tsbk_mat_compose(suffix[l], after[l]);
-    }
-    for (int l = 0; l < 64; ++l) {
-        const uint32_t beta_next = tsbk_mat_beta(suffix[l + 1 < 64 ? l + 1 : l]);
-        map[l] = l > last ? kTsbkIdentity : tsbk_viterbi_map(own[l], l == last ? 0u : beta_next);
-    }
-    *beta0 = tsbk_mat_beta(suffix[0]) & 255u;        // the least cost from state 0
-}
-
-struct Decoded { int state[64]; int cost, n_inexact; };
-
-// the block's lanes as tsbk_kernel goes through them: maps, the inclusive scan, the states, distance ballot and cost
-Decoded wave_form(const uint32_t (&c)[64], int last, bool viterbi)
-{
-    uint32_t map[64], beta0 = 0;
-    for (int l = 0; l < 64; ++l) map[l] = l <= last ? tsbk_map(c[l]) : kTsbkIdentity;
-    if (viterbi) viterbi_maps(c, last, map, &beta0);
-    nidc::tsbkc::scan64(map);
-    Decoded r{};
-    bool off[64];
-    for (int l = 0; l < 64; ++l) {
-        const int state = (int)(map[l] & 3u), prev = l ? (int)(map[l - 1] & 3u) : 0;
-        r.state[l] = state;
-        bool exact;
-        (void)tsbk_next_state(prev, c[l], &exact);
-        const int away = l <= last ? tsbk_branch_dist(prev, state, c[l]) : 0;
-        off[l] = viterbi ? away != 0 : l <= last && !exact;
-        r.cost += away;
-    }
-    r.n_inexact = slice_popcount64(nidc::ballot(off));
-    if (viterbi && (int)beta0 != r.cost) { fprintf(stderr, "beta_0[0] %u is not the path's cost %d\n", beta0, r.cost); exit(1); }
-    return r;
-}
 
 // the rule's sequential form, with nothing of the header but the table
 Decoded sequential_form(const uint32_t (&c)[64], int last)
@@ -142,7 +84,7 @@ int mode_blocks(int argc, char **argv)
     if (argc < 4) return 2;
     const int last = atoi(argv[2]);
     if (last < 1 || last > 62) return 2;
-    const std::vector<uint8_t> all = nidc::voicec::read_file<uint8_t>(argv[3]);
+    const std::vector<uint8_t> all = read_file<uint8_t>(argv[3]);
     for (size_t at = 0; at + (size_t)last + 1 <= all.size(); at += (size_t)last + 1) {
         uint32_t c[64] = {0};
         for (int l = 0; l <= last; ++l) c[l] = all[at + (size_t)l] & 15u;
@@ -182,73 +124,24 @@ int mode_random(int argc, char **argv)
     return 0;
 }
 
-struct TrellisCount { int64_t decoded = 0, clean = 0, bits = 0, words = 0; };
-
-// tsbk_kernel's block loop with the option in it
-void tsbk_frame(const Rings &R, nidc::State &st, bool nid, bool viterbi, nidc::NidCount &nc, TrellisCount &tc, int64_t s, int fd, int64_t k0, uint32_t dist,
-                std::vector<uint32_t> &out)
-{
-    uint32_t nid0, nid1, nidc_;
-    int fix;
-    nidc::read_nid(R, s, nid, nc, &nid0, &nid1, &nidc_, &fix);
-    const uint32_t w7 = (uint32_t)fd | (nid ? nid_tsbk_word7(fix) : 0u);
-    const int nb = tsbk_duid(nidc_) == 7 ? tsbk_blocks_in(fd) : 0;
-    if (nb == 0) {
-        const uint32_t rec[8] = {tsbk_word0(3, false, 0, 0, dist, nidc_), (uint32_t)(uint64_t)k0, 0, 0, 0, slice_word_mem(nid0), slice_word_mem(nid1), w7};
-        out.insert(out.end(), rec, rec + 8);
-        ++st.n_records;
-        return;
-    }
-    for (int b = 0; b < nb; ++b) {
-        uint32_t c[64] = {0};
-        for (int l = 0; l < kTsbkCodeWords; ++l) {
-            const int j = tsbk_block_dibit(b, tsbk_deinterleave(l));
-            c[l] = (uint32_t)(nidc::voicec::ring_dibit(R, s + tsbk_frame_pos(j)) << 2 | nidc::voicec::ring_dibit(R, s + tsbk_frame_pos(j + 1)));
-        }
-        const Decoded w = wave_form(c, kTsbkCodeWords - 1, viterbi);
-        bool hi_b[64], lo_b[64];
-        uint32_t crc = 0;
-        for (int l = 0; l < 64; ++l) {
-            hi_b[l] = l < 48 && (w.state[l] & 2);
-            lo_b[l] = l < 48 && (w.state[l] & 1);
-            if (l < 48) crc ^= tsbk_crc_term(l, w.state[l]);
-        }
-        const uint64_t hi = nidc::ballot(hi_b), lo = nidc::ballot(lo_b);
-        const bool bad = crc != 0xffffu;
-        const int jn = tsbk_frame_pos(tsbk_block_dibit(b, 98));
-        const int next_bit = jn < fd ? nidc::voicec::ring_dibit(R, s + jn) >> 1 : 0;
-        uint32_t rec[8] = {tsbk_word0(b, bad, next_bit, w.n_inexact, dist, nidc_), (uint32_t)(uint64_t)k0, 0, 0, 0, slice_word_mem(nid0), slice_word_mem(nid1), w7};
-        for (int q = 0; q < 3; ++q) rec[2 + q] = slice_word_mem(slice_word_be(hi, lo, 2, q));
-        if (viterbi) {
-            rec[7] |= tsbk_viterbi_word7(w.cost);
-            ++tc.decoded; tc.clean += w.cost == 0 ? 1 : 0; tc.bits += w.cost; tc.words += w.n_inexact;
-        }
-        out.insert(out.end(), rec, rec + 8);
-        ++st.n_records; ++st.n_a;
-        st.n_b += bad ? 1 : 0;
-    }
-}
-
 int mode_stream(int argc, char **argv)
 {
     if (argc < 9 || (argc - 9) % 4) return 2;
-    Rings R{nidc::voicec::read_file<uint32_t>(argv[2]), nidc::voicec::read_file<uint32_t>(argv[3]), (uint32_t)atoll(argv[7]) - 1u, (uint32_t)atoll(argv[8]) - 1u};
+    Rings R{read_file<uint32_t>(argv[2]), read_file<uint32_t>(argv[3]), (uint32_t)atoll(argv[7]) - 1u, (uint32_t)atoll(argv[8]) - 1u};
     const bool nid = atoi(argv[4]) != 0, viterbi = atoi(argv[5]) != 0;
-    nidc::State st;
-    nidc::NidCount nc;
+    State st;
+    NidCount nc;
     TrellisCount tc;
     st.next_hit = atoll(argv[6]);
     std::vector<uint32_t> out;
-    for (int i = 9; i + 3 < argc; i += 4) {
-        const int64_t n_words = atoll(argv[i]), n_hits = atoll(argv[i + 1]), n_sym = atoll(argv[i + 2]);
-        if (n_words > (int64_t)R.words.size() || n_hits > (int64_t)R.hits.size()) return 2;
-        nidc::walk(R, st, kTsbkDecideDibits, kTsbkFrameDibits, n_words, n_hits, n_sym, atoi(argv[i + 3]),
-                   [&](int64_t s, int fd, int64_t k0, uint32_t dist) { tsbk_frame(R, st, nid, viterbi, nc, tc, s, fd, k0, dist, out); });
-    }
+    if (!for_launches(R, argc, argv, 9, [&](int64_t n_words, int64_t n_hits, int64_t n_sym, int n_k) {
+            walk<TsbkWalk>(R, st, n_words, n_hits, n_sym, n_k,
+                           [&](int64_t s, int fd, int64_t k0, uint32_t dist) { tsbk_frame(R, st, nid, viterbi, nc, tc, s, fd, k0, dist, out); });
+        }))
+        return 2;
     printf("%" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " nid %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " trellis %" PRId64 " %" PRId64
            " %" PRId64 " %" PRId64 "\n", st.n_records, st.n_frames, st.n_a, st.n_b, st.n_lost, nc.decoded, nc.fixed, nc.bits, nc.bad, tc.decoded, tc.clean, tc.bits, tc.words);
-    for (size_t r = 0; r + 8 <= out.size(); r += 8)
-        for (int q = 0; q < 8; ++q) printf("%08x%s", out[r + q], q == 7 ? "\n" : " ");
+    print_records(out);
     return st.n_records * 8 == (int64_t)out.size() ? 0 : 1;
 }
 

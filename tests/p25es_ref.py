@@ -7,6 +7,7 @@ other direction for the tests' signals: the LDU2's encoder, a call with a known 
 units sit on and beyond every bound, and the census of what that stream guarantees."""
 import numpy as np
 
+from frames_ref import frame_walk
 from rcf import native
 import p25lc_ref as R
 from p25lc_ref import EXP, HDU, LDU1, NONE, TLC, gdiv, gmul, poly_eval
@@ -149,32 +150,13 @@ def run(words, k, dist, correct=1, options=0, first_hit=0, launches=None, word_c
     d = R.dibits_of(words)
     k = [int(v) for v in k]
     launches = [(len(d) // 16, len(k))] if launches is None else launches
-    i, k_last = first_hit, None
     out = []
     st = dict(n_records=0, n_frames=0, n_decoded=0, n_rs_bad=0, n_lost=0)
-    for n_words, n_hits in launches:
-        if hit_cap and i < n_hits - hit_cap:
-            st["n_lost"] += n_hits - hit_cap - i
-            i = n_hits - hit_cap
-        while i < n_hits:
-            if k_last is not None and k[i] < k_last + 24:
-                i += 1
-                continue
-            s = k[i] - 23
-            if 16 * n_words < s + R.DECIDE:
-                break
-            later = [v for v in k[i + 1:n_hits] if v >= k[i] + 24]
-            fd = min(R.FRAME, later[0] - k[i]) if later else R.FRAME
-            k_last = k[i]
-            st["n_frames"] += 1
-            i += 1
-            if word_cap and s // 16 < n_words - word_cap:
-                st["n_lost"] += 1
-                continue
-            r = frame_record(d, s, fd, k_last, dist[i - 1], correct, options, units)
-            out.append(r)
-            st["n_decoded"] += int(native.p25lc_fields(r)["kind"][0]) != NONE
-            st["n_rs_bad"] += int(r["flags"][0] >> 2 & 1)
+    for i, s, fd in frame_walk(k, launches, st, first_hit, word_cap, hit_cap, **R.WALK):
+        r = frame_record(d, s, fd, k[i], dist[i], correct, options, units)
+        out.append(r)
+        st["n_decoded"] += int(native.p25lc_fields(r)["kind"][0]) != NONE
+        st["n_rs_bad"] += int(r["flags"][0] >> 2 & 1)
     recs = np.concatenate(out) if out else np.zeros(0, native.P25LC_DTYPE)
     st["n_records"] = len(recs)
     return recs, st

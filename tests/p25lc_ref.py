@@ -7,11 +7,13 @@ block by block, and models the two rings' losses.  Below that the other directio
 the frames, the designed streams and what they guarantee."""
 import numpy as np
 
+from frames_ref import frame_walk
 from rcf import native
 from tsbk_ref import SYNC_DIBITS, dibits_of, pos
 
 DECIDE = 888                                       # dibits from the frame's start that must be in whole words
 FRAME = 864
+WALK = dict(sync=24, accept=24, decide=DECIDE, longest=FRAME, per_word=16, cut=True)   # frames_ref.frame_walk's constants
 HDU, LDU1, TLC, NONE = 0, 1, 2, 3
 DUID_OF = {HDU: 0x0, LDU1: 0x5, TLC: 0xF}
 LAST_DIBIT = {HDU: 389, LDU1: 788, TLC: 204}
@@ -271,32 +273,13 @@ def run(words, k, dist, correct=1, first_hit=0, launches=None, word_cap=None, hi
     d = dibits_of(words)
     k = [int(v) for v in k]
     launches = [(len(d) // 16, len(k))] if launches is None else launches
-    i, k_last = first_hit, None
     out = []
     st = dict(n_records=0, n_frames=0, n_decoded=0, n_rs_bad=0, n_lost=0)
-    for n_words, n_hits in launches:
-        if hit_cap and i < n_hits - hit_cap:
-            st["n_lost"] += n_hits - hit_cap - i
-            i = n_hits - hit_cap
-        while i < n_hits:
-            if k_last is not None and k[i] < k_last + 24:
-                i += 1
-                continue
-            s = k[i] - 23
-            if 16 * n_words < s + DECIDE:
-                break
-            later = [v for v in k[i + 1:n_hits] if v >= k[i] + 24]
-            fd = min(FRAME, later[0] - k[i]) if later else FRAME
-            k_last = k[i]
-            st["n_frames"] += 1
-            i += 1
-            if word_cap and s // 16 < n_words - word_cap:
-                st["n_lost"] += 1
-                continue
-            r = frame_record(d, s, fd, k_last, dist[i - 1], correct, units)
-            out.append(r)
-            st["n_decoded"] += int(r["flags"][0] & 3) != NONE
-            st["n_rs_bad"] += int(r["flags"][0] >> 2 & 1)
+    for i, s, fd in frame_walk(k, launches, st, first_hit, word_cap, hit_cap, **WALK):
+        r = frame_record(d, s, fd, k[i], dist[i], correct, units)
+        out.append(r)
+        st["n_decoded"] += int(r["flags"][0] & 3) != NONE
+        st["n_rs_bad"] += int(r["flags"][0] >> 2 & 1)
     recs = np.concatenate(out) if out else np.zeros(0, native.P25LC_DTYPE)
     st["n_records"] = len(recs)
     return recs, st

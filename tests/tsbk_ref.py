@@ -5,11 +5,13 @@ native.TSBK_DTYPE and the stage's counters.  `launches` walks the streams as the
 models the two rings' losses."""
 import numpy as np
 
+from frames_ref import frame_walk
 from rcf import native
 
 W = ((0x2, 0xC, 0x1, 0xF), (0xE, 0x0, 0xD, 0x3), (0x9, 0x7, 0xA, 0x4), (0x5, 0xB, 0x6, 0x8))
 ORDER = [i + j + e for i in range(0, 23, 2) for j in (0, 26, 50, 74) for e in (0, 1)] + [24, 25]   # deinterleaved dibit n <- block dibit ORDER[n]
 DECIDE = 384                                       # dibits from the frame's start that must be in whole words
+WALK = dict(sync=24, accept=24, decide=DECIDE, longest=360, per_word=16, cut=True)     # frames_ref.frame_walk's constants
 
 
 def dibits_of(words):
@@ -138,33 +140,14 @@ def run(words, k, dist, first_hit=0, launches=None, word_cap=None, hit_cap=None,
     d = dibits_of(words)
     k = [int(v) for v in k]
     launches = [(len(d) // 16, len(k))] if launches is None else launches
-    i, k_last = first_hit, None
     out = []
     st = dict(n_records=0, n_frames=0, n_blocks=0, n_crc_bad=0, n_lost=0)
-    for n_words, n_hits in launches:
-        if hit_cap and i < n_hits - hit_cap:
-            st["n_lost"] += n_hits - hit_cap - i
-            i = n_hits - hit_cap
-        while i < n_hits:
-            if k_last is not None and k[i] < k_last + 24:
-                i += 1
-                continue
-            s = k[i] - 23
-            if 16 * n_words < s + DECIDE:
-                break
-            later = [v for v in k[i + 1:n_hits] if v >= k[i] + 24]
-            fd = min(360, later[0] - k[i]) if later else 360
-            k_last = k[i]
-            st["n_frames"] += 1
-            i += 1
-            if word_cap and s // 16 < n_words - word_cap:
-                st["n_lost"] += 1
-                continue
-            recs = frame_records(d, s, fd, k_last, dist[i - 1], blocks)
-            out.append(recs)
-            decoded = recs[(recs["flags"] & 3) != 3]
-            st["n_blocks"] += len(decoded)
-            st["n_crc_bad"] += int(np.count_nonzero(decoded["flags"] & 4))
+    for i, s, fd in frame_walk(k, launches, st, first_hit, word_cap, hit_cap, **WALK):
+        recs = frame_records(d, s, fd, k[i], dist[i], blocks)
+        out.append(recs)
+        decoded = recs[(recs["flags"] & 3) != 3]
+        st["n_blocks"] += len(decoded)
+        st["n_crc_bad"] += int(np.count_nonzero(decoded["flags"] & 4))
     recs = np.concatenate(out) if out else np.zeros(0, native.TSBK_DTYPE)
     st["n_records"] = len(recs)
     return recs, st
